@@ -1,10 +1,19 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: images/sec for ESPCN 2x super-resolution, 1080p -> 4K, fp32 (BASELINE configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5] [--through host|capi]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5] [--through host|capi] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `--gpus N` (N > 1) from a plain shell re-executes itself under torch.distributed.run with N ranks (one per GPU, RCCL).
+
+A plain run does only what the headline figure needs: it builds the workload, pre-heats, runs the W warmup steps, times ONE region of exactly
+K steps (`ms_per_step` = that region / K), writes the outputs when --dump-outputs is given, and prints the line.  `--full` adds everything
+else described below: the in-run oracle check (`parity`), the CPU baseline, the other configs (`configs`), the median of R timed regions, both
+wait semantics, the launch trace (`roofline`, `kernels`) and the per-layer table.
+
+`--dump-outputs DIR`: right after the timed steps, rank 0's output arrays of the last step (what MixedInferenceCore / the plan chain hands its
+caller) as DIR/<name>.npy in float32, at most 48 MiB in all; a larger output (c5) is written as a fixed, seeded sample of its elements.  Inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 Configs (BASELINE.json `configs`, SURVEY 8d shapes; default c2 = the configuration the metric is quoted on):
   c1  single 3x3 Conv2D, 1x224x224x3 -> 64, relu, fp32; one layer launch per step and rank                        (weak)
@@ -21,8 +30,8 @@ default (libsnn_core.so: the net written as the reference's .json + .bin model -
 HipBackend::finalizeStages, the inference replayed as one recorded hipGraph); `--through capi` drives per-layer plans from Python instead.
 `value` is quoted with the K inferences of the timed region IN FLIGHT on the rank's stream (RunParameters::deferSync, one wait at the end:
 the serving mode of a batch-split replica); the reference's own semantics -- MixedInferenceCore::run waits once per inference, core.cpp:203 --
-are timed right after it on the same model and reported as `sync_per_inference` (polling wait and blocking wait).
-Before anything is timed, rank 0 downloads the GPU result of its first image and compares it with the CPU oracle's result for the same
+are timed right after it on the same model and reported as `sync_per_inference` (polling wait and blocking wait; --full).
+With --full, before anything is timed, rank 0 downloads the GPU result of its first image and compares it with the CPU oracle's result for the same
 input: `parity` {max_abs_err, max_rel_err, ...} goes on the line and a mismatch makes the run exit non-zero.
 Multi-GPU = embarrassingly parallel batch split: no data-path collective; RCCL carries only the barrier / MAX-reduction of the elapsed time.
 Rank 0 prints ONE JSON line.
@@ -30,10 +39,10 @@ Rank 0 prints ONE JSON line.
 Before the driver's `--warmup` steps a fixed time-based pre-heat (>= --preheat-ms of the workload, default 150 ms, reported as
 `preheat_ms`) brings the clocks up, so a 20-step run does not time the ramp.
 
-Timing: the timed region (K steps between two barriers + synchronisations, MAX over ranks) is repeated R times (--repeats; default 7 when K steps
-take less than 50 ms, else 3) and `value` / `ms_per_step` are the MEDIAN; `timing` carries min / max / every repeat.
+Timing: the timed region (K steps between two barriers + synchronisations, MAX over ranks) is repeated R times (--repeats; default 1, with --full 7
+when K steps take less than 50 ms, else 3) and `value` / `ms_per_step` are the MEDIAN; `timing` carries min / max / every repeat.
 
-Extra objects on the line (prompt section 4):
+Extra objects on the line (--full):
   roofline     -- the kernel FUNCTION the step spends most of its GPU time in (summed over all its launches and template instantiations;
                   a step that launches a convolution and a statistics sweep is two entries, never one): the algorithmic flops (or HBM
                   bytes) of those launches / their summed duration, against the dense MFMA peak of the dtype (fp32 157.3 TFLOP/s, fp16
@@ -44,7 +53,7 @@ Extra objects on the line (prompt section 4):
                   `traffic` = HBM bytes per launch from the committed PMC passes (profiles/pmc_latest.json), only when that file was
                   taken with the kernel sources of this build (fingerprint match), else null.
   kernels      -- every kernel function of the step by share of GPU time, each with its own bound and fraction.
-  configs      -- (default run: --config c2 on one GPU) compact records of the OTHER BASELINE configs c1, c3, c4, c5 measured the same way
+  configs      -- (--full with --config c2 on one GPU) compact records of the OTHER BASELINE configs c1, c3, c4, c5 measured the same way
                   in the same process: ms_per_step / images/s (median of R), in-run parity against the oracle, whole-step fraction,
                   dominant kernel with fraction and PMC traffic ratio (--also none switches them off).
   cpu_baseline -- the CPU oracle (kind "port": this repo's C restatement of the reference shaders; the reference has no CPU conv
@@ -182,6 +191,12 @@ class Workload:
     def launches(self):
         return sum(n * sum(p.num_steps() for p in plans) for (_, plans), n in zip(self.runners, self.counts))
 
+    def outputs(self):
+        """what a caller receives after the last step: the output tensor of every plan chain (one per distinct micro-batch size)"""
+        self.ctx.sync()
+        ys = [r.y.numpy() for r, _ in self.runners]
+        return {"output" if len(ys) == 1 else "output_b%d" % r.in_shape[0]: y for (r, _), y in zip(self.runners, ys)}
+
     def close(self):
         pass
 
@@ -273,6 +288,11 @@ class HostWorkload:
 
     def launches(self):
         return sum(n * len(m.plan_steps()) for m, n in zip(self.models, self.counts))
+
+    def outputs(self):
+        """what a caller receives after the last step: MixedInferenceCore's output of every model (one per distinct micro-batch size)"""
+        self.sync()
+        return {"output" if len(self.models) == 1 else "output_b%d" % m.batch: m.output() for m in self.models}
 
     def close(self):
         for m in self.models:
@@ -445,6 +465,32 @@ def compact_line(detail, detail_path="bench_detail.json"):
             if len(text) <= LINE_BUDGET:
                 break
     return text
+
+
+OUTPUT_BUDGET = 48 << 20  # bytes of float32 data --dump-outputs writes at most (c2's whole 4K frame is 33 MB; c5's 32 x 720p x 3 output is sampled)
+OUTPUT_SAMPLE_SEED = 7767517
+
+
+def write_outputs(outputs, outdir, budget=OUTPUT_BUDGET):
+    """--dump-outputs: every output array as <outdir>/<name>.npy in float32.  An array larger than its share of `budget` is written as a fixed sample:
+    the flattened array at the sorted, de-duplicated indices of `share` draws from a generator seeded with OUTPUT_SAMPLE_SEED (the same indices
+    for every run with the same shapes).  Returns {name: {"shape", "file", "sampled_elements" (None = whole array)}}."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // 4 // max(1, len(outputs))
+    record = {}
+    for name, a in sorted(outputs.items()):
+        a = np.asarray(a, dtype=np.float32)
+        shape, sampled = list(a.shape), None
+        if a.size > share:
+            idx = np.unique(np.random.default_rng(OUTPUT_SAMPLE_SEED).integers(0, a.size, share))
+            a = a.reshape(-1)[idx]
+            sampled = int(a.size)
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        record[name] = {"shape": shape, "file": path, "sampled_elements": sampled}
+    return record
 
 
 def write_detail(detail, path=None):
@@ -660,14 +706,14 @@ def run_config(config, args, env, primary):
 
     # ---- parity leg (rank 0): the GPU result of image 0 against the oracle's, before anything is timed
     parity, cpu_rec = None, None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         cpu_rec, want = cpu_baseline(config, net, timed_legs=(world == 1 and not args.no_cpu_baseline), compact=not primary)
         got = wl.first_input_output()
         got = np.asarray(got).reshape((-1,) + tuple(want.shape[1:]))[:1]
         parity = parity_record(config, got, want)
         if not parity["ok"]:
             sys.stderr.write("bench.py: PARITY FAILURE (%s) against the CPU oracle: %s\n" % (config, json.dumps(parity)))
-    elif rank == 0 and primary and world == 1 and not args.no_cpu_baseline:
+    elif rank == 0 and args.full and primary and world == 1 and not args.no_cpu_baseline:
         cpu_rec, _ = cpu_baseline(config, net)
 
     barrier = group.barrier  # dist.barrier + torch.cuda.synchronize()
@@ -700,16 +746,19 @@ def run_config(config, args, env, primary):
     value_fn = wl.run_sync if (args.value_mode == "sync" and through == "host") else wl.run_inflight
     for _ in range(warmup):
         value_fn()
-    # R timed regions of exactly `steps` steps each; the line quotes the median (a 20-step ESPCN region is 2.5 ms: one sample cannot be told from noise)
+    # R timed regions of exactly `steps` steps each; the line quotes the median (a 20-step ESPCN region is 2.5 ms: one sample cannot be told from noise).
+    # A plain run times ONE region: --steps is the number of timed steps
     first = timed_region(value_fn, steps)
-    repeats = args.repeats if args.repeats > 0 else (7 if first < 0.05 else 3)
+    repeats = args.repeats if args.repeats > 0 else ((7 if first < 0.05 else 3) if args.full else 1)
     if not primary:
         repeats = min(repeats, 5)
     samples = [first] + [timed_region(value_fn, steps) for _ in range(repeats - 1)]
     elapsed = float(np.median(samples))
+    # what the last timed step computed, before anything else runs on these models
+    dumped = write_outputs(wl.outputs(), args.dump_outputs) if (primary and rank == 0 and args.dump_outputs) else None
     # each rank's OWN clock over one more region of the same steps (the samples above are already the MAX over ranks): a slow GPU shows up by rank
     own_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -720,7 +769,7 @@ def run_config(config, args, env, primary):
 
     # the other wait semantics on the same models, same step count (host path; outside `value`)
     modes = {}
-    if through == "host" and primary:
+    if through == "host" and primary and args.full:
         other = wl.run_inflight if value_fn == wl.run_sync else wl.run_sync
         med = lambda fn: float(np.median([timed_region(fn, steps) for _ in range(min(repeats, 3))]))
         if value_fn == wl.run_sync:
@@ -736,7 +785,7 @@ def run_config(config, args, env, primary):
     # per-kernel durations: a launch trace over a fixed number of steps run launch by launch on the same plans and buffers, right after the timed
     # region (clocks still up); every kernel is stamped with its own dispatch start / end
     rows, trace_steps = [], 0
-    if not args.no_kernel_events and args.event_launches > 0:
+    if args.full and not args.no_kernel_events and args.event_launches > 0:
         trace_steps = max(1, min(args.event_launches, {"c1": 64, "c2": 32, "c3": 8, "c4": 4, "c5": 2}[config]))
         wl.launch_by_launch(True)
         wl.run_sync() if through == "host" else (wl.run_device(), wl.sync())  # first launch-by-launch pass untraced
@@ -751,7 +800,7 @@ def run_config(config, args, env, primary):
 
     layer_table = None
     table_loops = args.layer_table if args.layer_table is not None else (20 if world == 1 else 0)
-    if rank == 0 and through == "host" and primary and table_loops > 0:
+    if rank == 0 and through == "host" and primary and args.full and table_loops > 0:
         layer_table = wl.layer_table(table_loops)
 
     out = None
@@ -843,6 +892,8 @@ def run_config(config, args, env, primary):
                 out["roofline"]["whole_step_frac_sync_per_inference"] = out["frac_of_whole_step_roofline_sync_per_inference"]
         if cpu_rec is not None:
             out["cpu_baseline"] = cpu_rec
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if not primary:
             # the compact form of the `configs` block
             keep = ("value", "unit", "steps", "warmup", "ms_per_step", "dtype", "scaling", "value_mode", "frac_of_whole_step_roofline", "whole_step_roofline_ms", "unfused_accounting",
@@ -877,10 +928,17 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the in-run oracle check, the CPU baseline, the other configs (--also), the median of several "
+                         "timed regions, both wait semantics, the launch trace (roofline / kernels) and the per-layer table")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's output arrays) as DIR/<name>.npy in float32, at most 48 MiB in all "
+                         "(a larger output as a fixed, seeded sample)")
     ap.add_argument("--also", default=None,
-                    help="comma-separated configs measured in the same run and reported compactly under `configs` (default: the other four when --config c2 "
-                         "runs on one GPU; `none` = off)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions per config (value = median); 0 = 7 when a region is shorter than 50 ms, else 3")
+                    help="with --full: comma-separated configs measured in the same run and reported compactly under `configs` (default: the other four "
+                         "when --config c2 runs on one GPU; `none` = off)")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="timed regions per config (value = median); 0 = one region, or with --full 7 when a region is shorter than 50 ms, else 3")
     ap.add_argument("--preheat-ms", type=float, default=150.0, help="run the workload untimed for at least this long before --warmup (clock ramp)")
     ap.add_argument("--unfused", action="store_true", help="one kernel per layer, no chain fusion (debug / comparison)")
     ap.add_argument("--through", choices=["auto", "host", "capi"], default="auto",
@@ -892,14 +950,14 @@ def main():
     ap.add_argument("--all-kernels", action="store_true", help="list every kernel function and instantiation of the step in `kernels` (default: the 10 most expensive)")
     ap.add_argument("--micro", type=int, default=0, help="micro-batch size of the rank's share (default: the config's)")
     ap.add_argument("--no-capture", action="store_true", help="host path: launch kernel by kernel instead of replaying the recorded hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the timed CPU legs (the parity check still runs the oracle once)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run oracle check (debug only: the line then says parity: null)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip the launch-trace leg (no `roofline` / `kernels`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the timed CPU legs (the parity check still runs the oracle once)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the in-run oracle check (debug only: the line then says parity: null)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: skip the launch-trace leg (no `roofline` / `kernels`)")
     ap.add_argument("--event-launches", type=int, default=64, help="upper bound on the steps run under the launch trace after the timed region (per config: 64 / 32 / 8 / 4 / 2)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend of the barrier / MAX-reduction (nccl = RCCL, the driver's; gloo: several ranks may share one GPU -- rank r "
                          "runs on device r %% device_count -- which is how the N > 1 path is exercised on a one-GPU box)")
-    ap.add_argument("--layer-table", type=int, default=None, help="loops of the reference-style per-layer table (first 5 dropped); default 20 at N=1, 0 = off")
+    ap.add_argument("--layer-table", type=int, default=None, help="with --full: loops of the reference-style per-layer table (first 5 dropped); default 20 at N=1, 0 = off")
     ap.add_argument("--detail-out", default=None, help="where the full record goes (default: bench_detail.json beside bench.py, plus gpurun_out/ when present)")
     args = ap.parse_args()
 
@@ -944,6 +1002,8 @@ def main():
     out, parity = run_config(args.config, args, env, primary=True)
     failed = parity is not None and not parity["ok"]
     also = args.also if args.also is not None else ("c1,c3,c4,c5" if (args.config == "c2" and world == 1 and not args.unfused and args.through != "capi") else "none")
+    if not args.full:
+        also = "none"
     extra = [c for c in also.split(",") if c in CONFIGS and c != args.config] if also != "none" else []
     if extra:
         t0 = time.perf_counter()

@@ -77,3 +77,23 @@ def test_write_detail_keeps_the_full_record(tmp_path):
     p = str(tmp_path / "bench_detail.json")
     assert bench.write_detail(d, p) == [p]
     assert json.load(open(p)) == d
+
+
+def test_write_outputs_keeps_small_arrays_whole_and_samples_large_ones_the_same_way_every_run(tmp_path):
+    """--dump-outputs: float32 .npy files within the budget; an output over its share is a fixed sample (same indices for the same shapes)"""
+    import numpy as np
+
+    small = np.arange(12, dtype=np.float64).reshape(3, 4)
+    big = np.random.default_rng(1).standard_normal((5, 300, 7)).astype(np.float16)
+    budget = 4 * 2000
+    rec = bench.write_outputs({"small": small, "big": big}, str(tmp_path / "a"), budget=budget)
+    assert rec["small"]["shape"] == [3, 4] and rec["small"]["sampled_elements"] is None
+    assert rec["big"]["shape"] == [5, 300, 7] and 0 < rec["big"]["sampled_elements"] <= 1000
+    a_small, a_big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_small.dtype == np.float32 and a_big.dtype == np.float32
+    np.testing.assert_array_equal(a_small, small.astype(np.float32))
+    assert a_small.nbytes + a_big.nbytes <= budget
+    assert np.isin(a_big, big.astype(np.float32)).all()  # a sample of the array's own values
+    bench.write_outputs({"small": small, "big": big}, str(tmp_path / "b"), budget=budget)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "big.npy"), a_big)
+    assert bench.OUTPUT_BUDGET <= 64e6

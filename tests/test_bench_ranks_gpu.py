@@ -24,7 +24,7 @@ def _free_port():
 
 def _bench(ranks, extra, under_torchrun=True, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    tail = ["--gpus", str(ranks), "--also", "none", "--no-cpu-baseline", "--layer-table", "0"] + extra
+    tail = ["--gpus", str(ranks), "--full", "--also", "none", "--no-cpu-baseline", "--layer-table", "0"] + extra
     if under_torchrun:  # the driver's command
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                os.path.join(ROOT, "bench.py")] + tail
@@ -102,14 +102,14 @@ def test_two_rccl_ranks_on_the_one_device_exit_with_a_one_line_reason(built):
 
 
 def test_the_drivers_exact_command_prints_one_parsable_line_under_8_kb(built):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (BENCH_rNN.json's cmd): ONE line on stdout, < 8192 bytes (BENCH_r05.json: 22.7 KB -> parsed: null), with
-    the standard keys + roofline + cpu_baseline + the four other configs; the full record lands in bench_detail.json"""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` (BENCH_rNN.json's cmd) with --full: ONE line on stdout, < 8192 bytes (BENCH_r05.json: 22.7 KB ->
+    parsed: null), with the standard keys + roofline + cpu_baseline + the four other configs; the full record lands in bench_detail.json"""
     import torch
 
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900,
                        env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = r.stdout.strip().splitlines()
@@ -129,3 +129,38 @@ def test_the_drivers_exact_command_prints_one_parsable_line_under_8_kb(built):
     for k in ("kernels", "layer_table", "wait_semantics", "configs"):
         assert k in detail and k not in d
     assert abs(detail["value"] - d["value"]) <= 1e-4 * d["value"]
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_what_the_last_step_computed(built, tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` does only what the headline needs: ONE timed region of exactly N steps, no oracle check, no
+    other configs, no launch trace; --dump-outputs writes what the last timed step computed -- here the whole 4K frame, which is the oracle's."""
+    import numpy as np
+    import torch
+
+    import bench
+    import oracle_lib
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out, detail_path = tmp_path / "out", tmp_path / "detail.json"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out), "--detail-out", str(detail_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-1000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "images/s" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["metric"].startswith("images/sec (1080p ESPCN 2x)")
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["timing"]["repeats"] == 1
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    assert d["parity"] is None and "roofline" not in d and "cpu_baseline" not in d
+    detail = json.load(open(detail_path))
+    assert len(detail["timing"]["ms_per_step_of_each_repeat"]) == 1
+    for k in ("configs", "kernels", "layer_table", "wait_semantics"):
+        assert k not in detail
+    assert detail["dumped_outputs"]["output"]["shape"] == [2160, 3840, 1] and detail["dumped_outputs"]["output"]["sampled_elements"] is None
+    assert [p.name for p in out.iterdir()] == ["output.npy"] and (out / "output.npy").stat().st_size <= 64e6
+    y = np.load(out / "output.npy")
+    assert y.dtype == np.float32 and y.shape == (2160, 3840, 1)
+    want = oracle_lib.forward(bench.make_net("c2"), bench.oracle_input("c2"), threads=min(16, os.cpu_count() or 1))
+    np.testing.assert_allclose(y[None], want, rtol=1e-4, atol=1e-4)

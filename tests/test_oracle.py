@@ -1,5 +1,8 @@
 """CPU tests of the oracle itself: the two independent walks agree, and both agree with torch's CPU conv2d (the same
 math as the ncnn naive layers the reference's own unit tests compare against, demo/test/unittest/convolutionTest.cpp:44-94)."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -167,17 +170,23 @@ def test_dense_semantics_Q8_and_unknown_activation_Q19():
 
 @pytest.mark.parametrize("act", ["relu", "", "sigmoid", "tanh", "softmax", "leakyRelu", "SiLU", "linear"])
 def test_dense_against_reference_eigen_path(act):
-    """PINS the dense oracle: oracle/_ref/ref_dense is the reference's own CPUCommonUtil<float> (Eigen)."""
+    """PINS the dense oracle: oracle/_ref/ref_dense is the reference's own CPUCommonUtil<float> (Eigen).  Its outputs for these inputs are
+    stored in tests/golden/dense_ref.json (tests/golden/make_golden.py, the 11 -> 5 cases); where oracle/_ref/ref_dense is built it runs live too."""
     rng = np.random.default_rng(41)
     In, Out = 11, 5  # denseTest.cpp:111
     w = rng.standard_normal(In * Out).astype(np.float32)
     b = rng.standard_normal(Out).astype(np.float32)
     x = rng.standard_normal(In).astype(np.float32)
-    ref = O.ref_dense(In, Out, act, 0.3, w, b, x)
-    if ref is None:
-        pytest.skip("oracle/_ref/ref_dense not built (needs /root/reference)")
+    stored = [c for c in json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dense_ref.json")))["cases"]
+              if (c["in"], c["out"], c["act"]) == (In, Out, act)]
+    assert len(stored) == 1 and stored[0]["alpha"] == 0.3
+    for k, v in (("w_flat", w), ("bias", b), ("x", x)):  # the stored case is this test's draw
+        np.testing.assert_array_equal(np.array(stored[0][k], np.float32), v)
     got = O.dense(x[None], w, Out, b, act, 0.3)[0]
-    np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(got, stored[0]["expected"], rtol=1e-5, atol=1e-6)
+    ref = O.ref_dense(In, Out, act, 0.3, w, b, x)
+    if ref is not None:
+        np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-6)
 
 
 # ---- element-wise / pooling / shape operators (SURVEY 8f): the C restatements vs torch CPU ops ------------------------------

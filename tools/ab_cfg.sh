@@ -5,7 +5,7 @@ c=$1; shift
 D=$(mktemp -d)
 for r in 1 2; do
 for spec in "$@"; do
-  env $spec python bench.py --config $c --also none --no-cpu-baseline --layer-table 0 --detail-out $D/d.json >/dev/null 2>&1
+  env $spec python bench.py --config $c --full --also none --no-cpu-baseline --layer-table 0 --detail-out $D/d.json >/dev/null 2>&1
   python -c "
 import json
 d=json.load(open('$D/d.json'))

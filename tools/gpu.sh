@@ -3,9 +3,9 @@
 #   usage: gpurun --timeout S -- 'tools/gpu.sh <tag> <action> [<action> ...]'
 #   actions:
 #     tests[:<pytest -k expression>]   the -m gpu suite (or the tests matching the expression)            -> pytest[_N].txt
-#     bench[:c1,c2,...]                one bench.py line per config (default: all five), each with --also none -> bench_<c>.json / .err
-#     benchall                         the driver's command: python bench.py (c2 + the other four configs in `configs`) -> bench_all.json
-#     benchx:<c>:<extra bench args>    one bench line with extra arguments ('+' stands for a blank)        -> benchx_<n>.json
+#     bench[:c1,c2,...]                one bench.py --full line per config (default: all five), each with --also none -> bench_<c>.json / .err
+#     benchall                         the driver's command with --full: python bench.py --full (c2 + the other four configs in `configs`) -> bench_all.json
+#     benchx:<c>:<extra bench args>    one bench --full line with extra arguments ('+' stands for a blank)        -> benchx_<n>.json
 #     prof:<c>                         rocprofv3 kernel trace + PMC passes of that config's bench command -> <tag>_<c>/summary.md
 #     livecheck:<c>                    bench.py with its live launch trace under rocprofv3 --kernel-trace, same process -> live_vs_rocprof_<c>.json
 #     profx:<name>:<command>           the same passes around an arbitrary command ('+' stands for a blank)   -> <tag>_<name>/summary.md
@@ -15,6 +15,7 @@
 #     lib:<tag>                        load build/abl/libsnnhip_<tag>.so in the following actions ('lib:' = the product library again)
 #     env:NAME=VALUE                   export for the following actions
 cd "$GRAFT_REPO_ROOT" || exit 1
+ROOT=$(pwd)
 TAG=${1:-run}; shift
 O=gpurun_out/$TAG
 mkdir -p "$O"
@@ -30,15 +31,15 @@ for act in "$@"; do
       else timeout 2400 python -m pytest tests -m gpu -q --timeout 900 > "$O/pytest.txt" 2>&1; tail -6 "$O/pytest.txt"; fi ;;
     bench)
       for c in $(echo "${arg:-c2,c1,c3,c4,c5}" | tr ',' ' '); do
-        timeout 900 python bench.py --config "$c" --also none --detail-out "$O/bench_$c.detail.json" > "$O/bench_$c.json" 2> "$O/bench_$c.err" || { echo "bench $c rc=$?"; tail -3 "$O/bench_$c.err"; }
+        timeout 900 python bench.py --config "$c" --full --also none --detail-out "$O/bench_$c.detail.json" > "$O/bench_$c.json" 2> "$O/bench_$c.err" || { echo "bench $c rc=$?"; tail -3 "$O/bench_$c.err"; }
       done
       python tools/bench_digest.py "$O" ;;
     benchall)
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --detail-out "$O/bench_all.detail.json" > "$O/bench_all.json" 2> "$O/bench_all.err" || { echo "benchall rc=$?"; tail -3 "$O/bench_all.err"; }
+      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --detail-out "$O/bench_all.detail.json" > "$O/bench_all.json" 2> "$O/bench_all.err" || { echo "benchall rc=$?"; tail -3 "$O/bench_all.err"; }
       python tools/bench_digest.py "$O/bench_all.json" ;;
     benchx)
       c=${arg%%:*}; extra=${arg#*:}
-      timeout 900 python bench.py --config "$c" ${extra//+/ } --detail-out "$O/benchx_$n.detail.json" > "$O/benchx_$n.json" 2> "$O/benchx_$n.err" || { echo "benchx $arg rc=$?"; tail -3 "$O/benchx_$n.err"; }
+      timeout 900 python bench.py --config "$c" --full ${extra//+/ } --detail-out "$O/benchx_$n.detail.json" > "$O/benchx_$n.json" 2> "$O/benchx_$n.err" || { echo "benchx $arg rc=$?"; tail -3 "$O/benchx_$n.err"; }
       python tools/bench_digest.py "$O/benchx_$n.json" ;;
     prof)
       steps=$(python -c "print({'c1':'--steps 200 --warmup 20','c2':'--steps 100 --warmup 10','c3':'--steps 10 --warmup 2','c4':'--steps 4 --warmup 1','c5':'--steps 2 --warmup 1'}['$arg'])")
@@ -47,7 +48,7 @@ for act in "$@"; do
       grep "derived" -A30 "$O/profile_$arg.log" | cut -c1-240 | head -34 ;;
     livecheck) # livecheck:<c>: bench.py (its own launch trace ON) under rocprofv3 --kernel-trace in one process; tools/live_vs_rocprof.py compares the two on the same launches
       mkdir -p "$O/live_$arg"
-      ( cd /tmp && TMPDIR=/tmp timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$O/live_$arg" -- python "$GRAFT_REPO_ROOT/bench.py" --config "$arg" --also none --no-cpu-baseline --layer-table 0 --detail-out "$GRAFT_REPO_ROOT/$O/live_$arg/detail.json" > "$GRAFT_REPO_ROOT/$O/live_$arg/line.json" 2> "$GRAFT_REPO_ROOT/$O/live_$arg/err.txt" )
+      ( cd /tmp && TMPDIR=/tmp timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$O/live_$arg" -- python "$ROOT/bench.py" --config "$arg" --full --also none --no-cpu-baseline --layer-table 0 --detail-out "$ROOT/$O/live_$arg/detail.json" > "$ROOT/$O/live_$arg/line.json" 2> "$ROOT/$O/live_$arg/err.txt" )
       python tools/live_vs_rocprof.py "$O/live_$arg" | tee "$O/live_vs_rocprof_$arg.json" ;;
     profx) # profx:<name>:<command, '+' for blanks>: kernel trace + PMC passes of an arbitrary command (e.g. one layer through tools/bench_layers.py)
       nm=${arg%%:*}; cmd=${arg#*:}

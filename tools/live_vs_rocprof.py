@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """bench.py's live per-kernel leg against rocprofv3 IN THE SAME PROCESS: runs on the GPU box as
-    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python bench.py --config cN --also none --detail-out <dir>/detail.json ...
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python bench.py --config cN --full --also none --detail-out <dir>/detail.json ...
 (tools/gpu.sh action `livecheck:cN`) and then compares, for the dominant kernel function of the line's `roofline`, the average launch duration bench.py measured
 with its own launch trace (run right after the timed region) with the durations rocprofv3 recorded for the SAME launches -- the last launches of that kernel in
 the trace -- and with rocprofv3's --stats average over all launches (pre-heat and warm-up included).   python tools/live_vs_rocprof.py <dir>"""

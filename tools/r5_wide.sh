@@ -7,6 +7,6 @@ if [ $rc -ne 0 ]; then exit 0; fi
 timeout 900 python -m pytest tests/test_configs_gpu.py tests/test_fp16_gpu.py tests/test_guard_gpu.py -m gpu -q --timeout 600 -k "c5 or candy or guard or style" > "$O/t_c5.txt" 2>&1; echo "c5 tests rc=$?"; tail -8 "$O/t_c5.txt" | cut -c1-220
 tools/ab_wide.sh SNNHIP_WIDE_PERSIST=0 SNNHIP_WIDE_PERSIST=1 > "$O/ab.txt" 2>&1; cat "$O/ab.txt"
 for spec in SNNHIP_WIDE_PERSIST=0 SNNHIP_WIDE_PERSIST=1; do
-  env $spec timeout 600 python bench.py --config c5 --also none --no-cpu-baseline --layer-table 0 > "$O/bench_c5_$spec.json" 2> "$O/bench_c5_$spec.err" || tail -3 "$O/bench_c5_$spec.err"
+  env $spec timeout 600 python bench.py --config c5 --full --also none --no-cpu-baseline --layer-table 0 > "$O/bench_c5_$spec.json" 2> "$O/bench_c5_$spec.err" || tail -3 "$O/bench_c5_$spec.err"
   python tools/bench_digest.py "$O/bench_c5_$spec.json" | head -8
 done

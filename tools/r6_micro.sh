@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 D=$(mktemp -d)
 for r in 1 2; do for m in ${1:-16 32}; do
-  python bench.py --config c5 --also none --no-cpu-baseline --layer-table 0 --micro $m --detail-out $D/d.json >/dev/null 2>&1
+  python bench.py --config c5 --full --also none --no-cpu-baseline --layer-table 0 --micro $m --detail-out $D/d.json >/dev/null 2>&1
   python -c "
 import json
 d=json.load(open('$D/d.json'))
