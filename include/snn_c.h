@@ -36,6 +36,23 @@ int snn_model_create3(const char* json_path, int device, int in_w, int in_h, int
  * texture dimension to 1, core/src/ic2/core.cpp:371; here it carries the image count).  Uploads / downloads move batch x H x W x C floats. */
 int snn_model_create4(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, snn_model** out);
+/* 8-bit frames at the model's ends (the reference's InferenceGraph::IODesc::format / ShaderGenOptions::desiredOutputFormat = ColorFormat::R8,
+ * RGB8 or RGBA8).  in_format / out_format: SNN_IO_FLOAT (the model's fp32 / fp16 tensors, as snn_model_create4) or an 8-bit format whose channel
+ * count is the model input's / output's own.  The input frame is y = (u - in_means[c]) * in_norms[c], the output q = clamp(rint(fmaf(x,
+ * out_scale[c], out_offset[c])), 0, 255) (include/snnhip.h, snnhip_u8_in_plan_create / _u8_out_plan_create); the conversions join the fusion
+ * graph, so for ESPCN they run inside its two fused kernels. */
+enum { SNN_IO_FLOAT = 0, SNN_IO_R8 = 1, SNN_IO_RGB8 = 3, SNN_IO_RGBA8 = 4 };
+typedef struct snn_frame_io {
+    int in_format, out_format;
+    float in_means[4], in_norms[4];
+    float out_scale[4], out_offset[4];
+} snn_frame_io;
+int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_frame_io* io, snn_model** out);
+/* [batch][H][W][C] bytes into the model's input frame / out of its output frame (after snn_model_run or snn_model_sync); no allocation per
+ * call, the tensors are the model's own, so a recorded graph replays across calls.  -1 when the model has no 8-bit frame at that end. */
+int snn_model_upload_frame_u8(snn_model* m, const unsigned char* nhwc);
+int snn_model_download_frame_u8(snn_model* m, unsigned char* nhwc);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

@@ -71,7 +71,8 @@ enum { SNNHIP_PAD_NONE = 0, SNNHIP_PAD_CONSTANT = 1, SNNHIP_PAD_REPLICATE = 2, S
 /* element types.  SNNHIP_F16 = IEEE half storage (the reference's RGBA16F textures / "preferHp", inferencegraph.h ColorFormat::RGBA16F):
  * tensors hold halfs in HBM, kernels convert on load, accumulate in fp32 (fp16-input MFMA for the convolutions) and round to nearest even
  * on store.  The host-side upload / download entry points always speak fp32 and convert. */
-enum { SNNHIP_F32 = 0, SNNHIP_F16 = 1, SNNHIP_U8 = 2 /* 8-bit image input of snnhip_image_u8_plan_create only */ };
+enum { SNNHIP_F32 = 0, SNNHIP_F16 = 1, SNNHIP_U8 = 2 /* 8-bit frames: input of snnhip_image_u8_plan_create / snnhip_u8_in_plan_create, output of
+                                                          snnhip_u8_out_plan_create, and the two ends of a chain that starts / ends with those plans */ };
 
 /* ---- context -------------------------------------------------------------------------------------- */
 
@@ -334,6 +335,28 @@ typedef struct {
 int snnhip_image_u8_plan_create(snnhip_ctx* ctx, const snnhip_image_u8_desc* desc, snnhip_plan** out);
 /* raw byte upload for SNNHIP_U8 tensors (nbytes must equal snnhip_tensor_bytes) */
 int snnhip_tensor_upload_raw(snnhip_tensor* t, const void* host, size_t nbytes);
+/* raw byte download (any dtype; nbytes must equal snnhip_tensor_bytes): stream sync + D2H, the counterpart of snnhip_tensor_upload_raw */
+int snnhip_tensor_download_raw(const snnhip_tensor* t, void* host, size_t nbytes);
+
+/* 8-bit frames at both ends of a model.  Unlike snnhip_image_u8_plan_create these keep the channel count (no widening to RGBA).
+ *   u8_in :  U8 [N][H][W][C] -> dtype [N][H][W][C],   y = (float(u) - means[c]) * norms[c]      (a subtract, then a multiply: no fma)
+ *   u8_out:  dtype [N][H][W][C] -> U8 [N][H][W][C],   q = clamp(rint(fmaf(x, scale[c], offset[c])), 0, 255)
+ * The u8_out contract: fmaf in fp32 (an fp16 input is widened exactly first), rounding to nearest with ties to even, NaN -> 0, +inf -> 255,
+ * -inf -> 0.  It is the single definition: the chain rules that fold these plans into the ESPCN kernels (A8: u8_in with C == 1 and dtype F32 in
+ * front of rule A; B8: u8_out with C == 1 behind rule B) reproduce both maps bit for bit, out-of-image taps of kernel A staying 0 in the
+ * NORMALISED domain, exactly as the separate launches give them.  C is 1..4; dtype SNNHIP_F32 or SNNHIP_F16. */
+typedef struct {
+    int N, H, W, C;
+    int dtype;
+    float means[4], norms[4];
+} snnhip_u8_in_desc;
+int snnhip_u8_in_plan_create(snnhip_ctx* ctx, const snnhip_u8_in_desc* desc, snnhip_plan** out);
+typedef struct {
+    int N, H, W, C;
+    int dtype;
+    float scale[4], offset[4];
+} snnhip_u8_out_desc;
+int snnhip_u8_out_plan_create(snnhip_ctx* ctx, const snnhip_u8_out_desc* desc, snnhip_plan** out);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

@@ -78,6 +78,14 @@ class ImageU8Desc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("src_channels", C.c_int), ("means", C.c_float * 4), ("norms", C.c_float * 4)]
 
 
+class U8InDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("means", C.c_float * 4), ("norms", C.c_float * 4)]
+
+
+class U8OutDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("scale", C.c_float * 4), ("offset", C.c_float * 4)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -147,6 +155,9 @@ SIGNATURES = {
     "snnhip_resize_plan_create": (C.c_int, [_P, C.POINTER(ResizeDesc), C.POINTER(_P)]),
     "snnhip_image_u8_plan_create": (C.c_int, [_P, C.POINTER(ImageU8Desc), C.POINTER(_P)]),
     "snnhip_tensor_upload_raw": (C.c_int, [_P, _P, C.c_size_t]),
+    "snnhip_tensor_download_raw": (C.c_int, [_P, _P, C.c_size_t]),
+    "snnhip_u8_in_plan_create": (C.c_int, [_P, C.POINTER(U8InDesc), C.POINTER(_P)]),
+    "snnhip_u8_out_plan_create": (C.c_int, [_P, C.POINTER(U8OutDesc), C.POINTER(_P)]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_graph_fuse": (C.c_int, [_P, C.POINTER(GraphNode), C.c_int, C.POINTER(FusedNode)]),
@@ -290,7 +301,7 @@ class Context:
             self.h = None
 
 
-F32, F16, U8 = 0, 1, 2  # SNNHIP_F32 / SNNHIP_F16 / SNNHIP_U8 (8-bit image input of image_u8_plan only)
+F32, F16, U8 = 0, 1, 2  # SNNHIP_F32 / SNNHIP_F16 / SNNHIP_U8 (8-bit frames: image_u8_plan / u8_in_plan input, u8_out_plan output)
 
 
 class Tensor:
@@ -310,6 +321,13 @@ class Tensor:
 
     @staticmethod
     def from_numpy(ctx, a, dtype=F32):
+        """dtype=U8: the array's bytes as an 8-bit tensor (uploaded raw)."""
+        if dtype == U8:
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            assert a.ndim == 4, "expected NHWC"
+            t = Tensor(ctx, *a.shape, dtype=U8)
+            t.upload_u8(a)
+            return t
         a = np.ascontiguousarray(a, dtype=np.float32)
         assert a.ndim == 4, "expected NHWC"
         t = Tensor(ctx, *a.shape, dtype=dtype)
@@ -338,6 +356,13 @@ class Tensor:
         a = np.ascontiguousarray(a, dtype=np.uint8)
         assert self.dtype == U8 and a.size == int(np.prod(self.shape)), (a.shape, self.shape)
         check(lib().snnhip_tensor_upload_raw(self.h, a.ctypes.data_as(_P), a.size))
+
+    def numpy_u8(self):
+        """Raw byte download of an 8-bit tensor (dtype=U8) as uint8 NHWC (numpy() speaks float32 and refuses 8-bit tensors)."""
+        assert self.dtype == U8, self.dtype
+        out = np.empty(self.shape, dtype=np.uint8)
+        check(lib().snnhip_tensor_download_raw(self.h, out.ctypes.data_as(_P), out.size))
+        return out
 
     def argmax(self, n=0):
         """Index of the largest element of image n (first on ties) -- the reference reports this + 1 as classifierOutput (core.cpp:228-234)."""
@@ -600,6 +625,22 @@ def image_u8_plan(ctx, N, H, W, src_channels, means=(0, 0, 0, 0), norms=(1, 1, 1
     d = ImageU8Desc(N, H, W, src_channels, (C.c_float * 4)(*means), (C.c_float * 4)(*norms))
     h = _P()
     check(lib().snnhip_image_u8_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def u8_in_plan(ctx, N, H, W, Cc, means=(0, 0, 0, 0), norms=(1, 1, 1, 1), dtype=F32):
+    """U8 [N][H][W][Cc] -> dtype [N][H][W][Cc]: y = (float(u) - means[c]) * norms[c]."""
+    d = U8InDesc(N, H, W, Cc, dtype, (C.c_float * 4)(*means), (C.c_float * 4)(*norms))
+    h = _P()
+    check(lib().snnhip_u8_in_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def u8_out_plan(ctx, N, H, W, Cc, scale=(1, 1, 1, 1), offset=(0, 0, 0, 0), dtype=F32):
+    """dtype [N][H][W][Cc] -> U8: q = clamp(rint(fmaf(x, scale[c], offset[c])), 0, 255), NaN -> 0."""
+    d = U8OutDesc(N, H, W, Cc, dtype, (C.c_float * 4)(*scale), (C.c_float * 4)(*offset))
+    h = _P()
+    check(lib().snnhip_u8_out_plan_create(ctx.h, C.byref(d), C.byref(h)))
     return Plan(ctx, h)
 
 

@@ -746,6 +746,14 @@ int snnhip_tensor_upload_raw(snnhip_tensor* t, const void* host, size_t nbytes) 
     return SNNHIP_OK;
 }
 
+int snnhip_tensor_download_raw(const snnhip_tensor* t, void* host, size_t nbytes) {
+    SNNHIP_REQUIRE(t && host, "tensor_download_raw: null argument");
+    SNNHIP_REQUIRE(nbytes == t->bytes(), "tensor_download_raw: %zu bytes asked for, the tensor holds %zu", nbytes, t->bytes());
+    SNNHIP_CHECK_HIP(hipMemcpyAsync(host, t->data, nbytes, hipMemcpyDeviceToHost, t->ctx->stream));
+    SNNHIP_CHECK_HIP(hipStreamSynchronize(t->ctx->stream));
+    return (snnhip::guard_on() && t->ctx->stream == t->ctx->mainStream) ? snnhip::guard_check_device(t->ctx) : SNNHIP_OK;
+}
+
 // C4HW4 <-> NHWC conversion happens on the host: it is an API-edge format (uploads of test inputs, dumps), never
 // on the inference path.
 int snnhip_tensor_upload_c4hw4(snnhip_tensor* t, const float* c4) {
@@ -901,12 +909,17 @@ int snnhip_plan_run_n(snnhip_plan* plan, const snnhip_tensor* const* inputs, int
     if (!plan->u8Input) {
         for (int i = 0; i < n_in; ++i) SNNHIP_REQUIRE(inputs[i]->dtype != SNNHIP_U8, "plan_run: input %d is an 8-bit image tensor (%s)", i, plan->desc.c_str());
     }
-    SNNHIP_REQUIRE(out->dtype != SNNHIP_U8, "plan_run: the output is an 8-bit image tensor (%s)", plan->desc.c_str());
+    if (plan->u8Output) {
+        SNNHIP_REQUIRE(out->dtype == SNNHIP_U8, "plan_run: the output must be an 8-bit tensor (%s), got dtype %d", plan->desc.c_str(), out->dtype);
+    } else {
+        SNNHIP_REQUIRE(out->dtype != SNNHIP_U8, "plan_run: the output is an 8-bit image tensor (%s)", plan->desc.c_str());
+    }
     if (!plan->anyDtype) {
         for (int i = 0; i < n_in; ++i)
-            SNNHIP_REQUIRE(inputs[i]->dtype == plan->dtype, "plan_run: input %d has dtype %d, the plan (%s) was built for %d", i, inputs[i]->dtype,
-                           plan->desc.c_str(), plan->dtype);
-        SNNHIP_REQUIRE(out->dtype == plan->dtype, "plan_run: output has dtype %d, the plan (%s) was built for %d", out->dtype, plan->desc.c_str(), plan->dtype);
+            SNNHIP_REQUIRE(inputs[i]->dtype == (plan->u8Input && i == 0 ? SNNHIP_U8 : plan->dtype), "plan_run: input %d has dtype %d, the plan (%s) was built for %d", i,
+                           inputs[i]->dtype, plan->desc.c_str(), plan->u8Input && i == 0 ? SNNHIP_U8 : plan->dtype);
+        SNNHIP_REQUIRE(out->dtype == (plan->u8Output ? SNNHIP_U8 : plan->dtype), "plan_run: output has dtype %d, the plan (%s) was built for %d", out->dtype,
+                       plan->desc.c_str(), plan->u8Output ? SNNHIP_U8 : plan->dtype);
     }
     if (plan->profiling && !plan->profilesItself()) {
         int rc = plan->profBegin(0);

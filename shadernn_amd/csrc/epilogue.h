@@ -80,6 +80,15 @@ __device__ __forceinline__ float fast_tanh(float x) {
     return fmaf(-2.0f, __builtin_amdgcn_rcpf(t + 1.0f), 1.0f);
 }
 
+// The u8_out contract (include/snnhip.h, snnhip_u8_out_plan_create): q = clamp(rint(fmaf(x, scale, offset)), 0, 255), ties to even, NaN -> 0.
+// frame_u8.hip's stand-alone kernel and kernel B's 8-bit epilogue (chain rule B8, espcn_fused.hip) both call this one function.
+__device__ __forceinline__ unsigned quantize_u8(float x, float scale, float offset) {
+    float v = rintf(fmaf(x, scale, offset));
+    v = v >= 0.0f ? v : 0.0f; // NaN fails the test: 0
+    v = v <= 255.0f ? v : 255.0f;
+    return static_cast<unsigned>(v);
+}
+
 // Element access: every kernel is instantiated for T = float and T = _Float16 (SNNHIP_F16 tensors: half storage, fp32 arithmetic,
 // round-to-nearest-even on store) and for CV = 4 (C % 4 == 0: one 16- or 8-byte access) or CV = 1.
 template <typename T, int CV>

@@ -255,273 +255,29 @@ __device__ __forceinline__ float act_mode(const ActCfg& a, float v) {
     return epi_act(a.act, a.leaky, v, 0.0f);
 }
 
+// Chain rule A8: an 8-bit input frame normalised while the tile is staged, y = (float(u) - mean) * norm (snnhip_u8_in_plan_create's map)
+struct U8InCfg {
+    float mean, norm;
+};
+
+// rule A's kernel (fp32 input) and rule A8's (8-bit input): one body, espcn_wino_a_body.h
 template <int K1, int TH, int AM, int WPS>
 __global__ __launch_bounds__(256, WPS) void conv_kxk_c1o16_wino3x3_c16o16_kernel(FusedAParams p, const float* __restrict__ x,
                                                                            const float* __restrict__ wA1, const float* __restrict__ wU,
                                                                            const float* __restrict__ ep1, const float* __restrict__ ep2,
                                                                            float* __restrict__ y) {
-    constexpr int TW = WinoTile::TW, U = 2;
-    constexpr int P1 = K1 / 2;
-    constexpr int C1W = TW + 2, C1H = TH + 2;
-    constexpr int C1P = 40, HALFP = 20;                        // LDS row pitch / odd-column plane offset, in pixels (see phase 2)
-    constexpr int INW = TW + 2 + 2 * P1, INH = TH + 2 + 2 * P1;
-    constexpr int INP = 48;                                    // LDS row pitch of the input tile: == 16 (mod 32) puts the four tap rows a
-                                                               // wave reads in one ds_read_b32 (lane group g -> row g) on disjoint banks
-    constexpr int KS1 = wino_conv1_ksteps(K1);
-    constexpr int NG1 = (C1H * C1W + 15) / 16;                 // 16-pixel groups of phase 1
-    constexpr int GPW = (NG1 + 3) / 4;                         // groups per wave (contiguous range)
-    constexpr int NIT = (GPW + U - 1) / U;
-    constexpr int GROUPS2 = TH / 8;                            // Winograd tile rows (= phase-2 groups) per wave
-    constexpr int NLD = (INH * INP + 8 + 255) / 256;
-    static_assert(INW <= INP, "input pitch");
-    static_assert(C1W / 2 + 1 <= HALFP && HALFP + C1W / 2 <= C1P, "plane layout");
+    typedef float TIn;
+    constexpr U8InCfg qin{0.0f, 0.0f};
+#include "espcn_wino_a_body.h"
+}
 
-    __shared__ __attribute__((aligned(16))) float smem[C1H * C1P * 16 + 4096 + INH * INP + 8];
-    float* s_c1 = smem;
-    float* s_U = smem + C1H * C1P * 16;
-    float* s_in = s_U + 4096;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
-    const int px = lane & 15, g = lane >> 4;
-    const int ntiles = p.tilesX * p.tilesY * p.N;
-
-    // Persistent blocks (grid = WPS per CU): weights / epilogue constants are loaded once per block and the input tile of the
-    // NEXT tile is fetched into NLD registers while this tile is computed, so no wave ever waits on HBM inside the loop.
-    auto tile_origin = [&](int t, int& n, int& x0, int& y0) {
-        int b = xcd_tile_order(t, ntiles);
-        const int tx = b % p.tilesX;
-        b /= p.tilesX;
-        const int ty = b % p.tilesY;
-        n = b / p.tilesY;
-        x0 = tx * TW;
-        y0 = ty * TH;
-    };
-    float vin[NLD];
-    auto issue_loads = [&](int t) { // input tile (origin y0-1-P1, x0-1-P1), zero padded (+8 zero floats: invalid taps read them)
-        int n, x0, y0;
-        tile_origin(t, n, x0, y0);
-        const float* xn = x + static_cast<size_t>(n) * p.H * p.W;
-#pragma unroll
-        for (int k = 0; k < NLD; ++k) {
-            const int idx = tid + k * 256;
-            const int r = idx / INP, c = idx - r * INP;
-            const int gy = y0 - 1 - P1 + r, gx = x0 - 1 - P1 + c;
-            vin[k] = 0.0f;
-            if (r < INH && c < INW && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) vin[k] = xn[static_cast<size_t>(gy) * p.W + gx];
-        }
-    };
-    auto store_input = [&]() {
-#pragma unroll
-        for (int k = 0; k < NLD; ++k)
-            if (tid + k * 256 < INH * INP + 8) s_in[tid + k * 256] = vin[k];
-    };
-
-    int tile = blockIdx.x;
-    if (tile >= ntiles) return;
-    SNNHIP_STAMP(0);
-    issue_loads(tile);
-    {
-        float4 u[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) u[k] = reinterpret_cast<const float4*>(wU)[tid + k * 256];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) reinterpret_cast<float4*>(s_U)[tid + k * 256] = u[k];
-    }
-    store_input();
-
-    // 5x5: the 7th K step would carry ONE tap (row 4, column 4) in a 4-deep MFMA -- 32 pipe cycles for 64 useful FMAs per lane group.  That tap goes
-    // to the VALU instead: every lane reads the input value under its own pixel and adds w[oc][24] * x to its four accumulators (4 FMAs, ~10 cycles)
-    #ifdef SNNHIP_ESPCN_TAP25_MFMA // experiment builds (tools/exp_one.sh): the round-3 form, all 7 steps on the matrix pipe
-    constexpr bool kValuTap = false;
-#else
-    constexpr bool kValuTap = K1 == 5;
-#endif
-    constexpr int KSM = kValuTap ? KS1 - 1 : KS1; // K steps on the matrix pipe
-    float a1[KSM];
-#pragma unroll
-    for (int s = 0; s < KSM; ++s) a1[s] = wA1[s * 64 + lane];
-    float sc1[4], sh1[4], sc2[4], sh2[4], w24[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        sc1[r] = ep1[(4 * g + r) * 2];
-        sh1[r] = ep1[(4 * g + r) * 2 + 1];
-        sc2[r] = ep2[(4 * g + r) * 2];
-        sh2[r] = ep2[(4 * g + r) * 2 + 1];
-        w24[r] = kValuTap ? wA1[(KS1 - 1) * 64 + 4 * g + r] : 0.0f; // step 6 holds w[oc][24] at lane oc (its lane group 0)
-    }
-    const int rowTap = (g < K1 ? g : 0) * INP; // K-steps s < K1: tap row g (invalid g: zero weight, any initialised row)
-    const int lastTap = 4 * INP + g;           // K-steps s >= K1 (K1 == 5): tap row 4, col g (+4)
-    SNNHIP_STAMP(1);
-    __syncthreads();
-    SNNHIP_STAMP(2);
-
-  for (;;) {
-    int n, x0, y0;
-    tile_origin(tile, n, x0, y0);
-    const int next = tile + gridDim.x;
-    const bool more = next < ntiles;
-    // The two blocks of a CU (b and b + grid / 2: workgroups fill every CU's first slot before any second one) take turns at the higher wave priority,
-    // tile by tile -- conv2d_widep_f16.hip's rule, measured here as well: kernel A 75.4 -> 73.5 us in six of six ABAB pairs on one box (round 5), the
-    // headline 9.26 k -> 9.41 k images/s there.  Recorded as measured, not derived
-#ifndef SNNHIP_ESPCN_NO_PRIO_ALT // (experiment builds switch it off)
-    if (((tile / static_cast<int>(gridDim.x)) + (blockIdx.x >= (gridDim.x >> 1) ? 1 : 0)) & 1) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(0);
-#endif
-    if (more) issue_loads(next);
-    const bool border = x0 == 0 || y0 == 0 || x0 + TW >= p.W || y0 + TH >= p.H; // wave-uniform
-
-    // ---- phase 1: conv1 over the C1H x C1W region, pixels flattened into 16-wide groups; wave wv owns groups
-    // [wv*GPW, wv*GPW+GPW), two per iteration (two independent MFMA chains).  The LDS operands of iteration it+1 are
-    // fetched before the MFMAs of iteration it (the loop is fully unrolled, so this is register renaming, not copies).
-    {
-        float bv[2][U][KS1]; // (5x5: slot KS1 - 1 holds the input value of the VALU tap)
-        int rr[2][U], cc[2][U];
-        bool valid[2][U];
-        auto fetch = [&](int it, int buf) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int grp = wv * GPW + it * U + u;
-                const int pi = grp * 16 + px;
-                valid[buf][u] = (it * U + u < GPW) && pi < C1H * C1W;
-                const int pc = valid[buf][u] ? pi : 0;
-                rr[buf][u] = pc / C1W;
-                cc[buf][u] = pc - rr[buf][u] * C1W;
-                const float* src = s_in + rr[buf][u] * INP + cc[buf][u];
-                const float* srcRow = src + rowTap;
-#pragma unroll
-                for (int s = 0; s < KSM; ++s) bv[buf][u][s] = s < K1 ? srcRow[s] : src[lastTap + 4 * (s - K1)];
-                if (kValuTap) bv[buf][u][KS1 - 1] = src[4 * INP + 4]; // tap (4, 4) under this lane's pixel, whatever its lane group
-            }
-        };
-        fetch(0, 0);
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int cur = it & 1;
-            if (it + 1 < NIT) fetch(it + 1, cur ^ 1);
-            f32x4 acc[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[0], bv[cur][u][0], f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
-#pragma unroll
-            for (int s = 1; s < KSM; ++s)
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s], bv[cur][u][s], acc[u], 0, 0, 0);
-            if (kValuTap) {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) acc[u][k] = fmaf(w24[k], bv[cur][u][KS1 - 1], acc[u][k]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                float4 o;
-                o.x = act_mode<AM>(p.act1, fmaf(acc[u][0], sc1[0], sh1[0]));
-                o.y = act_mode<AM>(p.act1, fmaf(acc[u][1], sc1[1], sh1[1]));
-                o.z = act_mode<AM>(p.act1, fmaf(acc[u][2], sc1[2], sh1[2]));
-                o.w = act_mode<AM>(p.act1, fmaf(acc[u][3], sc1[3], sh1[3]));
-                if (border) { // only tiles on the image border have conv1 pixels outside the image: they are conv2's zero padding
-                    const int gy = y0 - 1 + rr[cur][u], gx = x0 - 1 + cc[cur][u];
-                    if (!(gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)) o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                }
-                if (valid[cur][u]) {
-                    const int c = cc[cur][u];
-                    const int pl = rr[cur][u] * C1P + (c & 1) * HALFP + (c >> 1);
-                    const int slot = g ^ (((pl >> 2) & 1) << 1);
-                    *reinterpret_cast<float4*>(s_c1 + pl * 16 + slot * 4) = o;
-                }
-            }
-        }
-    }
-    SNNHIP_STAMP(3);
-    __syncthreads(); // c1 complete; every wave is done reading s_in
-    if (more) store_input();
-    SNNHIP_STAMP(4);
-
-    // ---- phase 2: Winograd conv2.  Lane = (tile column t = px, channel quad g).
-    // c1 pixel (r, c) lives at linear pixel pl = r*C1P + (c&1)*HALFP + (c>>1), 16-byte slot  q ^ 2*((pl>>2)&1).
-    // Patch element (i, j) of tile (trow, t): pl = (2 trow + i)*C1P + (j&1)*HALFP + t + (j>>1).  C1P = 40 leaves bit 2 of
-    // pl alone, HALFP = 20 flips it, so the swizzle term is one of two per-lane values and everything else is an
-    // immediate offset: 4 address registers serve all 16 patch loads.
-    const float* uBase = s_U + (px * 4 + (g ^ (((px >> 2) & 1) << 1))) * 4; // + pos*256: U[pos][oc = px][ic = 4g..4g+3]
-    const float* dBase[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int t = px + (j >> 1);
-        const int slot = g ^ ((((t >> 2) & 1) ^ (j & 1)) << 1);
-        dBase[j] = s_c1 + (wv * (2 * GROUPS2) * C1P + (j & 1) * HALFP + t) * 16 + slot * 4;
-    }
-    float* yn = y + static_cast<size_t>(n) * p.H * p.W * 16;
-#pragma unroll
-    for (int gi = 0; gi < GROUPS2; ++gi) {
-        const int trow = wv * GROUPS2 + gi; // tile row: output rows 2*trow, 2*trow+1; patch rows 2*trow .. 2*trow+3 of the c1 tile
-        f32x4 d[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) d[i][j] = *reinterpret_cast<const f32x4*>(dBase[j] + (2 * gi + i) * C1P * 16);
-        f32x4 Y[2][2];
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-            // (d B)[:, nu], then V[xi] = (Bt (dB))[xi]
-            f32x4 e[4], V[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                e[i] = nu == 0 ? d[i][0] - d[i][2] : nu == 1 ? d[i][1] + d[i][2] : nu == 2 ? d[i][2] - d[i][1] : d[i][1] - d[i][3];
-            V[0] = e[0] - e[2];
-            V[1] = e[1] + e[2];
-            V[2] = e[2] - e[1];
-            V[3] = e[1] - e[3];
-            f32x4 u4[4], m[4];
-#pragma unroll
-            for (int xi = 0; xi < 4; ++xi) u4[xi] = *reinterpret_cast<const f32x4*>(uBase + (xi * 4 + nu) * 256);
-#pragma unroll
-            for (int xi = 0; xi < 4; ++xi) m[xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(u4[xi][0], V[xi][0], f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
-#pragma unroll
-            for (int kk = 1; kk < 4; ++kk)
-#pragma unroll
-                for (int xi = 0; xi < 4; ++xi) m[xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(u4[xi][kk], V[xi][kk], m[xi], 0, 0, 0);
-            // output transform: T[a] = (At M)[a][nu];  Y[a][b] += T[a] * At[b][nu]
-            const f32x4 T0 = m[0] + m[1] + m[2];
-            const f32x4 T1 = m[1] - m[2] - m[3];
-            if (nu == 0) {
-                Y[0][0] = T0;
-                Y[1][0] = T1;
-            } else if (nu == 1) {
-                Y[0][0] += T0;
-                Y[1][0] += T1;
-                Y[0][1] = T0;
-                Y[1][1] = T1;
-            } else if (nu == 2) {
-                Y[0][0] += T0;
-                Y[1][0] += T1;
-                Y[0][1] -= T0;
-                Y[1][1] -= T1;
-            } else {
-                Y[0][1] -= T0;
-                Y[1][1] -= T1;
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-                const int gy = y0 + 2 * trow + a, gx = x0 + 2 * px + bb;
-                if (!border || (gy < p.H && gx < p.W)) {
-                    float4 o;
-                    o.x = act_mode<AM>(p.act2, fmaf(Y[a][bb][0], sc2[0], sh2[0]));
-                    o.y = act_mode<AM>(p.act2, fmaf(Y[a][bb][1], sc2[1], sh2[1]));
-                    o.z = act_mode<AM>(p.act2, fmaf(Y[a][bb][2], sc2[2], sh2[2]));
-                    o.w = act_mode<AM>(p.act2, fmaf(Y[a][bb][3], sc2[3], sh2[3]));
-                    *reinterpret_cast<float4*>(yn + (static_cast<size_t>(gy) * p.W + gx) * 16 + g * 4) = o;
-                }
-            }
-    }
-    SNNHIP_STAMP(5);
-    if (!more) break;
-    __syncthreads(); // c1 consumed, next input tile visible
-    tile = next;
-  }
-    SNNHIP_STAMP(6);
+template <int K1, int TH, int AM, int WPS>
+__global__ __launch_bounds__(256, WPS) void conv_kxk_c1o16_wino3x3_c16o16_u8_kernel(FusedAParams p, U8InCfg qin, const unsigned char* __restrict__ x,
+                                                                              const float* __restrict__ wA1, const float* __restrict__ wU,
+                                                                              const float* __restrict__ ep1, const float* __restrict__ ep2,
+                                                                              float* __restrict__ y) {
+    typedef unsigned char TIn;
+#include "espcn_wino_a_body.h"
 }
 
 struct FusedBParams {
@@ -533,106 +289,25 @@ struct FusedBParams {
 // conv 3x3 (16 -> 4, zero padding 1) + act, then depth-to-space(2) + tanh.  One thread = one input-resolution pixel
 // = a 2x2 block of the output image.  LDS tile [TH+2][TW+2] pixels, 64 B each, 16-byte slots XOR-swizzled (conflict-free
 // b128 reads for 64 consecutive pixels, 21.8 KB per block -> 7 blocks/CU); weights are wave-uniform => scalar loads, FMAs take them as SGPR operands.
+// Chain rule B8: the output frame quantised in the epilogue, q = quantize_u8(o, scale, offset) (snnhip_u8_out_plan_create's map)
+struct U8OutCfg {
+    float scale, offset;
+};
+
+// rule B's kernel (fp32 output) and rule B8's (8-bit output): one body, espcn_d2s_b_body.h
 template <int TW, int TH, bool SIMPLE>
 __global__ __launch_bounds__(256) void conv3x3_c16o4_d2s_tanh_kernel(FusedBParams p, const float* __restrict__ x, const float* __restrict__ w,
                                                                      const float* __restrict__ ep, float* __restrict__ y) {
-    // LDS tile as four channel-quad PLANES, s_x[q][pixel] float4: a wave's 64 pixels (2 rows x 32) read 512 contiguous bytes per row from one
-    // plane -- conflict-free without a swizzle -- and every operand address of the tap loop is ONE per-thread base + a wave-uniform tap offset + a
-    // compile-time plane offset.  (The kernel is VALU-issue bound: rocprofv3 counted 708 VALU instructions per wave of which 288 are the
-    // packed FMAs; the previous [pixel][quad ^ swizzle] layout spent 21 VALU instructions per tap on addresses, this one 2.)
-    constexpr int TWH = TW + 2, THH = TH + 2, PLANE = THH * TWH * 4; // floats per plane
-    static_assert(TW * TH == 256, "one thread per pixel");
-    __shared__ __attribute__((aligned(16))) float s_x[4 * PLANE];
+    typedef float TOut;
+    constexpr U8OutCfg qout{0.0f, 0.0f};
+#include "espcn_d2s_b_body.h"
+}
 
-    const int tid = threadIdx.x;
-    // tile decode on the scalar unit: the divisions by tilesX / tilesY are mul-hi by host-computed magic numbers (a run-time integer division of
-    // a uniform value still compiles to ~20 VALU instructions of float reciprocal arithmetic, and this kernel is VALU-issue bound)
-    const unsigned bid = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(xcd_tile_order(blockIdx.x, gridDim.x)));
-    const unsigned bq = p.tilesX == 1 ? bid : __umulhi(bid, p.magicX);
-    const int tx = static_cast<int>(bid - bq * p.tilesX);
-    const unsigned n_u = p.tilesY == 1 ? bq : __umulhi(bq, p.magicY);
-    const int ty = static_cast<int>(bq - n_u * p.tilesY), n = static_cast<int>(n_u);
-    const int x0 = tx * TW, y0 = ty * TH;
-    const float* xn = x + static_cast<size_t>(n) * p.H * p.W * 16;
-
-    {
-        const bool interior = x0 >= 1 && y0 >= 1 && x0 + TW + 1 <= p.W && y0 + TH + 1 <= p.H; // block-uniform: 95 % of the tiles at 1080p
-        if (interior) {
-            // no bounds tests, no zero fill, no index arithmetic: thread t < 4*TWH owns float4 t of EVERY halo row (a row of the tile is 4*TWH
-            // contiguous float4 in memory), so its THH loads are one pointer walked by the image pitch and its THH LDS stores one offset walked by
-            // the tile pitch.  The other threads (the fourth wave entirely) skip the staging: fewer instructions issued in total is what counts.
-            if (tid < 4 * TWH) {
-                const float* src = xn + (static_cast<size_t>(y0 - 1) * p.W + (x0 - 1)) * 16 + tid * 4;
-                float4 rowv[THH];
-#pragma unroll
-                for (int rr = 0; rr < THH; ++rr) rowv[rr] = *reinterpret_cast<const float4*>(src + static_cast<size_t>(rr) * p.W * 16);
-                float* dst = s_x + (tid & 3) * PLANE + (tid >> 2) * 4;
-#pragma unroll
-                for (int rr = 0; rr < THH; ++rr) *reinterpret_cast<float4*>(dst + rr * TWH * 4) = rowv[rr];
-            }
-        } else {
-            constexpr int NLD = (THH * TWH * 4 + 255) / 256;
-            float4 v[NLD];
-#pragma unroll
-            for (int k = 0; k < NLD; ++k) { // every load of the halo tile is in flight before the first LDS write
-                const int idx = tid + k * 256;
-                const int q = idx & 3, pix = idx >> 2;
-                const int r = pix / TWH, c = pix - r * TWH;
-                const int gy = y0 - 1 + r, gx = x0 - 1 + c;
-                v[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (idx < THH * TWH * 4 && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
-                    v[k] = *reinterpret_cast<const float4*>(xn + (static_cast<size_t>(gy) * p.W + gx) * 16 + q * 4);
-            }
-#pragma unroll
-            for (int k = 0; k < NLD; ++k) {
-                const int idx = tid + k * 256;
-                if (idx < THH * TWH * 4) *reinterpret_cast<float4*>(s_x + (idx & 3) * PLANE + (idx >> 2) * 4) = v[k];
-            }
-        }
-    }
-    __syncthreads();
-
-    const int c = tid % TW, r = tid / TW;
-    // Packed fp32 FMAs: a wave64 v_fma_f32 occupies the VALU for 4 cycles on this kernel (measured: 20.3 M VALU instructions
-    // = 20.6 M quad-cycles busy), v_pk_fma_f32 retires two FMAs per lane in the same slot.  The accumulators are kept as two
-    // float2 so that every FMA is a v_pk_fma_f32 with the weight pair in an SGPR pair.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc01 = {0.0f, 0.0f}, acc23 = {0.0f, 0.0f};
-    const float* base = s_x + (r * TWH + c) * 4;
-    // one tap (64 uniform weights = 64 SGPRs) per iteration: unrolling further only spills SGPRs.  (Prefetching tap t+1's operand quads from
-    // LDS does not pay: LDS and scalar loads share lgkmcnt, so the wait for the next weights also waits for the prefetch.)
-#pragma unroll 1
-    for (int fy = 0; fy < 3; ++fy) {
-#pragma unroll 1
-        for (int fx = 0; fx < 3; ++fx) {
-            const int tap = fy * 3 + fx;
-            const float* src = base + (fy * TWH + fx) * 4; // wave-uniform offset
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 xv = *reinterpret_cast<const float4*>(src + q * PLANE); // compile-time plane offset -> ds_read_b128 offset:
-                const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float* wr = w + (tap * 16 + q * 4 + i) * 4; // uniform address -> s_load
-                    const f32x2 xx = {xs[i], xs[i]};
-                    const f32x2 w01 = {wr[0], wr[1]}, w23 = {wr[2], wr[3]};
-                    acc01 = __builtin_elementwise_fma(xx, w01, acc01);
-                    acc23 = __builtin_elementwise_fma(xx, w23, acc23);
-                }
-            }
-        }
-    }
-    const float acc[4] = {acc01.x, acc01.y, acc23.x, acc23.y};
-    const int gy = y0 + r, gx = x0 + c;
-    if (gy < p.H && gx < p.W) {
-        float o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = fast_tanh(apply_act<SIMPLE>(p.act, fmaf(acc[k], ep[2 * k], ep[2 * k + 1]), 0.0f));
-        float* yn = y + static_cast<size_t>(n) * (2 * p.H) * (2 * p.W);
-        // channel 2*dy+dx -> output pixel (2y+dy, 2x+dx)  (depth_to_space, fs_subpixel.glsl:41-64)
-        *reinterpret_cast<float2*>(yn + static_cast<size_t>(2 * gy) * (2 * p.W) + 2 * gx) = make_float2(o[0], o[1]);
-        *reinterpret_cast<float2*>(yn + static_cast<size_t>(2 * gy + 1) * (2 * p.W) + 2 * gx) = make_float2(o[2], o[3]);
-    }
+template <int TW, int TH, bool SIMPLE>
+__global__ __launch_bounds__(256) void conv3x3_c16o4_d2s_tanh_u8_kernel(FusedBParams p, U8OutCfg qout, const float* __restrict__ x, const float* __restrict__ w,
+                                                                        const float* __restrict__ ep, unsigned char* __restrict__ y) {
+    typedef unsigned char TOut;
+#include "espcn_d2s_b_body.h"
 }
 
 // Kernel B, Winograd variant (default): conv 3x3 (16 -> 4) as F(2x2, 3x3) on the matrix cores, then depth-to-space(2) + tanh.
@@ -916,6 +591,9 @@ struct ChainPlan : snnhip_plan {
         FusedBParams b{};
         int k1 = 5;
         bool wino = false; // FUSED_A / FUSED_B: the 3x3 conv as Winograd F(2x2,3x3) (default) or direct (SNNHIP_ESPCN_A / _B = direct)
+        bool u8in = false, u8out = false; // rule A8: FUSED_A reads the 8-bit frame; rule B8: FUSED_B writes one
+        U8InCfg qin{0.0f, 0.0f};
+        U8OutCfg qout{0.0f, 0.0f};
         float *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr, *w3 = nullptr, *e3 = nullptr;
         alignas(8) char streamCfg[kStreamCfgBytes] = {};
         int outDims[4] = {0, 0, 0, 0};
@@ -969,7 +647,11 @@ struct ChainPlan : snnhip_plan {
                 dim3 grid(ntilesA < slotsA ? ntilesA : slotsA); // persistent: W_WPS blocks per CU walk the tile list
                 const bool simple = act_is_simple(s.a.act1.act) && act_is_simple(s.a.act2.act);
 #define SNNHIP_LAUNCH_W(K, AM)                                                                                                                        \
-    SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_kernel<K, W_TH, AM, W_WPS>), grid, dim3(256), 0, ctx->stream, evStart, evStop, s.a, src->data, \
+    if (s.u8in)                                                                                                                                       \
+        SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_u8_kernel<K, W_TH, AM, W_WPS>), grid, dim3(256), 0, ctx->stream, evStart, evStop, s.a, s.qin, \
+                         reinterpret_cast<const unsigned char*>(src->data), s.w1, s.w2, s.e1, s.e2, dst->data);                                      \
+    else                                                                                                                                              \
+        SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_kernel<K, W_TH, AM, W_WPS>), grid, dim3(256), 0, ctx->stream, evStart, evStop, s.a, src->data, \
                           s.w1, s.w2, s.e1, s.e2, dst->data)
                 const int am = (s.a.act1.act == SNNHIP_ACT_RELU && s.a.act2.act == SNNHIP_ACT_RELU) ? 2 : (simple ? 1 : 0);
                 if (s.k1 == 5) {
@@ -1006,7 +688,14 @@ struct ChainPlan : snnhip_plan {
                 SNNHIP_CHECK_HIP(hipGetLastError());
             } else {
                 dim3 grid(s.b.tilesX * s.b.tilesY * s.b.N);
-                if (act_is_simple(s.b.act.act)) {
+                unsigned char* dst8 = reinterpret_cast<unsigned char*>(dst->data);
+                if (s.u8out && act_is_simple(s.b.act.act)) {
+                    SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u8_kernel<B_TW, B_TH, true>), grid, dim3(256), 0, ctx->stream, evStart, evStop, s.b, s.qout,
+                                          src->data, s.w1, s.e1, dst8);
+                } else if (s.u8out) {
+                    SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u8_kernel<B_TW, B_TH, false>), grid, dim3(256), 0, ctx->stream, evStart, evStop, s.b, s.qout,
+                                          src->data, s.w1, s.e1, dst8);
+                } else if (act_is_simple(s.b.act.act)) {
                     SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_kernel<B_TW, B_TH, true>), grid, dim3(256), 0, ctx->stream, evStart, evStop, s.b,
                                           src->data, s.w1, s.e1, dst->data);
                 } else {
@@ -1535,6 +1224,43 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
         a.bytes = both->bytes;
         chain->steps.erase(chain->steps.begin() + static_cast<long>(k) + 1);
     }
+    // ---- rules A8 / B8: an 8-bit frame conversion next to a fused ESPCN kernel moves into it.  A8: u8_in (1 channel, fp32) directly in front of
+    // rule A's Winograd kernel -> the kernel stages bytes and normalises them (SNNHIP_ESPCN_A=direct keeps the separate launch).  B8: u8_out
+    // (1 channel, fp32) directly behind rule B's direct kernel -> its epilogue quantises and stores bytes (SNNHIP_ESPCN_B=wino and rule C keep the
+    // separate launch).  Both compute the stand-alone plans' expressions, so the fused chain's bytes are the unfused chain's.  Only at the chain's
+    // ends: an 8-bit tensor is never one of its intermediates.
+    for (size_t k = 0; rc == SNNHIP_OK && k + 1 < chain->steps.size(); ++k) {
+        ChainPlan::Step &a = chain->steps[k], &b = chain->steps[k + 1];
+        snnhip_u8_in_desc ui;
+        snnhip_u8_out_desc uo;
+        if (k == 0 && a.kind == ChainPlan::PLAIN && b.kind == ChainPlan::FUSED_A && b.wino && !b.u8in && u8_in_plan_desc(a.plain, &ui) && ui.C == 1 &&
+            ui.dtype == SNNHIP_F32) {
+            b.u8in = true;
+            b.qin = U8InCfg{ui.means[0], ui.norms[0]};
+            const size_t at = b.desc.find("kernel=conv_kxk_c1o16_wino3x3_c16o16_kernel");
+            if (at != std::string::npos) b.desc.replace(at, strlen("kernel=conv_kxk_c1o16_wino3x3_c16o16_kernel"), "kernel=conv_kxk_c1o16_wino3x3_c16o16_u8_kernel");
+            b.desc = "u8_in(1ch) + " + b.desc;
+            b.flops += a.flops;
+            b.bytes -= 3.0 * ui.N * ui.H * ui.W; // 1 byte per input pixel instead of 4
+            chain->steps.erase(chain->steps.begin() + static_cast<long>(k));
+            ++fusedCount;
+            --k;
+            continue;
+        }
+        if (k + 2 == chain->steps.size() && a.kind == ChainPlan::FUSED_B && !a.wino && !a.u8out && b.kind == ChainPlan::PLAIN && u8_out_plan_desc(b.plain, &uo) && uo.C == 1 &&
+            uo.dtype == SNNHIP_F32) {
+            a.u8out = true;
+            a.qout = U8OutCfg{uo.scale[0], uo.offset[0]};
+            const size_t at = a.desc.find("kernel=conv3x3_c16o4_d2s_tanh_kernel");
+            if (at != std::string::npos) a.desc.replace(at, strlen("kernel=conv3x3_c16o4_d2s_tanh_kernel"), "kernel=conv3x3_c16o4_d2s_tanh_u8_kernel");
+            a.desc += " + u8_out(1ch)";
+            a.flops += b.flops;
+            a.bytes -= 3.0 * uo.N * uo.H * uo.W; // 1 byte per output pixel instead of 4
+            memcpy(a.outDims, b.outDims, sizeof(a.outDims));
+            chain->steps.erase(chain->steps.begin() + static_cast<long>(k) + 1);
+            ++fusedCount;
+        }
+    }
     if (rc == SNNHIP_OK && fusedCount == 0) {
         set_error("chain fusion: no rule matches these %d plans", n);
         rc = SNNHIP_E_UNSUPPORTED;
@@ -1559,6 +1285,8 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
         chain->flops += plans[i]->flops;
         chain->bytes += plans[i]->bytes;
     }
+    chain->u8Input = plans[0]->u8Input && !plans[0]->anyDtype; // a chain that starts with u8_in reads the 8-bit frame, one that ends with u8_out writes one
+    chain->u8Output = plans[n - 1]->u8Output;
     std::string d = "chain{";
     for (size_t i = 0; i < chain->steps.size(); ++i) d += (i ? " -> " : "") + chain->steps[i].desc;
     chain->desc = d + "}";

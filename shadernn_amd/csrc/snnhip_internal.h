@@ -139,7 +139,8 @@ struct snnhip_plan {
     int numInputs = 1;
     int dtype = SNNHIP_F32;   // element type of the tensors this plan runs on ...
     bool anyDtype = false;    // ... unless it adapts to the tensors of each call (element-wise / pooling / shape operators)
-    bool u8Input = false;     // snnhip_image_u8_plan_create: the only plan that reads SNNHIP_U8 tensors
+    bool u8Input = false;     // reads a SNNHIP_U8 tensor: snnhip_image_u8_plan_create / snnhip_u8_in_plan_create, or a chain that starts with the latter
+    bool u8Output = false;    // writes a SNNHIP_U8 tensor: snnhip_u8_out_plan_create, or a chain that ends with it
     std::string desc;
     double flops = 0, bytes = 0; // algorithmic cost in SURVEY 8(d)'s accounting (a fused plan: the sum over the layers it replaces)
     // what THIS plan's own launches have to move through HBM (inputs once + outputs once + weights): differs from `bytes` only for fused plans,
@@ -291,6 +292,9 @@ struct NormFoldTarget {
 bool instancenorm_fold_target(snnhip_plan* normPlan, NormFoldTarget* t);
 // eltwise_pool.hip: identify an InstanceNorm plan / run its fold + normalise passes in place from a convolution's tile statistics
 bool instancenorm_plan_desc(const snnhip_plan* plan, snnhip_instancenorm_desc* d);
+// frame_u8.hip: identify the 8-bit frame conversions (chain rules A8 / B8 fold them into the ESPCN kernels)
+bool u8_in_plan_desc(const snnhip_plan* plan, snnhip_u8_in_desc* d);
+bool u8_out_plan_desc(const snnhip_plan* plan, snnhip_u8_out_desc* d);
 // eltwise_pool.hip: identify a Pooling plan (resolved output dims included)
 bool pool2d_plan_desc(const snnhip_plan* plan, snnhip_pool2d_desc* d);
 // conv2d_stem_f32.hip, chain rule J: Conv2D 7x7 stride 2 of an RGB image -> MaxPooling2D 3x3 stride 2 (the head of ResNet-18) as one launch: the pooling

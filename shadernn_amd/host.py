@@ -17,6 +17,9 @@ SIGNATURES = {
     "snn_model_create2": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "snn_model_create3": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "snn_model_create4": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "snn_model_create5": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_upload_frame_u8": (C.c_int, [_P, _P]),
+    "snn_model_download_frame_u8": (C.c_int, [_P, _P]),
     "snn_model_batch": (C.c_int, [_P]),
     "snn_model_hip_ctx": (_P, [_P]),
     "snn_model_output_tensor": (_P, [_P]),
@@ -119,17 +122,44 @@ def yolo_decode(head_coarse, head_fine, net_size=416, max_rows=100):
     return rows[:n].copy()
 
 
+class FrameIO(C.Structure):
+    """snn_frame_io (include/snn_c.h): 8-bit frame formats at the model's ends and their affine maps."""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("in_means", C.c_float * 4), ("in_norms", C.c_float * 4), ("out_scale", C.c_float * 4),
+                ("out_offset", C.c_float * 4)]
+
+
+FRAME_FORMATS = {None: 0, "float": 0, "R8": 1, "RGB8": 3, "RGBA8": 4}  # SNN_IO_*
+
+
 class Model:
     """MixedInferenceCore::create(context, jsonFile, options) + run(), one W x H x C input image."""
 
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
-                 batch=1):
-        """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis."""
+                 batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
+                 out_offset=(0, 0, 0, 0)):
+        """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
+        input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
+        output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out."""
         self.h = _P()
-        assert lib().snn_model_create4(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half),
-                                       int(capture_graph), int(batch), C.byref(self.h)) == 0
+        io = FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], (C.c_float * 4)(*in_means), (C.c_float * 4)(*in_norms),
+                     (C.c_float * 4)(*out_scale), (C.c_float * 4)(*out_offset))
+        assert lib().snn_model_create5(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half),
+                                       int(capture_graph), int(batch), C.byref(io), C.byref(self.h)) == 0
         self.batch = batch
         self.in_shape = (h, w, c) if batch == 1 else (batch, h, w, c)
+
+    def upload_frame(self, img):
+        """uint8 [batch x] H x W x C into the model's 8-bit input frame (no per-call allocation)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8).reshape(self.in_shape)
+        assert lib().snn_model_upload_frame_u8(self.h, img.ctypes.data_as(_P)) == 0
+
+    def output_frame(self):
+        """the model's 8-bit output frame of the last run, uint8 [batch x] H x W x C"""
+        d = (C.c_int * 3)()
+        lib().snn_model_output_dims(self.h, C.byref(d))
+        out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=np.uint8)
+        assert lib().snn_model_download_frame_u8(self.h, out.ctypes.data_as(_P)) == 0
+        return out
 
     def upload(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.in_shape)

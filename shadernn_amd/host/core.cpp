@@ -27,6 +27,8 @@ std::unique_ptr<MixedInferenceCore> MixedInferenceCore::create(GpuContext* conte
     static_cast<InferenceGraph&>(cp) = dp::generateInferenceGraph(layers, options);
     cp.dumpOutputs = dumpOutputs;
     cp.fuseChains = options.fuseChains;
+    cp.outputFormat = options.desiredOutputFormat; // R8 / RGB8 / RGBA8: an 8-bit output frame (identity scale, zero offset)
+    cp.halfTensors = options.preferrHalfPrecision;
     return create(context, cp);
 }
 
@@ -92,6 +94,20 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         }
         if (cp.profiling) stage.timer.reset(backend->createDeviceTimer(layer.name));
     }
+    const bool frameIn = isFrameFormat(cp.inputsDesc[0].format), frameOut = isFrameFormat(cp.outputFormat);
+    if (frameIn || frameOut) {
+        auto* hb = dynamic_cast<dp::HipBackend*>(backend);
+        SNN_CHK(hb && stages.back().stageOutputs.size() > 0);
+        const ImageTexture& o = stages.back().stageOutputs[0];
+        const auto& id = cp.inputsDesc[0];
+        if (frameIn && getColorFormatDesc(id.format).ch != id.channels) SNN_RIP("input format %s for a %u-channel input", getColorFormatDesc(id.format).name, id.channels);
+        if (frameOut && getColorFormatDesc(cp.outputFormat).ch != o.channels())
+            SNN_RIP("output format %s for a %u-channel output", getColorFormatDesc(cp.outputFormat).name, static_cast<unsigned>(o.channels()));
+        hb->initFrameIO(frameIn, frameOut, static_cast<int>(o.batch()), static_cast<int>(id.height), static_cast<int>(id.width), static_cast<int>(id.channels),
+                        static_cast<int>(o.height()), static_cast<int>(o.width()), static_cast<int>(o.channels()), cp.halfTensors ? SNNHIP_F16 : SNNHIP_F32,
+                        cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset);
+        frameBackend = hb;
+    }
     backend->finalizeStages(stages, cp.dumpOutputs, cp.fuseChains);
     graphUsable = cp.captureGraph && !cp.dumpOutputs && !cp.profiling;
     for (auto& s : stages)
@@ -113,6 +129,9 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
     }
     return true;
 }
+
+snnhip_tensor* MixedInferenceCore::frameInput() const { return frameBackend ? frameBackend->frameInput() : nullptr; }
+snnhip_tensor* MixedInferenceCore::frameOutput() const { return frameBackend ? frameBackend->frameOutput() : nullptr; }
 
 void MixedInferenceCore::run(RunParameters& rp) { // core.cpp:97-245
     SNN_ASSERT(rp.inputImages && rp.inputImages->size() > 0);
@@ -161,6 +180,7 @@ void MixedInferenceCore::run(RunParameters& rp) { // core.cpp:97-245
         if (s.timer) s.timer->stop();
     };
     const bool sideBySide = !cp.profiling && !cp.dumpOutputs; // per-stage timers and dumps want one stream and the reference's order
+    if (frameBackend && !replayed) frameBackend->runFrameIn((*rp.inputImages)[0]); // (nothing when the conversion was folded into a fused plan)
     for (size_t i = 0; i < stages.size() && !replayed; i++) {
         auto& s = stages[i];
         if (s.layer->isInputLayer) continue;
@@ -193,6 +213,7 @@ void MixedInferenceCore::run(RunParameters& rp) { // core.cpp:97-245
         }
         runStage(s);
     }
+    if (frameBackend && !replayed) frameBackend->runFrameOut(stages.back().stageOutputs[0]);
     if (recordingNow) { // the loop above only recorded: submit it now
         if (!backend->endRecord() || !backend->replay()) SNN_RIP("hipGraph capture of the inference failed: %s", snnhip_last_error());
     }

@@ -22,12 +22,14 @@ HipRenderPass::~HipRenderPass() {
 
 void HipRenderPass::run() {
     if (skip) return;
+    const snnhip_tensor* in0 = rawInput ? rawInput : input->tensor();
+    snnhip_tensor* out = rawOutput ? rawOutput : output->tensor();
     if (extraInputs.empty()) {
-        hipChk(snnhip_plan_run(plan, input->tensor(), output->tensor()), "snnhip_plan_run");
+        hipChk(snnhip_plan_run(plan, in0, out), "snnhip_plan_run");
     } else {
-        std::vector<const snnhip_tensor*> ins{input->tensor()};
+        std::vector<const snnhip_tensor*> ins{in0};
         for (auto* t : extraInputs) ins.push_back(t->tensor());
-        hipChk(snnhip_plan_run_n(plan, ins.data(), static_cast<int>(ins.size()), output->tensor()), "snnhip_plan_run_n");
+        hipChk(snnhip_plan_run_n(plan, ins.data(), static_cast<int>(ins.size()), out), "snnhip_plan_run_n");
     }
 }
 
@@ -52,6 +54,32 @@ HipBackend::~HipBackend() {
     dropRecording();
     for (auto* p : chainPlans) snnhip_plan_destroy(p);
     replacedPasses.clear();
+    if (frameInPlan) snnhip_plan_destroy(frameInPlan);
+    if (frameOutPlan) snnhip_plan_destroy(frameOutPlan);
+    if (frameInT) snnhip_tensor_free(frameInT);
+    if (frameOutT) snnhip_tensor_free(frameOutT);
+}
+
+void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
+                             const float norms[4], const float scale[4], const float offset[4]) {
+    if (in) {
+        snnhip_u8_in_desc d{n, inH, inW, inC, dtype, {means[0], means[1], means[2], means[3]}, {norms[0], norms[1], norms[2], norms[3]}};
+        hipChk(snnhip_u8_in_plan_create(ctx, &d, &frameInPlan), "snnhip_u8_in_plan_create");
+        hipChk(snnhip_tensor_alloc(ctx, n, inH, inW, inC, SNNHIP_U8, &frameInT), "snnhip_tensor_alloc (input frame)");
+    }
+    if (out) {
+        snnhip_u8_out_desc d{n, outH, outW, outC, dtype, {scale[0], scale[1], scale[2], scale[3]}, {offset[0], offset[1], offset[2], offset[3]}};
+        hipChk(snnhip_u8_out_plan_create(ctx, &d, &frameOutPlan), "snnhip_u8_out_plan_create");
+        hipChk(snnhip_tensor_alloc(ctx, n, outH, outW, outC, SNNHIP_U8, &frameOutT), "snnhip_tensor_alloc (output frame)");
+    }
+}
+
+void HipBackend::runFrameIn(const ImageTexture& modelInput) {
+    if (frameInPlan && !frameInFused) hipChk(snnhip_plan_run(frameInPlan, frameInT, modelInput.tensor()), "snnhip_plan_run (u8_in)");
+}
+
+void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
+    if (frameOutPlan && !frameOutFused) hipChk(snnhip_plan_run(frameOutPlan, lastOutput.tensor(), frameOutT), "snnhip_plan_run (u8_out)");
 }
 
 // counterpart of VulkanBackend::initRenderPasses -> VulkanRenderPass ctor (vulkanBackend.cpp:43-78, vulkanRenderpass.cpp:103-178):
@@ -128,28 +156,77 @@ void HipBackend::finalizeStages(RenderStagesArray& stages, bool dumpOutputs, boo
         if (!ml || stages[i].layer->isInputLayer || stages[i].backend != Backend::Backend_GPU || ml->getRenderPasses().size() != 1) return nullptr;
         return dynamic_cast<HipRenderPass*>(ml->getRenderPasses()[0].get());
     };
-    const int n = static_cast<int>(stages.size());
-    std::vector<snnhip_graph_node> nodes(stages.size());
-    std::vector<snnhip_fused_node> fused(stages.size());
+    // node space: [u8_in frame conversion] + one node per stage + [u8_out frame conversion]; the conversions are ordinary plan nodes, so the
+    // chain rules see them (rules A8 / B8 fold them into the ESPCN kernels)
+    const int S = static_cast<int>(stages.size());
+    // the input layer's stage stands for model input 0 (its texture is the bound input): with an 8-bit input its node carries the u8_in plan, so the
+    // conversion sits right in front of its consumer in the linear run (a model without an input-layer stage gets an extra node 0 instead)
+    int inStage = -1;
+    for (size_t i = 0; i < stages.size() && inStage < 0; ++i)
+        if (stages[i].layer->isInputLayer && stages[i].layer->inputIndex == 0) inStage = static_cast<int>(i);
+    const int off = (frameInPlan && inStage < 0) ? 1 : 0;
+    const int inNode = frameInPlan ? (off ? 0 : inStage) : -1;
+    const int n = S + off + (frameOutPlan ? 1 : 0);
+    std::vector<snnhip_graph_node> gnodes(static_cast<size_t>(n));
+    std::vector<snnhip_fused_node> gfused(static_cast<size_t>(n));
+    auto setFrameInNode = [&]() {
+        if (inNode < 0) return;
+        gnodes[static_cast<size_t>(inNode)] = snnhip_graph_node{};
+        gnodes[static_cast<size_t>(inNode)].plan = frameInPlan;
+        gnodes[static_cast<size_t>(inNode)].n_inputs = 1;
+        gnodes[static_cast<size_t>(inNode)].inputs[0] = -1;
+    };
     for (size_t i = 0; i < stages.size(); ++i) {
-        snnhip_graph_node& nd = nodes[i];
+        snnhip_graph_node& nd = gnodes[i + static_cast<size_t>(off)];
         nd = snnhip_graph_node{};
         HipRenderPass* rp = passOf(i);
         nd.plan = rp ? rp->plan : nullptr;
-        nd.keep = (i + 1 == stages.size()) ? 1 : 0; // the model output (the reference binds the last stage's texture, core.cpp:219-227)
+        nd.keep = (i + 1 == stages.size() && !frameOutPlan) ? 1 : 0; // the model output (the reference binds the last stage's texture, core.cpp:219-227)
         if (stages[i].inputIds.size() > SNNHIP_GRAPH_MAX_INPUTS) nd.plan = nullptr;
         nd.n_inputs = nd.plan ? static_cast<int>(stages[i].inputIds.size()) : 0;
         for (int k = 0; k < nd.n_inputs; ++k) {
             const bool modelInput = stages[i].delayBindMask[static_cast<size_t>(k)] != 0;
-            nd.inputs[k] = modelInput ? -(stages[i].inputIds[static_cast<size_t>(k)] + 1) : stages[i].inputIds[static_cast<size_t>(k)];
+            const int id = stages[i].inputIds[static_cast<size_t>(k)];
+            nd.inputs[k] = modelInput ? ((inNode >= 0 && id == 0) ? inNode : -(id + 1)) : id + off;
         }
+    }
+    setFrameInNode();
+    if (frameOutPlan) {
+        snnhip_graph_node& nd = gnodes[static_cast<size_t>(n - 1)];
+        nd = snnhip_graph_node{};
+        nd.plan = frameOutPlan;
+        nd.n_inputs = 1;
+        nd.inputs[0] = S - 1 + off;
+        nd.keep = 1;
     }
     // an opaque stage (CPU layer, multi-pass layer) still consumes its producers: they must stay materialised
     for (size_t i = 0; i < stages.size(); ++i)
-        if (!nodes[i].plan)
-            for (size_t k = 0; k < stages[i].inputIds.size(); ++k)
-                if (!stages[i].delayBindMask[k] && stages[i].inputIds[k] >= 0) nodes[static_cast<size_t>(stages[i].inputIds[k])].keep = 1;
-    hipChk(snnhip_graph_fuse(ctx, nodes.data(), n, fused.data()), "snnhip_graph_fuse");
+        if (!gnodes[i + static_cast<size_t>(off)].plan)
+            for (size_t k = 0; k < stages[i].inputIds.size(); ++k) {
+                if (!stages[i].delayBindMask[k] && stages[i].inputIds[k] >= 0) gnodes[static_cast<size_t>(stages[i].inputIds[k] + off)].keep = 1;
+                if (inNode >= 0 && stages[i].delayBindMask[k] && stages[i].inputIds[k] == 0 && static_cast<int>(i) != inStage)
+                    gnodes[static_cast<size_t>(inNode)].keep = 1;
+            }
+    if (frameOutPlan && !gnodes[static_cast<size_t>(S - 1 + off)].plan) gnodes[static_cast<size_t>(S - 1 + off)].keep = 1;
+    hipChk(snnhip_graph_fuse(ctx, gnodes.data(), n, gfused.data()), "snnhip_graph_fuse");
+    frameInFused = inNode >= 0 && !gfused[static_cast<size_t>(inNode)].plan;
+    frameOutFused = frameOutPlan && gfused[static_cast<size_t>(n - 1)].owned;
+    // back to stage space: node 0 (the unfolded u8_in) is model input 0 again (it writes the model's input texture); a u8_out folded into a fused plan
+    // moves that plan onto the last stage, which then writes the output frame
+    auto toStage = [&](int id) { return id < 0 ? id : (off && id == 0) ? -1 : id - off; };
+    std::vector<snnhip_graph_node> nodes(stages.size());
+    std::vector<snnhip_fused_node> fused(stages.size());
+    for (size_t i = 0; i < stages.size(); ++i) {
+        nodes[i] = gnodes[i + static_cast<size_t>(off)];
+        fused[i] = gfused[i + static_cast<size_t>(off)];
+        if (frameOutFused && static_cast<int>(i) == S - 1) fused[i] = gfused[static_cast<size_t>(n - 1)];
+        for (int k = 0; k < nodes[i].n_inputs; ++k) nodes[i].inputs[k] = toStage(nodes[i].inputs[k]);
+        for (int k = 0; k < fused[i].n_inputs; ++k) fused[i].inputs[k] = toStage(fused[i].inputs[k]);
+    }
+    if (inStage >= 0 && !off && frameInPlan) { // the input layer's stage launches nothing itself: the u8_in node was only borrowed
+        nodes[static_cast<size_t>(inStage)] = snnhip_graph_node{};
+        fused[static_cast<size_t>(inStage)] = snnhip_fused_node{};
+    }
     // which texture carries input `id` of a fused plan: the stage output, or (model inputs, bound at run()) the input slot of the stage that named it
     auto textureOf = [&](size_t groupLast, int id) -> ImageTexture* {
         if (id >= 0) return &stages[static_cast<size_t>(id)].stageOutputs[0];
@@ -175,6 +252,9 @@ void HipBackend::finalizeStages(RenderStagesArray& stages, bool dumpOutputs, boo
         replacedPasses.push_back(ml->getRenderPasses()[0]); // its plan may still be launched by the fused one (unfused steps of a chain)
         auto np = std::make_shared<HipRenderPass>(fused[i].plan, textureOf(i, fused[i].inputs[0]), rp->output, rp->name + " (+fused)", false);
         for (int k = 1; k < fused[i].n_inputs; ++k) np->extraInputs.push_back(textureOf(i, fused[i].inputs[k]));
+        if (frameInFused && gfused[static_cast<size_t>(frameOutFused && static_cast<int>(i) == S - 1 ? n - 1 : static_cast<int>(i) + off)].inputs[0] == -1)
+            np->rawInput = frameInT; // (in node space, -1 = the u8_in node's own input: the 8-bit frame)
+        if (frameOutFused && static_cast<int>(i) == S - 1) np->rawOutput = frameOutT;
         ml->getRenderPasses()[0] = np;
         char buf[512];
         snnhip_plan_describe(fused[i].plan, buf, sizeof(buf));

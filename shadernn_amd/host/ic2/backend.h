@@ -88,6 +88,8 @@ public:
     std::string name;
     bool owns;
     bool skip = false; // fused into an earlier pass
+    const snnhip_tensor* rawInput = nullptr; // HIP extension: the 8-bit input frame a fused plan reads instead of `input` (rule A8)
+    snnhip_tensor* rawOutput = nullptr;      // ... and the 8-bit output frame it writes instead of `output` (rule B8)
 };
 
 class HipBackend : public DeviceBackend {
@@ -107,8 +109,19 @@ public:
     void joinSide() override;
     bool groupBegin() override;
     void groupEnd() override;
+    // 8-bit frame I/O (MixedInferenceCore::CreationParameters::outputFormat / inputsDesc[0].format): called before finalizeStages.  The conversion
+    // plans become nodes of the fusion graph; runFrameIn / runFrameOut launch whatever was not folded into a stage's fused plan.
+    void initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
+                     const float norms[4], const float scale[4], const float offset[4]);
+    void runFrameIn(const ImageTexture& modelInput);
+    void runFrameOut(const ImageTexture& lastOutput);
+    snnhip_tensor* frameInput() const { return frameInT; }
+    snnhip_tensor* frameOutput() const { return frameOutT; }
 
 private:
+    snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned
+    snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // owned, SNNHIP_U8
+    bool frameInFused = false, frameOutFused = false;
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

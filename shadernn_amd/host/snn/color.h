@@ -2,7 +2,8 @@
 #pragma once
 #include <cstddef>
 namespace snn {
-enum class ColorFormat { NONE, RGBA32F, RGBA16F, R32F };
+enum class ColorFormat { NONE, RGBA32F, RGBA16F, R32F, R8, RGB8, RGBA8 }; // the 8-bit ones (reference names): a model's input / output frame
+inline bool isFrameFormat(ColorFormat f) { return f == ColorFormat::R8 || f == ColorFormat::RGB8 || f == ColorFormat::RGBA8; }
 struct ColorFormatDesc {
     const char* name;
     size_t bits, ch;
@@ -13,6 +14,9 @@ inline ColorFormatDesc getColorFormatDesc(ColorFormat f) {
     case ColorFormat::RGBA32F: return {"RGBA32F", 128, 4};
     case ColorFormat::RGBA16F: return {"RGBA16F", 64, 4};
     case ColorFormat::R32F: return {"R32F", 32, 1};
+    case ColorFormat::R8: return {"R8", 8, 1};
+    case ColorFormat::RGB8: return {"RGB8", 24, 3};
+    case ColorFormat::RGBA8: return {"RGBA8", 32, 4};
     default: return {"NONE", 0, 0};
     }
 }

@@ -10,9 +10,11 @@
 #include "snn/layeroption.h"
 #include "snn/snn.h"
 
+struct snnhip_tensor;
 namespace snn {
 namespace dp {
 class DeviceBackend;
+class HipBackend;
 }
 typedef enum class Transition { Backend_CPU_GPU, Backend_GPU_CPU, NOT_DEFINED = 200 } Transition;
 
@@ -63,6 +65,13 @@ public:
         // HIP extension: record the launch sequence of the first run() as a hipGraph and replay it while the caller keeps feeding the same input
         // textures (re-recorded when they change).  Ignored with dumpOutputs / profiling / CPU stages (those need the host between launches).
         bool captureGraph = false;
+        // HIP extension: 8-bit frames at the model's ends (inputsDesc[0].format / outputFormat R8, RGB8 or RGBA8, channel count = the model's own).
+        // The conversions (snnhip_u8_in_plan_create / _u8_out_plan_create) join the stage graph handed to snnhip_graph_fuse, so the chain rules can
+        // fold them into fused kernels (ESPCN: rules A8 / B8); otherwise -- and always with dumps -- they run as launches of their own.
+        ColorFormat outputFormat = ColorFormat::RGBA32F;
+        float frameInMeans[4] = {0, 0, 0, 0}, frameInNorms[4] = {1, 1, 1, 1};
+        float frameOutScale[4] = {1, 1, 1, 1}, frameOutOffset[4] = {0, 0, 0, 0};
+        bool halfTensors = false; // the model's tensors are fp16 (preferHp): the conversions read / write halfs
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const std::string& modelFileName, const dp::ShaderGenOptions& options,
@@ -73,6 +82,9 @@ public:
     std::string describe() const; // HIP extension: which kernel variant each stage runs
     // HIP extension: run the next inferences launch by launch even when a recording exists (per-launch profiling needs the plans to run)
     void suspendReplay(bool suspend) { replaySuspended = suspend; }
+    // HIP extension: the model's 8-bit input / output frame tensors (SNNHIP_U8 [batch][H][W][C]; null without 8-bit I/O at that end)
+    snnhip_tensor* frameInput() const;
+    snnhip_tensor* frameOutput() const;
 
 private:
     GpuContext* context;
@@ -80,6 +92,7 @@ private:
     CreationParameters cp;
     RenderStagesArray stages;
     dp::DeviceBackend* backend = nullptr;
+    dp::HipBackend* frameBackend = nullptr; // set when the model has an 8-bit input or output frame
     DeviceTimer* gpuRunTime = nullptr;
     struct InputKey { // what a recorded launch sequence depends on: the device buffer (address), its extent and element type
         const void* data;

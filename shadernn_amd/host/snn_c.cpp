@@ -63,7 +63,25 @@ int snn_model_create3(const char* json_path, int device, int in_w, int in_h, int
 
 int snn_model_create4(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, snn_model** out) {
+    return snn_model_create5(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, nullptr, out);
+}
+
+static bool frameFormat(int f, ColorFormat* c) {
+    switch (f) {
+    case SNN_IO_FLOAT: return true;
+    case SNN_IO_R8: *c = ColorFormat::R8; return true;
+    case SNN_IO_RGB8: *c = ColorFormat::RGB8; return true;
+    case SNN_IO_RGBA8: *c = ColorFormat::RGBA8; return true;
+    default: return false;
+    }
+}
+
+int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_frame_io* io, snn_model** out) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
+    ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
+    if (io && (!frameFormat(io->in_format, &inFmt) || !frameFormat(io->out_format, &outFmt))) return -1;
+    if (io && io->in_format != SNN_IO_FLOAT && io->in_format != in_c) return -1;
     const bool half = prefer_half != 0;
     auto* m = new snn_model();
     // C++ exceptions (std::bad_alloc, a parser's std::out_of_range, ...) must not unwind through the C boundary: report -2 and free what was built.
@@ -75,6 +93,8 @@ int snn_model_create4(const char* json_path, int device, int in_w, int in_h, int
         m->inH = in_h;
         m->inC = in_c;
         dp::ShaderGenOptions sgo = makeOptions(in_w, in_h, in_c, fuse_chains != 0, half, batch);
+        if (inFmt != ColorFormat::NONE) sgo.desiredInput[0].format = inFmt;
+        if (outFmt != ColorFormat::NONE) sgo.desiredOutputFormat = outFmt;
         auto layers = dp::loadFromJsonModel(json_path, false, sgo.mrtMode, sgo.weightMode, half); // preferHp: weights truncated to fp16 (Q13)
         MixedInferenceCore::CreationParameters cp;
         static_cast<InferenceGraph&>(cp) = dp::generateInferenceGraph(layers, sgo);
@@ -82,6 +102,14 @@ int snn_model_create4(const char* json_path, int device, int in_w, int in_h, int
         cp.fuseChains = fuse_chains != 0;
         cp.profiling = profiling != 0;
         cp.captureGraph = capture_graph != 0;
+        cp.outputFormat = sgo.desiredOutputFormat;
+        cp.halfTensors = half;
+        if (io) {
+            memcpy(cp.frameInMeans, io->in_means, sizeof(cp.frameInMeans));
+            memcpy(cp.frameInNorms, io->in_norms, sizeof(cp.frameInNorms));
+            memcpy(cp.frameOutScale, io->out_scale, sizeof(cp.frameOutScale));
+            memcpy(cp.frameOutOffset, io->out_offset, sizeof(cp.frameOutOffset));
+        }
         m->core = MixedInferenceCore::create(m->context, cp);
         makeIO(m, half);
         m->half = half;
@@ -105,6 +133,16 @@ int snn_model_destroy(snn_model* m) {
     delete m->context;
     delete m;
     return 0;
+}
+
+int snn_model_upload_frame_u8(snn_model* m, const unsigned char* nhwc) {
+    snnhip_tensor* t = m && nhwc ? m->core->frameInput() : nullptr;
+    return t && snnhip_tensor_upload_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
+}
+
+int snn_model_download_frame_u8(snn_model* m, unsigned char* nhwc) {
+    snnhip_tensor* t = m && nhwc ? m->core->frameOutput() : nullptr;
+    return t && snnhip_tensor_download_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
 }
 
 int snn_model_upload_input(snn_model* m, const float* nhwc) {
