@@ -1,0 +1,65 @@
+// espcn_d2s_mfma.hip -- chain rule B for upscale factors R = 3 and 4: conv 3x3 (16 -> R*R) + act -> depth-to-space(R) + tanh on the fp32 matrix
+// cores (v_mfma_f32_16x16x4_f32), and its 8-bit form (rule B8).  One body for both kernels, espcn_d2s_mfma_body.h; the rule itself (pattern match,
+// weight image, cost) is in the chain planner, espcn_fused.hip.  R = 2 keeps its own kernels there.  DESIGN.md section 4.10.
+#include <hip/hip_ext.h>
+
+#include "espcn_d2s_mfma.h"
+#include "snnhip_internal.h"
+
+namespace snnhip {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// XCD-aware tile order, as espcn_fused.hip: workgroup b runs on XCD b % 8; each XCD gets a contiguous run of tiles
+__device__ __forceinline__ int xcd_tile_order(int b, int nb) {
+    const int q = nb >> 3, r = nb & 7;
+    const int xcd = b & 7, k = b >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
+struct U8OutCfg {
+    float scale, offset;
+};
+
+template <int R, bool SIMPLE>
+__global__ __launch_bounds__(256, 4) void conv3x3_c16oR_d2s_tanh_kernel(EspcnD2sParams p, const float* __restrict__ x, const float* __restrict__ w,
+                                                                        const float* __restrict__ ep, float* __restrict__ y) {
+    typedef float TOut;
+    constexpr U8OutCfg qout{0.0f, 0.0f};
+#include "espcn_d2s_mfma_body.h"
+}
+
+template <int R, bool SIMPLE>
+__global__ __launch_bounds__(256, 4) void conv3x3_c16oR_d2s_tanh_u8_kernel(EspcnD2sParams p, U8OutCfg qout, const float* __restrict__ x,
+                                                                           const float* __restrict__ w, const float* __restrict__ ep,
+                                                                           unsigned char* __restrict__ y) {
+    typedef unsigned char TOut;
+#include "espcn_d2s_mfma_body.h"
+}
+
+} // namespace
+
+int espcn_d2s_mfma_launch(hipStream_t stream, int r, const EspcnD2sParams& p, bool u8out, float qscale, float qoffset, const float* x, const float* w,
+                          const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop) {
+    SNNHIP_REQUIRE(r == 3 || r == 4, "espcn_d2s_mfma: upscale factor %d (3 or 4)", r);
+    const dim3 grid(p.tilesX * p.tilesY * p.N);
+    const U8OutCfg q{qscale, qoffset};
+    const bool simple = act_is_simple(p.act.act);
+#define SNNHIP_LAUNCH_BR(R, S)                                                                                                                   \
+    if (u8out)                                                                                                                                   \
+        SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_u8_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w, ep,                  \
+                         static_cast<unsigned char*>(y));                                                                                        \
+    else                                                                                                                                         \
+        SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<float*>(y))
+    if (r == 3) {
+        if (simple) SNNHIP_LAUNCH_BR(3, true); else SNNHIP_LAUNCH_BR(3, false);
+    } else {
+        if (simple) SNNHIP_LAUNCH_BR(4, true); else SNNHIP_LAUNCH_BR(4, false);
+    }
+#undef SNNHIP_LAUNCH_BR
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
+} // namespace snnhip

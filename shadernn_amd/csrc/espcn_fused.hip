@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "epilogue.h"
+#include "espcn_d2s_mfma.h"
 #include "snnhip_internal.h"
 
 // developer hook: tools/tune_espcn.hip defines SNNHIP_STAMP(k) to record s_memtime per wave and phase
@@ -554,6 +555,7 @@ bool is_same_conv(const ConvGeom& g, int k, int ic, int oc) { // the ESPCN kerne
 constexpr int A_TW = 64, A_TH = 8;
 constexpr int W_TH = 16, W_WPS = 2; // Winograd kernel A: tile 32 x W_TH, W_WPS blocks (waves/SIMD) per CU
 constexpr int B_TW = 32, B_TH = 8;
+constexpr int BR_TW = kD2sMfmaTW, BR_TH = kD2sMfmaTH; // rule B for upscale 3 / 4 (espcn_d2s_mfma.hip)
 
 // Chain rule F: Conv2D -> InstanceNorm.  The convolution (conv2d_mfma, fp16 LDS epilogue) leaves (mean, M2) of every output tile and channel
 // next to its output; the InstanceNorm's statistics sweep -- one of its three passes over the tensor -- is replaced by a fold over those
@@ -590,6 +592,7 @@ struct ChainPlan : snnhip_plan {
         FusedAParams a{};
         FusedBParams b{};
         int k1 = 5;
+        int r = 2; // FUSED_B: the upscale factor; 3 and 4 run conv3x3_c16oR_d2s_tanh_kernel<R> (espcn_d2s_mfma.hip)
         bool wino = false; // FUSED_A / FUSED_B: the 3x3 conv as Winograd F(2x2,3x3) (default) or direct (SNNHIP_ESPCN_A / _B = direct)
         bool u8in = false, u8out = false; // rule A8: FUSED_A reads the 8-bit frame; rule B8: FUSED_B writes one
         U8InCfg qin{0.0f, 0.0f};
@@ -674,6 +677,10 @@ struct ChainPlan : snnhip_plan {
                 }
 #undef SNNHIP_LAUNCH_A
                 SNNHIP_CHECK_HIP(hipGetLastError());
+            } else if (s.r != 2) { // rule B / B8 for upscale 3 / 4: the kernels live in espcn_d2s_mfma.hip
+                const EspcnD2sParams pr{s.b.N, s.b.H, s.b.W, s.b.tilesX, s.b.tilesY, s.b.act, s.b.magicX, s.b.magicY};
+                int rc = espcn_d2s_mfma_launch(ctx->stream, s.r, pr, s.u8out, s.qout.scale, s.qout.offset, src->data, s.w1, s.e1, dst->data, evStart, evStop);
+                if (rc != SNNHIP_OK) return rc;
             } else if (s.wino) {
                 // one block per tile
                 const int ntiles = s.b.tilesX * s.b.tilesY * s.b.N;
@@ -935,6 +942,42 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
             st.desc = buf;
             st.flops = c0->flops;
             st.bytes = 4.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (16 + 4) + 4.0 * 16 * 9);
+            i += 2;
+            ++fusedCount;
+        } else if (const int rB = (c0 && sp1) ? sp1->d.factor : 0; (rB == 3 || rB == 4) && !c0->depthwise && is_same_conv(c0->g, 3, 16, rB * rB) &&
+                                                                    sp1->d.mode == SNNHIP_SUBPIXEL_D2S && sp1->d.C == rB * rB) {
+            // ---- rule B, upscale 3 / 4: the matrix-core kernel of espcn_d2s_mfma.hip.  (SNNHIP_ESPCN_B=wino and rule C are x2-only alternatives:
+            // they leave this rule in force.)
+            const ConvGeom& g0 = c0->g;
+            st.kind = ChainPlan::FUSED_B;
+            st.r = rB;
+            st.wino = false;
+            st.b = FusedBParams{g0.N, g0.H, g0.W, up_div(g0.W, BR_TW), up_div(g0.H, BR_TH), make_act_cfg(g0.act, g0.leaky), 0u, 0u};
+            st.b.magicX = static_cast<unsigned>((0x100000000ull + static_cast<unsigned>(st.b.tilesX) - 1) / static_cast<unsigned>(st.b.tilesX));
+            st.b.magicY = static_cast<unsigned>((0x100000000ull + static_cast<unsigned>(st.b.tilesY) - 1) / static_cast<unsigned>(st.b.tilesY));
+            // MFMA row 4*dy + dx <- channel rB*dy + dx (rows without a channel stay zero); A-operand image: lane l supplies row l%16, ic 4*(l/16) + j
+            auto row_channel = [rB](int row) { return ((row & 3) < rB && (row >> 2) < rB) ? rB * (row >> 2) + (row & 3) : -1; };
+            std::vector<float> wR(36 * 64, 0.0f), eR(32, 0.0f);
+            const std::vector<float> e1 = fold_epilogue(c0->epi4, rB * rB, g0.useBN);
+            for (int row = 0; row < 16; ++row) {
+                const int ch = row_channel(row);
+                if (ch < 0) continue;
+                eR[row * 2] = e1[ch * 2];
+                eR[row * 2 + 1] = e1[ch * 2 + 1];
+                for (int tap = 0; tap < 9; ++tap)
+                    for (int ic = 0; ic < 16; ++ic)
+                        wR[(tap * 4 + (ic & 3)) * 64 + (ic >> 2) * 16 + row] = c0->w_oihw[(static_cast<size_t>(ch) * 16 + ic) * 9 + tap];
+            }
+            rc = chain->upload(wR.data(), wR.size(), &st.w1);
+            if (rc == SNNHIP_OK) rc = chain->upload(eR.data(), eR.size(), &st.e1);
+            memcpy(st.outDims, sp1->outDims, sizeof(st.outDims));
+            const double tilesB = static_cast<double>(st.b.tilesX) * st.b.tilesY * g0.N;
+            char buf[256];
+            snprintf(buf, sizeof(buf), "fused[conv3x3(16->%d)+depth_to_space(%d)+tanh] mfma_f32_16x16x4 tile=%dx%d kernel=conv3x3_c16oR_d2s_tanh_kernel<%d> mfma_flops=%.6g",
+                     rB * rB, rB, BR_TW, BR_TH, rB, tilesB * (BR_TW * BR_TH / 16) * 36.0 * 2048.0);
+            st.desc = buf;
+            st.flops = c0->flops;
+            st.bytes = 4.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (16 + rB * rB) + static_cast<double>(rB * rB) * 16 * 9);
             i += 2;
             ++fusedCount;
         } else if (snnhip_plan* spool = nullptr; i + 1 < n && c0 && !c0->depthwise && c0->g.kh == 7 && pool2d_plan_desc(plans[i + 1], nullptr) &&
@@ -1251,8 +1294,10 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
             uo.dtype == SNNHIP_F32) {
             a.u8out = true;
             a.qout = U8OutCfg{uo.scale[0], uo.offset[0]};
-            const size_t at = a.desc.find("kernel=conv3x3_c16o4_d2s_tanh_kernel");
-            if (at != std::string::npos) a.desc.replace(at, strlen("kernel=conv3x3_c16o4_d2s_tanh_kernel"), "kernel=conv3x3_c16o4_d2s_tanh_u8_kernel");
+            const char* fkern = a.r == 2 ? "kernel=conv3x3_c16o4_d2s_tanh_kernel" : "kernel=conv3x3_c16oR_d2s_tanh_kernel";
+            const char* ukern = a.r == 2 ? "kernel=conv3x3_c16o4_d2s_tanh_u8_kernel" : "kernel=conv3x3_c16oR_d2s_tanh_u8_kernel";
+            const size_t at = a.desc.find(fkern);
+            if (at != std::string::npos) a.desc.replace(at, strlen(fkern), ukern);
             a.desc += " + u8_out(1ch)";
             a.flops += b.flops;
             a.bytes -= 3.0 * uo.N * uo.H * uo.W; // 1 byte per output pixel instead of 4

@@ -84,6 +84,8 @@ def _fp(a):
 def graph_summary(json_path, w, h, c):
     buf = C.create_string_buffer(1 << 16)
     n = lib().snn_graph_summary(json_path.encode(), w, h, c, buf, len(buf))
+    if n < 0:  # the loader refused the model: buf holds its one-line reason
+        raise ValueError("snn_graph_summary(%s) failed (%d): %s" % (json_path, n, buf.value.decode(errors="replace")))
     rows = []
     for line in buf.value.decode().strip().split("\n"):
         idx, name, loc, dims, ins = line.split("|")

@@ -214,10 +214,9 @@ private:
 struct SubpixelDesc : CommonLayerDesc {
     uint32_t kernelSize = 2;
     std::vector<double> biases;
-    void parse(ModelParser& parser, int layerId) {
-        CommonLayerDesc::parse(parser, layerId);
-        kernelSize = 2; // hard-coded in the reference (subpixelmerge.h:26-33)
-    }
+    // the upscale factor: the layer's optional "upscale" key, 2 when absent (the reference hard-codes 2, subpixelmerge.h:26-33, and never calls
+    // the getUpscale() its parser declares).  A model whose factor or channel count cannot be a depth-to-space is refused with an exception.
+    void parse(ModelParser& parser, int layerId);
 };
 class SubpixelLayer : public ShaderLayer {
 public:

@@ -84,6 +84,7 @@ public:
                                       std::map<std::string, std::vector<float>>& batchNormalization, std::string& activation, float& leakyReluAlpha);
     float getUpSamplingScale(int layerId);
     std::string getUpSampling2DInterpolation(int layerId);
+    int getUpscale(int layerId); // the Subpixel lambda's optional "upscale" key (an integer >= 1), 2 when absent; throws std::invalid_argument otherwise
 
 private:
     json::Value _modelOb;

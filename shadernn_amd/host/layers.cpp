@@ -2,6 +2,7 @@
 // (reference core/src/ic2/genericlayer.cpp, conv2d.cpp, conv2dVulkan.cpp, separableconvolution*.cpp, denselayer*.cpp,
 //  subpixelmergeVulkan.cpp, layerFactory.cpp).  createCS() packs a host-side recipe; the backend turns it into a HIP plan.
 #include <mutex>
+#include <stdexcept>
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -343,6 +344,15 @@ InferencePassesSptr DenseLayerHip::createCS(const LayerGenOptions&) const {
 
 // ------------------------------------------------------------------------------------------------ Subpixel
 
+void SubpixelDesc::parse(ModelParser& parser, int layerId) {
+    CommonLayerDesc::parse(parser, layerId);
+    kernelSize = static_cast<uint32_t>(parser.getUpscale(layerId));
+    // depth-to-space consumes exactly upscale^2 channels (SNN_SUBPIXEL_VK_QUIRK keeps the reference's channel arithmetic for any count)
+    if (!getenv("SNN_SUBPIXEL_VK_QUIRK") && numInputPlanes != kernelSize * kernelSize)
+        throw std::invalid_argument(formatString("layer %d (%s): depth_to_space(%u) needs %u input channels, the model gives it %u", layerId,
+                                                 parser.getLayerName(layerId).c_str(), kernelSize, kernelSize * kernelSize, numInputPlanes));
+}
+
 InferencePassesSptr SubpixelLayerHip::createCS(const LayerGenOptions&) const { // subpixelmergeVulkan.cpp:29-91
     auto ret = std::make_shared<InferencePasses>();
     ret->passes.resize(1);
@@ -351,11 +361,13 @@ InferencePassesSptr SubpixelLayerHip::createCS(const LayerGenOptions&) const { /
     d.H = static_cast<int>(inputDims[0].height);
     d.W = static_cast<int>(inputDims[0].width);
     d.C = static_cast<int>(inputDims[0].channels);
-    d.factor = 2;
+    d.factor = static_cast<int>(_desc.kernelSize);
     // default = true depth-to-space (GL shader / Keras); SNN_SUBPIXEL_VK_QUIRK=1 reproduces vk_subpixel.comp:57-66
     d.mode = getenv("SNN_SUBPIXEL_VK_QUIRK") ? SNNHIP_SUBPIXEL_VK_QUIRK : SNNHIP_SUBPIXEL_D2S;
     InferencePass& pass = ret->passes[0];
-    pass.source = "Subpixel depth_to_space(2)+tanh";
+    if (d.mode == SNNHIP_SUBPIXEL_D2S && d.C != d.factor * d.factor)
+        throw std::invalid_argument(formatString("Subpixel: depth_to_space(%d) needs %d input channels, its producer has %d", d.factor, d.factor * d.factor, d.C));
+    pass.source = formatString("Subpixel depth_to_space(%d)+tanh", d.factor);
     pass.createPlan = [d](snnhip_ctx* ctx, snnhip_plan** out) { return snnhip_subpixel_plan_create(ctx, &d, out); };
     return ret;
 }

@@ -3,6 +3,7 @@
 // Deviation: a "bin_file_name" side file is resolved next to the JSON file (the reference builds a path from its
 // MODEL_DIR macro and the current directory, modelparser.cpp:234-257).
 #include <sstream>
+#include <stdexcept>
 
 #include "ic2/modelparser.h"
 
@@ -470,4 +471,14 @@ std::string ModelParser::getUpSampling2DInterpolation(int layerId) { // :999-100
     if (getLayerName(layerId) == "UpSampling2D") return layer(layerId).at("interpolation").asString();
     SNN_LOGW("ModelParser:: accessing interpolation in a non upsampling2D layer");
     return "";
+}
+
+int ModelParser::getUpscale(int layerId) { // the reference declares it (:272-276, a model-level "upscale" number) and never calls it
+    const json::Value& o = layer(layerId);
+    if (!o.has("upscale")) return 2;
+    const json::Value& v = o.at("upscale");
+    const double r = v.isNumber() ? v.asNumber() : 0.0;
+    if (!(r >= 1.0 && r <= 1024.0) || r != static_cast<double>(static_cast<int>(r)))
+        throw std::invalid_argument("layer " + std::to_string(layerId) + " (" + getLayerName(layerId) + "): \"upscale\" must be an integer >= 1");
+    return static_cast<int>(r);
 }

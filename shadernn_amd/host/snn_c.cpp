@@ -406,7 +406,8 @@ int snn_conv_test_with_layer(int device, const float* input_hwc, const float* we
     return 0;
 }
 
-int snn_graph_summary(const char* json_path, int in_w, int in_h, int in_c, char* buf, int buflen) {
+// A model the loader refuses (an exception of the parser or of a layer's validation) gives -2 and a one-line message in buf.
+int snn_graph_summary(const char* json_path, int in_w, int in_h, int in_c, char* buf, int buflen) try {
     dp::ShaderGenOptions sgo = makeOptions(in_w, in_h, in_c, true);
     auto layers = dp::loadFromJsonModel(json_path, false, sgo.mrtMode, sgo.weightMode, false);
     InferenceGraph g = dp::generateInferenceGraph(layers, sgo);
@@ -420,6 +421,13 @@ int snn_graph_summary(const char* json_path, int in_w, int in_h, int in_c, char*
     }
     snprintf(buf, static_cast<size_t>(buflen), "%s", out.c_str());
     return static_cast<int>(g.layers.size());
+} catch (const std::exception& e) {
+    SNN_LOGE("snn_graph_summary: %s", e.what());
+    if (buf && buflen > 0) snprintf(buf, static_cast<size_t>(buflen), "%s", e.what());
+    return -2;
+} catch (...) {
+    if (buf && buflen > 0) buf[0] = 0;
+    return -2;
 }
 
 int snn_dump_read(const char* path, int whdc[4], float* out, long out_floats) {

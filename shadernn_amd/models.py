@@ -37,12 +37,19 @@ def _dense(rng, name, inu, outu, act):
             "ic": inu, "oc": outu}
 
 
-def espcn_weights(seed=1):
-    """ESPCN 2x: conv5x5 1->16 relu, conv3x3 16->16 relu, conv3x3 16->4 linear, depth-to-space(2)+tanh."""
+def espcn_weights(seed=1, scale=2):
+    """ESPCN at upscale factor r = scale: conv5x5 1->16 relu, conv3x3 16->16 relu, conv3x3 16->r*r linear, depth-to-space(r)+tanh.
+    scale=2 is the net (names, weights, RNG order) this function has always returned; other factors carry "upscale" on the Subpixel layer."""
+    r = int(scale)
+    if r < 1:
+        raise ValueError("espcn_weights: scale must be >= 1, got %r" % (scale,))
     rng = np.random.default_rng(seed)
-    return {"name": "ESPCN_2X", "input_channels": 1,
-            "layers": [_conv(rng, "conv2d", 1, 16, 5, "relu"), _conv(rng, "conv2d_1", 16, 16, 3, "relu"), _conv(rng, "conv2d_2", 16, 4, 3, "linear"),
-                       {"type": "Subpixel", "name": "subpixel", "ic": 4, "oc": 1}]}
+    sub = {"type": "Subpixel", "name": "subpixel", "ic": r * r, "oc": 1}
+    if r != 2:
+        sub["upscale"] = r
+    return {"name": "ESPCN_%dX" % r, "input_channels": 1,
+            "layers": [_conv(rng, "conv2d", 1, 16, 5, "relu"), _conv(rng, "conv2d_1", 16, 16, 3, "relu"), _conv(rng, "conv2d_2", 16, r * r, 3, "linear"),
+                       sub]}
 
 
 def single_conv(seed=1, ic=3, oc=64, k=3, act="relu", stride=1, bn=False):
@@ -227,6 +234,8 @@ def to_json_dict(net, width, height):
         elif t == "Subpixel":
             o["type"] = "Lambda"  # dispatched by NAME (modelparser.cpp:82-84, layerFactory.cpp:147-149)
             o["name"] = "subpixel"
+            if int(l.get("upscale", 2)) != 2:  # optional key, default 2: files written for x2 stay byte-identical
+                o["upscale"] = int(l["upscale"])
         elif t in ("MaxPooling2D", "AveragePooling2D", "AdaptiveAvgPool2d"):
             o.update({"type": t, "pool": [int(l["pool"]), int(l["pool"])]})
             if t != "AdaptiveAvgPool2d":

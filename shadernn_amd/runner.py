@@ -19,7 +19,7 @@ def _layer_plan(ctx, layer, shape, dtype=capi.F32):
     if t == "Dense":
         return capi.dense_plan(ctx, n, layer["w"], layer["units"], layer["b"], act=layer["activation"] if layer["activation"] in capi.DENSE_ACT else "relu")
     if t == "Subpixel":
-        return capi.subpixel_plan(ctx, n, h, w, c, 2, layer.get("mode", 0))
+        return capi.subpixel_plan(ctx, n, h, w, c, int(layer.get("upscale", 2)), layer.get("mode", 0))
     if t in ("MaxPooling2D", "AveragePooling2D"):
         return capi.pool2d_plan(ctx, n, h, w, c, layer["pool"], layer["stride"], kind="max" if t == "MaxPooling2D" else "avg",
                                 same=layer["padding"] not in ("valid", "none", "0"))

@@ -8,6 +8,14 @@ adds the H2D upload of one input frame and the D2H download of one output frame 
 Then one launch-trace pass (snnhip_trace_begin / _end) lists the kernels of each form with their per-launch times.
 
     python tools/bench_frames.py [--h 1080 --w 1920 --rounds 7 --iters 20]
+
+--scale 3 / 4: the ESPCN of that upscale factor on the input size that keeps the output at 3840 x 2160 (1280 x 720, 960 x 540), and two more
+forms in the same alternation, f32_layers and u8_layers: one plan per layer (the generic convolutions, the stand-alone Subpixel launch and the
+stand-alone 8-bit conversions) -- the baseline rule B's kernel for that factor has to beat.  The report then also carries, per form, the traced
+kernels with their time per launch and, for the chain's fused steps, the fraction of the HBM roofline on the step's own bytes and of the fp32
+matrix peak on the MFMA flops it executes.  --per-layer adds the two forms at scale 2 as well.
+
+    python tools/bench_frames.py --scale 3
 """
 import argparse
 import json
@@ -24,8 +32,12 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--h", type=int, default=1080)
-    ap.add_argument("--w", type=int, default=1920)
+    ap.add_argument("--scale", type=int, default=2, choices=[2, 3, 4], help="upscale factor; the input size follows it (output 3840 x 2160) unless --h / --w are given")
+    ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
+    ap.add_argument("--h", type=int, default=0)
+    ap.add_argument("--w", type=int, default=0)
+    ap.add_argument("--hbm-tbs", type=float, default=8.0, help="HBM roofline, TB/s")
+    ap.add_argument("--mfma-tflops", type=float, default=157.3, help="fp32 matrix peak, TFLOP/s")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
@@ -37,8 +49,10 @@ def main():
 
     snn.load_library()
     ctx = capi.Context(0)
-    net = models.espcn_weights(seed=1)
-    H, W = a.h, a.w
+    R = a.scale
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    per_layer = a.per_layer or R != 2
     rng = np.random.default_rng(1)
     u8 = rng.integers(0, 256, size=(1, H, W, 1), dtype=np.uint8)
     f32 = ((u8.astype(np.float32) - 127.5) * np.float32(1 / 127.5))
@@ -75,6 +89,12 @@ def main():
         "u8_sep": dict(plan=Seq([uin, fchain, uout], [(1, H, W, 1), shape]), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8),
                        y=capi.Tensor(ctx, *shape, dtype=capi.U8), xh=u8, yh=np.empty(shape, np.uint8)),
     }
+    if per_layer:
+        lshapes = [p.out_shape() for p in layers[:-1]]
+        forms["f32_layers"] = dict(plan=Seq(layers, lshapes), x=capi.Tensor(ctx, 1, H, W, 1), y=capi.Tensor(ctx, *shape), xh=f32,
+                                   yh=np.empty(shape, np.float32))
+        forms["u8_layers"] = dict(plan=Seq([uin] + layers + [uout], [(1, H, W, 1)] + lshapes + [shape]), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8),
+                                  y=capi.Tensor(ctx, *shape, dtype=capi.U8), xh=u8, yh=np.empty(shape, np.uint8))
     for f in forms.values():
         if f["x"].dtype == capi.U8:
             f["x"].upload_u8(f["xh"])
@@ -116,7 +136,7 @@ def main():
                 f["plan"].run(f["x"], f["y"])
                 download(f)
             e2e[k].append((time.perf_counter() - t0) * 1e3 / a.iters)
-    out = {"frame": "%dx%d -> %dx%d" % (H, W, 2 * H, 2 * W), "rounds": a.rounds, "iters": a.iters}
+    out = {"frame": "%dx%d -> %dx%d" % (H, W, R * H, R * W), "rounds": a.rounds, "iters": a.iters}
     for k, f in forms.items():
         d, e = statistics.median(dev[k]), statistics.median(e2e[k])
         out[k] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[k]), 4), "device_ms_max": round(max(dev[k]), 4),
@@ -126,18 +146,45 @@ def main():
     out["device_u8_over_f32"] = round(out["u8"]["device_ms_median"] / out["f32"]["device_ms_median"], 4)
     out["device_u8_over_u8_sep"] = round(out["u8"]["device_ms_median"] / out["u8_sep"]["device_ms_median"], 4)
     out["e2e_fps_u8_over_f32"] = round(out["u8"]["e2e_frames_per_s"] / out["f32"]["e2e_frames_per_s"], 4)
-    print(json.dumps(out, indent=1))
+    if per_layer:
+        out["scale"] = R
+        for k in ("f32", "u8"):
+            out["device_%s_fused_over_layers" % k] = round(out[k]["device_ms_median"] / out[k + "_layers"]["device_ms_median"], 4)
+            # the spread between repeated regions of one form, as a fraction of its median: what a difference between forms has to exceed
+            out["device_%s_spread" % k] = round(max((max(dev[j]) - min(dev[j])) / statistics.median(dev[j]) for j in (k, k + "_layers")), 4)
+    traces = {}
     for k, f in forms.items():
         capi.trace_begin()
         for _ in range(a.iters):
             f["plan"].run(f["x"], f["y"])
         ctx.sync()
         rep = capi.trace_end()
-        print("launches (%s I/O), per-kernel time over %d steps:" % (k, a.iters))
         kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
-        for item in kernels:
-            name = item.get("function")
-            n, ms = item.get("launches", 0), item.get("total_ms", item.get("ms", 0.0))
+        traces[k] = [(item.get("function"), item.get("launches", 0), item.get("total_ms", item.get("ms", 0.0))) for item in kernels]
+    if per_layer:
+        import re
+
+        for k, f in forms.items():
+            out[k]["kernels"] = [{"function": name, "launches": n, "us_per_launch": round(1e3 * ms / max(n, 1), 2)} for name, n, ms in traces[k]]
+        for k in ("f32", "u8"):  # the fused chain: step i of the plan is kernel i of the trace's launch order; match by the kernel name in the description
+            plan, roof = forms[k]["plan"], []
+            for i in range(plan.num_steps()):
+                desc = plan.step_describe(i)
+                m = re.search(r"kernel=([A-Za-z0-9_]+)", desc)
+                fl = re.search(r"mfma_flops=([0-9.e+]+)", desc)
+                hit = [t for t in traces[k] if m and t[0] and t[0].split("<")[0].split("(")[0].strip().endswith(m.group(1))]
+                if not hit:
+                    continue
+                us = 1e3 * hit[0][2] / max(hit[0][1], 1)
+                _, nbytes = plan.step_cost(i)
+                roof.append({"kernel": m.group(1), "us_per_launch": round(us, 2), "hbm_bytes": int(nbytes),
+                             "hbm_fraction": round(nbytes / (us * 1e-6) / (a.hbm_tbs * 1e12), 4),
+                             "mfma_fraction": round(float(fl.group(1)) / (us * 1e-6) / (a.mfma_tflops * 1e12), 4) if fl else None})
+            out[k]["roofline"] = roof
+    print(json.dumps(out, indent=1))
+    for k in forms:
+        print("launches (%s I/O), per-kernel time over %d steps:" % (k, a.iters))
+        for name, n, ms in traces[k]:
             print("  %-48s launches=%-4d us/launch=%.2f" % (name, n, 1e3 * ms / max(n, 1)))
     ctx.close()
 
