@@ -366,6 +366,15 @@ int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);
  * materialised.  Returns SNNHIP_E_UNSUPPORTED when no fusion rule matches (callers keep the unfused plans).
  * Implemented rule set: see DESIGN.md section 4 (ESPCN: conv5x5(1->16)+conv3x3(16->16), conv3x3(16->4)+subpixel). */
 int snnhip_chain_plan_create(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_plan** out);
+/* The fp16 ESPCN rules (SNNHIP_ESPCN_F16=1) keep their weights as lane-ordered fp16 images for the f16 matrix cores.  This
+ * is the packing itself, host side only (no context, no device), so that it can be checked without a GPU.  w_oihw is fp32 and is rounded to nearest
+ * even; out receives the halfs' bit patterns, *count how many.
+ *   ic = 1, k = 3 or 5:        [16][1][k][k] -> 512 halfs,   out[lane*8 + j] = W[oc = lane%16][tap = 8*(lane/16) + j], zero from tap k*k on
+ *   ic = 16, k = 3, r = 0:     [16][16][3][3] -> 2304 halfs, MFMA row = output channel
+ *   ic = 16, k = 3, r = 2,3,4: [r*r][16][3][3] -> 2304 halfs, MFMA row 4*dy + dx = channel r*dy + dx (other rows zero)
+ *       out[(s*64 + lane)*8 + j] = W[row lane%16][ic = 8*(g%2) + j][tap = 2*s + g/2],  s = 0..3, g = lane/16, j = 0..7
+ *       out[2048 + lane*4 + j]   = W[row lane%16][ic = 4*g + j][tap = 8],               j = 0..3 */
+int snnhip_espcn_f16_pack_weights(const float* w_oihw, int ic, int k, int r, unsigned short* out, int capacity, int* count);
 
 /* Graph-level fusion: the ONE place where an operator DAG is searched for fusable groups (the host mirror's
  * HipBackend::finalizeStages and the Python GraphRunner both call it; the rules themselves are snnhip_chain_plan_create's).

@@ -160,6 +160,7 @@ SIGNATURES = {
     "snnhip_u8_out_plan_create": (C.c_int, [_P, C.POINTER(U8OutDesc), C.POINTER(_P)]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
+    "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_graph_fuse": (C.c_int, [_P, C.POINTER(GraphNode), C.c_int, C.POINTER(FusedNode)]),
     "snnhip_plan_run": (C.c_int, [_P, _P, _P]),
     "snnhip_plan_run_n": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P]),
@@ -656,6 +657,16 @@ def deconv2d_plan(ctx, N, H, W, w_oihw, bias=None, stride=2, same=True, act="", 
     h = _P()
     check(lib().snnhip_deconv2d_plan_create(ctx.h, C.byref(d), _fptr(w), _fptr(b), *[_fptr(a) for a in bnp], C.byref(h)))
     return Plan(ctx, h)
+
+
+def espcn_f16_pack_weights(w_oihw, r=0):
+    """snnhip_espcn_f16_pack_weights (host side only, no GPU): the lane-ordered fp16 image that the fp16 ESPCN kernels keep of a convolution's weights, as
+    float16.  w_oihw [16][1][k][k] (k = 3, 5) or [OC][16][3][3] with r = 0 (OC = 16: MFMA row = channel) or r = 2, 3, 4 (OC = r*r: row 4*dy + dx)."""
+    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
+    out = np.zeros(2304, np.uint16)
+    n = C.c_int(0)
+    check(lib().snnhip_espcn_f16_pack_weights(w.ctypes.data_as(_P), w.shape[1], w.shape[2], r, out.ctypes.data_as(_P), out.size, C.byref(n)))
+    return out[: n.value].view(np.float16).copy()
 
 
 def chain_plan(ctx, plans):

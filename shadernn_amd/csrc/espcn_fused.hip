@@ -23,6 +23,7 @@
 
 #include "epilogue.h"
 #include "espcn_d2s_mfma.h"
+#include "espcn_f16.h"
 #include "snnhip_internal.h"
 
 // developer hook: tools/tune_espcn.hip defines SNNHIP_STAMP(k) to record s_memtime per wave and phase
@@ -547,8 +548,9 @@ std::vector<float> fold_epilogue(const std::vector<float>& epi4, int OC, int use
 
 bool plain_act(int act) { return act >= 0 && act <= SNNHIP_ACT_SILU; }
 
-bool is_same_conv(const ConvGeom& g, int k, int ic, int oc) { // the ESPCN kernels are fp32
-    return g.dtype == SNNHIP_F32 && g.preMode == 0 && g.kh == k && g.kw == k && g.IC == ic && g.OC == oc && g.sh == 1 && g.sw == 1 && g.padx == k / 2 && g.pady == k / 2 &&
+// (the ESPCN kernels are fp32; rules A16 / B16 -- espcn_f16.hip, SNNHIP_ESPCN_F16=1 -- ask for SNNHIP_F16)
+bool is_same_conv(const ConvGeom& g, int k, int ic, int oc, int dtype = SNNHIP_F32) {
+    return g.dtype == dtype && g.preMode == 0 && g.kh == k && g.kw == k && g.IC == ic && g.OC == oc && g.sh == 1 && g.sw == 1 && g.padx == k / 2 && g.pady == k / 2 &&
            (g.padMode == SNNHIP_PAD_CONSTANT || g.padMode == SNNHIP_PAD_NONE) && g.OH == g.H && g.OW == g.W && plain_act(g.act);
 }
 
@@ -585,14 +587,16 @@ struct InstanceNormConvPlan : snnhip_plan {
 };
 
 struct ChainPlan : snnhip_plan {
-    enum Kind { PLAIN, FUSED_A, FUSED_B, FUSED_S };
+    enum Kind { PLAIN, FUSED_A, FUSED_B, FUSED_S, FUSED_A16, FUSED_B16 };
     struct Step {
         Kind kind = PLAIN;
         snnhip_plan* plain = nullptr; // borrowed
         FusedAParams a{};
         FusedBParams b{};
         int k1 = 5;
-        int r = 2; // FUSED_B: the upscale factor; 3 and 4 run conv3x3_c16oR_d2s_tanh_kernel<R> (espcn_d2s_mfma.hip)
+        int r = 2; // FUSED_B: the upscale factor; 3 and 4 run conv3x3_c16oR_d2s_tanh_kernel<R> (espcn_d2s_mfma.hip).  FUSED_B16: 2, 3 or 4
+        EspcnF16AParams a16{}; // FUSED_A16 / FUSED_B16 (espcn_f16.hip): w1, w2 hold halfs (espcn_f16_pack_w1 / _w3), u8in / u8out as for A8 / B8
+        EspcnF16BParams b16{};
         bool wino = false; // FUSED_A / FUSED_B: the 3x3 conv as Winograd F(2x2,3x3) (default) or direct (SNNHIP_ESPCN_A / _B = direct)
         bool u8in = false, u8out = false; // rule A8: FUSED_A reads the 8-bit frame; rule B8: FUSED_B writes one
         U8InCfg qin{0.0f, 0.0f};
@@ -633,13 +637,21 @@ struct ChainPlan : snnhip_plan {
             hipEvent_t evStart = nullptr, evStop = nullptr;
             TraceScope traceScope(s.desc, s.flops, s.bytes); // a PLAIN step's plan opens its own scope inside this one
             if (profiling) {
-                int rc = (s.kind == FUSED_A || s.kind == FUSED_B) ? profAcquire(static_cast<int>(i), &evStart, &evStop) : profBegin(static_cast<int>(i));
+                int rc = (s.kind == FUSED_A || s.kind == FUSED_B || s.kind == FUSED_A16 || s.kind == FUSED_B16) ? profAcquire(static_cast<int>(i), &evStart, &evStop) : profBegin(static_cast<int>(i));
                 if (rc != SNNHIP_OK) return rc;
             }
             if (s.kind == PLAIN) {
                 // a chain with two inputs: the second one belongs to its LAST step (InstanceNorm -> Add behind a run of layers, rules F + H)
                 const snnhip_tensor* two[2] = {src, nIn > 1 ? in[1] : nullptr};
                 int rc = s.plain->invoke(two, (i + 1 == steps.size()) ? nIn : 1, dst);
+                if (rc != SNNHIP_OK) return rc;
+            } else if (s.kind == FUSED_A16) {
+                int rc = espcn_f16_a_launch(ctx->stream, s.k1, s.a16, s.u8in, src->data, reinterpret_cast<const _Float16*>(s.w1),
+                                            reinterpret_cast<const _Float16*>(s.w2), s.e1, s.e2, reinterpret_cast<_Float16*>(dst->data), evStart, evStop);
+                if (rc != SNNHIP_OK) return rc;
+            } else if (s.kind == FUSED_B16) {
+                int rc = espcn_f16_b_launch(ctx->stream, s.r, s.b16, s.u8out, reinterpret_cast<const _Float16*>(src->data),
+                                            reinterpret_cast<const _Float16*>(s.w1), s.e1, dst->data, evStart, evStop);
                 if (rc != SNNHIP_OK) return rc;
             } else if (s.kind == FUSED_S) {
                 int rc = espcn_stream_launch(ctx->stream, s.streamCfg, src->data, s.w1, s.e1, s.w2, s.e2, s.w3, s.e3, dst->data);
@@ -711,7 +723,7 @@ struct ChainPlan : snnhip_plan {
                 }
                 SNNHIP_CHECK_HIP(hipGetLastError());
             }
-            if (profiling && !(s.kind == FUSED_A || s.kind == FUSED_B)) {
+            if (profiling && !(s.kind == FUSED_A || s.kind == FUSED_B || s.kind == FUSED_A16 || s.kind == FUSED_B16)) {
                 int rc = profEnd(static_cast<int>(i));
                 if (rc != SNNHIP_OK) return rc;
             }
@@ -747,8 +759,20 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
         }
     const char* mode = snnhip::option("SNNHIP_ESPCN_FUSION");
     const bool allowStream = mode && strcmp(mode, "stream") == 0;
+    // Rules A16 / B16 (espcn_f16.hip): the same layer patterns on SNNHIP_F16 tensors, opt-in.  The fp32 alternatives (rule C, the direct kernel A,
+    // the Winograd kernel B) have no fp16 form: with one of them selected the fp16 chain stays per layer.
+    const char* f16opt = snnhip::option("SNNHIP_ESPCN_F16");
+    const char* f16a = snnhip::option("SNNHIP_ESPCN_A");
+    const char* f16b = snnhip::option("SNNHIP_ESPCN_B");
+    const bool f16Rules = f16opt && f16opt[0] && strcmp(f16opt, "0") != 0 && !allowStream && !(f16a && strcmp(f16a, "direct") == 0) &&
+                          !(f16b && strcmp(f16b, "wino") == 0);
     auto* chain = new ChainPlan();
     chain->ctx = ctx;
+    auto upload_halfs = [&](const std::vector<_Float16>& h, float** dev) { // (plan buffers are handed out as float*: two halfs per element)
+        std::vector<float> raw((h.size() + 1) / 2, 0.0f);
+        memcpy(raw.data(), h.data(), h.size() * sizeof(_Float16));
+        return chain->upload(raw.data(), raw.size(), dev);
+    };
     chain->numInputs = plans[n - 1]->numInputs;
     memcpy(chain->inDims, plans[0]->inDims, sizeof(chain->inDims));
     memcpy(chain->outDims, plans[n - 1]->outDims, sizeof(chain->outDims));
@@ -821,6 +845,65 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
             st.flops = c0->flops + c1->flops + c2->flops;
             st.bytes = 4.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (1 + 4) + 16.0 * taps1 + 16.0 * 16 * 9 + 4.0 * 16 * 9);
             i += 4;
+            ++fusedCount;
+        } else if (f16Rules && c0 && c1 && !c0->depthwise && !c1->depthwise &&
+                   (is_same_conv(c0->g, 5, 1, 16, SNNHIP_F16) || is_same_conv(c0->g, 3, 1, 16, SNNHIP_F16)) && is_same_conv(c1->g, 3, 16, 16, SNNHIP_F16)) {
+            // ---- rule A16: rule A's pattern on fp16 tensors -> espcn_f16_conv_pair_kernel
+            const ConvGeom& g0 = c0->g;
+            const int K1 = g0.kh, taps1 = K1 * K1;
+            st.kind = ChainPlan::FUSED_A16;
+            st.k1 = K1;
+            st.a16 = EspcnF16AParams{g0.N, g0.H, g0.W, up_div(g0.W, kEspcnF16TW_A), up_div(g0.H, kEspcnF16TH_A), make_act_cfg(g0.act, g0.leaky),
+                                     make_act_cfg(c1->g.act, c1->g.leaky), 0.0f, 1.0f};
+            std::vector<_Float16> w1h(kEspcnF16W1Halfs), w2h(kEspcnF16W3Halfs);
+            espcn_f16_pack_w1(c0->w_oihw.data(), K1, w1h.data());
+            espcn_f16_pack_w3(c1->w_oihw.data(), 0, w2h.data());
+            std::vector<float> e1 = fold_epilogue(c0->epi4, 16, g0.useBN), e2 = fold_epilogue(c1->epi4, 16, c1->g.useBN);
+            rc = upload_halfs(w1h, &st.w1);
+            if (rc == SNNHIP_OK) rc = upload_halfs(w2h, &st.w2);
+            if (rc == SNNHIP_OK) rc = chain->upload(e1.data(), e1.size(), &st.e1);
+            if (rc == SNNHIP_OK) rc = chain->upload(e2.data(), e2.size(), &st.e2);
+            memcpy(st.outDims, c1->outDims, sizeof(st.outDims));
+            // MFMA flops issued per tile: conv1 one 16x16x32 per 16 pixels of the halo region (the four waves take two groups a turn), conv2 four
+            // 16x16x32 + one 16x16x16 per 16 pixels
+            const double tilesA = static_cast<double>(st.a16.tilesX) * st.a16.tilesY * g0.N;
+            const int groups1 = round_up(up_div((kEspcnF16TW_A + 2) * (kEspcnF16TH_A + 2), 16), 8);
+            char buf[320];
+            snprintf(buf, sizeof(buf), "fused[conv%dx%d(1->16)+conv3x3(16->16)] mfma_f32_16x16x32_f16 tile=%dx%d kernel=espcn_f16_conv_pair_kernel mfma_flops=%.6g",
+                     K1, K1, kEspcnF16TW_A, kEspcnF16TH_A, tilesA * (groups1 * 16384.0 + (kEspcnF16TW_A * kEspcnF16TH_A / 16) * (4 * 16384.0 + 8192.0)));
+            st.desc = buf;
+            st.flops = c0->flops + c1->flops;
+            st.bytes = 2.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (1 + 16) + 16.0 * taps1 + 16.0 * 16 * 9);
+            i += 2;
+            ++fusedCount;
+        } else if (const int r16 = (f16Rules && c0 && sp1) ? sp1->d.factor : 0; r16 >= 2 && r16 <= 4 && !c0->depthwise &&
+                                                                                 is_same_conv(c0->g, 3, 16, r16 * r16, SNNHIP_F16) &&
+                                                                                 sp1->d.mode == SNNHIP_SUBPIXEL_D2S && sp1->d.C == r16 * r16) {
+            // ---- rule B16: rule B's pattern (upscale 2, 3, 4) on fp16 tensors -> espcn_f16_d2s_kernel<r>
+            const ConvGeom& g0 = c0->g;
+            st.kind = ChainPlan::FUSED_B16;
+            st.r = r16;
+            st.b16 = EspcnF16BParams{g0.N, g0.H, g0.W, up_div(g0.W, kEspcnF16TW_B), up_div(g0.H, kEspcnF16TH_B), make_act_cfg(g0.act, g0.leaky), 1.0f, 0.0f};
+            std::vector<_Float16> wh(kEspcnF16W3Halfs);
+            espcn_f16_pack_w3(c0->w_oihw.data(), r16, wh.data());
+            std::vector<float> eR(32, 0.0f);
+            const std::vector<float> e1 = fold_epilogue(c0->epi4, r16 * r16, g0.useBN);
+            for (int row = 0; row < 16; ++row)
+                if (const int ch = espcn_f16_row_channel(r16, row); ch >= 0) {
+                    eR[row * 2] = e1[ch * 2];
+                    eR[row * 2 + 1] = e1[ch * 2 + 1];
+                }
+            rc = upload_halfs(wh, &st.w1);
+            if (rc == SNNHIP_OK) rc = chain->upload(eR.data(), eR.size(), &st.e1);
+            memcpy(st.outDims, sp1->outDims, sizeof(st.outDims));
+            const double tilesB = static_cast<double>(st.b16.tilesX) * st.b16.tilesY * g0.N;
+            char buf[256];
+            snprintf(buf, sizeof(buf), "fused[conv3x3(16->%d)+depth_to_space(%d)+tanh] mfma_f32_16x16x32_f16 tile=%dx%d kernel=espcn_f16_d2s_kernel<%d> mfma_flops=%.6g",
+                     r16 * r16, r16, kEspcnF16TW_B, kEspcnF16TH_B, r16, tilesB * (kEspcnF16TW_B * kEspcnF16TH_B / 16) * (4 * 16384.0 + 8192.0));
+            st.desc = buf;
+            st.flops = c0->flops;
+            st.bytes = 2.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (16 + r16 * r16) + static_cast<double>(r16 * r16) * 16 * 9);
+            i += 2;
             ++fusedCount;
         } else if (pairA) {
             // ---- rule A
@@ -1288,6 +1371,37 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
             chain->steps.erase(chain->steps.begin() + static_cast<long>(k));
             ++fusedCount;
             --k;
+            continue;
+        }
+        // ... and the fp16 forms: u8_in (1 channel, fp16) in front of rule A16, u8_out (1 channel, fp16) behind rule B16
+        if (k == 0 && a.kind == ChainPlan::PLAIN && b.kind == ChainPlan::FUSED_A16 && !b.u8in && u8_in_plan_desc(a.plain, &ui) && ui.C == 1 &&
+            ui.dtype == SNNHIP_F16) {
+            b.u8in = true;
+            b.a16.mean = ui.means[0];
+            b.a16.norm = ui.norms[0];
+            const size_t at = b.desc.find("kernel=espcn_f16_conv_pair_kernel");
+            if (at != std::string::npos) b.desc.replace(at, strlen("kernel=espcn_f16_conv_pair_kernel"), "kernel=espcn_f16_conv_pair_kernel<u8>");
+            b.desc = "u8_in(1ch) + " + b.desc;
+            b.flops += a.flops;
+            b.bytes -= 1.0 * ui.N * ui.H * ui.W; // 1 byte per input pixel instead of 2
+            chain->steps.erase(chain->steps.begin() + static_cast<long>(k));
+            ++fusedCount;
+            --k;
+            continue;
+        }
+        if (k + 2 == chain->steps.size() && a.kind == ChainPlan::FUSED_B16 && !a.u8out && b.kind == ChainPlan::PLAIN && u8_out_plan_desc(b.plain, &uo) &&
+            uo.C == 1 && uo.dtype == SNNHIP_F16) {
+            a.u8out = true;
+            a.b16.qscale = uo.scale[0];
+            a.b16.qoffset = uo.offset[0];
+            const size_t at = a.desc.find(">", a.desc.find("kernel=espcn_f16_d2s_kernel<"));
+            if (at != std::string::npos) a.desc.insert(at, ",u8");
+            a.desc += " + u8_out(1ch)";
+            a.flops += b.flops;
+            a.bytes -= 1.0 * uo.N * uo.H * uo.W; // 1 byte per output pixel instead of 2
+            memcpy(a.outDims, b.outDims, sizeof(a.outDims));
+            chain->steps.erase(chain->steps.begin() + static_cast<long>(k) + 1);
+            ++fusedCount;
             continue;
         }
         if (k + 2 == chain->steps.size() && a.kind == ChainPlan::FUSED_B && !a.wino && !a.u8out && b.kind == ChainPlan::PLAIN && u8_out_plan_desc(b.plain, &uo) && uo.C == 1 &&

@@ -16,6 +16,12 @@ kernels with their time per launch and, for the chain's fused steps, the fractio
 matrix peak on the MFMA flops it executes.  --per-layer adds the two forms at scale 2 as well.
 
     python tools/bench_frames.py --scale 3
+
+--half: the fp16 forms instead, in the same alternation: f32 (the fused fp32 chain), f16_layers (one fp16 plan per layer, what prefer_half runs by
+default), f16 (the fused fp16 chain, chain rules A16 / B16, SNNHIP_ESPCN_F16=1) and f16_u8 (the same with the 8-bit conversions folded in).  Device
+step per form with the spread over the rounds, the kernels of the launch trace, and the bytes each form's launches move per frame.
+
+    python tools/bench_frames.py --half --scale 2
 """
 import argparse
 import json
@@ -30,8 +36,113 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def main_half(a):
+    """--half: f32 / f16_layers / f16 / f16_u8, device step only."""
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R = a.scale
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    u8 = np.random.default_rng(1).integers(0, 256, size=(1, H, W, 1), dtype=np.uint8)
+    f32 = ((u8.astype(np.float32) - 127.5) * np.float32(1 / 127.5))
+
+    def layer_plans(dtype):
+        plans, shape = [], (1, H, W, 1)
+        for layer in net["layers"]:
+            p = _layer_plan(ctx, layer, shape, dtype)
+            plans.append(p)
+            shape = p.out_shape()
+        return plans, shape
+
+    class Seq:  # plans run one by one, each into a tensor of its own
+        def __init__(self, plans, dtype):
+            self.plans, self.mids = plans, [capi.Tensor(ctx, *p.out_shape(), dtype=dtype) for p in plans[:-1]]
+
+        def run(self, x, y):
+            src = x
+            for p, dst in zip(self.plans, self.mids + [y]):
+                p.run(src, dst)
+                src = dst
+
+        def num_steps(self):
+            return len(self.plans)
+
+        def step_describe(self, i):
+            return self.plans[i].describe()
+
+        def step_cost(self, i):
+            f, b = self.plans[i].cost()
+            return f, b * (0.5 if "subpixel" in self.plans[i].describe() else 1.0)  # (the dtype-agnostic Subpixel plan reports fp32 bytes)
+
+    l32, shape = layer_plans(capi.F32)
+    l16, _ = layer_plans(capi.F16)
+    uin = capi.u8_in_plan(ctx, 1, H, W, 1, (127.5, 0, 0, 0), (1 / 127.5, 1, 1, 1), dtype=capi.F16)
+    uout = capi.u8_out_plan(ctx, *shape, (127.5, 0, 0, 0), (127.5, 0, 0, 0), dtype=capi.F16)
+    capi.set_option("SNNHIP_ESPCN_F16", "1")
+    try:
+        c16, c16u8 = capi.chain_plan(ctx, l16), capi.chain_plan(ctx, [uin] + l16 + [uout])
+    finally:
+        capi.set_option("SNNHIP_ESPCN_F16", None)
+    assert c16.num_steps() == 2 and c16u8.num_steps() == 2, (c16.describe(), c16u8.describe())
+    forms = {
+        "f32": dict(plan=capi.chain_plan(ctx, l32), x=capi.Tensor(ctx, 1, H, W, 1), y=capi.Tensor(ctx, *shape)),
+        "f16_layers": dict(plan=Seq(l16, capi.F16), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.F16), y=capi.Tensor(ctx, *shape, dtype=capi.F16)),
+        "f16": dict(plan=c16, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.F16), y=capi.Tensor(ctx, *shape, dtype=capi.F16)),
+        "f16_u8": dict(plan=c16u8, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8), y=capi.Tensor(ctx, *shape, dtype=capi.U8)),
+    }
+    for f in forms.values():
+        if f["x"].dtype == capi.U8:
+            f["x"].upload_u8(u8)
+        else:
+            f["x"].upload(f32)
+    timer = capi.Timer(ctx)
+    dev = {k: [] for k in forms}
+    for f in forms.values():
+        for _ in range(a.warmup):
+            f["plan"].run(f["x"], f["y"])
+        ctx.sync()
+    order = list(forms) + list(forms)[::-1]  # mirrored: A B C D D C B A
+    for _ in range(a.rounds):
+        for k in order:
+            f = forms[k]
+            timer.start()
+            for _ in range(a.iters):
+                f["plan"].run(f["x"], f["y"])
+            timer.stop()
+            dev[k].append(timer.elapsed_ms() / a.iters)
+    y16, y32 = forms["f16"]["y"].numpy(), forms["f32"]["y"].numpy()
+    out = {"frame": "%dx%d -> %dx%d" % (H, W, R * H, R * W), "scale": R, "rounds": a.rounds, "iters": a.iters,
+           "max_abs_f16_minus_f32": float(np.abs(y16 - y32).max()), "max_abs_f16_minus_f16_layers": float(np.abs(y16 - forms["f16_layers"]["y"].numpy()).max())}
+    for k, f in forms.items():
+        plan, d = f["plan"], statistics.median(dev[k])
+        capi.trace_begin()
+        for _ in range(a.iters):
+            plan.run(f["x"], f["y"])
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        nbytes = sum(plan.step_cost(i)[1] for i in range(plan.num_steps()))
+        out[k] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[k]), 4), "device_ms_max": round(max(dev[k]), 4),
+                  "spread": round((max(dev[k]) - min(dev[k])) / d, 4), "hbm_bytes_per_frame": int(nbytes),
+                  "hbm_tbs_at_median": round(nbytes / (d * 1e-3) / 1e12, 3),
+                  "steps": [plan.step_describe(i) for i in range(plan.num_steps())],
+                  "kernels": [{"function": it.get("function"), "launches": it.get("launches", 0),
+                               "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]}
+    out["device_f16_over_f32"] = round(out["f16"]["device_ms_median"] / out["f32"]["device_ms_median"], 4)
+    out["device_f16_over_f16_layers"] = round(out["f16"]["device_ms_median"] / out["f16_layers"]["device_ms_median"], 4)
+    out["device_f16_u8_over_f16"] = round(out["f16_u8"]["device_ms_median"] / out["f16"]["device_ms_median"], 4)
+    out["spread_max"] = max(out[k]["spread"] for k in forms)
+    print(json.dumps(out, indent=1))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
     ap.add_argument("--scale", type=int, default=2, choices=[2, 3, 4], help="upscale factor; the input size follows it (output 3840 x 2160) unless --h / --w are given")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
     ap.add_argument("--h", type=int, default=0)
@@ -42,6 +153,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.half:
+        return main_half(a)
 
     import shadernn_amd as snn
     from shadernn_amd import capi, models
