@@ -3,7 +3,7 @@
 //
 // Replaces shadertemplate_vk_conv2d.comp:148-347 and shadertemplate_vk_conv2d_1x1.comp:68-210 of the reference.
 // This is the always-correct variant; GEMM-shaped layers are routed to conv2d_mfma.hip and the ESPCN chain to
-// espcn_fused.hip by snnhip_conv2d_plan_create / snnhip_chain_plan_create.
+// espcn_fused.hip (chain planner: chain_fuse.hip) by snnhip_conv2d_plan_create / snnhip_chain_plan_create.
 //
 // Work decomposition (wave64):
 //   block  = 256 threads = 32x8 output pixels x 16 output channels

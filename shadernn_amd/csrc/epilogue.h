@@ -81,7 +81,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 }
 
 // The u8_out contract (include/snnhip.h, snnhip_u8_out_plan_create): q = clamp(rint(fmaf(x, scale, offset)), 0, 255), ties to even, NaN -> 0.
-// frame_u8.hip's stand-alone kernel and kernel B's 8-bit epilogue (chain rule B8, espcn_fused.hip) both call this one function.
+// frame_u8.hip's stand-alone kernel and kernel B's 8-bit epilogue (chain rule B8 of chain_fuse.hip; espcn_d2s_b_body.h) both call this one function.
 __device__ __forceinline__ unsigned quantize_u8(float x, float scale, float offset) {
     float v = rintf(fmaf(x, scale, offset));
     v = v >= 0.0f ? v : 0.0f; // NaN fails the test: 0

@@ -1,0 +1,28 @@
+// espcn_common.h -- what the three ESPCN kernel units (espcn_fused.hip, espcn_d2s_mfma.hip, espcn_f16.hip) share.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace snnhip {
+
+// XCD-aware tile order (guide T1): workgroup b runs on XCD b % 8 and every XCD has a private 4 MiB L2.  Handing each XCD
+// a contiguous run of tiles keeps the halo rows/columns that neighbouring tiles share inside one L2 instead of
+// re-fetching them through the fabric.  Bijective for any grid size; purely a performance hint.
+__device__ __forceinline__ int xcd_tile_order(int b, int nb) {
+    const int q = nb >> 3, r = nb & 7;
+    const int xcd = b & 7, k = b >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
+// Chain rule A8: an 8-bit input frame normalised while the tile is staged, y = (float(u) - mean) * norm (snnhip_u8_in_plan_create's map)
+struct U8InCfg {
+    float mean, norm;
+};
+// Chain rule B8: the output frame quantised in the epilogue, q = quantize_u8(o, scale, offset) (snnhip_u8_out_plan_create's map)
+struct U8OutCfg {
+    float scale, offset;
+};
+
+// MFMA row of a depth-to-space tail (kernel B for r = 3 / 4, kernel B16): row 4*dy + dx holds channel r*dy + dx (r = 2, 3, 4); -1 = the row stays zero
+inline int espcn_d2s_row_channel(int r, int row) { return ((row & 3) < r && (row >> 2) < r) ? r * (row >> 2) + (row & 3) : -1; }
+
+} // namespace snnhip

@@ -1,4 +1,4 @@
-// espcn_d2s_b_body.h -- the body of kernel B's direct form (espcn_fused.hip), #included by its two kernels: rule B's (TOut = float) and rule B8's
+// espcn_d2s_b_body.h -- the body of kernel B's direct form (espcn_fused.hip; the rules are chain_fuse.hip's), #included by its two kernels: rule B's (TOut = float) and rule B8's
 // (TOut = unsigned char: the epilogue quantises with quantize_u8(o, qout.scale, qout.offset), snnhip_u8_out_plan_create's map, and stores two
 // 2-byte pairs instead of two float2).  Textual inclusion for the reason espcn_wino_a_body.h gives.  In scope: TW, TH, SIMPLE, the type TOut, the
 // kernel arguments p, qout, x, w, ep, y.

@@ -1,18 +1,15 @@
-// espcn_d2s_mfma.h -- chain rule B for upscale factors 3 and 4 (espcn_d2s_mfma.hip): what the chain planner (espcn_fused.hip) needs to launch it.
+// espcn_d2s_mfma.h -- chain rule B for upscale factors 3 and 4 (espcn_d2s_mfma.hip): what the chain planner (chain_fuse.hip) needs to launch it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "epilogue.h"
+#include "espcn_fused.h"
 
 namespace snnhip {
 
 constexpr int kD2sMfmaTW = 32, kD2sMfmaTH = 8; // low-resolution pixels per block
 
-struct EspcnD2sParams {
-    int N, H, W, tilesX, tilesY; // input [N, H, W, 16]; tiles of kD2sMfmaTW x kD2sMfmaTH
-    ActCfg act;
-    unsigned magicX, magicY; // ceil(2^32 / tilesX), ceil(2^32 / tilesY): tile decode without integer division
-};
+using EspcnD2sParams = FusedBParams; // input [N, H, W, 16]; tiles of kD2sMfmaTW x kD2sMfmaTH; same fields, same tile decode as kernel B for upscale 2
 
 // Conv2D 3x3 (16 -> r*r) + act -> depth-to-space(r) + tanh in one launch, r = 3 or 4.  w: the lane-ordered A-operand image (36 x 64 floats, MFMA
 // row 4*dy + dx = channel r*dy + dx), ep: 16 x {scale, shift} in MFMA row order.  u8out: y is an 8-bit frame, q = quantize_u8(o, qscale, qoffset).

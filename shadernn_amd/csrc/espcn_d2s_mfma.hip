@@ -1,8 +1,9 @@
 // espcn_d2s_mfma.hip -- chain rule B for upscale factors R = 3 and 4: conv 3x3 (16 -> R*R) + act -> depth-to-space(R) + tanh on the fp32 matrix
 // cores (v_mfma_f32_16x16x4_f32), and its 8-bit form (rule B8).  One body for both kernels, espcn_d2s_mfma_body.h; the rule itself (pattern match,
-// weight image, cost) is in the chain planner, espcn_fused.hip.  R = 2 keeps its own kernels there.  DESIGN.md section 4.10.
+// weight image, cost) is in the chain planner, chain_fuse.hip.  R = 2 keeps its own kernels in espcn_fused.hip.  DESIGN.md section 4.10.
 #include <hip/hip_ext.h>
 
+#include "espcn_common.h"
 #include "espcn_d2s_mfma.h"
 #include "snnhip_internal.h"
 
@@ -10,17 +11,6 @@ namespace snnhip {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// XCD-aware tile order, as espcn_fused.hip: workgroup b runs on XCD b % 8; each XCD gets a contiguous run of tiles
-__device__ __forceinline__ int xcd_tile_order(int b, int nb) {
-    const int q = nb >> 3, r = nb & 7;
-    const int xcd = b & 7, k = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
-struct U8OutCfg {
-    float scale, offset;
-};
 
 template <int R, bool SIMPLE>
 __global__ __launch_bounds__(256, 4) void conv3x3_c16oR_d2s_tanh_kernel(EspcnD2sParams p, const float* __restrict__ x, const float* __restrict__ w,

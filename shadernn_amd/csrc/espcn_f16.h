@@ -1,9 +1,10 @@
-// espcn_f16.h -- the fp16 ESPCN chain rules A16 / B16 (espcn_f16.hip): what the chain planner (espcn_fused.hip) needs to pack their weights and
+// espcn_f16.h -- the fp16 ESPCN chain rules A16 / B16 (espcn_f16.hip): what the chain planner (chain_fuse.hip) needs to pack their weights and
 // launch them.  Opt-in, SNNHIP_ESPCN_F16=1.  DESIGN.md section 4.11.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "epilogue.h"
+#include "espcn_common.h"
 
 namespace snnhip {
 
@@ -16,14 +17,11 @@ constexpr int kEspcnF16TW_B = 32, kEspcnF16TH_B = 8;  // kernel B16: a wave owns
 constexpr int kEspcnF16W3Halfs = 4 * 64 * 8 + 64 * 4;
 constexpr int kEspcnF16W1Halfs = 64 * 8; // conv1 (1 -> 16, up to 25 taps): one K-step of 32
 
-// MFMA row of the depth-to-space tail: row 4*dy + dx holds channel r*dy + dx (r = 2, 3, 4); -1 = the row stays zero
-inline int espcn_f16_row_channel(int r, int row) { return ((row & 3) < r && (row >> 2) < r) ? r * (row >> 2) + (row & 3) : -1; }
-
 // Lane-ordered fp16 A-operand image of a 3x3 convolution, K ordered tap-major, channel-minor (k = 16*tap + ic):
 //   out[(s*64 + lane)*8 + j]   = W[ch(lane & 15)][ic = 8*(g & 1) + j][tap = 2*s + (g >> 1)]      s = 0..3, g = lane >> 4, j = 0..7
 //   out[2048 + lane*4 + j]     = W[ch(lane & 15)][ic = 4*g + j][tap = 8]                          j = 0..3
 // w_oihw is [OC][16][3][3] fp32 and is rounded to nearest even, as the fp16 convolution plans round their weights.  r = 0: row = output channel
-// (OC = 16); r = 2, 3, 4: espcn_f16_row_channel (OC = r*r).
+// (OC = 16); r = 2, 3, 4: espcn_d2s_row_channel, espcn_common.h (OC = r*r).
 void espcn_f16_pack_w3(const float* w_oihw, int r, _Float16* out);
 // conv1 (1 -> 16, k x k, k*k <= 32): out[lane*8 + j] = W[oc = lane & 15][tap = 8*(lane >> 4) + j], zero from tap k*k on
 void espcn_f16_pack_w1(const float* w_oihw, int k, _Float16* out);

@@ -1,5 +1,5 @@
 // espcn_f16.hip -- the fp16 ESPCN chain in two launches on the f16 matrix cores (v_mfma_f32_16x16x32_f16 / v_mfma_f32_16x16x16_f16), opt-in with
-// SNNHIP_ESPCN_F16=1; the rules themselves (pattern match, cost) are in the chain planner, espcn_fused.hip.  DESIGN.md section 4.11.
+// SNNHIP_ESPCN_F16=1; the rules themselves (pattern match, cost) are in the chain planner, chain_fuse.hip.  DESIGN.md section 4.11.
 //
 //   kernel A16     conv k x k (1 -> 16, k = 3 or 5) + act -> conv 3x3 (16 -> 16) + act          fp16 [N,H,W,1] (or an 8-bit frame) -> fp16 [N,H,W,16]
 //   kernel B16<R>  conv 3x3 (16 -> R*R) + act -> depth-to-space(R) + tanh,  R = 2, 3, 4          fp16 [N,H,W,16] -> fp16 [N,R*H,R*W,1] (or an 8-bit frame)
@@ -32,13 +32,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// XCD-aware tile order, as espcn_fused.hip: workgroup b runs on XCD b % 8; each XCD gets a contiguous run of tiles
-__device__ __forceinline__ int xcd_tile_order(int b, int nb) {
-    const int q = nb >> 3, r = nb & 7;
-    const int xcd = b & 7, k = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
 
 // the A operand of a 3x3 convolution with 16 input channels (espcn_f16_pack_w3's image): 18 VGPRs, held for the whole kernel
 struct W3Regs {
@@ -208,7 +201,7 @@ __global__ __launch_bounds__(256) void espcn_f16_conv_pair_kernel(EspcnF16AParam
 
 // ---- kernel B16<R> (TOut = _Float16) and its 8-bit form (TOut = unsigned char: q = quantize_u8(float(half(tanh)), qscale, qoffset),
 // snnhip_u8_out_plan_create's map on the fp16 value the stand-alone chain would have stored).  The 16 MFMA rows are not the channels in order:
-// row 4*dy + dx holds channel R*dy + dx (espcn_f16_row_channel), so lane (px, g < R) ends up with the R consecutive pixels of output row R*y + g
+// row 4*dy + dx holds channel R*dy + dx (espcn_d2s_row_channel), so lane (px, g < R) ends up with the R consecutive pixels of output row R*y + g
 // that its low-resolution pixel owns and the 16 lanes of one g hold 16*R consecutive pixels of that row (espcn_d2s_mfma_body.h).
 template <int R, typename TOut, bool SIMPLE>
 __global__ __launch_bounds__(256) void espcn_f16_d2s_kernel(EspcnF16BParams p, const _Float16* __restrict__ x, const _Float16* __restrict__ w,
@@ -322,7 +315,7 @@ void espcn_f16_pack_w3(const float* w_oihw, int r, _Float16* out) {
     for (int i = 0; i < kEspcnF16W3Halfs; ++i) out[i] = static_cast<_Float16>(0.0f);
     for (int lane = 0; lane < 64; ++lane) {
         const int row = lane & 15, g = lane >> 4;
-        const int ch = r == 0 ? row : espcn_f16_row_channel(r, row);
+        const int ch = r == 0 ? row : espcn_d2s_row_channel(r, row);
         if (ch < 0) continue;
         const float* wc = w_oihw + static_cast<size_t>(ch) * 16 * 9;
         for (int s = 0; s < 4; ++s)

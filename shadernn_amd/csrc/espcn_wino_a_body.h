@@ -1,4 +1,4 @@
-// espcn_wino_a_body.h -- the body of kernel A's Winograd form (espcn_fused.hip), #included by its two kernels: rule A's (TIn = float) and rule A8's
+// espcn_wino_a_body.h -- the body of kernel A's Winograd form (espcn_fused.hip; the rules are chain_fuse.hip's), #included by its two kernels: rule A's (TIn = float) and rule A8's
 // (TIn = unsigned char: the 8-bit frame is normalised while the tile is staged, y = (float(u) - qin.mean) * qin.norm, snnhip_u8_in_plan_create's
 // map; taps outside the image stay 0 in the NORMALISED domain, as the separate u8_in launch in front of rule A gives them).  Textual inclusion
 // rather than a shared __device__ function: inlining a body through a call changed the fp32 kernels' register allocation (scratch spills in

@@ -5,7 +5,7 @@
 // (P = N*H*W pixels, C = 1..4, T = float or _Float16.)  The reference normalises on the host or in a resize pass (image.cpp:712-796,
 // ImageTexture::convertToRGBA32FAndNormalize) and reads results back as floats; ColorFormat::R8 / RGB8 / RGBA8 (color.h) name these formats.
 // Both are HBM-bound streams: one lane takes 4 pixels = 4C bytes (C dwords) and 4C elements (C 16-byte fp32 or 8-byte fp16 accesses), grid-stride;
-// the last P % 4 pixels take a scalar tail.  Chain rules A8 / B8 (espcn_fused.hip) compute the same two expressions inside the ESPCN kernels.
+// the last P % 4 pixels take a scalar tail.  Chain rules A8 / B8 (chain_fuse.hip) compute the same two expressions inside the ESPCN kernels.
 #include "epilogue.h"
 #include "plan_util.h"
 #include "snnhip_internal.h"

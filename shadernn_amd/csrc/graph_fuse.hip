@@ -1,6 +1,6 @@
 // graph_fuse.hip -- snnhip_graph_fuse: the single graph walk that looks for fusable operator groups (include/snnhip.h).
 //
-// The fusion RULES live in the chain planner (make_chain_plan, espcn_fused.hip: A/B/C ESPCN kernels, D [UpSampling2D ->] Pad -> Conv2D,
+// The fusion RULES live in the chain planner (make_chain_plan, chain_fuse.hip: A/B/C ESPCN kernels, D [UpSampling2D ->] Pad -> Conv2D,
 // E Conv2D -> Add, F Conv2D -> InstanceNorm).  This file only decides which groups of a DAG are offered to it:
 //   0. inverted-residual blocks with a skip connection: Add(project(depthwise(expand(X))), X) (MobileNetV2);
 //   1. residual pairs: an Add one of whose inputs is a convolution that nobody else reads (ResNet skip connections);

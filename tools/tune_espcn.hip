@@ -1,5 +1,6 @@
 // tune_espcn.hip -- developer harness (not part of the product): times template variants of the fused ESPCN kernels
-// on a 1080p frame with hipEvents.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune_espcn.hip -o /tmp/tune
+// on a 1080p frame with hipEvents.  It compiles the kernel unit (espcn_fused.hip: kernels, launch functions, weight images) into itself so that
+// SNNHIP_STAMP and the template arguments are its own.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/tune_espcn.hip -o tools/tune_espcn
 #include <hip/hip_runtime.h>
 #ifdef PHASE_TIMING
 __device__ long long g_stamps[8192 * 4 * 8];
@@ -28,32 +29,14 @@ __device__ unsigned g_hwid[8192 * 4 * 2];
 
 using namespace snnhip;
 
+// what the kernel unit needs from the rest of the library
 namespace snnhip {
 void set_error(const char* fmt, ...) { (void) fmt; }
-std::vector<float> make_epilogue_table(int, int, int, const float*, int, const float*, const float*, const float*, const float*) { return {}; }
+bool trace_active() { return false; }
+int trace_events(const void*, hipStream_t, hipEvent_t*, hipEvent_t*) { return 0; }
 } // namespace snnhip
-int snnhip_plan::upload(const float*, size_t, float**) { return 0; }
-int snnhip_plan::profBegin(int) { return 0; }
-int snnhip_plan::profEnd(int) { return 0; }
-int snnhip_plan::profAcquire(int, hipEvent_t*, hipEvent_t*) { return 0; }
-namespace snnhip {
-int make_conv2d_mfma_plan(snnhip_ctx*, const ConvGeom&, const float*, const std::vector<float>&, snnhip_plan**) { return 0; }
-bool instancenorm_plan_desc(const snnhip_plan*, snnhip_instancenorm_desc*) { return false; }
-int instancenorm_apply_tile_stats(snnhip_plan*, const float*, int, int, int, int, snnhip_tensor*) { return 0; }
-}
 static snnhip::FusedBParams mkB(int H, int W, int tw, int th) {
-    snnhip::FusedBParams p{1, H, W, (W + tw - 1) / tw, (H + th - 1) / th, snnhip::make_act_cfg(0, 0.f)};
-    p.magicX = static_cast<unsigned>((0x100000000ull + static_cast<unsigned>(p.tilesX) - 1) / static_cast<unsigned>(p.tilesX));
-    p.magicY = static_cast<unsigned>((0x100000000ull + static_cast<unsigned>(p.tilesY) - 1) / static_cast<unsigned>(p.tilesY));
-    return p;
-}
-extern "C" int snnhip_tensor_alloc(snnhip_ctx*, int, int, int, int, int, snnhip_tensor**) { return 0; }
-extern "C" int snnhip_tensor_free(snnhip_tensor*) { return 0; }
-namespace snnhip {
-size_t espcn_stream_step_size() { return 0; }
-void espcn_stream_configure(void*, int, int, int, int, int, float, int, float, int, float, int) {}
-void espcn_stream_describe(const void*, char*, size_t) {}
-int espcn_stream_launch(hipStream_t, const void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*, float*) { return 0; }
+    return snnhip::espcn_b_params(1, H, W, tw, th, snnhip::make_act_cfg(0, 0.f));
 }
 
 #define CK(x)                                                                 \
@@ -106,22 +89,6 @@ float timeOverlap(const float* x, const float* w, float* mid, float* mid2, float
     CK(hipEventRecord(e2, s2));
     CK(hipStreamWaitEvent(s1, e2, 0));
     CK(hipEventRecord(b, s1));
-    CK(hipEventSynchronize(b));
-    float ms = 0;
-    CK(hipEventElapsedTime(&ms, a, b));
-    return 1e3f * ms / reps;
-}
-
-float timeBD(const float* x, const float* w, const float* e, const float* zeros, float* y, int H, int W, int reps, int blocksPerCU) {
-    FusedBParams p = mkB(H, W, 32, 8);
-    dim3 grid(256 * blocksPerCU);
-    hipEvent_t a, b;
-    CK(hipEventCreate(&a));
-    CK(hipEventCreate(&b));
-    for (int i = 0; i < 5; ++i) hipLaunchKernelGGL((conv3x3_c16o4_d2s_tanh_dma_kernel<true>), grid, dim3(256), 0, 0, p, x, w, e, zeros, y);
-    CK(hipEventRecord(a));
-    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL((conv3x3_c16o4_d2s_tanh_dma_kernel<true>), grid, dim3(256), 0, 0, p, x, w, e, zeros, y);
-    CK(hipEventRecord(b));
     CK(hipEventSynchronize(b));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, a, b));
@@ -287,12 +254,6 @@ int main() {
     printf("W<5,8,3> wino  %.1f us\n", timeW<5, 8, 3>(x, w, w, w, w, mid, H, W, R));
     printf("A<5,64,8,U3,W3>  %.1f us\n", timeA<5, 64, 8, 3, 3>(x, w, w, w, w, mid, H, W, R));
     printf("BW wino    %.1f us\n", timeBW(mid, w, w, y, H, W, R));
-    {
-        float* zeros;
-        CK(hipMalloc(&zeros, 256));
-        CK(hipMemset(zeros, 0, 256));
-        for (int bpc : {2, 3}) printf("BD dma persistent x%d %.1f us\n", bpc, timeBD(mid, w, w, zeros, y, H, W, R, bpc));
-    }
     printf("B<32,8>    %.1f us\n", timeB<32, 8>(mid, w, w, y, H, W, R));
     printf("B<64,4>    %.1f us\n", timeB<64, 4>(mid, w, w, y, H, W, R));
     printf("B<16,16>   %.1f us\n", timeB<16, 16>(mid, w, w, y, H, W, R));
