@@ -53,6 +53,25 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
  * call, the tensors are the model's own, so a recorded graph replays across calls.  -1 when the model has no 8-bit frame at that end. */
 int snn_model_upload_frame_u8(snn_model* m, const unsigned char* nhwc);
 int snn_model_download_frame_u8(snn_model* m, unsigned char* nhwc);
+/* 16-bit frames at the model's ends (10 / 12 / 16-bit video in 2-byte containers): SNN_IO_R16 / RGB16 / RGBA16 beside the formats above, through
+ * a struct and an entry point of their own -- snn_frame_io and snn_model_create5 keep their layout and behaviour.  The input frame is
+ * y = (float(u >> in_shift) - in_means[c]) * in_norms[c], the output q = unsigned(clamp(rint(fmaf(x, out_scale[c], out_offset[c])), 0,
+ * out_maxval)) << out_shift (include/snnhip.h, snnhip_u16_in_plan_create / _u16_out_plan_create); the three fields are ignored at an end that is
+ * not 16-bit.  Low-aligned 10 / 12-bit: out_maxval 1023 / 4095, shifts 0; P010-style high-aligned 10-bit: out_maxval 1023, shifts 6; full
+ * 16-bit: out_maxval 65535.  For ESPCN in fp32 the conversions run inside its two fused kernels, as the 8-bit ones do. */
+enum { SNN_IO_R16 = 0x101, SNN_IO_RGB16 = 0x103, SNN_IO_RGBA16 = 0x104 }; /* (low byte = channel count) */
+typedef struct snn_frame_io2 {
+    int in_format, out_format;
+    float in_means[4], in_norms[4];
+    float out_scale[4], out_offset[4];
+    int in_shift, out_maxval, out_shift;
+} snn_frame_io2;
+int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_frame_io2* io, snn_model** out);
+/* [batch][H][W][C] 16-bit elements into the model's input frame / out of its output frame; -1 when that end is not a 16-bit frame (the _u8 calls
+ * likewise return -1 on a 16-bit end). */
+int snn_model_upload_frame_u16(snn_model* m, const unsigned short* nhwc);
+int snn_model_download_frame_u16(snn_model* m, unsigned short* nhwc);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

@@ -72,7 +72,9 @@ enum { SNNHIP_PAD_NONE = 0, SNNHIP_PAD_CONSTANT = 1, SNNHIP_PAD_REPLICATE = 2, S
  * tensors hold halfs in HBM, kernels convert on load, accumulate in fp32 (fp16-input MFMA for the convolutions) and round to nearest even
  * on store.  The host-side upload / download entry points always speak fp32 and convert. */
 enum { SNNHIP_F32 = 0, SNNHIP_F16 = 1, SNNHIP_U8 = 2 /* 8-bit frames: input of snnhip_image_u8_plan_create / snnhip_u8_in_plan_create, output of
-                                                          snnhip_u8_out_plan_create, and the two ends of a chain that starts / ends with those plans */ };
+                                                          snnhip_u8_out_plan_create, and the two ends of a chain that starts / ends with those plans */,
+       SNNHIP_U16 = 3 /* 16-bit frames (10 / 12 / 16-bit video in 2-byte containers): input of snnhip_u16_in_plan_create, output of
+                         snnhip_u16_out_plan_create, and the two ends of a chain that starts / ends with those plans */ };
 
 /* ---- context -------------------------------------------------------------------------------------- */
 
@@ -333,7 +335,7 @@ typedef struct {
     float means[4], norms[4];
 } snnhip_image_u8_desc;
 int snnhip_image_u8_plan_create(snnhip_ctx* ctx, const snnhip_image_u8_desc* desc, snnhip_plan** out);
-/* raw byte upload for SNNHIP_U8 tensors (nbytes must equal snnhip_tensor_bytes) */
+/* raw byte upload for SNNHIP_U8 / SNNHIP_U16 tensors (nbytes must equal snnhip_tensor_bytes; 16-bit elements in host byte order) */
 int snnhip_tensor_upload_raw(snnhip_tensor* t, const void* host, size_t nbytes);
 /* raw byte download (any dtype; nbytes must equal snnhip_tensor_bytes): stream sync + D2H, the counterpart of snnhip_tensor_upload_raw */
 int snnhip_tensor_download_raw(const snnhip_tensor* t, void* host, size_t nbytes);
@@ -357,6 +359,34 @@ typedef struct {
     float scale[4], offset[4];
 } snnhip_u8_out_desc;
 int snnhip_u8_out_plan_create(snnhip_ctx* ctx, const snnhip_u8_out_desc* desc, snnhip_plan** out);
+
+/* 16-bit frames at both ends of a model: 10-, 12- and 16-bit video in 2-byte unsigned containers (SNNHIP_U16), channel count kept.
+ *   u16_in :  U16 [N][H][W][C] -> dtype [N][H][W][C],   y = (float(u >> shift) - means[c]) * norms[c]      (a subtract, then a multiply: no fma;
+ *             an fp16 output rounds that fp32 value to nearest even)
+ *   u16_out:  dtype [N][H][W][C] -> U16 [N][H][W][C],   q = unsigned(clamp(rint(fmaf(x, scale[c], offset[c])), 0, maxval)) << shift
+ * The u16_out contract: fmaf in fp32 (an fp16 input is widened exactly first), rounding to nearest with ties to even, NaN -> 0,
+ * +inf -> maxval << shift, -inf -> 0.  It is the single definition of the 16-bit maps.  `shift` and `maxval` name the container layout:
+ *   low-aligned 10 / 12-bit (yuv420p10le, gray12le):   maxval 1023 / 4095,  shift 0
+ *   high-aligned 10-bit (P010: value in the top bits): maxval 1023,         shift 6
+ *   full 16-bit:                                       maxval 65535,        shift 0
+ * u16_in ignores the bits below `shift`; u16_out writes them as 0.  C is 1..4; dtype SNNHIP_F32 or SNNHIP_F16; shift 0..15.  u16_out_plan_create
+ * returns SNNHIP_E_INVALID with a message unless 1 <= maxval <= 65535 and (maxval << shift) <= 65535.  The chain planner folds both into the fused
+ * ESPCN kernels (C == 1, dtype = the launch's own: the fp32 kernels, and the fp16 ones under SNNHIP_ESPCN_F16=1; at the chain's ends), bit for bit what the separate launches give, out-of-image taps
+ * of kernel A staying 0 in the NORMALISED domain; every other chain runs them as launches of their own. */
+typedef struct {
+    int N, H, W, C;
+    int dtype;
+    float means[4], norms[4];
+    int shift;
+} snnhip_u16_in_desc;
+int snnhip_u16_in_plan_create(snnhip_ctx* ctx, const snnhip_u16_in_desc* desc, snnhip_plan** out);
+typedef struct {
+    int N, H, W, C;
+    int dtype;
+    float scale[4], offset[4];
+    int maxval, shift;
+} snnhip_u16_out_desc;
+int snnhip_u16_out_plan_create(snnhip_ctx* ctx, const snnhip_u16_out_desc* desc, snnhip_plan** out);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

@@ -86,6 +86,15 @@ class U8OutDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("scale", C.c_float * 4), ("offset", C.c_float * 4)]
 
 
+class U16InDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("means", C.c_float * 4), ("norms", C.c_float * 4), ("shift", C.c_int)]
+
+
+class U16OutDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("scale", C.c_float * 4), ("offset", C.c_float * 4), ("maxval", C.c_int),
+                ("shift", C.c_int)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -158,6 +167,8 @@ SIGNATURES = {
     "snnhip_tensor_download_raw": (C.c_int, [_P, _P, C.c_size_t]),
     "snnhip_u8_in_plan_create": (C.c_int, [_P, C.POINTER(U8InDesc), C.POINTER(_P)]),
     "snnhip_u8_out_plan_create": (C.c_int, [_P, C.POINTER(U8OutDesc), C.POINTER(_P)]),
+    "snnhip_u16_in_plan_create": (C.c_int, [_P, C.POINTER(U16InDesc), C.POINTER(_P)]),
+    "snnhip_u16_out_plan_create": (C.c_int, [_P, C.POINTER(U16OutDesc), C.POINTER(_P)]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -303,6 +314,7 @@ class Context:
 
 
 F32, F16, U8 = 0, 1, 2  # SNNHIP_F32 / SNNHIP_F16 / SNNHIP_U8 (8-bit frames: image_u8_plan / u8_in_plan input, u8_out_plan output)
+U16 = 3  # SNNHIP_U16 (16-bit frames: u16_in_plan input, u16_out_plan output)
 
 
 class Tensor:
@@ -322,7 +334,13 @@ class Tensor:
 
     @staticmethod
     def from_numpy(ctx, a, dtype=F32):
-        """dtype=U8: the array's bytes as an 8-bit tensor (uploaded raw)."""
+        """dtype=U8 / U16 (or a uint16 array): the array's bytes as an 8-bit / 16-bit frame tensor (uploaded raw)."""
+        if dtype == U16 or (dtype == F32 and getattr(a, "dtype", None) == np.uint16):
+            a = np.ascontiguousarray(a, dtype=np.uint16)
+            assert a.ndim == 4, "expected NHWC"
+            t = Tensor(ctx, *a.shape, dtype=U16)
+            t.upload_u16(a)
+            return t
         if dtype == U8:
             a = np.ascontiguousarray(a, dtype=np.uint8)
             assert a.ndim == 4, "expected NHWC"
@@ -363,6 +381,19 @@ class Tensor:
         assert self.dtype == U8, self.dtype
         out = np.empty(self.shape, dtype=np.uint8)
         check(lib().snnhip_tensor_download_raw(self.h, out.ctypes.data_as(_P), out.size))
+        return out
+
+    def upload_u16(self, a):
+        """Raw upload of a 16-bit frame tensor (dtype=U16)."""
+        a = np.ascontiguousarray(a, dtype=np.uint16)
+        assert self.dtype == U16 and a.size == int(np.prod(self.shape)), (a.shape, self.shape)
+        check(lib().snnhip_tensor_upload_raw(self.h, a.ctypes.data_as(_P), a.nbytes))
+
+    def numpy_u16(self):
+        """Raw download of a 16-bit frame tensor (dtype=U16) as uint16 NHWC (numpy() speaks float32 and refuses frame tensors)."""
+        assert self.dtype == U16, self.dtype
+        out = np.empty(self.shape, dtype=np.uint16)
+        check(lib().snnhip_tensor_download_raw(self.h, out.ctypes.data_as(_P), out.nbytes))
         return out
 
     def argmax(self, n=0):
@@ -634,6 +665,22 @@ def u8_in_plan(ctx, N, H, W, Cc, means=(0, 0, 0, 0), norms=(1, 1, 1, 1), dtype=F
     d = U8InDesc(N, H, W, Cc, dtype, (C.c_float * 4)(*means), (C.c_float * 4)(*norms))
     h = _P()
     check(lib().snnhip_u8_in_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def u16_in_plan(ctx, N, H, W, Cc, means=(0, 0, 0, 0), norms=(1, 1, 1, 1), shift=0, dtype=F32):
+    """U16 [N][H][W][Cc] -> dtype [N][H][W][Cc]: y = (float(u >> shift) - means[c]) * norms[c]."""
+    d = U16InDesc(N, H, W, Cc, dtype, (C.c_float * 4)(*means), (C.c_float * 4)(*norms), shift)
+    h = _P()
+    check(lib().snnhip_u16_in_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def u16_out_plan(ctx, N, H, W, Cc, scale=(1, 1, 1, 1), offset=(0, 0, 0, 0), maxval=65535, shift=0, dtype=F32):
+    """dtype [N][H][W][Cc] -> U16: q = unsigned(clamp(rint(fmaf(x, scale[c], offset[c])), 0, maxval)) << shift, NaN -> 0."""
+    d = U16OutDesc(N, H, W, Cc, dtype, (C.c_float * 4)(*scale), (C.c_float * 4)(*offset), maxval, shift)
+    h = _P()
+    check(lib().snnhip_u16_out_plan_create(ctx.h, C.byref(d), C.byref(h)))
     return Plan(ctx, h)
 
 

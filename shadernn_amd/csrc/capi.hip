@@ -657,7 +657,7 @@ int snnhip_guard_selftest(snnhip_ctx* ctx, snnhip_tensor* t, long offset) {
 
 int snnhip_tensor_alloc(snnhip_ctx* ctx, int n, int h, int w, int c, int dtype, snnhip_tensor** out) {
     SNNHIP_REQUIRE(ctx && out, "tensor_alloc: null argument");
-    SNNHIP_REQUIRE(dtype == SNNHIP_F32 || dtype == SNNHIP_F16 || dtype == SNNHIP_U8, "tensor_alloc: dtype %d not implemented", dtype);
+    SNNHIP_REQUIRE(dtype == SNNHIP_F32 || dtype == SNNHIP_F16 || dtype == SNNHIP_U8 || dtype == SNNHIP_U16, "tensor_alloc: dtype %d not implemented", dtype);
     SNNHIP_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0, "tensor_alloc: bad dims %dx%dx%dx%d", n, h, w, c);
     auto* t = new (std::nothrow) snnhip_tensor();
     if (!t) return SNNHIP_E_NOMEM;
@@ -679,7 +679,7 @@ int snnhip_tensor_alloc(snnhip_ctx* ctx, int n, int h, int w, int c, int dtype, 
 
 int snnhip_tensor_wrap(snnhip_ctx* ctx, void* device_ptr, int n, int h, int w, int c, int dtype, snnhip_tensor** out) {
     SNNHIP_REQUIRE(ctx && out && device_ptr, "tensor_wrap: null argument");
-    SNNHIP_REQUIRE(dtype == SNNHIP_F32 || dtype == SNNHIP_F16 || dtype == SNNHIP_U8, "tensor_wrap: dtype %d not implemented", dtype);
+    SNNHIP_REQUIRE(dtype == SNNHIP_F32 || dtype == SNNHIP_F16 || dtype == SNNHIP_U8 || dtype == SNNHIP_U16, "tensor_wrap: dtype %d not implemented", dtype);
     SNNHIP_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0, "tensor_wrap: bad dims %dx%dx%dx%d", n, h, w, c);
     SNNHIP_REQUIRE((reinterpret_cast<uintptr_t>(device_ptr) & 15) == 0, "tensor_wrap: pointer must be 16-byte aligned");
     auto* t = new (std::nothrow) snnhip_tensor();
@@ -711,6 +711,7 @@ int snnhip_tensor_dtype(const snnhip_tensor* t) { return t ? t->dtype : -1; }
 int snnhip_tensor_upload(snnhip_tensor* t, const float* host) {
     SNNHIP_REQUIRE(t && host, "tensor_upload: null argument");
     SNNHIP_REQUIRE(t->dtype != SNNHIP_U8, "tensor_upload: 8-bit image tensors take snnhip_tensor_upload_raw");
+    SNNHIP_REQUIRE(t->dtype != SNNHIP_U16, "tensor_upload: 16-bit frame tensors take snnhip_tensor_upload_raw");
     if (t->dtype == SNNHIP_F16) {
         std::vector<_Float16> tmp(t->count());
         for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = static_cast<_Float16>(host[i]);
@@ -726,6 +727,7 @@ int snnhip_tensor_upload(snnhip_tensor* t, const float* host) {
 int snnhip_tensor_download(const snnhip_tensor* t, float* host) {
     SNNHIP_REQUIRE(t && host, "tensor_download: null argument");
     SNNHIP_REQUIRE(t->dtype != SNNHIP_U8, "tensor_download: not available for 8-bit image tensors");
+    SNNHIP_REQUIRE(t->dtype != SNNHIP_U16, "tensor_download: not available for 16-bit frame tensors (snnhip_tensor_download_raw)");
     if (t->dtype == SNNHIP_F16) {
         std::vector<_Float16> tmp(t->count());
         SNNHIP_CHECK_HIP(hipMemcpyAsync(tmp.data(), t->data, t->bytes(), hipMemcpyDeviceToHost, t->ctx->stream));
@@ -798,6 +800,7 @@ __global__ void fill_half_kernel(_Float16* p, size_t n, float v) {
 int snnhip_tensor_fill(snnhip_tensor* t, float value) {
     SNNHIP_REQUIRE(t, "tensor_fill: null argument");
     SNNHIP_REQUIRE(t->dtype != SNNHIP_U8, "tensor_fill: not available for 8-bit image tensors");
+    SNNHIP_REQUIRE(t->dtype != SNNHIP_U16, "tensor_fill: not available for 16-bit frame tensors");
     size_t n = t->count();
     unsigned blocks = static_cast<unsigned>(std::min<size_t>((n + 255) / 256, 4096));
     if (t->dtype == SNNHIP_F16)
@@ -906,20 +909,22 @@ int snnhip_plan_run_n(snnhip_plan* plan, const snnhip_tensor* const* inputs, int
     SNNHIP_REQUIRE(plan && inputs && out && n_in > 0, "plan_run: null argument");
     for (int i = 0; i < n_in; ++i) SNNHIP_REQUIRE(inputs[i] && inputs[i]->data, "plan_run: input %d is null", i);
     SNNHIP_REQUIRE(out->data, "plan_run: output has no storage");
-    if (!plan->u8Input) {
-        for (int i = 0; i < n_in; ++i) SNNHIP_REQUIRE(inputs[i]->dtype != SNNHIP_U8, "plan_run: input %d is an 8-bit image tensor (%s)", i, plan->desc.c_str());
+    // a raw frame tensor (SNNHIP_U8 / SNNHIP_U16) is accepted exactly where the plan declares one
+    for (int i = 0; i < n_in; ++i) {
+        SNNHIP_REQUIRE(inputs[i]->dtype != SNNHIP_U8 || plan->rawInput == SNNHIP_U8, "plan_run: input %d is an 8-bit image tensor (%s)", i, plan->desc.c_str());
+        SNNHIP_REQUIRE(inputs[i]->dtype != SNNHIP_U16 || plan->rawInput == SNNHIP_U16, "plan_run: input %d is a 16-bit frame tensor (%s)", i, plan->desc.c_str());
     }
-    if (plan->u8Output) {
-        SNNHIP_REQUIRE(out->dtype == SNNHIP_U8, "plan_run: the output must be an 8-bit tensor (%s), got dtype %d", plan->desc.c_str(), out->dtype);
-    } else {
-        SNNHIP_REQUIRE(out->dtype != SNNHIP_U8, "plan_run: the output is an 8-bit image tensor (%s)", plan->desc.c_str());
-    }
+    if (plan->rawOutput == SNNHIP_U8) SNNHIP_REQUIRE(out->dtype == SNNHIP_U8, "plan_run: the output must be an 8-bit tensor (%s), got dtype %d", plan->desc.c_str(), out->dtype);
+    else SNNHIP_REQUIRE(out->dtype != SNNHIP_U8, "plan_run: the output is an 8-bit image tensor (%s)", plan->desc.c_str());
+    if (plan->rawOutput == SNNHIP_U16) SNNHIP_REQUIRE(out->dtype == SNNHIP_U16, "plan_run: the output must be a 16-bit tensor (%s), got dtype %d", plan->desc.c_str(), out->dtype);
+    else SNNHIP_REQUIRE(out->dtype != SNNHIP_U16, "plan_run: the output is a 16-bit frame tensor (%s)", plan->desc.c_str());
     if (!plan->anyDtype) {
-        for (int i = 0; i < n_in; ++i)
-            SNNHIP_REQUIRE(inputs[i]->dtype == (plan->u8Input && i == 0 ? SNNHIP_U8 : plan->dtype), "plan_run: input %d has dtype %d, the plan (%s) was built for %d", i,
-                           inputs[i]->dtype, plan->desc.c_str(), plan->u8Input && i == 0 ? SNNHIP_U8 : plan->dtype);
-        SNNHIP_REQUIRE(out->dtype == (plan->u8Output ? SNNHIP_U8 : plan->dtype), "plan_run: output has dtype %d, the plan (%s) was built for %d", out->dtype,
-                       plan->desc.c_str(), plan->u8Output ? SNNHIP_U8 : plan->dtype);
+        const int outDtype = plan->rawOutput >= 0 ? plan->rawOutput : plan->dtype;
+        for (int i = 0; i < n_in; ++i) {
+            const int inDtype = plan->rawInput >= 0 && i == 0 ? plan->rawInput : plan->dtype;
+            SNNHIP_REQUIRE(inputs[i]->dtype == inDtype, "plan_run: input %d has dtype %d, the plan (%s) was built for %d", i, inputs[i]->dtype, plan->desc.c_str(), inDtype);
+        }
+        SNNHIP_REQUIRE(out->dtype == outDtype, "plan_run: output has dtype %d, the plan (%s) was built for %d", out->dtype, plan->desc.c_str(), outDtype);
     }
     if (plan->profiling && !plan->profilesItself()) {
         int rc = plan->profBegin(0);

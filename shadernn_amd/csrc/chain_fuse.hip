@@ -107,22 +107,36 @@ struct FusedLaunch {
     // description.  false = this family (or the form selected) keeps the separate launch.
     virtual bool foldU8In(const snnhip_u8_in_desc&, std::string&) { return false; }
     virtual bool foldU8Out(const snnhip_u8_out_desc&, std::string&) { return false; }
+    // the same for the 16-bit frame conversions
+    virtual bool foldU16In(const snnhip_u16_in_desc&, std::string&) { return false; }
+    virtual bool foldU16Out(const snnhip_u16_out_desc&, std::string&) { return false; }
 };
 
 struct FusedA : FusedLaunch { // rules A / A8
     FusedAParams p{};
     int k1 = 5;
-    bool wino = true, u8in = false;
+    bool wino = true, u8in = false, u16in = false;
     U8InCfg qin{0.0f, 0.0f};
+    U16InCfg qin16{0.0f, 0.0f, 0};
     float *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
+        if (u16in)
+            return espcn_fused_a_u16_launch(ctx->stream, p, k1, qin16, ctx->props.multiProcessorCount, reinterpret_cast<const unsigned short*>(x), w1, w2, e1, e2, y,
+                                            evStart, evStop);
         return espcn_fused_a_launch(ctx->stream, p, k1, wino, u8in, qin, ctx->props.multiProcessorCount, x, w1, w2, e1, e2, y, evStart, evStop);
     }
     bool foldU8In(const snnhip_u8_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F32 || !wino || u8in) return false; // (SNNHIP_ESPCN_A=direct keeps the separate launch)
+        if (ui.dtype != SNNHIP_F32 || !wino || u8in || u16in) return false; // (SNNHIP_ESPCN_A=direct keeps the separate launch)
         u8in = true;
         qin = U8InCfg{ui.means[0], ui.norms[0]};
         rename_kernel(desc, "kernel=conv_kxk_c1o16_wino3x3_c16o16_kernel", "kernel=conv_kxk_c1o16_wino3x3_c16o16_u8_kernel");
+        return true;
+    }
+    bool foldU16In(const snnhip_u16_in_desc& ui, std::string& desc) override {
+        if (ui.dtype != SNNHIP_F32 || !wino || u8in || u16in) return false;
+        u16in = true;
+        qin16 = U16InCfg{ui.means[0], ui.norms[0], ui.shift};
+        rename_kernel(desc, "kernel=conv_kxk_c1o16_wino3x3_c16o16_kernel", "kernel=conv_kxk_c1o16_wino3x3_c16o16_u16_kernel");
         return true;
     }
 };
@@ -130,19 +144,30 @@ struct FusedA : FusedLaunch { // rules A / A8
 struct FusedB : FusedLaunch { // rules B / B8: upscale 2 on espcn_fused.hip's kernel B, 3 / 4 on the matrix-core kernel of espcn_d2s_mfma.hip
     FusedBParams p{};
     int r = 2;
-    bool wino = false, u8out = false;
+    bool wino = false, u8out = false, u16out = false;
     U8OutCfg qout{0.0f, 0.0f};
+    U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
     float *w = nullptr, *e = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
+        if (u16out && r == 2) return espcn_fused_b_u16_launch(ctx->stream, p, qout16, x, w, e, reinterpret_cast<unsigned short*>(y), evStart, evStop);
+        if (u16out) return espcn_d2s_mfma_u16_launch(ctx->stream, r, p, qout16, x, w, e, reinterpret_cast<unsigned short*>(y), evStart, evStop);
         if (r == 2) return espcn_fused_b_launch(ctx->stream, p, wino, u8out, qout, x, w, e, y, evStart, evStop);
         return espcn_d2s_mfma_launch(ctx->stream, r, p, u8out, qout.scale, qout.offset, x, w, e, y, evStart, evStop);
     }
     bool foldU8Out(const snnhip_u8_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F32 || wino || u8out) return false; // (SNNHIP_ESPCN_B=wino keeps the separate launch)
+        if (uo.dtype != SNNHIP_F32 || wino || u8out || u16out) return false; // (SNNHIP_ESPCN_B=wino keeps the separate launch)
         u8out = true;
         qout = U8OutCfg{uo.scale[0], uo.offset[0]};
         if (r == 2) rename_kernel(desc, "kernel=conv3x3_c16o4_d2s_tanh_kernel", "kernel=conv3x3_c16o4_d2s_tanh_u8_kernel");
         else rename_kernel(desc, "kernel=conv3x3_c16oR_d2s_tanh_kernel", "kernel=conv3x3_c16oR_d2s_tanh_u8_kernel");
+        return true;
+    }
+    bool foldU16Out(const snnhip_u16_out_desc& uo, std::string& desc) override {
+        if (uo.dtype != SNNHIP_F32 || wino || u8out || u16out) return false;
+        u16out = true;
+        qout16 = U16OutCfg{uo.scale[0], uo.offset[0], static_cast<float>(uo.maxval), uo.shift};
+        if (r == 2) rename_kernel(desc, "kernel=conv3x3_c16o4_d2s_tanh_kernel", "kernel=conv3x3_c16o4_d2s_tanh_u16_kernel");
+        else rename_kernel(desc, "kernel=conv3x3_c16oR_d2s_tanh_kernel", "kernel=conv3x3_c16oR_d2s_tanh_u16_kernel");
         return true;
     }
 };
@@ -150,18 +175,29 @@ struct FusedB : FusedLaunch { // rules B / B8: upscale 2 on espcn_fused.hip's ke
 struct FusedA16 : FusedLaunch { // rule A16 and its 8-bit form (espcn_f16.hip): w1, w2 hold halfs (espcn_f16_pack_w1 / _w3)
     EspcnF16AParams p{};
     int k1 = 5;
-    bool u8in = false;
+    bool u8in = false, u16in = false;
+    U16InCfg qin16{0.0f, 0.0f, 0};
     float *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
+        if (u16in)
+            return espcn_f16_a_u16_launch(ctx->stream, k1, p, qin16, reinterpret_cast<const unsigned short*>(x), reinterpret_cast<const _Float16*>(w1),
+                                          reinterpret_cast<const _Float16*>(w2), e1, e2, reinterpret_cast<_Float16*>(y), evStart, evStop);
         return espcn_f16_a_launch(ctx->stream, k1, p, u8in, x, reinterpret_cast<const _Float16*>(w1), reinterpret_cast<const _Float16*>(w2), e1, e2,
                                   reinterpret_cast<_Float16*>(y), evStart, evStop);
     }
     bool foldU8In(const snnhip_u8_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F16 || u8in) return false;
+        if (ui.dtype != SNNHIP_F16 || u8in || u16in) return false;
         u8in = true;
         p.mean = ui.means[0];
         p.norm = ui.norms[0];
         rename_kernel(desc, "kernel=espcn_f16_conv_pair_kernel", "kernel=espcn_f16_conv_pair_kernel<u8>");
+        return true;
+    }
+    bool foldU16In(const snnhip_u16_in_desc& ui, std::string& desc) override {
+        if (ui.dtype != SNNHIP_F16 || u8in || u16in) return false;
+        u16in = true;
+        qin16 = U16InCfg{ui.means[0], ui.norms[0], ui.shift};
+        rename_kernel(desc, "kernel=espcn_f16_conv_pair_kernel", "kernel=espcn_f16_conv_pair_u16_kernel");
         return true;
     }
 };
@@ -169,19 +205,30 @@ struct FusedA16 : FusedLaunch { // rule A16 and its 8-bit form (espcn_f16.hip): 
 struct FusedB16 : FusedLaunch { // rule B16 and its 8-bit form, upscale 2, 3 or 4 (espcn_f16.hip): w holds halfs
     EspcnF16BParams p{};
     int r = 2;
-    bool u8out = false;
+    bool u8out = false, u16out = false;
+    U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
     float *w = nullptr, *e = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
+        if (u16out)
+            return espcn_f16_b_u16_launch(ctx->stream, r, p, qout16, reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(w), e,
+                                          reinterpret_cast<unsigned short*>(y), evStart, evStop);
         return espcn_f16_b_launch(ctx->stream, r, p, u8out, reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(w), e, y, evStart,
                                   evStop);
     }
     bool foldU8Out(const snnhip_u8_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F16 || u8out) return false;
+        if (uo.dtype != SNNHIP_F16 || u8out || u16out) return false;
         u8out = true;
         p.qscale = uo.scale[0];
         p.qoffset = uo.offset[0];
         const size_t at = desc.find(">", desc.find("kernel=espcn_f16_d2s_kernel<"));
         if (at != std::string::npos) desc.insert(at, ",u8");
+        return true;
+    }
+    bool foldU16Out(const snnhip_u16_out_desc& uo, std::string& desc) override {
+        if (uo.dtype != SNNHIP_F16 || u8out || u16out) return false;
+        u16out = true;
+        qout16 = U16OutCfg{uo.scale[0], uo.offset[0], static_cast<float>(uo.maxval), uo.shift};
+        rename_kernel(desc, "kernel=espcn_f16_d2s_kernel", "kernel=espcn_f16_d2s_u16_kernel");
         return true;
     }
 };
@@ -696,6 +743,27 @@ void pass_u8_ends(Planner& pl) {
         Step &a = steps[k], &b = steps[k + 1];
         snnhip_u8_in_desc ui;
         snnhip_u8_out_desc uo;
+        snnhip_u16_in_desc wi;
+        snnhip_u16_out_desc wo;
+        // the 16-bit conversions, same places: 2 bytes per frame pixel instead of the fp32 tensor's 4 (the fp16 kernels move 2 either way)
+        if (k == 0 && a.plain && b.fused && u16_in_plan_desc(a.plain, &wi) && wi.C == 1 && b.fused->foldU16In(wi, b.desc)) {
+            b.desc = "u16_in(1ch) + " + b.desc;
+            b.flops += a.flops;
+            b.bytes -= (wi.dtype == SNNHIP_F16 ? 0.0 : 2.0) * wi.N * wi.H * wi.W;
+            steps.erase(steps.begin() + static_cast<long>(k));
+            ++pl.fusedCount;
+            --k;
+            continue;
+        }
+        if (k + 2 == steps.size() && a.fused && b.plain && u16_out_plan_desc(b.plain, &wo) && wo.C == 1 && a.fused->foldU16Out(wo, a.desc)) {
+            a.desc += " + u16_out(1ch)";
+            a.flops += b.flops;
+            a.bytes -= (wo.dtype == SNNHIP_F16 ? 0.0 : 2.0) * wo.N * wo.H * wo.W;
+            memcpy(a.outDims, b.outDims, sizeof(a.outDims));
+            steps.erase(steps.begin() + static_cast<long>(k) + 1);
+            ++pl.fusedCount;
+            continue;
+        }
         if (k == 0 && a.plain && b.fused && u8_in_plan_desc(a.plain, &ui) && ui.C == 1 && b.fused->foldU8In(ui, b.desc)) {
             b.desc = "u8_in(1ch) + " + b.desc;
             b.flops += a.flops;
@@ -793,8 +861,8 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
         chain->flops += plans[i]->flops;
         chain->bytes += plans[i]->bytes;
     }
-    chain->u8Input = plans[0]->u8Input && !plans[0]->anyDtype; // a chain that starts with u8_in reads the 8-bit frame, one that ends with u8_out writes one
-    chain->u8Output = plans[n - 1]->u8Output;
+    chain->rawInput = plans[0]->anyDtype ? -1 : plans[0]->rawInput; // a chain that starts with u8_in / u16_in reads the frame, one that ends with u8_out / u16_out writes one
+    chain->rawOutput = plans[n - 1]->rawOutput;
     std::string d = "chain{";
     for (size_t i = 0; i < chain->steps.size(); ++i) d += (i ? " -> " : "") + chain->steps[i].desc;
     chain->desc = d + "}";

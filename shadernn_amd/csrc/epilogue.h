@@ -89,6 +89,15 @@ __device__ __forceinline__ unsigned quantize_u8(float x, float scale, float offs
     return static_cast<unsigned>(v);
 }
 
+// The u16_out contract (include/snnhip.h, snnhip_u16_out_plan_create): clamp(rint(fmaf(x, scale, offset)), 0, maxval), ties to even, NaN -> 0; the
+// caller shifts the result into the container's alignment.  maxval is the integer 1..65535 as a float (exact).  Every 16-bit form calls this one function.
+__device__ __forceinline__ unsigned quantize_u16(float x, float scale, float offset, float maxval) {
+    float v = rintf(fmaf(x, scale, offset));
+    v = v >= 0.0f ? v : 0.0f; // NaN fails the test: 0
+    v = v <= maxval ? v : maxval;
+    return static_cast<unsigned>(v);
+}
+
 // Element access: every kernel is instantiated for T = float and T = _Float16 (SNNHIP_F16 tensors: half storage, fp32 arithmetic,
 // round-to-nearest-even on store) and for CV = 4 (C % 4 == 0: one 16- or 8-byte access) or CV = 1.
 template <typename T, int CV>

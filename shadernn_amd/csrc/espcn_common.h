@@ -21,6 +21,30 @@ struct U8InCfg {
 struct U8OutCfg {
     float scale, offset;
 };
+// The 16-bit forms of the two (snnhip_u16_in_plan_create's / snnhip_u16_out_plan_create's maps) carry parameter blocks of their own, so that the
+// blocks of the 8-bit kernels stay what they are: y = (float(u >> shift) - mean) * norm;  q = quantize_u16(o, scale, offset, maxval) << shift
+struct U16InCfg {
+    float mean, norm;
+    int shift;
+};
+struct U16OutCfg {
+    float scale, offset, maxval;
+    int shift;
+};
+// What a fused kernel's frame end stores: 0 = the launch's own tensor type (float / _Float16), 8 / 16 = an 8- / 16-bit frame.  (A 16-bit frame
+// element and a half are both 2 bytes: the kernel bodies ask this trait, not sizeof.)
+template <typename T>
+struct FrameBits {
+    static constexpr int value = 0;
+};
+template <>
+struct FrameBits<unsigned char> {
+    static constexpr int value = 8;
+};
+template <>
+struct FrameBits<unsigned short> {
+    static constexpr int value = 16;
+};
 
 // MFMA row of a depth-to-space tail (kernel B for r = 3 / 4, kernel B16): row 4*dy + dx holds channel r*dy + dx (r = 2, 3, 4); -1 = the row stays zero
 inline int espcn_d2s_row_channel(int r, int row) { return ((row & 3) < r && (row >> 2) < r) ? r * (row >> 2) + (row & 3) : -1; }

@@ -1,7 +1,8 @@
-// espcn_d2s_b_body.h -- the body of kernel B's direct form (espcn_fused.hip; the rules are chain_fuse.hip's), #included by its two kernels: rule B's (TOut = float) and rule B8's
+// espcn_d2s_b_body.h -- the body of kernel B's direct form (espcn_fused.hip; the rules are chain_fuse.hip's), #included by its three kernels: rule B's (TOut = float), rule B8's
 // (TOut = unsigned char: the epilogue quantises with quantize_u8(o, qout.scale, qout.offset), snnhip_u8_out_plan_create's map, and stores two
-// 2-byte pairs instead of two float2).  Textual inclusion for the reason espcn_wino_a_body.h gives.  In scope: TW, TH, SIMPLE, the type TOut, the
-// kernel arguments p, qout, x, w, ep, y.
+// 2-byte pairs instead of two float2) and the 16-bit form (TOut = unsigned short: quantize_u16(o, ...) << shift, snnhip_u16_out_plan_create's map,
+// two 4-byte pairs; element 2gy*2W + 2gx is even, so both are aligned).  Textual inclusion for the reason espcn_wino_a_body.h gives.  In scope: TW,
+// TH, SIMPLE, the type TOut, the kernel arguments p, qout, qout16 (each a constant dummy where the kernel has no such frame), x, w, ep, y.
     // LDS tile as four channel-quad PLANES, s_x[q][pixel] float4: a wave's 64 pixels (2 rows x 32) read 512 contiguous bytes per row from one
     // plane -- conflict-free without a swizzle -- and every operand address of the tap loop is ONE per-thread base + a wave-uniform tap offset + a
     // compile-time plane offset.  (The kernel is VALU-issue bound: rocprofv3 counted 708 VALU instructions per wave of which 288 are the
@@ -96,7 +97,13 @@
         for (int k = 0; k < 4; ++k) o[k] = fast_tanh(apply_act<SIMPLE>(p.act, fmaf(acc[k], ep[2 * k], ep[2 * k + 1]), 0.0f));
         TOut* yn = y + static_cast<size_t>(n) * (2 * p.H) * (2 * p.W);
         // channel 2*dy+dx -> output pixel (2y+dy, 2x+dx)  (depth_to_space, fs_subpixel.glsl:41-64)
-        if constexpr (sizeof(TOut) == 1) {
+        if constexpr (FrameBits<TOut>::value == 16) {
+            unsigned q[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[k] = quantize_u16(o[k], qout16.scale, qout16.offset, qout16.maxval) << qout16.shift;
+            *reinterpret_cast<unsigned*>(yn + static_cast<size_t>(2 * gy) * (2 * p.W) + 2 * gx) = q[0] | (q[1] << 16);
+            *reinterpret_cast<unsigned*>(yn + static_cast<size_t>(2 * gy + 1) * (2 * p.W) + 2 * gx) = q[2] | (q[3] << 16);
+        } else if constexpr (FrameBits<TOut>::value == 8) {
             const unsigned q[4] = {quantize_u8(o[0], qout.scale, qout.offset), quantize_u8(o[1], qout.scale, qout.offset),
                                    quantize_u8(o[2], qout.scale, qout.offset), quantize_u8(o[3], qout.scale, qout.offset)};
             *reinterpret_cast<unsigned short*>(yn + static_cast<size_t>(2 * gy) * (2 * p.W) + 2 * gx) = static_cast<unsigned short>(q[0] | (q[1] << 8));

@@ -16,5 +16,8 @@ using EspcnD2sParams = FusedBParams; // input [N, H, W, 16]; tiles of kD2sMfmaTW
 // evStart / evStop: a plan-profile event pair or null.
 int espcn_d2s_mfma_launch(hipStream_t stream, int r, const EspcnD2sParams& p, bool u8out, float qscale, float qoffset, const float* x, const float* w,
                           const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop);
+// The same with a 16-bit output frame: q = quantize_u16(o, scale, offset, maxval) << shift.
+int espcn_d2s_mfma_u16_launch(hipStream_t stream, int r, const EspcnD2sParams& p, const U16OutCfg& q, const float* x, const float* w, const float* ep,
+                              unsigned short* y, hipEvent_t evStart, hipEvent_t evStop);
 
 } // namespace snnhip

@@ -17,6 +17,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_c16oR_d2s_tanh_kernel(EspcnD2s
                                                                         const float* __restrict__ ep, float* __restrict__ y) {
     typedef float TOut;
     constexpr U8OutCfg qout{0.0f, 0.0f};
+    constexpr U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
 #include "espcn_d2s_mfma_body.h"
 }
 
@@ -25,6 +26,17 @@ __global__ __launch_bounds__(256, 4) void conv3x3_c16oR_d2s_tanh_u8_kernel(Espcn
                                                                            const float* __restrict__ w, const float* __restrict__ ep,
                                                                            unsigned char* __restrict__ y) {
     typedef unsigned char TOut;
+    constexpr U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
+#include "espcn_d2s_mfma_body.h"
+}
+
+// the 16-bit form (snnhip_u16_out_plan_create folded in)
+template <int R, bool SIMPLE>
+__global__ __launch_bounds__(256, 4) void conv3x3_c16oR_d2s_tanh_u16_kernel(EspcnD2sParams p, U16OutCfg qout16, const float* __restrict__ x,
+                                                                            const float* __restrict__ w, const float* __restrict__ ep,
+                                                                            unsigned short* __restrict__ y) {
+    typedef unsigned short TOut;
+    constexpr U8OutCfg qout{0.0f, 0.0f};
 #include "espcn_d2s_mfma_body.h"
 }
 
@@ -48,6 +60,22 @@ int espcn_d2s_mfma_launch(hipStream_t stream, int r, const EspcnD2sParams& p, bo
         if (simple) SNNHIP_LAUNCH_BR(4, true); else SNNHIP_LAUNCH_BR(4, false);
     }
 #undef SNNHIP_LAUNCH_BR
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
+int espcn_d2s_mfma_u16_launch(hipStream_t stream, int r, const EspcnD2sParams& p, const U16OutCfg& q, const float* x, const float* w, const float* ep,
+                              unsigned short* y, hipEvent_t evStart, hipEvent_t evStop) {
+    SNNHIP_REQUIRE(r == 3 || r == 4, "espcn_d2s_mfma: upscale factor %d (3 or 4)", r);
+    const dim3 grid(p.tilesX * p.tilesY * p.N);
+    const bool simple = act_is_simple(p.act.act);
+#define SNNHIP_LAUNCH_BR16(R, S) SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_u16_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w, ep, y)
+    if (r == 3) {
+        if (simple) SNNHIP_LAUNCH_BR16(3, true); else SNNHIP_LAUNCH_BR16(3, false);
+    } else {
+        if (simple) SNNHIP_LAUNCH_BR16(4, true); else SNNHIP_LAUNCH_BR16(4, false);
+    }
+#undef SNNHIP_LAUNCH_BR16
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
 }

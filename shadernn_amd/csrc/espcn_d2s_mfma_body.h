@@ -1,7 +1,8 @@
-// espcn_d2s_mfma_body.h -- the body of chain rule B for upscale factors R = 3 and 4 (espcn_d2s_mfma.hip), #included by its two kernels: the fp32 one
-// (TOut = float) and rule B8's (TOut = unsigned char: the epilogue quantises with quantize_u8(o, qout.scale, qout.offset),
-// snnhip_u8_out_plan_create's map).  Textual inclusion for the reason espcn_wino_a_body.h gives.  In scope: R, SIMPLE, the type TOut, the kernel
-// arguments p, qout, x, w, ep, y.
+// espcn_d2s_mfma_body.h -- the body of chain rule B for upscale factors R = 3 and 4 (espcn_d2s_mfma.hip), #included by its three kernels: the fp32 one
+// (TOut = float), rule B8's (TOut = unsigned char: the epilogue quantises with quantize_u8(o, qout.scale, qout.offset),
+// snnhip_u8_out_plan_create's map) and the 16-bit form (TOut = unsigned short: quantize_u16(o, ...) << shift, snnhip_u16_out_plan_create's map).
+// Textual inclusion for the reason espcn_wino_a_body.h gives.  In scope: R, SIMPLE, the type TOut, the kernel arguments p, qout, qout16 (each a
+// constant dummy where the kernel has no such frame), x, w, ep, y.
 //
 // conv 3x3 (16 -> R*R, zero padding 1) + act, then depth-to-space(R) + tanh, as a GEMM on v_mfma_f32_16x16x4_f32 (true fp32 products):
 //   D[row][pixel] += Wt[row][ic] * X[ic][pixel],  9 taps x 4 K-steps per group of 16 pixels, A operand = the weights (36 VGPRs, loaded once),
@@ -14,6 +15,9 @@
 //   R = 3: one 12-byte store per lane (192 B runs); bytes: the four lanes of a pixel quad hold 12 bytes = 3 dwords, lane j < 3 of the quad
 //          builds dword j from its own 3 bytes and its right neighbour's (one lane shift) -- 4-byte stores, 48 B runs.  That needs the row
 //          pitch 3*W to be a multiple of 4 (every video width is); other widths store the three bytes one by one.
+//   16-bit frames: R = 4: one 8-byte store per lane (element 4*(...) : always aligned).  R = 3: six bytes at a 2-byte-aligned address, element
+//          9nHW + (3gy + g)*3W + 3gx: even -> a 4-byte store of pixels 0, 1 and a 2-byte store of pixel 2, odd -> 2 bytes, then 4 (the half epilogue of
+//          espcn_f16.hip splits the same layout the same way).
 // Tile = 32 x 8 low-resolution pixels, 256 threads = 4 waves, a wave owns 2 rows = 4 groups (accumulators); LDS = the 34 x 10 halo tile,
 // [row][col][16 ch] with rule A's 16-byte-slot swizzle, 21.8 KB.
     constexpr int TW = kD2sMfmaTW, TH = kD2sMfmaTH, TWH = TW + 2, THH = TH + 2;
@@ -103,7 +107,22 @@
 #pragma unroll
         for (int r = 0; r < R; ++r) o[r] = fast_tanh(apply_act<SIMPLE>(p.act, fmaf(acc[gi][r], sc[r], sh[r]), 0.0f));
         TOut* dst = yn + static_cast<size_t>(R * gy + g) * (R * p.W) + R * gx;
-        if constexpr (sizeof(TOut) == 1) {
+        if constexpr (FrameBits<TOut>::value == 16) {
+            unsigned q[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) q[r] = quantize_u16(o[r], qout16.scale, qout16.offset, qout16.maxval) << qout16.shift;
+            if constexpr (R == 4) {
+                if (ok) *reinterpret_cast<uint2*>(dst) = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+            } else if (ok) {
+                if ((reinterpret_cast<uintptr_t>(dst) & 2) == 0) {
+                    *reinterpret_cast<unsigned*>(dst) = q[0] | (q[1] << 16);
+                    dst[2] = static_cast<TOut>(q[2]);
+                } else {
+                    dst[0] = static_cast<TOut>(q[0]);
+                    *reinterpret_cast<unsigned*>(dst + 1) = q[1] | (q[2] << 16);
+                }
+            }
+        } else if constexpr (FrameBits<TOut>::value == 8) {
             unsigned v = 0;
 #pragma unroll
             for (int r = 0; r < R; ++r) v |= quantize_u8(o[r], qout.scale, qout.offset) << (8 * r);

@@ -45,5 +45,11 @@ int espcn_f16_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, boo
 // in MFMA row order.
 int espcn_f16_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, bool u8out, const _Float16* x, const _Float16* w, const float* ep, void* y,
                        hipEvent_t evStart, hipEvent_t evStop);
+// The 16-bit frame forms of the two: x a 16-bit frame, half((float(u >> shift) - mean) * norm); y a 16-bit frame,
+// quantize_u16(float(half(tanh)), scale, offset, maxval) << shift.  Their parameter blocks are their own (espcn_common.h).
+int espcn_f16_a_u16_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const U16InCfg& q, const unsigned short* x, const _Float16* w1, const _Float16* w2,
+                           const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop);
+int espcn_f16_b_u16_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const U16OutCfg& q, const _Float16* x, const _Float16* w, const float* ep,
+                           unsigned short* y, hipEvent_t evStart, hipEvent_t evStop);
 
 } // namespace snnhip

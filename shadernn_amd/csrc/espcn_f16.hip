@@ -81,122 +81,17 @@ template <int K1, typename TIn, bool SIMPLE>
 __global__ __launch_bounds__(256) void espcn_f16_conv_pair_kernel(EspcnF16AParams p, const TIn* __restrict__ x, const _Float16* __restrict__ w1,
                                                                  const _Float16* __restrict__ w2, const float* __restrict__ ep1,
                                                                  const float* __restrict__ ep2, _Float16* __restrict__ y) {
-    constexpr int TW = kEspcnF16TW_A, TH = kEspcnF16TH_A, P1 = K1 / 2;
-    constexpr int C1W = TW + 2, C1H = TH + 2;                   // conv1 output region needed by conv2 (halo 1)
-    constexpr int INW = C1W + 2 * P1, INH = C1H + 2 * P1;       // input region needed by conv1 on that region
-    constexpr int NG1 = (C1H * C1W + 15) / 16;                  // 16-pixel groups of phase 1
-    constexpr int GPR = TW / 16, RPW = TH / 4, G = GPR * RPW;   // phase 2: groups per row, rows per wave, groups (= accumulators) per wave
-    constexpr int U = 2;                                        // phase 1: groups in flight per wave
-    static_assert(K1 * K1 <= 32, "conv1 is one K-step of 32 taps");
-    static_assert(TW % 16 == 0 && TH % 4 == 0, "whole 16-pixel groups, whole rows per wave");
-    __shared__ __attribute__((aligned(16))) _Float16 s_c1[C1H * C1W * 16];
-    __shared__ _Float16 s_in[INH * INW];
+    constexpr U16InCfg qin16{0.0f, 0.0f, 0};
+#include "espcn_f16_a_body.h"
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int px = lane & 15, g = lane >> 4;
-    int b = xcd_tile_order(blockIdx.x, gridDim.x);
-    const int tx = b % p.tilesX;
-    b /= p.tilesX;
-    const int ty = b % p.tilesY;
-    const int n = b / p.tilesY;
-    const int x0 = tx * TW, y0 = ty * TH;
-    const TIn* xn = x + static_cast<size_t>(n) * p.H * p.W;
-
-    // ---- phase 0: input tile (origin y0-1-P1, x0-1-P1) -> LDS as halfs, zero outside the image
-    {
-        constexpr int NLD = (INH * INW + 255) / 256;
-        _Float16 v[NLD];
-#pragma unroll
-        for (int k = 0; k < NLD; ++k) { // all loads in flight before the first LDS write
-            const int idx = tid + k * 256;
-            const int r = idx / INW, c = idx - r * INW;
-            const int gy = y0 - 1 - P1 + r, gx = x0 - 1 - P1 + c;
-            v[k] = static_cast<_Float16>(0.0f);
-            if (idx < INH * INW && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {
-                const TIn u = xn[static_cast<size_t>(gy) * p.W + gx];
-                if constexpr (sizeof(TIn) == 1)
-                    v[k] = static_cast<_Float16>((static_cast<float>(u) - p.mean) * p.norm);
-                else
-                    v[k] = u;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NLD; ++k)
-            if (tid + k * 256 < INH * INW) s_in[tid + k * 256] = v[k];
-    }
-
-    // ---- weights -> registers (the host packed them in lane order), epilogue (scale, shift) of this lane's four rows
-    const f16x8 a1 = *reinterpret_cast<const f16x8*>(w1 + lane * 8);
-    const W3Regs a2 = load_w3(w2, lane);
-    float sc1[4], sh1[4], sc2[4], sh2[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        sc1[r] = ep1[(4 * g + r) * 2];
-        sh1[r] = ep1[(4 * g + r) * 2 + 1];
-        sc2[r] = ep2[(4 * g + r) * 2];
-        sh2[r] = ep2[(4 * g + r) * 2 + 1];
-    }
-    // conv1's K axis = its taps: lane group g supplies taps 8g .. 8g+7 (a tap past the last one carries a zero weight and a zero value)
-    int off1[8];
-    bool tapok[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int t = 8 * g + j;
-        tapok[j] = t < K1 * K1;
-        const int tt = tapok[j] ? t : 0;
-        off1[j] = (tt / K1) * INW + (tt % K1);
-    }
-    __syncthreads();
-
-    // ---- phase 1: conv1 over the C1H x C1W halo region, pixels flattened into 16-wide groups: one MFMA per group
-    for (int grp0 = wv * U; grp0 < NG1; grp0 += 4 * U) {
-        f32x4 acc[U];
-        int rr[U], cc[U];
-        bool valid[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int pi = (grp0 + u) * 16 + px;
-            valid[u] = pi < C1H * C1W;
-            const int pc = valid[u] ? pi : C1H * C1W - 1;
-            rr[u] = pc / C1W;
-            cc[u] = pc - rr[u] * C1W;
-            const _Float16* src = s_in + rr[u] * INW + cc[u];
-            f16x8 bv;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bv[j] = tapok[j] ? src[off1[j]] : static_cast<_Float16>(0.0f);
-            acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bv, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int gy = y0 - 1 + rr[u], gx = x0 - 1 + cc[u];
-            const bool inside = gy >= 0 && gy < p.H && gx >= 0 && gx < p.W; // outside the image: conv2's zero padding
-            f16x4 o;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                o[r] = static_cast<_Float16>(inside ? apply_act<SIMPLE>(p.act1, fmaf(acc[u][r], sc1[r], sh1[r]), 0.0f) : 0.0f);
-            if (valid[u]) *reinterpret_cast<f16x4*>(s_c1 + (rr[u] * C1W + cc[u]) * 16 + slot_off(g >> 1, cc[u]) + (g & 1) * 4) = o;
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: conv2, G accumulators per wave
-    f32x4 acc2[G];
-#pragma unroll
-    for (int gi = 0; gi < G; ++gi) acc2[gi] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    conv3x3_c16_tile<G, GPR, C1W>(s_c1, wv * RPW, px, g, a2, acc2);
-
-    // ---- epilogue: lane holds output channels 4g .. 4g+3 of pixel (row, col0 + px): 8-byte stores
-    _Float16* yn = y + static_cast<size_t>(n) * p.H * p.W * 16;
-#pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-        const int gy = y0 + wv * RPW + gi / GPR, gx = x0 + (gi % GPR) * 16 + px;
-        if (gy < p.H && gx < p.W) {
-            f16x4 o;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = static_cast<_Float16>(apply_act<SIMPLE>(p.act2, fmaf(acc2[gi][r], sc2[r], sh2[r]), 0.0f));
-            *reinterpret_cast<f16x4*>(yn + (static_cast<size_t>(gy) * p.W + gx) * 16 + g * 4) = o;
-        }
-    }
+// the 16-bit frame form of kernel A16 (snnhip_u16_in_plan_create folded in): a parameter block of its own
+template <int K1, bool SIMPLE>
+__global__ __launch_bounds__(256) void espcn_f16_conv_pair_u16_kernel(EspcnF16AParams p, U16InCfg qin16, const unsigned short* __restrict__ x,
+                                                                     const _Float16* __restrict__ w1, const _Float16* __restrict__ w2,
+                                                                     const float* __restrict__ ep1, const float* __restrict__ ep2, _Float16* __restrict__ y) {
+    typedef unsigned short TIn;
+#include "espcn_f16_a_body.h"
 }
 
 // ---- kernel B16<R> (TOut = _Float16) and its 8-bit form (TOut = unsigned char: q = quantize_u8(float(half(tanh)), qscale, qoffset),
@@ -206,107 +101,16 @@ __global__ __launch_bounds__(256) void espcn_f16_conv_pair_kernel(EspcnF16AParam
 template <int R, typename TOut, bool SIMPLE>
 __global__ __launch_bounds__(256) void espcn_f16_d2s_kernel(EspcnF16BParams p, const _Float16* __restrict__ x, const _Float16* __restrict__ w,
                                                            const float* __restrict__ ep, TOut* __restrict__ y) {
-    constexpr int TW = kEspcnF16TW_B, TH = kEspcnF16TH_B, TWH = TW + 2, THH = TH + 2;
-    constexpr int NCH = THH * TWH * 2, NLD = (NCH + 255) / 256; // 16-byte chunks of the halo tile; per thread
-    constexpr int G = 4;                                        // 16-pixel groups per wave: rows 2wv, 2wv+1 x column halves
-    static_assert(TW == 32 && TH == 8, "a wave owns 2 rows of 32 pixels = four 16-pixel groups");
-    static_assert(R >= 2 && R <= 4, "rows 4*dy + dx: R <= 4");
-    __shared__ __attribute__((aligned(16))) _Float16 s_x[THH * TWH * 16];
+    constexpr U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
+#include "espcn_f16_b_body.h"
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int px = lane & 15, g = lane >> 4;
-    int b = xcd_tile_order(blockIdx.x, gridDim.x);
-    const int tx = b % p.tilesX;
-    b /= p.tilesX;
-    const int ty = b % p.tilesY;
-    const int n = b / p.tilesY;
-    const int x0 = tx * TW, y0 = ty * TH;
-    const _Float16* xn = x + static_cast<size_t>(n) * p.H * p.W * 16;
-
-    // ---- halo tile (origin y0-1, x0-1) -> LDS, zero outside the image (the convolution's padding)
-    {
-        uint4 v[NLD];
-#pragma unroll
-        for (int k = 0; k < NLD; ++k) { // every load is in flight before the first LDS write
-            const int idx = tid + k * 256;
-            const int h = idx & 1, pix = idx >> 1;
-            const int r = pix / TWH, c = pix - r * TWH;
-            const int gy = y0 - 1 + r, gx = x0 - 1 + c;
-            v[k] = make_uint4(0u, 0u, 0u, 0u);
-            if (idx < NCH && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
-                v[k] = *reinterpret_cast<const uint4*>(xn + (static_cast<size_t>(gy) * p.W + gx) * 16 + h * 8);
-        }
-#pragma unroll
-        for (int k = 0; k < NLD; ++k) {
-            const int idx = tid + k * 256;
-            const int h = idx & 1, pix = idx >> 1;
-            const int c = pix % TWH;
-            if (idx < NCH) *reinterpret_cast<uint4*>(s_x + pix * 16 + slot_off(h, c)) = v[k];
-        }
-    }
-    const W3Regs a = load_w3(w, lane);
-    float sc[4], sh[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        sc[r] = ep[(4 * g + r) * 2];
-        sh[r] = ep[(4 * g + r) * 2 + 1];
-    }
-    __syncthreads();
-
-    f32x4 acc[G];
-#pragma unroll
-    for (int gi = 0; gi < G; ++gi) acc[gi] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    conv3x3_c16_tile<G, 2, TWH>(s_x, wv * 2, px, g, a, acc);
-
-    // ---- epilogue: bias/BN/act -> half, tanh -> half; lane (px, g < R) holds output row R*gy + g, columns R*gx .. R*gx + R-1
-    TOut* yn = y + static_cast<size_t>(n) * (R * p.H) * (R * p.W);
-    [[maybe_unused]] const bool dwordRows = (p.W & 3) == 0; // R = 3, bytes: every pixel quad starts on a 4-byte boundary
-#pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-        const int gy = y0 + wv * 2 + (gi >> 1), gx = x0 + (gi & 1) * 16 + px;
-        const bool ok = g < R && gy < p.H && gx < p.W;
-        _Float16 o[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const _Float16 c3 = static_cast<_Float16>(apply_act<SIMPLE>(p.act, fmaf(acc[gi][r], sc[r], sh[r]), 0.0f)); // what the Subpixel plan would read
-            o[r] = static_cast<_Float16>(fast_tanh(static_cast<float>(c3)));
-        }
-        TOut* dst = yn + static_cast<size_t>(R * gy + g) * (R * p.W) + R * gx;
-        if constexpr (sizeof(TOut) == 1) {
-            unsigned v = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) v |= quantize_u8(static_cast<float>(o[r]), p.qscale, p.qoffset) << (8 * r);
-            if constexpr (R == 4) {
-                if (ok) *reinterpret_cast<unsigned*>(dst) = v;
-            } else if constexpr (R == 2) {
-                if (ok) *reinterpret_cast<unsigned short*>(dst) = static_cast<unsigned short>(v);
-            } else {
-                const unsigned nb = __shfl_down(v, 1); // the right neighbour's three bytes (every lane takes part)
-                const int j = px & 3;
-                if (dwordRows) { // W % 4 == 0: a quad is inside the image or outside it as a whole, and starts on a 4-byte boundary
-                    if (ok && j < 3) *reinterpret_cast<unsigned*>(dst + j) = (v >> (8 * j)) | (nb << (24 - 8 * j));
-                } else if (ok) {
-                    dst[0] = static_cast<unsigned char>(v);
-                    dst[1] = static_cast<unsigned char>(v >> 8);
-                    dst[2] = static_cast<unsigned char>(v >> 16);
-                }
-            }
-        } else {
-            if constexpr (R == 4) {
-                if (ok) *reinterpret_cast<f16x4*>(dst) = f16x4{o[0], o[1], o[2], o[3]};
-            } else if constexpr (R == 2) {
-                if (ok) *reinterpret_cast<f16x2*>(dst) = f16x2{o[0], o[1]};
-            } else if (ok) { // 6 bytes at a 2-byte aligned address: 4 + 2 or 2 + 4
-                if ((reinterpret_cast<uintptr_t>(dst) & 2) == 0) {
-                    *reinterpret_cast<f16x2*>(dst) = f16x2{o[0], o[1]};
-                    dst[2] = o[2];
-                } else {
-                    dst[0] = o[0];
-                    *reinterpret_cast<f16x2*>(dst + 1) = f16x2{o[1], o[2]};
-                }
-            }
-        }
-    }
+// the 16-bit frame form of kernel B16<R> (snnhip_u16_out_plan_create folded in)
+template <int R, bool SIMPLE>
+__global__ __launch_bounds__(256) void espcn_f16_d2s_u16_kernel(EspcnF16BParams p, U16OutCfg qout16, const _Float16* __restrict__ x,
+                                                               const _Float16* __restrict__ w, const float* __restrict__ ep, unsigned short* __restrict__ y) {
+    typedef unsigned short TOut;
+#include "espcn_f16_b_body.h"
 }
 
 } // namespace
@@ -350,6 +154,40 @@ int espcn_f16_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, boo
         if (simple) SNNHIP_LAUNCH_A16(3, true); else SNNHIP_LAUNCH_A16(3, false);
     }
 #undef SNNHIP_LAUNCH_A16
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
+int espcn_f16_a_u16_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const U16InCfg& q, const unsigned short* x, const _Float16* w1, const _Float16* w2,
+                           const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
+    SNNHIP_REQUIRE(k1 == 3 || k1 == 5, "espcn_f16: first convolution %dx%d (3x3 or 5x5)", k1, k1);
+    const dim3 grid(p.tilesX * p.tilesY * p.N);
+    const bool simple = act_is_simple(p.act1.act) && act_is_simple(p.act2.act);
+#define SNNHIP_LAUNCH_A16W(K, S) SNNHIP_LAUNCH_EV((espcn_f16_conv_pair_u16_kernel<K, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w1, w2, ep1, ep2, y)
+    if (k1 == 5) {
+        if (simple) SNNHIP_LAUNCH_A16W(5, true); else SNNHIP_LAUNCH_A16W(5, false);
+    } else {
+        if (simple) SNNHIP_LAUNCH_A16W(3, true); else SNNHIP_LAUNCH_A16W(3, false);
+    }
+#undef SNNHIP_LAUNCH_A16W
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
+int espcn_f16_b_u16_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const U16OutCfg& q, const _Float16* x, const _Float16* w, const float* ep,
+                           unsigned short* y, hipEvent_t evStart, hipEvent_t evStop) {
+    SNNHIP_REQUIRE(r >= 2 && r <= 4, "espcn_f16: upscale factor %d (2, 3 or 4)", r);
+    const dim3 grid(p.tilesX * p.tilesY * p.N);
+    const bool simple = act_is_simple(p.act.act);
+#define SNNHIP_LAUNCH_B16W(R, S) SNNHIP_LAUNCH_EV((espcn_f16_d2s_u16_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w, ep, y)
+    if (r == 2) {
+        if (simple) SNNHIP_LAUNCH_B16W(2, true); else SNNHIP_LAUNCH_B16W(2, false);
+    } else if (r == 3) {
+        if (simple) SNNHIP_LAUNCH_B16W(3, true); else SNNHIP_LAUNCH_B16W(3, false);
+    } else {
+        if (simple) SNNHIP_LAUNCH_B16W(4, true); else SNNHIP_LAUNCH_B16W(4, false);
+    }
+#undef SNNHIP_LAUNCH_B16W
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
 }

@@ -1,0 +1,123 @@
+// espcn_f16_b_body.h -- the body of kernel B16<R> (espcn_f16.hip), #included by its kernels: espcn_f16_d2s_kernel<R, TOut, SIMPLE> (TOut = _Float16,
+// or unsigned char: q = quantize_u8(float(half(tanh)), p.qscale, p.qoffset)) and the 16-bit frame form espcn_f16_d2s_u16_kernel (TOut = unsigned
+// short: quantize_u16(float(half(tanh)), qout16...) << qout16.shift, snnhip_u16_out_plan_create's map on the fp16 value the stand-alone chain would
+// have stored, through the store layout of the half output).  Textual inclusion as espcn_f16_a_body.h; the body asks FrameBits<TOut>, not sizeof.
+// In scope: R, SIMPLE, the type TOut, the kernel arguments p, qout16 (a constant dummy in the kernels without a 16-bit frame), x, w, ep, y.
+    constexpr int TW = kEspcnF16TW_B, TH = kEspcnF16TH_B, TWH = TW + 2, THH = TH + 2;
+    constexpr int NCH = THH * TWH * 2, NLD = (NCH + 255) / 256; // 16-byte chunks of the halo tile; per thread
+    constexpr int G = 4;                                        // 16-pixel groups per wave: rows 2wv, 2wv+1 x column halves
+    static_assert(TW == 32 && TH == 8, "a wave owns 2 rows of 32 pixels = four 16-pixel groups");
+    static_assert(R >= 2 && R <= 4, "rows 4*dy + dx: R <= 4");
+    __shared__ __attribute__((aligned(16))) _Float16 s_x[THH * TWH * 16];
+
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int px = lane & 15, g = lane >> 4;
+    int b = xcd_tile_order(blockIdx.x, gridDim.x);
+    const int tx = b % p.tilesX;
+    b /= p.tilesX;
+    const int ty = b % p.tilesY;
+    const int n = b / p.tilesY;
+    const int x0 = tx * TW, y0 = ty * TH;
+    const _Float16* xn = x + static_cast<size_t>(n) * p.H * p.W * 16;
+
+    // ---- halo tile (origin y0-1, x0-1) -> LDS, zero outside the image (the convolution's padding)
+    {
+        uint4 v[NLD];
+#pragma unroll
+        for (int k = 0; k < NLD; ++k) { // every load is in flight before the first LDS write
+            const int idx = tid + k * 256;
+            const int h = idx & 1, pix = idx >> 1;
+            const int r = pix / TWH, c = pix - r * TWH;
+            const int gy = y0 - 1 + r, gx = x0 - 1 + c;
+            v[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (idx < NCH && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
+                v[k] = *reinterpret_cast<const uint4*>(xn + (static_cast<size_t>(gy) * p.W + gx) * 16 + h * 8);
+        }
+#pragma unroll
+        for (int k = 0; k < NLD; ++k) {
+            const int idx = tid + k * 256;
+            const int h = idx & 1, pix = idx >> 1;
+            const int c = pix % TWH;
+            if (idx < NCH) *reinterpret_cast<uint4*>(s_x + pix * 16 + slot_off(h, c)) = v[k];
+        }
+    }
+    const W3Regs a = load_w3(w, lane);
+    float sc[4], sh[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        sc[r] = ep[(4 * g + r) * 2];
+        sh[r] = ep[(4 * g + r) * 2 + 1];
+    }
+    __syncthreads();
+
+    f32x4 acc[G];
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) acc[gi] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    conv3x3_c16_tile<G, 2, TWH>(s_x, wv * 2, px, g, a, acc);
+
+    // ---- epilogue: bias/BN/act -> half, tanh -> half; lane (px, g < R) holds output row R*gy + g, columns R*gx .. R*gx + R-1
+    TOut* yn = y + static_cast<size_t>(n) * (R * p.H) * (R * p.W);
+    [[maybe_unused]] const bool dwordRows = (p.W & 3) == 0; // R = 3, bytes: every pixel quad starts on a 4-byte boundary
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) {
+        const int gy = y0 + wv * 2 + (gi >> 1), gx = x0 + (gi & 1) * 16 + px;
+        const bool ok = g < R && gy < p.H && gx < p.W;
+        _Float16 o[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const _Float16 c3 = static_cast<_Float16>(apply_act<SIMPLE>(p.act, fmaf(acc[gi][r], sc[r], sh[r]), 0.0f)); // what the Subpixel plan would read
+            o[r] = static_cast<_Float16>(fast_tanh(static_cast<float>(c3)));
+        }
+        TOut* dst = yn + static_cast<size_t>(R * gy + g) * (R * p.W) + R * gx;
+        if constexpr (FrameBits<TOut>::value == 16) { // the half output's store layout, 2-byte elements
+            unsigned q[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) q[r] = quantize_u16(static_cast<float>(o[r]), qout16.scale, qout16.offset, qout16.maxval) << qout16.shift;
+            if constexpr (R == 4) {
+                if (ok) *reinterpret_cast<uint2*>(dst) = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+            } else if constexpr (R == 2) {
+                if (ok) *reinterpret_cast<unsigned*>(dst) = q[0] | (q[1] << 16);
+            } else if (ok) { // 6 bytes at a 2-byte aligned address: 4 + 2 or 2 + 4
+                if ((reinterpret_cast<uintptr_t>(dst) & 2) == 0) {
+                    *reinterpret_cast<unsigned*>(dst) = q[0] | (q[1] << 16);
+                    dst[2] = static_cast<TOut>(q[2]);
+                } else {
+                    dst[0] = static_cast<TOut>(q[0]);
+                    *reinterpret_cast<unsigned*>(dst + 1) = q[1] | (q[2] << 16);
+                }
+            }
+        } else if constexpr (FrameBits<TOut>::value == 8) {
+            unsigned v = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) v |= quantize_u8(static_cast<float>(o[r]), p.qscale, p.qoffset) << (8 * r);
+            if constexpr (R == 4) {
+                if (ok) *reinterpret_cast<unsigned*>(dst) = v;
+            } else if constexpr (R == 2) {
+                if (ok) *reinterpret_cast<unsigned short*>(dst) = static_cast<unsigned short>(v);
+            } else {
+                const unsigned nb = __shfl_down(v, 1); // the right neighbour's three bytes (every lane takes part)
+                const int j = px & 3;
+                if (dwordRows) { // W % 4 == 0: a quad is inside the image or outside it as a whole, and starts on a 4-byte boundary
+                    if (ok && j < 3) *reinterpret_cast<unsigned*>(dst + j) = (v >> (8 * j)) | (nb << (24 - 8 * j));
+                } else if (ok) {
+                    dst[0] = static_cast<unsigned char>(v);
+                    dst[1] = static_cast<unsigned char>(v >> 8);
+                    dst[2] = static_cast<unsigned char>(v >> 16);
+                }
+            }
+        } else {
+            if constexpr (R == 4) {
+                if (ok) *reinterpret_cast<f16x4*>(dst) = f16x4{o[0], o[1], o[2], o[3]};
+            } else if constexpr (R == 2) {
+                if (ok) *reinterpret_cast<f16x2*>(dst) = f16x2{o[0], o[1]};
+            } else if (ok) { // 6 bytes at a 2-byte aligned address: 4 + 2 or 2 + 4
+                if ((reinterpret_cast<uintptr_t>(dst) & 2) == 0) {
+                    *reinterpret_cast<f16x2*>(dst) = f16x2{o[0], o[1]};
+                    dst[2] = static_cast<TOut>(o[2]);
+                } else {
+                    dst[0] = static_cast<TOut>(o[0]);
+                    *reinterpret_cast<f16x2*>(dst + 1) = f16x2{o[1], o[2]};
+                }
+            }
+        }
+    }

@@ -55,6 +55,11 @@ int espcn_fused_a_launch(hipStream_t stream, const FusedAParams& p, int k1, bool
 // w = espcn_pack_wino), else the VALU form (B_TW x B_TH, w = espcn_pack_b_direct).  u8out (VALU form only): y is an 8-bit frame.
 int espcn_fused_b_launch(hipStream_t stream, const FusedBParams& p, bool wino, bool u8out, const U8OutCfg& qout, const float* x, const float* w,
                          const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop);
+// The 16-bit frame forms of the two (Winograd kernel A reading a 16-bit frame; VALU kernel B writing one): snnhip_u16_in / u16_out folded in.
+int espcn_fused_a_u16_launch(hipStream_t stream, const FusedAParams& p, int k1, const U16InCfg& qin, int computeUnits, const unsigned short* x, const float* w1,
+                             const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop);
+int espcn_fused_b_u16_launch(hipStream_t stream, const FusedBParams& p, const U16OutCfg& qout, const float* x, const float* w, const float* ep, unsigned short* y,
+                             hipEvent_t evStart, hipEvent_t evStop);
 
 // ---- host-side weight images; w_oihw = the convolution's [OC][IC][k][k] fp32 weights
 // lane-ordered conv1 (1 -> 16, k1 x k1) A operand: image[s*64 + l] = W[oc = l & 15][tap], tap = 4s + l/16 (zero from k1*k1 on), or -- winoOrder --

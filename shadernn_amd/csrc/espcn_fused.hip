@@ -247,6 +247,7 @@ __global__ __launch_bounds__(256, WPS) void conv_kxk_c1o16_wino3x3_c16o16_kernel
                                                                            float* __restrict__ y) {
     typedef float TIn;
     constexpr U8InCfg qin{0.0f, 0.0f};
+    constexpr U16InCfg qin16{0.0f, 0.0f, 0};
 #include "espcn_wino_a_body.h"
 }
 
@@ -256,6 +257,18 @@ __global__ __launch_bounds__(256, WPS) void conv_kxk_c1o16_wino3x3_c16o16_u8_ker
                                                                               const float* __restrict__ ep1, const float* __restrict__ ep2,
                                                                               float* __restrict__ y) {
     typedef unsigned char TIn;
+    constexpr U16InCfg qin16{0.0f, 0.0f, 0};
+#include "espcn_wino_a_body.h"
+}
+
+// the 16-bit form (snnhip_u16_in_plan_create folded in): its own parameter block, the 8-bit kernel's stays what it is
+template <int K1, int TH, int AM, int WPS>
+__global__ __launch_bounds__(256, WPS) void conv_kxk_c1o16_wino3x3_c16o16_u16_kernel(FusedAParams p, U16InCfg qin16, const unsigned short* __restrict__ x,
+                                                                               const float* __restrict__ wA1, const float* __restrict__ wU,
+                                                                               const float* __restrict__ ep1, const float* __restrict__ ep2,
+                                                                               float* __restrict__ y) {
+    typedef unsigned short TIn;
+    constexpr U8InCfg qin{0.0f, 0.0f};
 #include "espcn_wino_a_body.h"
 }
 
@@ -268,6 +281,7 @@ __global__ __launch_bounds__(256) void conv3x3_c16o4_d2s_tanh_kernel(FusedBParam
                                                                      const float* __restrict__ ep, float* __restrict__ y) {
     typedef float TOut;
     constexpr U8OutCfg qout{0.0f, 0.0f};
+    constexpr U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
 #include "espcn_d2s_b_body.h"
 }
 
@@ -275,6 +289,16 @@ template <int TW, int TH, bool SIMPLE>
 __global__ __launch_bounds__(256) void conv3x3_c16o4_d2s_tanh_u8_kernel(FusedBParams p, U8OutCfg qout, const float* __restrict__ x, const float* __restrict__ w,
                                                                         const float* __restrict__ ep, unsigned char* __restrict__ y) {
     typedef unsigned char TOut;
+    constexpr U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
+#include "espcn_d2s_b_body.h"
+}
+
+// the 16-bit form (snnhip_u16_out_plan_create folded in)
+template <int TW, int TH, bool SIMPLE>
+__global__ __launch_bounds__(256) void conv3x3_c16o4_d2s_tanh_u16_kernel(FusedBParams p, U16OutCfg qout16, const float* __restrict__ x, const float* __restrict__ w,
+                                                                         const float* __restrict__ ep, unsigned short* __restrict__ y) {
+    typedef unsigned short TOut;
+    constexpr U8OutCfg qout{0.0f, 0.0f};
 #include "espcn_d2s_b_body.h"
 }
 
@@ -537,6 +561,34 @@ int espcn_fused_a_launch(hipStream_t stream, const FusedAParams& p, int k1, bool
         }
 #undef SNNHIP_LAUNCH_A
     }
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
+int espcn_fused_a_u16_launch(hipStream_t stream, const FusedAParams& p, int k1, const U16InCfg& qin, int computeUnits, const unsigned short* x, const float* w1,
+                             const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop) {
+    const int ntiles = p.tilesX * p.tilesY * p.N;
+    const bool simple = act_is_simple(p.act1.act) && act_is_simple(p.act2.act);
+    const int slots = W_WPS * (computeUnits > 0 ? computeUnits : 256);
+    dim3 grid(ntiles < slots ? ntiles : slots); // persistent, as espcn_fused_a_launch
+#define SNNHIP_LAUNCH_W16(K, AM) \
+    SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_u16_kernel<K, W_TH, AM, W_WPS>), grid, dim3(256), 0, stream, evStart, evStop, p, qin, x, w1, w2, ep1, ep2, y)
+    const int am = (p.act1.act == SNNHIP_ACT_RELU && p.act2.act == SNNHIP_ACT_RELU) ? 2 : (simple ? 1 : 0);
+    if (k1 == 5) {
+        if (am == 2) SNNHIP_LAUNCH_W16(5, 2); else if (am == 1) SNNHIP_LAUNCH_W16(5, 1); else SNNHIP_LAUNCH_W16(5, 0);
+    } else {
+        if (am == 2) SNNHIP_LAUNCH_W16(3, 2); else if (am == 1) SNNHIP_LAUNCH_W16(3, 1); else SNNHIP_LAUNCH_W16(3, 0);
+    }
+#undef SNNHIP_LAUNCH_W16
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
+int espcn_fused_b_u16_launch(hipStream_t stream, const FusedBParams& p, const U16OutCfg& qout, const float* x, const float* w, const float* ep, unsigned short* y,
+                             hipEvent_t evStart, hipEvent_t evStop) {
+    dim3 grid(p.tilesX * p.tilesY * p.N); // one block per tile
+    if (act_is_simple(p.act.act)) SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u16_kernel<B_TW, B_TH, true>), grid, dim3(256), 0, stream, evStart, evStop, p, qout, x, w, ep, y);
+    else SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u16_kernel<B_TW, B_TH, false>), grid, dim3(256), 0, stream, evStart, evStop, p, qout, x, w, ep, y);
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
 }

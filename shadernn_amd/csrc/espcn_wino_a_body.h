@@ -1,10 +1,13 @@
-// espcn_wino_a_body.h -- the body of kernel A's Winograd form (espcn_fused.hip; the rules are chain_fuse.hip's), #included by its two kernels: rule A's (TIn = float) and rule A8's
+// espcn_wino_a_body.h -- the body of kernel A's Winograd form (espcn_fused.hip; the rules are chain_fuse.hip's), #included by its three kernels: rule A's (TIn = float), rule A8's
 // (TIn = unsigned char: the 8-bit frame is normalised while the tile is staged, y = (float(u) - qin.mean) * qin.norm, snnhip_u8_in_plan_create's
-// map; taps outside the image stay 0 in the NORMALISED domain, as the separate u8_in launch in front of rule A gives them).  Textual inclusion
+// map; taps outside the image stay 0 in the NORMALISED domain, as the separate u8_in launch in front of rule A gives them) and the 16-bit form
+// (TIn = unsigned short: y = (float(u >> qin16.shift) - qin16.mean) * qin16.norm, snnhip_u16_in_plan_create's map).  Textual inclusion
 // rather than a shared __device__ function: inlining a body through a call changed the fp32 kernels' register allocation (scratch spills in
 // <5,16,2,2>), and the fp32 instruction stream must stay what it was.  In scope: the template parameters K1, TH, AM, WPS, the type TIn, the
-// kernel arguments p, qin, x, wA1, wU, ep1, ep2, y.
-    constexpr bool kU8 = sizeof(TIn) == 1;
+// kernel arguments p, qin, qin16 (each a constant dummy where the kernel has no such frame), x, wA1, wU, ep1, ep2, y.
+    constexpr int kBits = FrameBits<TIn>::value;     // 0: fp32 input; 8 / 16: a frame, kept raw in the prefetch registers
+    constexpr bool kFrame = kBits != 0;
+    constexpr unsigned kOutside = kBits == 16 ? 65536u : 256u; // "outside the image": a value no load of the frame can produce
     constexpr int TW = WinoTile::TW, U = 2;
     constexpr int P1 = K1 / 2;
     constexpr int C1W = TW + 2, C1H = TH + 2;
@@ -43,7 +46,7 @@
         y0 = ty * TH;
     };
     float vin[NLD];
-    unsigned vin8[kU8 ? NLD : 1]; // (8-bit input only)
+    unsigned vraw[kFrame ? NLD : 1]; // (frame input only)
     auto issue_loads = [&](int t) { // input tile (origin y0-1-P1, x0-1-P1), zero padded (+8 zero floats: invalid taps read them)
         int n, x0, y0;
         tile_origin(t, n, x0, y0);
@@ -53,11 +56,11 @@
             const int idx = tid + k * 256;
             const int r = idx / INP, c = idx - r * INP;
             const int gy = y0 - 1 - P1 + r, gx = x0 - 1 - P1 + c;
-            if constexpr (kU8) {
+            if constexpr (kFrame) {
                 // the raw byte straight into its register (no conversion here: that would wait for the load, and these loads are the prefetch of
-                // the NEXT tile); 256 = outside the image.  Normalised in store_input, after the tile's compute.
-                vin8[k] = 256u;
-                if (r < INH && c < INW && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) vin8[k] = xn[static_cast<size_t>(gy) * p.W + gx];
+                // the NEXT tile); kOutside = outside the image.  Normalised in store_input, after the tile's compute.
+                vraw[k] = kOutside;
+                if (r < INH && c < INW && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) vraw[k] = xn[static_cast<size_t>(gy) * p.W + gx];
             } else {
                 vin[k] = 0.0f;
                 if (r < INH && c < INW && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) vin[k] = xn[static_cast<size_t>(gy) * p.W + gx];
@@ -68,7 +71,8 @@
 #pragma unroll
         for (int k = 0; k < NLD; ++k)
             if (tid + k * 256 < INH * INP + 8) {
-                if constexpr (kU8) s_in[tid + k * 256] = vin8[k] < 256u ? (static_cast<float>(vin8[k]) - qin.mean) * qin.norm : 0.0f;
+                if constexpr (kBits == 16) s_in[tid + k * 256] = vraw[k] < kOutside ? (static_cast<float>(vraw[k] >> qin16.shift) - qin16.mean) * qin16.norm : 0.0f;
+                else if constexpr (kFrame) s_in[tid + k * 256] = vraw[k] < kOutside ? (static_cast<float>(vraw[k]) - qin.mean) * qin.norm : 0.0f;
                 else s_in[tid + k * 256] = vin[k];
             }
     };

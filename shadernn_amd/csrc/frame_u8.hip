@@ -146,7 +146,7 @@ int snnhip_u8_in_plan_create(snnhip_ctx* ctx, const snnhip_u8_in_desc* desc, snn
     auto* plan = new U8InPlan();
     plan->ctx = ctx;
     plan->dtype = desc->dtype;
-    plan->u8Input = true;
+    plan->rawInput = SNNHIP_U8;
     plan->d = *desc;
     for (int i = 0; i < 4; ++i) {
         plan->inDims[i] = plan->outDims[i] = (&desc->N)[i];
@@ -168,7 +168,7 @@ int snnhip_u8_out_plan_create(snnhip_ctx* ctx, const snnhip_u8_out_desc* desc, s
     auto* plan = new U8OutPlan();
     plan->ctx = ctx;
     plan->dtype = desc->dtype;
-    plan->u8Output = true;
+    plan->rawOutput = SNNHIP_U8;
     plan->d = *desc;
     for (int i = 0; i < 4; ++i) {
         plan->inDims[i] = plan->outDims[i] = (&desc->N)[i];

@@ -426,7 +426,7 @@ int snnhip_image_u8_plan_create(snnhip_ctx* ctx, const snnhip_image_u8_desc* des
     auto* plan = new ImageU8Plan();
     plan->ctx = ctx;
     plan->anyDtype = true;
-    plan->u8Input = true;
+    plan->rawInput = SNNHIP_U8;
     plan->d = *desc;
     set_dims(plan, desc->N, desc->H, desc->W, desc->src_channels, desc->H, desc->W, 4);
     plan->bytes = static_cast<double>(desc->N) * desc->H * desc->W * (desc->src_channels + 16);

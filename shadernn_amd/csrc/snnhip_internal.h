@@ -114,7 +114,7 @@ struct snnhip_tensor {
     int n = 0, h = 0, w = 0, c = 0;
     int dtype = SNNHIP_F32; // SNNHIP_F16: `data` points at halfs
     size_t count() const { return static_cast<size_t>(n) * h * w * c; }
-    size_t elemSize() const { return dtype == SNNHIP_F16 ? 2 : dtype == SNNHIP_U8 ? 1 : 4; }
+    size_t elemSize() const { return dtype == SNNHIP_F16 || dtype == SNNHIP_U16 ? 2 : dtype == SNNHIP_U8 ? 1 : 4; }
     size_t bytes() const { return count() * elemSize(); }
 };
 
@@ -139,8 +139,10 @@ struct snnhip_plan {
     int numInputs = 1;
     int dtype = SNNHIP_F32;   // element type of the tensors this plan runs on ...
     bool anyDtype = false;    // ... unless it adapts to the tensors of each call (element-wise / pooling / shape operators)
-    bool u8Input = false;     // reads a SNNHIP_U8 tensor: snnhip_image_u8_plan_create / snnhip_u8_in_plan_create, or a chain that starts with the latter
-    bool u8Output = false;    // writes a SNNHIP_U8 tensor: snnhip_u8_out_plan_create, or a chain that ends with it
+    // raw frame dtype of this plan's input 0 / output (SNNHIP_U8 or SNNHIP_U16), -1 = none: snnhip_image_u8_plan_create and the u8_in / u16_in plans read
+    // one, the u8_out / u16_out plans write one, and so does a chain that starts / ends with them.  A raw tensor is accepted nowhere else.
+    int rawInput = -1;
+    int rawOutput = -1;
     std::string desc;
     double flops = 0, bytes = 0; // algorithmic cost in SURVEY 8(d)'s accounting (a fused plan: the sum over the layers it replaces)
     // what THIS plan's own launches have to move through HBM (inputs once + outputs once + weights): differs from `bytes` only for fused plans,
@@ -295,6 +297,9 @@ bool instancenorm_plan_desc(const snnhip_plan* plan, snnhip_instancenorm_desc* d
 // frame_u8.hip: identify the 8-bit frame conversions (chain rules A8 / B8 fold them into the ESPCN kernels)
 bool u8_in_plan_desc(const snnhip_plan* plan, snnhip_u8_in_desc* d);
 bool u8_out_plan_desc(const snnhip_plan* plan, snnhip_u8_out_desc* d);
+// frame_u16.hip: the same for the 16-bit frame conversions
+bool u16_in_plan_desc(const snnhip_plan* plan, snnhip_u16_in_desc* d);
+bool u16_out_plan_desc(const snnhip_plan* plan, snnhip_u16_out_desc* d);
 // eltwise_pool.hip: identify a Pooling plan (resolved output dims included)
 bool pool2d_plan_desc(const snnhip_plan* plan, snnhip_pool2d_desc* d);
 // conv2d_stem_f32.hip, chain rule J: Conv2D 7x7 stride 2 of an RGB image -> MaxPooling2D 3x3 stride 2 (the head of ResNet-18) as one launch: the pooling

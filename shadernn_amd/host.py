@@ -18,6 +18,9 @@ SIGNATURES = {
     "snn_model_create3": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "snn_model_create4": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "snn_model_create5": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create6": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_upload_frame_u16": (C.c_int, [_P, _P]),
+    "snn_model_download_frame_u16": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u8": (C.c_int, [_P, _P]),
     "snn_model_download_frame_u8": (C.c_int, [_P, _P]),
     "snn_model_batch": (C.c_int, [_P]),
@@ -130,7 +133,12 @@ class FrameIO(C.Structure):
                 ("out_offset", C.c_float * 4)]
 
 
-FRAME_FORMATS = {None: 0, "float": 0, "R8": 1, "RGB8": 3, "RGBA8": 4}  # SNN_IO_*
+class FrameIO2(C.Structure):
+    """snn_frame_io2 (include/snn_c.h): 8- or 16-bit frame formats at the model's ends, their affine maps and the 16-bit container layout."""
+    _fields_ = FrameIO._fields_ + [("in_shift", C.c_int), ("out_maxval", C.c_int), ("out_shift", C.c_int)]
+
+
+FRAME_FORMATS = {None: 0, "float": 0, "R8": 1, "RGB8": 3, "RGBA8": 4, "R16": 0x101, "RGB16": 0x103, "RGBA16": 0x104}  # SNN_IO_*
 
 
 class Model:
@@ -138,29 +146,40 @@ class Model:
 
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
-                 out_offset=(0, 0, 0, 0)):
+                 out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
-        output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out."""
+        output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
+        "R16" / "RGB16" / "RGBA16": 16-bit frames (snn_model_create6), uint16 arrays; y = ((u >> frame_in_shift) - in_means[c]) * in_norms[c] in,
+        clamp(rint(x * out_scale[c] + out_offset[c]), 0, frame_out_maxval) << frame_out_shift out (10-bit: maxval 1023; P010-style: shifts 6)."""
         self.h = _P()
-        io = FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], (C.c_float * 4)(*in_means), (C.c_float * 4)(*in_norms),
-                     (C.c_float * 4)(*out_scale), (C.c_float * 4)(*out_offset))
-        assert lib().snn_model_create5(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half),
-                                       int(capture_graph), int(batch), C.byref(io), C.byref(self.h)) == 0
+        self.frame_dtypes = tuple(np.uint16 if f in ("R16", "RGB16", "RGBA16") else np.uint8 for f in (input_format, output_format))
+        if np.uint16 in self.frame_dtypes:
+            io = FrameIO2(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], (C.c_float * 4)(*in_means), (C.c_float * 4)(*in_norms),
+                          (C.c_float * 4)(*out_scale), (C.c_float * 4)(*out_offset), frame_in_shift, frame_out_maxval, frame_out_shift)
+            create = lib().snn_model_create6
+        else:
+            io = FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], (C.c_float * 4)(*in_means), (C.c_float * 4)(*in_norms),
+                         (C.c_float * 4)(*out_scale), (C.c_float * 4)(*out_offset))
+            create = lib().snn_model_create5
+        assert create(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph), int(batch),
+                      C.byref(io), C.byref(self.h)) == 0
         self.batch = batch
         self.in_shape = (h, w, c) if batch == 1 else (batch, h, w, c)
 
     def upload_frame(self, img):
-        """uint8 [batch x] H x W x C into the model's 8-bit input frame (no per-call allocation)."""
-        img = np.ascontiguousarray(img, dtype=np.uint8).reshape(self.in_shape)
-        assert lib().snn_model_upload_frame_u8(self.h, img.ctypes.data_as(_P)) == 0
+        """uint8 (uint16 for a 16-bit input format) [batch x] H x W x C into the model's input frame (no per-call allocation)."""
+        img = np.ascontiguousarray(img, dtype=self.frame_dtypes[0]).reshape(self.in_shape)
+        up = lib().snn_model_upload_frame_u16 if self.frame_dtypes[0] == np.uint16 else lib().snn_model_upload_frame_u8
+        assert up(self.h, img.ctypes.data_as(_P)) == 0
 
     def output_frame(self):
-        """the model's 8-bit output frame of the last run, uint8 [batch x] H x W x C"""
+        """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
-        out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=np.uint8)
-        assert lib().snn_model_download_frame_u8(self.h, out.ctypes.data_as(_P)) == 0
+        out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=self.frame_dtypes[1])
+        down = lib().snn_model_download_frame_u16 if self.frame_dtypes[1] == np.uint16 else lib().snn_model_download_frame_u8
+        assert down(self.h, out.ctypes.data_as(_P)) == 0
         return out
 
     def upload(self, x):

@@ -105,7 +105,8 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
             SNN_RIP("output format %s for a %u-channel output", getColorFormatDesc(cp.outputFormat).name, static_cast<unsigned>(o.channels()));
         hb->initFrameIO(frameIn, frameOut, static_cast<int>(o.batch()), static_cast<int>(id.height), static_cast<int>(id.width), static_cast<int>(id.channels),
                         static_cast<int>(o.height()), static_cast<int>(o.width()), static_cast<int>(o.channels()), cp.halfTensors ? SNNHIP_F16 : SNNHIP_F32,
-                        cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset);
+                        cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset, frameIn && isFrame16Format(id.format),
+                        frameOut && isFrame16Format(cp.outputFormat), cp.frameInShift, cp.frameOutMaxval, cp.frameOutShift);
         frameBackend = hb;
     }
     backend->finalizeStages(stages, cp.dumpOutputs, cp.fuseChains);

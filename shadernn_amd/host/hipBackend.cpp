@@ -61,13 +61,22 @@ HipBackend::~HipBackend() {
 }
 
 void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
-                             const float norms[4], const float scale[4], const float offset[4]) {
-    if (in) {
+                             const float norms[4], const float scale[4], const float offset[4], bool in16, bool out16, int inShift, int outMaxval,
+                             int outShift) {
+    if (in && in16) {
+        snnhip_u16_in_desc d{n, inH, inW, inC, dtype, {means[0], means[1], means[2], means[3]}, {norms[0], norms[1], norms[2], norms[3]}, inShift};
+        hipChk(snnhip_u16_in_plan_create(ctx, &d, &frameInPlan), "snnhip_u16_in_plan_create");
+        hipChk(snnhip_tensor_alloc(ctx, n, inH, inW, inC, SNNHIP_U16, &frameInT), "snnhip_tensor_alloc (input frame)");
+    } else if (in) {
         snnhip_u8_in_desc d{n, inH, inW, inC, dtype, {means[0], means[1], means[2], means[3]}, {norms[0], norms[1], norms[2], norms[3]}};
         hipChk(snnhip_u8_in_plan_create(ctx, &d, &frameInPlan), "snnhip_u8_in_plan_create");
         hipChk(snnhip_tensor_alloc(ctx, n, inH, inW, inC, SNNHIP_U8, &frameInT), "snnhip_tensor_alloc (input frame)");
     }
-    if (out) {
+    if (out && out16) {
+        snnhip_u16_out_desc d{n, outH, outW, outC, dtype, {scale[0], scale[1], scale[2], scale[3]}, {offset[0], offset[1], offset[2], offset[3]}, outMaxval, outShift};
+        hipChk(snnhip_u16_out_plan_create(ctx, &d, &frameOutPlan), "snnhip_u16_out_plan_create");
+        hipChk(snnhip_tensor_alloc(ctx, n, outH, outW, outC, SNNHIP_U16, &frameOutT), "snnhip_tensor_alloc (output frame)");
+    } else if (out) {
         snnhip_u8_out_desc d{n, outH, outW, outC, dtype, {scale[0], scale[1], scale[2], scale[3]}, {offset[0], offset[1], offset[2], offset[3]}};
         hipChk(snnhip_u8_out_plan_create(ctx, &d, &frameOutPlan), "snnhip_u8_out_plan_create");
         hipChk(snnhip_tensor_alloc(ctx, n, outH, outW, outC, SNNHIP_U8, &frameOutT), "snnhip_tensor_alloc (output frame)");
@@ -75,11 +84,11 @@ void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC
 }
 
 void HipBackend::runFrameIn(const ImageTexture& modelInput) {
-    if (frameInPlan && !frameInFused) hipChk(snnhip_plan_run(frameInPlan, frameInT, modelInput.tensor()), "snnhip_plan_run (u8_in)");
+    if (frameInPlan && !frameInFused) hipChk(snnhip_plan_run(frameInPlan, frameInT, modelInput.tensor()), "snnhip_plan_run (frame in)");
 }
 
 void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
-    if (frameOutPlan && !frameOutFused) hipChk(snnhip_plan_run(frameOutPlan, lastOutput.tensor(), frameOutT), "snnhip_plan_run (u8_out)");
+    if (frameOutPlan && !frameOutFused) hipChk(snnhip_plan_run(frameOutPlan, lastOutput.tensor(), frameOutT), "snnhip_plan_run (frame out)");
 }
 
 // counterpart of VulkanBackend::initRenderPasses -> VulkanRenderPass ctor (vulkanBackend.cpp:43-78, vulkanRenderpass.cpp:103-178):

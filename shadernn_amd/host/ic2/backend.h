@@ -111,8 +111,10 @@ public:
     void groupEnd() override;
     // 8-bit frame I/O (MixedInferenceCore::CreationParameters::outputFormat / inputsDesc[0].format): called before finalizeStages.  The conversion
     // plans become nodes of the fusion graph; runFrameIn / runFrameOut launch whatever was not folded into a stage's fused plan.
+    // in16 / out16: that end is a 16-bit frame (u16 plans, SNNHIP_U16 tensor) with the container layout inShift / outMaxval, outShift.
     void initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
-                     const float norms[4], const float scale[4], const float offset[4]);
+                     const float norms[4], const float scale[4], const float offset[4], bool in16 = false, bool out16 = false, int inShift = 0,
+                     int outMaxval = 65535, int outShift = 0);
     void runFrameIn(const ImageTexture& modelInput);
     void runFrameOut(const ImageTexture& lastOutput);
     snnhip_tensor* frameInput() const { return frameInT; }
@@ -120,7 +122,7 @@ public:
 
 private:
     snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned
-    snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // owned, SNNHIP_U8
+    snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // owned, SNNHIP_U8 or SNNHIP_U16
     bool frameInFused = false, frameOutFused = false;
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned

@@ -71,6 +71,9 @@ public:
         ColorFormat outputFormat = ColorFormat::RGBA32F;
         float frameInMeans[4] = {0, 0, 0, 0}, frameInNorms[4] = {1, 1, 1, 1};
         float frameOutScale[4] = {1, 1, 1, 1}, frameOutOffset[4] = {0, 0, 0, 0};
+        // 16-bit frames (R16, RGB16, RGBA16: snnhip_u16_in_plan_create / _u16_out_plan_create, handled exactly as the 8-bit ones): the container's
+        // layout.  Low-aligned 10 / 12-bit: maxval 1023 / 4095, shifts 0; P010-style high-aligned 10-bit: maxval 1023, shifts 6; full 16-bit: 65535.
+        int frameInShift = 0, frameOutMaxval = 65535, frameOutShift = 0;
         bool halfTensors = false; // the model's tensors are fp16 (preferHp): the conversions read / write halfs
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
@@ -82,7 +85,7 @@ public:
     std::string describe() const; // HIP extension: which kernel variant each stage runs
     // HIP extension: run the next inferences launch by launch even when a recording exists (per-launch profiling needs the plans to run)
     void suspendReplay(bool suspend) { replaySuspended = suspend; }
-    // HIP extension: the model's 8-bit input / output frame tensors (SNNHIP_U8 [batch][H][W][C]; null without 8-bit I/O at that end)
+    // HIP extension: the model's input / output frame tensors (SNNHIP_U8 or SNNHIP_U16 [batch][H][W][C]; null without frame I/O at that end)
     snnhip_tensor* frameInput() const;
     snnhip_tensor* frameOutput() const;
 

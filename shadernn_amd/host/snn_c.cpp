@@ -76,12 +76,41 @@ static bool frameFormat(int f, ColorFormat* c) {
     }
 }
 
+static bool frameFormat2(int f, ColorFormat* c) {
+    switch (f) {
+    case SNN_IO_R16: *c = ColorFormat::R16; return true;
+    case SNN_IO_RGB16: *c = ColorFormat::RGB16; return true;
+    case SNN_IO_RGBA16: *c = ColorFormat::RGBA16; return true;
+    default: return frameFormat(f, c);
+    }
+}
+
 int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, const snn_frame_io* io, snn_model** out) {
+    ColorFormat probe = ColorFormat::NONE;
+    if (io && (!frameFormat(io->in_format, &probe) || !frameFormat(io->out_format, &probe))) return -1; // (the 8-bit formats only)
+    if (!io) return snn_model_create6(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, nullptr, out);
+    snn_frame_io2 io2{};
+    io2.in_format = io->in_format;
+    io2.out_format = io->out_format;
+    memcpy(io2.in_means, io->in_means, sizeof(io2.in_means));
+    memcpy(io2.in_norms, io->in_norms, sizeof(io2.in_norms));
+    memcpy(io2.out_scale, io->out_scale, sizeof(io2.out_scale));
+    memcpy(io2.out_offset, io->out_offset, sizeof(io2.out_offset));
+    io2.out_maxval = 65535;
+    return snn_model_create6(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, out);
+}
+
+int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_frame_io2* io, snn_model** out) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
     ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
-    if (io && (!frameFormat(io->in_format, &inFmt) || !frameFormat(io->out_format, &outFmt))) return -1;
-    if (io && io->in_format != SNN_IO_FLOAT && io->in_format != in_c) return -1;
+    if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
+    if (io && io->in_format != SNN_IO_FLOAT && (io->in_format & 0xff) != in_c) return -1;
+    if (io && isFrame16Format(inFmt) && (io->in_shift < 0 || io->in_shift > 15)) return -1;
+    if (io && isFrame16Format(outFmt) &&
+        (io->out_maxval < 1 || io->out_maxval > 65535 || io->out_shift < 0 || io->out_shift > 15 || (static_cast<long long>(io->out_maxval) << io->out_shift) > 65535))
+        return -1;
     const bool half = prefer_half != 0;
     auto* m = new snn_model();
     // C++ exceptions (std::bad_alloc, a parser's std::out_of_range, ...) must not unwind through the C boundary: report -2 and free what was built.
@@ -109,6 +138,9 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
             memcpy(cp.frameInNorms, io->in_norms, sizeof(cp.frameInNorms));
             memcpy(cp.frameOutScale, io->out_scale, sizeof(cp.frameOutScale));
             memcpy(cp.frameOutOffset, io->out_offset, sizeof(cp.frameOutOffset));
+            cp.frameInShift = io->in_shift;
+            cp.frameOutMaxval = io->out_maxval;
+            cp.frameOutShift = io->out_shift;
         }
         m->core = MixedInferenceCore::create(m->context, cp);
         makeIO(m, half);
@@ -137,12 +169,26 @@ int snn_model_destroy(snn_model* m) {
 
 int snn_model_upload_frame_u8(snn_model* m, const unsigned char* nhwc) {
     snnhip_tensor* t = m && nhwc ? m->core->frameInput() : nullptr;
+    if (t && snnhip_tensor_dtype(t) != SNNHIP_U8) return -1; // (a 16-bit end: snn_model_upload_frame_u16)
     return t && snnhip_tensor_upload_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
 }
 
 int snn_model_download_frame_u8(snn_model* m, unsigned char* nhwc) {
     snnhip_tensor* t = m && nhwc ? m->core->frameOutput() : nullptr;
+    if (t && snnhip_tensor_dtype(t) != SNNHIP_U8) return -1;
     return t && snnhip_tensor_download_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
+}
+
+int snn_model_upload_frame_u16(snn_model* m, const unsigned short* nhwc) {
+    snnhip_tensor* t = m && nhwc ? m->core->frameInput() : nullptr;
+    if (!t || snnhip_tensor_dtype(t) != SNNHIP_U16) return -1;
+    return snnhip_tensor_upload_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
+}
+
+int snn_model_download_frame_u16(snn_model* m, unsigned short* nhwc) {
+    snnhip_tensor* t = m && nhwc ? m->core->frameOutput() : nullptr;
+    if (!t || snnhip_tensor_dtype(t) != SNNHIP_U16) return -1;
+    return snnhip_tensor_download_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
 }
 
 int snn_model_upload_input(snn_model* m, const float* nhwc) {

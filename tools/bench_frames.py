@@ -22,6 +22,17 @@ default), f16 (the fused fp16 chain, chain rules A16 / B16, SNNHIP_ESPCN_F16=1) 
 step per form with the spread over the rounds, the kernels of the launch trace, and the bytes each form's launches move per frame.
 
     python tools/bench_frames.py --half --scale 2
+
+--bits 10 | 12 | 16 (with any --scale): two more forms in the same alternation and the same
+end-to-end rounds, u16 (16-bit frames, the conversions folded into the fp32 kernels: two launches) and u16_sep (u16_in, the fp32 chain, u16_out:
+four launches), on low-aligned frames of that bit depth normalised symmetrically ((2^bits - 1) / 2).  The f32 and u8 forms of the same run are the
+yardstick; the report carries every form's spread over its timed regions and its traced kernels.  With --half the two forms are f16_u16 and
+f16_u16_sep around the fused fp16 chain (device step only, as the other --half forms).  One run prints one scale; profiles/espcn_u16_frames.json
+holds the JSON objects of six runs (--bits 10 at --scale 2, 3, 4, each without and with --half) under the keys scale<r> / half_scale<r>, next to
+the line of `python bench.py --gpus 1 --steps 20 --warmup 5` taken in the same session.
+
+    python tools/bench_frames.py --bits 10 --scale 3
+    python tools/bench_frames.py --bits 10 --half
 """
 import argparse
 import json
@@ -88,15 +99,32 @@ def main_half(a):
     finally:
         capi.set_option("SNNHIP_ESPCN_F16", None)
     assert c16.num_steps() == 2 and c16u8.num_steps() == 2, (c16.describe(), c16u8.describe())
+    if a.bits:  # 16-bit frames of that depth around the fused fp16 chain: folded (two launches) and as launches of their own (four)
+        maxval = (1 << a.bits) - 1
+        halfv = maxval / 2.0
+        u16 = np.random.default_rng(2).integers(0, maxval + 1, size=(1, H, W, 1)).astype(np.uint16)
+        win = capi.u16_in_plan(ctx, 1, H, W, 1, (halfv, 0, 0, 0), (1 / halfv, 1, 1, 1), dtype=capi.F16)
+        wout = capi.u16_out_plan(ctx, *shape, (halfv, 0, 0, 0), (halfv, 0, 0, 0), maxval=maxval, dtype=capi.F16)
+        capi.set_option("SNNHIP_ESPCN_F16", "1")
+        try:
+            c16u16 = capi.chain_plan(ctx, [win] + l16 + [wout])
+        finally:
+            capi.set_option("SNNHIP_ESPCN_F16", None)
+        assert c16u16.num_steps() == 2, c16u16.describe()
     forms = {
         "f32": dict(plan=capi.chain_plan(ctx, l32), x=capi.Tensor(ctx, 1, H, W, 1), y=capi.Tensor(ctx, *shape)),
         "f16_layers": dict(plan=Seq(l16, capi.F16), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.F16), y=capi.Tensor(ctx, *shape, dtype=capi.F16)),
         "f16": dict(plan=c16, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.F16), y=capi.Tensor(ctx, *shape, dtype=capi.F16)),
         "f16_u8": dict(plan=c16u8, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8), y=capi.Tensor(ctx, *shape, dtype=capi.U8)),
     }
+    if a.bits:
+        forms["f16_u16"] = dict(plan=c16u16, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U16), y=capi.Tensor(ctx, *shape, dtype=capi.U16))
+        forms["f16_u16_sep"] = dict(plan=Seq([win, c16, wout], capi.F16), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U16), y=capi.Tensor(ctx, *shape, dtype=capi.U16))
     for f in forms.values():
         if f["x"].dtype == capi.U8:
             f["x"].upload_u8(u8)
+        elif f["x"].dtype == capi.U16:
+            f["x"].upload_u16(u16)
         else:
             f["x"].upload(f32)
     timer = capi.Timer(ctx)
@@ -135,6 +163,11 @@ def main_half(a):
     out["device_f16_over_f32"] = round(out["f16"]["device_ms_median"] / out["f32"]["device_ms_median"], 4)
     out["device_f16_over_f16_layers"] = round(out["f16"]["device_ms_median"] / out["f16_layers"]["device_ms_median"], 4)
     out["device_f16_u8_over_f16"] = round(out["f16_u8"]["device_ms_median"] / out["f16"]["device_ms_median"], 4)
+    if a.bits:
+        out["bits"] = a.bits
+        out["device_f16_u16_over_f16"] = round(out["f16_u16"]["device_ms_median"] / out["f16"]["device_ms_median"], 4)
+        out["device_f16_u16_over_f16_u8"] = round(out["f16_u16"]["device_ms_median"] / out["f16_u8"]["device_ms_median"], 4)
+        out["device_f16_u16_over_f16_u16_sep"] = round(out["f16_u16"]["device_ms_median"] / out["f16_u16_sep"]["device_ms_median"], 4)
     out["spread_max"] = max(out[k]["spread"] for k in forms)
     print(json.dumps(out, indent=1))
     ctx.close()
@@ -144,6 +177,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
     ap.add_argument("--scale", type=int, default=2, choices=[2, 3, 4], help="upscale factor; the input size follows it (output 3840 x 2160) unless --h / --w are given")
+    ap.add_argument("--bits", type=int, default=0, choices=[0, 10, 12, 16], help="also time 16-bit frames of this bit depth, folded and as separate launches")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
     ap.add_argument("--h", type=int, default=0)
     ap.add_argument("--w", type=int, default=0)
@@ -208,14 +242,27 @@ def main():
                                    yh=np.empty(shape, np.float32))
         forms["u8_layers"] = dict(plan=Seq([uin] + layers + [uout], [(1, H, W, 1)] + lshapes + [shape]), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8),
                                   y=capi.Tensor(ctx, *shape, dtype=capi.U8), xh=u8, yh=np.empty(shape, np.uint8))
+    if a.bits:
+        maxval = (1 << a.bits) - 1
+        half = maxval / 2.0
+        u16 = np.random.default_rng(2).integers(0, maxval + 1, size=(1, H, W, 1)).astype(np.uint16)
+        win = capi.u16_in_plan(ctx, 1, H, W, 1, (half, 0, 0, 0), (1 / half, 1, 1, 1))
+        wout = capi.u16_out_plan(ctx, *shape, (half, 0, 0, 0), (half, 0, 0, 0), maxval=maxval)
+        forms["u16"] = dict(plan=capi.chain_plan(ctx, [win] + layers + [wout]), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U16),
+                            y=capi.Tensor(ctx, *shape, dtype=capi.U16), xh=u16, yh=np.empty(shape, np.uint16))
+        forms["u16_sep"] = dict(plan=Seq([win, fchain, wout], [(1, H, W, 1), shape]), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U16),
+                                y=capi.Tensor(ctx, *shape, dtype=capi.U16), xh=u16, yh=np.empty(shape, np.uint16))
+        assert forms["u16"]["plan"].num_steps() == 2, forms["u16"]["plan"].describe()
     for f in forms.values():
         if f["x"].dtype == capi.U8:
             f["x"].upload_u8(f["xh"])
+        elif f["x"].dtype == capi.U16:
+            f["x"].upload_u16(f["xh"])
         else:
             f["x"].upload(f["xh"])
 
     def upload(f):
-        if f["x"].dtype == capi.U8:
+        if f["x"].dtype in (capi.U8, capi.U16):
             capi.check(capi.lib().snnhip_tensor_upload_raw(f["x"].h, f["xh"].ctypes.data_as(capi._P), f["xh"].nbytes))
         else:
             capi.check(capi.lib().snnhip_tensor_upload(f["x"].h, capi._fptr(f["xh"])))
@@ -259,6 +306,15 @@ def main():
     out["device_u8_over_f32"] = round(out["u8"]["device_ms_median"] / out["f32"]["device_ms_median"], 4)
     out["device_u8_over_u8_sep"] = round(out["u8"]["device_ms_median"] / out["u8_sep"]["device_ms_median"], 4)
     out["e2e_fps_u8_over_f32"] = round(out["u8"]["e2e_frames_per_s"] / out["f32"]["e2e_frames_per_s"], 4)
+    if a.bits:
+        out["scale"], out["bits"] = R, a.bits
+        for k in forms:
+            out[k]["device_spread"] = round((max(dev[k]) - min(dev[k])) / statistics.median(dev[k]), 4)
+        out["device_u16_over_f32"] = round(out["u16"]["device_ms_median"] / out["f32"]["device_ms_median"], 4)
+        out["device_u16_over_u8"] = round(out["u16"]["device_ms_median"] / out["u8"]["device_ms_median"], 4)
+        out["device_u16_over_u16_sep"] = round(out["u16"]["device_ms_median"] / out["u16_sep"]["device_ms_median"], 4)
+        out["e2e_fps_u16_over_f32"] = round(out["u16"]["e2e_frames_per_s"] / out["f32"]["e2e_frames_per_s"], 4)
+        out["e2e_fps_u16_over_u8"] = round(out["u16"]["e2e_frames_per_s"] / out["u8"]["e2e_frames_per_s"], 4)
     if per_layer:
         out["scale"] = R
         for k in ("f32", "u8"):
@@ -274,6 +330,9 @@ def main():
         rep = capi.trace_end()
         kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
         traces[k] = [(item.get("function"), item.get("launches", 0), item.get("total_ms", item.get("ms", 0.0))) for item in kernels]
+    if a.bits and not per_layer:
+        for k in forms:
+            out[k]["kernels"] = [{"function": name, "launches": n, "us_per_launch": round(1e3 * ms / max(n, 1), 2)} for name, n, ms in traces[k]]
     if per_layer:
         import re
 
