@@ -72,6 +72,23 @@ int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int
  * likewise return -1 on a 16-bit end). */
 int snn_model_upload_frame_u16(snn_model* m, const unsigned short* nhwc);
 int snn_model_download_frame_u16(snn_model* m, unsigned short* nhwc);
+/* Colour frames around a luma-only model (ESPCN: one channel in, one channel out at r times the extent, r = 1..4): RGB8 or RGBA8 frames at BOTH ends,
+ * through a struct and an entry point of their own -- snn_frame_io, snn_frame_io2 and snn_model_create5 / 6 keep their layout and behaviour (an RGB8
+ * format on a one-channel model through them still returns -1).  The model itself is built exactly as snn_model_create5 builds it with SNN_IO_R8 at
+ * both ends (in_mean / in_norm / out_scale / out_offset are the luma plane's u8_in / u8_out maps, so ESPCN still runs as its two fused 8-bit
+ * kernels); a run brackets it with two more launches on the same stream: the colour frame's luma plane into the model's input frame
+ * (snnhip_rgb_luma_plan_create), and the model's output frame merged with the colour frame's bicubically upsampled chroma into the colour output
+ * frame (snnhip_ycc_merge_plan_create; include/snnhip.h states the arithmetic, kr / kb are its matrix coefficients: BT.601 0.299 / 0.114).  With
+ * capture_graph all four launches are in the one recorded graph.  snn_model_upload_frame_u8 then takes [batch][H][W][C] bytes and
+ * snn_model_download_frame_u8 returns [batch][rH][rW][C]; snn_model_describe lists the two extra launches.  Returns -1 unless the model has a
+ * one-channel input and a one-channel output of r times the input's extent, r = 1..4, and format is SNN_IO_RGB8 or SNN_IO_RGBA8. */
+typedef struct snn_colour_io {
+    int format; /* SNN_IO_RGB8 or SNN_IO_RGBA8, both ends */
+    float kr, kb;
+    float in_mean, in_norm, out_scale, out_offset; /* the luma plane's u8_in / u8_out maps */
+} snn_colour_io;
+int snn_model_create7(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_colour_io* io, snn_model** out);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

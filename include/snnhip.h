@@ -387,6 +387,35 @@ typedef struct {
     int maxval, shift;
 } snnhip_u16_out_desc;
 int snnhip_u16_out_plan_create(snnhip_ctx* ctx, const snnhip_u16_out_desc* desc, snnhip_plan** out);
+
+/* Colour frames around a luma-only model (ESPCN, like the reference's demo/modelInferenceESPCN.py, takes and returns the Y plane only): the luma
+ * split in front of the model and the chroma merge behind it, on interleaved 8-bit RGB (C = 3) or RGBA (C = 4) frames.  DESIGN.md section 4.13.
+ * The arithmetic contract, stated once:
+ *   Matrix: full-range Y'CbCr with coefficients kr, kb of the desc and kg = 1 - kr - kb, computed in double and rounded to float.  BT.601 is
+ *     kr = 0.299, kb = 0.114 (what cv2.COLOR_BGR2YCrCb uses); BT.709 is 0.2126 / 0.0722.  Limited range is not offered.
+ *   rgb_luma:   U8 [N][H][W][C] -> U8 [N][H][W][1].  ylo = kr*R + kg*G + kb*B in fp32, q = clamp(rint(ylo), 0, 255), ties to even: the U8 luma plane
+ *     that snnhip_u8_in_plan_create (and chain rule A8) consumes unchanged.
+ *   ycc_merge:  inputs[0] = Yhi, U8 [N][r*H][r*W][1]; inputs[1] = the original low-resolution frame, U8 [N][H][W][C]; output U8 [N][r*H][r*W][C]
+ *     (snnhip_plan_run_n, 2 inputs).  r follows from the two shapes: an integer 1..4, the same on both axes (and the desc's r), else
+ *     SNNHIP_E_INVALID with a message.  No quantised CbCr plane exists anywhere: per low-resolution pixel ylo as above, unquantised (one device
+ *     function serves both plans), dR = R - ylo, dB = B - ylo.  dR~, dB~ are dR, dB resampled to the output grid with aligned pixel centres: output
+ *     column X samples sx = (X + 0.5) / r - 0.5 (rows likewise); i0 = floor(sx), t = sx - i0, taps at i0 - 1 .. i0 + 2 with indices clamped to
+ *     [0, W - 1] (replicate edge), weights the Keys cubic with a = -0.5 (Catmull-Rom) at distances 1 + t, t, 1 - t, 2 - t.  An integer r has
+ *     exactly r phases: the [r][4] weight table (row p = phase X mod r) is computed on the host in double, rounded to fp32 and handed to the
+ *     kernel (snnhip_bicubic_taps returns it).  The filter is separable: horizontal, then vertical.  Then
+ *         R' = Yhi + dR~,   B' = Yhi + dB~,   G' = Yhi - (kr*dR~ + kb*dB~) / kg,   q = clamp(rint(.), 0, 255)
+ *     and, for C = 4, the alpha byte of the low-resolution pixel (Y / r, X / r) (integer division), copied.
+ *   Consequences: a grey frame (R = G = B) comes out as R' = G' = B' = Yhi byte for byte; in fp32 the value in front of the rounding stays within
+ *     about 5e-5 of a float64 evaluation (fma contraction moves it by the same order).
+ * Both plans read and write SNNHIP_U8 tensors only (a float tensor at any position is refused by snnhip_plan_run_n); plan creation returns
+ * SNNHIP_E_INVALID with a message unless C is 3 or 4, r is 1..4 and 0 < kr, 0 < kb, kr + kb < 1.  snnhip_plan_cost reports the bytes each moves:
+ * every input once and the output once. */
+typedef struct { int N, H, W, C; float kr, kb; } snnhip_rgb_luma_desc;
+int snnhip_rgb_luma_plan_create(snnhip_ctx* ctx, const snnhip_rgb_luma_desc* desc, snnhip_plan** out);
+typedef struct { int N, H, W, C; int r; float kr, kb; } snnhip_ycc_merge_desc; /* H, W: the LOW-resolution frame */
+int snnhip_ycc_merge_plan_create(snnhip_ctx* ctx, const snnhip_ycc_merge_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_n, 2 inputs */
+/* host only, no context (like snnhip_espcn_f16_pack_weights): the [r][4] fp32 tap table the merge kernel uses, r = 1..4, capacity >= 4*r floats */
+int snnhip_bicubic_taps(int r, float* out, int capacity);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

@@ -95,6 +95,14 @@ class U16OutDesc(C.Structure):
                 ("shift", C.c_int)]
 
 
+class RgbLumaDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
+
+
+class YccMergeDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("r", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -169,6 +177,9 @@ SIGNATURES = {
     "snnhip_u8_out_plan_create": (C.c_int, [_P, C.POINTER(U8OutDesc), C.POINTER(_P)]),
     "snnhip_u16_in_plan_create": (C.c_int, [_P, C.POINTER(U16InDesc), C.POINTER(_P)]),
     "snnhip_u16_out_plan_create": (C.c_int, [_P, C.POINTER(U16OutDesc), C.POINTER(_P)]),
+    "snnhip_rgb_luma_plan_create": (C.c_int, [_P, C.POINTER(RgbLumaDesc), C.POINTER(_P)]),
+    "snnhip_ycc_merge_plan_create": (C.c_int, [_P, C.POINTER(YccMergeDesc), C.POINTER(_P)]),
+    "snnhip_bicubic_taps": (C.c_int, [C.c_int, _FP, C.c_int]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -690,6 +701,33 @@ def u8_out_plan(ctx, N, H, W, Cc, scale=(1, 1, 1, 1), offset=(0, 0, 0, 0), dtype
     h = _P()
     check(lib().snnhip_u8_out_plan_create(ctx.h, C.byref(d), C.byref(h)))
     return Plan(ctx, h)
+
+
+BT601 = (0.299, 0.114)  # (kr, kb): what cv2.COLOR_BGR2YCrCb uses; BT.709 is (0.2126, 0.0722)
+
+
+def rgb_luma_plan(ctx, N, H, W, Cc, kr=BT601[0], kb=BT601[1]):
+    """U8 [N][H][W][Cc] (Cc = 3 RGB, 4 RGBA) -> U8 [N][H][W][1]: q = clamp(rint(kr*R + kg*G + kb*B), 0, 255), kg = 1 - kr - kb."""
+    d = RgbLumaDesc(N, H, W, Cc, kr, kb)
+    h = _P()
+    check(lib().snnhip_rgb_luma_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def ycc_merge_plan(ctx, N, H, W, Cc, r, kr=BT601[0], kb=BT601[1]):
+    """plan.run([Yhi U8 [N][r*H][r*W][1], frame U8 [N][H][W][Cc]], out U8 [N][r*H][r*W][Cc]): the frame's chroma, bicubically upsampled, around Yhi
+    (include/snnhip.h states the arithmetic).  H, W are the LOW-resolution frame's."""
+    d = YccMergeDesc(N, H, W, Cc, r, kr, kb)
+    h = _P()
+    check(lib().snnhip_ycc_merge_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def bicubic_taps(r):
+    """snnhip_bicubic_taps (host side only, no GPU): the [r][4] float32 Catmull-Rom weight table of an r-fold upscale, row p = phase X mod r."""
+    out = np.zeros((r, 4), np.float32)
+    check(lib().snnhip_bicubic_taps(r, _fptr(out), out.size))
+    return out
 
 
 def deconv2d_plan(ctx, N, H, W, w_oihw, bias=None, stride=2, same=True, act="", leaky=0.0, bn=None):

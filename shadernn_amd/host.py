@@ -19,6 +19,7 @@ SIGNATURES = {
     "snn_model_create4": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "snn_model_create5": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create6": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create7": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_upload_frame_u16": (C.c_int, [_P, _P]),
     "snn_model_download_frame_u16": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u8": (C.c_int, [_P, _P]),
@@ -138,6 +139,12 @@ class FrameIO2(C.Structure):
     _fields_ = FrameIO._fields_ + [("in_shift", C.c_int), ("out_maxval", C.c_int), ("out_shift", C.c_int)]
 
 
+class ColourIO(C.Structure):
+    """snn_colour_io (include/snn_c.h): RGB8 / RGBA8 frames around a luma-only model, the matrix coefficients and the luma plane's 8-bit maps."""
+    _fields_ = [("format", C.c_int), ("kr", C.c_float), ("kb", C.c_float), ("in_mean", C.c_float), ("in_norm", C.c_float), ("out_scale", C.c_float),
+                ("out_offset", C.c_float)]
+
+
 FRAME_FORMATS = {None: 0, "float": 0, "R8": 1, "RGB8": 3, "RGBA8": 4, "R16": 0x101, "RGB16": 0x103, "RGBA16": 0x104}  # SNN_IO_*
 
 
@@ -146,13 +153,27 @@ class Model:
 
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
-                 out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0):
+                 out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
         output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
         "R16" / "RGB16" / "RGBA16": 16-bit frames (snn_model_create6), uint16 arrays; y = ((u >> frame_in_shift) - in_means[c]) * in_norms[c] in,
-        clamp(rint(x * out_scale[c] + out_offset[c]), 0, frame_out_maxval) << frame_out_shift out (10-bit: maxval 1023; P010-style: shifts 6)."""
+        clamp(rint(x * out_scale[c] + out_offset[c]), 0, frame_out_maxval) << frame_out_shift out (10-bit: maxval 1023; P010-style: shifts 6).
+        colour "RGB8" / "RGBA8" (snn_model_create7): colour frames around a luma-only model (c == 1, e.g. ESPCN) -- upload_frame takes uint8
+        [batch x] H x W x C, output_frame returns [batch x] rH x rW x C: the model runs on the frame's luma plane (coefficients kr, kb; BT.601 by
+        default) with R8 frames at its own ends (in_means[0] / in_norms[0] / out_scale[0] / out_offset[0]), the chroma is upsampled bicubically."""
         self.h = _P()
+        self.colour_channels = 0
+        if colour is not None:
+            assert input_format is None and output_format is None, "colour frames replace input_format / output_format"
+            self.colour_channels = {"RGB8": 3, "RGBA8": 4}[colour]
+            self.frame_dtypes = (np.uint8, np.uint8)
+            io = ColourIO(FRAME_FORMATS[colour], kr, kb, in_means[0], in_norms[0], out_scale[0], out_offset[0])
+            assert lib().snn_model_create7(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                           int(batch), C.byref(io), C.byref(self.h)) == 0
+            self.batch = batch
+            self.in_shape = (h, w, self.colour_channels) if batch == 1 else (batch, h, w, self.colour_channels)
+            return
         self.frame_dtypes = tuple(np.uint16 if f in ("R16", "RGB16", "RGBA16") else np.uint8 for f in (input_format, output_format))
         if np.uint16 in self.frame_dtypes:
             io = FrameIO2(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], (C.c_float * 4)(*in_means), (C.c_float * 4)(*in_norms),
@@ -177,6 +198,8 @@ class Model:
         """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
+        if self.colour_channels:
+            d = (d[0], d[1], self.colour_channels)
         out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=self.frame_dtypes[1])
         down = lib().snn_model_download_frame_u16 if self.frame_dtypes[1] == np.uint16 else lib().snn_model_download_frame_u8
         assert down(self.h, out.ctypes.data_as(_P)) == 0

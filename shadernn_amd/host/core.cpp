@@ -107,6 +107,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
                         static_cast<int>(o.height()), static_cast<int>(o.width()), static_cast<int>(o.channels()), cp.halfTensors ? SNNHIP_F16 : SNNHIP_F32,
                         cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset, frameIn && isFrame16Format(id.format),
                         frameOut && isFrame16Format(cp.outputFormat), cp.frameInShift, cp.frameOutMaxval, cp.frameOutShift);
+        if (cp.colourChannels) hb->initColourIO(cp.colourChannels, cp.colourKr, cp.colourKb);
         frameBackend = hb;
     }
     backend->finalizeStages(stages, cp.dumpOutputs, cp.fuseChains);
@@ -117,7 +118,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         // A recorded graph pays off when an inference is MANY launches (ResNet-18 23, MobileNetV2 41, Candy 88 after fusion).  For a handful it costs:
         // consecutive hipGraphLaunch calls leave ~5 us between graphs on the stream where plain kernel launches queue back to back (measured on the
         // fused ESPCN, 2 launches of 86 + 34 us: 125.0 us per inference replayed, 120 launched directly) -- below the threshold run() just launches.
-        int launches = 0;
+        int launches = frameBackend ? frameBackend->colourLaunches() : 0;
         for (auto& s : stages) {
             auto* ml = static_cast<dp::GenericModelLayer*>(s.layer->modelLayer);
             if (!ml || s.layer->isInputLayer) continue;
@@ -265,6 +266,7 @@ std::string MixedInferenceCore::describe() const {
         if (stages[i].fusedAway) ss << "  (fused into a later stage's plan)";
         ss << "\n";
     }
+    if (frameBackend) ss << frameBackend->describeColour();
     return ss.str();
 }
 

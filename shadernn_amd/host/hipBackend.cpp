@@ -58,6 +58,10 @@ HipBackend::~HipBackend() {
     if (frameOutPlan) snnhip_plan_destroy(frameOutPlan);
     if (frameInT) snnhip_tensor_free(frameInT);
     if (frameOutT) snnhip_tensor_free(frameOutT);
+    if (lumaPlan) snnhip_plan_destroy(lumaPlan);
+    if (mergePlan) snnhip_plan_destroy(mergePlan);
+    if (colourInT) snnhip_tensor_free(colourInT);
+    if (colourOutT) snnhip_tensor_free(colourOutT);
 }
 
 void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
@@ -83,12 +87,41 @@ void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC
     }
 }
 
+void HipBackend::initColourIO(int channels, float kr, float kb) {
+    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == SNNHIP_U8 && snnhip_tensor_dtype(frameOutT) == SNNHIP_U8);
+    int in[4], out[4];
+    hipChk(snnhip_tensor_dims(frameInT, in), "snnhip_tensor_dims");
+    hipChk(snnhip_tensor_dims(frameOutT, out), "snnhip_tensor_dims");
+    const int r = out[1] / in[1];
+    if (in[3] != 1 || out[3] != 1 || out[0] != in[0] || r < 1 || r > 4 || out[1] != r * in[1] || out[2] != r * in[2])
+        SNN_RIP("colour frames need a one-channel model whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d", in[1], in[2], in[3], out[1], out[2], out[3]);
+    snnhip_rgb_luma_desc ld{in[0], in[1], in[2], channels, kr, kb};
+    hipChk(snnhip_rgb_luma_plan_create(ctx, &ld, &lumaPlan), "snnhip_rgb_luma_plan_create");
+    snnhip_ycc_merge_desc md{in[0], in[1], in[2], channels, r, kr, kb};
+    hipChk(snnhip_ycc_merge_plan_create(ctx, &md, &mergePlan), "snnhip_ycc_merge_plan_create");
+    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1], in[2], channels, SNNHIP_U8, &colourInT), "snnhip_tensor_alloc (colour input frame)");
+    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1], out[2], channels, SNNHIP_U8, &colourOutT), "snnhip_tensor_alloc (colour output frame)");
+}
+
+std::string HipBackend::describeColour() const {
+    std::string s;
+    char buf[256];
+    if (lumaPlan && snnhip_plan_describe(lumaPlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[colour in] ") + buf + "\n";
+    if (mergePlan && snnhip_plan_describe(mergePlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[colour out] ") + buf + "\n";
+    return s;
+}
+
 void HipBackend::runFrameIn(const ImageTexture& modelInput) {
+    if (lumaPlan) hipChk(snnhip_plan_run(lumaPlan, colourInT, frameInT), "snnhip_plan_run (colour frame -> luma)");
     if (frameInPlan && !frameInFused) hipChk(snnhip_plan_run(frameInPlan, frameInT, modelInput.tensor()), "snnhip_plan_run (frame in)");
 }
 
 void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
     if (frameOutPlan && !frameOutFused) hipChk(snnhip_plan_run(frameOutPlan, lastOutput.tensor(), frameOutT), "snnhip_plan_run (frame out)");
+    if (mergePlan) {
+        const snnhip_tensor* ins[2] = {frameOutT, colourInT};
+        hipChk(snnhip_plan_run_n(mergePlan, ins, 2, colourOutT), "snnhip_plan_run_n (luma + chroma -> colour frame)");
+    }
 }
 
 // counterpart of VulkanBackend::initRenderPasses -> VulkanRenderPass ctor (vulkanBackend.cpp:43-78, vulkanRenderpass.cpp:103-178):

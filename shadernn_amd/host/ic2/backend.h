@@ -117,13 +117,21 @@ public:
                      int outMaxval = 65535, int outShift = 0);
     void runFrameIn(const ImageTexture& modelInput);
     void runFrameOut(const ImageTexture& lastOutput);
-    snnhip_tensor* frameInput() const { return frameInT; }
-    snnhip_tensor* frameOutput() const { return frameOutT; }
+    // colour frames around a luma-only model (CreationParameters::colourChannels): called after initFrameIO with R8 frames at both ends.  The luma
+    // plan fills the model's input frame from the colour frame in runFrameIn, the merge plan builds the colour output frame from the model's output
+    // frame and the colour frame in runFrameOut: two launches more on the context's stream, in front of and behind everything else of an inference.
+    void initColourIO(int channels, float kr, float kb);
+    int colourLaunches() const { return lumaPlan ? 2 : 0; }
+    std::string describeColour() const; // one line per extra launch (empty without colour frames)
+    snnhip_tensor* frameInput() const { return colourInT ? colourInT : frameInT; }
+    snnhip_tensor* frameOutput() const { return colourOutT ? colourOutT : frameOutT; }
 
 private:
     snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned
     snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // owned, SNNHIP_U8 or SNNHIP_U16
     bool frameInFused = false, frameOutFused = false;
+    snnhip_plan *lumaPlan = nullptr, *mergePlan = nullptr;   // owned
+    snnhip_tensor *colourInT = nullptr, *colourOutT = nullptr; // owned, SNNHIP_U8 [n][H][W][C] / [n][rH][rW][C]
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

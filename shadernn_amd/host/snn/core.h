@@ -75,6 +75,10 @@ public:
         // layout.  Low-aligned 10 / 12-bit: maxval 1023 / 4095, shifts 0; P010-style high-aligned 10-bit: maxval 1023, shifts 6; full 16-bit: 65535.
         int frameInShift = 0, frameOutMaxval = 65535, frameOutShift = 0;
         bool halfTensors = false; // the model's tensors are fp16 (preferHp): the conversions read / write halfs
+        // HIP extension: colour frames around a luma-only model (snn_model_create7).  colourChannels 3 / 4 = RGB8 / RGBA8 frames at both ends of a model
+        // whose own ends are R8 frames: run() puts snnhip_rgb_luma_plan_create's launch in front of the model and snnhip_ycc_merge_plan_create's behind it
+        int colourChannels = 0;
+        float colourKr = 0.299f, colourKb = 0.114f;
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const std::string& modelFileName, const dp::ShaderGenOptions& options,

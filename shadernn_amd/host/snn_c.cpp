@@ -101,8 +101,9 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
     return snn_model_create6(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, out);
 }
 
-int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                      int prefer_half, int capture_graph, int batch, const snn_frame_io2* io, snn_model** out) {
+// snn_model_create6 / 7: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends
+static int createModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
+                       int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
     ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
     if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
@@ -133,6 +134,17 @@ int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int
         cp.captureGraph = capture_graph != 0;
         cp.outputFormat = sgo.desiredOutputFormat;
         cp.halfTensors = half;
+        if (colour) { // the model must be luma-only: one channel out, at 1..4 times the input's extent (refused here, before anything is built on the device)
+            const auto& od = cp.layers.back()->outputDesc;
+            const uint32_t r = od.width / static_cast<uint32_t>(in_w);
+            if (od.channels != 1 || r < 1 || r > 4 || od.width != r * static_cast<uint32_t>(in_w) || od.height != r * static_cast<uint32_t>(in_h)) {
+                snn_model_destroy(m);
+                return -1;
+            }
+            cp.colourChannels = colour->format & 0xff;
+            cp.colourKr = colour->kr;
+            cp.colourKb = colour->kb;
+        }
         if (io) {
             memcpy(cp.frameInMeans, io->in_means, sizeof(cp.frameInMeans));
             memcpy(cp.frameInNorms, io->in_norms, sizeof(cp.frameInNorms));
@@ -155,6 +167,27 @@ int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int
     }
     *out = m;
     return 0;
+}
+
+int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_frame_io2* io, snn_model** out) {
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, nullptr, out);
+}
+
+int snn_model_create7(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_colour_io* io, snn_model** out) {
+    if (!io || (io->format != SNN_IO_RGB8 && io->format != SNN_IO_RGBA8) || in_c != 1) return -1;
+    if (!(io->kr > 0.0f && io->kb > 0.0f && io->kr + io->kb < 1.0f)) return -1;
+    snn_frame_io2 io2{};
+    io2.in_format = io2.out_format = SNN_IO_R8;
+    for (int c = 0; c < 4; ++c) {
+        io2.in_means[c] = io->in_mean;
+        io2.in_norms[c] = io->in_norm;
+        io2.out_scale[c] = io->out_scale;
+        io2.out_offset[c] = io->out_offset;
+    }
+    io2.out_maxval = 65535;
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, io, out);
 }
 
 int snn_model_destroy(snn_model* m) {

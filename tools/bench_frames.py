@@ -33,6 +33,15 @@ the line of `python bench.py --gpus 1 --steps 20 --warmup 5` taken in the same s
 
     python tools/bench_frames.py --bits 10 --scale 3
     python tools/bench_frames.py --bits 10 --half
+
+--colour RGB8 | RGBA8 (with any --scale): colour frames around the luma chain.  Four forms in the same mirrored alternation:
+r8 (the 8-bit chain on a luma plane: two launches), colour (the luma plan, the same chain, the chroma-merge plan: four launches, on the context's
+stream in a straight line), merge (the merge launch alone) and copy (one hipMemcpyDtoDAsync that moves as many bytes through HBM as the merge
+kernel has to: half of them read, half written).  Device step per form with the spread over the rounds, frames/s including one frame's H2D + D2H
+for r8 and colour, the kernels of the launch trace, and the merge kernel's bytes/s beside the copy's.  profiles/espcn_colour_frames.json holds the
+runs at --scale 2 and --scale 3 under the keys scale<r>.
+
+    python tools/bench_frames.py --colour RGB8 --scale 3
 """
 import argparse
 import json
@@ -173,11 +182,138 @@ def main_half(a):
     ctx.close()
 
 
+def _hip_runtime():
+    """the HIP runtime this process already has mapped (torch's), for the one call the C-ABI does not wrap: hipMemcpyDtoDAsync"""
+    import ctypes
+
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64" in line:
+                return ctypes.CDLL(line.split()[-1])
+    raise RuntimeError("no HIP runtime is mapped into this process")
+
+
+def main_colour(a):
+    """--colour: r8 / colour / merge / copy."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R, Cc = a.scale, {"RGB8": 3, "RGBA8": 4}[a.colour]
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    rgb = np.random.default_rng(1).integers(0, 256, size=(1, H, W, Cc), dtype=np.uint8)
+    luma_h = np.random.default_rng(2).integers(0, 256, size=(1, H, W, 1), dtype=np.uint8)
+    layers, shape = [], (1, H, W, 1)
+    for layer in net["layers"]:
+        p = _layer_plan(ctx, layer, shape)
+        layers.append(p)
+        shape = p.out_shape()
+    uin = capi.u8_in_plan(ctx, 1, H, W, 1, (127.5, 0, 0, 0), (1 / 127.5, 1, 1, 1))
+    uout = capi.u8_out_plan(ctx, *shape, (127.5, 0, 0, 0), (127.5, 0, 0, 0))
+    chain = capi.chain_plan(ctx, [uin] + layers + [uout])
+    assert chain.num_steps() == 2, chain.describe()
+    luma, merge = capi.rgb_luma_plan(ctx, 1, H, W, Cc), capi.ycc_merge_plan(ctx, 1, H, W, Cc, R)
+    oshape = (1, R * H, R * W, Cc)
+    t_rgb = capi.Tensor.from_numpy(ctx, rgb, dtype=capi.U8)
+    t_luma = capi.Tensor.from_numpy(ctx, luma_h, dtype=capi.U8)
+    t_yhi = capi.Tensor(ctx, *shape, dtype=capi.U8)
+    t_out = capi.Tensor(ctx, *oshape, dtype=capi.U8)
+    merge_bytes = int(merge.cost()[1])
+    half = merge_bytes // 2
+    t_src, t_dst = capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8)
+    t_src.upload_u8(np.random.default_rng(3).integers(0, 256, size=half, dtype=np.uint8))
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+
+    def run_r8():
+        chain.run(t_luma, t_yhi)
+
+    def run_colour():
+        luma.run(t_rgb, t_luma)
+        chain.run(t_luma, t_yhi)
+        merge.run([t_yhi, t_rgb], t_out)
+
+    def run_merge():
+        merge.run([t_yhi, t_rgb], t_out)
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(t_dst.data_ptr(), t_src.data_ptr(), half, stream)
+        assert rc == 0, rc
+
+    forms = {"r8": run_r8, "colour": run_colour, "merge": run_merge, "copy": run_copy}
+    yhi_h, out_h = np.empty(shape, np.uint8), np.empty(oshape, np.uint8)
+    io = {"r8": (t_luma, luma_h, t_yhi, yhi_h), "colour": (t_rgb, rgb, t_out, out_h)}
+    for f in forms.values():
+        for _ in range(a.warmup):
+            f()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {k: [] for k in forms}
+    e2e = {k: [] for k in io}
+    order = list(forms) + list(forms)[::-1]  # mirrored: A B C D D C B A
+    for _ in range(a.rounds):
+        for k in order:
+            timer.start()
+            for _ in range(a.iters):
+                forms[k]()
+            timer.stop()
+            dev[k].append(timer.elapsed_ms() / a.iters)
+    for _ in range(a.rounds):
+        for k in list(io) + list(io)[::-1]:
+            x, xh, y, yh = io[k]
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                capi.check(capi.lib().snnhip_tensor_upload_raw(x.h, xh.ctypes.data_as(capi._P), xh.nbytes))
+                forms[k]()
+                capi.check(capi.lib().snnhip_tensor_download_raw(y.h, yh.ctypes.data_as(capi._P), yh.nbytes))
+            e2e[k].append((time.perf_counter() - t0) * 1e3 / a.iters)
+    out = {"frame": "%dx%d -> %dx%d" % (H, W, R * H, R * W), "scale": R, "colour": a.colour, "rounds": a.rounds, "iters": a.iters}
+    for k in forms:
+        d = statistics.median(dev[k])
+        out[k] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[k]), 4), "device_ms_max": round(max(dev[k]), 4),
+                  "device_spread": round((max(dev[k]) - min(dev[k])) / d, 4)}
+        if k in io:
+            e = statistics.median(e2e[k])
+            out[k].update({"e2e_ms_median": round(e, 4), "e2e_frames_per_s": round(1e3 / e, 1), "io_bytes_per_frame": int(io[k][1].nbytes + io[k][3].nbytes)})
+    out["r8"]["steps"] = [chain.step_describe(i) for i in range(2)]
+    out["colour"]["steps"] = [luma.describe()] + out["r8"]["steps"] + [merge.describe()]
+    for k in ("r8", "colour", "merge"):  # the launch trace: per-kernel times of each form (a copy is no kernel of the library)
+        capi.trace_begin()
+        for _ in range(a.iters):
+            forms[k]()
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        out[k]["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                              "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+    out["device_colour_over_r8"] = round(out["colour"]["device_ms_median"] / out["r8"]["device_ms_median"], 4)
+    out["e2e_fps_colour_over_r8"] = round(out["colour"]["e2e_frames_per_s"] / out["r8"]["e2e_frames_per_s"], 4)
+    traced = [it for it in out["merge"]["kernels"] if it["function"] and "ycc_merge" in it["function"]]
+    merge_us = traced[0]["us_per_launch"] if traced else 1e3 * out["merge"]["device_ms_median"]
+    copy_us = 1e3 * out["copy"]["device_ms_median"]
+    out["merge_vs_copy"] = {"merge_hbm_bytes": merge_bytes, "merge_us_per_launch_traced": merge_us, "merge_tbs": round(merge_bytes / (merge_us * 1e-6) / 1e12, 3),
+                            "merge_tbs_event_timed_loop": round(merge_bytes / (out["merge"]["device_ms_median"] * 1e-3) / 1e12, 3),
+                            "copy_bytes_each_way": half, "copy_hbm_bytes": 2 * half, "copy_us": round(copy_us, 2),
+                            "copy_tbs": round(2 * half / (copy_us * 1e-6) / 1e12, 3)}
+    out["merge_vs_copy"]["merge_over_copy_rate"] = round(out["merge_vs_copy"]["merge_tbs_event_timed_loop"] / out["merge_vs_copy"]["copy_tbs"], 4)
+    print(json.dumps(out, indent=1))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
     ap.add_argument("--scale", type=int, default=2, choices=[2, 3, 4], help="upscale factor; the input size follows it (output 3840 x 2160) unless --h / --w are given")
     ap.add_argument("--bits", type=int, default=0, choices=[0, 10, 12, 16], help="also time 16-bit frames of this bit depth, folded and as separate launches")
+    ap.add_argument("--colour", choices=["RGB8", "RGBA8"], default=None, help="colour frames around the luma chain: r8, colour, the merge launch alone and a device copy of its bytes")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
     ap.add_argument("--h", type=int, default=0)
     ap.add_argument("--w", type=int, default=0)
@@ -187,6 +323,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.colour:
+        return main_colour(a)
     if a.half:
         return main_half(a)
 
