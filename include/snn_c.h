@@ -89,6 +89,34 @@ typedef struct snn_colour_io {
 } snn_colour_io;
 int snn_model_create7(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, const snn_colour_io* io, snn_model** out);
+/* Video frames around a luma-only model: NV12 (8-bit) or P010-style (2-byte containers) frames at BOTH ends, as a hardware decoder hands them out
+ * -- a full-resolution luma plane followed by a half-resolution plane of interleaved CbCr.  Through a struct and an entry point of their own: every
+ * earlier struct and entry point keeps its layout and behaviour.  The model is built exactly as snn_model_create5 builds it with SNN_IO_R8 at both
+ * ends (SNN_IO_NV12), or as snn_model_create6 builds it with SNN_IO_R16, in_shift = out_shift = shift and out_maxval = maxval (SNN_IO_NV12_16;
+ * P010 is maxval 1023, shift 6), so ESPCN still runs as its two fused kernels with the conversions folded in (the fp16 opt-in folds them too).
+ * in_mean / in_norm / out_scale / out_offset are the luma plane's maps: limited-range video is mean 16, norm 1/219, scale 219, offset 16 (in
+ * units of the bit depth).  The chroma plane [batch][H/2][W/2][2] goes through one more launch, behind the model's on the same stream and inside
+ * the recorded graph with capture_graph (it counts towards SNN_GRAPH_MIN_LAUNCHES): snnhip_chroma_up_plan_create with the model's r, maxval, shift
+ * and siting (SNN_SITING_LEFT: chroma co-sited with even luma columns, the default of H.264 / HEVC / AV1 streams; SNN_SITING_CENTRE: JPEG /
+ * MPEG-1); include/snnhip.h states the arithmetic.  snn_model_describe lists the launch.  Returns -1, before anything is built on the device,
+ * for a null struct, a format that is not one of the two, a model that is not one channel in and one channel out at 1..4 times the extent, an odd
+ * in_w or in_h, maxval > 4095 (or one that does not fit the container with shift), an unknown siting and batch 0.  The reference has no video
+ * frame path (core/inc/snn/color.h only names the layouts). */
+enum { SNN_IO_NV12 = 0x201, SNN_IO_NV12_16 = 0x301 }; /* (low byte = the model's channel count) */
+enum { SNN_SITING_CENTRE = 0, SNN_SITING_LEFT = 1 };
+typedef struct snn_video_io {
+    int format; /* SNN_IO_NV12 or SNN_IO_NV12_16, both ends */
+    int maxval, shift, siting;
+    float in_mean, in_norm, out_scale, out_offset; /* the luma plane's maps */
+} snn_video_io;
+int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_video_io* io, snn_model** out);
+/* `batch` frames, each H*W luma elements followed by (H/2)*W interleaved chroma elements (bytes for SNN_IO_NV12, 2-byte elements for
+ * SNN_IO_NV12_16), into the model's luma frame tensor and its chroma tensor; the download returns `batch` frames of rH*rW + (rH/2)*rW elements.
+ * With batch 1 the two planes are copied straight from / to the caller's memory; a larger batch is regrouped through a host buffer (the device
+ * tensors stay contiguous [N][H][W][C]).  -1 when the model was not made by snn_model_create8. */
+int snn_model_upload_frame_nv12(snn_model* m, const void* frames);
+int snn_model_download_frame_nv12(snn_model* m, void* frames);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

@@ -416,6 +416,40 @@ typedef struct { int N, H, W, C; int r; float kr, kb; } snnhip_ycc_merge_desc; /
 int snnhip_ycc_merge_plan_create(snnhip_ctx* ctx, const snnhip_ycc_merge_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_n, 2 inputs */
 /* host only, no context (like snnhip_espcn_f16_pack_weights): the [r][4] fp32 tap table the merge kernel uses, r = 1..4, capacity >= 4*r floats */
 int snnhip_bicubic_taps(int r, float* out, int capacity);
+
+/* The chroma plane of a 4:2:0 video frame upsampled beside a luma-only model (NV12 / P010 from a hardware decoder: a full-resolution luma plane,
+ * which the 8 / 16-bit frame ends above already take, and a half-resolution chroma plane, which this plan takes).  DESIGN.md section 4.14.
+ * The contract, stated once:
+ *   Shapes: the input is a chroma plane [N][H][W][C] -- C = 2: interleaved CbCr (NV12 / P010), C = 1: one plane of a planar format (I420,
+ *     yuv420p10le) -- of dtype SNNHIP_U8 or SNNHIP_U16; H, W are the CHROMA plane's extent.  The output is [N][r*H][r*W][C] of the same dtype,
+ *     r = 1..4.  Channels never mix.
+ *   Value: v = float(u >> shift) (shift = 0 for SNNHIP_U8).  The filter is ycc_merge's: the Keys cubic with a = -0.5, separable, horizontal then
+ *     vertical, indices clamped to the plane (replicate edge), fp32 weights computed on the host in double and rounded to float, fp32
+ *     accumulation.  q = unsigned(clamp(rint(.), 0, maxval)) << shift, ties to even.  At r = 1 the output is the input with the bits below
+ *     `shift` cleared (for values up to maxval).
+ *   Siting: output sample r*x + p reads source position x + s.  The vertical axis always uses aligned sample centres, s = (p + 0.5) / r - 0.5
+ *     (scaling a 4:2:0 plane by an integer about aligned centres keeps vertically centred chroma centred).  The horizontal axis follows `siting`:
+ *     SNNHIP_SITING_CENTRE is the same phase (JPEG / MPEG-1 siting); SNNHIP_SITING_LEFT is chroma co-sited with the even luma columns (the
+ *     default of H.264 / HEVC / AV1 streams, hence of NV12 / P010 from decoders), s = (p + 0.25) / r - 0.25: chroma sample i sits at luma column
+ *     2i, output chroma sample j at output luma column 2j = low-resolution luma column (2j + 0.5) / r - 0.5, which halved is chroma index
+ *     j / r + 0.25 / r - 0.25.  Taps are floor(s) - 1 .. floor(s) + 2 relative to x; floor(s) (the phase's base, -1 or 0) travels with the
+ *     weights; the reach is x - 2 .. x + 2.
+ *   Bit depth: maxval is at most 255 for SNNHIP_U8 and at most 4095 for SNNHIP_U16 (10-bit: 1023, 12-bit: 4095); shift is 0, or 16 - bits for the
+ *     high-aligned containers (P010: maxval 1023, shift 6); maxval << shift must fit the container.  maxval > 4095 is refused: on full 16-bit values
+ *     the fp32 filter is 1.5e-2 away from its float64 value, too far for a rounding contract (P016 chroma is not built).
+ * Plan creation returns SNNHIP_E_INVALID with a message for C outside {1, 2}, r outside 1..4, a dtype that is neither SNNHIP_U8 nor SNNHIP_U16, a
+ * maxval / shift that does not fit the container and an unknown siting; snnhip_plan_run for a tensor of another dtype at either end and an output
+ * that is not r times the input.  snnhip_plan_describe: "chroma_up_u8 r=2 c=2 siting=left tile=8x256 ...".  snnhip_plan_cost counts the input once
+ * and the output once.  The reference has nothing for this: core/inc/snn/color.h only enumerates YUV layouts, and the libyuv it vendors scales planes
+ * on the CPU with box / bilinear filters. */
+#define SNNHIP_SITING_CENTRE 0
+#define SNNHIP_SITING_LEFT 1
+typedef struct { int N, H, W, C; int r; int dtype; int maxval, shift; int siting; } snnhip_chroma_up_desc; /* H, W: the chroma plane */
+int snnhip_chroma_up_plan_create(snnhip_ctx* ctx, const snnhip_chroma_up_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run */
+/* host only, no context: the tap table of the horizontal axis (and, with SNNHIP_SITING_CENTRE, of the vertical one): weights [r][4] (capacity >= 4*r
+ * floats) and base [r] ints; phase p reads x + base[p] - 1 .. x + base[p] + 2.  With SNNHIP_SITING_CENTRE the weights are snnhip_bicubic_taps' and
+ * base is its phase start.  The reference has no counterpart (its libyuv scalers are bilinear / box). */
+int snnhip_bicubic_taps_sited(int r, int siting, float* weights, int* base, int capacity);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

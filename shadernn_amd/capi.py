@@ -103,6 +103,11 @@ class YccMergeDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("r", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
 
 
+class ChromaUpDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("r", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int),
+                ("siting", C.c_int)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -180,6 +185,8 @@ SIGNATURES = {
     "snnhip_rgb_luma_plan_create": (C.c_int, [_P, C.POINTER(RgbLumaDesc), C.POINTER(_P)]),
     "snnhip_ycc_merge_plan_create": (C.c_int, [_P, C.POINTER(YccMergeDesc), C.POINTER(_P)]),
     "snnhip_bicubic_taps": (C.c_int, [C.c_int, _FP, C.c_int]),
+    "snnhip_chroma_up_plan_create": (C.c_int, [_P, C.POINTER(ChromaUpDesc), C.POINTER(_P)]),
+    "snnhip_bicubic_taps_sited": (C.c_int, [C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -728,6 +735,28 @@ def bicubic_taps(r):
     out = np.zeros((r, 4), np.float32)
     check(lib().snnhip_bicubic_taps(r, _fptr(out), out.size))
     return out
+
+
+SITING = {"centre": 0, "left": 1}  # SNNHIP_SITING_*
+
+
+def chroma_up_plan(ctx, N, H, W, Cc, r, dtype=U8, maxval=None, shift=0, siting="left"):
+    """dtype (U8 / U16) [N][H][W][Cc] -> [N][r*H][r*W][Cc]: a chroma plane (Cc = 2 interleaved CbCr, 1 one planar plane; H, W its own extent)
+    upsampled with the sited Catmull-Rom filter of include/snnhip.h; maxval defaults to 255 for U8 (a 16-bit plane must say: 1023 or 4095)."""
+    if maxval is None:
+        maxval = 255
+    d = ChromaUpDesc(N, H, W, Cc, r, dtype, maxval, shift, SITING.get(siting, siting))
+    h = _P()
+    check(lib().snnhip_chroma_up_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def bicubic_taps_sited(r, siting="left"):
+    """snnhip_bicubic_taps_sited (host side only, no GPU): (weights float32 [r][4], base int32 [r]); phase p reads x + base[p] - 1 .. x + base[p] + 2."""
+    w = np.zeros((max(r, 0), 4), np.float32)
+    base = (C.c_int * max(r, 1))()
+    check(lib().snnhip_bicubic_taps_sited(r, SITING.get(siting, siting), _fptr(w), base, w.size))
+    return w, np.array(base[:max(r, 0)], np.int32)
 
 
 def deconv2d_plan(ctx, N, H, W, w_oihw, bias=None, stride=2, same=True, act="", leaky=0.0, bn=None):

@@ -20,6 +20,9 @@ SIGNATURES = {
     "snn_model_create5": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create6": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create7": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create8": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_upload_frame_nv12": (C.c_int, [_P, _P]),
+    "snn_model_download_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u16": (C.c_int, [_P, _P]),
     "snn_model_download_frame_u16": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u8": (C.c_int, [_P, _P]),
@@ -145,6 +148,14 @@ class ColourIO(C.Structure):
                 ("out_offset", C.c_float)]
 
 
+class VideoIO(C.Structure):
+    """snn_video_io (include/snn_c.h): NV12 / P010 frames around a luma-only model, the chroma plane's depth and siting and the luma plane's maps."""
+    _fields_ = [("format", C.c_int), ("maxval", C.c_int), ("shift", C.c_int), ("siting", C.c_int), ("in_mean", C.c_float), ("in_norm", C.c_float),
+                ("out_scale", C.c_float), ("out_offset", C.c_float)]
+
+
+VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6)}  # name: (SNN_IO_NV12 / SNN_IO_NV12_16, maxval, shift)
+SITINGS = {"centre": 0, "left": 1}  # SNN_SITING_*
 FRAME_FORMATS = {None: 0, "float": 0, "R8": 1, "RGB8": 3, "RGBA8": 4, "R16": 0x101, "RGB16": 0x103, "RGBA16": 0x104}  # SNN_IO_*
 
 
@@ -153,7 +164,8 @@ class Model:
 
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
-                 out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114):
+                 out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114, video=None,
+                 siting="left", video_maxval=None, video_shift=None):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
         output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
@@ -161,9 +173,28 @@ class Model:
         clamp(rint(x * out_scale[c] + out_offset[c]), 0, frame_out_maxval) << frame_out_shift out (10-bit: maxval 1023; P010-style: shifts 6).
         colour "RGB8" / "RGBA8" (snn_model_create7): colour frames around a luma-only model (c == 1, e.g. ESPCN) -- upload_frame takes uint8
         [batch x] H x W x C, output_frame returns [batch x] rH x rW x C: the model runs on the frame's luma plane (coefficients kr, kb; BT.601 by
-        default) with R8 frames at its own ends (in_means[0] / in_norms[0] / out_scale[0] / out_offset[0]), the chroma is upsampled bicubically."""
+        default) with R8 frames at its own ends (in_means[0] / in_norms[0] / out_scale[0] / out_offset[0]), the chroma is upsampled bicubically.
+        video "NV12" / "P010" (snn_model_create8): a decoder's 4:2:0 frames around a luma-only model -- upload_frame takes a pair (y, cbcr) of uint8
+        (uint16 for P010) arrays [batch x] H x W and [batch x] H/2 x W/2 x 2, output_frame / download_frame return the pair at r times the extent;
+        the luma plane runs through the model with R8 / R16 frames at its ends, the chroma plane through one more launch (siting "left": co-sited
+        with even luma columns, the default of H.264 / HEVC / AV1; "centre": JPEG / MPEG-1).  video_maxval / video_shift override the format's depth
+        (P010: 1023, 6; low-aligned 12-bit would be 4095, 0)."""
         self.h = _P()
         self.colour_channels = 0
+        self.video = video
+        if video is not None:
+            assert input_format is None and output_format is None and colour is None, "video frames replace input_format / output_format / colour"
+            fmt, maxval, shift = VIDEO_FORMATS[video]
+            maxval = maxval if video_maxval is None else video_maxval
+            shift = shift if video_shift is None else video_shift
+            dt = np.uint8 if fmt == 0x201 else np.uint16
+            self.frame_dtypes = (dt, dt)
+            io = VideoIO(fmt, maxval, shift, SITINGS[siting], in_means[0], in_norms[0], out_scale[0], out_offset[0])
+            assert lib().snn_model_create8(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                           int(batch), C.byref(io), C.byref(self.h)) == 0
+            self.batch = batch
+            self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
+            return
         if colour is not None:
             assert input_format is None and output_format is None, "colour frames replace input_format / output_format"
             self.colour_channels = {"RGB8": 3, "RGBA8": 4}[colour]
@@ -190,6 +221,8 @@ class Model:
 
     def upload_frame(self, img):
         """uint8 (uint16 for a 16-bit input format) [batch x] H x W x C into the model's input frame (no per-call allocation)."""
+        if self.video:
+            return self._upload_video(*img)
         img = np.ascontiguousarray(img, dtype=self.frame_dtypes[0]).reshape(self.in_shape)
         up = lib().snn_model_upload_frame_u16 if self.frame_dtypes[0] == np.uint16 else lib().snn_model_upload_frame_u8
         assert up(self.h, img.ctypes.data_as(_P)) == 0
@@ -198,12 +231,33 @@ class Model:
         """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
+        if self.video:
+            return self._download_video(d[0], d[1])
         if self.colour_channels:
             d = (d[0], d[1], self.colour_channels)
         out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=self.frame_dtypes[1])
         down = lib().snn_model_download_frame_u16 if self.frame_dtypes[1] == np.uint16 else lib().snn_model_download_frame_u8
         assert down(self.h, out.ctypes.data_as(_P)) == 0
         return out
+
+    download_frame = output_frame
+
+    def _upload_video(self, y, cbcr):
+        """(y, cbcr) -> `batch` frames, each the luma plane followed by the interleaved chroma plane, the layout snn_model_upload_frame_nv12 takes"""
+        dt, n = self.frame_dtypes[0], self.batch
+        h, w = self.in_shape[-3], self.in_shape[-2]
+        y = np.ascontiguousarray(y, dtype=dt).reshape(n, h * w)
+        cbcr = np.ascontiguousarray(cbcr, dtype=dt).reshape(n, (h // 2) * w)
+        frames = np.ascontiguousarray(np.concatenate([y, cbcr], axis=1))
+        assert lib().snn_model_upload_frame_nv12(self.h, frames.ctypes.data_as(_P)) == 0
+
+    def _download_video(self, oh, ow):
+        dt, n = self.frame_dtypes[1], self.batch
+        frames = np.empty((n, oh * ow + (oh // 2) * ow), dtype=dt)
+        assert lib().snn_model_download_frame_nv12(self.h, frames.ctypes.data_as(_P)) == 0
+        y = frames[:, :oh * ow].reshape(n, oh, ow)
+        cbcr = frames[:, oh * ow:].reshape(n, oh // 2, ow // 2, 2)
+        return (y[0].copy(), cbcr[0].copy()) if n == 1 else (y.copy(), cbcr.copy())
 
     def upload(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.in_shape)

@@ -108,6 +108,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
                         cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset, frameIn && isFrame16Format(id.format),
                         frameOut && isFrame16Format(cp.outputFormat), cp.frameInShift, cp.frameOutMaxval, cp.frameOutShift);
         if (cp.colourChannels) hb->initColourIO(cp.colourChannels, cp.colourKr, cp.colourKb);
+        if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting);
         frameBackend = hb;
     }
     backend->finalizeStages(stages, cp.dumpOutputs, cp.fuseChains);
@@ -118,7 +119,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         // A recorded graph pays off when an inference is MANY launches (ResNet-18 23, MobileNetV2 41, Candy 88 after fusion).  For a handful it costs:
         // consecutive hipGraphLaunch calls leave ~5 us between graphs on the stream where plain kernel launches queue back to back (measured on the
         // fused ESPCN, 2 launches of 86 + 34 us: 125.0 us per inference replayed, 120 launched directly) -- below the threshold run() just launches.
-        int launches = frameBackend ? frameBackend->colourLaunches() : 0;
+        int launches = frameBackend ? frameBackend->colourLaunches() + frameBackend->videoLaunches() : 0;
         for (auto& s : stages) {
             auto* ml = static_cast<dp::GenericModelLayer*>(s.layer->modelLayer);
             if (!ml || s.layer->isInputLayer) continue;
@@ -134,6 +135,8 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
 
 snnhip_tensor* MixedInferenceCore::frameInput() const { return frameBackend ? frameBackend->frameInput() : nullptr; }
 snnhip_tensor* MixedInferenceCore::frameOutput() const { return frameBackend ? frameBackend->frameOutput() : nullptr; }
+snnhip_tensor* MixedInferenceCore::chromaInput() const { return frameBackend ? frameBackend->chromaInput() : nullptr; }
+snnhip_tensor* MixedInferenceCore::chromaOutput() const { return frameBackend ? frameBackend->chromaOutput() : nullptr; }
 
 void MixedInferenceCore::run(RunParameters& rp) { // core.cpp:97-245
     SNN_ASSERT(rp.inputImages && rp.inputImages->size() > 0);
@@ -266,7 +269,7 @@ std::string MixedInferenceCore::describe() const {
         if (stages[i].fusedAway) ss << "  (fused into a later stage's plan)";
         ss << "\n";
     }
-    if (frameBackend) ss << frameBackend->describeColour();
+    if (frameBackend) ss << frameBackend->describeColour() << frameBackend->describeVideo();
     return ss.str();
 }
 

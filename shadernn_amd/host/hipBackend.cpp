@@ -62,6 +62,9 @@ HipBackend::~HipBackend() {
     if (mergePlan) snnhip_plan_destroy(mergePlan);
     if (colourInT) snnhip_tensor_free(colourInT);
     if (colourOutT) snnhip_tensor_free(colourOutT);
+    if (chromaPlan) snnhip_plan_destroy(chromaPlan);
+    if (chromaInT) snnhip_tensor_free(chromaInT);
+    if (chromaOutT) snnhip_tensor_free(chromaOutT);
 }
 
 void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
@@ -111,6 +114,27 @@ std::string HipBackend::describeColour() const {
     return s;
 }
 
+void HipBackend::initVideoIO(int dtype, int maxval, int shift, int siting) {
+    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
+    int in[4], out[4];
+    hipChk(snnhip_tensor_dims(frameInT, in), "snnhip_tensor_dims");
+    hipChk(snnhip_tensor_dims(frameOutT, out), "snnhip_tensor_dims");
+    const int r = out[1] / in[1];
+    if (in[3] != 1 || out[3] != 1 || out[0] != in[0] || r < 1 || r > 4 || out[1] != r * in[1] || out[2] != r * in[2] || in[1] % 2 || in[2] % 2)
+        SNN_RIP("video frames need a one-channel model of even extent whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d", in[1], in[2], in[3], out[1], out[2],
+                out[3]);
+    snnhip_chroma_up_desc cd{in[0], in[1] / 2, in[2] / 2, 2, r, dtype, maxval, shift, siting};
+    hipChk(snnhip_chroma_up_plan_create(ctx, &cd, &chromaPlan), "snnhip_chroma_up_plan_create");
+    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
+    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1] / 2, out[2] / 2, 2, dtype, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
+}
+
+std::string HipBackend::describeVideo() const {
+    char buf[256];
+    if (chromaPlan && snnhip_plan_describe(chromaPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
+    return std::string();
+}
+
 void HipBackend::runFrameIn(const ImageTexture& modelInput) {
     if (lumaPlan) hipChk(snnhip_plan_run(lumaPlan, colourInT, frameInT), "snnhip_plan_run (colour frame -> luma)");
     if (frameInPlan && !frameInFused) hipChk(snnhip_plan_run(frameInPlan, frameInT, modelInput.tensor()), "snnhip_plan_run (frame in)");
@@ -122,6 +146,7 @@ void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
         const snnhip_tensor* ins[2] = {frameOutT, colourInT};
         hipChk(snnhip_plan_run_n(mergePlan, ins, 2, colourOutT), "snnhip_plan_run_n (luma + chroma -> colour frame)");
     }
+    if (chromaPlan) hipChk(snnhip_plan_run(chromaPlan, chromaInT, chromaOutT), "snnhip_plan_run (chroma plane)");
 }
 
 // counterpart of VulkanBackend::initRenderPasses -> VulkanRenderPass ctor (vulkanBackend.cpp:43-78, vulkanRenderpass.cpp:103-178):

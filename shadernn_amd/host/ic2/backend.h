@@ -123,6 +123,14 @@ public:
     void initColourIO(int channels, float kr, float kb);
     int colourLaunches() const { return lumaPlan ? 2 : 0; }
     std::string describeColour() const; // one line per extra launch (empty without colour frames)
+    // NV12 / P010 video frames around a luma-only model (CreationParameters::videoDtype): called after initFrameIO with R8 / R16 frames at both
+    // ends.  The luma plane IS the model's frame; the chroma plan upsamples the CbCr plane [n][H/2][W/2][2] to [n][rH/2][rW/2][2] in runFrameOut,
+    // one launch more on the context's stream behind everything else of an inference (a straight line: no side stream, no parallel graph branch).
+    void initVideoIO(int dtype, int maxval, int shift, int siting);
+    int videoLaunches() const { return chromaPlan ? 1 : 0; }
+    std::string describeVideo() const; // one line for the extra launch (empty without video frames)
+    snnhip_tensor* chromaInput() const { return chromaInT; }
+    snnhip_tensor* chromaOutput() const { return chromaOutT; }
     snnhip_tensor* frameInput() const { return colourInT ? colourInT : frameInT; }
     snnhip_tensor* frameOutput() const { return colourOutT ? colourOutT : frameOutT; }
 
@@ -132,6 +140,8 @@ private:
     bool frameInFused = false, frameOutFused = false;
     snnhip_plan *lumaPlan = nullptr, *mergePlan = nullptr;   // owned
     snnhip_tensor *colourInT = nullptr, *colourOutT = nullptr; // owned, SNNHIP_U8 [n][H][W][C] / [n][rH][rW][C]
+    snnhip_plan* chromaPlan = nullptr;                          // owned
+    snnhip_tensor *chromaInT = nullptr, *chromaOutT = nullptr;  // owned, SNNHIP_U8 / SNNHIP_U16 [n][H/2][W/2][2] / [n][rH/2][rW/2][2]
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

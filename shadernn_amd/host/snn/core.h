@@ -79,6 +79,9 @@ public:
         // whose own ends are R8 frames: run() puts snnhip_rgb_luma_plan_create's launch in front of the model and snnhip_ycc_merge_plan_create's behind it
         int colourChannels = 0;
         float colourKr = 0.299f, colourKb = 0.114f;
+        // HIP extension: NV12 / P010 video frames around a luma-only model (snn_model_create8).  videoDtype SNNHIP_U8 / SNNHIP_U16 (0 = none): the
+        // model's own ends are R8 / R16 frames; run() puts snnhip_chroma_up_plan_create's launch on the half-resolution CbCr plane behind the model
+        int videoDtype = 0, videoMaxval = 255, videoShift = 0, videoSiting = 1;
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const std::string& modelFileName, const dp::ShaderGenOptions& options,
@@ -92,6 +95,8 @@ public:
     // HIP extension: the model's input / output frame tensors (SNNHIP_U8 or SNNHIP_U16 [batch][H][W][C]; null without frame I/O at that end)
     snnhip_tensor* frameInput() const;
     snnhip_tensor* frameOutput() const;
+    snnhip_tensor* chromaInput() const; // the CbCr planes of a video model (snn_model_create8), null otherwise
+    snnhip_tensor* chromaOutput() const;
 
 private:
     GpuContext* context;

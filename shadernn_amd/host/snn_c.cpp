@@ -1,5 +1,6 @@
 // snn_c.cpp -- C binding of the host mirror for tests / harnesses (see include/snn_c.h).
 #include <cstring>
+#include <vector>
 
 #include "../../include/snn_c.h"
 #include "../../include/snnhip.h"
@@ -101,9 +102,10 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
     return snn_model_create6(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, out);
 }
 
-// snn_model_create6 / 7: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends
+// snn_model_create6 / 7 / 8: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends, `video`
+// (snn_model_create8) for NV12 / P010 frames around a model that `io` gives R8 / R16 frames
 static int createModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                       int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out) {
+                       int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out, const snn_video_io* video = nullptr) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
     ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
     if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
@@ -134,16 +136,23 @@ static int createModel(const char* json_path, int device, int in_w, int in_h, in
         cp.captureGraph = capture_graph != 0;
         cp.outputFormat = sgo.desiredOutputFormat;
         cp.halfTensors = half;
-        if (colour) { // the model must be luma-only: one channel out, at 1..4 times the input's extent (refused here, before anything is built on the device)
+        if (colour || video) { // the model must be luma-only: one channel out, at 1..4 times the input's extent (refused here, before anything is built on the device)
             const auto& od = cp.layers.back()->outputDesc;
             const uint32_t r = od.width / static_cast<uint32_t>(in_w);
             if (od.channels != 1 || r < 1 || r > 4 || od.width != r * static_cast<uint32_t>(in_w) || od.height != r * static_cast<uint32_t>(in_h)) {
                 snn_model_destroy(m);
                 return -1;
             }
-            cp.colourChannels = colour->format & 0xff;
-            cp.colourKr = colour->kr;
-            cp.colourKb = colour->kb;
+            if (colour) {
+                cp.colourChannels = colour->format & 0xff;
+                cp.colourKr = colour->kr;
+                cp.colourKb = colour->kb;
+            } else {
+                cp.videoDtype = video->format == SNN_IO_NV12 ? SNNHIP_U8 : SNNHIP_U16;
+                cp.videoMaxval = video->maxval;
+                cp.videoShift = video->shift;
+                cp.videoSiting = video->siting;
+            }
         }
         if (io) {
             memcpy(cp.frameInMeans, io->in_means, sizeof(cp.frameInMeans));
@@ -189,6 +198,57 @@ int snn_model_create7(const char* json_path, int device, int in_w, int in_h, int
     io2.out_maxval = 65535;
     return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, io, out);
 }
+
+int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_video_io* io, snn_model** out) {
+    if (!io || (io->format != SNN_IO_NV12 && io->format != SNN_IO_NV12_16) || in_c != 1 || batch < 1) return -1;
+    if (in_w < 2 || in_h < 2 || in_w % 2 || in_h % 2) return -1; // 4:2:0: the chroma plane is half the extent
+    const bool wide = io->format == SNN_IO_NV12_16;
+    if (io->siting != SNN_SITING_CENTRE && io->siting != SNN_SITING_LEFT) return -1;
+    if (io->maxval < 1 || io->maxval > 4095 || io->shift < 0 || io->shift > (wide ? 15 : 0)) return -1; // (P016 chroma is not built: include/snnhip.h)
+    if ((static_cast<long long>(io->maxval) << io->shift) > (wide ? 65535 : 255)) return -1;
+    snn_frame_io2 io2{};
+    io2.in_format = io2.out_format = wide ? SNN_IO_R16 : SNN_IO_R8;
+    for (int c = 0; c < 4; ++c) {
+        io2.in_means[c] = io->in_mean;
+        io2.in_norms[c] = io->in_norm;
+        io2.out_scale[c] = io->out_scale;
+        io2.out_offset[c] = io->out_offset;
+    }
+    io2.in_shift = wide ? io->shift : 0;
+    io2.out_maxval = wide ? io->maxval : 65535; // (snn_model_create5 passes 65535 for the 8-bit formats: the same model)
+    io2.out_shift = wide ? io->shift : 0;
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, io);
+}
+
+// one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame
+static int movePlane(snnhip_tensor* t, int batch, char* frames, size_t stride, size_t offset, bool upload) {
+    const size_t total = snnhip_tensor_bytes(t), plane = total / static_cast<size_t>(batch);
+    if (batch == 1) return (upload ? snnhip_tensor_upload_raw(t, frames + offset, total) : snnhip_tensor_download_raw(t, frames + offset, total)) == SNNHIP_OK ? 0 : -1;
+    std::vector<char> staging(total);
+    if (upload) {
+        for (int n = 0; n < batch; ++n) memcpy(staging.data() + n * plane, frames + n * stride + offset, plane);
+        return snnhip_tensor_upload_raw(t, staging.data(), total) == SNNHIP_OK ? 0 : -1;
+    }
+    if (snnhip_tensor_download_raw(t, staging.data(), total) != SNNHIP_OK) return -1;
+    for (int n = 0; n < batch; ++n) memcpy(frames + n * stride + offset, staging.data() + n * plane, plane);
+    return 0;
+}
+
+static int moveVideoFrames(snn_model* m, void* frames, bool upload) {
+    if (!m || !frames || !m->core) return -1;
+    snnhip_tensor* y = upload ? m->core->frameInput() : m->core->frameOutput();
+    snnhip_tensor* c = upload ? m->core->chromaInput() : m->core->chromaOutput();
+    if (!y || !c) return -1;
+    const size_t yb = snnhip_tensor_bytes(y) / static_cast<size_t>(m->batch), cb = snnhip_tensor_bytes(c) / static_cast<size_t>(m->batch);
+    char* p = static_cast<char*>(frames);
+    if (movePlane(y, m->batch, p, yb + cb, 0, upload) != 0) return -1;
+    return movePlane(c, m->batch, p, yb + cb, yb, upload);
+}
+
+int snn_model_upload_frame_nv12(snn_model* m, const void* frames) { return moveVideoFrames(m, const_cast<void*>(frames), true); }
+
+int snn_model_download_frame_nv12(snn_model* m, void* frames) { return moveVideoFrames(m, frames, false); }
 
 int snn_model_destroy(snn_model* m) {
     if (!m) return 0;
