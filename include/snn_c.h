@@ -117,6 +117,28 @@ int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int
  * tensors stay contiguous [N][H][W][C]).  -1 when the model was not made by snn_model_create8. */
 int snn_model_upload_frame_nv12(snn_model* m, const void* frames);
 int snn_model_download_frame_nv12(snn_model* m, void* frames);
+/* Video in, display out: NV12 / P010 frames at the model's INPUT, packed full-range RGB or RGBA at its output.  Through a struct and an entry point
+ * of their own: every earlier struct and entry point keeps its layout and behaviour.  The luma plane's maps follow from `range` and are not given --
+ * with k = (maxval + 1) / 256, SNN_RANGE_LIMITED: mean 16k, norm 1 / (219k), scale 219k, offset 16k; SNN_RANGE_FULL: mean 0, norm 1 / maxval, scale
+ * maxval, offset 0 -- and the model is built exactly as snn_model_create8 builds it with them, so ESPCN stays two fused kernels with folded ends
+ * (the fp16 opt-in folds them too).  One more launch sits behind the model's on the same stream and inside the recorded graph, three launches in
+ * all: snnhip_yuv_rgb_plan_create (include/snnhip.h states the arithmetic) takes the model's output luma frame and the ORIGINAL chroma plane
+ * [batch][H/2][W/2][2] and writes the RGB frame; the chroma_up launch of snn_model_create8 is not made and no upscaled chroma plane exists.
+ * snn_model_upload_frame_nv12 takes the frames; snn_model_download_frame_u8 / _u16 return [batch][rH][rW][C] (C = 3, or 4 with A = maxval << shift);
+ * snn_model_download_frame_nv12 returns -1.  snn_model_describe lists the extra launch.  Returns -1, before anything is built on the device, unless
+ * the model has one channel in and one channel out at r = 1..4 times the extent, in_w and in_h are even, the formats pair up (SNN_IO_NV12 with
+ * SNN_IO_RGB8 / RGBA8, SNN_IO_NV12_16 with SNN_IO_RGB16 / RGBA16), maxval + 1 is a multiple of 256, maxval <= 255 (8-bit) / 4095 (16-bit) and
+ * maxval << shift fits the container, siting and range are known, 0 < kr, 0 < kb, kr + kb < 1 and batch >= 1.  The reference has no video frame
+ * path (core/inc/snn/color.h only names the layouts; its vendored libyuv converts on the CPU). */
+enum { SNN_RANGE_LIMITED = 0, SNN_RANGE_FULL = 1 };
+typedef struct snn_video_rgb_io {
+    int in_format;  /* SNN_IO_NV12 or SNN_IO_NV12_16 */
+    int out_format; /* SNN_IO_RGB8 or SNN_IO_RGBA8; SNN_IO_RGB16 or SNN_IO_RGBA16 for a 16-bit input */
+    int maxval, shift, siting, range;
+    float kr, kb;
+} snn_video_rgb_io;
+int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

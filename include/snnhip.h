@@ -392,7 +392,8 @@ int snnhip_u16_out_plan_create(snnhip_ctx* ctx, const snnhip_u16_out_desc* desc,
  * split in front of the model and the chroma merge behind it, on interleaved 8-bit RGB (C = 3) or RGBA (C = 4) frames.  DESIGN.md section 4.13.
  * The arithmetic contract, stated once:
  *   Matrix: full-range Y'CbCr with coefficients kr, kb of the desc and kg = 1 - kr - kb, computed in double and rounded to float.  BT.601 is
- *     kr = 0.299, kb = 0.114 (what cv2.COLOR_BGR2YCrCb uses); BT.709 is 0.2126 / 0.0722.  Limited range is not offered.
+ *     kr = 0.299, kb = 0.114 (what cv2.COLOR_BGR2YCrCb uses); BT.709 is 0.2126 / 0.0722.  Limited range is not offered on this RGB-in path; video
+ *     sources (NV12 / P010, limited range almost always) go through snnhip_yuv_rgb_plan_create below, which takes either range.
  *   rgb_luma:   U8 [N][H][W][C] -> U8 [N][H][W][1].  ylo = kr*R + kg*G + kb*B in fp32, q = clamp(rint(ylo), 0, 255), ties to even: the U8 luma plane
  *     that snnhip_u8_in_plan_create (and chain rule A8) consumes unchanged.
  *   ycc_merge:  inputs[0] = Yhi, U8 [N][r*H][r*W][1]; inputs[1] = the original low-resolution frame, U8 [N][H][W][C]; output U8 [N][r*H][r*W][C]
@@ -450,6 +451,44 @@ int snnhip_chroma_up_plan_create(snnhip_ctx* ctx, const snnhip_chroma_up_desc* d
  * floats) and base [r] ints; phase p reads x + base[p] - 1 .. x + base[p] + 2.  With SNNHIP_SITING_CENTRE the weights are snnhip_bicubic_taps' and
  * base is its phase start.  The reference has no counterpart (its libyuv scalers are bilinear / box). */
 int snnhip_bicubic_taps_sited(int r, int siting, float* weights, int* base, int capacity);
+
+/* A 4:2:0 video frame to packed RGB behind a luma-only model: the model's upscaled luma frame and the ORIGINAL half-resolution CbCr plane in, RGB or
+ * RGBA at the output resolution out, in one launch.  No upscaled chroma plane is written to memory.  DESIGN.md section 4.15.  The contract, stated once:
+ *   Shapes: inputs[0] = Yhi [N][2rH][2rW][1], the model's output luma frame; inputs[1] = the original chroma plane [N][H][W][2], interleaved CbCr
+ *     (H, W of the desc are the CHROMA plane's extent); output [N][2rH][2rW][C], C = 3 (R, G, B) or 4 (R, G, B, A with A = maxval << shift); run with
+ *     snnhip_plan_run_n, 2 inputs.  All three have the same dtype, SNNHIP_U8 or SNNHIP_U16.  r = 1..4; r = 1 is plain NV12 -> RGB with no model in
+ *     between.  Values are float(u >> shift).
+ *   Chroma filter: the Keys cubic of ycc_merge and chroma_up (a = -0.5), separable, horizontal then vertical, indices clamped to the plane, fp32
+ *     weights computed on the host in double and rounded to float, fp32 accumulation.  The chroma grid is resampled straight to the output luma
+ *     grid, R = 2r-fold: output column X = R*x + p reads chroma position x + s, s = (p + 0.5) / R - off, off = 0.5 for SNNHIP_SITING_CENTRE and
+ *     0.25 for SNNHIP_SITING_LEFT (chroma sample i is co-sited with low-resolution luma column 2i; output luma column X sits at low-resolution
+ *     position (X + 0.5) / r - 0.5, which halved is chroma index (X + 0.5) / R - 0.25).  This is NOT chroma_up's left phase, whose output is itself
+ *     a chroma grid.  The vertical axis always uses off = 0.5, as chroma_up does.  base = floor(s) is -1 or 0 and travels with the weights; taps are
+ *     x + base - 1 .. x + base + 2, the reach x - 2 .. x + 2.  What is filtered is the sample minus Coff (an exact fp32 difference of integers), so
+ *     Cb~ - Coff and Cr~ - Coff below are the filter's results themselves.
+ *   Matrix: k = (maxval + 1) / 256.  SNNHIP_RANGE_LIMITED: Yoff = 16k, Yrange = 219k, Coff = 128k, Crange = 224k.  SNNHIP_RANGE_FULL: Yoff = 0,
+ *     Yrange = maxval, Coff = 128k, Crange = maxval.  kg = 1 - kr - kb.  Five coefficients, computed in double and rounded to float:
+ *         cy = maxval / Yrange,  crv = 2(1 - kr) maxval / Crange,  cbu = 2(1 - kb) maxval / Crange,  cgv = kr crv / kg,  cgu = kb cbu / kg
+ *     Per output pixel, in fp32:  yl = cy (Y - Yoff),  R = yl + crv (Cr~ - Coff),  B = yl + cbu (Cb~ - Coff),
+ *         G = yl - (cgv (Cr~ - Coff) + cgu (Cb~ - Coff)),  q = unsigned(clamp(rint(.), 0, maxval)) << shift, ties to even.
+ *     The output is always full-range RGB.
+ *   Consequences: neutral chroma (both samples equal to Coff) gives R = G = B = the quantised yl, byte for byte; constant chroma planes give
+ *     constant chroma terms.  In fp32 the value in front of the rounding stays within 3e-5 / 1.1e-4 / 5.2e-4 (8 / 10 / 12 bits) of a float64 evaluation.
+ * Plan creation returns SNNHIP_E_INVALID with a message for C outside {3, 4}, r outside 1..4, a dtype that is neither SNNHIP_U8 nor SNNHIP_U16,
+ * maxval above 255 (U8) or above 4095 (U16, as for chroma_up), a maxval << shift that does not fit the container, maxval + 1 not a multiple of 256,
+ * an unknown siting or range and kr, kb outside 0 < kr, 0 < kb, kr + kb < 1; snnhip_plan_run_n for a tensor of another dtype at any position and for
+ * shapes that are not 2r times the chroma plane.  snnhip_plan_describe: "yuv_rgb_u8 r=2 c=3 siting=left range=limited tile=8x128 ... kernel=
+ * yuv_rgb_kernel" (the tile in chroma pixels).  snnhip_plan_cost counts both inputs once and the output once.  The reference has nothing for this:
+ * core/inc/snn/color.h only enumerates YUV layouts, and the libyuv it vendors converts on the CPU. */
+#define SNNHIP_RANGE_LIMITED 0
+#define SNNHIP_RANGE_FULL 1
+typedef struct { int N, H, W, C; int r; int dtype; int maxval, shift; int siting; int range; float kr, kb; } snnhip_yuv_rgb_desc; /* H, W: the CHROMA plane */
+int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_n, 2 inputs */
+/* host only, no context: the tap table of the plan's horizontal axis (and, with SNNHIP_SITING_CENTRE, of its vertical one): weights [2r][4]
+ * (capacity >= 8*r floats) and base [2r] ints; phase p = X mod 2r reads x + base[p] - 1 .. x + base[p] + 2 */
+int snnhip_bicubic_taps_420(int r, int siting, float* weights, int* base, int capacity);
+/* host only, no context: out[0..6] = Yoff, Coff, cy, crv, cbu, cgv, cgu of the matrix above (capacity >= 7 floats) */
+int snnhip_yuv_rgb_coefficients(int maxval, int range, float kr, float kb, float* out, int capacity);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

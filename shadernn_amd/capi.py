@@ -108,6 +108,11 @@ class ChromaUpDesc(C.Structure):
                 ("siting", C.c_int)]
 
 
+class YuvRgbDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("r", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int),
+                ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -187,6 +192,9 @@ SIGNATURES = {
     "snnhip_bicubic_taps": (C.c_int, [C.c_int, _FP, C.c_int]),
     "snnhip_chroma_up_plan_create": (C.c_int, [_P, C.POINTER(ChromaUpDesc), C.POINTER(_P)]),
     "snnhip_bicubic_taps_sited": (C.c_int, [C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
+    "snnhip_yuv_rgb_plan_create": (C.c_int, [_P, C.POINTER(YuvRgbDesc), C.POINTER(_P)]),
+    "snnhip_bicubic_taps_420": (C.c_int, [C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
+    "snnhip_yuv_rgb_coefficients": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, _FP, C.c_int]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -757,6 +765,37 @@ def bicubic_taps_sited(r, siting="left"):
     base = (C.c_int * max(r, 1))()
     check(lib().snnhip_bicubic_taps_sited(r, SITING.get(siting, siting), _fptr(w), base, w.size))
     return w, np.array(base[:max(r, 0)], np.int32)
+
+
+RANGE = {"limited": 0, "full": 1}  # SNNHIP_RANGE_*
+
+
+def yuv_rgb_plan(ctx, N, H, W, Cc, r, dtype=U8, maxval=None, shift=0, siting="left", range="limited", kr=BT601[0], kb=BT601[1]):
+    """plan.run([Yhi [N][2r*H][2r*W][1], CbCr [N][H][W][2]], out [N][2r*H][2r*W][Cc]), all of dtype U8 / U16: a 4:2:0 frame to RGB (Cc = 3) or RGBA
+    (Cc = 4) in one launch (include/snnhip.h states the arithmetic).  H, W are the CHROMA plane's; maxval defaults to 255 (a 16-bit frame must say)."""
+    if maxval is None:
+        maxval = 255
+    d = YuvRgbDesc(N, H, W, Cc, r, dtype, maxval, shift, SITING.get(siting, siting), RANGE.get(range, range), kr, kb)
+    h = _P()
+    check(lib().snnhip_yuv_rgb_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def bicubic_taps_420(r, siting="left", capacity=None):
+    """snnhip_bicubic_taps_420 (host side only, no GPU): (weights float32 [2r][4], base int32 [2r]) of a chroma plane resampled to the output luma
+    grid; phase p = X mod 2r reads x + base[p] - 1 .. x + base[p] + 2."""
+    n = 2 * max(r, 0)
+    w = np.zeros((n, 4), np.float32)
+    base = (C.c_int * max(n, 1))()
+    check(lib().snnhip_bicubic_taps_420(r, SITING.get(siting, siting), _fptr(w), base, w.size if capacity is None else capacity))
+    return w, np.array(base[:n], np.int32)
+
+
+def yuv_rgb_coefficients(maxval=255, range="limited", kr=BT601[0], kb=BT601[1]):
+    """snnhip_yuv_rgb_coefficients (host side only, no GPU): float32 (Yoff, Coff, cy, crv, cbu, cgv, cgu) of the Y'CbCr -> RGB matrix."""
+    out = np.zeros(7, np.float32)
+    check(lib().snnhip_yuv_rgb_coefficients(maxval, RANGE.get(range, range), kr, kb, _fptr(out), out.size))
+    return out
 
 
 def deconv2d_plan(ctx, N, H, W, w_oihw, bias=None, stride=2, same=True, act="", leaky=0.0, bn=None):

@@ -21,6 +21,7 @@ SIGNATURES = {
     "snn_model_create6": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create7": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create8": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create9": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_upload_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_download_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u16": (C.c_int, [_P, _P]),
@@ -154,8 +155,16 @@ class VideoIO(C.Structure):
                 ("out_scale", C.c_float), ("out_offset", C.c_float)]
 
 
+class VideoRgbIO(C.Structure):
+    """snn_video_rgb_io (include/snn_c.h): NV12 / P010 frames in, RGB / RGBA frames out around a luma-only model; the luma maps follow from the range."""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("maxval", C.c_int), ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int),
+                ("kr", C.c_float), ("kb", C.c_float)]
+
+
 VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6)}  # name: (SNN_IO_NV12 / SNN_IO_NV12_16, maxval, shift)
 SITINGS = {"centre": 0, "left": 1}  # SNN_SITING_*
+VIDEO_RANGES = {"limited": 0, "full": 1}  # SNN_RANGE_*
+VIDEO_OUT_FORMATS = {"RGB8": (0x201, 3), "RGBA8": (0x201, 4), "RGB16": (0x301, 3), "RGBA16": (0x301, 4)}  # name: (the input format it pairs with, channels)
 FRAME_FORMATS = {None: 0, "float": 0, "R8": 1, "RGB8": 3, "RGBA8": 4, "R16": 0x101, "RGB16": 0x103, "RGBA16": 0x104}  # SNN_IO_*
 
 
@@ -165,7 +174,7 @@ class Model:
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
                  out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114, video=None,
-                 siting="left", video_maxval=None, video_shift=None):
+                 siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited"):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
         output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
@@ -178,10 +187,36 @@ class Model:
         (uint16 for P010) arrays [batch x] H x W and [batch x] H/2 x W/2 x 2, output_frame / download_frame return the pair at r times the extent;
         the luma plane runs through the model with R8 / R16 frames at its ends, the chroma plane through one more launch (siting "left": co-sited
         with even luma columns, the default of H.264 / HEVC / AV1; "centre": JPEG / MPEG-1).  video_maxval / video_shift override the format's depth
-        (P010: 1023, 6; low-aligned 12-bit would be 4095, 0)."""
+        (P010: 1023, 6; low-aligned 12-bit would be 4095, 0).
+        video_out "RGB8" / "RGBA8" (with "NV12") or "RGB16" / "RGBA16" (with "P010") beside video (snn_model_create9): the frames go in as above and
+        come back as packed full-range RGB -- output_frame / download_frame return uint8 / uint16 [batch x] rH x rW x C.  video_range "limited" /
+        "full" is the stream's range and sets the luma plane's maps (in_means / in_norms / out_scale / out_offset are not used); kr, kb are the
+        stream's matrix (BT.601 by default, BT.709 is 0.2126 / 0.0722).  One launch behind the model's two converts: no chroma_up launch."""
         self.h = _P()
         self.colour_channels = 0
         self.video = video
+        self.video_out_channels = 0
+        if video_out is not None:
+            assert video is not None, "video_out needs video=\"NV12\" or \"P010\""
+            assert video_out in VIDEO_OUT_FORMATS, "video_out is one of %s" % sorted(VIDEO_OUT_FORMATS)
+            assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
+            assert siting in SITINGS, "siting is \"left\" or \"centre\""
+            assert input_format is None and output_format is None and colour is None, "video frames replace input_format / output_format / colour"
+            fmt, maxval, shift = VIDEO_FORMATS[video]
+            pair, channels = VIDEO_OUT_FORMATS[video_out]
+            assert pair == fmt, "%s frames come back as %s" % (video, "RGB8 / RGBA8" if fmt == 0x201 else "RGB16 / RGBA16")
+            assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
+            maxval = maxval if video_maxval is None else video_maxval
+            shift = shift if video_shift is None else video_shift
+            dt = np.uint8 if fmt == 0x201 else np.uint16
+            self.frame_dtypes = (dt, dt)
+            io = VideoRgbIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
+            assert lib().snn_model_create9(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                           int(batch), C.byref(io), C.byref(self.h)) == 0
+            self.video_out_channels = channels
+            self.batch = batch
+            self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
+            return
         if video is not None:
             assert input_format is None and output_format is None and colour is None, "video frames replace input_format / output_format / colour"
             fmt, maxval, shift = VIDEO_FORMATS[video]
@@ -231,10 +266,10 @@ class Model:
         """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
-        if self.video:
+        if self.video and not self.video_out_channels:
             return self._download_video(d[0], d[1])
-        if self.colour_channels:
-            d = (d[0], d[1], self.colour_channels)
+        if self.colour_channels or self.video_out_channels:
+            d = (d[0], d[1], self.colour_channels or self.video_out_channels)
         out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=self.frame_dtypes[1])
         down = lib().snn_model_download_frame_u16 if self.frame_dtypes[1] == np.uint16 else lib().snn_model_download_frame_u8
         assert down(self.h, out.ctypes.data_as(_P)) == 0

@@ -108,7 +108,9 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
                         cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset, frameIn && isFrame16Format(id.format),
                         frameOut && isFrame16Format(cp.outputFormat), cp.frameInShift, cp.frameOutMaxval, cp.frameOutShift);
         if (cp.colourChannels) hb->initColourIO(cp.colourChannels, cp.colourKr, cp.colourKb);
-        if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting);
+        if (cp.videoDtype && cp.videoRgbChannels)
+            hb->initVideoRgbIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoRgbChannels, cp.videoRange, cp.videoKr, cp.videoKb);
+        else if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting);
         frameBackend = hb;
     }
     backend->finalizeStages(stages, cp.dumpOutputs, cp.fuseChains);

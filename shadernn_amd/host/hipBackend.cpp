@@ -65,6 +65,8 @@ HipBackend::~HipBackend() {
     if (chromaPlan) snnhip_plan_destroy(chromaPlan);
     if (chromaInT) snnhip_tensor_free(chromaInT);
     if (chromaOutT) snnhip_tensor_free(chromaOutT);
+    if (yuvRgbPlan) snnhip_plan_destroy(yuvRgbPlan);
+    if (rgbOutT) snnhip_tensor_free(rgbOutT);
 }
 
 void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
@@ -129,8 +131,24 @@ void HipBackend::initVideoIO(int dtype, int maxval, int shift, int siting) {
     hipChk(snnhip_tensor_alloc(ctx, out[0], out[1] / 2, out[2] / 2, 2, dtype, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
 }
 
+void HipBackend::initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb) {
+    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
+    int in[4], out[4];
+    hipChk(snnhip_tensor_dims(frameInT, in), "snnhip_tensor_dims");
+    hipChk(snnhip_tensor_dims(frameOutT, out), "snnhip_tensor_dims");
+    const int r = out[1] / in[1];
+    if (in[3] != 1 || out[3] != 1 || out[0] != in[0] || r < 1 || r > 4 || out[1] != r * in[1] || out[2] != r * in[2] || in[1] % 2 || in[2] % 2)
+        SNN_RIP("video frames need a one-channel model of even extent whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d", in[1], in[2], in[3], out[1], out[2],
+                out[3]);
+    snnhip_yuv_rgb_desc yd{in[0], in[1] / 2, in[2] / 2, channels, r, dtype, maxval, shift, siting, range, kr, kb};
+    hipChk(snnhip_yuv_rgb_plan_create(ctx, &yd, &yuvRgbPlan), "snnhip_yuv_rgb_plan_create");
+    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
+    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1], out[2], channels, dtype, &rgbOutT), "snnhip_tensor_alloc (RGB output frame)");
+}
+
 std::string HipBackend::describeVideo() const {
-    char buf[256];
+    char buf[320];
+    if (yuvRgbPlan && snnhip_plan_describe(yuvRgbPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[rgb out] ") + buf + "\n";
     if (chromaPlan && snnhip_plan_describe(chromaPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
     return std::string();
 }
@@ -147,6 +165,10 @@ void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
         hipChk(snnhip_plan_run_n(mergePlan, ins, 2, colourOutT), "snnhip_plan_run_n (luma + chroma -> colour frame)");
     }
     if (chromaPlan) hipChk(snnhip_plan_run(chromaPlan, chromaInT, chromaOutT), "snnhip_plan_run (chroma plane)");
+    if (yuvRgbPlan) {
+        const snnhip_tensor* ins[2] = {frameOutT, chromaInT};
+        hipChk(snnhip_plan_run_n(yuvRgbPlan, ins, 2, rgbOutT), "snnhip_plan_run_n (luma + chroma plane -> RGB frame)");
+    }
 }
 
 // counterpart of VulkanBackend::initRenderPasses -> VulkanRenderPass ctor (vulkanBackend.cpp:43-78, vulkanRenderpass.cpp:103-178):

@@ -127,12 +127,15 @@ public:
     // ends.  The luma plane IS the model's frame; the chroma plan upsamples the CbCr plane [n][H/2][W/2][2] to [n][rH/2][rW/2][2] in runFrameOut,
     // one launch more on the context's stream behind everything else of an inference (a straight line: no side stream, no parallel graph branch).
     void initVideoIO(int dtype, int maxval, int shift, int siting);
-    int videoLaunches() const { return chromaPlan ? 1 : 0; }
+    // ... or to packed RGB (CreationParameters::videoRgbChannels): the yuv_rgb plan builds the RGB / RGBA output frame [n][rH][rW][channels] from the
+    // model's output luma frame and the ORIGINAL CbCr plane in runFrameOut, in the chroma launch's place (no chroma plan, no upscaled chroma plane)
+    void initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb);
+    int videoLaunches() const { return chromaPlan || yuvRgbPlan ? 1 : 0; }
     std::string describeVideo() const; // one line for the extra launch (empty without video frames)
     snnhip_tensor* chromaInput() const { return chromaInT; }
     snnhip_tensor* chromaOutput() const { return chromaOutT; }
     snnhip_tensor* frameInput() const { return colourInT ? colourInT : frameInT; }
-    snnhip_tensor* frameOutput() const { return colourOutT ? colourOutT : frameOutT; }
+    snnhip_tensor* frameOutput() const { return rgbOutT ? rgbOutT : colourOutT ? colourOutT : frameOutT; }
 
 private:
     snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned
@@ -142,6 +145,8 @@ private:
     snnhip_tensor *colourInT = nullptr, *colourOutT = nullptr; // owned, SNNHIP_U8 [n][H][W][C] / [n][rH][rW][C]
     snnhip_plan* chromaPlan = nullptr;                          // owned
     snnhip_tensor *chromaInT = nullptr, *chromaOutT = nullptr;  // owned, SNNHIP_U8 / SNNHIP_U16 [n][H/2][W/2][2] / [n][rH/2][rW/2][2]
+    snnhip_plan* yuvRgbPlan = nullptr;                          // owned
+    snnhip_tensor* rgbOutT = nullptr;                           // owned, SNNHIP_U8 / SNNHIP_U16 [n][rH][rW][3 or 4]
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

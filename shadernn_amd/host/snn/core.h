@@ -82,6 +82,10 @@ public:
         // HIP extension: NV12 / P010 video frames around a luma-only model (snn_model_create8).  videoDtype SNNHIP_U8 / SNNHIP_U16 (0 = none): the
         // model's own ends are R8 / R16 frames; run() puts snnhip_chroma_up_plan_create's launch on the half-resolution CbCr plane behind the model
         int videoDtype = 0, videoMaxval = 255, videoShift = 0, videoSiting = 1;
+        // ... or, with videoRgbChannels 3 / 4 (snn_model_create9), snnhip_yuv_rgb_plan_create's launch instead: the model's output luma frame and the
+        // original CbCr plane to an RGB / RGBA frame (videoRange SNNHIP_RANGE_*, matrix videoKr / videoKb)
+        int videoRgbChannels = 0, videoRange = 0;
+        float videoKr = 0.299f, videoKb = 0.114f;
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const std::string& modelFileName, const dp::ShaderGenOptions& options,

@@ -103,9 +103,11 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
 }
 
 // snn_model_create6 / 7 / 8: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends, `video`
-// (snn_model_create8) for NV12 / P010 frames around a model that `io` gives R8 / R16 frames
+// (snn_model_create8) for NV12 / P010 frames around a model that `io` gives R8 / R16 frames, `videoRgb` (snn_model_create9, beside `video`) for an RGB
+// frame at the output instead of NV12 / P010
 static int createModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                       int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out, const snn_video_io* video = nullptr) {
+                       int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out, const snn_video_io* video = nullptr,
+                       const snn_video_rgb_io* videoRgb = nullptr) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
     ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
     if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
@@ -152,6 +154,12 @@ static int createModel(const char* json_path, int device, int in_w, int in_h, in
                 cp.videoMaxval = video->maxval;
                 cp.videoShift = video->shift;
                 cp.videoSiting = video->siting;
+                if (videoRgb) {
+                    cp.videoRgbChannels = videoRgb->out_format & 0xff;
+                    cp.videoRange = videoRgb->range;
+                    cp.videoKr = videoRgb->kr;
+                    cp.videoKb = videoRgb->kb;
+                }
             }
         }
         if (io) {
@@ -219,6 +227,43 @@ int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int
     io2.out_maxval = wide ? io->maxval : 65535; // (snn_model_create5 passes 65535 for the 8-bit formats: the same model)
     io2.out_shift = wide ? io->shift : 0;
     return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, io);
+}
+
+int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out) {
+    if (!io || (io->in_format != SNN_IO_NV12 && io->in_format != SNN_IO_NV12_16) || in_c != 1 || batch < 1) return -1;
+    const bool wide = io->in_format == SNN_IO_NV12_16;
+    if (wide ? (io->out_format != SNN_IO_RGB16 && io->out_format != SNN_IO_RGBA16) : (io->out_format != SNN_IO_RGB8 && io->out_format != SNN_IO_RGBA8)) return -1;
+    if (in_w < 2 || in_h < 2 || in_w % 2 || in_h % 2) return -1; // 4:2:0: the chroma plane is half the extent
+    if (io->siting != SNN_SITING_CENTRE && io->siting != SNN_SITING_LEFT) return -1;
+    if (io->range != SNN_RANGE_LIMITED && io->range != SNN_RANGE_FULL) return -1;
+    if (io->maxval < 255 || io->maxval > (wide ? 4095 : 255) || (io->maxval + 1) % 256 || io->shift < 0 || io->shift > (wide ? 15 : 0)) return -1;
+    if ((static_cast<long long>(io->maxval) << io->shift) > (wide ? 65535 : 255)) return -1;
+    if (!(io->kr > 0.0f && io->kb > 0.0f && io->kr + io->kb < 1.0f)) return -1;
+    // the luma plane's maps follow from the range
+    const double k = (io->maxval + 1) / 256.0;
+    const double yoff = io->range == SNN_RANGE_LIMITED ? 16.0 * k : 0.0, yrange = io->range == SNN_RANGE_LIMITED ? 219.0 * k : io->maxval;
+    snn_video_io video{};
+    video.format = io->in_format;
+    video.maxval = io->maxval;
+    video.shift = io->shift;
+    video.siting = io->siting;
+    video.in_mean = static_cast<float>(yoff);
+    video.in_norm = static_cast<float>(1.0 / yrange);
+    video.out_scale = static_cast<float>(yrange);
+    video.out_offset = static_cast<float>(yoff);
+    snn_frame_io2 io2{};
+    io2.in_format = io2.out_format = wide ? SNN_IO_R16 : SNN_IO_R8;
+    for (int c = 0; c < 4; ++c) {
+        io2.in_means[c] = video.in_mean;
+        io2.in_norms[c] = video.in_norm;
+        io2.out_scale[c] = video.out_scale;
+        io2.out_offset[c] = video.out_offset;
+    }
+    io2.in_shift = wide ? io->shift : 0;
+    io2.out_maxval = wide ? io->maxval : 65535; // (as snn_model_create8)
+    io2.out_shift = wide ? io->shift : 0;
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, &video, io);
 }
 
 // one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame

@@ -52,6 +52,16 @@ rgb8 (an NV12 frame moves 1.5 bytes per pixel over the link, an RGB8 frame 3), t
 beside the copy's.  profiles/espcn_video_frames.json holds the runs under the keys <format>_scale<r>.
 
     python tools/bench_frames.py --video P010 --scale 2
+
+--video NV12 | P010 --video-out RGB8 | RGBA8 (with any --scale): video in, display out.  Five forms in the same mirrored
+alternation: nv12 (the NV12 -> NV12 step of --video: the chain plus the chroma launch, three launches), nv12_rgb (the chain with the range's luma
+maps plus the yuv_rgb launch on its output and the ORIGINAL chroma plane: three launches, packed RGB out; a P010 frame comes back in 16-bit
+containers), yuv_rgb (that launch alone), copy (one hipMemcpyDtoDAsync that moves as many bytes through HBM as the yuv_rgb kernel has to) and rgb8
+(the RGB8 colour step of --colour: four launches).  Device step per form with the spread over the rounds, frames/s including one frame's H2D + D2H
+for nv12, nv12_rgb and rgb8, the kernels of the launch trace, and the yuv_rgb kernel's bytes/s beside the copy's.
+profiles/espcn_video_rgb_frames.json holds the runs under the keys <format>_<out>_scale<r>.
+
+    python tools/bench_frames.py --video NV12 --video-out RGB8 --scale 2
 """
 import argparse
 import json
@@ -458,6 +468,151 @@ def main_video(a):
     ctx.close()
 
 
+def main_video_rgb(a):
+    """--video ... --video-out ...: nv12 / nv12_rgb / yuv_rgb / copy / rgb8."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R, Cc = a.scale, {"RGB8": 3, "RGBA8": 4}[a.video_out]
+    wide = a.video == "P010"
+    maxval, shift, dt, npdt = (1023, 6, capi.U16, np.uint16) if wide else (255, 0, capi.U8, np.uint8)
+    k = (maxval + 1) / 256.0
+    yoff, yspan = (16.0 * k, 219.0 * k) if a.range == "limited" else (0.0, float(maxval))  # the luma maps snn_model_create9 derives from the range
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    assert H % 2 == 0 and W % 2 == 0, "4:2:0 frames have even extents"
+    rng = np.random.default_rng(1)
+    y_h = (rng.integers(int(16 * k), int(236 * k), size=(1, H, W, 1)) << shift).astype(npdt)
+    c_h = (rng.integers(int(16 * k), int(241 * k), size=(1, H // 2, W // 2, 2)) << shift).astype(npdt)
+    rgb = rng.integers(0, 256, size=(1, H, W, 3), dtype=np.uint8)
+
+    def chain_for(first, last_of):
+        layers, shape = [], (1, H, W, 1)
+        for layer in net["layers"]:
+            p = _layer_plan(ctx, layer, shape)
+            layers.append(p)
+            shape = p.out_shape()
+        chain = capi.chain_plan(ctx, [first] + layers + [last_of(shape)])
+        assert chain.num_steps() == 2, chain.describe()
+        return chain, shape
+
+    if wide:
+        grey, shape = chain_for(capi.u16_in_plan(ctx, 1, H, W, 1, (yoff, 0, 0, 0), (1 / yspan, 1, 1, 1), shift),
+                                lambda sh: capi.u16_out_plan(ctx, *sh, (yspan, 0, 0, 0), (yoff, 0, 0, 0), maxval, shift))
+    else:
+        grey, shape = chain_for(capi.u8_in_plan(ctx, 1, H, W, 1, (yoff, 0, 0, 0), (1 / yspan, 1, 1, 1)), lambda sh: capi.u8_out_plan(ctx, *sh, (yspan, 0, 0, 0), (yoff, 0, 0, 0)))
+    chain8, _ = chain_for(capi.u8_in_plan(ctx, 1, H, W, 1, (127.5, 0, 0, 0), (1 / 127.5, 1, 1, 1)), lambda sh: capi.u8_out_plan(ctx, *sh, (127.5, 0, 0, 0), (127.5, 0, 0, 0)))
+    chroma = capi.chroma_up_plan(ctx, 1, H // 2, W // 2, 2, R, dt, maxval, shift, a.siting)
+    yuv = capi.yuv_rgb_plan(ctx, 1, H // 2, W // 2, Cc, R, dt, maxval, shift, a.siting, a.range)
+    luma, merge = capi.rgb_luma_plan(ctx, 1, H, W, 3), capi.ycc_merge_plan(ctx, 1, H, W, 3, R)
+    cshape, vshape, oshape = (1, R * H // 2, R * W // 2, 2), (1, R * H, R * W, Cc), (1, R * H, R * W, 3)
+    t_y, t_c = capi.Tensor.from_numpy(ctx, y_h, dtype=dt), capi.Tensor.from_numpy(ctx, c_h, dtype=dt)
+    t_yhi, t_chi, t_vout = capi.Tensor(ctx, *shape, dtype=dt), capi.Tensor(ctx, *cshape, dtype=dt), capi.Tensor(ctx, *vshape, dtype=dt)
+    t_rgb, t_luma = capi.Tensor.from_numpy(ctx, rgb, dtype=capi.U8), capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8)
+    t_yhi8, t_out = capi.Tensor(ctx, *shape, dtype=capi.U8), capi.Tensor(ctx, *oshape, dtype=capi.U8)
+    yuv_bytes = int(yuv.cost()[1])
+    half = yuv_bytes // 2
+    t_src, t_dst = capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8)
+    t_src.upload_u8(np.random.default_rng(3).integers(0, 256, size=half, dtype=np.uint8))
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+
+    def run_nv12():
+        grey.run(t_y, t_yhi)
+        chroma.run(t_c, t_chi)
+
+    def run_nv12_rgb():
+        grey.run(t_y, t_yhi)
+        yuv.run([t_yhi, t_c], t_vout)
+
+    def run_yuv_rgb():
+        yuv.run([t_yhi, t_c], t_vout)
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(t_dst.data_ptr(), t_src.data_ptr(), half, stream)
+        assert rc == 0, rc
+
+    def run_rgb8():
+        luma.run(t_rgb, t_luma)
+        chain8.run(t_luma, t_yhi8)
+        merge.run([t_yhi8, t_rgb], t_out)
+
+    forms = {"nv12": run_nv12, "nv12_rgb": run_nv12_rgb, "yuv_rgb": run_yuv_rgb, "copy": run_copy, "rgb8": run_rgb8}
+    yhi_h, chi_h, vout_h, out_h = np.empty(shape, npdt), np.empty(cshape, npdt), np.empty(vshape, npdt), np.empty(oshape, np.uint8)
+    io = {"nv12": ([(t_y, y_h), (t_c, c_h)], [(t_yhi, yhi_h), (t_chi, chi_h)]), "nv12_rgb": ([(t_y, y_h), (t_c, c_h)], [(t_vout, vout_h)]), "rgb8": ([(t_rgb, rgb)], [(t_out, out_h)])}
+    for f in forms.values():
+        for _ in range(a.warmup):
+            f()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {k_: [] for k_ in forms}
+    e2e = {k_: [] for k_ in io}
+    order = list(forms) + list(forms)[::-1]  # mirrored: A B C D E E D C B A
+    for _ in range(a.rounds):
+        for k_ in order:
+            timer.start()
+            for _ in range(a.iters):
+                forms[k_]()
+            timer.stop()
+            dev[k_].append(timer.elapsed_ms() / a.iters)
+    for _ in range(a.rounds):
+        for k_ in list(io) + list(io)[::-1]:
+            ups, downs = io[k_]
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                for t, h in ups:
+                    capi.check(capi.lib().snnhip_tensor_upload_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+                forms[k_]()
+                for t, h in downs:
+                    capi.check(capi.lib().snnhip_tensor_download_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+            e2e[k_].append((time.perf_counter() - t0) * 1e3 / a.iters)
+    out = {"frame": "%dx%d -> %dx%d" % (H, W, R * H, R * W), "scale": R, "video": a.video, "video_out": a.video_out, "siting": a.siting, "range": a.range,
+           "rounds": a.rounds, "iters": a.iters}
+    for k_ in forms:
+        d = statistics.median(dev[k_])
+        out[k_] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[k_]), 4), "device_ms_max": round(max(dev[k_]), 4),
+                   "device_spread": round((max(dev[k_]) - min(dev[k_])) / d, 4)}
+        if k_ in io:
+            e = statistics.median(e2e[k_])
+            out[k_].update({"e2e_ms_median": round(e, 4), "e2e_ms_min": round(min(e2e[k_]), 4), "e2e_ms_max": round(max(e2e[k_]), 4), "e2e_frames_per_s": round(1e3 / e, 1),
+                            "io_bytes_per_frame": int(sum(h.nbytes for _, h in io[k_][0]) + sum(h.nbytes for _, h in io[k_][1]))})
+    chain_steps = [grey.step_describe(i) for i in range(2)]
+    out["nv12"]["steps"] = chain_steps + [chroma.describe()]
+    out["nv12_rgb"]["steps"] = chain_steps + [yuv.describe()]
+    out["rgb8"]["steps"] = [luma.describe()] + [chain8.step_describe(i) for i in range(2)] + [merge.describe()]
+    for k_ in ("nv12", "nv12_rgb", "yuv_rgb", "rgb8"):  # the launch trace: per-kernel times of each form (a copy is no kernel of the library)
+        capi.trace_begin()
+        for _ in range(a.iters):
+            forms[k_]()
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        out[k_]["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                               "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+    out["device_nv12_rgb_over_nv12"] = round(out["nv12_rgb"]["device_ms_median"] / out["nv12"]["device_ms_median"], 4)
+    out["device_nv12_rgb_over_rgb8"] = round(out["nv12_rgb"]["device_ms_median"] / out["rgb8"]["device_ms_median"], 4)
+    out["e2e_fps_nv12_rgb_over_nv12"] = round(out["nv12_rgb"]["e2e_frames_per_s"] / out["nv12"]["e2e_frames_per_s"], 4)
+    out["e2e_fps_nv12_rgb_over_rgb8"] = round(out["nv12_rgb"]["e2e_frames_per_s"] / out["rgb8"]["e2e_frames_per_s"], 4)
+    traced = [it for it in out["yuv_rgb"]["kernels"] if it["function"] and "yuv_rgb" in it["function"]]
+    yuv_us = traced[0]["us_per_launch"] if traced else 1e3 * out["yuv_rgb"]["device_ms_median"]
+    copy_us = 1e3 * out["copy"]["device_ms_median"]
+    out["yuv_rgb_vs_copy"] = {"yuv_rgb_hbm_bytes": yuv_bytes, "yuv_rgb_us_per_launch_traced": yuv_us, "yuv_rgb_tbs_traced": round(yuv_bytes / (yuv_us * 1e-6) / 1e12, 3),
+                              "yuv_rgb_tbs_event_timed_loop": round(yuv_bytes / (out["yuv_rgb"]["device_ms_median"] * 1e-3) / 1e12, 3),
+                              "copy_bytes_each_way": half, "copy_hbm_bytes": 2 * half, "copy_us": round(copy_us, 2),
+                              "copy_tbs": round(2 * half / (copy_us * 1e-6) / 1e12, 3)}
+    out["yuv_rgb_vs_copy"]["yuv_rgb_over_copy_rate"] = round(out["yuv_rgb_vs_copy"]["yuv_rgb_tbs_event_timed_loop"] / out["yuv_rgb_vs_copy"]["copy_tbs"], 4)
+    print(json.dumps(out, indent=1))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
@@ -465,6 +620,8 @@ def main():
     ap.add_argument("--bits", type=int, default=0, choices=[0, 10, 12, 16], help="also time 16-bit frames of this bit depth, folded and as separate launches")
     ap.add_argument("--colour", choices=["RGB8", "RGBA8"], default=None, help="colour frames around the luma chain: r8, colour, the merge launch alone and a device copy of its bytes")
     ap.add_argument("--video", choices=["NV12", "P010"], default=None, help="4:2:0 video frames around the luma chain: grey, video, the chroma launch alone, a device copy of its bytes and the RGB8 colour step")
+    ap.add_argument("--video-out", choices=["RGB8", "RGBA8"], default=None, help="with --video: packed RGB / RGBA out of the yuv_rgb launch (16-bit containers for P010) beside the NV12 step")
+    ap.add_argument("--range", choices=["limited", "full"], default="limited", help="the stream's range with --video-out")
     ap.add_argument("--siting", choices=["left", "centre"], default="left", help="horizontal chroma siting of --video")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
     ap.add_argument("--h", type=int, default=0)
@@ -475,6 +632,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.video and a.video_out:
+        return main_video_rgb(a)
     if a.video:
         return main_video(a)
     if a.colour:
