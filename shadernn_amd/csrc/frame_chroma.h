@@ -1,28 +1,10 @@
-// frame_chroma.h -- what the chroma-plane upsampler of frame_chroma.hip shares between its kernel, its plan and the host-side tap table
-// (include/snnhip.h: snnhip_chroma_up_plan_create / snnhip_bicubic_taps_sited): the sited phase and the lane geometry of one (R, C, E) instance.
-// The Keys cubic and the quantiser are frame_colour.h's; nothing there changes.
+// frame_chroma.h -- what the chroma-plane upsampler of frame_chroma.hip shares between its kernel and its plan (include/snnhip.h:
+// snnhip_chroma_up_plan_create / snnhip_bicubic_taps_sited): the lane geometry of one (R, C, E) instance.  The sited phase (bicubic_phase_sited:
+// centre s = (p + 0.5) / r - 0.5, left s = (p + 0.25) / r - 0.25), the Keys cubic and the quantiser are frame_resample.h's.
 #pragma once
-#include "../../include/snnhip.h"
-#include "frame_colour.h"
+#include "frame_resample.h"
 
 namespace snnhip {
-
-// Output sample r*x + p of an r-fold upscale reads source position x + s:
-//   centre siting (aligned sample centres, what bicubic_phase computes):  s = (p + 0.5)  / r - 0.5
-//   left siting (the sample co-sited with the even luma column):          s = (p + 0.25) / r - 0.25
-// base = floor(s) is -1 or 0; taps at x + base - 1 .. x + base + 2 with the Keys weights at distances 1 + t, t, 1 - t, 2 - t, t = s - base.
-inline void bicubic_phase_sited(int r, int p, int siting, int* base, double w[4]) {
-#pragma clang fp contract(off)
-    const double off = siting == SNNHIP_SITING_LEFT ? 0.25 : 0.5;
-    const double s = (p + off) / r - off;
-    const double i0 = std::floor(s);
-    const double t = s - i0;
-    *base = static_cast<int>(i0);
-    w[0] = keys_cubic(1.0 + t);
-    w[1] = keys_cubic(t);
-    w[2] = keys_cubic(1.0 - t);
-    w[3] = keys_cubic(2.0 - t);
-}
 
 // One lane of the kernel owns kIn bytes of an input row (a whole number of pixels) and R times as many bytes of each of the R output rows under it:
 // 16 bytes out wherever R divides 16 (two such stores for 16-bit r = 4), 24 for r = 3.  A wave is 64 lanes side by side, a block four waves one above

@@ -29,12 +29,6 @@ struct ChromaParams {
     float wv[4][5]; // ... along a column (aligned centres)
 };
 
-template <typename E>
-__device__ __forceinline__ unsigned chroma_elem(const unsigned* w, int i) {
-    constexpr int PER = 4 / static_cast<int>(sizeof(E)), BITS = 8 * static_cast<int>(sizeof(E));
-    return (w[i / PER] >> (BITS * (i % PER))) & ((1u << BITS) - 1u);
-}
-
 // BYTES (2, 4, 8 or 16) from an address aligned to BYTES, as dwords
 template <int BYTES>
 __device__ __forceinline__ void chroma_load(const void* p, unsigned* w) {
@@ -61,7 +55,7 @@ __device__ __forceinline__ void chroma_load_row(const E* __restrict__ row, int x
         unsigned w[G::IN / 4];
         chroma_load<G::IN>(row + static_cast<size_t>(x0) * C, w);
 #pragma unroll
-        for (int e = 0; e < G::NE; ++e) v[G::AE + e] = static_cast<float>(chroma_elem<E>(w, e) >> shift);
+        for (int e = 0; e < G::NE; ++e) v[G::AE + e] = static_cast<float>(frame_elem<E>(w, e) >> shift);
     } else {
 #pragma unroll
         for (int e = 0; e < G::NE; ++e) {
@@ -73,7 +67,7 @@ __device__ __forceinline__ void chroma_load_row(const E* __restrict__ row, int x
         unsigned w[(AP + 3) / 4];
         chroma_load<AP>(row + static_cast<size_t>(x0 - 2) * C, w);
 #pragma unroll
-        for (int e = 0; e < G::AE; ++e) v[e] = static_cast<float>(chroma_elem<E>(w, e) >> shift);
+        for (int e = 0; e < G::AE; ++e) v[e] = static_cast<float>(frame_elem<E>(w, e) >> shift);
     } else {
 #pragma unroll
         for (int e = 0; e < G::AE; ++e) {
@@ -85,7 +79,7 @@ __device__ __forceinline__ void chroma_load_row(const E* __restrict__ row, int x
         unsigned w[(AP + 3) / 4];
         chroma_load<AP>(row + static_cast<size_t>(x0 + G::PX) * C, w);
 #pragma unroll
-        for (int e = 0; e < G::AE; ++e) v[G::AE + G::NE + e] = static_cast<float>(chroma_elem<E>(w, e) >> shift);
+        for (int e = 0; e < G::AE; ++e) v[G::AE + G::NE + e] = static_cast<float>(frame_elem<E>(w, e) >> shift);
     } else {
 #pragma unroll
         for (int e = 0; e < G::AE; ++e) {
@@ -98,18 +92,7 @@ __device__ __forceinline__ void chroma_load_row(const E* __restrict__ row, int x
 // one staged row to the lane's R * PX output columns: output pixel j reads input pixel j / R at phase j % R, five weights over its offsets -2 .. 2
 template <int R, int C, typename E>
 __device__ __forceinline__ void chroma_hfilter(const ChromaParams& P, const float* v, float* h) {
-    using G = ChromaGeom<R, C, E>;
-#pragma unroll
-    for (int j = 0; j < R * G::PX; ++j) {
-        const int x = j / R, p = j % R;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            float acc = P.wh[p][0] * v[x * C + c];
-#pragma unroll
-            for (int k = 1; k < 5; ++k) acc += P.wh[p][k] * v[(x + k) * C + c];
-            h[j * C + c] = acc;
-        }
-    }
+    frame_hfilter<R, C, ChromaGeom<R, C, E>::PX>(P.wh, v, h);
 }
 
 template <int R, int C, typename E>
@@ -118,12 +101,10 @@ __device__ __forceinline__ void chroma_up_body(const ChromaParams& P, const E* _
     constexpr int ROWS = kChromaRows + 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int H = P.H, W = P.W, OH = R * P.H, OW = R * P.W;
-    const unsigned b = blockIdx.x;
-    const int tx = static_cast<int>(b % static_cast<unsigned>(P.tilesX));
-    const int ty = static_cast<int>((b / static_cast<unsigned>(P.tilesX)) % static_cast<unsigned>(P.tilesY));
-    const size_t n = b / (static_cast<unsigned>(P.tilesX) * static_cast<unsigned>(P.tilesY));
-    const int x0 = (tx * 64 + lane) * G::PX;
-    const int y0 = ty * G::TILE_H + wave * kChromaRows;
+    const FrameTile tile = frame_tile(blockIdx.x, P.tilesX, P.tilesY);
+    const size_t n = tile.n;
+    const int x0 = (tile.tx * 64 + lane) * G::PX;
+    const int y0 = tile.ty * G::TILE_H + wave * kChromaRows;
     if (x0 >= W || y0 >= H) return; // (no barrier anywhere below)
     const E* plane = in + n * H * W * C;
 
@@ -147,11 +128,11 @@ __device__ __forceinline__ void chroma_up_body(const ChromaParams& P, const E* _
             float v[G::NB];
 #pragma unroll
             for (int e = 0; e < G::AE; ++e) {
-                v[e] = static_cast<float>(chroma_elem<E>(raw[i], e) >> P.shift);
-                v[G::AE + G::NE + e] = static_cast<float>(chroma_elem<E>(raw[i] + APW + INW, e) >> P.shift);
+                v[e] = static_cast<float>(frame_elem<E>(raw[i], e) >> P.shift);
+                v[G::AE + G::NE + e] = static_cast<float>(frame_elem<E>(raw[i] + APW + INW, e) >> P.shift);
             }
 #pragma unroll
-            for (int e = 0; e < G::NE; ++e) v[G::AE + e] = static_cast<float>(chroma_elem<E>(raw[i] + APW, e) >> P.shift);
+            for (int e = 0; e < G::NE; ++e) v[G::AE + e] = static_cast<float>(frame_elem<E>(raw[i] + APW, e) >> P.shift);
             chroma_hfilter<R, C, E>(P, v, h[i]);
         }
     } else {
@@ -229,20 +210,9 @@ struct ChromaUpPlan : snnhip_plan {
         const dim3 grid(static_cast<unsigned>(P.N) * static_cast<unsigned>(P.tilesX) * static_cast<unsigned>(P.tilesY));
         const E* src = reinterpret_cast<const E*>(in->data);
         E* dst = reinterpret_cast<E*>(out->data);
-#define SNNHIP_CHROMA(RR, CC) SNNHIP_LAUNCH((chroma_up_kernel<RR, CC, E>), grid, dim3(256), 0, ctx->stream, P, src, dst)
-#define SNNHIP_CHROMA_C(RR)            \
-    do {                               \
-        if (d.C == 1) SNNHIP_CHROMA(RR, 1); \
-        else SNNHIP_CHROMA(RR, 2);     \
-    } while (0)
-        switch (d.r) {
-        case 1: SNNHIP_CHROMA_C(1); break;
-        case 2: SNNHIP_CHROMA_C(2); break;
-        case 3: SNNHIP_CHROMA_C(3); break;
-        default: SNNHIP_CHROMA_C(4); break;
-        }
-#undef SNNHIP_CHROMA_C
-#undef SNNHIP_CHROMA
+        dispatch_r_c<1, 2>(d.r, d.C, [&](auto R, auto C) {
+            SNNHIP_LAUNCH((chroma_up_kernel<decltype(R)::value, decltype(C)::value, E>), grid, dim3(256), 0, ctx->stream, P, src, dst);
+        });
     }
 
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
@@ -259,12 +229,6 @@ struct ChromaUpPlan : snnhip_plan {
     }
 };
 
-// a phase's four weights at base - 1 .. base + 2 as five weights over -2 .. 2
-void widen_taps(int r, const float* w4, const int* base, float w5[4][5]) {
-    for (int p = 0; p < r; ++p)
-        for (int k = 0; k < 4; ++k) w5[p][base[p] + 1 + k] = w4[4 * p + k];
-}
-
 } // namespace
 } // namespace snnhip
 
@@ -273,19 +237,8 @@ using namespace snnhip;
 extern "C" {
 
 int snnhip_bicubic_taps_sited(int r, int siting, float* weights, int* base, int capacity) {
-    SNNHIP_REQUIRE(weights && base, "bicubic_taps_sited: null argument");
-    SNNHIP_REQUIRE(r >= 1 && r <= 4, "bicubic_taps_sited: r = %d (1..4)", r);
-    SNNHIP_REQUIRE(siting == SNNHIP_SITING_CENTRE || siting == SNNHIP_SITING_LEFT, "bicubic_taps_sited: siting %d (SNNHIP_SITING_CENTRE or SNNHIP_SITING_LEFT)", siting);
-    SNNHIP_REQUIRE(capacity >= 4 * r, "bicubic_taps_sited: room for %d floats, %d needed", capacity, 4 * r);
-    for (int p = 0; p < r; ++p) {
-        double w[4];
-        int b = 0;
-        bicubic_phase_sited(r, p, siting, &b, w);
-        SNNHIP_REQUIRE(b == -1 || b == 0, "bicubic_taps_sited: phase %d of r = %d starts at %d", p, r, b);
-        base[p] = b;
-        for (int k = 0; k < 4; ++k) weights[4 * p + k] = static_cast<float>(w[k]);
-    }
-    return SNNHIP_OK;
+    // the output is itself a chroma grid of the same siting (bicubic_phase_sited): lead = off
+    return fill_bicubic_taps("bicubic_taps_sited", r, r, siting, siting_offset(siting), siting_offset(siting), weights, base, capacity);
 }
 
 int snnhip_chroma_up_plan_create(snnhip_ctx* ctx, const snnhip_chroma_up_desc* desc, snnhip_plan** out) {
@@ -293,17 +246,9 @@ int snnhip_chroma_up_plan_create(snnhip_ctx* ctx, const snnhip_chroma_up_desc* d
     SNNHIP_REQUIRE(desc->N > 0 && desc->H > 0 && desc->W > 0, "chroma_up desc: bad dims %dx%dx%d", desc->N, desc->H, desc->W);
     SNNHIP_REQUIRE(desc->C == 1 || desc->C == 2, "chroma_up desc: %d channels (1: one plane of a planar format, 2: interleaved CbCr)", desc->C);
     SNNHIP_REQUIRE(desc->r >= 1 && desc->r <= 4, "chroma_up desc: r = %d (an integer 1..4)", desc->r);
-    SNNHIP_REQUIRE(desc->dtype == SNNHIP_U8 || desc->dtype == SNNHIP_U16, "chroma_up desc: dtype %d (SNNHIP_U8 or SNNHIP_U16)", desc->dtype);
-    SNNHIP_REQUIRE(desc->siting == SNNHIP_SITING_CENTRE || desc->siting == SNNHIP_SITING_LEFT, "chroma_up desc: siting %d (SNNHIP_SITING_CENTRE or SNNHIP_SITING_LEFT)",
-                   desc->siting);
-    const int bits = desc->dtype == SNNHIP_U8 ? 8 : 16;
-    SNNHIP_REQUIRE(desc->shift >= 0 && desc->shift < bits && (bits == 16 || desc->shift == 0), "chroma_up desc: shift %d (0 for 8-bit planes, 0..15 for 16-bit containers)",
-                   desc->shift);
-    SNNHIP_REQUIRE(desc->maxval >= 1, "chroma_up desc: maxval %d (at least 1)", desc->maxval);
-    // the fp32 filter on full 16-bit values is 1.5e-2 away from its float64 value: too far for a rounding contract (P016 chroma is not built)
-    SNNHIP_REQUIRE(desc->maxval <= 4095, "chroma_up desc: maxval %d is above 4095 (12 bits): the fp32 filter cannot keep the rounding contract for wider samples", desc->maxval);
-    SNNHIP_REQUIRE((static_cast<long long>(desc->maxval) << desc->shift) < (1ll << bits), "chroma_up desc: maxval %d << shift %d does not fit %d bits", desc->maxval, desc->shift,
-                   bits);
+    int bits = 0;
+    const int fmt = check_sample_format("chroma_up desc", "planes", desc->dtype, desc->siting, desc->shift, desc->maxval, &bits);
+    if (fmt != SNNHIP_OK) return fmt;
     int th = 0, tw = 0;
     chroma_tile(desc->r, desc->C, bits / 8, &th, &tw);
     const int tilesX = up_div(desc->W, tw), tilesY = up_div(desc->H, th);

@@ -28,6 +28,7 @@ namespace {
 // i0 of phase p relative to the low-resolution pixel underneath, floor((p + 0.5) / r - 0.5): -1 or 0 (bicubic_phase computes the same on the host)
 constexpr int phase_first(int r, int p) { return 2 * p + 1 < r ? -1 : 0; }
 
+// (a kernel parameter: the type stays in this unit's unnamed namespace, where the kernels' symbols have it)
 struct ColourMatrix {
     float kr, kg, kb;
 };
@@ -83,11 +84,9 @@ __device__ __forceinline__ void ycc_merge_body(const MergeParams& P, const E* __
     const float maxval = FrameElem<E>::maxval;
     const int tid = threadIdx.x;
     const int H = P.H, W = P.W, OH = R * P.H, OW = R * P.W;
-    const unsigned b = blockIdx.x;
-    const int tx = static_cast<int>(b % static_cast<unsigned>(P.tilesX));
-    const int ty = static_cast<int>((b / static_cast<unsigned>(P.tilesX)) % static_cast<unsigned>(P.tilesY));
-    const size_t n = b / (static_cast<unsigned>(P.tilesX) * static_cast<unsigned>(P.tilesY));
-    const int x0 = tx * TW, y0 = ty * TH;
+    const FrameTile tile = frame_tile(blockIdx.x, P.tilesX, P.tilesY);
+    const size_t n = tile.n;
+    const int x0 = tile.tx * TW, y0 = tile.ty * TH;
     const bool loWide = C == 4 && sizeof(E) == 1 && (reinterpret_cast<size_t>(lo) & 3) == 0;
 
     for (int i = tid; i < SH * SW; i += 256) {
@@ -201,8 +200,6 @@ __global__ __launch_bounds__(256) void ycc_merge_u8_kernel(MergeParams P, const 
     ycc_merge_body<R, C, unsigned char>(P, yhi, lo, out);
 }
 
-bool matrix_ok(float kr, float kb) { return kr > 0.0f && kb > 0.0f && kr + kb < 1.0f; }
-
 ColourMatrix make_matrix(float kr, float kb) {
     return ColourMatrix{kr, static_cast<float>(1.0 - static_cast<double>(kr) - static_cast<double>(kb)), kb};
 }
@@ -243,20 +240,9 @@ struct YccMergePlan : snnhip_plan {
                        d.r * d.H, d.r * d.W, d.C);
         const dim3 grid(static_cast<unsigned>(P.N) * static_cast<unsigned>(P.tilesX) * static_cast<unsigned>(P.tilesY));
         unsigned char* dst = reinterpret_cast<unsigned char*>(out->data);
-#define SNNHIP_MERGE(RR, CC) SNNHIP_LAUNCH((ycc_merge_u8_kernel<RR, CC>), grid, dim3(256), 0, ctx->stream, P, bytes_of(in[0]), bytes_of(in[1]), dst)
-#define SNNHIP_MERGE_C(RR)        \
-    do {                          \
-        if (d.C == 3) SNNHIP_MERGE(RR, 3); \
-        else SNNHIP_MERGE(RR, 4); \
-    } while (0)
-        switch (d.r) {
-        case 1: SNNHIP_MERGE_C(1); break;
-        case 2: SNNHIP_MERGE_C(2); break;
-        case 3: SNNHIP_MERGE_C(3); break;
-        default: SNNHIP_MERGE_C(4); break;
-        }
-#undef SNNHIP_MERGE_C
-#undef SNNHIP_MERGE
+        dispatch_r_c<3, 4>(d.r, d.C, [&](auto R, auto C) {
+            SNNHIP_LAUNCH((ycc_merge_u8_kernel<decltype(R)::value, decltype(C)::value>), grid, dim3(256), 0, ctx->stream, P, bytes_of(in[0]), bytes_of(in[1]), dst);
+        });
         SNNHIP_CHECK_HIP(hipGetLastError());
         return SNNHIP_OK;
     }
@@ -270,16 +256,10 @@ using namespace snnhip;
 extern "C" {
 
 int snnhip_bicubic_taps(int r, float* out, int capacity) {
-    SNNHIP_REQUIRE(out, "bicubic_taps: null argument");
-    SNNHIP_REQUIRE(r >= 1 && r <= 4, "bicubic_taps: r = %d (1..4)", r);
-    SNNHIP_REQUIRE(capacity >= 4 * r, "bicubic_taps: room for %d floats, %d needed", capacity, 4 * r);
-    for (int p = 0; p < r; ++p) {
-        int first = 0;
-        double w[4];
-        bicubic_phase(r, p, &first, w);
-        SNNHIP_REQUIRE(first == phase_first(r, p), "bicubic_taps: phase %d of r = %d starts at %d", p, r, first);
-        for (int k = 0; k < 4; ++k) out[4 * p + k] = static_cast<float>(w[k]);
-    }
+    int first[4] = {0};
+    const int rc = fill_bicubic_taps("bicubic_taps", r, r, SNNHIP_SITING_CENTRE, 0.5, 0.5, out, first, capacity);
+    if (rc != SNNHIP_OK) return rc;
+    for (int p = 0; p < r; ++p) SNNHIP_REQUIRE(first[p] == phase_first(r, p), "bicubic_taps: phase %d of r = %d starts at %d", p, r, first[p]);
     return SNNHIP_OK;
 }
 

@@ -1,35 +1,11 @@
-// frame_yuv_rgb.h -- what the NV12 / P010 -> RGB kernel of frame_yuv_rgb.hip shares between its kernel, its plan and the two host-side tables
-// (include/snnhip.h: snnhip_yuv_rgb_plan_create / snnhip_bicubic_taps_420 / snnhip_yuv_rgb_coefficients): the phase of a resampling whose output
-// grid is not the source's own, the matrix coefficients and the lane geometry of one (R, E) instance.  The Keys cubic and the quantiser are
-// frame_colour.h's, the siting constants frame_chroma.h's; nothing there changes.
+// frame_yuv_rgb.h -- what the NV12 / P010 -> RGB kernel of frame_yuv_rgb.hip shares between its kernel, its plan and the coefficient table
+// (include/snnhip.h: snnhip_yuv_rgb_plan_create / snnhip_bicubic_taps_420 / snnhip_yuv_rgb_coefficients): the matrix coefficients and the lane
+// geometry of one (R, E) instance.  The phase of a resampling whose output grid is not the source's own (bicubic_phase_general, bicubic_phase_420),
+// the Keys cubic and the quantiser are frame_resample.h's.
 #pragma once
-#include "../../include/snnhip.h"
-#include "frame_chroma.h"
+#include "frame_resample.h"
 
 namespace snnhip {
-
-// The generalised phase: output sample R*x + p of an R-fold resampling reads source position x + s, s = (p + lead) / R - off.  `lead` is where the
-// output sample sits inside its own cell, `off` where the source sample sits inside its cell, both in units of the cell.  bicubic_phase is
-// lead = off = 0.5, bicubic_phase_sited (the output is itself a chroma grid) lead = off = 0.25 for left siting.  base = floor(s), taps at
-// x + base - 1 .. x + base + 2 with the Keys weights at distances 1 + t, t, 1 - t, 2 - t, t = s - base.
-inline void bicubic_phase_general(int R, int p, double lead, double off, int* base, double w[4]) {
-#pragma clang fp contract(off)
-    const double s = (p + lead) / R - off;
-    const double i0 = std::floor(s);
-    const double t = s - i0;
-    *base = static_cast<int>(i0);
-    w[0] = keys_cubic(1.0 + t);
-    w[1] = keys_cubic(t);
-    w[2] = keys_cubic(1.0 - t);
-    w[3] = keys_cubic(2.0 - t);
-}
-
-// A 4:2:0 chroma plane resampled straight to the OUTPUT LUMA grid, R = 2r-fold: output luma column X = R*x + p sits at low-resolution luma position
-// (X + 0.5) / r - 0.5, which halved is chroma index (X + 0.5) / R - 0.25 for left-sited chroma (sample i co-sited with luma column 2i) and
-// (X + 0.5) / R - 0.5 for centred chroma: lead = 0.5 either way.
-inline void bicubic_phase_420(int R, int p, int siting, int* base, double w[4]) {
-    bicubic_phase_general(R, p, 0.5, siting == SNNHIP_SITING_LEFT ? 0.25 : 0.5, base, w);
-}
 
 // Y'CbCr -> full-range RGB at `maxval`: the offsets and the five coefficients of the contract, computed in double and rounded to float.
 struct YuvRgbCoeffs {

@@ -81,12 +81,6 @@ __device__ __forceinline__ void store_words(void* p, const unsigned* w) {
     }
 }
 
-template <typename E>
-__device__ __forceinline__ unsigned yuv_elem(const unsigned* w, int i) {
-    constexpr int PER = 4 / static_cast<int>(sizeof(E)), BITS = 8 * static_cast<int>(sizeof(E));
-    return (w[i / PER] >> (BITS * (i % PER))) & ((1u << BITS) - 1u);
-}
-
 // raw[b * 2 + c] = chroma pixel (x0 - 2 + b, channel c) of the row at `row`.  WIDE: three aligned loads -- the lane's own dword and the aprons either
 // side (the row is dword-aligned, x0 >= 2 and x0 + CP + 2 <= W); otherwise elements, indices clamped to [0, W - 1] (x0 < W)
 template <int R, typename E, bool WIDE>
@@ -100,7 +94,7 @@ __device__ __forceinline__ void yuv_load_chroma(const E* __restrict__ row, int x
         load_words<1>(p, w + AW);
         load_words<AW>(p + 2 * G::CP, w + AW + 1);
 #pragma unroll
-        for (int e = 0; e < G::NB; ++e) raw[e] = yuv_elem<E>(w, e);
+        for (int e = 0; e < G::NB; ++e) raw[e] = frame_elem<E>(w, e);
     } else {
 #pragma unroll
         for (int e = 0; e < G::NB; ++e) {
@@ -117,17 +111,7 @@ __device__ __forceinline__ void yuv_hfilter(const YuvRgbParams& P, const unsigne
     float v[G::NB];
 #pragma unroll
     for (int e = 0; e < G::NB; ++e) v[e] = static_cast<float>(raw[e] >> P.shift) - P.m.coff;
-#pragma unroll
-    for (int j = 0; j < G::OPX; ++j) {
-        const int x = j / G::R2, p = j % G::R2;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            float acc = P.wh[p][0] * v[x * 2 + c];
-#pragma unroll
-            for (int k = 1; k < 5; ++k) acc += P.wh[p][k] * v[(x + k) * 2 + c];
-            h[j * 2 + c] = acc;
-        }
-    }
+    frame_hfilter<G::R2, 2, G::CP>(P.wh, v, h);
 }
 
 // the lane's OPX pixels of one output row: u = its dwords of Yhi, w = its C * r dwords of output
@@ -144,7 +128,7 @@ __device__ __forceinline__ void yuv_row(const YuvRgbParams& P, const float (&h)[
             cb += P.wv[q][k] * h[k][j * 2];
             cr += P.wv[q][k] * h[k][j * 2 + 1];
         }
-        const float yl = P.m.cy * (static_cast<float>(yuv_elem<E>(u, j) >> P.shift) - P.m.yoff);
+        const float yl = P.m.cy * (static_cast<float>(frame_elem<E>(u, j) >> P.shift) - P.m.yoff);
         unsigned e[4];
         e[0] = quantize_frame(yl + P.m.crv * cr, P.maxval) << P.shift;
         e[1] = quantize_frame(yl - (P.m.cgv * cr + P.m.cgu * cb), P.maxval) << P.shift;
@@ -165,12 +149,10 @@ __device__ __forceinline__ void yuv_rgb_body(const YuvRgbParams& P, const E* __r
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int H = P.H, W = P.W;
     const size_t OH = static_cast<size_t>(G::R2) * H, OW = static_cast<size_t>(G::R2) * W;
-    const unsigned b = blockIdx.x;
-    const int tx = static_cast<int>(b % static_cast<unsigned>(P.tilesX));
-    const int ty = static_cast<int>((b / static_cast<unsigned>(P.tilesX)) % static_cast<unsigned>(P.tilesY));
-    const size_t n = b / (static_cast<unsigned>(P.tilesX) * static_cast<unsigned>(P.tilesY));
-    const int x0 = (tx * 64 + lane) * G::CP;
-    const int y = ty * G::TILE_H + wave;
+    const FrameTile tile = frame_tile(blockIdx.x, P.tilesX, P.tilesY);
+    const size_t n = tile.n;
+    const int x0 = (tile.tx * 64 + lane) * G::CP;
+    const int y = tile.ty * G::TILE_H + wave;
     if (x0 >= W || y >= H) return; // (no barrier anywhere below)
     const E* plane = cbcr + n * H * W * 2;
 
@@ -224,7 +206,7 @@ __device__ __forceinline__ void yuv_rgb_body(const YuvRgbParams& P, const E* __r
             yuv_row<R, C, E>(P, h, q, u, w);
 #pragma unroll
             for (int i = 0; i < G::OPX * C; ++i)
-                if (i < valid * C) dst[i] = static_cast<E>(yuv_elem<E>(w, i));
+                if (i < valid * C) dst[i] = static_cast<E>(frame_elem<E>(w, i));
         }
     }
 }
@@ -244,20 +226,9 @@ struct YuvRgbPlan : snnhip_plan {
         const E* ysrc = reinterpret_cast<const E*>(y->data);
         const E* csrc = reinterpret_cast<const E*>(c->data);
         E* dst = reinterpret_cast<E*>(out->data);
-#define SNNHIP_YUV(RR, CC) SNNHIP_LAUNCH((yuv_rgb_kernel<RR, CC, E>), grid, dim3(256), 0, ctx->stream, P, ysrc, csrc, dst)
-#define SNNHIP_YUV_C(RR)               \
-    do {                               \
-        if (d.C == 3) SNNHIP_YUV(RR, 3); \
-        else SNNHIP_YUV(RR, 4);        \
-    } while (0)
-        switch (d.r) {
-        case 1: SNNHIP_YUV_C(1); break;
-        case 2: SNNHIP_YUV_C(2); break;
-        case 3: SNNHIP_YUV_C(3); break;
-        default: SNNHIP_YUV_C(4); break;
-        }
-#undef SNNHIP_YUV_C
-#undef SNNHIP_YUV
+        dispatch_r_c<3, 4>(d.r, d.C, [&](auto R, auto C) {
+            SNNHIP_LAUNCH((yuv_rgb_kernel<decltype(R)::value, decltype(C)::value, E>), grid, dim3(256), 0, ctx->stream, P, ysrc, csrc, dst);
+        });
     }
 
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
@@ -278,14 +249,6 @@ struct YuvRgbPlan : snnhip_plan {
     }
 };
 
-// a phase's four weights at base - 1 .. base + 2 as five weights over -2 .. 2
-void widen_taps_420(int phases, const float* w4, const int* base, float w5[8][5]) {
-    for (int p = 0; p < phases; ++p)
-        for (int k = 0; k < 4; ++k) w5[p][base[p] + 1 + k] = w4[4 * p + k];
-}
-
-bool matrix_ok(float kr, float kb) { return kr > 0.0f && kb > 0.0f && kr + kb < 1.0f; }
-
 } // namespace
 } // namespace snnhip
 
@@ -294,19 +257,8 @@ using namespace snnhip;
 extern "C" {
 
 int snnhip_bicubic_taps_420(int r, int siting, float* weights, int* base, int capacity) {
-    SNNHIP_REQUIRE(weights && base, "bicubic_taps_420: null argument");
-    SNNHIP_REQUIRE(r >= 1 && r <= 4, "bicubic_taps_420: r = %d (1..4)", r);
-    SNNHIP_REQUIRE(siting == SNNHIP_SITING_CENTRE || siting == SNNHIP_SITING_LEFT, "bicubic_taps_420: siting %d (SNNHIP_SITING_CENTRE or SNNHIP_SITING_LEFT)", siting);
-    SNNHIP_REQUIRE(capacity >= 8 * r, "bicubic_taps_420: room for %d floats, %d needed", capacity, 8 * r);
-    for (int p = 0; p < 2 * r; ++p) {
-        double w[4];
-        int b = 0;
-        bicubic_phase_420(2 * r, p, siting, &b, w);
-        SNNHIP_REQUIRE(b == -1 || b == 0, "bicubic_taps_420: phase %d of r = %d starts at %d", p, r, b);
-        base[p] = b;
-        for (int k = 0; k < 4; ++k) weights[4 * p + k] = static_cast<float>(w[k]);
-    }
-    return SNNHIP_OK;
+    // straight to the output luma grid, 2r-fold (bicubic_phase_420): lead = 0.5 whatever the siting
+    return fill_bicubic_taps("bicubic_taps_420", r, 2 * r, siting, 0.5, siting_offset(siting), weights, base, capacity);
 }
 
 int snnhip_yuv_rgb_coefficients(int maxval, int range, float kr, float kb, float* out, int capacity) {
@@ -325,16 +277,10 @@ int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc,
     SNNHIP_REQUIRE(desc->N > 0 && desc->H > 0 && desc->W > 0, "yuv_rgb desc: bad dims %dx%dx%d", desc->N, desc->H, desc->W);
     SNNHIP_REQUIRE(desc->C == 3 || desc->C == 4, "yuv_rgb desc: %d channels (3: RGB, 4: RGBA)", desc->C);
     SNNHIP_REQUIRE(desc->r >= 1 && desc->r <= 4, "yuv_rgb desc: r = %d (an integer 1..4)", desc->r);
-    SNNHIP_REQUIRE(desc->dtype == SNNHIP_U8 || desc->dtype == SNNHIP_U16, "yuv_rgb desc: dtype %d (SNNHIP_U8 or SNNHIP_U16)", desc->dtype);
-    SNNHIP_REQUIRE(desc->siting == SNNHIP_SITING_CENTRE || desc->siting == SNNHIP_SITING_LEFT, "yuv_rgb desc: siting %d (SNNHIP_SITING_CENTRE or SNNHIP_SITING_LEFT)", desc->siting);
+    int bits = 0;
+    const int fmt = check_sample_format("yuv_rgb desc", "frames", desc->dtype, desc->siting, desc->shift, desc->maxval, &bits);
+    if (fmt != SNNHIP_OK) return fmt;
     SNNHIP_REQUIRE(desc->range == SNNHIP_RANGE_LIMITED || desc->range == SNNHIP_RANGE_FULL, "yuv_rgb desc: range %d (SNNHIP_RANGE_LIMITED or SNNHIP_RANGE_FULL)", desc->range);
-    const int bits = desc->dtype == SNNHIP_U8 ? 8 : 16;
-    SNNHIP_REQUIRE(desc->shift >= 0 && desc->shift < bits && (bits == 16 || desc->shift == 0), "yuv_rgb desc: shift %d (0 for 8-bit frames, 0..15 for 16-bit containers)",
-                   desc->shift);
-    SNNHIP_REQUIRE(desc->maxval >= 1, "yuv_rgb desc: maxval %d (at least 1)", desc->maxval);
-    // as for chroma_up: the fp32 filter on wider samples is too far from its float64 value for a rounding contract
-    SNNHIP_REQUIRE(desc->maxval <= 4095, "yuv_rgb desc: maxval %d is above 4095 (12 bits): the fp32 filter cannot keep the rounding contract for wider samples", desc->maxval);
-    SNNHIP_REQUIRE((static_cast<long long>(desc->maxval) << desc->shift) < (1ll << bits), "yuv_rgb desc: maxval %d << shift %d does not fit %d bits", desc->maxval, desc->shift, bits);
     SNNHIP_REQUIRE((desc->maxval + 1) % 256 == 0, "yuv_rgb desc: maxval %d: maxval + 1 must be a multiple of 256 (the offsets 16k, 128k of the matrix are integers)", desc->maxval);
     SNNHIP_REQUIRE(matrix_ok(desc->kr, desc->kb), "yuv_rgb desc: kr = %g, kb = %g (0 < kr, 0 < kb, kr + kb < 1)", desc->kr, desc->kb);
     int th = 0, tw = 0;
@@ -368,8 +314,8 @@ int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc,
     plan->P.maxval = static_cast<float>(desc->maxval);
     plan->P.alpha = static_cast<unsigned>(desc->maxval) << desc->shift;
     plan->P.m = yuv_rgb_coeffs(desc->maxval, desc->range, desc->kr, desc->kb);
-    widen_taps_420(R2, wh, bh, plan->P.wh);
-    widen_taps_420(R2, wv, bv, plan->P.wv);
+    widen_taps(R2, wh, bh, plan->P.wh);
+    widen_taps(R2, wv, bv, plan->P.wv);
     plan->inDims[0] = plan->outDims[0] = desc->N;
     plan->inDims[1] = plan->outDims[1] = R2 * desc->H;
     plan->inDims[2] = plan->outDims[2] = R2 * desc->W;

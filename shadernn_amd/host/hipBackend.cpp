@@ -92,14 +92,23 @@ void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC
     }
 }
 
+// The upscale factor of a luma model from its two frame tensors, whose dims it returns: one channel in and out, an integer 1..4, the same on both
+// axes; video frames (4:2:0: a chroma sample under every 2 x 2 luma samples) also need an even extent.
+static int frameScale(const snnhip_tensor* frameIn, const snnhip_tensor* frameOut, bool needEvenExtent, int in[4], int out[4]) {
+    hipChk(snnhip_tensor_dims(frameIn, in), "snnhip_tensor_dims");
+    hipChk(snnhip_tensor_dims(frameOut, out), "snnhip_tensor_dims");
+    const int r = out[1] / in[1];
+    if (in[3] != 1 || out[3] != 1 || out[0] != in[0] || r < 1 || r > 4 || out[1] != r * in[1] || out[2] != r * in[2] || (needEvenExtent && (in[1] % 2 || in[2] % 2)))
+        SNN_RIP(needEvenExtent ? "video frames need a one-channel model of even extent whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d"
+                               : "colour frames need a one-channel model whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d",
+                in[1], in[2], in[3], out[1], out[2], out[3]);
+    return r;
+}
+
 void HipBackend::initColourIO(int channels, float kr, float kb) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == SNNHIP_U8 && snnhip_tensor_dtype(frameOutT) == SNNHIP_U8);
     int in[4], out[4];
-    hipChk(snnhip_tensor_dims(frameInT, in), "snnhip_tensor_dims");
-    hipChk(snnhip_tensor_dims(frameOutT, out), "snnhip_tensor_dims");
-    const int r = out[1] / in[1];
-    if (in[3] != 1 || out[3] != 1 || out[0] != in[0] || r < 1 || r > 4 || out[1] != r * in[1] || out[2] != r * in[2])
-        SNN_RIP("colour frames need a one-channel model whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d", in[1], in[2], in[3], out[1], out[2], out[3]);
+    const int r = frameScale(frameInT, frameOutT, false, in, out);
     snnhip_rgb_luma_desc ld{in[0], in[1], in[2], channels, kr, kb};
     hipChk(snnhip_rgb_luma_plan_create(ctx, &ld, &lumaPlan), "snnhip_rgb_luma_plan_create");
     snnhip_ycc_merge_desc md{in[0], in[1], in[2], channels, r, kr, kb};
@@ -119,12 +128,7 @@ std::string HipBackend::describeColour() const {
 void HipBackend::initVideoIO(int dtype, int maxval, int shift, int siting) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
     int in[4], out[4];
-    hipChk(snnhip_tensor_dims(frameInT, in), "snnhip_tensor_dims");
-    hipChk(snnhip_tensor_dims(frameOutT, out), "snnhip_tensor_dims");
-    const int r = out[1] / in[1];
-    if (in[3] != 1 || out[3] != 1 || out[0] != in[0] || r < 1 || r > 4 || out[1] != r * in[1] || out[2] != r * in[2] || in[1] % 2 || in[2] % 2)
-        SNN_RIP("video frames need a one-channel model of even extent whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d", in[1], in[2], in[3], out[1], out[2],
-                out[3]);
+    const int r = frameScale(frameInT, frameOutT, true, in, out);
     snnhip_chroma_up_desc cd{in[0], in[1] / 2, in[2] / 2, 2, r, dtype, maxval, shift, siting};
     hipChk(snnhip_chroma_up_plan_create(ctx, &cd, &chromaPlan), "snnhip_chroma_up_plan_create");
     hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
@@ -134,12 +138,7 @@ void HipBackend::initVideoIO(int dtype, int maxval, int shift, int siting) {
 void HipBackend::initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
     int in[4], out[4];
-    hipChk(snnhip_tensor_dims(frameInT, in), "snnhip_tensor_dims");
-    hipChk(snnhip_tensor_dims(frameOutT, out), "snnhip_tensor_dims");
-    const int r = out[1] / in[1];
-    if (in[3] != 1 || out[3] != 1 || out[0] != in[0] || r < 1 || r > 4 || out[1] != r * in[1] || out[2] != r * in[2] || in[1] % 2 || in[2] % 2)
-        SNN_RIP("video frames need a one-channel model of even extent whose output is 1..4 times its input: %dx%dx%d -> %dx%dx%d", in[1], in[2], in[3], out[1], out[2],
-                out[3]);
+    const int r = frameScale(frameInT, frameOutT, true, in, out);
     snnhip_yuv_rgb_desc yd{in[0], in[1] / 2, in[2] / 2, channels, r, dtype, maxval, shift, siting, range, kr, kb};
     hipChk(snnhip_yuv_rgb_plan_create(ctx, &yd, &yuvRgbPlan), "snnhip_yuv_rgb_plan_create");
     hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");

@@ -3,6 +3,10 @@ split in front of a luma-only model and the bicubic chroma merge behind it.  The
 float32, kg = 1 - kr - kb formed in double and rounded to float32); everything else is float64."""
 import numpy as np
 
+import resample_ref
+from resample_ref import keys, near_tie  # noqa: F401  (re-exported for the tests)
+from resample_ref import quantise as _quantise
+
 BT601 = (0.299, 0.114)
 BT709 = (0.2126, 0.0722)
 
@@ -21,47 +25,21 @@ def luma_values(rgb, kr=BT601[0], kb=BT601[1]):
 
 
 def quantise(v):
-    return np.clip(np.rint(v), 0.0, 255.0).astype(np.uint8)  # np.rint: ties to even
+    return _quantise(v, 255, 0, np.uint8)
 
 
 def luma(rgb, kr=BT601[0], kb=BT601[1]):
     return quantise(luma_values(rgb, kr, kb))
 
 
-def keys(d):
-    """Keys cubic, a = -0.5 (Catmull-Rom), at distance d >= 0; the products are written out so that any IEEE double arithmetic gives the same bits."""
-    d = np.asarray(d, np.float64)
-    a = -0.5
-    near = (a + 2.0) * (d * d * d) - (a + 3.0) * (d * d) + 1.0
-    far = a * (d * d * d) - 5.0 * a * (d * d) + 8.0 * a * d - 4.0 * a
-    return np.where(d <= 1.0, near, np.where(d < 2.0, far, 0.0))
-
-
 def taps(r):
-    """The [r][4] float64 weight table of an r-fold upscale: row p = the phase of output sample X = r*x + p."""
-    rows = []
-    for p in range(r):
-        sx = (p + 0.5) / r - 0.5
-        t = sx - np.floor(sx)
-        rows.append(keys(np.array([1.0 + t, t, 1.0 - t, 2.0 - t])))
-    return np.stack(rows)
+    """The [r][4] float64 weight table of an r-fold upscale with aligned pixel centres: row p = the phase of output sample X = r*x + p."""
+    return resample_ref.taps(r, 0.5, 0.5)[0]
 
 
 def _resample(a, r, axis):
     """`a` resampled r-fold along `axis`: aligned pixel centres, taps i0 - 1 .. i0 + 2 with replicate edge, Keys weights."""
-    size = a.shape[axis]
-    X = np.arange(r * size, dtype=np.float64)
-    sx = (X + 0.5) / r - 0.5
-    i0 = np.floor(sx)
-    t = sx - i0
-    w = np.stack([keys(1.0 + t), keys(t), keys(1.0 - t), keys(2.0 - t)])  # [4][r*size]
-    out = 0.0
-    shape = [1] * a.ndim
-    shape[axis] = r * size
-    for k in range(4):
-        idx = np.clip(i0.astype(np.int64) - 1 + k, 0, size - 1)
-        out = out + np.take(a, idx, axis=axis) * w[k].reshape(shape)
-    return out
+    return resample_ref._resample(a, r, axis, 0.5, 0.5)
 
 
 def merge_values(yhi, rgb, r, kr=BT601[0], kb=BT601[1]):
@@ -88,35 +66,17 @@ def merge(yhi, rgb, r, kr=BT601[0], kb=BT601[1]):
     return out
 
 
-def near_tie(v, eps=1e-3):
-    v = np.asarray(v, np.float64)
-    return np.abs(v - np.floor(v) - 0.5) < eps
-
-
 def compare(got, want_values, max_tie_fraction=0.01, eps=1e-3):
-    """The comparison rule: bytes equal the reference's wherever its pre-rounding value is no near tie, and differ by at most 1 on near ties; near ties
-    are at most `max_tie_fraction` of the compared values (asserted on the reference alone; None: the caller pools several inputs and asserts it
-    itself, see compare_all).  Returns (near ties, values compared, bytes that differ)."""
-    want = quantise(want_values)
-    got = np.asarray(got)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    tie = near_tie(want_values, eps)
+    """The comparison rule (resample_ref.compare on bytes): bytes equal the reference's wherever its pre-rounding value is no near tie, and differ by
+    at most 1 on near ties; near ties are at most `max_tie_fraction` of the compared values (asserted on the reference alone; None: the caller pools
+    several inputs and asserts it itself, see compare_all).  Returns (near ties, values compared, bytes that differ)."""
+    ties, total, ndiff = resample_ref.compare(got, want_values, 255, 0, eps)
     if max_tie_fraction is not None:
-        assert tie.mean() <= max_tie_fraction, "near ties are %.3f %% of the reference values" % (100 * tie.mean())
-    diff = got.astype(np.int32) - want.astype(np.int32)
-    bad = (diff != 0) & ~tie
-    assert not bad.any(), "%d bytes differ off the near ties, first at %s: got %s, reference value %s" % (
-        int(bad.sum()), tuple(np.argwhere(bad)[0]), got[bad][0], want_values[bad][0])
-    assert np.abs(diff).max(initial=0) <= 1, "a near-tie byte differs by %d" % int(np.abs(diff).max())
-    return int(tie.sum()), int(tie.size), int((diff != 0).sum())
+        assert ties / total <= max_tie_fraction, "near ties are %.3f %% of the reference values" % (100 * ties / total)
+    return ties, total, ndiff
 
 
 def compare_all(pairs, max_tie_fraction=0.01):
-    """compare() over the (got, want_values) pairs of one sweep; the near-tie bound holds for the sweep's inputs taken together (its smallest frames
-    have three values each).  Returns (near-tie fraction, bytes that differ)."""
-    ties = total = ndiff = 0
-    for got, want_values in pairs:
-        t, n, d = compare(got, want_values, None)
-        ties, total, ndiff = ties + t, total + n, ndiff + d
-    assert ties <= max_tie_fraction * total, "near ties are %d of %d reference values" % (ties, total)
-    return ties / max(total, 1), ndiff
+    """compare() over the (got, want_values) pairs of one sweep; the near-tie bound holds for the sweep's inputs taken together.  Returns (near-tie
+    fraction, bytes that differ)."""
+    return resample_ref.compare_all(pairs, lambda got, want_values: compare(got, want_values, None), max_tie_fraction)

@@ -1,15 +1,15 @@
 """Float64 NumPy restatement of the NV12 / P010 -> RGB contract of include/snnhip.h (snnhip_yuv_rgb_plan_create / snnhip_bicubic_taps_420 /
 snnhip_yuv_rgb_coefficients): the model's upscaled luma frame and the original half-resolution CbCr plane in, full-range RGB at the output
 resolution out.  The five matrix coefficients are the fp32 values the device sees (computed in double from the float32 kr, kb, rounded to float32);
-everything else is float64.  The Keys kernel and the near-tie helper are tests/colour_ref.py's.  values32() evaluates the same expression in float32
-and sets the comparison rule's eps (measured_distance)."""
+everything else is float64.  The filter, the quantiser and the comparison rule are tests/resample_ref.py's.  values32() evaluates the same
+expression in float32 and sets the comparison rule's eps (measured_distance)."""
 import numpy as np
 
-from colour_ref import BT601, BT709, keys, near_tie  # noqa: F401  (BT601 / BT709 are re-exported for the tests)
+import resample_ref
+from colour_ref import BT601, BT709  # noqa: F401  (re-exported for the tests)
+from resample_ref import CENTRE, LEFT, SITING_OFFSET, keys, near_tie, quantise  # noqa: F401  (re-exported for the tests)
 
-CENTRE, LEFT = 0, 1
 LIMITED, FULL = 0, 1
-SITING_OFFSET = {CENTRE: 0.5, LEFT: 0.25, "centre": 0.5, "left": 0.25}
 RANGES = {LIMITED: LIMITED, FULL: FULL, "limited": LIMITED, "full": FULL}
 # near-tie half-width by bit depth.  Measured with this file's own float32 path (measured_distance: r = 1..4, both ranges, both sitings, the input
 # recipe below, 12 x 16 chroma planes): the largest fp32-to-float64 distance of the value in front of the rounding is
@@ -23,21 +23,9 @@ MAX_TIE_FRACTION = 0.03
 MAX_CLAMP_FRACTION = 0.02
 
 
-def phase(r, p, siting):
-    """(base, t) of output luma column X = 2r*x + p: it reads chroma position x + s, s = (p + 0.5) / 2r - off, base = floor(s), t = s - base."""
-    s = (p + 0.5) / (2 * r) - SITING_OFFSET[siting]
-    base = np.floor(s)
-    return int(base), s - base
-
-
 def taps(r, siting):
-    """(weights float64 [2r][4], base int [2r]): phase p reads x + base[p] - 1 .. x + base[p] + 2."""
-    rows, bases = [], []
-    for p in range(2 * r):
-        b, t = phase(r, p, siting)
-        rows.append(keys(np.array([1.0 + t, t, 1.0 - t, 2.0 - t])))
-        bases.append(b)
-    return np.stack(rows), np.array(bases, np.int64)
+    """(weights float64 [2r][4], base int [2r]) of a chroma plane resampled 2r-fold straight to the output luma grid: lead = 0.5, off by siting."""
+    return resample_ref.taps(2 * r, 0.5, SITING_OFFSET[siting])
 
 
 def coefficients(maxval=255, rng=LIMITED, kr=BT601[0], kb=BT601[1]):
@@ -55,20 +43,7 @@ def coefficients(maxval=255, rng=LIMITED, kr=BT601[0], kb=BT601[1]):
 
 def _resample(a, r, axis, siting, dtype=np.float64):
     """`a` resampled 2r-fold along `axis` to the output luma grid; with dtype float32 the weights are rounded and the sum runs in float32."""
-    size = a.shape[axis]
-    w, base = taps(r, siting)
-    w = w.astype(dtype)
-    R = 2 * r
-    X = np.arange(R * size)
-    x, p = X // R, X % R
-    out = None
-    shape = [1] * a.ndim
-    shape[axis] = R * size
-    for k in range(4):
-        idx = np.clip(x + base[p] - 1 + k, 0, size - 1)
-        term = np.take(a, idx, axis=axis) * w[p, k].reshape(shape)
-        out = term if out is None else out + term
-    return out
+    return resample_ref._resample(a, 2 * r, axis, 0.5, SITING_OFFSET[siting], dtype)
 
 
 def _values(yhi, cbcr, r, siting, rng, maxval, shift, kr, kb, dtype):
@@ -93,10 +68,6 @@ def values(yhi, cbcr, r, siting=LEFT, rng=LIMITED, maxval=255, shift=0, kr=BT601
 def values32(yhi, cbcr, r, siting=LEFT, rng=LIMITED, maxval=255, shift=0, kr=BT601[0], kb=BT601[1]):
     """The same expression with float32 weights, coefficients and arithmetic (no fused multiply-add): what sets eps."""
     return _values(yhi, cbcr, r, siting, rng, maxval, shift, kr, kb, np.float32)
-
-
-def quantise(v, maxval, shift, dtype):
-    return (np.clip(np.rint(v), 0.0, float(maxval)).astype(np.int64) << shift).astype(dtype)  # np.rint: ties to even
 
 
 def rgb(yhi, cbcr, r, C=3, siting=LEFT, rng=LIMITED, maxval=255, shift=0, kr=BT601[0], kb=BT601[1]):
@@ -138,31 +109,14 @@ def measured_distance(maxval, shift=0, dtype=None, shape=(12, 16)):
 
 
 def compare(got, want_values, maxval, shift):
-    """The comparison rule for one output (its R, G, B channels; alpha, if any, must be maxval << shift): equal to the reference wherever its
-    pre-rounding value is farther than EPS[maxval] from a tie, at most 1 << shift off on near ties.  Returns (near ties, values compared, values
-    that differ); the caller bounds the near ties of its sweep."""
+    """resample_ref.compare on the R, G, B channels with this contract's near-tie half-width EPS[maxval]; alpha, if any, must be maxval << shift."""
     got = np.asarray(got)
     if got.shape[-1] == 4:
         assert (got[..., 3] == (maxval << shift)).all(), "alpha is not maxval << shift everywhere"
         got = got[..., :3]
-    want = quantise(want_values, maxval, shift, got.dtype)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    tie = near_tie(want_values, EPS[maxval])
-    assert not (got.astype(np.int64) & ((1 << shift) - 1)).any(), "bits below the shift are set"
-    diff = (got.astype(np.int64) >> shift) - (want.astype(np.int64) >> shift)
-    bad = (diff != 0) & ~tie
-    assert not bad.any(), "%d values differ off the near ties, first at %s: got %s, reference value %s" % (
-        int(bad.sum()), tuple(np.argwhere(bad)[0]), got[bad][0], want_values[bad][0])
-    assert np.abs(diff).max(initial=0) <= 1, "a near-tie value differs by %d" % int(np.abs(diff).max())
-    return int(tie.sum()), int(tie.size), int((diff != 0).sum())
+    return resample_ref.compare(got, want_values, maxval, shift, EPS[maxval])
 
 
 def compare_all(items):
-    """compare() over the (got, want_values, maxval, shift) items of one sweep; near ties are at most MAX_TIE_FRACTION of the sweep's values taken
-    together (asserted on the reference alone).  Returns (near-tie fraction, values that differ)."""
-    ties = total = ndiff = 0
-    for got, want_values, maxval, shift in items:
-        t, n, d = compare(got, want_values, maxval, shift)
-        ties, total, ndiff = ties + t, total + n, ndiff + d
-    assert ties <= MAX_TIE_FRACTION * total, "near ties are %d of %d reference values: change the seed" % (ties, total)
-    return ties / max(total, 1), ndiff
+    """compare() over the (got, want_values, maxval, shift) items of one sweep, near ties at most MAX_TIE_FRACTION of the sweep's values."""
+    return resample_ref.compare_all(items, compare, MAX_TIE_FRACTION)
