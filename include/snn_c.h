@@ -139,6 +139,26 @@ typedef struct snn_video_rgb_io {
 } snn_video_rgb_io;
 int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out);
+/* Capture in, encoder out: RGB8 / RGBA8 frames at the model's INPUT, an NV12 frame (4:2:0, what a hardware encoder takes) at its output.  Through a
+ * struct and an entry point of their own: every earlier struct and entry point keeps its layout and behaviour.  The model is built exactly as
+ * snn_model_create5 builds it with SNN_IO_R8 at both ends; the luma maps follow from `range` and are not given, as in snn_model_create9 -- in: mean
+ * 0, norm 1 / 255 (the full-range luma of snnhip_rgb_luma_plan_create); out: scale 219, offset 16 (SNN_RANGE_LIMITED) or scale 255, offset 0
+ * (SNN_RANGE_FULL) -- so ESPCN stays its two fused 8-bit kernels (the fp16 opt-in works too).  Four launches in all, on one stream and all inside
+ * the recorded graph with capture_graph: snnhip_rgb_luma_plan_create in front (as snn_model_create7), the two fused kernels, and
+ * snnhip_rgb_cbcr_plan_create behind them, from the colour input frame to the chroma plane [batch][rH/2][rW/2][2] (include/snnhip.h states the
+ * arithmetic; kr / kb are the matrix of both, BT.601 0.299 / 0.114).  snn_model_upload_frame_u8 takes [batch][H][W][C];
+ * snn_model_download_frame_nv12 returns `batch` frames of rH*rW + (rH/2)*rW bytes; snn_model_download_frame_u8 returns -1.  snn_model_describe
+ * lists both extra launches.  Returns -1, before anything is built on the device, for a null struct, other formats, a model that is not one channel in
+ * and one channel out at r = 2..4 times the extent, an odd r*in_w or r*in_h, an unknown siting or range, a matrix outside 0 < kr, 0 < kb, kr + kb < 1
+ * and batch < 1.  16-bit sources (RGB16 -> P010) need a 16-bit luma split that does not exist: not offered. */
+typedef struct snn_encode_io {
+    int in_format;  /* SNN_IO_RGB8 or SNN_IO_RGBA8 */
+    int out_format; /* SNN_IO_NV12 */
+    int siting, range;
+    float kr, kb;
+} snn_encode_io;
+int snn_model_create10(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_encode_io* io, snn_model** out);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

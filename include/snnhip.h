@@ -393,7 +393,8 @@ int snnhip_u16_out_plan_create(snnhip_ctx* ctx, const snnhip_u16_out_desc* desc,
  * The arithmetic contract, stated once:
  *   Matrix: full-range Y'CbCr with coefficients kr, kb of the desc and kg = 1 - kr - kb, computed in double and rounded to float.  BT.601 is
  *     kr = 0.299, kb = 0.114 (what cv2.COLOR_BGR2YCrCb uses); BT.709 is 0.2126 / 0.0722.  Limited range is not offered on this RGB-in path; video
- *     sources (NV12 / P010, limited range almost always) go through snnhip_yuv_rgb_plan_create below, which takes either range.
+ *     sources (NV12 / P010, limited range almost always) go through snnhip_yuv_rgb_plan_create below, which takes either range, and an RGB frame
+ *     leaves as limited-range NV12 through snnhip_rgb_cbcr_plan_create.
  *   rgb_luma:   U8 [N][H][W][C] -> U8 [N][H][W][1].  ylo = kr*R + kg*G + kb*B in fp32, q = clamp(rint(ylo), 0, 255), ties to even: the U8 luma plane
  *     that snnhip_u8_in_plan_create (and chain rule A8) consumes unchanged.
  *   ycc_merge:  inputs[0] = Yhi, U8 [N][r*H][r*W][1]; inputs[1] = the original low-resolution frame, U8 [N][H][W][C]; output U8 [N][r*H][r*W][C]
@@ -489,6 +490,40 @@ int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc,
 int snnhip_bicubic_taps_420(int r, int siting, float* weights, int* base, int capacity);
 /* host only, no context: out[0..6] = Yoff, Coff, cy, crv, cbu, cgv, cgu of the matrix above (capacity >= 7 floats) */
 int snnhip_yuv_rgb_coefficients(int maxval, int range, float kr, float kb, float* out, int capacity);
+
+/* RGB frames in, NV12 out around a luma-only model: the chroma plane of the UPSCALED 4:2:0 frame from the ORIGINAL low-resolution RGB frame, in one
+ * launch (capture, upscale, then encode: a hardware encoder takes NV12).  The luma plane of that frame is the model's own 8-bit output (rgb_luma in
+ * front, the output map scale 219 / offset 16 for limited range, 255 / 0 for full).  DESIGN.md section 4.17.  The contract, stated once:
+ *   Shapes: the input is U8 [N][H][W][C], C = 3 (R, G, B) or 4 (alpha is ignored); H, W are the LOW-resolution frame's.  The output is U8
+ *     [N][rH/2][rW/2][2], interleaved Cb, Cr: the chroma plane of an NV12 frame of rH x rW.  r = 2, 3, 4, and rH and rW must be even (r = 3 needs
+ *     even H and W).  r = 1 is refused: it would halve the chroma grid, which needs a decimation filter, and is not built.  16-bit sources (RGB16 ->
+ *     P010) need a 16-bit luma split that does not exist either.
+ *   Chroma differences: per low-resolution pixel ylo = kr R + kg G + kb B in fp32, unquantised (the one device function of rgb_luma and ycc_merge,
+ *     kg = 1 - kr - kb as there), dB = B - ylo, dR = R - ylo.
+ *   Resampling: the Keys cubic of the plans above (a = -0.5), separable, horizontal then vertical, indices clamped to the frame, fp32 weights computed
+ *     on the host in double and rounded to float, fp32 accumulation.  Output chroma column I sits at output luma position 2I for SNNHIP_SITING_LEFT
+ *     and midway between columns 2I and 2I + 1 for SNNHIP_SITING_CENTRE: it reads low-resolution position sx = (2I + lead) / r - 0.5, lead = 0.5
+ *     (left) or 1.0 (centre).  Rows always use the centre form, as chroma_up and yuv_rgb do.  With g = gcd(r, 2) the pattern repeats every P = r / g
+ *     outputs over S = 2 / g inputs ((P, S) = (1, 1), (3, 2), (2, 1) for r = 2, 3, 4): output I = P x' + p reads S x' + s_p, s_p = (2p + lead) / r -
+ *     0.5; base_p = floor(s_p) lies in {-1, 0, 1} and travels with the weights; taps are S x' + base_p - 1 .. S x' + base_p + 2.  r = 2 centre is the
+ *     identity (s = 0, weights 0, 1, 0, 0), r = 2 left a quarter-pixel shift (s = -0.25), r = 3 left phase 2 the identity on input 2x' + 1.
+ *   Matrix: Coff = 128; Crange = 224 for SNNHIP_RANGE_LIMITED, 255 for SNNHIP_RANGE_FULL; cbs = Crange / (2 (1 - kb) 255), crs = Crange /
+ *     (2 (1 - kr) 255), computed in double and rounded to float: the inverses of yuv_rgb's cbu and crv.  Cb = Coff + cbs dB~, Cr = Coff + crs dR~,
+ *     q = clamp(rint(.), 0, 255), ties to even.
+ *   Consequences: a grey frame (R = G = B) gives Cb = Cr = 128 byte for byte; a constant frame gives a constant plane; at r = 2 centre the plane is
+ *     the per-pixel conversion of the input.  In fp32 the value in front of the rounding stays within 2.6e-5 of a float64 evaluation (measured; the
+ *     worst case of the expression, sixteen roundings at half an ulp of 256, is 2.4e-4).
+ * Plan creation returns SNNHIP_E_INVALID with a message for C outside {3, 4}, r outside 2..4, an odd rH or rW, an unknown siting or range and kr, kb
+ * outside 0 < kr, 0 < kb, kr + kb < 1; snnhip_plan_run for a tensor that is not SNNHIP_U8 at either end and an output that is not [N][rH/2][rW/2][2].
+ * snnhip_plan_describe: "rgb_cbcr_u8 r=2 c=3 siting=left range=limited tile=8x256 ... kernel=rgb_cbcr_kernel" (the tile in output chroma pixels).
+ * snnhip_plan_cost counts the input once and the output once.  The reference has nothing for this (its ESPCN demo writes a grey image). */
+typedef struct { int N, H, W, C; int r; int siting; int range; float kr, kb; } snnhip_rgb_cbcr_desc; /* H, W: the LOW-resolution RGB frame */
+int snnhip_rgb_cbcr_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run */
+/* host only, no context: the tap table of the plan's horizontal axis (and, with SNNHIP_SITING_CENTRE, of its vertical one): weights [P][4] (capacity
+ * >= 4 * P floats, P = 1, 3, 2 for r = 2, 3, 4) and base [P] ints; phase p reads S x' + base[p] - 1 .. S x' + base[p] + 2 */
+int snnhip_bicubic_taps_rgb420(int r, int siting, float* weights, int* base, int capacity);
+/* host only, no context: out[0..2] = Coff, cbs, crs of the matrix above (capacity >= 3 floats) */
+int snnhip_rgb_cbcr_coefficients(int range, float kr, float kb, float* out, int capacity);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

@@ -113,6 +113,10 @@ class YuvRgbDesc(C.Structure):
                 ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
 
 
+class RgbCbcrDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("r", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -195,6 +199,9 @@ SIGNATURES = {
     "snnhip_yuv_rgb_plan_create": (C.c_int, [_P, C.POINTER(YuvRgbDesc), C.POINTER(_P)]),
     "snnhip_bicubic_taps_420": (C.c_int, [C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_yuv_rgb_coefficients": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, _FP, C.c_int]),
+    "snnhip_rgb_cbcr_plan_create": (C.c_int, [_P, C.POINTER(RgbCbcrDesc), C.POINTER(_P)]),
+    "snnhip_bicubic_taps_rgb420": (C.c_int, [C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
+    "snnhip_rgb_cbcr_coefficients": (C.c_int, [C.c_int, C.c_float, C.c_float, _FP, C.c_int]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -795,6 +802,37 @@ def yuv_rgb_coefficients(maxval=255, range="limited", kr=BT601[0], kb=BT601[1]):
     """snnhip_yuv_rgb_coefficients (host side only, no GPU): float32 (Yoff, Coff, cy, crv, cbu, cgv, cgu) of the Y'CbCr -> RGB matrix."""
     out = np.zeros(7, np.float32)
     check(lib().snnhip_yuv_rgb_coefficients(maxval, RANGE.get(range, range), kr, kb, _fptr(out), out.size))
+    return out
+
+
+def rgb_cbcr_plan(ctx, N, H, W, Cc, r, siting="left", range="limited", kr=BT601[0], kb=BT601[1]):
+    """plan.run([frame U8 [N][H][W][Cc]], out U8 [N][r*H/2][r*W/2][2]): the CbCr plane of the r-fold upscaled 4:2:0 frame from the low-resolution RGB
+    (Cc = 3) or RGBA (Cc = 4) frame, r = 2..4, in one launch (include/snnhip.h states the arithmetic)."""
+    d = RgbCbcrDesc(N, H, W, Cc, r, SITING.get(siting, siting), RANGE.get(range, range), kr, kb)
+    h = _P()
+    check(lib().snnhip_rgb_cbcr_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def rgb420_phases(r):
+    """rows of snnhip_bicubic_taps_rgb420's table: the output chroma pattern repeats every r / gcd(r, 2) samples"""
+    return r if r % 2 else r // 2
+
+
+def bicubic_taps_rgb420(r, siting="left", capacity=None):
+    """snnhip_bicubic_taps_rgb420 (host side only, no GPU): (weights float32 [P][4], base int32 [P]), P = 1, 3, 2 for r = 2, 3, 4; output P x' + p
+    of the upscaled frame's chroma grid reads low-resolution pixels S x' + base[p] - 1 .. S x' + base[p] + 2, S = 1, 2, 1."""
+    n = rgb420_phases(r) if 2 <= r <= 4 else 0
+    w = np.zeros((n, 4), np.float32)
+    base = (C.c_int * max(n, 1))()
+    check(lib().snnhip_bicubic_taps_rgb420(r, SITING.get(siting, siting), _fptr(w), base, w.size if capacity is None else capacity))
+    return w, np.array(base[:n], np.int32)
+
+
+def rgb_cbcr_coefficients(range="limited", kr=BT601[0], kb=BT601[1]):
+    """snnhip_rgb_cbcr_coefficients (host side only, no GPU): float32 (Coff, cbs, crs) of the full-range differences -> CbCr codes map."""
+    out = np.zeros(3, np.float32)
+    check(lib().snnhip_rgb_cbcr_coefficients(RANGE.get(range, range), kr, kb, _fptr(out), out.size))
     return out
 
 

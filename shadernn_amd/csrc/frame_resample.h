@@ -1,7 +1,8 @@
 // frame_resample.h -- the one definition of what the frame kernels around the luma model share (frame_colour.hip, frame_chroma.hip,
-// frame_yuv_rgb.hip): the Keys cubic and its phase, the tap-table filler behind the three snnhip_bicubic_taps* entry points,
-// the five-weight form of a table, the matrix and sample-format checks of the plan descs, the r x C launch dispatch, and on the device the quantiser,
-// the element of a run of dwords, the five-weight horizontal filter and the tile decode.  Loads, stores and lane geometry stay with each unit.
+// frame_yuv_rgb.hip, frame_rgb_cbcr.hip): the Keys cubic and its phase, the tap-table filler behind the four
+// snnhip_bicubic_taps* entry points, the five-weight form of a table, the matrix and sample-format checks of the plan descs, the r x C launch dispatch,
+// and on the device the quantiser, the element of a run of dwords, loads and stores of dword-aligned runs, the five-weight horizontal filter and the
+// tile decode.  Which bytes a lane loads and stores and its geometry stay with each unit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,9 +29,11 @@ inline double keys_cubic(double d) {
 // The phase: output sample R*x + p of an R-fold resampling reads source position x + s, s = (p + lead) / R - off.  `lead` is where the output sample
 // sits inside its own cell, `off` where the source sample sits inside its cell, both in units of the cell.  base = floor(s), taps at
 // x + base - 1 .. x + base + 2 with the Keys weights at distances 1 + t, t, 1 - t, 2 - t, t = s - base.
-inline void bicubic_phase_general(int R, int p, double lead, double off, int* base, double w[4]) {
+// ... and, for a grid whose step is not one source cell per R outputs, output sample p of a pattern that advances `step` / `den` source cells per output:
+// s = (step * p + lead) / den - off (bicubic_phase_general is step = 1, den = R)
+inline void bicubic_phase_ratio(int step, int den, int p, double lead, double off, int* base, double w[4]) {
 #pragma clang fp contract(off)
-    const double s = (p + lead) / R - off;
+    const double s = (step * p + lead) / den - off;
     const double i0 = std::floor(s);
     const double t = s - i0;
     *base = static_cast<int>(i0);
@@ -39,6 +42,7 @@ inline void bicubic_phase_general(int R, int p, double lead, double off, int* ba
     w[2] = keys_cubic(1.0 - t);
     w[3] = keys_cubic(2.0 - t);
 }
+inline void bicubic_phase_general(int R, int p, double lead, double off, int* base, double w[4]) { bicubic_phase_ratio(1, R, p, lead, off, base, w); }
 
 inline bool siting_ok(int siting) { return siting == SNNHIP_SITING_CENTRE || siting == SNNHIP_SITING_LEFT; }
 // where a chroma sample sits inside its cell: co-sited with the even luma column (left) or between the two (centre)
@@ -55,9 +59,12 @@ inline void bicubic_phase_sited(int r, int p, int siting, int* base, double w[4]
 // (X + 0.5) / R - 0.5 for centred chroma: lead = 0.5 either way.
 inline void bicubic_phase_420(int R, int p, int siting, int* base, double w[4]) { bicubic_phase_general(R, p, 0.5, siting_offset(siting), base, w); }
 
-// The table behind snnhip_bicubic_taps / _sited / _420 (`name` without the prefix): `phases` rows of four float weights and each row's base, for a
-// `phases`-fold resampling with (lead, off); `r` is the caller's upscale factor, the one the messages speak of.
-inline int fill_bicubic_taps(const char* name, int r, int phases, int siting, double lead, double off, float* weights, int* base, int capacity) {
+// The table behind snnhip_bicubic_taps / _sited / _420 / _rgb420 (`name` without the prefix): `phases` rows of four float weights and each row's base,
+// for a `phases`-fold resampling with (lead, off); `r` is the caller's upscale factor, the one the messages speak of.  The first three advance one
+// source cell per `phases` outputs and know bases -1 and 0 only; _rgb420 advances `step` / `den` cells per output (bicubic_phase_ratio) and reaches
+// base `maxBase` = 1.
+inline int fill_bicubic_taps(const char* name, int r, int phases, int siting, double lead, double off, float* weights, int* base, int capacity, int step = 1, int den = 0,
+                             int maxBase = 0) {
     SNNHIP_REQUIRE(weights && base, "%s: null argument", name);
     SNNHIP_REQUIRE(r >= 1 && r <= 4, "%s: r = %d (1..4)", name, r);
     SNNHIP_REQUIRE(siting_ok(siting), "%s: siting %d (SNNHIP_SITING_CENTRE or SNNHIP_SITING_LEFT)", name, siting);
@@ -65,8 +72,8 @@ inline int fill_bicubic_taps(const char* name, int r, int phases, int siting, do
     for (int p = 0; p < phases; ++p) {
         double w[4];
         int b = 0;
-        bicubic_phase_general(phases, p, lead, off, &b, w);
-        SNNHIP_REQUIRE(b == -1 || b == 0, "%s: phase %d of r = %d starts at %d", name, p, r, b);
+        bicubic_phase_ratio(step, den ? den : phases, p, lead, off, &b, w);
+        SNNHIP_REQUIRE(b >= -1 && b <= maxBase, "%s: phase %d of r = %d starts at %d", name, p, r, b);
         base[p] = b;
         for (int k = 0; k < 4; ++k) weights[4 * p + k] = static_cast<float>(w[k]);
     }
@@ -131,6 +138,52 @@ template <typename E>
 __device__ __forceinline__ unsigned frame_elem(const unsigned* w, int i) {
     constexpr int PER = 4 / static_cast<int>(sizeof(E)), BITS = 8 * static_cast<int>(sizeof(E));
     return (w[i / PER] >> (BITS * (i % PER))) & ((1u << BITS) - 1u);
+}
+
+// NW (1..4) dwords at an address that is only dword-aligned, as one access: a vector type whose alignment is lowered to 4, which global memory
+// takes at any width
+template <int NW>
+struct WordsOf;
+template <>
+struct WordsOf<1> {
+    typedef unsigned type __attribute__((aligned(4)));
+};
+template <>
+struct WordsOf<2> {
+    typedef unsigned type __attribute__((ext_vector_type(2), aligned(4)));
+};
+template <>
+struct WordsOf<3> {
+    typedef unsigned type __attribute__((ext_vector_type(3), aligned(4)));
+};
+template <>
+struct WordsOf<4> {
+    typedef unsigned type __attribute__((ext_vector_type(4), aligned(4)));
+};
+template <int NW>
+__device__ __forceinline__ void load_words(const void* p, unsigned* w) {
+    if constexpr (NW == 1) {
+        w[0] = *reinterpret_cast<const unsigned*>(p);
+    } else {
+        const typename WordsOf<NW>::type q = *reinterpret_cast<const typename WordsOf<NW>::type*>(p);
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w[k] = q[k];
+    }
+}
+// NW dwords (any number) to a dword-aligned address, four at a time
+template <int NW>
+__device__ __forceinline__ void store_words(void* p, const unsigned* w) {
+    if constexpr (NW > 4) {
+        store_words<4>(p, w);
+        store_words<NW - 4>(reinterpret_cast<unsigned*>(p) + 4, w + 4);
+    } else if constexpr (NW == 1) {
+        *reinterpret_cast<unsigned*>(p) = w[0];
+    } else {
+        typename WordsOf<NW>::type q;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) q[k] = w[k];
+        *reinterpret_cast<typename WordsOf<NW>::type*>(p) = q;
+    }
 }
 
 // One staged row v (PX + 4 pixels of C channels: two pixels of apron either side) to the lane's PHASES * PX output pixels: output pixel j reads

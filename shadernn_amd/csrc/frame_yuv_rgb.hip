@@ -35,52 +35,6 @@ struct YuvRgbParams {
     float wv[8][5]; // ... along a column (centred)
 };
 
-// NW (1..4) dwords at an address that is only dword-aligned, as one access: a vector type whose alignment is lowered to 4, which global memory
-// takes at any width
-template <int NW>
-struct WordsOf;
-template <>
-struct WordsOf<1> {
-    typedef unsigned type __attribute__((aligned(4)));
-};
-template <>
-struct WordsOf<2> {
-    typedef unsigned type __attribute__((ext_vector_type(2), aligned(4)));
-};
-template <>
-struct WordsOf<3> {
-    typedef unsigned type __attribute__((ext_vector_type(3), aligned(4)));
-};
-template <>
-struct WordsOf<4> {
-    typedef unsigned type __attribute__((ext_vector_type(4), aligned(4)));
-};
-template <int NW>
-__device__ __forceinline__ void load_words(const void* p, unsigned* w) {
-    if constexpr (NW == 1) {
-        w[0] = *reinterpret_cast<const unsigned*>(p);
-    } else {
-        const typename WordsOf<NW>::type q = *reinterpret_cast<const typename WordsOf<NW>::type*>(p);
-#pragma unroll
-        for (int k = 0; k < NW; ++k) w[k] = q[k];
-    }
-}
-// NW dwords (any number) to a dword-aligned address, four at a time
-template <int NW>
-__device__ __forceinline__ void store_words(void* p, const unsigned* w) {
-    if constexpr (NW > 4) {
-        store_words<4>(p, w);
-        store_words<NW - 4>(reinterpret_cast<unsigned*>(p) + 4, w + 4);
-    } else if constexpr (NW == 1) {
-        *reinterpret_cast<unsigned*>(p) = w[0];
-    } else {
-        typename WordsOf<NW>::type q;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) q[k] = w[k];
-        *reinterpret_cast<typename WordsOf<NW>::type*>(p) = q;
-    }
-}
-
 // raw[b * 2 + c] = chroma pixel (x0 - 2 + b, channel c) of the row at `row`.  WIDE: three aligned loads -- the lane's own dword and the aprons either
 // side (the row is dword-aligned, x0 >= 2 and x0 + CP + 2 <= W); otherwise elements, indices clamped to [0, W - 1] (x0 < W)
 template <int R, typename E, bool WIDE>

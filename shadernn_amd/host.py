@@ -22,6 +22,7 @@ SIGNATURES = {
     "snn_model_create7": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create8": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create9": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create10": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_upload_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_download_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u16": (C.c_int, [_P, _P]),
@@ -161,6 +162,11 @@ class VideoRgbIO(C.Structure):
                 ("kr", C.c_float), ("kb", C.c_float)]
 
 
+class EncodeIO(C.Structure):
+    """snn_encode_io (include/snn_c.h): RGB8 / RGBA8 frames in, an NV12 frame out around a luma-only model; the luma maps follow from the range."""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
+
+
 VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6)}  # name: (SNN_IO_NV12 / SNN_IO_NV12_16, maxval, shift)
 SITINGS = {"centre": 0, "left": 1}  # SNN_SITING_*
 VIDEO_RANGES = {"limited": 0, "full": 1}  # SNN_RANGE_*
@@ -191,11 +197,33 @@ class Model:
         video_out "RGB8" / "RGBA8" (with "NV12") or "RGB16" / "RGBA16" (with "P010") beside video (snn_model_create9): the frames go in as above and
         come back as packed full-range RGB -- output_frame / download_frame return uint8 / uint16 [batch x] rH x rW x C.  video_range "limited" /
         "full" is the stream's range and sets the luma plane's maps (in_means / in_norms / out_scale / out_offset are not used); kr, kb are the
-        stream's matrix (BT.601 by default, BT.709 is 0.2126 / 0.0722).  One launch behind the model's two converts: no chroma_up launch."""
+        stream's matrix (BT.601 by default, BT.709 is 0.2126 / 0.0722).  One launch behind the model's two converts: no chroma_up launch.
+        colour "RGB8" / "RGBA8" with video_out "NV12" (snn_model_create10): capture in, encoder out -- upload_frame takes the uint8 RGB frame
+        [batch x] H x W x C, output_frame / download_frame return the pair (y, cbcr) of the NV12 frame at r times the extent (r = 2..4, rH and rW
+        even): y from the model (video_range sets its output map: "limited" 16 + 219 x, "full" 255 x), cbcr [batch x] rH/2 x rW/2 x 2 from the
+        RGB frame in one launch behind the model (siting, kr, kb as above).  in_means / in_norms / out_scale / out_offset are not used."""
         self.h = _P()
         self.colour_channels = 0
         self.video = video
         self.video_out_channels = 0
+        self.encode = False
+        if colour is not None and video_out is not None:
+            assert video is None, "colour frames go in: video= names NV12 / P010 frames at the input"
+            assert colour in ("RGB8", "RGBA8"), "colour is \"RGB8\" or \"RGBA8\""
+            assert video_out == "NV12", "a colour frame leaves as video_out=\"NV12\""
+            assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
+            assert siting in SITINGS, "siting is \"left\" or \"centre\""
+            assert input_format is None and output_format is None, "colour frames replace input_format / output_format"
+            assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
+            channels = {"RGB8": 3, "RGBA8": 4}[colour]
+            self.frame_dtypes = (np.uint8, np.uint8)
+            io = EncodeIO(FRAME_FORMATS[colour], VIDEO_FORMATS["NV12"][0], SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
+            assert lib().snn_model_create10(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                            int(batch), C.byref(io), C.byref(self.h)) == 0
+            self.encode = True
+            self.batch = batch
+            self.in_shape = (h, w, channels) if batch == 1 else (batch, h, w, channels)
+            return
         if video_out is not None:
             assert video is not None, "video_out needs video=\"NV12\" or \"P010\""
             assert video_out in VIDEO_OUT_FORMATS, "video_out is one of %s" % sorted(VIDEO_OUT_FORMATS)
@@ -266,7 +294,7 @@ class Model:
         """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
-        if self.video and not self.video_out_channels:
+        if (self.video and not self.video_out_channels) or self.encode:
             return self._download_video(d[0], d[1])
         if self.colour_channels or self.video_out_channels:
             d = (d[0], d[1], self.colour_channels or self.video_out_channels)

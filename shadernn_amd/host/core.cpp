@@ -108,6 +108,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
                         cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset, frameIn && isFrame16Format(id.format),
                         frameOut && isFrame16Format(cp.outputFormat), cp.frameInShift, cp.frameOutMaxval, cp.frameOutShift);
         if (cp.colourChannels) hb->initColourIO(cp.colourChannels, cp.colourKr, cp.colourKb);
+        if (cp.encodeChannels) hb->initEncodeIO(cp.encodeChannels, cp.encodeSiting, cp.encodeRange, cp.colourKr, cp.colourKb);
         if (cp.videoDtype && cp.videoRgbChannels)
             hb->initVideoRgbIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoRgbChannels, cp.videoRange, cp.videoKr, cp.videoKb);
         else if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting);
@@ -139,6 +140,7 @@ snnhip_tensor* MixedInferenceCore::frameInput() const { return frameBackend ? fr
 snnhip_tensor* MixedInferenceCore::frameOutput() const { return frameBackend ? frameBackend->frameOutput() : nullptr; }
 snnhip_tensor* MixedInferenceCore::chromaInput() const { return frameBackend ? frameBackend->chromaInput() : nullptr; }
 snnhip_tensor* MixedInferenceCore::chromaOutput() const { return frameBackend ? frameBackend->chromaOutput() : nullptr; }
+bool MixedInferenceCore::encodeOutput() const { return frameBackend && frameBackend->encodeOutput(); }
 
 void MixedInferenceCore::run(RunParameters& rp) { // core.cpp:97-245
     SNN_ASSERT(rp.inputImages && rp.inputImages->size() > 0);

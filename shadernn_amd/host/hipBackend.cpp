@@ -67,6 +67,7 @@ HipBackend::~HipBackend() {
     if (chromaOutT) snnhip_tensor_free(chromaOutT);
     if (yuvRgbPlan) snnhip_plan_destroy(yuvRgbPlan);
     if (rgbOutT) snnhip_tensor_free(rgbOutT);
+    if (cbcrPlan) snnhip_plan_destroy(cbcrPlan);
 }
 
 void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
@@ -145,8 +146,22 @@ void HipBackend::initVideoRgbIO(int dtype, int maxval, int shift, int siting, in
     hipChk(snnhip_tensor_alloc(ctx, out[0], out[1], out[2], channels, dtype, &rgbOutT), "snnhip_tensor_alloc (RGB output frame)");
 }
 
+void HipBackend::initEncodeIO(int channels, int siting, int range, float kr, float kb) {
+    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == SNNHIP_U8 && snnhip_tensor_dtype(frameOutT) == SNNHIP_U8);
+    int in[4], out[4];
+    const int r = frameScale(frameInT, frameOutT, false, in, out);
+    if (r < 2 || out[1] % 2 || out[2] % 2) SNN_RIP("an NV12 output frame needs r = 2..4 and an even extent: %dx%d -> %dx%d", in[1], in[2], out[1], out[2]);
+    snnhip_rgb_luma_desc ld{in[0], in[1], in[2], channels, kr, kb};
+    hipChk(snnhip_rgb_luma_plan_create(ctx, &ld, &lumaPlan), "snnhip_rgb_luma_plan_create");
+    snnhip_rgb_cbcr_desc cd{in[0], in[1], in[2], channels, r, siting, range, kr, kb};
+    hipChk(snnhip_rgb_cbcr_plan_create(ctx, &cd, &cbcrPlan), "snnhip_rgb_cbcr_plan_create");
+    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1], in[2], channels, SNNHIP_U8, &colourInT), "snnhip_tensor_alloc (colour input frame)");
+    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1] / 2, out[2] / 2, 2, SNNHIP_U8, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
+}
+
 std::string HipBackend::describeVideo() const {
     char buf[320];
+    if (cbcrPlan && snnhip_plan_describe(cbcrPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
     if (yuvRgbPlan && snnhip_plan_describe(yuvRgbPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[rgb out] ") + buf + "\n";
     if (chromaPlan && snnhip_plan_describe(chromaPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
     return std::string();
@@ -164,6 +179,7 @@ void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
         hipChk(snnhip_plan_run_n(mergePlan, ins, 2, colourOutT), "snnhip_plan_run_n (luma + chroma -> colour frame)");
     }
     if (chromaPlan) hipChk(snnhip_plan_run(chromaPlan, chromaInT, chromaOutT), "snnhip_plan_run (chroma plane)");
+    if (cbcrPlan) hipChk(snnhip_plan_run(cbcrPlan, colourInT, chromaOutT), "snnhip_plan_run (colour frame -> chroma plane)");
     if (yuvRgbPlan) {
         const snnhip_tensor* ins[2] = {frameOutT, chromaInT};
         hipChk(snnhip_plan_run_n(yuvRgbPlan, ins, 2, rgbOutT), "snnhip_plan_run_n (luma + chroma plane -> RGB frame)");

@@ -121,7 +121,7 @@ public:
     // plan fills the model's input frame from the colour frame in runFrameIn, the merge plan builds the colour output frame from the model's output
     // frame and the colour frame in runFrameOut: two launches more on the context's stream, in front of and behind everything else of an inference.
     void initColourIO(int channels, float kr, float kb);
-    int colourLaunches() const { return lumaPlan ? 2 : 0; }
+    int colourLaunches() const { return (lumaPlan ? 1 : 0) + (mergePlan ? 1 : 0); }
     std::string describeColour() const; // one line per extra launch (empty without colour frames)
     // NV12 / P010 video frames around a luma-only model (CreationParameters::videoDtype): called after initFrameIO with R8 / R16 frames at both
     // ends.  The luma plane IS the model's frame; the chroma plan upsamples the CbCr plane [n][H/2][W/2][2] to [n][rH/2][rW/2][2] in runFrameOut,
@@ -130,7 +130,12 @@ public:
     // ... or to packed RGB (CreationParameters::videoRgbChannels): the yuv_rgb plan builds the RGB / RGBA output frame [n][rH][rW][channels] from the
     // model's output luma frame and the ORIGINAL CbCr plane in runFrameOut, in the chroma launch's place (no chroma plan, no upscaled chroma plane)
     void initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb);
-    int videoLaunches() const { return chromaPlan || yuvRgbPlan ? 1 : 0; }
+    // RGB8 / RGBA8 frames in, an NV12 frame out (CreationParameters::encodeChannels): called after initFrameIO with R8 frames at both ends.  The luma
+    // plan of initColourIO fills the model's input frame in runFrameIn; the model's output frame IS the NV12 frame's luma plane; the rgb_cbcr plan
+    // builds its chroma plane [n][rH/2][rW/2][2] from the colour input frame in runFrameOut (no merge plan, no colour output frame)
+    void initEncodeIO(int channels, int siting, int range, float kr, float kb);
+    bool encodeOutput() const { return cbcrPlan != nullptr; }
+    int videoLaunches() const { return chromaPlan || yuvRgbPlan || cbcrPlan ? 1 : 0; }
     std::string describeVideo() const; // one line for the extra launch (empty without video frames)
     snnhip_tensor* chromaInput() const { return chromaInT; }
     snnhip_tensor* chromaOutput() const { return chromaOutT; }
@@ -147,6 +152,7 @@ private:
     snnhip_tensor *chromaInT = nullptr, *chromaOutT = nullptr;  // owned, SNNHIP_U8 / SNNHIP_U16 [n][H/2][W/2][2] / [n][rH/2][rW/2][2]
     snnhip_plan* yuvRgbPlan = nullptr;                          // owned
     snnhip_tensor* rgbOutT = nullptr;                           // owned, SNNHIP_U8 / SNNHIP_U16 [n][rH][rW][3 or 4]
+    snnhip_plan* cbcrPlan = nullptr;                            // owned (its output is chromaOutT, its input colourInT)
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

@@ -86,6 +86,10 @@ public:
         // original CbCr plane to an RGB / RGBA frame (videoRange SNNHIP_RANGE_*, matrix videoKr / videoKb)
         int videoRgbChannels = 0, videoRange = 0;
         float videoKr = 0.299f, videoKb = 0.114f;
+        // HIP extension: RGB8 / RGBA8 frames in, an NV12 frame out around a luma-only model (snn_model_create10).  encodeChannels 3 / 4: run() puts
+        // snnhip_rgb_luma_plan_create's launch in front of the model, as colourChannels does, and snnhip_rgb_cbcr_plan_create's behind it, from the
+        // colour input frame to the output frame's chroma plane (encodeSiting SNNHIP_SITING_*, encodeRange SNNHIP_RANGE_*, matrix colourKr / colourKb)
+        int encodeChannels = 0, encodeSiting = 1, encodeRange = 0;
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const std::string& modelFileName, const dp::ShaderGenOptions& options,
@@ -101,6 +105,7 @@ public:
     snnhip_tensor* frameOutput() const;
     snnhip_tensor* chromaInput() const; // the CbCr planes of a video model (snn_model_create8), null otherwise
     snnhip_tensor* chromaOutput() const;
+    bool encodeOutput() const; // the output is the NV12 frame of snn_model_create10: frameOutput() its luma plane, chromaOutput() its CbCr plane
 
 private:
     GpuContext* context;

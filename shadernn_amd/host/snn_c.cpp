@@ -104,10 +104,11 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
 
 // snn_model_create6 / 7 / 8: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends, `video`
 // (snn_model_create8) for NV12 / P010 frames around a model that `io` gives R8 / R16 frames, `videoRgb` (snn_model_create9, beside `video`) for an RGB
-// frame at the output instead of NV12 / P010
+// frame at the output instead of NV12 / P010, `encode` (snn_model_create10) for RGB8 / RGBA8 frames in and an NV12 frame out around a model that `io`
+// gives R8 frames
 static int createModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
                        int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out, const snn_video_io* video = nullptr,
-                       const snn_video_rgb_io* videoRgb = nullptr) {
+                       const snn_video_rgb_io* videoRgb = nullptr, const snn_encode_io* encode = nullptr) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
     ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
     if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
@@ -138,14 +139,24 @@ static int createModel(const char* json_path, int device, int in_w, int in_h, in
         cp.captureGraph = capture_graph != 0;
         cp.outputFormat = sgo.desiredOutputFormat;
         cp.halfTensors = half;
-        if (colour || video) { // the model must be luma-only: one channel out, at 1..4 times the input's extent (refused here, before anything is built on the device)
+        if (colour || video || encode) { // the model must be luma-only: one channel out, at 1..4 times the input's extent (refused here, before anything is built on the device)
             const auto& od = cp.layers.back()->outputDesc;
             const uint32_t r = od.width / static_cast<uint32_t>(in_w);
             if (od.channels != 1 || r < 1 || r > 4 || od.width != r * static_cast<uint32_t>(in_w) || od.height != r * static_cast<uint32_t>(in_h)) {
                 snn_model_destroy(m);
                 return -1;
             }
-            if (colour) {
+            if (encode) { // the output frame is 4:2:0: r = 2..4 (r = 1 would decimate the chroma grid) and an even extent
+                if (r < 2 || (r * static_cast<uint32_t>(in_w)) % 2 || (r * static_cast<uint32_t>(in_h)) % 2) {
+                    snn_model_destroy(m);
+                    return -1;
+                }
+                cp.encodeChannels = encode->in_format & 0xff;
+                cp.encodeSiting = encode->siting;
+                cp.encodeRange = encode->range;
+                cp.colourKr = encode->kr;
+                cp.colourKb = encode->kb;
+            } else if (colour) {
                 cp.colourChannels = colour->format & 0xff;
                 cp.colourKr = colour->kr;
                 cp.colourKb = colour->kb;
@@ -266,6 +277,27 @@ int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int
     return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, &video, io);
 }
 
+int snn_model_create10(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_encode_io* io, snn_model** out) {
+    if (!io || (io->in_format != SNN_IO_RGB8 && io->in_format != SNN_IO_RGBA8) || io->out_format != SNN_IO_NV12 || in_c != 1 || batch < 1) return -1;
+    if (io->siting != SNN_SITING_CENTRE && io->siting != SNN_SITING_LEFT) return -1;
+    if (io->range != SNN_RANGE_LIMITED && io->range != SNN_RANGE_FULL) return -1;
+    if (!(io->kr > 0.0f && io->kb > 0.0f && io->kr + io->kb < 1.0f)) return -1;
+    // (whether r * in_w and r * in_h are even is known once the model file gives r: createModel refuses an odd one before any plan is made)
+    // the luma maps follow from the range: full-range luma in (rgb_luma), the range's luma codes out
+    const bool limited = io->range == SNN_RANGE_LIMITED;
+    snn_frame_io2 io2{};
+    io2.in_format = io2.out_format = SNN_IO_R8;
+    for (int c = 0; c < 4; ++c) {
+        io2.in_means[c] = 0.0f;
+        io2.in_norms[c] = 1.0f / 255.0f;
+        io2.out_scale[c] = limited ? 219.0f : 255.0f;
+        io2.out_offset[c] = limited ? 16.0f : 0.0f;
+    }
+    io2.out_maxval = 65535; // (as snn_model_create5)
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, nullptr, nullptr, io);
+}
+
 // one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame
 static int movePlane(snnhip_tensor* t, int batch, char* frames, size_t stride, size_t offset, bool upload) {
     const size_t total = snnhip_tensor_bytes(t), plane = total / static_cast<size_t>(batch);
@@ -314,6 +346,7 @@ int snn_model_upload_frame_u8(snn_model* m, const unsigned char* nhwc) {
 int snn_model_download_frame_u8(snn_model* m, unsigned char* nhwc) {
     snnhip_tensor* t = m && nhwc ? m->core->frameOutput() : nullptr;
     if (t && snnhip_tensor_dtype(t) != SNNHIP_U8) return -1;
+    if (t && m->core->encodeOutput()) return -1; // (an NV12 frame: snn_model_download_frame_nv12)
     return t && snnhip_tensor_download_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
 }
 

@@ -62,6 +62,16 @@ for nv12, nv12_rgb and rgb8, the kernels of the launch trace, and the yuv_rgb ke
 profiles/espcn_video_rgb_frames.json holds the runs under the keys <format>_<out>_scale<r>.
 
     python tools/bench_frames.py --video NV12 --video-out RGB8 --scale 2
+
+--colour RGB8 | RGBA8 --video-out NV12 (with any --scale): capture in, encoder out.  Five forms in the same mirrored
+alternation: grey (the 8-bit chain on a luma plane: two launches), rgb_nv12 (the luma plan, the chain with the range's output map, the rgb_cbcr
+launch from the RGB frame to the chroma plane of the upscaled frame: four launches, an NV12 frame out), rgb_cbcr (that launch alone), copy (one
+hipMemcpyDtoDAsync that moves as many bytes through HBM as the rgb_cbcr kernel has to) and rgb8 (the RGB8 -> RGB8 colour step of --colour: four
+launches).  Device step per form with the spread over the rounds, frames/s including one frame's H2D + D2H for grey, rgb_nv12 and rgb8 (an NV12
+frame comes back as 1.5 bytes per pixel, an RGB8 frame as 3), the kernels of the launch trace, and the rgb_cbcr kernel's bytes/s beside the copy's.
+profiles/espcn_rgb_nv12_frames.json holds the runs under the keys <format>_nv12_scale<r>.
+
+    python tools/bench_frames.py --colour RGB8 --video-out NV12 --scale 2
 """
 import argparse
 import json
@@ -613,6 +623,139 @@ def main_video_rgb(a):
     ctx.close()
 
 
+def main_rgb_nv12(a):
+    """--colour ... --video-out NV12: grey / rgb_nv12 / rgb_cbcr / copy / rgb8."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R, Cc = a.scale, {"RGB8": 3, "RGBA8": 4}[a.colour]
+    scale, off = (219.0, 16.0) if a.range == "limited" else (255.0, 0.0)  # the output map snn_model_create10 derives from the range
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    assert (R * H) % 2 == 0 and (R * W) % 2 == 0, "the 4:2:0 output frame has even extents"
+    rng = np.random.default_rng(1)
+    rgb = rng.integers(0, 256, size=(1, H, W, Cc), dtype=np.uint8)
+    y_h = rng.integers(0, 256, size=(1, H, W, 1), dtype=np.uint8)
+
+    def chain_for(first, last_of):
+        layers, shape = [], (1, H, W, 1)
+        for layer in net["layers"]:
+            p = _layer_plan(ctx, layer, shape)
+            layers.append(p)
+            shape = p.out_shape()
+        chain = capi.chain_plan(ctx, [first] + layers + [last_of(shape)])
+        assert chain.num_steps() == 2, chain.describe()
+        return chain, shape
+
+    enc, shape = chain_for(capi.u8_in_plan(ctx, 1, H, W, 1, (0, 0, 0, 0), (1 / 255.0, 1, 1, 1)), lambda sh: capi.u8_out_plan(ctx, *sh, (scale, 0, 0, 0), (off, 0, 0, 0)))
+    chain8, _ = chain_for(capi.u8_in_plan(ctx, 1, H, W, 1, (127.5, 0, 0, 0), (1 / 127.5, 1, 1, 1)), lambda sh: capi.u8_out_plan(ctx, *sh, (127.5, 0, 0, 0), (127.5, 0, 0, 0)))
+    luma, merge = capi.rgb_luma_plan(ctx, 1, H, W, Cc), capi.ycc_merge_plan(ctx, 1, H, W, Cc, R)
+    cbcr = capi.rgb_cbcr_plan(ctx, 1, H, W, Cc, R, a.siting, a.range)
+    cshape, oshape = (1, R * H // 2, R * W // 2, 2), (1, R * H, R * W, Cc)
+    t_rgb, t_y = capi.Tensor.from_numpy(ctx, rgb, dtype=capi.U8), capi.Tensor.from_numpy(ctx, y_h, dtype=capi.U8)
+    t_luma, t_yhi, t_chi = capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8), capi.Tensor(ctx, *shape, dtype=capi.U8), capi.Tensor(ctx, *cshape, dtype=capi.U8)
+    t_yhi8, t_out = capi.Tensor(ctx, *shape, dtype=capi.U8), capi.Tensor(ctx, *oshape, dtype=capi.U8)
+    cbcr_bytes = int(cbcr.cost()[1])
+    half = cbcr_bytes // 2
+    t_src, t_dst = capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8)
+    t_src.upload_u8(np.random.default_rng(3).integers(0, 256, size=half, dtype=np.uint8))
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+
+    def run_grey():
+        chain8.run(t_y, t_yhi8)
+
+    def run_rgb_nv12():
+        luma.run(t_rgb, t_luma)
+        enc.run(t_luma, t_yhi)
+        cbcr.run(t_rgb, t_chi)
+
+    def run_rgb_cbcr():
+        cbcr.run(t_rgb, t_chi)
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(t_dst.data_ptr(), t_src.data_ptr(), half, stream)
+        assert rc == 0, rc
+
+    def run_rgb8():
+        luma.run(t_rgb, t_luma)
+        chain8.run(t_luma, t_yhi8)
+        merge.run([t_yhi8, t_rgb], t_out)
+
+    forms = {"grey": run_grey, "rgb_nv12": run_rgb_nv12, "rgb_cbcr": run_rgb_cbcr, "copy": run_copy, "rgb8": run_rgb8}
+    yhi_h, chi_h, out_h = np.empty(shape, np.uint8), np.empty(cshape, np.uint8), np.empty(oshape, np.uint8)
+    io = {"grey": ([(t_y, y_h)], [(t_yhi8, yhi_h)]), "rgb_nv12": ([(t_rgb, rgb)], [(t_yhi, yhi_h), (t_chi, chi_h)]), "rgb8": ([(t_rgb, rgb)], [(t_out, out_h)])}
+    for f in forms.values():
+        for _ in range(a.warmup):
+            f()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {k_: [] for k_ in forms}
+    e2e = {k_: [] for k_ in io}
+    order = list(forms) + list(forms)[::-1]  # mirrored: A B C D E E D C B A
+    for _ in range(a.rounds):
+        for k_ in order:
+            timer.start()
+            for _ in range(a.iters):
+                forms[k_]()
+            timer.stop()
+            dev[k_].append(timer.elapsed_ms() / a.iters)
+    for _ in range(a.rounds):
+        for k_ in list(io) + list(io)[::-1]:
+            ups, downs = io[k_]
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                for t, h in ups:
+                    capi.check(capi.lib().snnhip_tensor_upload_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+                forms[k_]()
+                for t, h in downs:
+                    capi.check(capi.lib().snnhip_tensor_download_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+            e2e[k_].append((time.perf_counter() - t0) * 1e3 / a.iters)
+    out = {"frame": "%dx%d -> %dx%d" % (H, W, R * H, R * W), "scale": R, "colour": a.colour, "video_out": a.video_out, "siting": a.siting, "range": a.range,
+           "rounds": a.rounds, "iters": a.iters}
+    for k_ in forms:
+        d = statistics.median(dev[k_])
+        out[k_] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[k_]), 4), "device_ms_max": round(max(dev[k_]), 4),
+                   "device_spread": round((max(dev[k_]) - min(dev[k_])) / d, 4)}
+        if k_ in io:
+            e = statistics.median(e2e[k_])
+            out[k_].update({"e2e_ms_median": round(e, 4), "e2e_ms_min": round(min(e2e[k_]), 4), "e2e_ms_max": round(max(e2e[k_]), 4), "e2e_frames_per_s": round(1e3 / e, 1),
+                            "io_bytes_per_frame": int(sum(h.nbytes for _, h in io[k_][0]) + sum(h.nbytes for _, h in io[k_][1]))})
+    out["grey"]["steps"] = [chain8.step_describe(i) for i in range(2)]
+    out["rgb_nv12"]["steps"] = [luma.describe()] + [enc.step_describe(i) for i in range(2)] + [cbcr.describe()]
+    out["rgb8"]["steps"] = [luma.describe()] + [chain8.step_describe(i) for i in range(2)] + [merge.describe()]
+    for k_ in ("grey", "rgb_nv12", "rgb_cbcr", "rgb8"):  # the launch trace: per-kernel times of each form (a copy is no kernel of the library)
+        capi.trace_begin()
+        for _ in range(a.iters):
+            forms[k_]()
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        out[k_]["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                               "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+    out["device_rgb_nv12_over_grey"] = round(out["rgb_nv12"]["device_ms_median"] / out["grey"]["device_ms_median"], 4)
+    out["device_rgb_nv12_over_rgb8"] = round(out["rgb_nv12"]["device_ms_median"] / out["rgb8"]["device_ms_median"], 4)
+    out["e2e_fps_rgb_nv12_over_rgb8"] = round(out["rgb_nv12"]["e2e_frames_per_s"] / out["rgb8"]["e2e_frames_per_s"], 4)
+    traced = [it for it in out["rgb_cbcr"]["kernels"] if it["function"] and "rgb_cbcr" in it["function"]]
+    cbcr_us = traced[0]["us_per_launch"] if traced else 1e3 * out["rgb_cbcr"]["device_ms_median"]
+    copy_us = 1e3 * out["copy"]["device_ms_median"]
+    out["rgb_cbcr_vs_copy"] = {"rgb_cbcr_hbm_bytes": cbcr_bytes, "rgb_cbcr_us_per_launch_traced": cbcr_us, "rgb_cbcr_tbs_traced": round(cbcr_bytes / (cbcr_us * 1e-6) / 1e12, 3),
+                               "rgb_cbcr_tbs_event_timed_loop": round(cbcr_bytes / (out["rgb_cbcr"]["device_ms_median"] * 1e-3) / 1e12, 3),
+                               "copy_bytes_each_way": half, "copy_hbm_bytes": 2 * half, "copy_us": round(copy_us, 2),
+                               "copy_tbs": round(2 * half / (copy_us * 1e-6) / 1e12, 3)}
+    out["rgb_cbcr_vs_copy"]["rgb_cbcr_over_copy_rate"] = round(out["rgb_cbcr_vs_copy"]["rgb_cbcr_tbs_event_timed_loop"] / out["rgb_cbcr_vs_copy"]["copy_tbs"], 4)
+    print(json.dumps(out, indent=1))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
@@ -620,7 +763,8 @@ def main():
     ap.add_argument("--bits", type=int, default=0, choices=[0, 10, 12, 16], help="also time 16-bit frames of this bit depth, folded and as separate launches")
     ap.add_argument("--colour", choices=["RGB8", "RGBA8"], default=None, help="colour frames around the luma chain: r8, colour, the merge launch alone and a device copy of its bytes")
     ap.add_argument("--video", choices=["NV12", "P010"], default=None, help="4:2:0 video frames around the luma chain: grey, video, the chroma launch alone, a device copy of its bytes and the RGB8 colour step")
-    ap.add_argument("--video-out", choices=["RGB8", "RGBA8"], default=None, help="with --video: packed RGB / RGBA out of the yuv_rgb launch (16-bit containers for P010) beside the NV12 step")
+    ap.add_argument("--video-out", choices=["RGB8", "RGBA8", "NV12"], default=None,
+                    help="with --video: packed RGB / RGBA out of the yuv_rgb launch (16-bit containers for P010) beside the NV12 step; NV12 with --colour: an NV12 frame out of the rgb_cbcr launch")
     ap.add_argument("--range", choices=["limited", "full"], default="limited", help="the stream's range with --video-out")
     ap.add_argument("--siting", choices=["left", "centre"], default="left", help="horizontal chroma siting of --video")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
@@ -632,6 +776,9 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.video_out == "NV12":
+        assert a.colour and not a.video, "--video-out NV12 goes with --colour RGB8 | RGBA8"
+        return main_rgb_nv12(a)
     if a.video and a.video_out:
         return main_video_rgb(a)
     if a.video:
