@@ -159,6 +159,25 @@ typedef struct snn_encode_io {
 } snn_encode_io;
 int snn_model_create10(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_encode_io* io, snn_model** out);
+/* NV12 / P010 frames to ANY output size behind a luma-only model: the model runs at its own factor r, then the frame is resampled down to
+ * out_w x out_h on the device (720p to 1080p is the x2 model, then 3/4).  Through a struct and an entry point of their own: every earlier struct and
+ * entry point keeps its layout and behaviour.  `video` is snn_model_create8's struct and the model is built exactly as snn_model_create8 builds it,
+ * so ESPCN stays its two fused kernels with folded ends (the fp16 opt-in works too).  Two launches sit behind the model's on the same stream and
+ * inside the recorded graph with capture_graph (they count towards SNN_GRAPH_MIN_LAUNCHES), four in all: snnhip_plane_fit_plan_create with C = 1
+ * from the model's output luma frame rH x rW to out_h x out_w, and with C = 2 from the ORIGINAL chroma plane H/2 x W/2 to out_h/2 x out_w/2 with
+ * the stream's siting (include/snnhip.h states the arithmetic).  There is no chroma_up launch and no r-fold chroma plane.
+ * snn_model_upload_frame_nv12 is unchanged; snn_model_download_frame_nv12 returns `batch` frames of out_h*out_w + (out_h/2)*out_w elements;
+ * snn_model_describe lists both launches.  Returns -1, before anything is built on the device, for a null struct, for what snn_model_create8
+ * refuses, for an out_w or out_h that is odd or below 2 and for out_w / in_w or out_h / in_h outside [1/2, 4]; and, once the model file gives r,
+ * for an output larger than r * in or smaller than r * in / 2 on either axis (the logged message names r and says which r would fit).
+ * Not offered: RGB output at a fitted size, fitted RGB8 colour frames, grey frames (the plan itself takes them: snnhip_plane_fit_plan_create),
+ * ratios below 1/2.  The reference has nothing for this: its vendored libyuv scales planes on the CPU with box / bilinear filters. */
+typedef struct snn_fit_io {
+    snn_video_io video;
+    int out_w, out_h;
+} snn_fit_io;
+int snn_model_create11(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_fit_io* io, snn_model** out);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

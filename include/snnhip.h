@@ -524,6 +524,42 @@ int snnhip_rgb_cbcr_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* des
 int snnhip_bicubic_taps_rgb420(int r, int siting, float* weights, int* base, int capacity);
 /* host only, no context: out[0..2] = Coff, cbs, crs of the matrix above (capacity >= 3 floats) */
 int snnhip_rgb_cbcr_coefficients(int range, float kr, float kb, float* out, int capacity);
+
+/* A plane resampled to any size between half and four times its own, each axis with its own ratio: what brings the r-fold frame of the luma model
+ * (and the original chroma plane beside it) to the size a pipeline asks for -- 720p to 1080p is the x2 model, then 3/4.  The plans above change a
+ * frame's size by the model's factor only.  DESIGN.md section 4.18.  The contract, stated once:
+ *   Shapes: the input is a plane [N][H][W][C] of dtype SNNHIP_U8 or SNNHIP_U16, C = 1 (a luma plane, a grey frame, one plane of a planar chroma
+ *     format) or C = 2 (interleaved CbCr); the output is [N][OH][OW][C] of the same dtype.  Channels never mix.  Values are float(u >> shift), maxval
+ *     and shift as for chroma_up (maxval <= 4095).
+ *   Phase: separable, each axis on its own.  Along an axis with I inputs and O outputs, output X reads source position s = (X + lead) I / O - off.
+ *     The vertical axis, and a horizontal axis with SNNHIP_SITING_CENTRE, use lead = off = 1/2 (aligned centres; a luma plane always does); a
+ *     horizontal axis with SNNHIP_SITING_LEFT uses lead = off = 1/4: the output is a chroma grid of the same siting, as in chroma_up.  In integers,
+ *     so that every implementation gets the same base: a = 4 lead (2 or 1), Nn = (4X + a) I - a O, D = 4 O, base = floor(Nn / D),
+ *     t = (Nn - base D) / D.
+ *   Weights: eight taps at base - 3 .. base + 4, tap k at distance |k - 3 - t|, weight keys_cubic(distance * f) with the Keys cubic of the plans
+ *     above (a = -0.5) and f = min(O / I, 1): the kernel is stretched when shrinking (the anti-aliasing low-pass) and is the plain four-tap cubic
+ *     when enlarging, where the outer four weights are exactly 0.  The eight are summed in ascending tap order in double, divided by that sum and
+ *     rounded to float.  Source indices clamp to the plane (replicate edge).  fp32 accumulation, vertical then horizontal;
+ *     q = unsigned(clamp(rint(.), 0, maxval)) << shift, ties to even.
+ *   Ratios: 1/2 <= O / I <= 4 on each axis (eight taps are exactly enough at 1/2); everything else is refused.
+ *   Consequences: O == I on an axis gives base = X, t = 0 and weights (0, 0, 0, 1, 0, 0, 0, 0): that axis copies, and with both the output is the
+ *     input with the bits below `shift` cleared.  For O = r I the inner four weights are snnhip_bicubic_taps_sited's row of phase X mod r (to one
+ *     float ulp: the division by a sum that is 1 to 1e-16) with the same bases.  A constant plane stays constant.  In fp32 the value in front of
+ *     the rounding stays within 4.6e-5 / 2.1e-4 / 7.3e-4 (8 / 10 / 12 bits) of a float64 evaluation.
+ * Plan creation returns SNNHIP_E_INVALID with a message starting "plane_fit desc" for C outside {1, 2}, a ratio outside [1/2, 4] on either axis (the
+ * message names the axis and both extents), bad dims, and dtype, maxval, shift and siting as chroma_up does; snnhip_plan_run for a tensor of another
+ * dtype or shape at either end.  snnhip_plan_describe: "plane_fit_u8 c=2 1440x2560->1080x1920 siting=left tile=22x128 taps=8 ... kernel=
+ * plane_fit_kernel" (the tile in output pixels).  snnhip_plan_cost counts the input once and the output once.
+ * Not built: RGB output at a fitted size, fitted RGB8 colour frames, ratios below 1/2 (they need more than eight taps); the host mirror
+ * (include/snn_c.h, snn_model_create11) puts this plan behind NV12 / P010 models only, grey frames go through the plan itself.  The reference has
+ * nothing for this: the libyuv it vendors scales planes on the CPU with box / bilinear filters. */
+typedef struct { int N, H, W, C; int OH, OW; int dtype; int maxval, shift; int siting; } snnhip_plane_fit_desc;
+int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run */
+/* host only, no context: the table of one axis with `in` inputs and `out` outputs: weights [out][8] (capacity >= 8 * out floats) and base [out]
+ * ints; output X reads in[clamp(base[X] - 3 + k)] with weights[X][k], k = 0..7.  The plan builds its two tables with this function (the vertical
+ * one with SNNHIP_SITING_CENTRE) and keeps them in device memory.  SNNHIP_E_INVALID with a message for a ratio outside [1/2, 4], a null pointer,
+ * too little room and an unknown siting. */
+int snnhip_fit_taps(int in, int out, int siting, float* weights, int* base, int capacity);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

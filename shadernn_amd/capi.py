@@ -117,6 +117,11 @@ class RgbCbcrDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("r", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
 
 
+class PlaneFitDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("OH", C.c_int), ("OW", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int),
+                ("siting", C.c_int)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -202,6 +207,8 @@ SIGNATURES = {
     "snnhip_rgb_cbcr_plan_create": (C.c_int, [_P, C.POINTER(RgbCbcrDesc), C.POINTER(_P)]),
     "snnhip_bicubic_taps_rgb420": (C.c_int, [C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_rgb_cbcr_coefficients": (C.c_int, [C.c_int, C.c_float, C.c_float, _FP, C.c_int]),
+    "snnhip_plane_fit_plan_create": (C.c_int, [_P, C.POINTER(PlaneFitDesc), C.POINTER(_P)]),
+    "snnhip_fit_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -834,6 +841,27 @@ def rgb_cbcr_coefficients(range="limited", kr=BT601[0], kb=BT601[1]):
     out = np.zeros(3, np.float32)
     check(lib().snnhip_rgb_cbcr_coefficients(RANGE.get(range, range), kr, kb, _fptr(out), out.size))
     return out
+
+
+def plane_fit_plan(ctx, N, H, W, Cc, OH, OW, dtype=U8, maxval=None, shift=0, siting="left"):
+    """plan.run([plane [N][H][W][Cc]], out [N][OH][OW][Cc]): a U8 / U16 plane (Cc = 1: luma or one planar chroma plane, 2: interleaved CbCr) resampled
+    to OH x OW, 1/2 <= OH / H, OW / W <= 4, with the stretched Keys cubic of include/snnhip.h; siting "left" or "centre" (the horizontal axis)."""
+    if maxval is None:
+        maxval = 255 if dtype == U8 else 1023
+    d = PlaneFitDesc(N, H, W, Cc, OH, OW, dtype, maxval, shift, SITING.get(siting, siting))
+    h = _P()
+    check(lib().snnhip_plane_fit_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def fit_taps(n_in, n_out, siting="centre", capacity=None):
+    """snnhip_fit_taps (host side only, no GPU): (weights float32 [n_out][8], base int32 [n_out]) of one axis; output X reads
+    in[clamp(base[X] - 3 + k)] with weights[X][k]."""
+    n = max(int(n_out), 0)
+    w = np.zeros((n, 8), np.float32)
+    base = (C.c_int * max(n, 1))()
+    check(lib().snnhip_fit_taps(n_in, n_out, SITING.get(siting, siting), _fptr(w), base, w.size if capacity is None else capacity))
+    return w, np.array(base[:n], np.int32)
 
 
 def deconv2d_plan(ctx, N, H, W, w_oihw, bias=None, stride=2, same=True, act="", leaky=0.0, bn=None):

@@ -23,6 +23,7 @@ SIGNATURES = {
     "snn_model_create8": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create9": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create10": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create11": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_upload_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_download_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u16": (C.c_int, [_P, _P]),
@@ -156,6 +157,11 @@ class VideoIO(C.Structure):
                 ("out_scale", C.c_float), ("out_offset", C.c_float)]
 
 
+class FitIO(C.Structure):
+    """snn_fit_io (include/snn_c.h): snn_video_io and the size the output frame is resampled to."""
+    _fields_ = [("video", VideoIO), ("out_w", C.c_int), ("out_h", C.c_int)]
+
+
 class VideoRgbIO(C.Structure):
     """snn_video_rgb_io (include/snn_c.h): NV12 / P010 frames in, RGB / RGBA frames out around a luma-only model; the luma maps follow from the range."""
     _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("maxval", C.c_int), ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int),
@@ -180,7 +186,7 @@ class Model:
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
                  out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114, video=None,
-                 siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited"):
+                 siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited", out_size=None):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
         output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
@@ -201,12 +207,17 @@ class Model:
         colour "RGB8" / "RGBA8" with video_out "NV12" (snn_model_create10): capture in, encoder out -- upload_frame takes the uint8 RGB frame
         [batch x] H x W x C, output_frame / download_frame return the pair (y, cbcr) of the NV12 frame at r times the extent (r = 2..4, rH and rW
         even): y from the model (video_range sets its output map: "limited" 16 + 219 x, "full" 255 x), cbcr [batch x] rH/2 x rW/2 x 2 from the
-        RGB frame in one launch behind the model (siting, kr, kb as above).  in_means / in_norms / out_scale / out_offset are not used."""
+        RGB frame in one launch behind the model (siting, kr, kb as above).  in_means / in_norms / out_scale / out_offset are not used.
+        out_size (w, h) beside video alone (snn_model_create11): the NV12 / P010 frame comes back at that size, both even, between half and all of
+        r times the input on each axis -- the model's luma frame and the original chroma plane resampled on the device, two launches behind the
+        model's (no chroma launch); output_frame / download_frame return the pair (y, cbcr) at h x w and h/2 x w/2."""
         self.h = _P()
         self.colour_channels = 0
         self.video = video
         self.video_out_channels = 0
         self.encode = False
+        self.out_size = None
+        assert out_size is None or (video is not None and video_out is None and colour is None), "out_size fits an NV12 / P010 frame: it goes with video= alone"
         if colour is not None and video_out is not None:
             assert video is None, "colour frames go in: video= names NV12 / P010 frames at the input"
             assert colour in ("RGB8", "RGBA8"), "colour is \"RGB8\" or \"RGBA8\""
@@ -253,8 +264,14 @@ class Model:
             dt = np.uint8 if fmt == 0x201 else np.uint16
             self.frame_dtypes = (dt, dt)
             io = VideoIO(fmt, maxval, shift, SITINGS[siting], in_means[0], in_norms[0], out_scale[0], out_offset[0])
-            assert lib().snn_model_create8(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                           int(batch), C.byref(io), C.byref(self.h)) == 0
+            if out_size is not None:
+                fit = FitIO(io, int(out_size[0]), int(out_size[1]))
+                assert lib().snn_model_create11(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half),
+                                                int(capture_graph), int(batch), C.byref(fit), C.byref(self.h)) == 0
+                self.out_size = (int(out_size[0]), int(out_size[1]))
+            else:
+                assert lib().snn_model_create8(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                               int(batch), C.byref(io), C.byref(self.h)) == 0
             self.batch = batch
             self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
             return
@@ -294,6 +311,8 @@ class Model:
         """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
+        if self.out_size is not None:
+            return self._download_video(self.out_size[1], self.out_size[0])
         if (self.video and not self.video_out_channels) or self.encode:
             return self._download_video(d[0], d[1])
         if self.colour_channels or self.video_out_channels:

@@ -111,6 +111,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         if (cp.encodeChannels) hb->initEncodeIO(cp.encodeChannels, cp.encodeSiting, cp.encodeRange, cp.colourKr, cp.colourKb);
         if (cp.videoDtype && cp.videoRgbChannels)
             hb->initVideoRgbIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoRgbChannels, cp.videoRange, cp.videoKr, cp.videoKb);
+        else if (cp.videoDtype && cp.fitW) hb->initVideoFitIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.fitW, cp.fitH);
         else if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting);
         frameBackend = hb;
     }

@@ -68,6 +68,9 @@ HipBackend::~HipBackend() {
     if (yuvRgbPlan) snnhip_plan_destroy(yuvRgbPlan);
     if (rgbOutT) snnhip_tensor_free(rgbOutT);
     if (cbcrPlan) snnhip_plan_destroy(cbcrPlan);
+    if (fitLumaPlan) snnhip_plan_destroy(fitLumaPlan);
+    if (fitChromaPlan) snnhip_plan_destroy(fitChromaPlan);
+    if (fitLumaT) snnhip_tensor_free(fitLumaT);
 }
 
 void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
@@ -146,6 +149,19 @@ void HipBackend::initVideoRgbIO(int dtype, int maxval, int shift, int siting, in
     hipChk(snnhip_tensor_alloc(ctx, out[0], out[1], out[2], channels, dtype, &rgbOutT), "snnhip_tensor_alloc (RGB output frame)");
 }
 
+void HipBackend::initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH) {
+    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
+    int in[4], out[4];
+    (void) frameScale(frameInT, frameOutT, true, in, out);
+    snnhip_plane_fit_desc ld{out[0], out[1], out[2], 1, outH, outW, dtype, maxval, shift, SNNHIP_SITING_CENTRE}; // a luma plane always uses centre
+    hipChk(snnhip_plane_fit_plan_create(ctx, &ld, &fitLumaPlan), "snnhip_plane_fit_plan_create (luma)");
+    snnhip_plane_fit_desc cd{in[0], in[1] / 2, in[2] / 2, 2, outH / 2, outW / 2, dtype, maxval, shift, siting};
+    hipChk(snnhip_plane_fit_plan_create(ctx, &cd, &fitChromaPlan), "snnhip_plane_fit_plan_create (chroma)");
+    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
+    hipChk(snnhip_tensor_alloc(ctx, out[0], outH, outW, 1, dtype, &fitLumaT), "snnhip_tensor_alloc (fitted luma plane)");
+    hipChk(snnhip_tensor_alloc(ctx, out[0], outH / 2, outW / 2, 2, dtype, &chromaOutT), "snnhip_tensor_alloc (fitted chroma plane)");
+}
+
 void HipBackend::initEncodeIO(int channels, int siting, int range, float kr, float kb) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == SNNHIP_U8 && snnhip_tensor_dtype(frameOutT) == SNNHIP_U8);
     int in[4], out[4];
@@ -161,6 +177,12 @@ void HipBackend::initEncodeIO(int channels, int siting, int range, float kr, flo
 
 std::string HipBackend::describeVideo() const {
     char buf[320];
+    if (fitLumaPlan && fitChromaPlan) {
+        std::string s;
+        if (snnhip_plan_describe(fitLumaPlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[luma fit] ") + buf + "\n";
+        if (snnhip_plan_describe(fitChromaPlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[chroma fit] ") + buf + "\n";
+        return s;
+    }
     if (cbcrPlan && snnhip_plan_describe(cbcrPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
     if (yuvRgbPlan && snnhip_plan_describe(yuvRgbPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[rgb out] ") + buf + "\n";
     if (chromaPlan && snnhip_plan_describe(chromaPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
@@ -180,6 +202,8 @@ void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
     }
     if (chromaPlan) hipChk(snnhip_plan_run(chromaPlan, chromaInT, chromaOutT), "snnhip_plan_run (chroma plane)");
     if (cbcrPlan) hipChk(snnhip_plan_run(cbcrPlan, colourInT, chromaOutT), "snnhip_plan_run (colour frame -> chroma plane)");
+    if (fitLumaPlan) hipChk(snnhip_plan_run(fitLumaPlan, frameOutT, fitLumaT), "snnhip_plan_run (luma frame -> fitted luma plane)");
+    if (fitChromaPlan) hipChk(snnhip_plan_run(fitChromaPlan, chromaInT, chromaOutT), "snnhip_plan_run (chroma plane -> fitted chroma plane)");
     if (yuvRgbPlan) {
         const snnhip_tensor* ins[2] = {frameOutT, chromaInT};
         hipChk(snnhip_plan_run_n(yuvRgbPlan, ins, 2, rgbOutT), "snnhip_plan_run_n (luma + chroma plane -> RGB frame)");

@@ -130,17 +130,20 @@ public:
     // ... or to packed RGB (CreationParameters::videoRgbChannels): the yuv_rgb plan builds the RGB / RGBA output frame [n][rH][rW][channels] from the
     // model's output luma frame and the ORIGINAL CbCr plane in runFrameOut, in the chroma launch's place (no chroma plan, no upscaled chroma plane)
     void initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb);
+    // ... or to an NV12 / P010 frame of any size between half and all of the model's output (CreationParameters::fitW / fitH): two plane_fit plans in
+    // runFrameOut, the model's output luma frame to [n][outH][outW][1] and the ORIGINAL CbCr plane to [n][outH/2][outW/2][2] (no chroma plan)
+    void initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH);
     // RGB8 / RGBA8 frames in, an NV12 frame out (CreationParameters::encodeChannels): called after initFrameIO with R8 frames at both ends.  The luma
     // plan of initColourIO fills the model's input frame in runFrameIn; the model's output frame IS the NV12 frame's luma plane; the rgb_cbcr plan
     // builds its chroma plane [n][rH/2][rW/2][2] from the colour input frame in runFrameOut (no merge plan, no colour output frame)
     void initEncodeIO(int channels, int siting, int range, float kr, float kb);
     bool encodeOutput() const { return cbcrPlan != nullptr; }
-    int videoLaunches() const { return chromaPlan || yuvRgbPlan || cbcrPlan ? 1 : 0; }
-    std::string describeVideo() const; // one line for the extra launch (empty without video frames)
+    int videoLaunches() const { return fitLumaPlan ? 2 : chromaPlan || yuvRgbPlan || cbcrPlan ? 1 : 0; }
+    std::string describeVideo() const; // one line for every extra launch (empty without video frames)
     snnhip_tensor* chromaInput() const { return chromaInT; }
     snnhip_tensor* chromaOutput() const { return chromaOutT; }
     snnhip_tensor* frameInput() const { return colourInT ? colourInT : frameInT; }
-    snnhip_tensor* frameOutput() const { return rgbOutT ? rgbOutT : colourOutT ? colourOutT : frameOutT; }
+    snnhip_tensor* frameOutput() const { return fitLumaT ? fitLumaT : rgbOutT ? rgbOutT : colourOutT ? colourOutT : frameOutT; }
 
 private:
     snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned
@@ -153,6 +156,8 @@ private:
     snnhip_plan* yuvRgbPlan = nullptr;                          // owned
     snnhip_tensor* rgbOutT = nullptr;                           // owned, SNNHIP_U8 / SNNHIP_U16 [n][rH][rW][3 or 4]
     snnhip_plan* cbcrPlan = nullptr;                            // owned (its output is chromaOutT, its input colourInT)
+    snnhip_plan *fitLumaPlan = nullptr, *fitChromaPlan = nullptr; // owned (the chroma plan runs chromaInT -> chromaOutT)
+    snnhip_tensor* fitLumaT = nullptr;                          // owned, SNNHIP_U8 / SNNHIP_U16 [n][outH][outW][1]
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

@@ -85,6 +85,9 @@ public:
         // ... or, with videoRgbChannels 3 / 4 (snn_model_create9), snnhip_yuv_rgb_plan_create's launch instead: the model's output luma frame and the
         // original CbCr plane to an RGB / RGBA frame (videoRange SNNHIP_RANGE_*, matrix videoKr / videoKb)
         int videoRgbChannels = 0, videoRange = 0;
+        // ... or, with fitW / fitH (snn_model_create11), two snnhip_plane_fit_plan_create launches instead: the model's output luma frame and the
+        // original CbCr plane resampled to an NV12 / P010 frame of fitW x fitH (no chroma_up launch)
+        int fitW = 0, fitH = 0;
         float videoKr = 0.299f, videoKb = 0.114f;
         // HIP extension: RGB8 / RGBA8 frames in, an NV12 frame out around a luma-only model (snn_model_create10).  encodeChannels 3 / 4: run() puts
         // snnhip_rgb_luma_plan_create's launch in front of the model, as colourChannels does, and snnhip_rgb_cbcr_plan_create's behind it, from the

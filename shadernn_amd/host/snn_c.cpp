@@ -105,10 +105,10 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
 // snn_model_create6 / 7 / 8: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends, `video`
 // (snn_model_create8) for NV12 / P010 frames around a model that `io` gives R8 / R16 frames, `videoRgb` (snn_model_create9, beside `video`) for an RGB
 // frame at the output instead of NV12 / P010, `encode` (snn_model_create10) for RGB8 / RGBA8 frames in and an NV12 frame out around a model that `io`
-// gives R8 frames
+// gives R8 frames, `fit` (snn_model_create11, beside `video`) for an NV12 / P010 output frame of fit->out_w x fit->out_h instead of r times the input
 static int createModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
                        int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out, const snn_video_io* video = nullptr,
-                       const snn_video_rgb_io* videoRgb = nullptr, const snn_encode_io* encode = nullptr) {
+                       const snn_video_rgb_io* videoRgb = nullptr, const snn_encode_io* encode = nullptr, const snn_fit_io* fit = nullptr) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
     ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
     if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
@@ -165,6 +165,22 @@ static int createModel(const char* json_path, int device, int in_w, int in_h, in
                 cp.videoMaxval = video->maxval;
                 cp.videoShift = video->shift;
                 cp.videoSiting = video->siting;
+                if (fit) { // the r-fold frame is resampled DOWN to the target: r * in / 2 <= out <= r * in on both axes
+                    const long long rw = static_cast<long long>(r) * in_w, rh = static_cast<long long>(r) * in_h;
+                    if (fit->out_w > rw || fit->out_h > rh || 2ll * fit->out_w < rw || 2ll * fit->out_h < rh) {
+                        std::string fits;
+                        for (int q = 1; q <= 4; ++q)
+                            if (fit->out_w <= 1ll * q * in_w && fit->out_h <= 1ll * q * in_h && 2ll * fit->out_w >= 1ll * q * in_w && 2ll * fit->out_h >= 1ll * q * in_h)
+                                fits += (fits.empty() ? "" : ", ") + std::to_string(q);
+                        SNN_LOGE("snn_model_create11: the model is r = %u: %dx%d -> %lldx%lld, and %dx%d is %s; %s%s", r, in_w, in_h, rw, rh, fit->out_w, fit->out_h,
+                                 (fit->out_w > rw || fit->out_h > rh) ? "larger than that" : "less than half of that", fits.empty() ? "no r = 1..4 fits both axes" : "a model of r = ",
+                                 fits.c_str());
+                        snn_model_destroy(m);
+                        return -1;
+                    }
+                    cp.fitW = fit->out_w;
+                    cp.fitH = fit->out_h;
+                }
                 if (videoRgb) {
                     cp.videoRgbChannels = videoRgb->out_format & 0xff;
                     cp.videoRange = videoRgb->range;
@@ -218,8 +234,9 @@ int snn_model_create7(const char* json_path, int device, int in_w, int in_h, int
     return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, io, out);
 }
 
-int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                      int prefer_half, int capture_graph, int batch, const snn_video_io* io, snn_model** out) {
+// snn_model_create8, and snn_model_create11 with `fit`
+static int createVideoModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
+                            int capture_graph, int batch, const snn_video_io* io, snn_model** out, const snn_fit_io* fit) {
     if (!io || (io->format != SNN_IO_NV12 && io->format != SNN_IO_NV12_16) || in_c != 1 || batch < 1) return -1;
     if (in_w < 2 || in_h < 2 || in_w % 2 || in_h % 2) return -1; // 4:2:0: the chroma plane is half the extent
     const bool wide = io->format == SNN_IO_NV12_16;
@@ -237,7 +254,22 @@ int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int
     io2.in_shift = wide ? io->shift : 0;
     io2.out_maxval = wide ? io->maxval : 65535; // (snn_model_create5 passes 65535 for the 8-bit formats: the same model)
     io2.out_shift = wide ? io->shift : 0;
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, io);
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, io, nullptr, nullptr,
+                       fit);
+}
+
+int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_video_io* io, snn_model** out) {
+    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, nullptr);
+}
+
+int snn_model_create11(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_fit_io* io, snn_model** out) {
+    if (!io) return -1;
+    if (io->out_w < 2 || io->out_h < 2 || io->out_w % 2 || io->out_h % 2) return -1; // 4:2:0 at the output too
+    if (in_w < 1 || in_h < 1) return -1;
+    if (2ll * io->out_w < in_w || 2ll * io->out_h < in_h || io->out_w > 4ll * in_w || io->out_h > 4ll * in_h) return -1; // the chroma plane's ratio: [1/2, 4]
+    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io->video, out, io);
 }
 
 int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,

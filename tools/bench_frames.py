@@ -72,6 +72,15 @@ frame comes back as 1.5 bytes per pixel, an RGB8 frame as 3), the kernels of the
 profiles/espcn_rgb_nv12_frames.json holds the runs under the keys <format>_nv12_scale<r>.
 
     python tools/bench_frames.py --colour RGB8 --video-out NV12 --scale 2
+
+--video NV12 | P010 --fit WxH (with any --scale, --h / --w the input): the frame at any output size.  Four forms in the same
+mirrored alternation: nv12 (the NV12 -> NV12 step of --video at the same r: the chain plus the chroma launch, three launches), fitted (the chain plus
+the two plane_fit launches, the model's luma frame to H x W and the ORIGINAL chroma plane to H/2 x W/2: four launches), fit (those two launches
+alone) and copy (one hipMemcpyDtoDAsync that moves as many bytes through HBM as the two have to).  Device step per form with the spread over the
+rounds, frames/s including one frame's H2D + D2H for nv12 and fitted, the kernels of the launch trace, and the two launches' bytes/s beside the
+copy's.  profiles/espcn_fit_frames.json holds the runs under the keys <format>_<in>_x<r>_<out>.
+
+    python tools/bench_frames.py --video NV12 --scale 2 --h 720 --w 1280 --fit 1920x1080
 """
 import argparse
 import json
@@ -478,6 +487,146 @@ def main_video(a):
     ctx.close()
 
 
+def main_fit(a):
+    """--video ... --fit WxH: nv12 / fitted / fit / copy."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R = a.scale
+    OW, OH = (int(v) for v in a.fit.lower().split("x"))
+    wide = a.video == "P010"
+    maxval, shift, dt, npdt = (1023, 6, capi.U16, np.uint16) if wide else (255, 0, capi.U8, np.uint8)
+    half_range = maxval / 2.0
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    assert H % 2 == 0 and W % 2 == 0 and OH % 2 == 0 and OW % 2 == 0, "4:2:0 frames have even extents"
+    assert R * H >= OH >= R * H / 2 and R * W >= OW >= R * W / 2, "the target lies between half and all of the x%d frame %dx%d" % (R, R * W, R * H)
+    rng = np.random.default_rng(1)
+    y_h = (rng.integers(0, maxval + 1, size=(1, H, W, 1)) << shift).astype(npdt)
+    c_h = (rng.integers(0, maxval + 1, size=(1, H // 2, W // 2, 2)) << shift).astype(npdt)
+    layers, shape = [], (1, H, W, 1)
+    for layer in net["layers"]:
+        p = _layer_plan(ctx, layer, shape)
+        layers.append(p)
+        shape = p.out_shape()
+    if wide:
+        ends = (capi.u16_in_plan(ctx, 1, H, W, 1, (half_range, 0, 0, 0), (1 / half_range, 1, 1, 1), shift), capi.u16_out_plan(ctx, *shape, (half_range, 0, 0, 0), (half_range, 0, 0, 0), maxval, shift))
+    else:
+        ends = (capi.u8_in_plan(ctx, 1, H, W, 1, (127.5, 0, 0, 0), (1 / 127.5, 1, 1, 1)), capi.u8_out_plan(ctx, *shape, (127.5, 0, 0, 0), (127.5, 0, 0, 0)))
+    grey = capi.chain_plan(ctx, [ends[0]] + layers + [ends[1]])
+    assert grey.num_steps() == 2, grey.describe()
+    chroma = capi.chroma_up_plan(ctx, 1, H // 2, W // 2, 2, R, dt, maxval, shift, a.siting)
+    fit_y = capi.plane_fit_plan(ctx, 1, R * H, R * W, 1, OH, OW, dt, maxval, shift, "centre")
+    fit_c = capi.plane_fit_plan(ctx, 1, H // 2, W // 2, 2, OH // 2, OW // 2, dt, maxval, shift, a.siting)
+    cshape, fyshape, fcshape = (1, R * H // 2, R * W // 2, 2), (1, OH, OW, 1), (1, OH // 2, OW // 2, 2)
+    t_y, t_c = capi.Tensor.from_numpy(ctx, y_h, dtype=dt), capi.Tensor.from_numpy(ctx, c_h, dtype=dt)
+    t_yhi, t_chi = capi.Tensor(ctx, *shape, dtype=dt), capi.Tensor(ctx, *cshape, dtype=dt)
+    t_fy, t_fc = capi.Tensor(ctx, *fyshape, dtype=dt), capi.Tensor(ctx, *fcshape, dtype=dt)
+    fit_bytes = int(fit_y.cost()[1] + fit_c.cost()[1])
+    half = fit_bytes // 2
+    t_src, t_dst = capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8)
+    t_src.upload_u8(np.random.default_rng(3).integers(0, 256, size=half, dtype=np.uint8))
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+
+    def run_nv12():
+        grey.run(t_y, t_yhi)
+        chroma.run(t_c, t_chi)
+
+    def run_fit():
+        fit_y.run(t_yhi, t_fy)
+        fit_c.run(t_c, t_fc)
+
+    def run_fitted():
+        grey.run(t_y, t_yhi)
+        run_fit()
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(t_dst.data_ptr(), t_src.data_ptr(), half, stream)
+        assert rc == 0, rc
+
+    forms = {"nv12": run_nv12, "fitted": run_fitted, "fit": run_fit, "copy": run_copy}
+    yhi_h, chi_h, fy_h, fc_h = np.empty(shape, npdt), np.empty(cshape, npdt), np.empty(fyshape, npdt), np.empty(fcshape, npdt)
+    io = {"nv12": ([(t_y, y_h), (t_c, c_h)], [(t_yhi, yhi_h), (t_chi, chi_h)]), "fitted": ([(t_y, y_h), (t_c, c_h)], [(t_fy, fy_h), (t_fc, fc_h)])}
+    for f in forms.values():
+        for _ in range(a.warmup):
+            f()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {k: [] for k in forms}
+    e2e = {k: [] for k in io}
+    order = list(forms) + list(forms)[::-1]  # mirrored: A B C D D C B A
+    for _ in range(a.rounds):
+        for k in order:
+            timer.start()
+            for _ in range(a.iters):
+                forms[k]()
+            timer.stop()
+            dev[k].append(timer.elapsed_ms() / a.iters)
+    for _ in range(a.rounds):
+        for k in list(io) + list(io)[::-1]:
+            ups, downs = io[k]
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                for t, h in ups:
+                    capi.check(capi.lib().snnhip_tensor_upload_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+                forms[k]()
+                for t, h in downs:
+                    capi.check(capi.lib().snnhip_tensor_download_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+            e2e[k].append((time.perf_counter() - t0) * 1e3 / a.iters)
+    out = {"frame": "%dx%d -> x%d %dx%d -> %dx%d" % (H, W, R, R * H, R * W, OH, OW), "scale": R, "video": a.video, "siting": a.siting, "ratio": round(OH / (R * H), 4),
+           "rounds": a.rounds, "iters": a.iters}
+    for k in forms:
+        d = statistics.median(dev[k])
+        out[k] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[k]), 4), "device_ms_max": round(max(dev[k]), 4),
+                  "device_spread": round((max(dev[k]) - min(dev[k])) / d, 4)}
+        if k in io:
+            e = statistics.median(e2e[k])
+            out[k].update({"e2e_ms_median": round(e, 4), "e2e_ms_min": round(min(e2e[k]), 4), "e2e_ms_max": round(max(e2e[k]), 4), "e2e_frames_per_s": round(1e3 / e, 1),
+                           "io_bytes_per_frame": int(sum(h.nbytes for _, h in io[k][0]) + sum(h.nbytes for _, h in io[k][1]))})
+    out["nv12"]["steps"] = [grey.step_describe(i) for i in range(2)] + [chroma.describe()]
+    out["fitted"]["steps"] = [grey.step_describe(i) for i in range(2)] + [fit_y.describe(), fit_c.describe()]
+    for k in ("nv12", "fitted", "fit"):  # the launch trace: per-kernel times of each form (a copy is no kernel of the library)
+        capi.trace_begin()
+        for _ in range(a.iters):
+            forms[k]()
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        out[k]["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                              "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+    out["fit"]["luma"] = {"plan": fit_y.describe(), "hbm_bytes": int(fit_y.cost()[1])}
+    out["fit"]["chroma"] = {"plan": fit_c.describe(), "hbm_bytes": int(fit_c.cost()[1])}
+    for k, plan in (("luma", fit_y), ("chroma", fit_c)):  # each launch alone, traced, so that the two have a time of their own
+        capi.trace_begin()
+        for _ in range(a.iters):
+            plan.run(*((t_yhi, t_fy) if k == "luma" else (t_c, t_fc)))
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        hit = [it for it in kernels if it.get("function") and "plane_fit" in it["function"]]
+        if hit:
+            us = 1e3 * hit[0].get("total_ms", hit[0].get("ms", 0.0)) / max(hit[0].get("launches", 0), 1)
+            out["fit"][k].update({"us_per_launch_traced": round(us, 2), "tbs_traced": round(out["fit"][k]["hbm_bytes"] / (us * 1e-6) / 1e12, 3)})
+    out["device_fitted_over_nv12"] = round(out["fitted"]["device_ms_median"] / out["nv12"]["device_ms_median"], 4)
+    out["e2e_fps_fitted_over_nv12"] = round(out["fitted"]["e2e_frames_per_s"] / out["nv12"]["e2e_frames_per_s"], 4)
+    copy_us = 1e3 * out["copy"]["device_ms_median"]
+    out["fit_vs_copy"] = {"fit_hbm_bytes": fit_bytes, "fit_us_event_timed_loop": round(1e3 * out["fit"]["device_ms_median"], 2),
+                          "fit_tbs_event_timed_loop": round(fit_bytes / (out["fit"]["device_ms_median"] * 1e-3) / 1e12, 3),
+                          "copy_bytes_each_way": half, "copy_hbm_bytes": 2 * half, "copy_us": round(copy_us, 2), "copy_tbs": round(2 * half / (copy_us * 1e-6) / 1e12, 3)}
+    out["fit_vs_copy"]["fit_over_copy_rate"] = round(out["fit_vs_copy"]["fit_tbs_event_timed_loop"] / out["fit_vs_copy"]["copy_tbs"], 4)
+    print(json.dumps(out, indent=1))
+    ctx.close()
+
+
 def main_video_rgb(a):
     """--video ... --video-out ...: nv12 / nv12_rgb / yuv_rgb / copy / rgb8."""
     import ctypes
@@ -765,6 +914,7 @@ def main():
     ap.add_argument("--video", choices=["NV12", "P010"], default=None, help="4:2:0 video frames around the luma chain: grey, video, the chroma launch alone, a device copy of its bytes and the RGB8 colour step")
     ap.add_argument("--video-out", choices=["RGB8", "RGBA8", "NV12"], default=None,
                     help="with --video: packed RGB / RGBA out of the yuv_rgb launch (16-bit containers for P010) beside the NV12 step; NV12 with --colour: an NV12 frame out of the rgb_cbcr launch")
+    ap.add_argument("--fit", default=None, metavar="WxH", help="with --video: the NV12 / P010 frame at this output size (the chain, then two plane_fit launches) beside the plain step of the same r")
     ap.add_argument("--range", choices=["limited", "full"], default="limited", help="the stream's range with --video-out")
     ap.add_argument("--siting", choices=["left", "centre"], default="left", help="horizontal chroma siting of --video")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
@@ -779,6 +929,9 @@ def main():
     if a.video_out == "NV12":
         assert a.colour and not a.video, "--video-out NV12 goes with --colour RGB8 | RGBA8"
         return main_rgb_nv12(a)
+    if a.fit:
+        assert a.video and not a.video_out and not a.colour, "--fit goes with --video alone"
+        return main_fit(a)
     if a.video and a.video_out:
         return main_video_rgb(a)
     if a.video:
