@@ -178,6 +178,42 @@ typedef struct snn_fit_io {
 } snn_fit_io;
 int snn_model_create11(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_fit_io* io, snn_model** out);
+/* Planar 4:2:0 frames (I420 / I010: ffmpeg's yuv420p / yuv420p10le, what dav1d, libvpx and libavcodec decode to and x264, x265 and SVT-AV1 take)
+ * around a luma-only model, and plane pointers with row pitches for every video end.  Through a struct and an entry point of their own: every
+ * earlier struct and entry point keeps its layout and behaviour.  Four paths, each built exactly as its NV12 counterpart -- the two fused ESPCN
+ * kernels with folded ends (the fp16 opt-in works too), every launch on one stream and inside the recorded graph with capture_graph -- and with the
+ * same number of launches; no launch interleaves or splits chroma anywhere:
+ *     planar -> the same planar format, r-fold     3 launches   snn_model_create8's path: snnhip_chroma_up_plan_create, C = 1 over 2 * batch planes
+ *     planar -> planar at out_w x out_h            4 launches   snn_model_create11's path and rules: two snnhip_plane_fit_plan_create, chroma C = 1
+ *     planar -> RGB8 / RGBA8 (RGB16 / RGBA16)      3 launches   snn_model_create9's path: snnhip_yuv_rgb_planar_plan_create
+ *     RGB8 / RGBA8 -> SNN_IO_I420                  4 launches   snn_model_create10's path: snnhip_rgb_luma in front, snnhip_rgb_cbcr_planar_plan_create behind
+ * The device chroma tensors are [2 * batch][h][w][1]: plane 2n is Cb, 2n + 1 Cr of frame n (include/snnhip.h).  The luma plane's maps follow from
+ * `range` on every path, as snn_model_create9 / snn_model_create10 state them; kr / kb are the matrix of the RGB end (not looked at planar to planar).
+ * snn_model_describe lists the extra launches.  Returns -1, before anything is built on the device, for a null struct, formats that do not pair up
+ * as above, a fitted size together with an RGB end, and everything the NV12 counterpart of the path refuses: a model that is not one channel in and
+ * out, odd extents, maxval other than 255 (8-bit) or outside 255 .. 4095 (16-bit) or with maxval + 1 not a multiple of 256, a shift that does not fit, an unknown
+ * siting or range, a matrix outside 0 < kr, 0 < kb, kr + kb < 1, batch < 1; the fitted size's rules (even, ratio in [1/2, 4]); and, once the model file
+ * gives r, r = 1 with RGB in and a fitted size outside [r * in / 2, r * in].  Not offered: 4:2:2 / 4:4:4 and packed layouts, BGR order, RGB output at a
+ * fitted size, 16-bit RGB -> I010, pitched DEVICE surfaces (the device tensors stay dense). */
+enum { SNN_IO_I420 = 0x401, SNN_IO_I420_16 = 0x501 }; /* (low byte = the model's channel count) */
+typedef struct snn_planar_io {
+    int in_format;  /* SNN_IO_I420, SNN_IO_I420_16, or SNN_IO_RGB8 / SNN_IO_RGBA8 (capture in) */
+    int out_format; /* planar in: the same planar format, or RGB8 / RGBA8 (8-bit), RGB16 / RGBA16 (16-bit); RGB in: SNN_IO_I420 */
+    int maxval, shift, siting, range;
+    float kr, kb;
+    int out_w, out_h; /* 0, 0: r times the input; otherwise the fitted size, planar in and planar out only */
+} snn_planar_io;      /* 10 * 4 bytes */
+int snn_model_create12(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_planar_io* io, snn_model** out);
+/* Frames as plane pointers with row pitches (ffmpeg's data[] / linesize[]).  `planes` holds batch * n_planes pointers, frame by frame, in the order
+ * Y, Cb, Cr (a YV12 caller swaps the last two) for a planar end, n_planes = 3; Y, CbCr for the NV12 / P010 ends of models made by snn_model_create8
+ * / 9 / 10 / 11, n_planes = 2 (pitched NV12 surfaces).  pitch_bytes[n_planes] is the row pitch of each plane, the same for every frame.  Planes that
+ * are tight (pitch = the row's bytes) and adjacent in memory in the device tensor's order are copied straight; anything else is gathered through the
+ * model's host staging buffer row by row with memcpy: padding bytes are never read, and a download writes width * element size bytes per row and
+ * leaves the padding untouched.  -1 for a null argument (a null plane pointer among them), an n_planes that does not match that end of the model, a
+ * pitch below the row's bytes, or an RGB end.  snn_model_upload_frame_nv12 / _download_frame_nv12 keep their behaviour and return -1 on planar ends. */
+int snn_model_upload_frame_planes(snn_model* m, const void* const* planes, const int* pitch_bytes, int n_planes);
+int snn_model_download_frame_planes(snn_model* m, void* const* planes, const int* pitch_bytes, int n_planes);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

@@ -525,6 +525,26 @@ int snnhip_bicubic_taps_rgb420(int r, int siting, float* weights, int* base, int
 /* host only, no context: out[0..2] = Coff, cbs, crs of the matrix above (capacity >= 3 floats) */
 int snnhip_rgb_cbcr_coefficients(int range, float kr, float kb, float* out, int capacity);
 
+/* Planar 4:2:0 chroma (I420 / I010: ffmpeg's yuv420p / yuv420p10le, what software decoders write and software encoders read) for the two plans above
+ * that touch BOTH chroma components.  DESIGN.md section 4.19.  The contract, stated once:
+ *   The planar chroma tensor is [2N][H][W][1] of dtype SNNHIP_U8 or SNNHIP_U16: plane 2n is the Cb plane of image n, plane 2n + 1 its Cr plane, each
+ *     dense.  (A YV12 caller swaps the two planes when it copies them in or out.)
+ *   snnhip_yuv_rgb_planar_plan_create takes snnhip_yuv_rgb_desc unchanged.  inputs[0] = Yhi [N][2rH][2rW][1], inputs[1] = the planar chroma tensor
+ *     [2N][H][W][1]; output [N][2rH][2rW][C].  Output, arithmetic, tap tables and coefficients are exactly those of snnhip_yuv_rgb_plan_create on
+ *     the interleaved plane with the same samples (r = 1..4, C = 3 | 4, 8 / 10 / 12 bits, high-aligned containers, either range and siting); so are
+ *     the refusals at plan creation.  snnhip_plan_run_n refuses, with a message starting "yuv_rgb_planar", a tensor of another dtype at any position,
+ *     a chroma tensor that is not [2N][H][W][1] and shapes that are not 2r times a chroma plane.  snnhip_plan_describe: "yuv_rgb_planar_u8 r=2 c=3 ...
+ *     kernel=yuv_rgb_planar_kernel", the tile that of the interleaved plan.
+ *   snnhip_rgb_cbcr_planar_plan_create takes snnhip_rgb_cbcr_desc unchanged.  Input U8 [N][H][W][C]; output U8 [2N][rH/2][rW/2][1], r = 2..4; the
+ *     arithmetic and the refusals at plan creation (r = 1 among them) are those of snnhip_rgb_cbcr_plan_create.  snnhip_plan_run refuses, with a message
+ *     starting "rgb_cbcr_planar", a tensor that is not SNNHIP_U8 and an output that is not [2N][rH/2][rW/2][1].  snnhip_plan_describe:
+ *     "rgb_cbcr_planar_u8 r=2 c=3 ... kernel=rgb_cbcr_planar_kernel".
+ *   Both are one launch: no interleaved plane is formed anywhere, and no LDS, barrier or scratch is used.  Every byte of both output planes (of the RGB
+ *     frame) is written.  Planar in, planar out needs no plan of its own: snnhip_chroma_up_plan_create and snnhip_plane_fit_plan_create with C = 1
+ *     and N = 2 * batch run over the planar chroma tensor. */
+int snnhip_yuv_rgb_planar_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_n, 2 inputs */
+int snnhip_rgb_cbcr_planar_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run */
+
 /* A plane resampled to any size between half and four times its own, each axis with its own ratio: what brings the r-fold frame of the luma model
  * (and the original chroma plane beside it) to the size a pipeline asks for -- 720p to 1080p is the x2 model, then 3/4.  The plans above change a
  * frame's size by the model's factor only.  DESIGN.md section 4.18.  The contract, stated once:

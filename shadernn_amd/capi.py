@@ -207,6 +207,8 @@ SIGNATURES = {
     "snnhip_rgb_cbcr_plan_create": (C.c_int, [_P, C.POINTER(RgbCbcrDesc), C.POINTER(_P)]),
     "snnhip_bicubic_taps_rgb420": (C.c_int, [C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_rgb_cbcr_coefficients": (C.c_int, [C.c_int, C.c_float, C.c_float, _FP, C.c_int]),
+    "snnhip_yuv_rgb_planar_plan_create": (C.c_int, [_P, C.POINTER(YuvRgbDesc), C.POINTER(_P)]),
+    "snnhip_rgb_cbcr_planar_plan_create": (C.c_int, [_P, C.POINTER(RgbCbcrDesc), C.POINTER(_P)]),
     "snnhip_plane_fit_plan_create": (C.c_int, [_P, C.POINTER(PlaneFitDesc), C.POINTER(_P)]),
     "snnhip_fit_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
@@ -841,6 +843,26 @@ def rgb_cbcr_coefficients(range="limited", kr=BT601[0], kb=BT601[1]):
     out = np.zeros(3, np.float32)
     check(lib().snnhip_rgb_cbcr_coefficients(RANGE.get(range, range), kr, kb, _fptr(out), out.size))
     return out
+
+
+def yuv_rgb_planar_plan(ctx, N, H, W, Cc, r, dtype=U8, maxval=None, shift=0, siting="left", range="limited", kr=BT601[0], kb=BT601[1]):
+    """plan.run([Yhi [N][2r*H][2r*W][1], chroma [2N][H][W][1]], out [N][2r*H][2r*W][Cc]): yuv_rgb_plan for planar chroma (I420 / I010): plane 2n is
+    the Cb plane of image n, 2n + 1 its Cr plane.  One launch, the arithmetic of yuv_rgb_plan."""
+    if maxval is None:
+        maxval = 255
+    d = YuvRgbDesc(N, H, W, Cc, r, dtype, maxval, shift, SITING.get(siting, siting), RANGE.get(range, range), kr, kb)
+    h = _P()
+    check(lib().snnhip_yuv_rgb_planar_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def rgb_cbcr_planar_plan(ctx, N, H, W, Cc, r, siting="left", range="limited", kr=BT601[0], kb=BT601[1]):
+    """plan.run([frame U8 [N][H][W][Cc]], out U8 [2N][r*H/2][r*W/2][1]): rgb_cbcr_plan with a planar output (I420): plane 2n is the Cb plane of image
+    n, 2n + 1 its Cr plane.  One launch, the arithmetic of rgb_cbcr_plan, r = 2..4."""
+    d = RgbCbcrDesc(N, H, W, Cc, r, SITING.get(siting, siting), RANGE.get(range, range), kr, kb)
+    h = _P()
+    check(lib().snnhip_rgb_cbcr_planar_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
 
 
 def plane_fit_plan(ctx, N, H, W, Cc, OH, OW, dtype=U8, maxval=None, shift=0, siting="left"):

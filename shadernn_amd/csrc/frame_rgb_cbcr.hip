@@ -17,6 +17,9 @@
 // compile-time constant (a term 0 * v adds exactly nothing).  Rows whose address is not dword-aligned (the RGB8 pitch 3W for W not a multiple of 4;
 // the output pitch 2 * rW / 2 for odd rW / 2), the lane that straddles the right edge and aprons outside the frame take a byte path with clamped
 // indices.
+//
+//   rgb_cbcr_planar (snnhip_rgb_cbcr_planar_plan_create): the same into two planes U8 [2N][rH/2][rW/2][1] (I420).  Only the
+//              store side differs: the PLANAR branch of rgb_cbcr_body.
 #include "frame_rgb_cbcr.h"
 #include "plan_util.h"
 #include "snnhip_internal.h"
@@ -60,7 +63,10 @@ __device__ __forceinline__ void cbcr_hfilter(const RgbCbcrParams& P, const float
     }
 }
 
-template <int R, int C>
+// PLANAR (snnhip_rgb_cbcr_planar_plan_create): the output is U8 [2N][OH][OW][1], plane 2n = Cb, 2n + 1 = Cr of image n.  The load and filter side is
+// the interleaved kernel's; the lane's OPX Cb bytes and OPX Cr bytes go to the two planes, OPX bytes into each row from OPX * (its index in the row):
+// whole dwords where that row of that plane starts on one (OPX = 4, 8 at r = 2, 4), halfwords at r = 3 (OPX = 6) on an even address, bytes otherwise
+template <int R, int C, bool PLANAR = false>
 __device__ __forceinline__ void rgb_cbcr_body(const RgbCbcrParams& P, const unsigned char* __restrict__ in, unsigned char* __restrict__ out) {
     using G = CbcrGeom<R>;
     constexpr int NW = C + 4;       // dwords that cover the lane's staged pixels of a row: 8 bytes, the lane's own 4 * C, 8 bytes
@@ -132,6 +138,28 @@ __device__ __forceinline__ void rgb_cbcr_body(const RgbCbcrParams& P, const unsi
                 e[i] = quantize_frame(P.m.coff + (i % 2 ? P.m.crs : P.m.cbs) * acc, 255.0f);
             }
             const size_t J = static_cast<size_t>(G::P) * (py0 + t) + q;
+            if constexpr (PLANAR) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    unsigned char* prow = out + ((2 * n + c) * P.OH + J) * P.OW; // (the Cr plane lies OH * OW bytes behind Cb: its rows align on their own)
+                    unsigned char* dst = prow + col0;
+                    const size_t al = reinterpret_cast<size_t>(prow);
+                    if (full && G::OPX % 4 == 0 && (al & 3) == 0) {
+                        unsigned w[(G::OPX + 3) / 4];
+#pragma unroll
+                        for (int k = 0; k < G::OPX / 4; ++k) w[k] = e[8 * k + c] | (e[8 * k + 2 + c] << 8) | (e[8 * k + 4 + c] << 16) | (e[8 * k + 6 + c] << 24);
+                        store_words<(G::OPX + 3) / 4>(dst, w);
+                    } else if (full && (al & 1) == 0) { // (OPX is even: the piece starts on a halfword)
+#pragma unroll
+                        for (int k = 0; k < G::OPX / 2; ++k) reinterpret_cast<unsigned short*>(dst)[k] = static_cast<unsigned short>(e[4 * k + c] | (e[4 * k + 2 + c] << 8));
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < G::OPX; ++i)
+                            if (i * 2 < valid) dst[i] = static_cast<unsigned char>(e[i * 2 + c]);
+                    }
+                }
+                continue;
+            }
             unsigned char* orow = out + (n * P.OH + J) * P.OW * 2;
             unsigned char* dst = orow + col0 * 2;
             if (full && (reinterpret_cast<size_t>(orow) & 3) == 0) { // the lane's piece starts a multiple of 4 bytes into the row
@@ -153,22 +181,39 @@ __global__ __launch_bounds__(256) void rgb_cbcr_kernel(RgbCbcrParams P, const un
     if constexpr (R >= 2) rgb_cbcr_body<R, C>(P, in, out); // (dispatch_r_c names r = 1 too; the plan refuses it)
 }
 
+template <int R, int C>
+__global__ __launch_bounds__(256) void rgb_cbcr_planar_kernel(RgbCbcrParams P, const unsigned char* __restrict__ in, unsigned char* __restrict__ out) {
+    if constexpr (R >= 2) rgb_cbcr_body<R, C, true>(P, in, out);
+}
+
 struct RgbCbcrPlan : snnhip_plan {
     snnhip_rgb_cbcr_desc d;
     RgbCbcrParams P;
+    bool planar = false; // the output is [2N][OH][OW][1] (snnhip_rgb_cbcr_planar_plan_create)
 
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
-        SNNHIP_REQUIRE(nIn == 1, "rgb_cbcr: expects 1 input, got %d", nIn);
-        SNNHIP_REQUIRE(in[0]->dtype == SNNHIP_U8 && out->dtype == SNNHIP_U8, "rgb_cbcr: both tensors must be SNNHIP_U8, got dtypes %d and %d", in[0]->dtype, out->dtype);
-        SNNHIP_REQUIRE(dims_match(in[0], d.N, d.H, d.W, d.C), "rgb_cbcr: the input frame is %dx%dx%dx%d, the plan was built for %dx%dx%dx%d", in[0]->n, in[0]->h, in[0]->w,
-                       in[0]->c, d.N, d.H, d.W, d.C);
-        SNNHIP_REQUIRE(dims_match(out, d.N, P.OH, P.OW, 2), "rgb_cbcr: the output is %dx%dx%dx%d, expected %dx%dx%dx2 (the chroma plane of a %dx%d frame, r = %d)", out->n, out->h,
-                       out->w, out->c, d.N, P.OH, P.OW, d.r * d.H, d.r * d.W, d.r);
+        if (planar) {
+            SNNHIP_REQUIRE(nIn == 1, "rgb_cbcr_planar: expects 1 input, got %d", nIn);
+            SNNHIP_REQUIRE(in[0]->dtype == SNNHIP_U8 && out->dtype == SNNHIP_U8, "rgb_cbcr_planar: both tensors must be SNNHIP_U8, got dtypes %d and %d", in[0]->dtype, out->dtype);
+            SNNHIP_REQUIRE(dims_match(in[0], d.N, d.H, d.W, d.C), "rgb_cbcr_planar: the input frame is %dx%dx%dx%d, the plan was built for %dx%dx%dx%d", in[0]->n, in[0]->h,
+                           in[0]->w, in[0]->c, d.N, d.H, d.W, d.C);
+            SNNHIP_REQUIRE(dims_match(out, 2 * d.N, P.OH, P.OW, 1),
+                           "rgb_cbcr_planar: the output is %dx%dx%dx%d, expected %dx%dx%dx1 ([2N][rH/2][rW/2][1]: the Cb and Cr planes of a %dx%d frame, r = %d)", out->n, out->h,
+                           out->w, out->c, 2 * d.N, P.OH, P.OW, d.r * d.H, d.r * d.W, d.r);
+        } else {
+            SNNHIP_REQUIRE(nIn == 1, "rgb_cbcr: expects 1 input, got %d", nIn);
+            SNNHIP_REQUIRE(in[0]->dtype == SNNHIP_U8 && out->dtype == SNNHIP_U8, "rgb_cbcr: both tensors must be SNNHIP_U8, got dtypes %d and %d", in[0]->dtype, out->dtype);
+            SNNHIP_REQUIRE(dims_match(in[0], d.N, d.H, d.W, d.C), "rgb_cbcr: the input frame is %dx%dx%dx%d, the plan was built for %dx%dx%dx%d", in[0]->n, in[0]->h, in[0]->w,
+                           in[0]->c, d.N, d.H, d.W, d.C);
+            SNNHIP_REQUIRE(dims_match(out, d.N, P.OH, P.OW, 2), "rgb_cbcr: the output is %dx%dx%dx%d, expected %dx%dx%dx2 (the chroma plane of a %dx%d frame, r = %d)", out->n, out->h,
+                           out->w, out->c, d.N, P.OH, P.OW, d.r * d.H, d.r * d.W, d.r);
+        }
         const dim3 grid(static_cast<unsigned>(P.N) * static_cast<unsigned>(P.tilesX) * static_cast<unsigned>(P.tilesY));
         const unsigned char* src = reinterpret_cast<const unsigned char*>(in[0]->data);
         unsigned char* dst = reinterpret_cast<unsigned char*>(out->data);
         dispatch_r_c<3, 4>(d.r, d.C, [&](auto R, auto C) {
-            SNNHIP_LAUNCH((rgb_cbcr_kernel<decltype(R)::value, decltype(C)::value>), grid, dim3(256), 0, ctx->stream, P, src, dst);
+            if (planar) SNNHIP_LAUNCH((rgb_cbcr_planar_kernel<decltype(R)::value, decltype(C)::value>), grid, dim3(256), 0, ctx->stream, P, src, dst);
+            else SNNHIP_LAUNCH((rgb_cbcr_kernel<decltype(R)::value, decltype(C)::value>), grid, dim3(256), 0, ctx->stream, P, src, dst);
         });
         SNNHIP_CHECK_HIP(hipGetLastError());
         return SNNHIP_OK;
@@ -204,8 +249,10 @@ int snnhip_rgb_cbcr_coefficients(int range, float kr, float kb, float* out, int 
     return SNNHIP_OK;
 }
 
-int snnhip_rgb_cbcr_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* desc, snnhip_plan** out) {
-    SNNHIP_REQUIRE(ctx && desc && out, "rgb_cbcr_plan_create: null argument");
+// snnhip_rgb_cbcr_plan_create and snnhip_rgb_cbcr_planar_plan_create: one desc, one set of checks, tables and coefficients (the messages speak of
+// "rgb_cbcr desc" for both: it is the same struct)
+static int rgb_cbcr_plan_make(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* desc, snnhip_plan** out, bool planar) {
+    SNNHIP_REQUIRE(ctx && desc && out, "%s: null argument", planar ? "rgb_cbcr_planar_plan_create" : "rgb_cbcr_plan_create");
     SNNHIP_REQUIRE(desc->N > 0 && desc->H > 0 && desc->W > 0, "rgb_cbcr desc: bad dims %dx%dx%d", desc->N, desc->H, desc->W);
     SNNHIP_REQUIRE(desc->C == 3 || desc->C == 4, "rgb_cbcr desc: %d channels (3: RGB8, 4: RGBA8)", desc->C);
     SNNHIP_REQUIRE(desc->r != 1, "rgb_cbcr desc: r = 1 would halve the chroma grid, which needs a decimation filter: not built (r is 2..4)");
@@ -236,6 +283,7 @@ int snnhip_rgb_cbcr_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* des
     plan->rawInput = SNNHIP_U8;
     plan->rawOutput = SNNHIP_U8;
     plan->d = *desc;
+    plan->planar = planar;
     plan->P = RgbCbcrParams{};
     plan->P.N = desc->N;
     plan->P.H = desc->H;
@@ -257,15 +305,20 @@ int snnhip_rgb_cbcr_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* des
     plan->outDims[1] = OH;
     plan->outDims[2] = OW;
     plan->outDims[3] = 2;
+    if (planar) plan->outDims[0] = 2 * desc->N, plan->outDims[3] = 1;
     plan->bytes = inBytes + outBytes; // the input once, the output once
     const double inPixels = static_cast<double>(desc->N) * desc->H * desc->W;
     plan->flops = inPixels * 7.0 + outBytes * (2.0 * 4.0 * (1.0 + 2.0 / desc->r) + 2.0); // the differences; 4 taps per pass (the horizontal pass on 2 / r rows per output row); the scale
     char buf[280];
-    snprintf(buf, sizeof(buf), "rgb_cbcr_u8 r=%d c=%d siting=%s range=%s tile=%dx%d %dx%d -> %dx%d kr=%g kb=%g kernel=rgb_cbcr_kernel", desc->r, desc->C,
-             desc->siting == SNNHIP_SITING_LEFT ? "left" : "centre", desc->range == SNNHIP_RANGE_LIMITED ? "limited" : "full", th, tw, desc->H, desc->W, OH, OW, desc->kr, desc->kb);
+    snprintf(buf, sizeof(buf), "%s r=%d c=%d siting=%s range=%s tile=%dx%d %dx%d -> %dx%d kr=%g kb=%g kernel=%s", planar ? "rgb_cbcr_planar_u8" : "rgb_cbcr_u8", desc->r, desc->C,
+             desc->siting == SNNHIP_SITING_LEFT ? "left" : "centre", desc->range == SNNHIP_RANGE_LIMITED ? "limited" : "full", th, tw, desc->H, desc->W, OH, OW, desc->kr, desc->kb, planar ? "rgb_cbcr_planar_kernel" : "rgb_cbcr_kernel");
     plan->desc = buf;
     *out = plan;
     return SNNHIP_OK;
 }
+
+int snnhip_rgb_cbcr_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* desc, snnhip_plan** out) { return rgb_cbcr_plan_make(ctx, desc, out, false); }
+
+int snnhip_rgb_cbcr_planar_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_desc* desc, snnhip_plan** out) { return rgb_cbcr_plan_make(ctx, desc, out, true); }
 
 } // extern "C"

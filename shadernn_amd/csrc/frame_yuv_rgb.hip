@@ -17,6 +17,9 @@
 // base (-1 or 0) is folded into the tap table on the host as in frame_chroma.hip: five weights over x - 2 .. x + 2, one of them 0, so that every
 // register index is a compile-time constant.  Rows whose address is not dword-aligned (the RGB8 pitch 3 * 2rW is 2 mod 4 for odd r and W, and so is
 // the 8-bit Yhi pitch), the lane that straddles the right edge and aprons outside the plane take an element path with clamped indices.
+//
+//   yuv_rgb_planar (snnhip_yuv_rgb_planar_plan_create): the same, with the chroma as two planes E [2N][H][W][1] (I420 / I010).
+//             Only the chroma staging differs: the PLANAR branch of yuv_rgb_body; the filter, the matrix and the output side are shared.
 #include "frame_yuv_rgb.h"
 #include "plan_util.h"
 #include "snnhip_internal.h"
@@ -96,7 +99,52 @@ __device__ __forceinline__ void yuv_row(const YuvRgbParams& P, const float (&h)[
     }
 }
 
-template <int R, int C, typename E>
+// ---- planar chroma (I420 / I010): E [2N][H][W][1], plane 2n = Cb, 2n + 1 = Cr of image n.  The lane keeps the geometry of the interleaved kernel
+// (CP chroma pixels, the same raw[NB] and h[5][OPX * 2]): its CP + 4 staged samples of ONE component are 6 bytes (8-bit) or 10 bytes (16-bit) that
+// start 2 (x0 - 2) * ES / 2 bytes into the row -- a multiple of 2.  The PW dwords from the dword at or below that byte cover them (2 + 6 <= 8,
+// 2 + 10 <= 12): one load per plane and row, ten per lane where the interleaved kernel issues fifteen, shifted right by 0 or 16 bits.  Widening the
+// lane to a dword of each plane instead would double h to 320 floats at r = 4.
+
+template <typename E>
+struct YuvPlanarGeom {
+    static constexpr int ES = static_cast<int>(sizeof(E));
+    static constexpr int NS = 4 / (2 * ES) + 4;            // staged samples of one component per lane and row (YuvGeom::NB / 2)
+    static constexpr int PW = (NS * ES + 2 + 3) / 4;        // dwords that cover them from the dword below their first byte
+};
+
+// whether the PW dwords of a lane lie inside a row of W samples (x0 < W): the first at or below sample x0 - 2, the last ending at or before the row's end
+template <typename E>
+__device__ __forceinline__ bool yuv_planar_inside(int x0, int W) {
+    using Q = YuvPlanarGeom<E>;
+    if (x0 < 2) return false;
+    const size_t a = static_cast<size_t>(x0 - 2) * Q::ES;
+    return (a & ~static_cast<size_t>(3)) + 4 * Q::PW <= static_cast<size_t>(W) * Q::ES;
+}
+
+// raw[b * 2 + c] = sample x0 - 2 + b of component c's row at `row`.  WIDE: one load of PW dwords (the row is dword-aligned and yuv_planar_inside);
+// otherwise elements, indices clamped to [0, W - 1]
+template <typename E, bool WIDE>
+__device__ __forceinline__ void yuv_load_plane(const E* __restrict__ row, int x0, int W, int c, unsigned* raw) {
+    using Q = YuvPlanarGeom<E>;
+    if constexpr (WIDE) {
+        const size_t a = static_cast<size_t>(x0 - 2) * Q::ES;
+        const unsigned sh = static_cast<unsigned>(a & 3) * 8u; // 0 or 16
+        unsigned w[Q::PW], s[Q::PW];
+        load_words<Q::PW>(reinterpret_cast<const unsigned char*>(row) + (a & ~static_cast<size_t>(3)), w);
+#pragma unroll
+        for (int k = 0; k + 1 < Q::PW; ++k) s[k] = static_cast<unsigned>(((static_cast<unsigned long long>(w[k + 1]) << 32) | w[k]) >> sh);
+        s[Q::PW - 1] = w[Q::PW - 1] >> sh;
+#pragma unroll
+        for (int b = 0; b < Q::NS; ++b) raw[b * 2 + c] = frame_elem<E>(s, b);
+    } else {
+#pragma unroll
+        for (int b = 0; b < Q::NS; ++b) raw[b * 2 + c] = row[min(max(x0 - 2 + b, 0), W - 1)];
+    }
+}
+
+// PLANAR (snnhip_yuv_rgb_planar_plan_create): `cbcr` is the planar chroma tensor [2N][H][W][1].  Only the staging of the five chroma rows differs; the
+// lane, raw[], h[][], the filter and the whole output side are the interleaved kernel's
+template <int R, int C, typename E, bool PLANAR = false>
 __device__ __forceinline__ void yuv_rgb_body(const YuvRgbParams& P, const E* __restrict__ yhi, const E* __restrict__ cbcr, E* __restrict__ out) {
     using G = YuvGeom<R, E>;
     constexpr int OD = G::YW * C; // dwords of output per lane and output row
@@ -108,25 +156,61 @@ __device__ __forceinline__ void yuv_rgb_body(const YuvRgbParams& P, const E* __r
     const int x0 = (tile.tx * 64 + lane) * G::CP;
     const int y = tile.ty * G::TILE_H + wave;
     if (x0 >= W || y >= H) return; // (no barrier anywhere below)
-    const E* plane = cbcr + n * H * W * 2;
-
-    // chroma rows y - 2 .. y + 2 (clamped to the plane), resampled to the lane's output columns.  Whether a row starts on a dword is the same for
-    // every row of a plane whose pitch is a multiple of 4 bytes: one decision for the wave, and all fifteen loads of an interior lane are in flight
-    // before the first is used
     float h[5][G::OPX * 2];
-    const bool chromaAligned = (reinterpret_cast<size_t>(plane) & 3) == 0 && (static_cast<size_t>(W) * 2 * G::ES) % 4 == 0;
-    if (chromaAligned && x0 >= 2 && x0 + G::CP + 2 <= W) {
-        unsigned raw[5][G::NB];
+    if constexpr (PLANAR) {
+        static_assert(YuvPlanarGeom<E>::NS * 2 == G::NB, "the planar staging fills the interleaved kernel's raw[]");
+        const size_t planeElems = static_cast<size_t>(H) * W;
+        const E* cb = cbcr + 2 * n * planeElems;
+        const E* cr = cb + planeElems; // H * W * sizeof(E) bytes behind Cb: aligned as Cb is only if that is a multiple of 4
+        // chroma rows y - 2 .. y + 2 (clamped to the plane) of both planes.  With a pitch that is a multiple of 4 bytes and both planes on a dword every
+        // row is: one decision for the wave, the ten loads of an interior lane in flight before the first is used.  Otherwise each row of each plane
+        // decides for itself (an odd W puts every other 16-bit row and every fourth 8-bit row on a dword)
+        const bool inside = yuv_planar_inside<E>(x0, W);
+        const bool planesAligned = ((reinterpret_cast<size_t>(cb) | reinterpret_cast<size_t>(cr)) & 3) == 0 && (static_cast<size_t>(W) * G::ES) % 4 == 0;
+        if (planesAligned && inside) {
+            unsigned raw[5][G::NB];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) yuv_load_chroma<R, E, true>(plane + static_cast<size_t>(min(max(y - 2 + i, 0), H - 1)) * W * 2, x0, W, raw[i]);
+            for (int i = 0; i < 5; ++i) {
+                const size_t ro = static_cast<size_t>(min(max(y - 2 + i, 0), H - 1)) * W;
+                yuv_load_plane<E, true>(cb + ro, x0, W, 0, raw[i]);
+                yuv_load_plane<E, true>(cr + ro, x0, W, 1, raw[i]);
+            }
 #pragma unroll
-        for (int i = 0; i < 5; ++i) yuv_hfilter<R, E>(P, raw[i], h[i]);
+            for (int i = 0; i < 5; ++i) yuv_hfilter<R, E>(P, raw[i], h[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const size_t ro = static_cast<size_t>(min(max(y - 2 + i, 0), H - 1)) * W;
+                unsigned raw[G::NB];
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const E* row = (c ? cr : cb) + ro;
+                    if (inside && (reinterpret_cast<size_t>(row) & 3) == 0) yuv_load_plane<E, true>(row, x0, W, c, raw);
+                    else yuv_load_plane<E, false>(row, x0, W, c, raw);
+                }
+                yuv_hfilter<R, E>(P, raw, h[i]);
+            }
+        }
     } else {
+        const E* plane = cbcr + n * H * W * 2;
+
+        // chroma rows y - 2 .. y + 2 (clamped to the plane), resampled to the lane's output columns.  Whether a row starts on a dword is the same for
+        // every row of a plane whose pitch is a multiple of 4 bytes: one decision for the wave, and all fifteen loads of an interior lane are in flight
+        // before the first is used
+        const bool chromaAligned = (reinterpret_cast<size_t>(plane) & 3) == 0 && (static_cast<size_t>(W) * 2 * G::ES) % 4 == 0;
+        if (chromaAligned && x0 >= 2 && x0 + G::CP + 2 <= W) {
+            unsigned raw[5][G::NB];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            unsigned raw[G::NB];
-            yuv_load_chroma<R, E, false>(plane + static_cast<size_t>(min(max(y - 2 + i, 0), H - 1)) * W * 2, x0, W, raw);
-            yuv_hfilter<R, E>(P, raw, h[i]);
+            for (int i = 0; i < 5; ++i) yuv_load_chroma<R, E, true>(plane + static_cast<size_t>(min(max(y - 2 + i, 0), H - 1)) * W * 2, x0, W, raw[i]);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) yuv_hfilter<R, E>(P, raw[i], h[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                unsigned raw[G::NB];
+                yuv_load_chroma<R, E, false>(plane + static_cast<size_t>(min(max(y - 2 + i, 0), H - 1)) * W * 2, x0, W, raw);
+                yuv_hfilter<R, E>(P, raw, h[i]);
+            }
         }
     }
 
@@ -170,9 +254,15 @@ __global__ __launch_bounds__(256) void yuv_rgb_kernel(YuvRgbParams P, const E* _
     yuv_rgb_body<R, C, E>(P, yhi, cbcr, out);
 }
 
+template <int R, int C, typename E>
+__global__ __launch_bounds__(256) void yuv_rgb_planar_kernel(YuvRgbParams P, const E* __restrict__ yhi, const E* __restrict__ chroma, E* __restrict__ out) {
+    yuv_rgb_body<R, C, E, true>(P, yhi, chroma, out);
+}
+
 struct YuvRgbPlan : snnhip_plan {
     snnhip_yuv_rgb_desc d;
     YuvRgbParams P;
+    bool planar = false; // the chroma input is [2N][H][W][1] (snnhip_yuv_rgb_planar_plan_create)
 
     template <typename E>
     void launch(const snnhip_tensor* y, const snnhip_tensor* c, snnhip_tensor* out) {
@@ -181,11 +271,31 @@ struct YuvRgbPlan : snnhip_plan {
         const E* csrc = reinterpret_cast<const E*>(c->data);
         E* dst = reinterpret_cast<E*>(out->data);
         dispatch_r_c<3, 4>(d.r, d.C, [&](auto R, auto C) {
-            SNNHIP_LAUNCH((yuv_rgb_kernel<decltype(R)::value, decltype(C)::value, E>), grid, dim3(256), 0, ctx->stream, P, ysrc, csrc, dst);
+            if (planar) SNNHIP_LAUNCH((yuv_rgb_planar_kernel<decltype(R)::value, decltype(C)::value, E>), grid, dim3(256), 0, ctx->stream, P, ysrc, csrc, dst);
+            else SNNHIP_LAUNCH((yuv_rgb_kernel<decltype(R)::value, decltype(C)::value, E>), grid, dim3(256), 0, ctx->stream, P, ysrc, csrc, dst);
         });
     }
 
+    int run_planar(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) {
+        const int R2 = 2 * d.r;
+        SNNHIP_REQUIRE(nIn == 2, "yuv_rgb_planar: expects 2 inputs (Yhi, the planar chroma tensor), got %d", nIn);
+        SNNHIP_REQUIRE(in[0]->dtype == d.dtype && in[1]->dtype == d.dtype && out->dtype == d.dtype, "yuv_rgb_planar: every tensor must have dtype %d, got %d, %d and %d", d.dtype,
+                       in[0]->dtype, in[1]->dtype, out->dtype);
+        SNNHIP_REQUIRE(dims_match(in[1], 2 * d.N, d.H, d.W, 1),
+                       "yuv_rgb_planar: the chroma tensor is %dx%dx%dx%d, the plan was built for %dx%dx%dx1 ([2N][H][W][1]: plane 2n is Cb, 2n + 1 Cr of image n)", in[1]->n,
+                       in[1]->h, in[1]->w, in[1]->c, 2 * d.N, d.H, d.W);
+        SNNHIP_REQUIRE(dims_match(in[0], d.N, R2 * d.H, R2 * d.W, 1), "yuv_rgb_planar: Yhi is %dx%dx%dx%d beside %dx%d chroma planes: it must be %dx%dx%dx1 (2r = %d times a plane)",
+                       in[0]->n, in[0]->h, in[0]->w, in[0]->c, d.H, d.W, d.N, R2 * d.H, R2 * d.W, R2);
+        SNNHIP_REQUIRE(dims_match(out, d.N, R2 * d.H, R2 * d.W, d.C), "yuv_rgb_planar: the output is %dx%dx%dx%d, expected %dx%dx%dx%d (2r = %d times a chroma plane)", out->n,
+                       out->h, out->w, out->c, d.N, R2 * d.H, R2 * d.W, d.C, R2);
+        if (d.dtype == SNNHIP_U8) launch<unsigned char>(in[0], in[1], out);
+        else launch<unsigned short>(in[0], in[1], out);
+        SNNHIP_CHECK_HIP(hipGetLastError());
+        return SNNHIP_OK;
+    }
+
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
+        if (planar) return run_planar(in, nIn, out);
         const int R2 = 2 * d.r;
         SNNHIP_REQUIRE(nIn == 2, "yuv_rgb: expects 2 inputs (Yhi, the chroma plane), got %d", nIn);
         SNNHIP_REQUIRE(in[0]->dtype == d.dtype && in[1]->dtype == d.dtype && out->dtype == d.dtype, "yuv_rgb: every tensor must have dtype %d, got %d, %d and %d", d.dtype,
@@ -226,8 +336,9 @@ int snnhip_yuv_rgb_coefficients(int maxval, int range, float kr, float kb, float
     return SNNHIP_OK;
 }
 
-int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc, snnhip_plan** out) {
-    SNNHIP_REQUIRE(ctx && desc && out, "yuv_rgb_plan_create: null argument");
+// snnhip_yuv_rgb_plan_create and snnhip_yuv_rgb_planar_plan_create: one desc, one set of checks, tables and coefficients
+static int yuv_rgb_plan_make(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc, snnhip_plan** out, bool planar) {
+    SNNHIP_REQUIRE(ctx && desc && out, "%s: null argument", planar ? "yuv_rgb_planar_plan_create" : "yuv_rgb_plan_create");
     SNNHIP_REQUIRE(desc->N > 0 && desc->H > 0 && desc->W > 0, "yuv_rgb desc: bad dims %dx%dx%d", desc->N, desc->H, desc->W);
     SNNHIP_REQUIRE(desc->C == 3 || desc->C == 4, "yuv_rgb desc: %d channels (3: RGB, 4: RGBA)", desc->C);
     SNNHIP_REQUIRE(desc->r >= 1 && desc->r <= 4, "yuv_rgb desc: r = %d (an integer 1..4)", desc->r);
@@ -258,6 +369,7 @@ int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc,
     plan->rawInput = desc->dtype;
     plan->rawOutput = desc->dtype;
     plan->d = *desc;
+    plan->planar = planar;
     plan->P = YuvRgbParams{};
     plan->P.N = desc->N;
     plan->P.H = desc->H;
@@ -278,12 +390,16 @@ int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc,
     plan->bytes = (outPixels + chromaElems + outPixels * desc->C) * (bits / 8); // Yhi, the chroma plane and the output: once each
     plan->flops = outPixels * (2.0 * 2.0 * 4.0 * (1.0 + 1.0 / R2) + 12.0);        // two planes, 4 taps per pass (the horizontal pass shared by 2r rows), the matrix
     char buf[280];
-    snprintf(buf, sizeof(buf), "yuv_rgb_u%d r=%d c=%d siting=%s range=%s tile=%dx%d %dx%d -> %dx%d maxval=%d shift=%d kr=%g kb=%g kernel=yuv_rgb_kernel", bits, desc->r, desc->C,
+    snprintf(buf, sizeof(buf), "%s%d r=%d c=%d siting=%s range=%s tile=%dx%d %dx%d -> %dx%d maxval=%d shift=%d kr=%g kb=%g kernel=%s", planar ? "yuv_rgb_planar_u" : "yuv_rgb_u", bits, desc->r, desc->C,
              desc->siting == SNNHIP_SITING_LEFT ? "left" : "centre", desc->range == SNNHIP_RANGE_LIMITED ? "limited" : "full", th, tw, desc->H, desc->W, R2 * desc->H,
-             R2 * desc->W, desc->maxval, desc->shift, desc->kr, desc->kb);
+             R2 * desc->W, desc->maxval, desc->shift, desc->kr, desc->kb, planar ? "yuv_rgb_planar_kernel" : "yuv_rgb_kernel");
     plan->desc = buf;
     *out = plan;
     return SNNHIP_OK;
 }
+
+int snnhip_yuv_rgb_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc, snnhip_plan** out) { return yuv_rgb_plan_make(ctx, desc, out, false); }
+
+int snnhip_yuv_rgb_planar_plan_create(snnhip_ctx* ctx, const snnhip_yuv_rgb_desc* desc, snnhip_plan** out) { return yuv_rgb_plan_make(ctx, desc, out, true); }
 
 } // extern "C"

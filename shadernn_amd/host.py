@@ -24,6 +24,9 @@ SIGNATURES = {
     "snn_model_create9": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create10": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create11": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create12": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_upload_frame_planes": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
+    "snn_model_download_frame_planes": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     "snn_model_upload_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_download_frame_nv12": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u16": (C.c_int, [_P, _P]),
@@ -173,7 +176,15 @@ class EncodeIO(C.Structure):
     _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
 
 
-VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6)}  # name: (SNN_IO_NV12 / SNN_IO_NV12_16, maxval, shift)
+class PlanarIO(C.Structure):
+    """snn_planar_io (include/snn_c.h): planar 4:2:0 frames (I420 / I010) in and out around a luma-only model; the luma maps follow from the range."""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("maxval", C.c_int), ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int),
+                ("kr", C.c_float), ("kb", C.c_float), ("out_w", C.c_int), ("out_h", C.c_int)]
+
+
+# name: (SNN_IO_NV12 / SNN_IO_NV12_16 / SNN_IO_I420 / SNN_IO_I420_16, maxval, shift); I010 is ffmpeg's yuv420p10le: 10 bits in the low end of 2 bytes
+VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6), "I420": (0x401, 255, 0), "I010": (0x501, 1023, 0)}
+PLANAR_FORMATS = ("I420", "I010")
 SITINGS = {"centre": 0, "left": 1}  # SNN_SITING_*
 VIDEO_RANGES = {"limited": 0, "full": 1}  # SNN_RANGE_*
 VIDEO_OUT_FORMATS = {"RGB8": (0x201, 3), "RGBA8": (0x201, 4), "RGB16": (0x301, 3), "RGBA16": (0x301, 4)}  # name: (the input format it pairs with, channels)
@@ -210,8 +221,13 @@ class Model:
         RGB frame in one launch behind the model (siting, kr, kb as above).  in_means / in_norms / out_scale / out_offset are not used.
         out_size (w, h) beside video alone (snn_model_create11): the NV12 / P010 frame comes back at that size, both even, between half and all of
         r times the input on each axis -- the model's luma frame and the original chroma plane resampled on the device, two launches behind the
-        model's (no chroma launch); output_frame / download_frame return the pair (y, cbcr) at h x w and h/2 x w/2."""
+        model's (no chroma launch); output_frame / download_frame return the pair (y, cbcr) at h x w and h/2 x w/2.
+        video "I420" / "I010" (snn_model_create12): planar 4:2:0 frames, what software decoders and encoders use -- everything above for "NV12" /
+        "P010" with the triple (y, cb, cr) in place of the pair: alone (the same planar format comes back), with out_size, with video_out "RGB8" /
+        "RGBA8" ("I420") or "RGB16" / "RGBA16" ("I010"); and colour "RGB8" / "RGBA8" with video_out "I420".  video_range sets the luma plane's maps on
+        every one of them (in_means / in_norms / out_scale / out_offset are not used).  upload_planes / download_planes take arrays with a row pitch."""
         self.h = _P()
+        self.planar = False
         self.colour_channels = 0
         self.video = video
         self.video_out_channels = 0
@@ -221,19 +237,23 @@ class Model:
         if colour is not None and video_out is not None:
             assert video is None, "colour frames go in: video= names NV12 / P010 frames at the input"
             assert colour in ("RGB8", "RGBA8"), "colour is \"RGB8\" or \"RGBA8\""
-            assert video_out == "NV12", "a colour frame leaves as video_out=\"NV12\""
+            assert video_out in ("NV12", "I420"), "a colour frame leaves as video_out=\"NV12\" or \"I420\""
             assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
             assert siting in SITINGS, "siting is \"left\" or \"centre\""
             assert input_format is None and output_format is None, "colour frames replace input_format / output_format"
             assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
             channels = {"RGB8": 3, "RGBA8": 4}[colour]
             self.frame_dtypes = (np.uint8, np.uint8)
-            io = EncodeIO(FRAME_FORMATS[colour], VIDEO_FORMATS["NV12"][0], SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
-            assert lib().snn_model_create10(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                            int(batch), C.byref(io), C.byref(self.h)) == 0
             self.encode = True
             self.batch = batch
             self.in_shape = (h, w, channels) if batch == 1 else (batch, h, w, channels)
+            if video_out == "I420":
+                io = PlanarIO(FRAME_FORMATS[colour], VIDEO_FORMATS["I420"][0], 255, 0, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, 0, 0)
+                self._create12(json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io)
+                return
+            io = EncodeIO(FRAME_FORMATS[colour], VIDEO_FORMATS["NV12"][0], SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
+            assert lib().snn_model_create10(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                            int(batch), C.byref(io), C.byref(self.h)) == 0
             return
         if video_out is not None:
             assert video is not None, "video_out needs video=\"NV12\" or \"P010\""
@@ -243,26 +263,41 @@ class Model:
             assert input_format is None and output_format is None and colour is None, "video frames replace input_format / output_format / colour"
             fmt, maxval, shift = VIDEO_FORMATS[video]
             pair, channels = VIDEO_OUT_FORMATS[video_out]
-            assert pair == fmt, "%s frames come back as %s" % (video, "RGB8 / RGBA8" if fmt == 0x201 else "RGB16 / RGBA16")
+            wide = fmt in (0x301, 0x501)
+            assert pair == (0x301 if wide else 0x201), "%s frames come back as %s" % (video, "RGB16 / RGBA16" if wide else "RGB8 / RGBA8")
             assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
             maxval = maxval if video_maxval is None else video_maxval
             shift = shift if video_shift is None else video_shift
-            dt = np.uint8 if fmt == 0x201 else np.uint16
+            dt = np.uint16 if wide else np.uint8
             self.frame_dtypes = (dt, dt)
-            io = VideoRgbIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
-            assert lib().snn_model_create9(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                           int(batch), C.byref(io), C.byref(self.h)) == 0
             self.video_out_channels = channels
             self.batch = batch
             self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
+            if video in PLANAR_FORMATS:
+                io = PlanarIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, 0, 0)
+                self._create12(json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io)
+                return
+            io = VideoRgbIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
+            assert lib().snn_model_create9(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                           int(batch), C.byref(io), C.byref(self.h)) == 0
             return
         if video is not None:
             assert input_format is None and output_format is None and colour is None, "video frames replace input_format / output_format / colour"
             fmt, maxval, shift = VIDEO_FORMATS[video]
             maxval = maxval if video_maxval is None else video_maxval
             shift = shift if video_shift is None else video_shift
-            dt = np.uint8 if fmt == 0x201 else np.uint16
+            dt = np.uint16 if fmt in (0x301, 0x501) else np.uint8
             self.frame_dtypes = (dt, dt)
+            self.batch = batch
+            self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
+            if video in PLANAR_FORMATS:
+                assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
+                assert siting in SITINGS, "siting is \"left\" or \"centre\""
+                ow, oh = (int(out_size[0]), int(out_size[1])) if out_size is not None else (0, 0)
+                io = PlanarIO(fmt, fmt, maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, ow, oh)
+                self._create12(json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io)
+                self.out_size = (ow, oh) if out_size is not None else None
+                return
             io = VideoIO(fmt, maxval, shift, SITINGS[siting], in_means[0], in_norms[0], out_scale[0], out_offset[0])
             if out_size is not None:
                 fit = FitIO(io, int(out_size[0]), int(out_size[1]))
@@ -272,8 +307,6 @@ class Model:
             else:
                 assert lib().snn_model_create8(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
                                                int(batch), C.byref(io), C.byref(self.h)) == 0
-            self.batch = batch
-            self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
             return
         if colour is not None:
             assert input_format is None and output_format is None, "colour frames replace input_format / output_format"
@@ -299,8 +332,15 @@ class Model:
         self.batch = batch
         self.in_shape = (h, w, c) if batch == 1 else (batch, h, w, c)
 
+    def _create12(self, json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io):
+        assert lib().snn_model_create12(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
+                                        int(batch), C.byref(io), C.byref(self.h)) == 0
+        self.planar = True
+
     def upload_frame(self, img):
         """uint8 (uint16 for a 16-bit input format) [batch x] H x W x C into the model's input frame (no per-call allocation)."""
+        if self.video and self.planar:
+            return self._upload_planar(*img)
         if self.video:
             return self._upload_video(*img)
         img = np.ascontiguousarray(img, dtype=self.frame_dtypes[0]).reshape(self.in_shape)
@@ -311,6 +351,9 @@ class Model:
         """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
+        video_end = self.out_size is not None or (self.video and not self.video_out_channels) or self.encode
+        if video_end and self.planar:
+            return self._download_planar(*((self.out_size[1], self.out_size[0]) if self.out_size is not None else (d[0], d[1])))
         if self.out_size is not None:
             return self._download_video(self.out_size[1], self.out_size[0])
         if (self.video and not self.video_out_channels) or self.encode:
@@ -340,6 +383,49 @@ class Model:
         y = frames[:, :oh * ow].reshape(n, oh, ow)
         cbcr = frames[:, oh * ow:].reshape(n, oh // 2, ow // 2, 2)
         return (y[0].copy(), cbcr[0].copy()) if n == 1 else (y.copy(), cbcr.copy())
+
+    def _plane_args(self, planes, dtype):
+        """(pointer array, pitch array, n_planes) of snn_model_upload_frame_planes / _download_frame_planes from batch * n_planes 2-D arrays, frame
+        by frame (Y, Cb, Cr; or Y, CbCr with the interleaved plane as rows of W elements): rows contiguous, strides[0] the pitch in bytes, the same
+        for that plane of every frame."""
+        planes = list(planes)
+        assert planes and len(planes) % self.batch == 0, "batch * n_planes arrays, frame by frame"
+        k = len(planes) // self.batch
+        for a in planes:
+            assert isinstance(a, np.ndarray) and a.ndim == 2 and a.dtype == dtype and a.strides[1] == a.itemsize and a.strides[0] >= 0, "2-D %s arrays with contiguous rows" % np.dtype(dtype).name
+        pitches = [planes[p].strides[0] for p in range(k)]
+        for i, a in enumerate(planes):
+            assert a.strides[0] == pitches[i % k], "one pitch per plane, the same for every frame"
+        return (C.c_void_p * len(planes))(*[a.ctypes.data for a in planes]), (C.c_int * k)(*pitches), k, planes
+
+    def upload_planes(self, planes):
+        """snn_model_upload_frame_planes: batch * n_planes 2-D arrays with any row pitch (views into wider buffers: ffmpeg's data[] / linesize[]),
+        frame by frame -- Y, Cb, Cr on a planar end, Y, CbCr (rows of W interleaved elements) on an NV12 / P010 end.  Padding is never read."""
+        ptrs, pitches, k, keep = self._plane_args(planes, self.frame_dtypes[0])
+        assert lib().snn_model_upload_frame_planes(self.h, ptrs, pitches, k) == 0
+        del keep
+
+    def download_planes(self, planes):
+        """snn_model_download_frame_planes into the caller's (writable) arrays, laid out as for upload_planes at the output's extent; only each
+        row's own bytes are written."""
+        ptrs, pitches, k, keep = self._plane_args(planes, self.frame_dtypes[1])
+        assert all(a.flags.writeable for a in keep)
+        assert lib().snn_model_download_frame_planes(self.h, ptrs, pitches, k) == 0
+
+    def _upload_planar(self, y, cb, cr):
+        """(y, cb, cr), [batch x] H x W and twice [batch x] H/2 x W/2 -> snn_model_upload_frame_planes with tight pitches"""
+        dt, n = self.frame_dtypes[0], self.batch
+        h, w = self.in_shape[-3], self.in_shape[-2]
+        y = np.ascontiguousarray(y, dtype=dt).reshape(n, h, w)
+        cb = np.ascontiguousarray(cb, dtype=dt).reshape(n, h // 2, w // 2)
+        cr = np.ascontiguousarray(cr, dtype=dt).reshape(n, h // 2, w // 2)
+        self.upload_planes([a[i] for i in range(n) for a in (y, cb, cr)])
+
+    def _download_planar(self, oh, ow):
+        dt, n = self.frame_dtypes[1], self.batch
+        y, cb, cr = np.empty((n, oh, ow), dt), np.empty((n, oh // 2, ow // 2), dt), np.empty((n, oh // 2, ow // 2), dt)
+        self.download_planes([a[i] for i in range(n) for a in (y, cb, cr)])
+        return (y[0], cb[0], cr[0]) if n == 1 else (y, cb, cr)
 
     def upload(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.in_shape)

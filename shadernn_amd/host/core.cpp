@@ -108,11 +108,11 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
                         cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset, frameIn && isFrame16Format(id.format),
                         frameOut && isFrame16Format(cp.outputFormat), cp.frameInShift, cp.frameOutMaxval, cp.frameOutShift);
         if (cp.colourChannels) hb->initColourIO(cp.colourChannels, cp.colourKr, cp.colourKb);
-        if (cp.encodeChannels) hb->initEncodeIO(cp.encodeChannels, cp.encodeSiting, cp.encodeRange, cp.colourKr, cp.colourKb);
+        if (cp.encodeChannels) hb->initEncodeIO(cp.encodeChannels, cp.encodeSiting, cp.encodeRange, cp.colourKr, cp.colourKb, cp.videoPlanar);
         if (cp.videoDtype && cp.videoRgbChannels)
-            hb->initVideoRgbIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoRgbChannels, cp.videoRange, cp.videoKr, cp.videoKb);
-        else if (cp.videoDtype && cp.fitW) hb->initVideoFitIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.fitW, cp.fitH);
-        else if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting);
+            hb->initVideoRgbIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoRgbChannels, cp.videoRange, cp.videoKr, cp.videoKb, cp.videoPlanar);
+        else if (cp.videoDtype && cp.fitW) hb->initVideoFitIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.fitW, cp.fitH, cp.videoPlanar);
+        else if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoPlanar);
         frameBackend = hb;
     }
     backend->finalizeStages(stages, cp.dumpOutputs, cp.fuseChains);
@@ -141,6 +141,7 @@ snnhip_tensor* MixedInferenceCore::frameInput() const { return frameBackend ? fr
 snnhip_tensor* MixedInferenceCore::frameOutput() const { return frameBackend ? frameBackend->frameOutput() : nullptr; }
 snnhip_tensor* MixedInferenceCore::chromaInput() const { return frameBackend ? frameBackend->chromaInput() : nullptr; }
 snnhip_tensor* MixedInferenceCore::chromaOutput() const { return frameBackend ? frameBackend->chromaOutput() : nullptr; }
+bool MixedInferenceCore::planarVideo() const { return frameBackend && frameBackend->planarVideo(); }
 bool MixedInferenceCore::encodeOutput() const { return frameBackend && frameBackend->encodeOutput(); }
 
 void MixedInferenceCore::run(RunParameters& rp) { // core.cpp:97-245

@@ -129,40 +129,46 @@ std::string HipBackend::describeColour() const {
     return s;
 }
 
-void HipBackend::initVideoIO(int dtype, int maxval, int shift, int siting) {
+void HipBackend::initVideoIO(int dtype, int maxval, int shift, int siting, bool planar) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
     int in[4], out[4];
     const int r = frameScale(frameInT, frameOutT, true, in, out);
-    snnhip_chroma_up_desc cd{in[0], in[1] / 2, in[2] / 2, 2, r, dtype, maxval, shift, siting};
+    const int cn = planar ? 2 * in[0] : in[0], cc = planar ? 1 : 2; // planar: every Cb and Cr plane is an image of one channel
+    planarChroma = planar;
+    snnhip_chroma_up_desc cd{cn, in[1] / 2, in[2] / 2, cc, r, dtype, maxval, shift, siting};
     hipChk(snnhip_chroma_up_plan_create(ctx, &cd, &chromaPlan), "snnhip_chroma_up_plan_create");
-    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
-    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1] / 2, out[2] / 2, 2, dtype, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
+    hipChk(snnhip_tensor_alloc(ctx, cn, in[1] / 2, in[2] / 2, cc, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
+    hipChk(snnhip_tensor_alloc(ctx, cn, out[1] / 2, out[2] / 2, cc, dtype, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
 }
 
-void HipBackend::initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb) {
+void HipBackend::initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb, bool planar) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
     int in[4], out[4];
     const int r = frameScale(frameInT, frameOutT, true, in, out);
     snnhip_yuv_rgb_desc yd{in[0], in[1] / 2, in[2] / 2, channels, r, dtype, maxval, shift, siting, range, kr, kb};
-    hipChk(snnhip_yuv_rgb_plan_create(ctx, &yd, &yuvRgbPlan), "snnhip_yuv_rgb_plan_create");
-    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
+    planarChroma = planar;
+    if (planar) hipChk(snnhip_yuv_rgb_planar_plan_create(ctx, &yd, &yuvRgbPlan), "snnhip_yuv_rgb_planar_plan_create");
+    else hipChk(snnhip_yuv_rgb_plan_create(ctx, &yd, &yuvRgbPlan), "snnhip_yuv_rgb_plan_create");
+    hipChk(snnhip_tensor_alloc(ctx, planar ? 2 * in[0] : in[0], in[1] / 2, in[2] / 2, planar ? 1 : 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
     hipChk(snnhip_tensor_alloc(ctx, out[0], out[1], out[2], channels, dtype, &rgbOutT), "snnhip_tensor_alloc (RGB output frame)");
 }
 
-void HipBackend::initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH) {
+void HipBackend::initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH, bool planar) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
     int in[4], out[4];
     (void) frameScale(frameInT, frameOutT, true, in, out);
     snnhip_plane_fit_desc ld{out[0], out[1], out[2], 1, outH, outW, dtype, maxval, shift, SNNHIP_SITING_CENTRE}; // a luma plane always uses centre
     hipChk(snnhip_plane_fit_plan_create(ctx, &ld, &fitLumaPlan), "snnhip_plane_fit_plan_create (luma)");
-    snnhip_plane_fit_desc cd{in[0], in[1] / 2, in[2] / 2, 2, outH / 2, outW / 2, dtype, maxval, shift, siting};
+    const int cn = planar ? 2 * in[0] : in[0], cc = planar ? 1 : 2;
+    planarChroma = planar;
+    snnhip_plane_fit_desc cd{cn, in[1] / 2, in[2] / 2, cc, outH / 2, outW / 2, dtype, maxval, shift, siting};
     hipChk(snnhip_plane_fit_plan_create(ctx, &cd, &fitChromaPlan), "snnhip_plane_fit_plan_create (chroma)");
-    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1] / 2, in[2] / 2, 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
+    hipChk(snnhip_tensor_alloc(ctx, cn, in[1] / 2, in[2] / 2, cc, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
     hipChk(snnhip_tensor_alloc(ctx, out[0], outH, outW, 1, dtype, &fitLumaT), "snnhip_tensor_alloc (fitted luma plane)");
-    hipChk(snnhip_tensor_alloc(ctx, out[0], outH / 2, outW / 2, 2, dtype, &chromaOutT), "snnhip_tensor_alloc (fitted chroma plane)");
+    hipChk(snnhip_tensor_alloc(ctx, cn, outH / 2, outW / 2, cc, dtype, &chromaOutT), "snnhip_tensor_alloc (fitted chroma plane)");
 }
 
-void HipBackend::initEncodeIO(int channels, int siting, int range, float kr, float kb) {
+void HipBackend::initEncodeIO(int channels, int siting, int range, float kr, float kb, bool planar) {
     SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == SNNHIP_U8 && snnhip_tensor_dtype(frameOutT) == SNNHIP_U8);
     int in[4], out[4];
     const int r = frameScale(frameInT, frameOutT, false, in, out);
@@ -170,9 +176,11 @@ void HipBackend::initEncodeIO(int channels, int siting, int range, float kr, flo
     snnhip_rgb_luma_desc ld{in[0], in[1], in[2], channels, kr, kb};
     hipChk(snnhip_rgb_luma_plan_create(ctx, &ld, &lumaPlan), "snnhip_rgb_luma_plan_create");
     snnhip_rgb_cbcr_desc cd{in[0], in[1], in[2], channels, r, siting, range, kr, kb};
-    hipChk(snnhip_rgb_cbcr_plan_create(ctx, &cd, &cbcrPlan), "snnhip_rgb_cbcr_plan_create");
+    planarChroma = planar;
+    if (planar) hipChk(snnhip_rgb_cbcr_planar_plan_create(ctx, &cd, &cbcrPlan), "snnhip_rgb_cbcr_planar_plan_create");
+    else hipChk(snnhip_rgb_cbcr_plan_create(ctx, &cd, &cbcrPlan), "snnhip_rgb_cbcr_plan_create");
     hipChk(snnhip_tensor_alloc(ctx, in[0], in[1], in[2], channels, SNNHIP_U8, &colourInT), "snnhip_tensor_alloc (colour input frame)");
-    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1] / 2, out[2] / 2, 2, SNNHIP_U8, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
+    hipChk(snnhip_tensor_alloc(ctx, planar ? 2 * out[0] : out[0], out[1] / 2, out[2] / 2, planar ? 1 : 2, SNNHIP_U8, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
 }
 
 std::string HipBackend::describeVideo() const {

@@ -126,17 +126,21 @@ public:
     // NV12 / P010 video frames around a luma-only model (CreationParameters::videoDtype): called after initFrameIO with R8 / R16 frames at both
     // ends.  The luma plane IS the model's frame; the chroma plan upsamples the CbCr plane [n][H/2][W/2][2] to [n][rH/2][rW/2][2] in runFrameOut,
     // one launch more on the context's stream behind everything else of an inference (a straight line: no side stream, no parallel graph branch).
-    void initVideoIO(int dtype, int maxval, int shift, int siting);
+    void initVideoIO(int dtype, int maxval, int shift, int siting, bool planar = false);
     // ... or to packed RGB (CreationParameters::videoRgbChannels): the yuv_rgb plan builds the RGB / RGBA output frame [n][rH][rW][channels] from the
     // model's output luma frame and the ORIGINAL CbCr plane in runFrameOut, in the chroma launch's place (no chroma plan, no upscaled chroma plane)
-    void initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb);
+    void initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb, bool planar = false);
     // ... or to an NV12 / P010 frame of any size between half and all of the model's output (CreationParameters::fitW / fitH): two plane_fit plans in
     // runFrameOut, the model's output luma frame to [n][outH][outW][1] and the ORIGINAL CbCr plane to [n][outH/2][outW/2][2] (no chroma plan)
-    void initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH);
+    void initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH, bool planar = false);
     // RGB8 / RGBA8 frames in, an NV12 frame out (CreationParameters::encodeChannels): called after initFrameIO with R8 frames at both ends.  The luma
     // plan of initColourIO fills the model's input frame in runFrameIn; the model's output frame IS the NV12 frame's luma plane; the rgb_cbcr plan
     // builds its chroma plane [n][rH/2][rW/2][2] from the colour input frame in runFrameOut (no merge plan, no colour output frame)
-    void initEncodeIO(int channels, int siting, int range, float kr, float kb);
+    void initEncodeIO(int channels, int siting, int range, float kr, float kb, bool planar = false);
+    // `planar` on the four above (CreationParameters::videoPlanar, I420 / I010): the chroma tensors are [2n][h][w][1], plane 2k = Cb and 2k + 1 = Cr of
+    // frame k; chroma_up and plane_fit run with C = 1 over the 2n planes, yuv_rgb and rgb_cbcr as snnhip_yuv_rgb_planar_plan_create /
+    // snnhip_rgb_cbcr_planar_plan_create.  The launches are the same in number and place
+    bool planarVideo() const { return planarChroma; }
     bool encodeOutput() const { return cbcrPlan != nullptr; }
     int videoLaunches() const { return fitLumaPlan ? 2 : chromaPlan || yuvRgbPlan || cbcrPlan ? 1 : 0; }
     std::string describeVideo() const; // one line for every extra launch (empty without video frames)
@@ -158,6 +162,7 @@ private:
     snnhip_plan* cbcrPlan = nullptr;                            // owned (its output is chromaOutT, its input colourInT)
     snnhip_plan *fitLumaPlan = nullptr, *fitChromaPlan = nullptr; // owned (the chroma plan runs chromaInT -> chromaOutT)
     snnhip_tensor* fitLumaT = nullptr;                          // owned, SNNHIP_U8 / SNNHIP_U16 [n][outH][outW][1]
+    bool planarChroma = false;                                  // chromaInT / chromaOutT are [2n][h][w][1]
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

@@ -93,6 +93,10 @@ public:
         // snnhip_rgb_luma_plan_create's launch in front of the model, as colourChannels does, and snnhip_rgb_cbcr_plan_create's behind it, from the
         // colour input frame to the output frame's chroma plane (encodeSiting SNNHIP_SITING_*, encodeRange SNNHIP_RANGE_*, matrix colourKr / colourKb)
         int encodeChannels = 0, encodeSiting = 1, encodeRange = 0;
+        // HIP extension: planar 4:2:0 frames (I420 / I010, snn_model_create12) on the video end(s) of any of the four paths above: the chroma tensors
+        // are [2 * batch][h][w][1] (plane 2n = Cb, 2n + 1 = Cr of frame n) instead of [batch][h][w][2]; chroma_up and plane_fit run with C = 1 over
+        // the 2 * batch planes, yuv_rgb and rgb_cbcr as their planar plans.  The same number of launches; no interleaving launch anywhere
+        bool videoPlanar = false;
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const std::string& modelFileName, const dp::ShaderGenOptions& options,
@@ -108,6 +112,7 @@ public:
     snnhip_tensor* frameOutput() const;
     snnhip_tensor* chromaInput() const; // the CbCr planes of a video model (snn_model_create8), null otherwise
     snnhip_tensor* chromaOutput() const;
+    bool planarVideo() const;  // the chroma tensors are planar [2 * batch][h][w][1] (snn_model_create12)
     bool encodeOutput() const; // the output is the NV12 frame of snn_model_create10: frameOutput() its luma plane, chromaOutput() its CbCr plane
 
 private:

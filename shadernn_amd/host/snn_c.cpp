@@ -10,6 +10,7 @@
 #include "ic2/layerFactory.h"
 #include "snn/contextFactory.h"
 #include "snn/core.h"
+#include "snn/planes.h"
 
 using namespace snn;
 
@@ -21,6 +22,7 @@ struct snn_model {
     int inW = 0, inH = 0, inC = 0, batch = 1;
     bool half = false;
     SNNModelOutput modelOutput;
+    std::vector<char> staging; // host buffer of snn_model_upload_frame_planes / _download_frame_planes for planes that are not tight and adjacent
 };
 
 static dp::ShaderGenOptions makeOptions(int w, int h, int c, bool fuse, bool half = false, int batch = 1) {
@@ -105,10 +107,11 @@ int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int
 // snn_model_create6 / 7 / 8: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends, `video`
 // (snn_model_create8) for NV12 / P010 frames around a model that `io` gives R8 / R16 frames, `videoRgb` (snn_model_create9, beside `video`) for an RGB
 // frame at the output instead of NV12 / P010, `encode` (snn_model_create10) for RGB8 / RGBA8 frames in and an NV12 frame out around a model that `io`
-// gives R8 frames, `fit` (snn_model_create11, beside `video`) for an NV12 / P010 output frame of fit->out_w x fit->out_h instead of r times the input
+// gives R8 frames, `fit` (snn_model_create11, beside `video`) for an NV12 / P010 output frame of fit->out_w x fit->out_h instead of r times the input,
+// `planar` (snn_model_create12, beside `video` or `encode`) for I420 / I010 planes instead of the interleaved chroma plane on the video end(s)
 static int createModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
                        int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out, const snn_video_io* video = nullptr,
-                       const snn_video_rgb_io* videoRgb = nullptr, const snn_encode_io* encode = nullptr, const snn_fit_io* fit = nullptr) {
+                       const snn_video_rgb_io* videoRgb = nullptr, const snn_encode_io* encode = nullptr, const snn_fit_io* fit = nullptr, bool planar = false) {
     if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
     ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
     if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
@@ -139,6 +142,7 @@ static int createModel(const char* json_path, int device, int in_w, int in_h, in
         cp.captureGraph = capture_graph != 0;
         cp.outputFormat = sgo.desiredOutputFormat;
         cp.halfTensors = half;
+        cp.videoPlanar = planar;
         if (colour || video || encode) { // the model must be luma-only: one channel out, at 1..4 times the input's extent (refused here, before anything is built on the device)
             const auto& od = cp.layers.back()->outputDesc;
             const uint32_t r = od.width / static_cast<uint32_t>(in_w);
@@ -172,7 +176,7 @@ static int createModel(const char* json_path, int device, int in_w, int in_h, in
                         for (int q = 1; q <= 4; ++q)
                             if (fit->out_w <= 1ll * q * in_w && fit->out_h <= 1ll * q * in_h && 2ll * fit->out_w >= 1ll * q * in_w && 2ll * fit->out_h >= 1ll * q * in_h)
                                 fits += (fits.empty() ? "" : ", ") + std::to_string(q);
-                        SNN_LOGE("snn_model_create11: the model is r = %u: %dx%d -> %lldx%lld, and %dx%d is %s; %s%s", r, in_w, in_h, rw, rh, fit->out_w, fit->out_h,
+                        SNN_LOGE("snn_model_create1%c: the model is r = %u: %dx%d -> %lldx%lld, and %dx%d is %s; %s%s", planar ? '2' : '1', r, in_w, in_h, rw, rh, fit->out_w, fit->out_h,
                                  (fit->out_w > rw || fit->out_h > rh) ? "larger than that" : "less than half of that", fits.empty() ? "no r = 1..4 fits both axes" : "a model of r = ",
                                  fits.c_str());
                         snn_model_destroy(m);
@@ -234,9 +238,9 @@ int snn_model_create7(const char* json_path, int device, int in_w, int in_h, int
     return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, io, out);
 }
 
-// snn_model_create8, and snn_model_create11 with `fit`
+// snn_model_create8, snn_model_create11 with `fit`, and the planar-to-planar paths of snn_model_create12 with `planar`
 static int createVideoModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                            int capture_graph, int batch, const snn_video_io* io, snn_model** out, const snn_fit_io* fit) {
+                            int capture_graph, int batch, const snn_video_io* io, snn_model** out, const snn_fit_io* fit, bool planar = false) {
     if (!io || (io->format != SNN_IO_NV12 && io->format != SNN_IO_NV12_16) || in_c != 1 || batch < 1) return -1;
     if (in_w < 2 || in_h < 2 || in_w % 2 || in_h % 2) return -1; // 4:2:0: the chroma plane is half the extent
     const bool wide = io->format == SNN_IO_NV12_16;
@@ -255,7 +259,7 @@ static int createVideoModel(const char* json_path, int device, int in_w, int in_
     io2.out_maxval = wide ? io->maxval : 65535; // (snn_model_create5 passes 65535 for the 8-bit formats: the same model)
     io2.out_shift = wide ? io->shift : 0;
     return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, io, nullptr, nullptr,
-                       fit);
+                       fit, planar);
 }
 
 int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
@@ -263,17 +267,34 @@ int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int
     return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, nullptr);
 }
 
-int snn_model_create11(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                       int prefer_half, int capture_graph, int batch, const snn_fit_io* io, snn_model** out) {
+// snn_model_create11, and the fitted path of snn_model_create12 with `planar`
+static int createFitModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
+                          int capture_graph, int batch, const snn_fit_io* io, snn_model** out, bool planar) {
     if (!io) return -1;
     if (io->out_w < 2 || io->out_h < 2 || io->out_w % 2 || io->out_h % 2) return -1; // 4:2:0 at the output too
     if (in_w < 1 || in_h < 1) return -1;
     if (2ll * io->out_w < in_w || 2ll * io->out_h < in_h || io->out_w > 4ll * in_w || io->out_h > 4ll * in_h) return -1; // the chroma plane's ratio: [1/2, 4]
-    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io->video, out, io);
+    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io->video, out, io, planar);
 }
 
-int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                      int prefer_half, int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out) {
+int snn_model_create11(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_fit_io* io, snn_model** out) {
+    return createFitModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, false);
+}
+
+// the luma plane's maps of a video frame from its range (snn_model_create9 states them): k = (maxval + 1) / 256
+static void lumaMapsOfRange(int maxval, int range, snn_video_io* video) {
+    const double k = (maxval + 1) / 256.0;
+    const double yoff = range == SNN_RANGE_LIMITED ? 16.0 * k : 0.0, yrange = range == SNN_RANGE_LIMITED ? 219.0 * k : maxval;
+    video->in_mean = static_cast<float>(yoff);
+    video->in_norm = static_cast<float>(1.0 / yrange);
+    video->out_scale = static_cast<float>(yrange);
+    video->out_offset = static_cast<float>(yoff);
+}
+
+// snn_model_create9, and the planar-to-RGB path of snn_model_create12 with `planar` (io->in_format names the interleaved format of the same depth)
+static int createVideoRgbModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
+                               int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out, bool planar) {
     if (!io || (io->in_format != SNN_IO_NV12 && io->in_format != SNN_IO_NV12_16) || in_c != 1 || batch < 1) return -1;
     const bool wide = io->in_format == SNN_IO_NV12_16;
     if (wide ? (io->out_format != SNN_IO_RGB16 && io->out_format != SNN_IO_RGBA16) : (io->out_format != SNN_IO_RGB8 && io->out_format != SNN_IO_RGBA8)) return -1;
@@ -284,17 +305,12 @@ int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int
     if ((static_cast<long long>(io->maxval) << io->shift) > (wide ? 65535 : 255)) return -1;
     if (!(io->kr > 0.0f && io->kb > 0.0f && io->kr + io->kb < 1.0f)) return -1;
     // the luma plane's maps follow from the range
-    const double k = (io->maxval + 1) / 256.0;
-    const double yoff = io->range == SNN_RANGE_LIMITED ? 16.0 * k : 0.0, yrange = io->range == SNN_RANGE_LIMITED ? 219.0 * k : io->maxval;
     snn_video_io video{};
     video.format = io->in_format;
     video.maxval = io->maxval;
     video.shift = io->shift;
     video.siting = io->siting;
-    video.in_mean = static_cast<float>(yoff);
-    video.in_norm = static_cast<float>(1.0 / yrange);
-    video.out_scale = static_cast<float>(yrange);
-    video.out_offset = static_cast<float>(yoff);
+    lumaMapsOfRange(io->maxval, io->range, &video);
     snn_frame_io2 io2{};
     io2.in_format = io2.out_format = wide ? SNN_IO_R16 : SNN_IO_R8;
     for (int c = 0; c < 4; ++c) {
@@ -306,11 +322,18 @@ int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int
     io2.in_shift = wide ? io->shift : 0;
     io2.out_maxval = wide ? io->maxval : 65535; // (as snn_model_create8)
     io2.out_shift = wide ? io->shift : 0;
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, &video, io);
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, &video, io, nullptr,
+                       nullptr, planar);
 }
 
-int snn_model_create10(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                       int prefer_half, int capture_graph, int batch, const snn_encode_io* io, snn_model** out) {
+int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out) {
+    return createVideoRgbModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, false);
+}
+
+// snn_model_create10, and the RGB-to-planar path of snn_model_create12 with `planar` (io->out_format is SNN_IO_NV12 either way)
+static int createEncodeModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
+                             int capture_graph, int batch, const snn_encode_io* io, snn_model** out, bool planar) {
     if (!io || (io->in_format != SNN_IO_RGB8 && io->in_format != SNN_IO_RGBA8) || io->out_format != SNN_IO_NV12 || in_c != 1 || batch < 1) return -1;
     if (io->siting != SNN_SITING_CENTRE && io->siting != SNN_SITING_LEFT) return -1;
     if (io->range != SNN_RANGE_LIMITED && io->range != SNN_RANGE_FULL) return -1;
@@ -327,7 +350,60 @@ int snn_model_create10(const char* json_path, int device, int in_w, int in_h, in
         io2.out_offset[c] = limited ? 16.0f : 0.0f;
     }
     io2.out_maxval = 65535; // (as snn_model_create5)
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, nullptr, nullptr, io);
+    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, nullptr, nullptr, io,
+                       nullptr, planar);
+}
+
+int snn_model_create10(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_encode_io* io, snn_model** out) {
+    return createEncodeModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, false);
+}
+
+int snn_model_create12(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_planar_io* io, snn_model** out) {
+    if (!io || in_c != 1 || batch < 1) return -1;
+    const bool fitted = io->out_w != 0 || io->out_h != 0;
+    if (io->in_format == SNN_IO_RGB8 || io->in_format == SNN_IO_RGBA8) { // capture in, planar out: snn_model_create10's path
+        if (io->out_format != SNN_IO_I420 || fitted) return -1;
+        snn_encode_io e{};
+        e.in_format = io->in_format;
+        e.out_format = SNN_IO_NV12;
+        e.siting = io->siting;
+        e.range = io->range;
+        e.kr = io->kr;
+        e.kb = io->kb;
+        return createEncodeModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &e, out, true);
+    }
+    if (io->in_format != SNN_IO_I420 && io->in_format != SNN_IO_I420_16) return -1;
+    const bool wide = io->in_format == SNN_IO_I420_16;
+    const int interleaved = wide ? SNN_IO_NV12_16 : SNN_IO_NV12;
+    if (io->out_format != io->in_format) { // planar in, RGB out: snn_model_create9's path (which checks the rest)
+        if (fitted) return -1; // (RGB output at a fitted size is not built)
+        snn_video_rgb_io v{};
+        v.in_format = interleaved;
+        v.out_format = io->out_format; // RGB8 / RGBA8 beside 8-bit planes, RGB16 / RGBA16 beside 16-bit ones: anything else is refused there
+        v.maxval = io->maxval;
+        v.shift = io->shift;
+        v.siting = io->siting;
+        v.range = io->range;
+        v.kr = io->kr;
+        v.kb = io->kb;
+        return createVideoRgbModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &v, out, true);
+    }
+    // planar in, planar out: snn_model_create8's path, or snn_model_create11's with a fitted size.  The luma maps follow from the range, which needs
+    // the depth's k = (maxval + 1) / 256 to be an integer, as in snn_model_create9 (the matrix is not used: kr and kb are not looked at)
+    if (io->range != SNN_RANGE_LIMITED && io->range != SNN_RANGE_FULL) return -1;
+    if (io->maxval < 255 || io->maxval > (wide ? 4095 : 255) || (io->maxval + 1) % 256) return -1;
+    snn_fit_io f{};
+    f.video.format = interleaved;
+    f.video.maxval = io->maxval;
+    f.video.shift = io->shift;
+    f.video.siting = io->siting;
+    lumaMapsOfRange(io->maxval, io->range, &f.video);
+    f.out_w = io->out_w;
+    f.out_h = io->out_h;
+    if (fitted) return createFitModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &f, out, true);
+    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &f.video, out, nullptr, true);
 }
 
 // one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame
@@ -348,7 +424,7 @@ static int moveVideoFrames(snn_model* m, void* frames, bool upload) {
     if (!m || !frames || !m->core) return -1;
     snnhip_tensor* y = upload ? m->core->frameInput() : m->core->frameOutput();
     snnhip_tensor* c = upload ? m->core->chromaInput() : m->core->chromaOutput();
-    if (!y || !c) return -1;
+    if (!y || !c || m->core->planarVideo()) return -1; // (planar ends: snn_model_upload_frame_planes / _download_frame_planes)
     const size_t yb = snnhip_tensor_bytes(y) / static_cast<size_t>(m->batch), cb = snnhip_tensor_bytes(c) / static_cast<size_t>(m->batch);
     char* p = static_cast<char*>(frames);
     if (movePlane(y, m->batch, p, yb + cb, 0, upload) != 0) return -1;
@@ -358,6 +434,63 @@ static int moveVideoFrames(snn_model* m, void* frames, bool upload) {
 int snn_model_upload_frame_nv12(snn_model* m, const void* frames) { return moveVideoFrames(m, const_cast<void*>(frames), true); }
 
 int snn_model_download_frame_nv12(snn_model* m, void* frames) { return moveVideoFrames(m, frames, false); }
+
+// `pieces` (one plane of one frame each: `rows` rows of `rowBytes` bytes, pitch[i] bytes apart, in the order the dense device tensor t holds them)
+// between the caller's memory and t.  Tight, adjacent pieces are one run of memory: copied straight.  Anything else goes through the model's staging
+// buffer row by row; only the rows' own bytes are read or written, never the padding between them
+static int movePieces(snn_model* m, snnhip_tensor* t, const std::vector<char*>& pieces, const std::vector<size_t>& pitch, size_t rowBytes, size_t rows, bool upload) {
+    const size_t piece = rowBytes * rows, total = snnhip_tensor_bytes(t);
+    if (piece * pieces.size() != total) return -1;
+    if (planesAreDense(pieces.data(), pitch.data(), pieces.size(), rowBytes, rows))
+        return (upload ? snnhip_tensor_upload_raw(t, pieces[0], total) : snnhip_tensor_download_raw(t, pieces[0], total)) == SNNHIP_OK ? 0 : -1;
+    if (m->staging.size() < total) m->staging.resize(total);
+    char* s = m->staging.data();
+    if (!upload && snnhip_tensor_download_raw(t, s, total) != SNNHIP_OK) return -1;
+    copyPlaneRows(s, pieces.data(), pitch.data(), pieces.size(), rowBytes, rows, upload);
+    return upload ? (snnhip_tensor_upload_raw(t, s, total) == SNNHIP_OK ? 0 : -1) : 0;
+}
+
+static int moveFramePlanes(snn_model* m, void* const* planes, const int* pitch, int n_planes, bool upload) {
+    if (!m || !planes || !pitch || !m->core) return -1;
+    snnhip_tensor* y = upload ? m->core->frameInput() : m->core->frameOutput();
+    snnhip_tensor* c = upload ? m->core->chromaInput() : m->core->chromaOutput();
+    if (!y || !c) return -1; // an RGB end, or no video frames at all
+    const bool planar = m->core->planarVideo();
+    if (n_planes != (planar ? 3 : 2)) return -1;
+    int yd[4], cd[4];
+    if (snnhip_tensor_dims(y, yd) != SNNHIP_OK || snnhip_tensor_dims(c, cd) != SNNHIP_OK || yd[0] != m->batch || yd[3] != 1) return -1;
+    const size_t es = snnhip_tensor_dtype(y) == SNNHIP_U16 ? 2 : 1;
+    const size_t yRow = static_cast<size_t>(yd[2]) * es, cRow = static_cast<size_t>(cd[2]) * static_cast<size_t>(cd[3]) * es;
+    if (pitch[0] < 0 || static_cast<size_t>(pitch[0]) < yRow) return -1;
+    for (int p = 1; p < n_planes; ++p)
+        if (pitch[p] < 0 || static_cast<size_t>(pitch[p]) < cRow) return -1;
+    for (int i = 0; i < m->batch * n_planes; ++i)
+        if (!planes[i]) return -1;
+    try {
+        std::vector<size_t> lumaPitch, chromaPitch;
+        std::vector<char*> luma, chroma; // in the order of the device tensors: [batch] and [batch] (CbCr) or [2 * batch] (Cb, Cr of each frame)
+        for (int n = 0; n < m->batch; ++n) {
+            luma.push_back(static_cast<char*>(planes[n * n_planes]));
+            lumaPitch.push_back(static_cast<size_t>(pitch[0]));
+            for (int p = 1; p < n_planes; ++p) {
+                chroma.push_back(static_cast<char*>(planes[n * n_planes + p]));
+                chromaPitch.push_back(static_cast<size_t>(pitch[p]));
+            }
+        }
+        if (movePieces(m, y, luma, lumaPitch, yRow, static_cast<size_t>(yd[1]), upload) != 0) return -1;
+        return movePieces(m, c, chroma, chromaPitch, cRow, static_cast<size_t>(cd[1]), upload);
+    } catch (...) { // (std::bad_alloc of the staging buffer)
+        return -2;
+    }
+}
+
+int snn_model_upload_frame_planes(snn_model* m, const void* const* planes, const int* pitch_bytes, int n_planes) {
+    return moveFramePlanes(m, const_cast<void* const*>(planes), pitch_bytes, n_planes, true);
+}
+
+int snn_model_download_frame_planes(snn_model* m, void* const* planes, const int* pitch_bytes, int n_planes) {
+    return moveFramePlanes(m, planes, pitch_bytes, n_planes, false);
+}
 
 int snn_model_destroy(snn_model* m) {
     if (!m) return 0;

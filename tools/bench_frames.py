@@ -81,6 +81,18 @@ rounds, frames/s including one frame's H2D + D2H for nv12 and fitted, the kernel
 copy's.  profiles/espcn_fit_frames.json holds the runs under the keys <format>_<in>_x<r>_<out>.
 
     python tools/bench_frames.py --video NV12 --scale 2 --h 720 --w 1280 --fit 1920x1080
+
+--video I420 | I010 [--video-out RGB8 | RGBA8] [--fit WxH], and --colour RGB8 | RGBA8 --video-out I420 (with any --scale): planar 4:2:0 frames
+(DESIGN.md section 4.19).  Each of the four paths beside its NV12 / P010 counterpart at the same depth, in the same process, in the same mirrored
+alternation: planar (the chain plus the launches behind / in front of it on planar chroma), nv12 (the same step on the interleaved plane),
+planar_kernels and nv12_kernels (the launches around the chain alone: chroma_up / plane_fit with C = 1 over two planes against C = 2 over one,
+yuv_rgb_planar against yuv_rgb, rgb_cbcr_planar against rgb_cbcr) and copy (one hipMemcpyDtoDAsync that moves as many bytes through HBM as those
+launches have to).  Device step per form as the median of the timed regions with their min - max spread, frames/s including one frame's H2D + D2H
+for planar and nv12, the kernels of the launch trace, and the planar launches' bytes/s beside the copy's.  --out FILE merges the record into a JSON
+file under the key <format>[_<out>]_<in>_x<r>[_<fit>]: profiles/espcn_planar_frames.json holds the runs at 1080p x2, 720p x3, 540p x4 and 720p ->
+1080p.
+
+    python tools/bench_frames.py --video I420 --video-out RGB8 --scale 2 --out profiles/espcn_planar_frames.json
 """
 import argparse
 import json
@@ -905,14 +917,194 @@ def main_rgb_nv12(a):
     ctx.close()
 
 
+def main_planar(a):
+    """--video I420 | I010 ..., --colour ... --video-out I420: planar / nv12 / planar_kernels / nv12_kernels / copy."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R = a.scale
+    encode = a.video_out == "I420"
+    wide = a.video == "I010"
+    maxval, shift, dt, npdt = (1023, 0, capi.U16, np.uint16) if wide else (255, 0, capi.U8, np.uint8)  # I010: 10 bits in the low end of 2 bytes
+    k = (maxval + 1) / 256.0
+    yoff, yspan = (16.0 * k, 219.0 * k) if a.range == "limited" else (0.0, float(maxval))  # the luma maps snn_model_create12 derives from the range
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    assert (R * H) % 2 == 0 and (R * W) % 2 == 0 and (encode or (H % 2 == 0 and W % 2 == 0)), "4:2:0 frames have even extents"
+    rng = np.random.default_rng(1)
+    layers, shape = [], (1, H, W, 1)
+    for layer in net["layers"]:
+        p = _layer_plan(ctx, layer, shape)
+        layers.append(p)
+        shape = p.out_shape()
+    if encode:
+        ends = (capi.u8_in_plan(ctx, 1, H, W, 1, (0, 0, 0, 0), (1 / 255.0, 1, 1, 1)), capi.u8_out_plan(ctx, *shape, (yspan, 0, 0, 0), (yoff, 0, 0, 0)))
+    elif wide:
+        ends = (capi.u16_in_plan(ctx, 1, H, W, 1, (yoff, 0, 0, 0), (1 / yspan, 1, 1, 1), shift), capi.u16_out_plan(ctx, *shape, (yspan, 0, 0, 0), (yoff, 0, 0, 0), maxval, shift))
+    else:
+        ends = (capi.u8_in_plan(ctx, 1, H, W, 1, (yoff, 0, 0, 0), (1 / yspan, 1, 1, 1)), capi.u8_out_plan(ctx, *shape, (yspan, 0, 0, 0), (yoff, 0, 0, 0)))
+    chain = capi.chain_plan(ctx, [ends[0]] + layers + [ends[1]])
+    assert chain.num_steps() == 2, chain.describe()
+    t_yhi = capi.Tensor(ctx, *shape, dtype=dt)
+    ch, cw = H // 2, W // 2
+    front = None  # a launch in front of the chain (RGB in), shared by both forms
+    if encode:
+        Cc = {"RGB8": 3, "RGBA8": 4}[a.colour]
+        rgb_h = rng.integers(0, 256, size=(1, H, W, Cc), dtype=np.uint8)
+        t_rgb, t_y = capi.Tensor.from_numpy(ctx, rgb_h, dtype=capi.U8), capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8)
+        front = capi.rgb_luma_plan(ctx, 1, H, W, Cc)
+        pl, nv = capi.rgb_cbcr_planar_plan(ctx, 1, H, W, Cc, R, a.siting, a.range), capi.rgb_cbcr_plan(ctx, 1, H, W, Cc, R, a.siting, a.range)
+        t_pc, t_nc = capi.Tensor(ctx, 2, R * H // 2, R * W // 2, 1, dtype=capi.U8), capi.Tensor(ctx, 1, R * H // 2, R * W // 2, 2, dtype=capi.U8)
+        behind = {"planar": [(pl, [t_rgb], t_pc)], "nv12": [(nv, [t_rgb], t_nc)]}
+        ups = {"planar": [(t_rgb, rgb_h)], "nv12": [(t_rgb, rgb_h)]}
+        downs = {"planar": [t_yhi, t_pc], "nv12": [t_yhi, t_nc]}
+        key = "%s_I420_%dx%d_x%d" % (a.colour, W, H, R)
+    else:
+        y_h = (rng.integers(int(16 * k), int(236 * k), size=(1, H, W, 1)) << shift).astype(npdt)
+        c_h = (rng.integers(int(16 * k), int(241 * k), size=(1, ch, cw, 2)) << shift).astype(npdt)
+        p_h = np.ascontiguousarray(np.moveaxis(c_h, 3, 1).reshape(2, ch, cw, 1))  # the same samples as two planes
+        t_y, t_nc_in, t_pc_in = capi.Tensor.from_numpy(ctx, y_h, dtype=dt), capi.Tensor.from_numpy(ctx, c_h, dtype=dt), capi.Tensor.from_numpy(ctx, p_h, dtype=dt)
+        ups = {"planar": [(t_y, y_h), (t_pc_in, p_h)], "nv12": [(t_y, y_h), (t_nc_in, c_h)]}
+        if a.video_out:
+            Cc = {"RGB8": 3, "RGBA8": 4}[a.video_out]
+            pl = capi.yuv_rgb_planar_plan(ctx, 1, ch, cw, Cc, R, dt, maxval, shift, a.siting, a.range)
+            nv = capi.yuv_rgb_plan(ctx, 1, ch, cw, Cc, R, dt, maxval, shift, a.siting, a.range)
+            t_po, t_no = capi.Tensor(ctx, 1, R * H, R * W, Cc, dtype=dt), capi.Tensor(ctx, 1, R * H, R * W, Cc, dtype=dt)
+            behind = {"planar": [(pl, [t_yhi, t_pc_in], t_po)], "nv12": [(nv, [t_yhi, t_nc_in], t_no)]}
+            downs = {"planar": [t_po], "nv12": [t_no]}
+            key = "%s_%s_%dx%d_x%d" % (a.video, a.video_out, W, H, R)
+        elif a.fit:
+            OW, OH = (int(v) for v in a.fit.lower().split("x"))
+            assert OH % 2 == 0 and OW % 2 == 0 and R * H >= OH >= R * H / 2 and R * W >= OW >= R * W / 2, "the target is even and lies between half and all of the x%d frame" % R
+            fit_y = capi.plane_fit_plan(ctx, 1, R * H, R * W, 1, OH, OW, dt, maxval, shift, "centre")
+            pl = capi.plane_fit_plan(ctx, 2, ch, cw, 1, OH // 2, OW // 2, dt, maxval, shift, a.siting)
+            nv = capi.plane_fit_plan(ctx, 1, ch, cw, 2, OH // 2, OW // 2, dt, maxval, shift, a.siting)
+            t_fy = capi.Tensor(ctx, 1, OH, OW, 1, dtype=dt)
+            t_po, t_no = capi.Tensor(ctx, 2, OH // 2, OW // 2, 1, dtype=dt), capi.Tensor(ctx, 1, OH // 2, OW // 2, 2, dtype=dt)
+            behind = {"planar": [(fit_y, [t_yhi], t_fy), (pl, [t_pc_in], t_po)], "nv12": [(fit_y, [t_yhi], t_fy), (nv, [t_nc_in], t_no)]}
+            downs = {"planar": [t_fy, t_po], "nv12": [t_fy, t_no]}
+            key = "%s_%dx%d_x%d_%dx%d" % (a.video, W, H, R, OW, OH)
+        else:
+            pl = capi.chroma_up_plan(ctx, 2, ch, cw, 1, R, dt, maxval, shift, a.siting)
+            nv = capi.chroma_up_plan(ctx, 1, ch, cw, 2, R, dt, maxval, shift, a.siting)
+            t_po, t_no = capi.Tensor(ctx, 2, R * ch, R * cw, 1, dtype=dt), capi.Tensor(ctx, 1, R * ch, R * cw, 2, dtype=dt)
+            behind = {"planar": [(pl, [t_pc_in], t_po)], "nv12": [(nv, [t_nc_in], t_no)]}
+            downs = {"planar": [t_yhi, t_po], "nv12": [t_yhi, t_no]}
+            key = "%s_%dx%d_x%d" % (a.video, W, H, R)
+    kernel_bytes = int(sum(plan.cost()[1] for plan, _, _ in behind["planar"]))
+    assert kernel_bytes == int(sum(plan.cost()[1] for plan, _, _ in behind["nv12"])), "the two forms move the same bytes"
+    half = kernel_bytes // 2
+    t_src, t_dst = capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8)
+    t_src.upload_u8(np.random.default_rng(3).integers(0, 256, size=half, dtype=np.uint8))
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+
+    def run_kernels(form):
+        for plan, ins, out_t in behind[form]:
+            plan.run(ins if len(ins) > 1 else ins[0], out_t)
+
+    def run_step(form):
+        if front is not None:
+            front.run(t_rgb, t_y)
+        chain.run(t_y, t_yhi)
+        run_kernels(form)
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(t_dst.data_ptr(), t_src.data_ptr(), half, stream)
+        assert rc == 0, rc
+
+    forms = {"planar": lambda: run_step("planar"), "nv12": lambda: run_step("nv12"), "planar_kernels": lambda: run_kernels("planar"),
+             "nv12_kernels": lambda: run_kernels("nv12"), "copy": run_copy}
+    for f in forms.values():
+        for _ in range(a.warmup):
+            f()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {k_: [] for k_ in forms}
+    order = list(forms) + list(forms)[::-1]  # mirrored: A B C D E E D C B A
+    for _ in range(a.rounds):
+        for k_ in order:
+            timer.start()
+            for _ in range(a.iters):
+                forms[k_]()
+            timer.stop()
+            dev[k_].append(timer.elapsed_ms() / a.iters)
+    host_out = {form: [np.empty(t.shape, npdt if t.dtype == capi.U16 else np.uint8) for t in downs[form]] for form in downs}
+    e2e = {form: [] for form in downs}
+    for _ in range(a.rounds):
+        for form in ("planar", "nv12", "nv12", "planar"):
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                for t, h in ups[form]:
+                    capi.check(capi.lib().snnhip_tensor_upload_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+                forms[form]()
+                for t, h in zip(downs[form], host_out[form]):
+                    capi.check(capi.lib().snnhip_tensor_download_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+            e2e[form].append((time.perf_counter() - t0) * 1e3 / a.iters)
+    out = {"frame": "%dx%d x%d" % (W, H, R), "scale": R, "video": a.video, "colour": a.colour, "video_out": a.video_out, "fit": a.fit, "siting": a.siting, "range": a.range,
+           "rounds": a.rounds, "iters": a.iters}
+    for k_ in forms:
+        d = statistics.median(dev[k_])
+        out[k_] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[k_]), 4), "device_ms_max": round(max(dev[k_]), 4),
+                   "device_spread": round((max(dev[k_]) - min(dev[k_])) / d, 4)}
+        if k_ in e2e:
+            e = statistics.median(e2e[k_])
+            out[k_].update({"e2e_ms_median": round(e, 4), "e2e_ms_min": round(min(e2e[k_]), 4), "e2e_ms_max": round(max(e2e[k_]), 4), "e2e_frames_per_s": round(1e3 / e, 1),
+                            "io_bytes_per_frame": int(sum(h.nbytes for _, h in ups[k_]) + sum(h.nbytes for h in host_out[k_]))})
+    for form in ("planar", "nv12"):
+        out[form]["steps"] = ([front.describe()] if front is not None else []) + [chain.step_describe(i) for i in range(2)] + [plan.describe() for plan, _, _ in behind[form]]
+    for k_ in ("planar", "nv12", "planar_kernels", "nv12_kernels"):  # the launch trace: per-kernel times of each form (a copy is no kernel of the library)
+        capi.trace_begin()
+        for _ in range(a.iters):
+            forms[k_]()
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        out[k_]["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                               "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+    # the planar step against its counterpart; the margin is this run's own spread (min - max of the repeated regions, the wider of the two forms)
+    out["device_planar_over_nv12"] = round(out["planar"]["device_ms_median"] / out["nv12"]["device_ms_median"], 4)
+    out["device_kernels_planar_over_nv12"] = round(out["planar_kernels"]["device_ms_median"] / out["nv12_kernels"]["device_ms_median"], 4)
+    out["spread_of_the_two_steps"] = max(out["planar"]["device_spread"], out["nv12"]["device_spread"])
+    out["planar_within_spread"] = bool(out["device_planar_over_nv12"] <= 1.0 + out["spread_of_the_two_steps"])
+    out["e2e_fps_planar_over_nv12"] = round(out["planar"]["e2e_frames_per_s"] / out["nv12"]["e2e_frames_per_s"], 4)
+    copy_us = 1e3 * out["copy"]["device_ms_median"]
+    pk = out["planar_kernels"]["device_ms_median"]
+    out["kernels_vs_copy"] = {"hbm_bytes": kernel_bytes, "planar_us_event_timed_loop": round(1e3 * pk, 2), "planar_tbs": round(kernel_bytes / (pk * 1e-3) / 1e12, 3),
+                              "nv12_us_event_timed_loop": round(1e3 * out["nv12_kernels"]["device_ms_median"], 2),
+                              "nv12_tbs": round(kernel_bytes / (out["nv12_kernels"]["device_ms_median"] * 1e-3) / 1e12, 3),
+                              "copy_bytes_each_way": half, "copy_hbm_bytes": 2 * half, "copy_us": round(copy_us, 2), "copy_tbs": round(2 * half / (copy_us * 1e-6) / 1e12, 3)}
+    out["kernels_vs_copy"]["planar_over_copy_rate"] = round(out["kernels_vs_copy"]["planar_tbs"] / out["kernels_vs_copy"]["copy_tbs"], 4)
+    print(json.dumps(out, indent=1))
+    if a.out:
+        record = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                record = json.load(f)
+        record[key] = out
+        with open(a.out, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
     ap.add_argument("--scale", type=int, default=2, choices=[2, 3, 4], help="upscale factor; the input size follows it (output 3840 x 2160) unless --h / --w are given")
     ap.add_argument("--bits", type=int, default=0, choices=[0, 10, 12, 16], help="also time 16-bit frames of this bit depth, folded and as separate launches")
     ap.add_argument("--colour", choices=["RGB8", "RGBA8"], default=None, help="colour frames around the luma chain: r8, colour, the merge launch alone and a device copy of its bytes")
-    ap.add_argument("--video", choices=["NV12", "P010"], default=None, help="4:2:0 video frames around the luma chain: grey, video, the chroma launch alone, a device copy of its bytes and the RGB8 colour step")
-    ap.add_argument("--video-out", choices=["RGB8", "RGBA8", "NV12"], default=None,
+    ap.add_argument("--video", choices=["NV12", "P010", "I420", "I010"], default=None, help="4:2:0 video frames around the luma chain: grey, video, the chroma launch alone, a device copy of its bytes and the RGB8 colour step")
+    ap.add_argument("--out", default=None, metavar="FILE", help="with the planar forms: merge the record into this JSON file")
+    ap.add_argument("--video-out", choices=["RGB8", "RGBA8", "NV12", "I420"], default=None,
                     help="with --video: packed RGB / RGBA out of the yuv_rgb launch (16-bit containers for P010) beside the NV12 step; NV12 with --colour: an NV12 frame out of the rgb_cbcr launch")
     ap.add_argument("--fit", default=None, metavar="WxH", help="with --video: the NV12 / P010 frame at this output size (the chain, then two plane_fit launches) beside the plain step of the same r")
     ap.add_argument("--range", choices=["limited", "full"], default="limited", help="the stream's range with --video-out")
@@ -926,6 +1118,10 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.video in ("I420", "I010") or a.video_out == "I420":
+        assert (a.video_out == "I420") == bool(a.colour) and not (a.colour and a.video), "--video I420 | I010 [--video-out RGB8 | RGBA8] [--fit WxH], or --colour ... --video-out I420"
+        assert not (a.fit and a.video_out), "--fit goes with --video alone"
+        return main_planar(a)
     if a.video_out == "NV12":
         assert a.colour and not a.video, "--video-out NV12 goes with --colour RGB8 | RGBA8"
         return main_rgb_nv12(a)
