@@ -294,6 +294,12 @@ int snn_yolo_decode(const float* head_coarse, const float* head_fine, int net_si
  * Test hook for the loader's number grammar (overflow saturates to +-HUGE_VAL, underflow gives +-0 / a denormal, like the reference's strtod). */
 int snn_json_number(const char* text, double* out);
 
+/* Host-only: what snn_model_create<entry> (entry = 5..12, `io` that entry point's struct or NULL) resolves its struct to for an in_w x in_h x in_c
+ * input and `batch` images, before any model file is opened: -1 where the entry point refuses the request, otherwise 0 and one canonical text line in
+ * buf, "<the model's own end formats and maps> | <the frames the caller uploads and gets back, and their parameters> | entry=<name>".  Test hook for
+ * the "built exactly as" statements above: two requests that name the same model resolve to the same first part (shadernn_amd/host/snn/frames.h). */
+int snn_frames_resolve(int entry, const void* io, int in_w, int in_h, int in_c, int batch, char* buf, int buflen);
+
 /* ".dump" reader (image.cpp:300-311): returns W,H,D,C and, if out != NULL, the RGBA32F pixels ([D][H][W][4] floats). */
 int snn_dump_read(const char* path, int whdc[4], float* out, long out_floats);
 

@@ -72,6 +72,7 @@ SIGNATURES = {
                                            C.c_char_p, C.c_int]),
     "snn_graph_summary": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "snn_json_number": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]),
+    "snn_frames_resolve": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "snn_dump_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int * 4), _FP, C.c_long]),
 }
 
@@ -112,6 +113,14 @@ def json_number(text):
     """The model loader's JSON parser on one number literal (None if it refuses it)."""
     d = C.c_double()
     return d.value if lib().snn_json_number(text.encode(), C.byref(d)) == 0 else None
+
+
+def frames_resolve(entry, io, w, h, c, batch=1):
+    """The frame description snn_model_create<entry> resolves its struct `io` (None: a null struct) to, as one canonical line "<the model part> |
+    <the frame ends> | entry=<name>"; None if the entry point refuses the request before it opens the model file.  Host-only."""
+    buf = C.create_string_buffer(1024)
+    rc = lib().snn_frames_resolve(entry, None if io is None else C.byref(io), w, h, c, batch, buf, len(buf))
+    return buf.value.decode() if rc == 0 else None
 
 
 def read_dump(path):
@@ -227,12 +236,12 @@ class Model:
         "RGBA8" ("I420") or "RGB16" / "RGBA16" ("I010"); and colour "RGB8" / "RGBA8" with video_out "I420".  video_range sets the luma plane's maps on
         every one of them (in_means / in_norms / out_scale / out_offset are not used).  upload_planes / download_planes take arrays with a row pitch."""
         self.h = _P()
-        self.planar = False
-        self.colour_channels = 0
-        self.video = video
-        self.video_out_channels = 0
-        self.encode = False
+        self.batch = batch
+        self.video = video  # the upload end: None = one array (the model's frame or a colour frame), else planes of this format
+        self.out_end = "frame"  # what comes back: "frame" = one array of out_channels (0: the model's own), "yuv" = luma + chroma planes
+        self.out_channels = 0
         self.out_size = None
+        in_channels, u8 = c, (np.uint8, np.uint8)
         assert out_size is None or (video is not None and video_out is None and colour is None), "out_size fits an NV12 / P010 frame: it goes with video= alone"
         if colour is not None and video_out is not None:
             assert video is None, "colour frames go in: video= names NV12 / P010 frames at the input"
@@ -242,100 +251,61 @@ class Model:
             assert siting in SITINGS, "siting is \"left\" or \"centre\""
             assert input_format is None and output_format is None, "colour frames replace input_format / output_format"
             assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
-            channels = {"RGB8": 3, "RGBA8": 4}[colour]
-            self.frame_dtypes = (np.uint8, np.uint8)
-            self.encode = True
-            self.batch = batch
-            self.in_shape = (h, w, channels) if batch == 1 else (batch, h, w, channels)
+            in_channels, self.frame_dtypes, self.out_end = {"RGB8": 3, "RGBA8": 4}[colour], u8, "yuv"
             if video_out == "I420":
-                io = PlanarIO(FRAME_FORMATS[colour], VIDEO_FORMATS["I420"][0], 255, 0, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, 0, 0)
-                self._create12(json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io)
-                return
-            io = EncodeIO(FRAME_FORMATS[colour], VIDEO_FORMATS["NV12"][0], SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
-            assert lib().snn_model_create10(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                            int(batch), C.byref(io), C.byref(self.h)) == 0
-            return
-        if video_out is not None:
+                entry, io = 12, PlanarIO(FRAME_FORMATS[colour], VIDEO_FORMATS["I420"][0], 255, 0, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, 0, 0)
+            else:
+                entry, io = 10, EncodeIO(FRAME_FORMATS[colour], VIDEO_FORMATS["NV12"][0], SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
+        elif video_out is not None:
             assert video is not None, "video_out needs video=\"NV12\" or \"P010\""
             assert video_out in VIDEO_OUT_FORMATS, "video_out is one of %s" % sorted(VIDEO_OUT_FORMATS)
             assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
             assert siting in SITINGS, "siting is \"left\" or \"centre\""
             assert input_format is None and output_format is None and colour is None, "video frames replace input_format / output_format / colour"
             fmt, maxval, shift = VIDEO_FORMATS[video]
-            pair, channels = VIDEO_OUT_FORMATS[video_out]
+            pair, self.out_channels = VIDEO_OUT_FORMATS[video_out]
             wide = fmt in (0x301, 0x501)
             assert pair == (0x301 if wide else 0x201), "%s frames come back as %s" % (video, "RGB16 / RGBA16" if wide else "RGB8 / RGBA8")
             assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
             maxval = maxval if video_maxval is None else video_maxval
             shift = shift if video_shift is None else video_shift
-            dt = np.uint16 if wide else np.uint8
-            self.frame_dtypes = (dt, dt)
-            self.video_out_channels = channels
-            self.batch = batch
-            self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
+            in_channels, self.frame_dtypes = 1, ((np.uint16, np.uint16) if wide else u8)
             if video in PLANAR_FORMATS:
-                io = PlanarIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, 0, 0)
-                self._create12(json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io)
-                return
-            io = VideoRgbIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
-            assert lib().snn_model_create9(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                           int(batch), C.byref(io), C.byref(self.h)) == 0
-            return
-        if video is not None:
+                entry, io = 12, PlanarIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, 0, 0)
+            else:
+                entry, io = 9, VideoRgbIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb)
+        elif video is not None:
             assert input_format is None and output_format is None and colour is None, "video frames replace input_format / output_format / colour"
             fmt, maxval, shift = VIDEO_FORMATS[video]
             maxval = maxval if video_maxval is None else video_maxval
             shift = shift if video_shift is None else video_shift
-            dt = np.uint16 if fmt in (0x301, 0x501) else np.uint8
-            self.frame_dtypes = (dt, dt)
-            self.batch = batch
-            self.in_shape = (h, w, 1) if batch == 1 else (batch, h, w, 1)
+            in_channels, self.frame_dtypes, self.out_end = 1, ((np.uint16, np.uint16) if fmt in (0x301, 0x501) else u8), "yuv"
+            size = self.out_size = (int(out_size[0]), int(out_size[1])) if out_size is not None else None
             if video in PLANAR_FORMATS:
                 assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
                 assert siting in SITINGS, "siting is \"left\" or \"centre\""
-                ow, oh = (int(out_size[0]), int(out_size[1])) if out_size is not None else (0, 0)
-                io = PlanarIO(fmt, fmt, maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, ow, oh)
-                self._create12(json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io)
-                self.out_size = (ow, oh) if out_size is not None else None
-                return
-            io = VideoIO(fmt, maxval, shift, SITINGS[siting], in_means[0], in_norms[0], out_scale[0], out_offset[0])
-            if out_size is not None:
-                fit = FitIO(io, int(out_size[0]), int(out_size[1]))
-                assert lib().snn_model_create11(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half),
-                                                int(capture_graph), int(batch), C.byref(fit), C.byref(self.h)) == 0
-                self.out_size = (int(out_size[0]), int(out_size[1]))
+                entry, io = 12, PlanarIO(fmt, fmt, maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, *(size or (0, 0)))
             else:
-                assert lib().snn_model_create8(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                               int(batch), C.byref(io), C.byref(self.h)) == 0
-            return
-        if colour is not None:
+                entry, io = 8, VideoIO(fmt, maxval, shift, SITINGS[siting], in_means[0], in_norms[0], out_scale[0], out_offset[0])
+                if size is not None:
+                    entry, io = 11, FitIO(io, *size)
+        elif colour is not None:
             assert input_format is None and output_format is None, "colour frames replace input_format / output_format"
-            self.colour_channels = {"RGB8": 3, "RGBA8": 4}[colour]
-            self.frame_dtypes = (np.uint8, np.uint8)
-            io = ColourIO(FRAME_FORMATS[colour], kr, kb, in_means[0], in_norms[0], out_scale[0], out_offset[0])
-            assert lib().snn_model_create7(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                           int(batch), C.byref(io), C.byref(self.h)) == 0
-            self.batch = batch
-            self.in_shape = (h, w, self.colour_channels) if batch == 1 else (batch, h, w, self.colour_channels)
-            return
-        self.frame_dtypes = tuple(np.uint16 if f in ("R16", "RGB16", "RGBA16") else np.uint8 for f in (input_format, output_format))
-        if np.uint16 in self.frame_dtypes:
-            io = FrameIO2(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], (C.c_float * 4)(*in_means), (C.c_float * 4)(*in_norms),
-                          (C.c_float * 4)(*out_scale), (C.c_float * 4)(*out_offset), frame_in_shift, frame_out_maxval, frame_out_shift)
-            create = lib().snn_model_create6
+            in_channels = self.out_channels = {"RGB8": 3, "RGBA8": 4}[colour]
+            self.frame_dtypes = u8
+            entry, io = 7, ColourIO(FRAME_FORMATS[colour], kr, kb, in_means[0], in_norms[0], out_scale[0], out_offset[0])
         else:
-            io = FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], (C.c_float * 4)(*in_means), (C.c_float * 4)(*in_norms),
-                         (C.c_float * 4)(*out_scale), (C.c_float * 4)(*out_offset))
-            create = lib().snn_model_create5
+            self.frame_dtypes = tuple(np.uint16 if f in ("R16", "RGB16", "RGBA16") else np.uint8 for f in (input_format, output_format))
+            maps = [(C.c_float * 4)(*m) for m in (in_means, in_norms, out_scale, out_offset)]
+            if np.uint16 in self.frame_dtypes:
+                entry, io = 6, FrameIO2(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps, frame_in_shift, frame_out_maxval, frame_out_shift)
+            else:
+                entry, io = 5, FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps)
+        self.planar = entry == 12
+        self.in_shape = (h, w, in_channels) if batch == 1 else (batch, h, w, in_channels)
+        create = getattr(lib(), "snn_model_create%d" % entry)
         assert create(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph), int(batch),
                       C.byref(io), C.byref(self.h)) == 0
-        self.batch = batch
-        self.in_shape = (h, w, c) if batch == 1 else (batch, h, w, c)
-
-    def _create12(self, json_path, device, w, h, c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io):
-        assert lib().snn_model_create12(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph),
-                                        int(batch), C.byref(io), C.byref(self.h)) == 0
-        self.planar = True
 
     def upload_frame(self, img):
         """uint8 (uint16 for a 16-bit input format) [batch x] H x W x C into the model's input frame (no per-call allocation)."""
@@ -351,15 +321,11 @@ class Model:
         """the model's output frame of the last run, uint8 (uint16 for a 16-bit output format) [batch x] H x W x C"""
         d = (C.c_int * 3)()
         lib().snn_model_output_dims(self.h, C.byref(d))
-        video_end = self.out_size is not None or (self.video and not self.video_out_channels) or self.encode
-        if video_end and self.planar:
-            return self._download_planar(*((self.out_size[1], self.out_size[0]) if self.out_size is not None else (d[0], d[1])))
-        if self.out_size is not None:
-            return self._download_video(self.out_size[1], self.out_size[0])
-        if (self.video and not self.video_out_channels) or self.encode:
-            return self._download_video(d[0], d[1])
-        if self.colour_channels or self.video_out_channels:
-            d = (d[0], d[1], self.colour_channels or self.video_out_channels)
+        if self.out_end == "yuv":
+            oh, ow = (self.out_size[1], self.out_size[0]) if self.out_size is not None else (d[0], d[1])
+            return self._download_planar(oh, ow) if self.planar else self._download_video(oh, ow)
+        if self.out_channels:
+            d = (d[0], d[1], self.out_channels)
         out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=self.frame_dtypes[1])
         down = lib().snn_model_download_frame_u16 if self.frame_dtypes[1] == np.uint16 else lib().snn_model_download_frame_u8
         assert down(self.h, out.ctypes.data_as(_P)) == 0

@@ -27,7 +27,8 @@ std::unique_ptr<MixedInferenceCore> MixedInferenceCore::create(GpuContext* conte
     static_cast<InferenceGraph&>(cp) = dp::generateInferenceGraph(layers, options);
     cp.dumpOutputs = dumpOutputs;
     cp.fuseChains = options.fuseChains;
-    cp.outputFormat = options.desiredOutputFormat; // R8 / RGB8 / RGBA8: an 8-bit output frame (identity scale, zero offset)
+    cp.frames.model.in_format = frameIoFormat(cp.inputsDesc[0].format); // R8 / RGB8 / RGBA8 / ...16: a frame at that end (identity maps)
+    cp.frames.model.out_format = frameIoFormat(options.desiredOutputFormat);
     cp.halfTensors = options.preferrHalfPrecision;
     return create(context, cp);
 }
@@ -94,25 +95,18 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         }
         if (cp.profiling) stage.timer.reset(backend->createDeviceTimer(layer.name));
     }
-    const bool frameIn = isFrameFormat(cp.inputsDesc[0].format), frameOut = isFrameFormat(cp.outputFormat);
-    if (frameIn || frameOut) {
+    const int frameIn = cp.frames.model.in_format, frameOut = cp.frames.model.out_format; // SNN_IO_*: the low byte is the channel count
+    if (frameIn != SNN_IO_FLOAT || frameOut != SNN_IO_FLOAT) {
         auto* hb = dynamic_cast<dp::HipBackend*>(backend);
         SNN_CHK(hb && stages.back().stageOutputs.size() > 0);
         const ImageTexture& o = stages.back().stageOutputs[0];
         const auto& id = cp.inputsDesc[0];
-        if (frameIn && getColorFormatDesc(id.format).ch != id.channels) SNN_RIP("input format %s for a %u-channel input", getColorFormatDesc(id.format).name, id.channels);
-        if (frameOut && getColorFormatDesc(cp.outputFormat).ch != o.channels())
-            SNN_RIP("output format %s for a %u-channel output", getColorFormatDesc(cp.outputFormat).name, static_cast<unsigned>(o.channels()));
-        hb->initFrameIO(frameIn, frameOut, static_cast<int>(o.batch()), static_cast<int>(id.height), static_cast<int>(id.width), static_cast<int>(id.channels),
-                        static_cast<int>(o.height()), static_cast<int>(o.width()), static_cast<int>(o.channels()), cp.halfTensors ? SNNHIP_F16 : SNNHIP_F32,
-                        cp.frameInMeans, cp.frameInNorms, cp.frameOutScale, cp.frameOutOffset, frameIn && isFrame16Format(id.format),
-                        frameOut && isFrame16Format(cp.outputFormat), cp.frameInShift, cp.frameOutMaxval, cp.frameOutShift);
-        if (cp.colourChannels) hb->initColourIO(cp.colourChannels, cp.colourKr, cp.colourKb);
-        if (cp.encodeChannels) hb->initEncodeIO(cp.encodeChannels, cp.encodeSiting, cp.encodeRange, cp.colourKr, cp.colourKb, cp.videoPlanar);
-        if (cp.videoDtype && cp.videoRgbChannels)
-            hb->initVideoRgbIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoRgbChannels, cp.videoRange, cp.videoKr, cp.videoKb, cp.videoPlanar);
-        else if (cp.videoDtype && cp.fitW) hb->initVideoFitIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.fitW, cp.fitH, cp.videoPlanar);
-        else if (cp.videoDtype) hb->initVideoIO(cp.videoDtype, cp.videoMaxval, cp.videoShift, cp.videoSiting, cp.videoPlanar);
+        if (frameIn && static_cast<uint32_t>(frameIn & 0xff) != id.channels)
+            SNN_RIP("input format %s for a %u-channel input", getColorFormatDesc(frameColorFormat(frameIn)).name, id.channels);
+        if (frameOut && static_cast<uint32_t>(frameOut & 0xff) != o.channels())
+            SNN_RIP("output format %s for a %u-channel output", getColorFormatDesc(frameColorFormat(frameOut)).name, static_cast<unsigned>(o.channels()));
+        hb->initFrames(cp.frames, static_cast<int>(o.batch()), static_cast<int>(id.height), static_cast<int>(id.width), static_cast<int>(id.channels),
+                       static_cast<int>(o.height()), static_cast<int>(o.width()), static_cast<int>(o.channels()), cp.halfTensors ? SNNHIP_F16 : SNNHIP_F32);
         frameBackend = hb;
     }
     backend->finalizeStages(stages, cp.dumpOutputs, cp.fuseChains);
@@ -123,7 +117,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         // A recorded graph pays off when an inference is MANY launches (ResNet-18 23, MobileNetV2 41, Candy 88 after fusion).  For a handful it costs:
         // consecutive hipGraphLaunch calls leave ~5 us between graphs on the stream where plain kernel launches queue back to back (measured on the
         // fused ESPCN, 2 launches of 86 + 34 us: 125.0 us per inference replayed, 120 launched directly) -- below the threshold run() just launches.
-        int launches = frameBackend ? frameBackend->colourLaunches() + frameBackend->videoLaunches() : 0;
+        int launches = frameBackend ? frameBackend->frameLaunches() : 0;
         for (auto& s : stages) {
             auto* ml = static_cast<dp::GenericModelLayer*>(s.layer->modelLayer);
             if (!ml || s.layer->isInputLayer) continue;
@@ -275,7 +269,7 @@ std::string MixedInferenceCore::describe() const {
         if (stages[i].fusedAway) ss << "  (fused into a later stage's plan)";
         ss << "\n";
     }
-    if (frameBackend) ss << frameBackend->describeColour() << frameBackend->describeVideo();
+    if (frameBackend) ss << frameBackend->describeFrames();
     return ss.str();
 }
 

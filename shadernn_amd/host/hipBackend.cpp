@@ -56,44 +56,16 @@ HipBackend::~HipBackend() {
     replacedPasses.clear();
     if (frameInPlan) snnhip_plan_destroy(frameInPlan);
     if (frameOutPlan) snnhip_plan_destroy(frameOutPlan);
-    if (frameInT) snnhip_tensor_free(frameInT);
-    if (frameOutT) snnhip_tensor_free(frameOutT);
-    if (lumaPlan) snnhip_plan_destroy(lumaPlan);
-    if (mergePlan) snnhip_plan_destroy(mergePlan);
-    if (colourInT) snnhip_tensor_free(colourInT);
-    if (colourOutT) snnhip_tensor_free(colourOutT);
-    if (chromaPlan) snnhip_plan_destroy(chromaPlan);
-    if (chromaInT) snnhip_tensor_free(chromaInT);
-    if (chromaOutT) snnhip_tensor_free(chromaOutT);
-    if (yuvRgbPlan) snnhip_plan_destroy(yuvRgbPlan);
-    if (rgbOutT) snnhip_tensor_free(rgbOutT);
-    if (cbcrPlan) snnhip_plan_destroy(cbcrPlan);
-    if (fitLumaPlan) snnhip_plan_destroy(fitLumaPlan);
-    if (fitChromaPlan) snnhip_plan_destroy(fitChromaPlan);
-    if (fitLumaT) snnhip_tensor_free(fitLumaT);
+    for (auto* steps : {&stepsIn, &stepsOut})
+        for (auto& s : *steps) snnhip_plan_destroy(s.plan);
+    for (auto* t : frameTensors) snnhip_tensor_free(t);
 }
 
-void HipBackend::initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
-                             const float norms[4], const float scale[4], const float offset[4], bool in16, bool out16, int inShift, int outMaxval,
-                             int outShift) {
-    if (in && in16) {
-        snnhip_u16_in_desc d{n, inH, inW, inC, dtype, {means[0], means[1], means[2], means[3]}, {norms[0], norms[1], norms[2], norms[3]}, inShift};
-        hipChk(snnhip_u16_in_plan_create(ctx, &d, &frameInPlan), "snnhip_u16_in_plan_create");
-        hipChk(snnhip_tensor_alloc(ctx, n, inH, inW, inC, SNNHIP_U16, &frameInT), "snnhip_tensor_alloc (input frame)");
-    } else if (in) {
-        snnhip_u8_in_desc d{n, inH, inW, inC, dtype, {means[0], means[1], means[2], means[3]}, {norms[0], norms[1], norms[2], norms[3]}};
-        hipChk(snnhip_u8_in_plan_create(ctx, &d, &frameInPlan), "snnhip_u8_in_plan_create");
-        hipChk(snnhip_tensor_alloc(ctx, n, inH, inW, inC, SNNHIP_U8, &frameInT), "snnhip_tensor_alloc (input frame)");
-    }
-    if (out && out16) {
-        snnhip_u16_out_desc d{n, outH, outW, outC, dtype, {scale[0], scale[1], scale[2], scale[3]}, {offset[0], offset[1], offset[2], offset[3]}, outMaxval, outShift};
-        hipChk(snnhip_u16_out_plan_create(ctx, &d, &frameOutPlan), "snnhip_u16_out_plan_create");
-        hipChk(snnhip_tensor_alloc(ctx, n, outH, outW, outC, SNNHIP_U16, &frameOutT), "snnhip_tensor_alloc (output frame)");
-    } else if (out) {
-        snnhip_u8_out_desc d{n, outH, outW, outC, dtype, {scale[0], scale[1], scale[2], scale[3]}, {offset[0], offset[1], offset[2], offset[3]}};
-        hipChk(snnhip_u8_out_plan_create(ctx, &d, &frameOutPlan), "snnhip_u8_out_plan_create");
-        hipChk(snnhip_tensor_alloc(ctx, n, outH, outW, outC, SNNHIP_U8, &frameOutT), "snnhip_tensor_alloc (output frame)");
-    }
+snnhip_tensor* HipBackend::ownTensor(int n, int h, int w, int c, int dtype, const char* what) {
+    snnhip_tensor* t = nullptr;
+    hipChk(snnhip_tensor_alloc(ctx, n, h, w, c, dtype, &t), what);
+    frameTensors.push_back(t);
+    return t;
 }
 
 // The upscale factor of a luma model from its two frame tensors, whose dims it returns: one channel in and out, an integer 1..4, the same on both
@@ -109,113 +81,119 @@ static int frameScale(const snnhip_tensor* frameIn, const snnhip_tensor* frameOu
     return r;
 }
 
-void HipBackend::initColourIO(int channels, float kr, float kb) {
-    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == SNNHIP_U8 && snnhip_tensor_dtype(frameOutT) == SNNHIP_U8);
+void HipBackend::initFrames(const FrameSpec& f, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype) {
+    using Source = FrameSpec::Source;
+    using Sink = FrameSpec::Sink;
+    const snn_frame_io2& m = f.model;
+    const float *mn = m.in_means, *nm = m.in_norms, *sc = m.out_scale, *of = m.out_offset;
+    if (m.in_format & 0x100) { // SNN_IO_R16 ..: a 16-bit frame
+        snnhip_u16_in_desc d{n, inH, inW, inC, dtype, {mn[0], mn[1], mn[2], mn[3]}, {nm[0], nm[1], nm[2], nm[3]}, m.in_shift};
+        hipChk(snnhip_u16_in_plan_create(ctx, &d, &frameInPlan), "snnhip_u16_in_plan_create");
+    } else if (m.in_format != SNN_IO_FLOAT) {
+        snnhip_u8_in_desc d{n, inH, inW, inC, dtype, {mn[0], mn[1], mn[2], mn[3]}, {nm[0], nm[1], nm[2], nm[3]}};
+        hipChk(snnhip_u8_in_plan_create(ctx, &d, &frameInPlan), "snnhip_u8_in_plan_create");
+    }
+    if (frameInPlan) frameInT = ownTensor(n, inH, inW, inC, (m.in_format & 0x100) ? SNNHIP_U16 : SNNHIP_U8, "snnhip_tensor_alloc (input frame)");
+    if (m.out_format & 0x100) {
+        snnhip_u16_out_desc d{n, outH, outW, outC, dtype, {sc[0], sc[1], sc[2], sc[3]}, {of[0], of[1], of[2], of[3]}, m.out_maxval, m.out_shift};
+        hipChk(snnhip_u16_out_plan_create(ctx, &d, &frameOutPlan), "snnhip_u16_out_plan_create");
+    } else if (m.out_format != SNN_IO_FLOAT) {
+        snnhip_u8_out_desc d{n, outH, outW, outC, dtype, {sc[0], sc[1], sc[2], sc[3]}, {of[0], of[1], of[2], of[3]}};
+        hipChk(snnhip_u8_out_plan_create(ctx, &d, &frameOutPlan), "snnhip_u8_out_plan_create");
+    }
+    if (frameOutPlan) frameOutT = ownTensor(n, outH, outW, outC, (m.out_format & 0x100) ? SNNHIP_U16 : SNNHIP_U8, "snnhip_tensor_alloc (output frame)");
+    uploadT = frameInT;
+    downloadT = frameOutT;
+    if (f.source == Source::MODEL && f.sink == Sink::MODEL) return;
+
+    // colour or video frames around a luma-only model: the luma plane IS the model's frame at a video end
+    const int vd = f.wide ? SNNHIP_U16 : SNNHIP_U8;
+    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == vd && snnhip_tensor_dtype(frameOutT) == vd);
     int in[4], out[4];
-    const int r = frameScale(frameInT, frameOutT, false, in, out);
-    snnhip_rgb_luma_desc ld{in[0], in[1], in[2], channels, kr, kb};
-    hipChk(snnhip_rgb_luma_plan_create(ctx, &ld, &lumaPlan), "snnhip_rgb_luma_plan_create");
-    snnhip_ycc_merge_desc md{in[0], in[1], in[2], channels, r, kr, kb};
-    hipChk(snnhip_ycc_merge_plan_create(ctx, &md, &mergePlan), "snnhip_ycc_merge_plan_create");
-    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1], in[2], channels, SNNHIP_U8, &colourInT), "snnhip_tensor_alloc (colour input frame)");
-    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1], out[2], channels, SNNHIP_U8, &colourOutT), "snnhip_tensor_alloc (colour output frame)");
+    const int r = frameScale(frameInT, frameOutT, f.source == Source::YUV420, in, out);
+    const int cc = f.planar ? 1 : 2, cn = f.planar ? 2 * in[0] : in[0]; // planar: every Cb and Cr plane is an image of one channel
+    planarChroma = f.planar;
+    snnhip_plan* p = nullptr;
+    if (f.source == Source::RGB) { // the colour frame's luma plane into the model's input frame
+        snnhip_rgb_luma_desc d{in[0], in[1], in[2], f.channels, f.kr, f.kb};
+        hipChk(snnhip_rgb_luma_plan_create(ctx, &d, &p), "snnhip_rgb_luma_plan_create");
+        uploadT = ownTensor(in[0], in[1], in[2], f.channels, SNNHIP_U8, "snnhip_tensor_alloc (colour input frame)");
+        stepsIn.push_back({p, uploadT, nullptr, frameInT, "[colour in]", "snnhip_plan_run (colour frame -> luma)"});
+    } else {
+        chromaInT = ownTensor(cn, in[1] / 2, in[2] / 2, cc, vd, "snnhip_tensor_alloc (chroma input plane)");
+    }
+    switch (f.sink) {
+    case Sink::MODEL: break;
+    case Sink::RGB_MERGED: { // the model's output frame merged with the colour frame's upsampled chroma
+        snnhip_ycc_merge_desc d{in[0], in[1], in[2], f.channels, r, f.kr, f.kb};
+        hipChk(snnhip_ycc_merge_plan_create(ctx, &d, &p), "snnhip_ycc_merge_plan_create");
+        downloadT = ownTensor(out[0], out[1], out[2], f.channels, SNNHIP_U8, "snnhip_tensor_alloc (colour output frame)");
+        stepsOut.push_back({p, frameOutT, uploadT, downloadT, "[colour out]", "snnhip_plan_run_n (luma + chroma -> colour frame)"});
+        break;
+    }
+    case Sink::CHROMA_UP: { // the chroma planes r-fold
+        snnhip_chroma_up_desc d{cn, in[1] / 2, in[2] / 2, cc, r, vd, f.maxval, f.shift, f.siting};
+        hipChk(snnhip_chroma_up_plan_create(ctx, &d, &p), "snnhip_chroma_up_plan_create");
+        chromaOutT = ownTensor(cn, out[1] / 2, out[2] / 2, cc, vd, "snnhip_tensor_alloc (chroma output plane)");
+        stepsOut.push_back({p, chromaInT, nullptr, chromaOutT, "[chroma out]", "snnhip_plan_run (chroma plane)"});
+        break;
+    }
+    case Sink::FITTED: { // the model's output luma frame and the ORIGINAL chroma planes, each resampled to the target (no r-fold chroma)
+        snnhip_plane_fit_desc ld{out[0], out[1], out[2], 1, f.fitH, f.fitW, vd, f.maxval, f.shift, SNNHIP_SITING_CENTRE}; // a luma plane always uses centre
+        hipChk(snnhip_plane_fit_plan_create(ctx, &ld, &p), "snnhip_plane_fit_plan_create (luma)");
+        downloadT = ownTensor(out[0], f.fitH, f.fitW, 1, vd, "snnhip_tensor_alloc (fitted luma plane)");
+        stepsOut.push_back({p, frameOutT, nullptr, downloadT, "[luma fit]", "snnhip_plan_run (luma frame -> fitted luma plane)"});
+        snnhip_plane_fit_desc cd{cn, in[1] / 2, in[2] / 2, cc, f.fitH / 2, f.fitW / 2, vd, f.maxval, f.shift, f.siting};
+        hipChk(snnhip_plane_fit_plan_create(ctx, &cd, &p), "snnhip_plane_fit_plan_create (chroma)");
+        chromaOutT = ownTensor(cn, f.fitH / 2, f.fitW / 2, cc, vd, "snnhip_tensor_alloc (fitted chroma plane)");
+        stepsOut.push_back({p, chromaInT, nullptr, chromaOutT, "[chroma fit]", "snnhip_plan_run (chroma plane -> fitted chroma plane)"});
+        break;
+    }
+    case Sink::RGB_FROM_YUV: { // the model's output luma frame and the ORIGINAL chroma planes to packed RGB (no r-fold chroma)
+        snnhip_yuv_rgb_desc d{in[0], in[1] / 2, in[2] / 2, f.channels, r, vd, f.maxval, f.shift, f.siting, f.range, f.kr, f.kb};
+        if (f.planar) hipChk(snnhip_yuv_rgb_planar_plan_create(ctx, &d, &p), "snnhip_yuv_rgb_planar_plan_create");
+        else hipChk(snnhip_yuv_rgb_plan_create(ctx, &d, &p), "snnhip_yuv_rgb_plan_create");
+        downloadT = ownTensor(out[0], out[1], out[2], f.channels, vd, "snnhip_tensor_alloc (RGB output frame)");
+        stepsOut.push_back({p, frameOutT, chromaInT, downloadT, "[rgb out]", "snnhip_plan_run_n (luma + chroma plane -> RGB frame)"});
+        break;
+    }
+    case Sink::YUV420_FROM_RGB: { // the model's output frame IS the luma plane; the chroma planes from the colour input frame
+        if (r < 2 || out[1] % 2 || out[2] % 2) SNN_RIP("an NV12 output frame needs r = 2..4 and an even extent: %dx%d -> %dx%d", in[1], in[2], out[1], out[2]);
+        snnhip_rgb_cbcr_desc d{in[0], in[1], in[2], f.channels, r, f.siting, f.range, f.kr, f.kb};
+        if (f.planar) hipChk(snnhip_rgb_cbcr_planar_plan_create(ctx, &d, &p), "snnhip_rgb_cbcr_planar_plan_create");
+        else hipChk(snnhip_rgb_cbcr_plan_create(ctx, &d, &p), "snnhip_rgb_cbcr_plan_create");
+        chromaOutT = ownTensor(f.planar ? 2 * out[0] : out[0], out[1] / 2, out[2] / 2, cc, SNNHIP_U8, "snnhip_tensor_alloc (chroma output plane)");
+        stepsOut.push_back({p, uploadT, nullptr, chromaOutT, "[chroma out]", "snnhip_plan_run (colour frame -> chroma plane)"});
+        lumaChromaFromRgb = true;
+        break;
+    }
+    }
 }
 
-std::string HipBackend::describeColour() const {
+std::string HipBackend::describeFrames() const {
     std::string s;
-    char buf[256];
-    if (lumaPlan && snnhip_plan_describe(lumaPlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[colour in] ") + buf + "\n";
-    if (mergePlan && snnhip_plan_describe(mergePlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[colour out] ") + buf + "\n";
+    char buf[320];
+    for (auto* steps : {&stepsIn, &stepsOut})
+        for (auto& st : *steps)
+            if (snnhip_plan_describe(st.plan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string(st.label) + " " + buf + "\n";
     return s;
 }
 
-void HipBackend::initVideoIO(int dtype, int maxval, int shift, int siting, bool planar) {
-    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
-    int in[4], out[4];
-    const int r = frameScale(frameInT, frameOutT, true, in, out);
-    const int cn = planar ? 2 * in[0] : in[0], cc = planar ? 1 : 2; // planar: every Cb and Cr plane is an image of one channel
-    planarChroma = planar;
-    snnhip_chroma_up_desc cd{cn, in[1] / 2, in[2] / 2, cc, r, dtype, maxval, shift, siting};
-    hipChk(snnhip_chroma_up_plan_create(ctx, &cd, &chromaPlan), "snnhip_chroma_up_plan_create");
-    hipChk(snnhip_tensor_alloc(ctx, cn, in[1] / 2, in[2] / 2, cc, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
-    hipChk(snnhip_tensor_alloc(ctx, cn, out[1] / 2, out[2] / 2, cc, dtype, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
-}
-
-void HipBackend::initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb, bool planar) {
-    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
-    int in[4], out[4];
-    const int r = frameScale(frameInT, frameOutT, true, in, out);
-    snnhip_yuv_rgb_desc yd{in[0], in[1] / 2, in[2] / 2, channels, r, dtype, maxval, shift, siting, range, kr, kb};
-    planarChroma = planar;
-    if (planar) hipChk(snnhip_yuv_rgb_planar_plan_create(ctx, &yd, &yuvRgbPlan), "snnhip_yuv_rgb_planar_plan_create");
-    else hipChk(snnhip_yuv_rgb_plan_create(ctx, &yd, &yuvRgbPlan), "snnhip_yuv_rgb_plan_create");
-    hipChk(snnhip_tensor_alloc(ctx, planar ? 2 * in[0] : in[0], in[1] / 2, in[2] / 2, planar ? 1 : 2, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
-    hipChk(snnhip_tensor_alloc(ctx, out[0], out[1], out[2], channels, dtype, &rgbOutT), "snnhip_tensor_alloc (RGB output frame)");
-}
-
-void HipBackend::initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH, bool planar) {
-    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == dtype && snnhip_tensor_dtype(frameOutT) == dtype);
-    int in[4], out[4];
-    (void) frameScale(frameInT, frameOutT, true, in, out);
-    snnhip_plane_fit_desc ld{out[0], out[1], out[2], 1, outH, outW, dtype, maxval, shift, SNNHIP_SITING_CENTRE}; // a luma plane always uses centre
-    hipChk(snnhip_plane_fit_plan_create(ctx, &ld, &fitLumaPlan), "snnhip_plane_fit_plan_create (luma)");
-    const int cn = planar ? 2 * in[0] : in[0], cc = planar ? 1 : 2;
-    planarChroma = planar;
-    snnhip_plane_fit_desc cd{cn, in[1] / 2, in[2] / 2, cc, outH / 2, outW / 2, dtype, maxval, shift, siting};
-    hipChk(snnhip_plane_fit_plan_create(ctx, &cd, &fitChromaPlan), "snnhip_plane_fit_plan_create (chroma)");
-    hipChk(snnhip_tensor_alloc(ctx, cn, in[1] / 2, in[2] / 2, cc, dtype, &chromaInT), "snnhip_tensor_alloc (chroma input plane)");
-    hipChk(snnhip_tensor_alloc(ctx, out[0], outH, outW, 1, dtype, &fitLumaT), "snnhip_tensor_alloc (fitted luma plane)");
-    hipChk(snnhip_tensor_alloc(ctx, cn, outH / 2, outW / 2, cc, dtype, &chromaOutT), "snnhip_tensor_alloc (fitted chroma plane)");
-}
-
-void HipBackend::initEncodeIO(int channels, int siting, int range, float kr, float kb, bool planar) {
-    SNN_CHK(frameInT && frameOutT && snnhip_tensor_dtype(frameInT) == SNNHIP_U8 && snnhip_tensor_dtype(frameOutT) == SNNHIP_U8);
-    int in[4], out[4];
-    const int r = frameScale(frameInT, frameOutT, false, in, out);
-    if (r < 2 || out[1] % 2 || out[2] % 2) SNN_RIP("an NV12 output frame needs r = 2..4 and an even extent: %dx%d -> %dx%d", in[1], in[2], out[1], out[2]);
-    snnhip_rgb_luma_desc ld{in[0], in[1], in[2], channels, kr, kb};
-    hipChk(snnhip_rgb_luma_plan_create(ctx, &ld, &lumaPlan), "snnhip_rgb_luma_plan_create");
-    snnhip_rgb_cbcr_desc cd{in[0], in[1], in[2], channels, r, siting, range, kr, kb};
-    planarChroma = planar;
-    if (planar) hipChk(snnhip_rgb_cbcr_planar_plan_create(ctx, &cd, &cbcrPlan), "snnhip_rgb_cbcr_planar_plan_create");
-    else hipChk(snnhip_rgb_cbcr_plan_create(ctx, &cd, &cbcrPlan), "snnhip_rgb_cbcr_plan_create");
-    hipChk(snnhip_tensor_alloc(ctx, in[0], in[1], in[2], channels, SNNHIP_U8, &colourInT), "snnhip_tensor_alloc (colour input frame)");
-    hipChk(snnhip_tensor_alloc(ctx, planar ? 2 * out[0] : out[0], out[1] / 2, out[2] / 2, planar ? 1 : 2, SNNHIP_U8, &chromaOutT), "snnhip_tensor_alloc (chroma output plane)");
-}
-
-std::string HipBackend::describeVideo() const {
-    char buf[320];
-    if (fitLumaPlan && fitChromaPlan) {
-        std::string s;
-        if (snnhip_plan_describe(fitLumaPlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[luma fit] ") + buf + "\n";
-        if (snnhip_plan_describe(fitChromaPlan, buf, sizeof(buf)) == SNNHIP_OK) s += std::string("[chroma fit] ") + buf + "\n";
-        return s;
+void HipBackend::runSteps(const std::vector<FrameStep>& steps) {
+    for (auto& s : steps) {
+        const snnhip_tensor* ins[2] = {s.in0, s.in1};
+        hipChk(s.in1 ? snnhip_plan_run_n(s.plan, ins, 2, s.out) : snnhip_plan_run(s.plan, s.in0, s.out), s.what);
     }
-    if (cbcrPlan && snnhip_plan_describe(cbcrPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
-    if (yuvRgbPlan && snnhip_plan_describe(yuvRgbPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[rgb out] ") + buf + "\n";
-    if (chromaPlan && snnhip_plan_describe(chromaPlan, buf, sizeof(buf)) == SNNHIP_OK) return std::string("[chroma out] ") + buf + "\n";
-    return std::string();
 }
 
 void HipBackend::runFrameIn(const ImageTexture& modelInput) {
-    if (lumaPlan) hipChk(snnhip_plan_run(lumaPlan, colourInT, frameInT), "snnhip_plan_run (colour frame -> luma)");
+    runSteps(stepsIn);
     if (frameInPlan && !frameInFused) hipChk(snnhip_plan_run(frameInPlan, frameInT, modelInput.tensor()), "snnhip_plan_run (frame in)");
 }
 
 void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
     if (frameOutPlan && !frameOutFused) hipChk(snnhip_plan_run(frameOutPlan, lastOutput.tensor(), frameOutT), "snnhip_plan_run (frame out)");
-    if (mergePlan) {
-        const snnhip_tensor* ins[2] = {frameOutT, colourInT};
-        hipChk(snnhip_plan_run_n(mergePlan, ins, 2, colourOutT), "snnhip_plan_run_n (luma + chroma -> colour frame)");
-    }
-    if (chromaPlan) hipChk(snnhip_plan_run(chromaPlan, chromaInT, chromaOutT), "snnhip_plan_run (chroma plane)");
-    if (cbcrPlan) hipChk(snnhip_plan_run(cbcrPlan, colourInT, chromaOutT), "snnhip_plan_run (colour frame -> chroma plane)");
-    if (fitLumaPlan) hipChk(snnhip_plan_run(fitLumaPlan, frameOutT, fitLumaT), "snnhip_plan_run (luma frame -> fitted luma plane)");
-    if (fitChromaPlan) hipChk(snnhip_plan_run(fitChromaPlan, chromaInT, chromaOutT), "snnhip_plan_run (chroma plane -> fitted chroma plane)");
-    if (yuvRgbPlan) {
-        const snnhip_tensor* ins[2] = {frameOutT, chromaInT};
-        hipChk(snnhip_plan_run_n(yuvRgbPlan, ins, 2, rgbOutT), "snnhip_plan_run_n (luma + chroma plane -> RGB frame)");
-    }
+    runSteps(stepsOut);
 }
 
 // counterpart of VulkanBackend::initRenderPasses -> VulkanRenderPass ctor (vulkanBackend.cpp:43-78, vulkanRenderpass.cpp:103-178):

@@ -109,60 +109,44 @@ public:
     void joinSide() override;
     bool groupBegin() override;
     void groupEnd() override;
-    // 8-bit frame I/O (MixedInferenceCore::CreationParameters::outputFormat / inputsDesc[0].format): called before finalizeStages.  The conversion
-    // plans become nodes of the fusion graph; runFrameIn / runFrameOut launch whatever was not folded into a stage's fused plan.
-    // in16 / out16: that end is a 16-bit frame (u16 plans, SNNHIP_U16 tensor) with the container layout inShift / outMaxval, outShift.
-    void initFrameIO(bool in, bool out, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype, const float means[4],
-                     const float norms[4], const float scale[4], const float offset[4], bool in16 = false, bool out16 = false, int inShift = 0,
-                     int outMaxval = 65535, int outShift = 0);
+    // The frames at the model's ends (MixedInferenceCore::CreationParameters::frames, snn/frames.h): called once, before finalizeStages, with the
+    // model's input and output extents and its tensors' dtype.  spec.model: the 8- / 16-bit conversion plans (u16 plans and SNNHIP_U16 tensors at a
+    // 16-bit end) become nodes of the fusion graph; runFrameIn / runFrameOut launch whatever was not folded into a stage's fused plan.  spec.source /
+    // spec.sink: colour or video frames around a luma-only model whose own ends are R8 / R16 frames -- every plan they need becomes a step of stepsIn
+    // (in front of everything else of an inference) or stepsOut (behind it), launched in order on the context's stream (a straight line: no side
+    // stream, no parallel graph branch).  spec.planar (I420 / I010): the chroma tensors are [2n][h][w][1], plane 2k = Cb and 2k + 1 = Cr of frame k;
+    // chroma_up and plane_fit run with C = 1 over the 2n planes, yuv_rgb and rgb_cbcr as their planar plans: the launches are the same in number and place
+    void initFrames(const FrameSpec& spec, int n, int inH, int inW, int inC, int outH, int outW, int outC, int dtype);
     void runFrameIn(const ImageTexture& modelInput);
     void runFrameOut(const ImageTexture& lastOutput);
-    // colour frames around a luma-only model (CreationParameters::colourChannels): called after initFrameIO with R8 frames at both ends.  The luma
-    // plan fills the model's input frame from the colour frame in runFrameIn, the merge plan builds the colour output frame from the model's output
-    // frame and the colour frame in runFrameOut: two launches more on the context's stream, in front of and behind everything else of an inference.
-    void initColourIO(int channels, float kr, float kb);
-    int colourLaunches() const { return (lumaPlan ? 1 : 0) + (mergePlan ? 1 : 0); }
-    std::string describeColour() const; // one line per extra launch (empty without colour frames)
-    // NV12 / P010 video frames around a luma-only model (CreationParameters::videoDtype): called after initFrameIO with R8 / R16 frames at both
-    // ends.  The luma plane IS the model's frame; the chroma plan upsamples the CbCr plane [n][H/2][W/2][2] to [n][rH/2][rW/2][2] in runFrameOut,
-    // one launch more on the context's stream behind everything else of an inference (a straight line: no side stream, no parallel graph branch).
-    void initVideoIO(int dtype, int maxval, int shift, int siting, bool planar = false);
-    // ... or to packed RGB (CreationParameters::videoRgbChannels): the yuv_rgb plan builds the RGB / RGBA output frame [n][rH][rW][channels] from the
-    // model's output luma frame and the ORIGINAL CbCr plane in runFrameOut, in the chroma launch's place (no chroma plan, no upscaled chroma plane)
-    void initVideoRgbIO(int dtype, int maxval, int shift, int siting, int channels, int range, float kr, float kb, bool planar = false);
-    // ... or to an NV12 / P010 frame of any size between half and all of the model's output (CreationParameters::fitW / fitH): two plane_fit plans in
-    // runFrameOut, the model's output luma frame to [n][outH][outW][1] and the ORIGINAL CbCr plane to [n][outH/2][outW/2][2] (no chroma plan)
-    void initVideoFitIO(int dtype, int maxval, int shift, int siting, int outW, int outH, bool planar = false);
-    // RGB8 / RGBA8 frames in, an NV12 frame out (CreationParameters::encodeChannels): called after initFrameIO with R8 frames at both ends.  The luma
-    // plan of initColourIO fills the model's input frame in runFrameIn; the model's output frame IS the NV12 frame's luma plane; the rgb_cbcr plan
-    // builds its chroma plane [n][rH/2][rW/2][2] from the colour input frame in runFrameOut (no merge plan, no colour output frame)
-    void initEncodeIO(int channels, int siting, int range, float kr, float kb, bool planar = false);
-    // `planar` on the four above (CreationParameters::videoPlanar, I420 / I010): the chroma tensors are [2n][h][w][1], plane 2k = Cb and 2k + 1 = Cr of
-    // frame k; chroma_up and plane_fit run with C = 1 over the 2n planes, yuv_rgb and rgb_cbcr as snnhip_yuv_rgb_planar_plan_create /
-    // snnhip_rgb_cbcr_planar_plan_create.  The launches are the same in number and place
+    int frameLaunches() const { return static_cast<int>(stepsIn.size() + stepsOut.size()); }
+    std::string describeFrames() const; // one line for every step: "<label> <the plan's description>"
     bool planarVideo() const { return planarChroma; }
-    bool encodeOutput() const { return cbcrPlan != nullptr; }
-    int videoLaunches() const { return fitLumaPlan ? 2 : chromaPlan || yuvRgbPlan || cbcrPlan ? 1 : 0; }
-    std::string describeVideo() const; // one line for every extra launch (empty without video frames)
+    bool encodeOutput() const { return lumaChromaFromRgb; }
+    // the tensors the caller moves frames through, by role (null: no such end)
+    snnhip_tensor* frameInput() const { return uploadT; }
+    snnhip_tensor* frameOutput() const { return downloadT; }
     snnhip_tensor* chromaInput() const { return chromaInT; }
     snnhip_tensor* chromaOutput() const { return chromaOutT; }
-    snnhip_tensor* frameInput() const { return colourInT ? colourInT : frameInT; }
-    snnhip_tensor* frameOutput() const { return fitLumaT ? fitLumaT : rgbOutT ? rgbOutT : colourOutT ? colourOutT : frameOutT; }
 
 private:
-    snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned
-    snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // owned, SNNHIP_U8 or SNNHIP_U16
+    // one launch in front of or behind the model: plan (owned) from in0 (and in1) to out, all three among frameTensors
+    struct FrameStep {
+        snnhip_plan* plan;
+        const snnhip_tensor *in0, *in1;
+        snnhip_tensor* out;
+        const char *label, *what; // the bracketed name of describe(); what a failed launch is reported as
+    };
+    snnhip_tensor* ownTensor(int n, int h, int w, int c, int dtype, const char* what);
+    static void runSteps(const std::vector<FrameStep>& steps);
+    snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned: the model's own conversions, nodes of the fusion graph (finalizeStages)
+    snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // the model's own frames, SNNHIP_U8 or SNNHIP_U16
     bool frameInFused = false, frameOutFused = false;
-    snnhip_plan *lumaPlan = nullptr, *mergePlan = nullptr;   // owned
-    snnhip_tensor *colourInT = nullptr, *colourOutT = nullptr; // owned, SNNHIP_U8 [n][H][W][C] / [n][rH][rW][C]
-    snnhip_plan* chromaPlan = nullptr;                          // owned
-    snnhip_tensor *chromaInT = nullptr, *chromaOutT = nullptr;  // owned, SNNHIP_U8 / SNNHIP_U16 [n][H/2][W/2][2] / [n][rH/2][rW/2][2]
-    snnhip_plan* yuvRgbPlan = nullptr;                          // owned
-    snnhip_tensor* rgbOutT = nullptr;                           // owned, SNNHIP_U8 / SNNHIP_U16 [n][rH][rW][3 or 4]
-    snnhip_plan* cbcrPlan = nullptr;                            // owned (its output is chromaOutT, its input colourInT)
-    snnhip_plan *fitLumaPlan = nullptr, *fitChromaPlan = nullptr; // owned (the chroma plan runs chromaInT -> chromaOutT)
-    snnhip_tensor* fitLumaT = nullptr;                          // owned, SNNHIP_U8 / SNNHIP_U16 [n][outH][outW][1]
-    bool planarChroma = false;                                  // chromaInT / chromaOutT are [2n][h][w][1]
+    std::vector<FrameStep> stepsIn, stepsOut;
+    std::vector<snnhip_tensor*> frameTensors; // owned: every frame tensor
+    snnhip_tensor *uploadT = nullptr, *downloadT = nullptr, *chromaInT = nullptr, *chromaOutT = nullptr; // by role, among frameTensors
+    bool planarChroma = false;      // chromaInT / chromaOutT are [2n][h][w][1]
+    bool lumaChromaFromRgb = false; // downloadT is the luma plane and chromaOutT the chroma plane of a 4:2:0 frame made from RGB
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned
     void* recording = nullptr;            // snnhip_graph* of the last recorded inference

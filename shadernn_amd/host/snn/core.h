@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "snn/deviceTimer.h"
+#include "snn/frames.h"
 #include "snn/inferencegraph.h"
 #include "snn/layeroption.h"
 #include "snn/snn.h"
@@ -65,38 +66,13 @@ public:
         // HIP extension: record the launch sequence of the first run() as a hipGraph and replay it while the caller keeps feeding the same input
         // textures (re-recorded when they change).  Ignored with dumpOutputs / profiling / CPU stages (those need the host between launches).
         bool captureGraph = false;
-        // HIP extension: 8-bit frames at the model's ends (inputsDesc[0].format / outputFormat R8, RGB8 or RGBA8, channel count = the model's own).
-        // The conversions (snnhip_u8_in_plan_create / _u8_out_plan_create) join the stage graph handed to snnhip_graph_fuse, so the chain rules can
-        // fold them into fused kernels (ESPCN: rules A8 / B8); otherwise -- and always with dumps -- they run as launches of their own.
-        ColorFormat outputFormat = ColorFormat::RGBA32F;
-        float frameInMeans[4] = {0, 0, 0, 0}, frameInNorms[4] = {1, 1, 1, 1};
-        float frameOutScale[4] = {1, 1, 1, 1}, frameOutOffset[4] = {0, 0, 0, 0};
-        // 16-bit frames (R16, RGB16, RGBA16: snnhip_u16_in_plan_create / _u16_out_plan_create, handled exactly as the 8-bit ones): the container's
-        // layout.  Low-aligned 10 / 12-bit: maxval 1023 / 4095, shifts 0; P010-style high-aligned 10-bit: maxval 1023, shifts 6; full 16-bit: 65535.
-        int frameInShift = 0, frameOutMaxval = 65535, frameOutShift = 0;
-        bool halfTensors = false; // the model's tensors are fp16 (preferHp): the conversions read / write halfs
-        // HIP extension: colour frames around a luma-only model (snn_model_create7).  colourChannels 3 / 4 = RGB8 / RGBA8 frames at both ends of a model
-        // whose own ends are R8 frames: run() puts snnhip_rgb_luma_plan_create's launch in front of the model and snnhip_ycc_merge_plan_create's behind it
-        int colourChannels = 0;
-        float colourKr = 0.299f, colourKb = 0.114f;
-        // HIP extension: NV12 / P010 video frames around a luma-only model (snn_model_create8).  videoDtype SNNHIP_U8 / SNNHIP_U16 (0 = none): the
-        // model's own ends are R8 / R16 frames; run() puts snnhip_chroma_up_plan_create's launch on the half-resolution CbCr plane behind the model
-        int videoDtype = 0, videoMaxval = 255, videoShift = 0, videoSiting = 1;
-        // ... or, with videoRgbChannels 3 / 4 (snn_model_create9), snnhip_yuv_rgb_plan_create's launch instead: the model's output luma frame and the
-        // original CbCr plane to an RGB / RGBA frame (videoRange SNNHIP_RANGE_*, matrix videoKr / videoKb)
-        int videoRgbChannels = 0, videoRange = 0;
-        // ... or, with fitW / fitH (snn_model_create11), two snnhip_plane_fit_plan_create launches instead: the model's output luma frame and the
-        // original CbCr plane resampled to an NV12 / P010 frame of fitW x fitH (no chroma_up launch)
-        int fitW = 0, fitH = 0;
-        float videoKr = 0.299f, videoKb = 0.114f;
-        // HIP extension: RGB8 / RGBA8 frames in, an NV12 frame out around a luma-only model (snn_model_create10).  encodeChannels 3 / 4: run() puts
-        // snnhip_rgb_luma_plan_create's launch in front of the model, as colourChannels does, and snnhip_rgb_cbcr_plan_create's behind it, from the
-        // colour input frame to the output frame's chroma plane (encodeSiting SNNHIP_SITING_*, encodeRange SNNHIP_RANGE_*, matrix colourKr / colourKb)
-        int encodeChannels = 0, encodeSiting = 1, encodeRange = 0;
-        // HIP extension: planar 4:2:0 frames (I420 / I010, snn_model_create12) on the video end(s) of any of the four paths above: the chroma tensors
-        // are [2 * batch][h][w][1] (plane 2n = Cb, 2n + 1 = Cr of frame n) instead of [batch][h][w][2]; chroma_up and plane_fit run with C = 1 over
-        // the 2 * batch planes, yuv_rgb and rgb_cbcr as their planar plans.  The same number of launches; no interleaving launch anywhere
-        bool videoPlanar = false;
+        bool halfTensors = false; // the model's tensors are fp16 (preferHp): the frame conversions read / write halfs
+        // HIP extension: the frames at the model's ends (snn/frames.h; the default is none: float tensors in and out).  frames.model names 8- / 16-bit
+        // frames of the model's own channel count (inputsDesc[0].format is the same format as a ColorFormat): their conversions join the stage graph
+        // handed to snnhip_graph_fuse, so the chain rules can fold them into fused kernels (ESPCN: rules A8 / B8); otherwise -- and always with dumps --
+        // they run as launches of their own.  frames.source / sink name colour or video frames around a luma-only model: launches in front of and
+        // behind the model's on the same stream (HipBackend::initFrames)
+        FrameSpec frames;
     };
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const CreationParameters& cp);
     static std::unique_ptr<MixedInferenceCore> create(GpuContext* context, const std::string& modelFileName, const dp::ShaderGenOptions& options,

@@ -10,6 +10,7 @@
 #include "ic2/layerFactory.h"
 #include "snn/contextFactory.h"
 #include "snn/core.h"
+#include "snn/frames.h"
 #include "snn/planes.h"
 
 using namespace snn;
@@ -49,158 +50,40 @@ static void makeIO(snn_model* m, bool half = false) {
 
 extern "C" {
 
-int snn_model_create(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                     snn_model** out) {
-    return snn_model_create2(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, 0, out);
-}
+// what every snn_model_create* takes beside its frame struct
+struct ModelArgs {
+    const char* json_path;
+    int device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch;
+    snn_model** out;
+};
 
-int snn_model_create2(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                      int prefer_half, snn_model** out) {
-    return snn_model_create3(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, 0, out);
-}
-
-int snn_model_create3(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                      int prefer_half, int capture_graph, snn_model** out) {
-    return snn_model_create4(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, 1, out);
-}
-
-int snn_model_create4(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                      int prefer_half, int capture_graph, int batch, snn_model** out) {
-    return snn_model_create5(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, nullptr, out);
-}
-
-static bool frameFormat(int f, ColorFormat* c) {
-    switch (f) {
-    case SNN_IO_FLOAT: return true;
-    case SNN_IO_R8: *c = ColorFormat::R8; return true;
-    case SNN_IO_RGB8: *c = ColorFormat::RGB8; return true;
-    case SNN_IO_RGBA8: *c = ColorFormat::RGBA8; return true;
-    default: return false;
-    }
-}
-
-static bool frameFormat2(int f, ColorFormat* c) {
-    switch (f) {
-    case SNN_IO_R16: *c = ColorFormat::R16; return true;
-    case SNN_IO_RGB16: *c = ColorFormat::RGB16; return true;
-    case SNN_IO_RGBA16: *c = ColorFormat::RGBA16; return true;
-    default: return frameFormat(f, c);
-    }
-}
-
-int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                      int prefer_half, int capture_graph, int batch, const snn_frame_io* io, snn_model** out) {
-    ColorFormat probe = ColorFormat::NONE;
-    if (io && (!frameFormat(io->in_format, &probe) || !frameFormat(io->out_format, &probe))) return -1; // (the 8-bit formats only)
-    if (!io) return snn_model_create6(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, nullptr, out);
-    snn_frame_io2 io2{};
-    io2.in_format = io->in_format;
-    io2.out_format = io->out_format;
-    memcpy(io2.in_means, io->in_means, sizeof(io2.in_means));
-    memcpy(io2.in_norms, io->in_norms, sizeof(io2.in_norms));
-    memcpy(io2.out_scale, io->out_scale, sizeof(io2.out_scale));
-    memcpy(io2.out_offset, io->out_offset, sizeof(io2.out_offset));
-    io2.out_maxval = 65535;
-    return snn_model_create6(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, out);
-}
-
-// snn_model_create6 / 7 / 8: `colour` (snn_model_create7) asks for RGB8 / RGBA8 frames around a model that `io` gives R8 frames at both ends, `video`
-// (snn_model_create8) for NV12 / P010 frames around a model that `io` gives R8 / R16 frames, `videoRgb` (snn_model_create9, beside `video`) for an RGB
-// frame at the output instead of NV12 / P010, `encode` (snn_model_create10) for RGB8 / RGBA8 frames in and an NV12 frame out around a model that `io`
-// gives R8 frames, `fit` (snn_model_create11, beside `video`) for an NV12 / P010 output frame of fit->out_w x fit->out_h instead of r times the input,
-// `planar` (snn_model_create12, beside `video` or `encode`) for I420 / I010 planes instead of the interleaved chroma plane on the video end(s)
-static int createModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                       int capture_graph, int batch, const snn_frame_io2* io, const snn_colour_io* colour, snn_model** out, const snn_video_io* video = nullptr,
-                       const snn_video_rgb_io* videoRgb = nullptr, const snn_encode_io* encode = nullptr, const snn_fit_io* fit = nullptr, bool planar = false) {
-    if (!json_path || !out || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return -1;
-    ColorFormat inFmt = ColorFormat::NONE, outFmt = ColorFormat::NONE;
-    if (io && (!frameFormat2(io->in_format, &inFmt) || !frameFormat2(io->out_format, &outFmt))) return -1;
-    if (io && io->in_format != SNN_IO_FLOAT && (io->in_format & 0xff) != in_c) return -1;
-    if (io && isFrame16Format(inFmt) && (io->in_shift < 0 || io->in_shift > 15)) return -1;
-    if (io && isFrame16Format(outFmt) &&
-        (io->out_maxval < 1 || io->out_maxval > 65535 || io->out_shift < 0 || io->out_shift > 15 || (static_cast<long long>(io->out_maxval) << io->out_shift) > 65535))
-        return -1;
-    const bool half = prefer_half != 0;
+static int createModel(const ModelArgs& a, const FrameSpec& spec) {
+    if (!a.json_path || !a.out) return -1;
+    const bool half = a.prefer_half != 0;
     auto* m = new snn_model();
     // C++ exceptions (std::bad_alloc, a parser's std::out_of_range, ...) must not unwind through the C boundary: report -2 and free what was built.
     // (SNN_RIP is the reference's abort-on-fatal-error convention, utils.h:57-62: it terminates the process and is not an exception.)
     try {
-        m->batch = batch;
-        m->context = createHipContext(device);
-        m->inW = in_w;
-        m->inH = in_h;
-        m->inC = in_c;
-        dp::ShaderGenOptions sgo = makeOptions(in_w, in_h, in_c, fuse_chains != 0, half, batch);
-        if (inFmt != ColorFormat::NONE) sgo.desiredInput[0].format = inFmt;
-        if (outFmt != ColorFormat::NONE) sgo.desiredOutputFormat = outFmt;
-        auto layers = dp::loadFromJsonModel(json_path, false, sgo.mrtMode, sgo.weightMode, half); // preferHp: weights truncated to fp16 (Q13)
+        m->batch = a.batch;
+        m->context = createHipContext(a.device);
+        m->inW = a.in_w;
+        m->inH = a.in_h;
+        m->inC = a.in_c;
+        dp::ShaderGenOptions sgo = makeOptions(a.in_w, a.in_h, a.in_c, a.fuse_chains != 0, half, a.batch);
+        if (spec.model.in_format != SNN_IO_FLOAT) sgo.desiredInput[0].format = frameColorFormat(spec.model.in_format);
+        if (spec.model.out_format != SNN_IO_FLOAT) sgo.desiredOutputFormat = frameColorFormat(spec.model.out_format);
+        auto layers = dp::loadFromJsonModel(a.json_path, false, sgo.mrtMode, sgo.weightMode, half); // preferHp: weights truncated to fp16 (Q13)
         MixedInferenceCore::CreationParameters cp;
         static_cast<InferenceGraph&>(cp) = dp::generateInferenceGraph(layers, sgo);
-        cp.dumpOutputs = dump_outputs != 0;
-        cp.fuseChains = fuse_chains != 0;
-        cp.profiling = profiling != 0;
-        cp.captureGraph = capture_graph != 0;
-        cp.outputFormat = sgo.desiredOutputFormat;
+        cp.dumpOutputs = a.dump_outputs != 0;
+        cp.fuseChains = a.fuse_chains != 0;
+        cp.profiling = a.profiling != 0;
+        cp.captureGraph = a.capture_graph != 0;
         cp.halfTensors = half;
-        cp.videoPlanar = planar;
-        if (colour || video || encode) { // the model must be luma-only: one channel out, at 1..4 times the input's extent (refused here, before anything is built on the device)
-            const auto& od = cp.layers.back()->outputDesc;
-            const uint32_t r = od.width / static_cast<uint32_t>(in_w);
-            if (od.channels != 1 || r < 1 || r > 4 || od.width != r * static_cast<uint32_t>(in_w) || od.height != r * static_cast<uint32_t>(in_h)) {
-                snn_model_destroy(m);
-                return -1;
-            }
-            if (encode) { // the output frame is 4:2:0: r = 2..4 (r = 1 would decimate the chroma grid) and an even extent
-                if (r < 2 || (r * static_cast<uint32_t>(in_w)) % 2 || (r * static_cast<uint32_t>(in_h)) % 2) {
-                    snn_model_destroy(m);
-                    return -1;
-                }
-                cp.encodeChannels = encode->in_format & 0xff;
-                cp.encodeSiting = encode->siting;
-                cp.encodeRange = encode->range;
-                cp.colourKr = encode->kr;
-                cp.colourKb = encode->kb;
-            } else if (colour) {
-                cp.colourChannels = colour->format & 0xff;
-                cp.colourKr = colour->kr;
-                cp.colourKb = colour->kb;
-            } else {
-                cp.videoDtype = video->format == SNN_IO_NV12 ? SNNHIP_U8 : SNNHIP_U16;
-                cp.videoMaxval = video->maxval;
-                cp.videoShift = video->shift;
-                cp.videoSiting = video->siting;
-                if (fit) { // the r-fold frame is resampled DOWN to the target: r * in / 2 <= out <= r * in on both axes
-                    const long long rw = static_cast<long long>(r) * in_w, rh = static_cast<long long>(r) * in_h;
-                    if (fit->out_w > rw || fit->out_h > rh || 2ll * fit->out_w < rw || 2ll * fit->out_h < rh) {
-                        std::string fits;
-                        for (int q = 1; q <= 4; ++q)
-                            if (fit->out_w <= 1ll * q * in_w && fit->out_h <= 1ll * q * in_h && 2ll * fit->out_w >= 1ll * q * in_w && 2ll * fit->out_h >= 1ll * q * in_h)
-                                fits += (fits.empty() ? "" : ", ") + std::to_string(q);
-                        SNN_LOGE("snn_model_create1%c: the model is r = %u: %dx%d -> %lldx%lld, and %dx%d is %s; %s%s", planar ? '2' : '1', r, in_w, in_h, rw, rh, fit->out_w, fit->out_h,
-                                 (fit->out_w > rw || fit->out_h > rh) ? "larger than that" : "less than half of that", fits.empty() ? "no r = 1..4 fits both axes" : "a model of r = ",
-                                 fits.c_str());
-                        snn_model_destroy(m);
-                        return -1;
-                    }
-                    cp.fitW = fit->out_w;
-                    cp.fitH = fit->out_h;
-                }
-                if (videoRgb) {
-                    cp.videoRgbChannels = videoRgb->out_format & 0xff;
-                    cp.videoRange = videoRgb->range;
-                    cp.videoKr = videoRgb->kr;
-                    cp.videoKb = videoRgb->kb;
-                }
-            }
-        }
-        if (io) {
-            memcpy(cp.frameInMeans, io->in_means, sizeof(cp.frameInMeans));
-            memcpy(cp.frameInNorms, io->in_norms, sizeof(cp.frameInNorms));
-            memcpy(cp.frameOutScale, io->out_scale, sizeof(cp.frameOutScale));
-            memcpy(cp.frameOutOffset, io->out_offset, sizeof(cp.frameOutOffset));
-            cp.frameInShift = io->in_shift;
-            cp.frameOutMaxval = io->out_maxval;
-            cp.frameOutShift = io->out_shift;
+        cp.frames = spec;
+        if (!framesFitModel(spec, a.in_w, a.in_h, cp.layers.back()->outputDesc)) { // (refused here, before anything is built on the device)
+            snn_model_destroy(m);
+            return -1;
         }
         m->core = MixedInferenceCore::create(m->context, cp);
         makeIO(m, half);
@@ -213,197 +96,82 @@ static int createModel(const char* json_path, int device, int in_w, int in_h, in
         snn_model_destroy(m);
         return -2;
     }
-    *out = m;
+    *a.out = m;
     return 0;
+}
+
+// snn_model_create<entry>: `io` is that entry point's struct, resolved to the one description everything below takes (snn/frames.h)
+static int create(const ModelArgs& a, int entry, const void* io) {
+    FrameSpec spec;
+    if (!resolveFrames(entry, io, a.in_w, a.in_h, a.in_c, a.batch, &spec)) return -1;
+    return createModel(a, spec);
+}
+
+int snn_frames_resolve(int entry, const void* io, int in_w, int in_h, int in_c, int batch, char* buf, int buflen) {
+    FrameSpec spec;
+    if (!resolveFrames(entry, io, in_w, in_h, in_c, batch, &spec)) return -1;
+    if (buf && buflen > 0) snprintf(buf, static_cast<size_t>(buflen), "%s", formatFrameSpec(spec).c_str());
+    return 0;
+}
+
+int snn_model_create(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                     snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, 0, 0, 1, out}, 5, nullptr);
+}
+
+int snn_model_create2(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, 0, 1, out}, 5, nullptr);
+}
+
+int snn_model_create3(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, 1, out}, 5, nullptr);
+}
+
+int snn_model_create4(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 5, nullptr);
+}
+
+int snn_model_create5(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                      int prefer_half, int capture_graph, int batch, const snn_frame_io* io, snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 5, io);
 }
 
 int snn_model_create6(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, const snn_frame_io2* io, snn_model** out) {
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, nullptr, out);
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 6, io);
 }
 
 int snn_model_create7(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, const snn_colour_io* io, snn_model** out) {
-    if (!io || (io->format != SNN_IO_RGB8 && io->format != SNN_IO_RGBA8) || in_c != 1) return -1;
-    if (!(io->kr > 0.0f && io->kb > 0.0f && io->kr + io->kb < 1.0f)) return -1;
-    snn_frame_io2 io2{};
-    io2.in_format = io2.out_format = SNN_IO_R8;
-    for (int c = 0; c < 4; ++c) {
-        io2.in_means[c] = io->in_mean;
-        io2.in_norms[c] = io->in_norm;
-        io2.out_scale[c] = io->out_scale;
-        io2.out_offset[c] = io->out_offset;
-    }
-    io2.out_maxval = 65535;
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, io, out);
-}
-
-// snn_model_create8, snn_model_create11 with `fit`, and the planar-to-planar paths of snn_model_create12 with `planar`
-static int createVideoModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                            int capture_graph, int batch, const snn_video_io* io, snn_model** out, const snn_fit_io* fit, bool planar = false) {
-    if (!io || (io->format != SNN_IO_NV12 && io->format != SNN_IO_NV12_16) || in_c != 1 || batch < 1) return -1;
-    if (in_w < 2 || in_h < 2 || in_w % 2 || in_h % 2) return -1; // 4:2:0: the chroma plane is half the extent
-    const bool wide = io->format == SNN_IO_NV12_16;
-    if (io->siting != SNN_SITING_CENTRE && io->siting != SNN_SITING_LEFT) return -1;
-    if (io->maxval < 1 || io->maxval > 4095 || io->shift < 0 || io->shift > (wide ? 15 : 0)) return -1; // (P016 chroma is not built: include/snnhip.h)
-    if ((static_cast<long long>(io->maxval) << io->shift) > (wide ? 65535 : 255)) return -1;
-    snn_frame_io2 io2{};
-    io2.in_format = io2.out_format = wide ? SNN_IO_R16 : SNN_IO_R8;
-    for (int c = 0; c < 4; ++c) {
-        io2.in_means[c] = io->in_mean;
-        io2.in_norms[c] = io->in_norm;
-        io2.out_scale[c] = io->out_scale;
-        io2.out_offset[c] = io->out_offset;
-    }
-    io2.in_shift = wide ? io->shift : 0;
-    io2.out_maxval = wide ? io->maxval : 65535; // (snn_model_create5 passes 65535 for the 8-bit formats: the same model)
-    io2.out_shift = wide ? io->shift : 0;
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, io, nullptr, nullptr,
-                       fit, planar);
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 7, io);
 }
 
 int snn_model_create8(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, const snn_video_io* io, snn_model** out) {
-    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, nullptr);
-}
-
-// snn_model_create11, and the fitted path of snn_model_create12 with `planar`
-static int createFitModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                          int capture_graph, int batch, const snn_fit_io* io, snn_model** out, bool planar) {
-    if (!io) return -1;
-    if (io->out_w < 2 || io->out_h < 2 || io->out_w % 2 || io->out_h % 2) return -1; // 4:2:0 at the output too
-    if (in_w < 1 || in_h < 1) return -1;
-    if (2ll * io->out_w < in_w || 2ll * io->out_h < in_h || io->out_w > 4ll * in_w || io->out_h > 4ll * in_h) return -1; // the chroma plane's ratio: [1/2, 4]
-    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io->video, out, io, planar);
-}
-
-int snn_model_create11(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
-                       int prefer_half, int capture_graph, int batch, const snn_fit_io* io, snn_model** out) {
-    return createFitModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, false);
-}
-
-// the luma plane's maps of a video frame from its range (snn_model_create9 states them): k = (maxval + 1) / 256
-static void lumaMapsOfRange(int maxval, int range, snn_video_io* video) {
-    const double k = (maxval + 1) / 256.0;
-    const double yoff = range == SNN_RANGE_LIMITED ? 16.0 * k : 0.0, yrange = range == SNN_RANGE_LIMITED ? 219.0 * k : maxval;
-    video->in_mean = static_cast<float>(yoff);
-    video->in_norm = static_cast<float>(1.0 / yrange);
-    video->out_scale = static_cast<float>(yrange);
-    video->out_offset = static_cast<float>(yoff);
-}
-
-// snn_model_create9, and the planar-to-RGB path of snn_model_create12 with `planar` (io->in_format names the interleaved format of the same depth)
-static int createVideoRgbModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                               int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out, bool planar) {
-    if (!io || (io->in_format != SNN_IO_NV12 && io->in_format != SNN_IO_NV12_16) || in_c != 1 || batch < 1) return -1;
-    const bool wide = io->in_format == SNN_IO_NV12_16;
-    if (wide ? (io->out_format != SNN_IO_RGB16 && io->out_format != SNN_IO_RGBA16) : (io->out_format != SNN_IO_RGB8 && io->out_format != SNN_IO_RGBA8)) return -1;
-    if (in_w < 2 || in_h < 2 || in_w % 2 || in_h % 2) return -1; // 4:2:0: the chroma plane is half the extent
-    if (io->siting != SNN_SITING_CENTRE && io->siting != SNN_SITING_LEFT) return -1;
-    if (io->range != SNN_RANGE_LIMITED && io->range != SNN_RANGE_FULL) return -1;
-    if (io->maxval < 255 || io->maxval > (wide ? 4095 : 255) || (io->maxval + 1) % 256 || io->shift < 0 || io->shift > (wide ? 15 : 0)) return -1;
-    if ((static_cast<long long>(io->maxval) << io->shift) > (wide ? 65535 : 255)) return -1;
-    if (!(io->kr > 0.0f && io->kb > 0.0f && io->kr + io->kb < 1.0f)) return -1;
-    // the luma plane's maps follow from the range
-    snn_video_io video{};
-    video.format = io->in_format;
-    video.maxval = io->maxval;
-    video.shift = io->shift;
-    video.siting = io->siting;
-    lumaMapsOfRange(io->maxval, io->range, &video);
-    snn_frame_io2 io2{};
-    io2.in_format = io2.out_format = wide ? SNN_IO_R16 : SNN_IO_R8;
-    for (int c = 0; c < 4; ++c) {
-        io2.in_means[c] = video.in_mean;
-        io2.in_norms[c] = video.in_norm;
-        io2.out_scale[c] = video.out_scale;
-        io2.out_offset[c] = video.out_offset;
-    }
-    io2.in_shift = wide ? io->shift : 0;
-    io2.out_maxval = wide ? io->maxval : 65535; // (as snn_model_create8)
-    io2.out_shift = wide ? io->shift : 0;
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, &video, io, nullptr,
-                       nullptr, planar);
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 8, io);
 }
 
 int snn_model_create9(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                       int prefer_half, int capture_graph, int batch, const snn_video_rgb_io* io, snn_model** out) {
-    return createVideoRgbModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, false);
-}
-
-// snn_model_create10, and the RGB-to-planar path of snn_model_create12 with `planar` (io->out_format is SNN_IO_NV12 either way)
-static int createEncodeModel(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling, int prefer_half,
-                             int capture_graph, int batch, const snn_encode_io* io, snn_model** out, bool planar) {
-    if (!io || (io->in_format != SNN_IO_RGB8 && io->in_format != SNN_IO_RGBA8) || io->out_format != SNN_IO_NV12 || in_c != 1 || batch < 1) return -1;
-    if (io->siting != SNN_SITING_CENTRE && io->siting != SNN_SITING_LEFT) return -1;
-    if (io->range != SNN_RANGE_LIMITED && io->range != SNN_RANGE_FULL) return -1;
-    if (!(io->kr > 0.0f && io->kb > 0.0f && io->kr + io->kb < 1.0f)) return -1;
-    // (whether r * in_w and r * in_h are even is known once the model file gives r: createModel refuses an odd one before any plan is made)
-    // the luma maps follow from the range: full-range luma in (rgb_luma), the range's luma codes out
-    const bool limited = io->range == SNN_RANGE_LIMITED;
-    snn_frame_io2 io2{};
-    io2.in_format = io2.out_format = SNN_IO_R8;
-    for (int c = 0; c < 4; ++c) {
-        io2.in_means[c] = 0.0f;
-        io2.in_norms[c] = 1.0f / 255.0f;
-        io2.out_scale[c] = limited ? 219.0f : 255.0f;
-        io2.out_offset[c] = limited ? 16.0f : 0.0f;
-    }
-    io2.out_maxval = 65535; // (as snn_model_create5)
-    return createModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &io2, nullptr, out, nullptr, nullptr, io,
-                       nullptr, planar);
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 9, io);
 }
 
 int snn_model_create10(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_encode_io* io, snn_model** out) {
-    return createEncodeModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, io, out, false);
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 10, io);
+}
+
+int snn_model_create11(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_fit_io* io, snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 11, io);
 }
 
 int snn_model_create12(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_planar_io* io, snn_model** out) {
-    if (!io || in_c != 1 || batch < 1) return -1;
-    const bool fitted = io->out_w != 0 || io->out_h != 0;
-    if (io->in_format == SNN_IO_RGB8 || io->in_format == SNN_IO_RGBA8) { // capture in, planar out: snn_model_create10's path
-        if (io->out_format != SNN_IO_I420 || fitted) return -1;
-        snn_encode_io e{};
-        e.in_format = io->in_format;
-        e.out_format = SNN_IO_NV12;
-        e.siting = io->siting;
-        e.range = io->range;
-        e.kr = io->kr;
-        e.kb = io->kb;
-        return createEncodeModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &e, out, true);
-    }
-    if (io->in_format != SNN_IO_I420 && io->in_format != SNN_IO_I420_16) return -1;
-    const bool wide = io->in_format == SNN_IO_I420_16;
-    const int interleaved = wide ? SNN_IO_NV12_16 : SNN_IO_NV12;
-    if (io->out_format != io->in_format) { // planar in, RGB out: snn_model_create9's path (which checks the rest)
-        if (fitted) return -1; // (RGB output at a fitted size is not built)
-        snn_video_rgb_io v{};
-        v.in_format = interleaved;
-        v.out_format = io->out_format; // RGB8 / RGBA8 beside 8-bit planes, RGB16 / RGBA16 beside 16-bit ones: anything else is refused there
-        v.maxval = io->maxval;
-        v.shift = io->shift;
-        v.siting = io->siting;
-        v.range = io->range;
-        v.kr = io->kr;
-        v.kb = io->kb;
-        return createVideoRgbModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &v, out, true);
-    }
-    // planar in, planar out: snn_model_create8's path, or snn_model_create11's with a fitted size.  The luma maps follow from the range, which needs
-    // the depth's k = (maxval + 1) / 256 to be an integer, as in snn_model_create9 (the matrix is not used: kr and kb are not looked at)
-    if (io->range != SNN_RANGE_LIMITED && io->range != SNN_RANGE_FULL) return -1;
-    if (io->maxval < 255 || io->maxval > (wide ? 4095 : 255) || (io->maxval + 1) % 256) return -1;
-    snn_fit_io f{};
-    f.video.format = interleaved;
-    f.video.maxval = io->maxval;
-    f.video.shift = io->shift;
-    f.video.siting = io->siting;
-    lumaMapsOfRange(io->maxval, io->range, &f.video);
-    f.out_w = io->out_w;
-    f.out_h = io->out_h;
-    if (fitted) return createFitModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &f, out, true);
-    return createVideoModel(json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, &f.video, out, nullptr, true);
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 12, io);
 }
 
 // one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame
