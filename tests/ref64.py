@@ -4,12 +4,30 @@ fused kernels to fp32 accuracy.
 The fp32 C oracle is itself 2e-7 to 5e-7 (max) and about 3e-8 (mean) away from the exact result: those two numbers, measured on the very input of a
 test (E32max, E32mean), are the unit in which a kernel's own distance from the exact result is expressed.  A kernel that computes in fp32 lands within
 a small multiple M of them; one that lost mantissa bits somewhere (a TF32 or split-f16 product, a truncated weight, a bias off by 2e-6) does not,
-although all of these pass rtol = atol = 1e-4 against the oracle."""
+although all of these pass rtol = atol = 1e-4 against the oracle.
+
+The general fp32 convolution kernels (deep reductions: K = IC k^2 up to 4608, split-K, Winograd) get a reference of any kernel size, stride, pad mode and
+output extent (conv2d_general) and a sharper unit: the oracle sums its K terms one after the other, so its own error grows with K (21 x a pairwise sum's at
+K = 4608) and a budget in units of it lets 16-bit weights through.  conv2d_pairwise32 forms every product in fp32 and reduces K by a tree of fp32 additions;
+its distance from float64 (E32p) is what an fp32 kernel with a blocked or tree-shaped reduction can reach, and budget_pairwise holds a kernel to M_CONV times it,
+with a third bound on the mean signed error per output channel (a bias off by 2e-6 hides in max and mean at these depths)."""
 import numpy as np
 
 # The margin of every budget test: twice the largest ratio any fp32 kernel family showed against float64 on an MI355X (2.02, DESIGN.md section 3
 # has the table), rounded up to a power of two.  It is also the largest at which the 2e-6 bias mutant of tests/test_ref64.py (9.7 x E32mean) is rejected.
 M = 8
+
+# The margin of the convolution budget tests (budget_pairwise), one value for all fp32 convolution families.  Measured on an MI355X in units of E32p
+# (DESIGN.md section 3 has the table): up to 8.4 where no accumulator adds more than 1152 terms one after the other, 12.1 to 13.2 in the three cases with a
+# chain of 2304 (conv2d_generic at K = 2304, conv2d_mfma split two ways and conv2d_ksplit over two waves at K = 4608).  The rule of M (twice the largest,
+# rounded up to a power of two) gives 32, but from 27 on the 2e-6 bias mutant of tests/test_ref64.py is no longer rejected: the constant is the largest power
+# of two at which all four mutants are, and the chain-2304 cases keep a factor of 1.2 instead of two (the kernels are deterministic: the ratios reproduce).
+M_CONV = 16
+# conv2d_mfma with the split over K pinned off at K = 4608 (SNNHIP_CONV_SPLITK=1: one chain of 4608 terms per output, which the planner never chooses):
+# 24.5 x max, the fp32 C oracle's own ratio on that layer (18.8 x: it adds one term after the other too).  Summation order, not lost bits; held to the cap
+# of 32, at which the 16-bit-weight mutant (52 x max, 64 x mean at its smallest), the missing block and the unwritten row are rejected and the bias mutant
+# (27 x to 31 x per channel) is not.
+M_CONV_UNSPLIT = 32
 
 _BN_EPS = float(np.float32(0.001))    # oracle/snn_oracle.c:bn_apply: sqrtf(var + 0.001f) ...
 _BN_FLOOR = float(np.float32(0.0001))  # ... floored at 0.0001f
@@ -56,7 +74,150 @@ def activation(name, v, alpha=0.0):
         return 1.0 / (1.0 + np.exp(-v))
     if name == "tanh":
         return np.tanh(v)
+    if name == "SiLU":
+        return v / (1.0 + np.exp(-v))
     raise ValueError("ref64: unknown activation %r" % (name,))
+
+
+def _resolve(lo, count, size, pad_mode):
+    """The source coordinates lo .. lo + count - 1 under a pad mode; -1 = the read returns zero.  Reflect mirrors once about the first / last sample
+    (no repeated edge) and reads zero where that still falls outside, replicate clamps, constant (and "none") reads zero outside."""
+    s = np.arange(lo, lo + count)
+    if pad_mode == "replicate":
+        return np.clip(s, 0, size - 1)
+    if pad_mode == "reflect":
+        s = np.abs(s)
+        s = np.where(s >= size, 2 * size - 2 - s, s)
+    elif pad_mode not in ("constant", "none"):
+        raise ValueError("ref64: unknown pad mode %r" % (pad_mode,))
+    return np.where((s >= 0) & (s < size), s, -1)
+
+
+def _padded(x, k, stride, pads, pad_mode, out_hw):
+    """x [N,H,W,C] as the explicitly padded array an output of out_hw reads: rows -padL .. (OH - 1) stride + k - 1 - padL, columns likewise from -padT
+    (pads = (T, B, L, R); the reference hands T to the column offset and L to the row offset, its quirk Q3 -- every "same" / "valid" layer has T = L).
+    The far pads are not used: the extent comes from the caller, and what lies beyond the data reads padding.  A 1 x 1 kernel has no padding at all."""
+    n, h, w, c = x.shape
+    oh, ow = out_hw
+    padx, pady = (0, 0) if k == 1 else (pads[0], pads[2])
+    rows = _resolve(-pady, (oh - 1) * stride + k, h, "constant" if k == 1 else pad_mode)
+    cols = _resolve(-padx, (ow - 1) * stride + k, w, "constant" if k == 1 else pad_mode)
+    xp = x[:, np.maximum(rows, 0)][:, :, np.maximum(cols, 0)]
+    xp[:, rows < 0] = 0
+    xp[:, :, cols < 0] = 0
+    return xp
+
+
+def conv2d_general(x, w_oihw, bias=None, stride=1, pads=(0, 0, 0, 0), pad_mode="constant", out_hw=None):
+    """k x k convolution in float64: any k (even k with the asymmetric "same" offsets of quirk Q1 in pads), stride 1 or 2, constant / replicate / reflect
+    padding, the output extent out_hw = (OH, OW) from the caller (the reference's size rules Q2 / Q20 stay with oracle_lib.out_dim).  k*k shifted matmuls
+    over the padded array.  x [N,H,W,IC], w [OC,IC,k,k] -> [N,OH,OW,OC]."""
+    x, w = _f64(x), _f64(w_oihw)
+    oc, ic, k, k2 = w.shape
+    assert x.ndim == 4 and x.shape[3] == ic and k == k2 and stride in (1, 2), (x.shape, w.shape, stride)
+    oh, ow = out_hw
+    xp = _padded(x, k, stride, pads, pad_mode, out_hw)
+    y = np.zeros((x.shape[0], oh, ow, oc), np.float64)
+    for dy in range(k):
+        for dx in range(k):
+            y += xp[:, dy:dy + (oh - 1) * stride + 1:stride, dx:dx + (ow - 1) * stride + 1:stride, :] @ w[:, :, dy, dx].T
+    if bias is not None:
+        y += _f64(bias)
+    return y
+
+
+def maxpool(x, k=3, stride=2, out_hw=None):
+    """Max-pooling with the window clipped to the image (no padding), in the dtype of x; the extent from the caller (oracle_lib.pool_out_dim)."""
+    x = np.asarray(x)
+    n, h, w, c = x.shape
+    oh, ow = out_hw
+    assert (oh - 1) * stride < h and (ow - 1) * stride < w, (x.shape, out_hw)
+    y = np.full((n, oh, ow, c), -np.inf, x.dtype)
+    for fy in range(k):
+        for fx in range(k):
+            v = x[:, fy::stride, fx::stride][:, :oh, :ow]
+            y[:, :v.shape[1], :v.shape[2]] = np.maximum(y[:, :v.shape[1], :v.shape[2]], v)
+    return y
+
+
+_PAIRWISE_BYTES = 1 << 27  # the product array of one output-channel chunk
+
+
+def conv2d_pairwise32(x, w_oihw, bias=None, stride=1, pads=(0, 0, 0, 0), pad_mode="constant", out_hw=None):
+    """The same convolution in fp32 with a pairwise reduction: every product x * w formed in np.float32, the K = k*k*IC products of an output ordered
+    (dy, dx, ic) and summed by a tree of fp32 additions (neighbours added level by level; an odd level is padded with one zero), then the bias added in
+    fp32.  No matmul, no einsum: deterministic on every machine.  Its distance from conv2d_general is the unit E32p of budget_pairwise."""
+    x, w = np.asarray(x, np.float32), np.asarray(w_oihw, np.float32)
+    oc, ic, k, k2 = w.shape
+    assert x.ndim == 4 and x.shape[3] == ic and k == k2 and stride in (1, 2), (x.shape, w.shape, stride)
+    oh, ow = out_hw
+    xp = _padded(x, k, stride, pads, pad_mode, out_hw)
+    pix, kk = x.shape[0] * oh * ow, k * k * ic
+    xs = np.empty((kk, pix), np.float32)
+    for dy in range(k):
+        for dx in range(k):
+            xs[(dy * k + dx) * ic:(dy * k + dx + 1) * ic] = xp[:, dy:dy + (oh - 1) * stride + 1:stride, dx:dx + (ow - 1) * stride + 1:stride, :].reshape(pix, ic).T
+    ws = np.ascontiguousarray(w.transpose(2, 3, 1, 0).reshape(kk, oc))
+    y = np.empty((pix, oc), np.float32)
+    step = max(1, _PAIRWISE_BYTES // (4 * kk * pix))
+    for o in range(0, oc, step):
+        p = xs[:, :, None] * ws[:, None, o:o + step]
+        assert p.dtype == np.float32
+        while p.shape[0] > 1:
+            q = p[0:p.shape[0] - 1:2] + p[1::2]
+            p = np.concatenate([q, p[-1:]]) if p.shape[0] & 1 else q  # (the odd one out + 0.0f)
+        y[:, o:o + step] = p[0]
+    if bias is not None:
+        y += np.asarray(bias, np.float32)
+    return y.reshape(x.shape[0], oh, ow, oc)
+
+
+def batchnorm32(v, bn):
+    """batchnorm in fp32 NumPy, in the oracle's order of operations."""
+    f = lambda a: np.asarray(a, np.float32)
+    s = np.maximum(np.sqrt(f(bn["var"]) + np.float32(0.001)), np.float32(0.0001))
+    y = (f(bn["gamma"]) / s) * (f(v) - f(bn["mean"])) + f(bn["beta"])
+    assert y.dtype == np.float32
+    return y
+
+
+def activation32(name, v, alpha=0.0):
+    """activation in fp32 NumPy."""
+    v = np.asarray(v, np.float32)
+    one = np.float32(1.0)
+    if name in ("", "linear", "none", None):
+        return v
+    if name == "relu":
+        return np.maximum(v, np.float32(0.0))
+    if name == "relu6":
+        return np.clip(v, np.float32(0.0), np.float32(6.0))
+    if name == "leakyRelu":
+        return np.maximum(v, v * np.float32(alpha))
+    if name == "sigmoid":
+        return one / (one + np.exp(-v))
+    if name == "tanh":
+        return np.tanh(v)
+    if name == "SiLU":
+        return v / (one + np.exp(-v))
+    raise ValueError("ref64: unknown activation %r" % (name,))
+
+
+def conv_layer_general(x, w_oihw, bias, stride, pads, pad_mode, out_hw, bn=None, act="", alpha=0.0):
+    """convolution -> batchnorm -> activation in float64."""
+    v = conv2d_general(x, w_oihw, bias, stride, pads, pad_mode, out_hw)
+    if bn is not None:
+        v = batchnorm(v, bn)
+    return activation(act, v, alpha)
+
+
+def conv_layer_pairwise32(x, w_oihw, bias, stride, pads, pad_mode, out_hw, bn=None, act="", alpha=0.0):
+    """The same layer with conv2d_pairwise32 and the fp32 epilogue."""
+    v = conv2d_pairwise32(x, w_oihw, bias, stride, pads, pad_mode, out_hw)
+    if bn is not None:
+        v = batchnorm32(v, bn)
+    y = activation32(act, v, alpha)
+    assert y.dtype == np.float32
+    return y
 
 
 def depth_to_space_tanh(x, r):
@@ -139,3 +300,45 @@ def budget(got, ref64, oracle32, M, r=1, tiles=None, what=""):
         raise AssertionError("%sout of the float64 budget: max error %.3e = %.2f x E32max (%.3e), mean error %.3e = %.2f x E32mean (%.3e), allowed %g x; %s"
                              % (what and what + ": ", emax, rmax, e32max, emean, rmean, e32mean, M, _where(int(np.argmax(err)), got.shape, r, tiles)))
     return rmax, rmean
+
+
+def _where_conv(idx, shape, tile):
+    """The worst output element in words: (n, y, x, channel) and, given the kernel's pixel tile (TH, TW), the tile and the place inside it."""
+    n, y, x, c = (int(v) for v in np.unravel_index(idx, shape))
+    txt = "worst (n, y, x, channel) = (%d, %d, %d, %d)" % (n, y, x, c)
+    if tile:
+        th, tw = tile
+        iy, ix = y % th, x % tw
+        seam = [s for s, hit in (("left", ix == 0), ("right", ix == tw - 1), ("top", iy == 0), ("bottom", iy == th - 1)) if hit]
+        txt += "; tile %dx%d (TH x TW): tile (ty, tx) = (%d, %d), at (%d, %d) inside it, %s" % (
+            th, tw, y // th, x // tw, iy, ix, ("on the " + "/".join(seam) + " seam") if seam else "not on a seam")
+    return txt
+
+
+def budget_pairwise(got, ref64, pair32, M, what="", tile=None):
+    """Holds `got` [N,H,W,C] to M times the distance of the pairwise fp32 evaluation from the float64 reference on this very input, E32p = |pair32 - ref64|:
+        max |got - ref64| <= M * E32p_max,     mean |got - ref64| <= M * E32p_mean     and
+        max over channels |mean over (n, y, x) of (got - ref64)| <= M * E32p_mean       (a systematic offset of one channel: a bias, a folded BN shift).
+    Returns (max ratio, mean ratio, per-channel ratio).  tile = (TH, TW) in output pixels only serves the failure message."""
+    ref64 = _f64(ref64)
+    got = np.asarray(got)
+    assert got.ndim == 4 and got.shape == ref64.shape == np.asarray(pair32).shape, (got.shape, ref64.shape, np.asarray(pair32).shape)
+    e32 = np.abs(_f64(pair32) - ref64)
+    e32max, e32mean = float(e32.max()), float(e32.mean())
+    bad = ~np.isfinite(got)
+    if bad.any():
+        raise AssertionError("%s%d of %d values are not finite (never written, or NaN / Inf computed): first at %s"
+                             % (what and what + ": ", int(bad.sum()), bad.size, _where_conv(int(np.argmax(bad)), got.shape, tile)))
+    diff = _f64(got) - ref64
+    err = np.abs(diff)
+    chan = np.abs(diff.mean(axis=(0, 1, 2)))
+    emax, emean, echan = float(err.max()), float(err.mean()), float(chan.max())
+    ratio = lambda e, unit: e / unit if unit > 0 else (0.0 if e == 0 else np.inf)
+    rmax, rmean, rchan = ratio(emax, e32max), ratio(emean, e32mean), ratio(echan, e32mean)
+    failed = [name for name, ok in (("max", emax <= M * e32max), ("mean", emean <= M * e32mean), ("per-channel mean", echan <= M * e32mean)) if not ok]
+    if failed:
+        raise AssertionError("%sout of the float64 budget (%s): max error %.3e = %.2f x E32p max (%.3e), mean error %.3e = %.2f x E32p mean (%.3e), "
+                             "per-channel mean signed error %.3e = %.2f x E32p mean (channel %d), allowed %g x; %s"
+                             % (what and what + ": ", ", ".join(failed), emax, rmax, e32max, emean, rmean, e32mean, echan, rchan, int(np.argmax(chan)), M,
+                                _where_conv(int(np.argmax(err)), got.shape, tile)))
+    return rmax, rmean, rchan
