@@ -2,7 +2,7 @@
 // v_mfma_f32_32x32x16_f16 (half tensors, see conv1x1_stream_f16_kernel), for the layers whose time is
 // their activation / output stream rather than their arithmetic: MobileNetV2's expand (16->96 ... 96->576) and project (96->24 ... 192->32)
 // convolutions at 112x112 .. 28x28 (BASELINE configs[3]).  Replaces shadertemplate_vk_conv2d_1x1.comp:68-210 of the reference for those
-// shapes; bias -> BN -> activation epilogue and the fused residual Add are those of conv2d_mfma_kernel (same helpers, same rounding points).
+// shapes; bias -> BN -> activation epilogue and the fused residual Add are those of conv2d_mfma_kernel (same helpers, one rounding on store).
 //
 // Why a second kernel: for a 1x1 stride-1 layer the NHWC tensor IS the row-major GEMM operand (M = N*H*W pixels, K = IC contiguous), so the
 // halo-tile machinery of conv2d_mfma_kernel (LDS staging, a barrier per chunk, a prologue / epilogue per 128-pixel block) is pure overhead:
@@ -402,8 +402,8 @@ __global__ __launch_bounds__(64 * (3 * TS + 1), (3 * TS + 4) / 4) void conv1x1_m
 // fp16 tensors (half storage, fp32 accumulation on v_mfma_f32_32x32x16_f16): a chunk is 16 channels, lane (row, h) loads the 16 bytes
 // x[row][16c + 8h .. +7] and ONE MFMA consumes them.  A lane's results are single halfs of 16 different pixels; written directly they would
 // leave as 2-byte stores in 64-byte runs, so every wave transposes its 32 x BN tile through its own LDS region (no block barrier: the wave
-// only reads what it wrote itself) and stores 16-byte vectors, a pixel's BN channels contiguous.  The fused Add is applied there, on the
-// rounded convolution result, with conv2d_mfma's rounding points.  Needs OC % 8 == 0.
+// only reads what it wrote itself) and stores 16-byte vectors, a pixel's BN channels contiguous.  The fused Add's residual takes the same way
+// in the other direction and is added to the fp32 value, as in conv2d_mfma: one rounding, on store.  Needs OC % 8 == 0.
 template <int NT, bool SIMPLE>
 __global__ __launch_bounds__(256) void conv1x1_stream_f16_kernel(StreamParams p, ActCfg ac, const float* __restrict__ xv, const float4* __restrict__ wp,
                                                               const float4* __restrict__ epi, float* __restrict__ yv) {
@@ -474,8 +474,25 @@ __global__ __launch_bounds__(256) void conv1x1_stream_f16_kernel(StreamParams p,
             }
         }
     }
-    // epilogue: bias -> BN -> activation, rounded to half into the wave's own LDS tile [row][BN]
+    // epilogue: bias -> BN -> activation [-> fused Add], rounded to half into the wave's own LDS tile [row][BN]
     _Float16* const ot = reinterpret_cast<_Float16*>(s_w + p.nChunks * 2 * BN) + wave * 32 * EP;
+    constexpr int VPR = BN / 8; // 16-byte vectors per row
+    const bool addSimple = act_is_simple_dev(p.ac2.act);
+    const _Float16* res = reinterpret_cast<const _Float16*>(p.res);
+    if (res) { // the residual comes in through the tile, transposed the other way: 16-byte vectors land where the result will stand
+#pragma unroll
+        for (int j = 0; j < 32 * VPR / 64; ++j) {
+            const int vi = lane + 64 * j;
+            const int r = vi / VPR, c8 = vi - r * VPR;
+            const int row = tile * 32 + r, oc = n0 + c8 * 8;
+            float4 rpack = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (row < p.M && oc < p.OC) rpack = *reinterpret_cast<const float4*>(res + static_cast<size_t>(row) * p.OC + oc);
+            *reinterpret_cast<float4*>(ot + r * EP + c8 * 8) = rpack;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -485,34 +502,20 @@ __global__ __launch_bounds__(256) void conv1x1_stream_f16_kernel(StreamParams p,
             for (int u = 0; u < NT; ++u) {
                 float v = epi_affine(acc[u][4 * g + k], e[u], p.useBN);
                 v = SIMPLE ? apply_act<true>(ac, v, 0.0f) : epi_act(ac.act, ac.leaky, v, 0.0f);
-                ot[r * EP + u * 32 + l32] = static_cast<_Float16>(v);
+                _Float16* const slot = ot + r * EP + u * 32 + l32;
+                if (res) v = add_act(p.ac2, addSimple, v + static_cast<float>(*slot)); // on the fp32 value: the store below is the one rounding
+                *slot = static_cast<_Float16>(v);
             }
         }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    constexpr int VPR = BN / 8; // 16-byte vectors per row
-    const bool addSimple = act_is_simple_dev(p.ac2.act);
-    const _Float16* res = reinterpret_cast<const _Float16*>(p.res);
 #pragma unroll
     for (int j = 0; j < 32 * VPR / 64; ++j) {
         const int vi = lane + 64 * j;
         const int r = vi / VPR, c8 = vi - r * VPR;
         const int row = tile * 32 + r, oc = n0 + c8 * 8;
-        if (row < p.M && oc < p.OC) {
-            const size_t o = static_cast<size_t>(row) * p.OC + oc;
-            float4 pack = *reinterpret_cast<const float4*>(ot + r * EP + c8 * 8);
-            if (res) {
-                const float4 rpack = *reinterpret_cast<const float4*>(res + o);
-                const _Float16* ch = reinterpret_cast<const _Float16*>(&pack);
-                const _Float16* rh = reinterpret_cast<const _Float16*>(&rpack);
-                _Float16 oh[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) oh[q] = static_cast<_Float16>(add_act(p.ac2, addSimple, static_cast<float>(ch[q]) + static_cast<float>(rh[q])));
-                pack = *reinterpret_cast<const float4*>(oh);
-            }
-            *reinterpret_cast<float4*>(y + o) = pack;
-        }
+        if (row < p.M && oc < p.OC) *reinterpret_cast<float4*>(y + static_cast<size_t>(row) * p.OC + oc) = *reinterpret_cast<const float4*>(ot + r * EP + c8 * 8);
     }
 }
 

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(size_t MN, int OC, i
         for (int z = 0; z < splitK; ++z) v += ws[static_cast<size_t>(z) * MN + i];
         v = epi_affine(v, epi[i % OC], useBN);
         v = SIMPLE ? apply_act<true>(ac, v, 0.0f) : epi_act(ac.act, ac.leaky, v, 0.0f);
-        if (res) v = add_act(ac2, addSimple, static_cast<float>(static_cast<T>(v)) + static_cast<float>(res[i])); // fused residual Add
+        if (res) v = add_act(ac2, addSimple, v + static_cast<float>(res[i])); // fused residual Add: on the fp32 value, one rounding on store
         y[i] = static_cast<T>(v);
     }
 }
@@ -277,11 +277,16 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     // waves per SIMD; at 48 KB the graph is 1.7 % faster, at 24 KB U-Net loses 4 %.  fp16 layers were 1-2 % slower with the lower bound.)
     size_t narrowAbove = (f16 ? 80 : 48) * 1024;
     if (const char* e = snnhip::option("SNNHIP_CONV_NARROW_KB")) narrowAbove = static_cast<size_t>(atoi(e)) * 1024; // experiments
-    if (C8 == 2 && (best < 0 || bestLds > narrowAbove) && !snnhip::option("SNNHIP_CONV_WIDE_CHUNKS")) {
-        C8 = 1;
-        Qs = 2;
-        ICc = 2 * CH;
-        choose();
+    bool wideKept = false; // SNNHIP_CONV_WIDE_CHUNKS=1 kept full-width chunks where the default stages half-width ones
+    if (C8 == 2 && (best < 0 || bestLds > narrowAbove)) {
+        if (!snnhip::option("SNNHIP_CONV_WIDE_CHUNKS")) {
+            C8 = 1;
+            Qs = 2;
+            ICc = 2 * CH;
+            choose();
+        } else {
+            wideKept = true;
+        }
     }
     if (best < 0) return SNNHIP_E_UNSUPPORTED;
     MfmaParams p{};
@@ -364,6 +369,9 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     }
     // fp16 output tile through LDS (see the kernel's epilogue): needs whole 8-channel vectors and the direct (non split-K) epilogue
     p.ldsEpi = (f16 && p.splitK == 1 && g.OC % 8 == 0 && !snnhip::option("SNNHIP_CONV_DIRECT_STORE")) ? 1 : 0;
+    // fp16 with the chunks kept wide by the switch: the K steps of a chunk run half by half (the run-time tap loop has that order), so that the switch
+    // changes how the operands are staged and never what is computed
+    p.c8Outer = (f16 && wideKept) ? 1 : 0;
     size_t ldsNeed = p.chunksPerSplit == 1 ? L.ldsBytes / 2 : L.ldsBytes; // one chunk per block: no second staging buffer
     p.normShift = g.normShift; p.normMul = g.normMul;
     p.normAc = make_act_cfg(preNorm ? g.normAct : SNNHIP_ACT_NONE, g.normLeaky);
@@ -374,9 +382,10 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     if (p.ldsEpi) ldsNeed = std::max(ldsNeed, static_cast<size_t>(128) * (BN + 8) * 2);
     const bool simple = act_is_simple(g.act);
     KernelFn fn = nullptr;
-    if (BN == 128) fn = f16 ? pick_conv2d_mfma_bn128_f16(C8, R, simple, taps) : pick_conv2d_mfma_bn128_f32(C8, R, simple, taps);
-    if (BN == 64) fn = f16 ? pick_conv2d_mfma_bn64_f16(C8, R, simple, taps) : pick_conv2d_mfma_bn64_f32(C8, R, simple, taps);
-    if (BN == 32) fn = f16 ? pick_conv2d_mfma_bn32_f16(C8, R, simple, taps) : pick_conv2d_mfma_bn32_f32(C8, R, simple, taps);
+    const int staticTaps = p.c8Outer ? 0 : taps; // (the half-by-half order lives in the run-time tap loop)
+    if (BN == 128) fn = f16 ? pick_conv2d_mfma_bn128_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn128_f32(C8, R, simple, taps);
+    if (BN == 64) fn = f16 ? pick_conv2d_mfma_bn64_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn64_f32(C8, R, simple, taps);
+    if (BN == 32) fn = f16 ? pick_conv2d_mfma_bn32_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn32_f32(C8, R, simple, taps);
     if (!fn) return SNNHIP_E_UNSUPPORTED;
 
     auto* plan = new MfmaConvPlan();
@@ -411,7 +420,7 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         }
     }
 
-    // weights: Wp[chunk][tap][c8][h][OCp][j], ic = chunk*ICc + (c8*2 + h)*CH + j, j < CH (+ 10 zero steps: the prefetch ring reads up to 9
+    // weights: Wp[chunk][tap][c8][h][OCp][j] (c8Outer: Wp[chunk][c8][tap]...), ic = chunk*ICc + (c8*2 + h)*CH + j, j < CH (+ 10 zero steps: the prefetch ring reads up to 9
     // steps ahead); 16 bytes per (h, oc): 4 floats or 8 halfs (fp32 -> fp16 rounds to nearest; weights that went through the reference's
     // truncating convertToMediumPrecision are representable and convert exactly)
     const size_t steps = C8 ? static_cast<size_t>(p.nChunks) * taps * C8 : static_cast<size_t>((taps + 1) / 2);
@@ -435,7 +444,8 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
                     for (int j = 0; j < CH; ++j) {
                         const int ic = chunk * ICc + (c8 * 2 + hh) * CH + j;
                         if (ic >= g.IC) continue;
-                        const size_t base = (((static_cast<size_t>(chunk) * taps + t) * C8 + c8) * 2 + hh) * p.OCp;
+                        const size_t step = p.c8Outer ? (static_cast<size_t>(chunk) * C8 + c8) * taps + t : (static_cast<size_t>(chunk) * taps + t) * C8 + c8;
+                        const size_t base = (step * 2 + hh) * p.OCp;
                         for (int o = 0; o < g.OC; ++o) {
                             const float wv = w_oihw[(static_cast<size_t>(o) * g.IC + ic) * taps + t];
                             if (f16) wph[(base + o) * 8 + j] = static_cast<_Float16>(wv);

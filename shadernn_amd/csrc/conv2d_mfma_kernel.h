@@ -35,6 +35,8 @@ struct MfmaParams { // (declared after ActCfg: epilogue.h)
     int splitK;          // > 1: blockIdx.z owns chunks [z*chunksPerSplit, ...) and stores raw partial sums to the workspace
     int chunksPerSplit;
     int ldsEpi;          // fp16, OC % 8 == 0, no split-K: the output tile leaves through LDS as 16-byte channel-contiguous stores
+    int c8Outer;         // fp16, SNNHIP_CONV_WIDE_CHUNKS=1 where the default would stage half-width chunks: 32-channel chunks in LDS, but the K steps run
+                         // (16-channel half, tap) like the default's (chunk, tap) -- the same MFMAs in the same order, bit-identical results
     int preMode, preX, preY, srcH, srcW; // fused Pad layer (ConvGeom): H, W are the padded dims, the tensor is srcH x srcW (== H, W when preMode == 0)
     int preShift;                        // fused nearest x2 upsampling in front of the pad: resolve against (srcH, srcW) << 1, then >> 1
     unsigned magicW, magicH; // ceil(2^32 / tileW), ceil(2^32 / tileH): the prologue's divisions by run-time values become one v_mul_hi each
@@ -352,6 +354,49 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
             __syncthreads();
             continue;
         }
+        if constexpr (F16 && C8 == 2 && TAPS == 0) {
+            if (p.c8Outer) { // the halves of the chunk one after the other, every tap of a half: the order of two half-width chunks
+#pragma unroll 1
+                for (int c8 = 0; c8 < C8; ++c8) {
+                    int fx = 0, rowoff = 0;
+#pragma unroll 1
+                    for (int tap = 0; tap < taps; ++tap) {
+                        int fxn = fx + 1, rown = rowoff;
+                        if (fxn == p.kw) {
+                            fxn = 0;
+                            rown += p.rowPitch;
+                        }
+                        const bool last = tap + 1 == taps; // then the next step is tap 0 of the other half (after the last half: never consumed)
+                        if (last) {
+                            fxn = 0;
+                            rown = 0;
+                        }
+                        const int dnext = rown + (p.evenCols ? (fxn & 1) * p.evenCols + (fxn >> 1) : fxn);
+                        const int slot = (last ? (c8 + 1 < C8 ? c8 + 1 : 0) : c8) * 2 + h;
+                        float4 a[MT], b[NT];
+#pragma unroll
+                        for (int t = 0; t < MT; ++t) a[t] = an[t];
+#pragma unroll
+                        for (int u = 0; u < NT; ++u) b[u] = bq[0][u];
+#pragma unroll
+                        for (int d = 0; d + 1 < D; ++d)
+#pragma unroll
+                            for (int u = 0; u < NT; ++u) bq[d][u] = bq[d + 1][u];
+#pragma unroll
+                        for (int u = 0; u < NT; ++u) bq[D - 1][u] = bptr[u * 32];
+                        bptr += bstep;
+#pragma unroll
+                        for (int t = 0; t < MT; ++t) an[t] = *reinterpret_cast<const float4*>(cur + lds_off<C8>(apix[t] + dnext, slot));
+                        k_step(a, b);
+                        fx = fxn;
+                        rowoff = rown;
+                    }
+                }
+                if (more) stage_store(smem + ((chunk + 1 - chunk0) & 1) * p.bufFloats, (chunk + 1) * 2 * CH * C8);
+                __syncthreads();
+                continue;
+            }
+        }
         int fx = 0, rowoff = 0;
 #pragma unroll 1
         for (int tap = 0; tap < taps; ++tap) {
@@ -401,9 +446,29 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
     // fp16 (p.ldsEpi): a lane's accumulators are single halfs of 16 different pixels -- stored directly they leave as 2-byte scatters in
     // 64-byte runs (measured: 19 of 69 us of a 3x3 256->128 layer).  The tile is transposed through LDS instead ([pixel][BN halfs], row
     // pitch BN*2+16 bytes so that the two half-waves hit disjoint banks) and written as 16-byte vectors, a pixel's BN channels contiguous.
+    // Fused Add (chain rule E): the residual is added to the fp32 value, in front of the one rounding of the store.  On the LDS path it comes in through
+    // the output tile, transposed the other way: 16-byte vectors of the residual, a pixel's channels contiguous, land where the result will stand, and
+    // every lane replaces the halfs of its own accumulator slots by act2(value + residual).
     constexpr int EPITCH = BN + 8; // halfs per LDS row of the output tile
     const bool addSimple = act_is_simple_dev(p.ac2.act);
     _Float16* const otile = reinterpret_cast<_Float16*>(smem);
+    const bool resTile = F16 && p.ldsEpi && p.res;
+    if (resTile) { // (the K loop ended on a barrier: the staging buffers under the tile are dead)
+        constexpr int VPR = BN / 8;
+#pragma unroll
+        for (int j = 0; j < 128 * VPR / 256; ++j) {
+            const int v = tid + 256 * j;
+            const int i = v / VPR, c8 = v - i * VPR;
+            const int b = i >> (p.THs + p.TWs), py = (i >> p.TWs) & THm, px = i & TWm;
+            const int n = b0 + b, oy = oy0 + py, ox = ox0 + px;
+            const int oc = blockIdx.y * BN + c8 * 8;
+            float4 rpack = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (n < p.N && oy < p.OH && ox < p.OW && oc < p.OC)
+                rpack = *reinterpret_cast<const float4*>(static_cast<const T*>(p.res) + static_cast<size_t>((n * p.OH + oy) * p.OW + ox) * p.OC + oc);
+            *reinterpret_cast<float4*>(otile + i * EPITCH + c8 * 8) = rpack;
+        }
+        __syncthreads();
+    }
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
         const int ibase = (wm * MT + t) * 32 + 4 * h;
@@ -460,12 +525,11 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
                         if (k == 0) first = v;
                     }
                     if (F16 && p.ldsEpi) {
-                        otile[(i + k) * EPITCH + wn * (NT * 32) + u * 32 + l32] = static_cast<_Float16>(v);
+                        _Float16* const slot = otile + (i + k) * EPITCH + wn * (NT * 32) + u * 32 + l32;
+                        if (resTile) v = add_act(p.ac2, addSimple, v + static_cast<float>(*slot));
+                        *slot = static_cast<_Float16>(v);
                     } else if (ok && ox + k < p.OW && (!(SNNHIP_ABL & 8) || v == 12345.678f)) { // ablation bit 8: no output stores
-                        if (resDirect) { // the Add layer behind this convolution: same rounding points as the two separate launches
-                            const float cv = static_cast<float>(static_cast<T>(v));
-                            v = add_act(p.ac2, addSimple, cv + rv[g][u][k]);
-                        }
+                        if (resDirect) v = add_act(p.ac2, addSimple, v + rv[g][u][k]); // the Add layer behind this convolution
                         y[pofs + k * p.OC + oc] = static_cast<T>(v);
                     }
                 }
@@ -498,15 +562,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
                         sa[e] += f;
                         sb[e] = fmaf(f, f, sb[e]);
                     }
-                }
-                if (p.res) {
-                    const float4 rpack = *reinterpret_cast<const float4*>(static_cast<const T*>(p.res) + o);
-                    const _Float16* ch = reinterpret_cast<const _Float16*>(&pack);
-                    const _Float16* rh = reinterpret_cast<const _Float16*>(&rpack);
-                    _Float16 oh[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) oh[e] = static_cast<_Float16>(add_act(p.ac2, addSimple, static_cast<float>(ch[e]) + static_cast<float>(rh[e])));
-                    pack = *reinterpret_cast<const float4*>(oh);
                 }
                 *reinterpret_cast<float4*>(y + o) = pack;
             }

@@ -280,9 +280,9 @@ __global__ __launch_bounds__(256, 2) void conv2d_wide_kernel(WideParams p, ActCf
     // (row wm*MT + t, column l32).  bias -> BN -> activation, each run goes to the LDS tile [pixel][BN halfs] as ONE ds_write_b64 (with the
     // pixels in the accumulator rows it took 128 ds_write_b16 per wave and the epilogue ran as long as the block's MFMAs); the tile then leaves
     // as 16-byte vectors, a pixel's BN channels contiguous (whole 128-byte lines -- storing the 8-byte runs directly was measured 10 % slower
-    // than this round trip: 32 partial lines per store instruction).  Fused residual Add on the way out, same rounding points as the separate
-    // launches; its loads are all issued before the first store (gfx9 counts loads and stores in one vmcnt and retires them out of order with
-    // respect to each other: a load behind a store can only be waited for with vmcnt(0), the full write round trip).
+    // than this round trip: 32 partial lines per store instruction).  The fused residual Add (RES) is added to the fp32 values, in front of
+    // the one rounding; its loads are all issued before the first store (gfx9 counts loads and stores in one vmcnt and retires them out of order
+    // with respect to each other: a load behind a store can only be waited for with vmcnt(0), the full write round trip).
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     constexpr int EPITCH = BN + 8; // halfs per pixel row of the LDS tile: 8-byte runs of 16 consecutive pixels land in distinct banks
     _Float16* const otile = reinterpret_cast<_Float16*>(smem);
@@ -301,6 +301,27 @@ __global__ __launch_bounds__(256, 2) void conv2d_wide_kernel(WideParams p, ActCf
     // the general form below (run-time batch-norm select, mul / max / med3 activation) is seven, and with 128 values per lane the epilogue's
     // VALU work was a third of the wave's MFMA time
     const bool fastEpi = SIMPLE && !p.useBN && ac.alpha == 1.0f && ac.hi == __builtin_huge_valf();
+    constexpr int VPR = BN / 8;             // 16-byte vectors per pixel of the tile
+    constexpr int NV = PIX * VPR / 256;     // ... per thread
+    int oofs[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int v = tid + 256 * j;
+        const int i = v / VPR, c8 = v - i * VPR;
+        const int oy = oy0 + (i >> 5), ox = ox0 + (i & 31);
+        oofs[j] = (oy < p.OH && ox < p.OW) ? ((n * p.OH + oy) * p.OW + ox) * p.OC + blockIdx.y * BN + c8 * 8 : -1;
+    }
+    if (RES) { // the residual comes in through the tile, transposed the other way: its 16-byte vectors land where the result will stand (the K loop ended
+               // on a barrier: the staging buffers under the tile are dead), and every lane below adds the run it is about to overwrite to its fp32 values
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int v = tid + 256 * j;
+            const int i = v / VPR, c8 = v - i * VPR;
+            *reinterpret_cast<float4*>(otile + i * EPITCH + c8 * 8) =
+                oofs[j] >= 0 ? *reinterpret_cast<const float4*>(static_cast<const _Float16*>(p.res) + oofs[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        __syncthreads();
+    }
     if (fastEpi) {
 #pragma unroll
         for (int u = 0; u < NT; ++u)
@@ -309,10 +330,16 @@ __global__ __launch_bounds__(256, 2) void conv2d_wide_kernel(WideParams p, ActCf
                 const float bk[4] = {bias4[u][g].x, bias4[u][g].y, bias4[u][g].z, bias4[u][g].w};
 #pragma unroll
                 for (int t = 0; t < MT; ++t) {
-                    h4 o;
+                    h4* const slot = reinterpret_cast<h4*>(otile + ((wm * MT + t) * 32 + l32) * EPITCH + wn * (NT * 32) + u * 32 + 8 * g + 4 * h);
+                    h4 o, r;
+                    if (RES) r = *slot;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) o[k] = static_cast<_Float16>(fmaxf(acc[t][u][4 * g + k] + bk[k], ac.lo));
-                    *reinterpret_cast<h4*>(otile + ((wm * MT + t) * 32 + l32) * EPITCH + wn * (NT * 32) + u * 32 + 8 * g + 4 * h) = o;
+                    for (int k = 0; k < 4; ++k) {
+                        float v = fmaxf(acc[t][u][4 * g + k] + bk[k], ac.lo);
+                        if (RES) v = add_act(p.ac2, true, v + static_cast<float>(r[k]));
+                        o[k] = static_cast<_Float16>(v);
+                    }
+                    *slot = o;
                 }
             }
     } else
@@ -329,32 +356,20 @@ __global__ __launch_bounds__(256, 2) void conv2d_wide_kernel(WideParams p, ActCf
             }
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
-                h4 o;
+                h4* const slot = reinterpret_cast<h4*>(otile + ((wm * MT + t) * 32 + l32) * EPITCH + wn * (NT * 32) + u * 32 + 8 * g + 4 * h);
+                h4 o, r;
+                if (RES) r = *slot;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float v = epi_affine(acc[t][u][4 * g + k], e[k], p.useBN);
                     v = SIMPLE ? apply_act<true>(ac, v, 0.0f) : epi_act(ac.act, ac.leaky, v, 0.0f);
+                    if (RES) v = add_act(p.ac2, true, v + static_cast<float>(r[k])); // on the fp32 value: the store is the one rounding
                     o[k] = static_cast<_Float16>(v);
                 }
-                *reinterpret_cast<h4*>(otile + ((wm * MT + t) * 32 + l32) * EPITCH + wn * (NT * 32) + u * 32 + 8 * g + 4 * h) = o;
+                *slot = o;
             }
         }
-    constexpr int VPR = BN / 8;             // 16-byte vectors per pixel of the tile
-    constexpr int NV = PIX * VPR / 256;     // ... per thread
-    int oofs[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int v = tid + 256 * j;
-        const int i = v / VPR, c8 = v - i * VPR;
-        const int oy = oy0 + (i >> 5), ox = ox0 + (i & 31);
-        oofs[j] = (oy < p.OH && ox < p.OW) ? ((n * p.OH + oy) * p.OW + ox) * p.OC + blockIdx.y * BN + c8 * 8 : -1;
-    }
     WIDE_MARK(4);
-    float4 rpack[RES ? NV : 1];
-    if (RES) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) rpack[j] = oofs[j] >= 0 ? *reinterpret_cast<const float4*>(static_cast<const _Float16*>(p.res) + oofs[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
     __syncthreads();
     // chain rule F (p.statPart, uniform): the InstanceNorm behind this layer needs mean and variance per (image, channel).  A thread's NV vectors are
     // NV pixels of ONE 8-channel column (256 % VPR == 0): sums of (v - pivot) and (v - pivot)^2 of the stored (rounded) values accumulate in
@@ -382,14 +397,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_wide_kernel(WideParams p, ActCf
                 sB[e] = fmaf(f, f, sB[e]);
             }
             ++sCnt;
-        }
-        if (RES) {
-            const _Float16* ch = reinterpret_cast<const _Float16*>(&pack);
-            const _Float16* rh = reinterpret_cast<const _Float16*>(&rpack[RES ? j : 0]);
-            _Float16 oh[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oh[e] = static_cast<_Float16>(add_act(p.ac2, true, static_cast<float>(ch[e]) + static_cast<float>(rh[e])));
-            pack = *reinterpret_cast<const float4*>(oh);
         }
         if (oofs[j] >= 0 && !((SNNHIP_WIDE_ABL & 8) && p.OC != 12345)) *reinterpret_cast<float4*>(y + oofs[j]) = pack;
     }

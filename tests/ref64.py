@@ -10,7 +10,11 @@ The general fp32 convolution kernels (deep reductions: K = IC k^2 up to 4608, sp
 output extent (conv2d_general) and a sharper unit: the oracle sums its K terms one after the other, so its own error grows with K (21 x a pairwise sum's at
 K = 4608) and a budget in units of it lets 16-bit weights through.  conv2d_pairwise32 forms every product in fp32 and reduces K by a tree of fp32 additions;
 its distance from float64 (E32p) is what an fp32 kernel with a blocked or tree-shaped reduction can reach, and budget_pairwise holds a kernel to M_CONV times it,
-with a third bound on the mean signed error per output channel (a bias off by 2e-6 hides in max and mean at these depths)."""
+with a third bound on the mean signed error per output channel (a bias off by 2e-6 hides in max and mean at these depths).
+
+The fp16 convolution kernels (half storage, products of half operands accumulated in fp32, an fp32 epilogue, one round-to-nearest-even store) are held to
+the correctly rounded half of the exact result: budget_half allows M_F16 times E32p max beyond half a binary16 ulp (ulp16), where a tolerance of a few
+half ulps lets a truncating store or partial sums kept in half through."""
 import numpy as np
 
 # The margin of every budget test: twice the largest ratio any fp32 kernel family showed against float64 on an MI355X (2.02, DESIGN.md section 3
@@ -28,6 +32,14 @@ M_CONV = 16
 # of 32, at which the 16-bit-weight mutant (52 x max, 64 x mean at its smallest), the missing block and the unwritten row are rejected and the bias mutant
 # (27 x to 31 x per channel) is not.
 M_CONV_UNSPLIT = 32
+
+# The margin of the fp16 convolution budget tests (budget_half), one value for all f16 convolution families: how far beyond half a binary16 ulp of the exact
+# value a result may lie, in units of E32p max.  Measured on an MI355X (DESIGN.md section 3 has the table): at most 1.56 (conv2d_widep_f16, a row of ten
+# tiles), 1.22 on conv2d_wide_f16, 1.11 on conv2d_mfma with one chain of K = 4608, below 1 elsewhere.  The rule of M (twice the largest, rounded up to a power
+# of two) gives 4.  An fp32 sum taken one term after the other is just as honest as the kernels' blocked sums, though, and tests/test_ref64.py holds the budget
+# to accepting it: the C oracle and torch's fp32 convolution, rounded to half, reach 5.8 at K = 2304.  The constant is the smallest power of two that accepts
+# every honest evaluation; the smallest mutant of tests/test_ref64.py (a bias rounded to half) stands at 116, so every power of two up to 64 rejects them all.
+M_F16 = 8
 
 _BN_EPS = float(np.float32(0.001))    # oracle/snn_oracle.c:bn_apply: sqrtf(var + 0.001f) ...
 _BN_FLOOR = float(np.float32(0.0001))  # ... floored at 0.0001f
@@ -342,3 +354,50 @@ def budget_pairwise(got, ref64, pair32, M, what="", tile=None):
                              % (what and what + ": ", ", ".join(failed), emax, rmax, e32max, emean, rmean, e32mean, echan, rchan, int(np.argmax(chan)), M,
                                 _where_conv(int(np.argmax(err)), got.shape, tile)))
     return rmax, rmean, rchan
+
+
+def half(v):
+    """v rounded to binary16 (nearest, ties to even) and back, as float64."""
+    with np.errstate(over="ignore"):
+        return _f64(v).astype(np.float16).astype(np.float64)
+
+
+def ulp16(v):
+    """The spacing of binary16 at a float64 value: 2^(floor(log2 |v|) - 10) for |v| >= 2^-14, 2^-24 below (the subnormals and zero)."""
+    a = np.abs(_f64(v))
+    e = np.where(a > 0, np.frexp(a)[1] - 1, -14)  # |v| = m 2^(e + 1), m in [0.5, 1): e = floor(log2 |v|), exactly (frexp(0) = (0, 0))
+    return np.ldexp(1.0, np.maximum(e, -14) - 10)
+
+
+def budget_half(got, ref64, pair32, M, what="", tile=None):
+    """Holds `got` [N,H,W,C], read back from a half tensor, to the correctly rounded half of the exact result.  ref64 is the float64 layer on the
+    half-rounded inputs and weights (bias and BN parameters fp32), pair32 the pairwise fp32 evaluation of the same values, not rounded to half.
+        max over elements of max(|got - ref64| - 0.5 ulp16(ref64), 0) <= M * E32p_max,     E32p_max = max |pair32 - ref64|.
+    Two half operands multiply exactly in fp32, so a kernel that accumulates in fp32, runs its epilogue in fp32 and rounds once on store is within half
+    an ulp of the exact value everywhere, except where its fp32 error carried the value across a rounding tie: the right side is that error (about 1 % of
+    an ulp at unit scale).  Returns (the ratio of the left side to E32p_max, the share of elements that differ from ref64 rounded to half, the largest
+    per-channel mean signed error in ulps) for printing.  tile = (TH, TW) in output pixels only serves the failure message."""
+    ref64 = _f64(ref64)
+    got = np.asarray(got)
+    assert got.ndim == 4 and got.shape == ref64.shape == np.asarray(pair32).shape, (got.shape, ref64.shape, np.asarray(pair32).shape)
+    e32max = float(np.abs(_f64(pair32) - ref64).max())
+    bad = ~np.isfinite(got)
+    if bad.any():
+        raise AssertionError("%s%d of %d values are not finite (never written, or NaN / Inf computed): first at %s"
+                             % (what and what + ": ", int(bad.sum()), bad.size, _where_conv(int(np.argmax(bad)), got.shape, tile)))
+    ulp = ulp16(ref64)
+    diff = _f64(got) - ref64
+    over = np.maximum(np.abs(diff) - 0.5 * ulp, 0.0)
+    omax = float(over.max())
+    ratio = omax / e32max if e32max > 0 else (0.0 if omax == 0 else np.inf)
+    mismatch = float(np.mean(_f64(got) != half(ref64)))
+    chan = diff / ulp
+    chan = np.abs(chan.mean(axis=(0, 1, 2)))
+    if not omax <= M * e32max:
+        i = int(np.argmax(over))
+        raise AssertionError("%sout of the half budget: %.3e beyond half an ulp of the exact value = %.2f x E32p max (%.3e), allowed %g x; got %.9g, exact %.9g "
+                             "(ulp %.3e, off by %.3f ulp), %.2f %% of the elements differ from the rounded exact value, per-channel mean signed error %.4f ulp "
+                             "(channel %d); %s"
+                             % (what and what + ": ", omax, ratio, e32max, M, got.flat[i], ref64.flat[i], ulp.flat[i], diff.flat[i] / ulp.flat[i], 100 * mismatch,
+                                float(chan.max()), int(np.argmax(chan)), _where_conv(i, got.shape, tile)))
+    return ratio, mismatch, float(chan.max())

@@ -97,8 +97,16 @@ def test_wide_with_fused_pad_upsample_and_add(ctx, monkeypatch, oc, with_up):
     a, r = _rand((n, hh, ww, oc), 6), _rand((n, hh, ww, oc), 7)
     at, rt = snn.Tensor.from_numpy(ctx, a, dtype=snn.F16), snn.Tensor.from_numpy(ctx, r, dtype=snn.F16)
     got = fused([at, rt]).numpy()
+    c = conv(at).numpy()
     two = add([conv(at), rt]).numpy()
-    np.testing.assert_array_equal(got, two)
+    # the fused launch adds the residual to the fp32 value v and rounds once, on store (tests/test_conv_f16_budget_gpu.py holds that to the float64
+    # reference); the two launches round the convolution's output (c, within half an ulp of v) and then the sum.  relu does not stretch a difference, so
+    # |fused - two| <= ulp(c) / 2 + ulp(two) / 2 + ulp(fused) / 2, and most elements agree
+    import ref64
+
+    bound = 0.5 * (ref64.ulp16(c) + ref64.ulp16(two) + ref64.ulp16(got)) + 2.0 ** -22 * (np.abs(c) + np.abs(two))  # (+ the fp32 roundings of the two sums)
+    assert (np.abs(got.astype(np.float64) - two) <= bound).all(), float((np.abs(got.astype(np.float64) - two) - bound).max())
+    assert np.mean(got != two) < 0.25, float(np.mean(got != two))
 
 
 def test_wide_is_the_default_on_large_maps_only(ctx):

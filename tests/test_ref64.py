@@ -1,5 +1,7 @@
 """tests/ref64.py on the CPU: the float64 reference against torch's float64 convolution, the fp32 C oracle inside its own budget, and the comparator
-against mutants of the oracle that rtol = atol = 1e-4 lets through (they must be rejected at the margin M the GPU tests use) and one it must accept."""
+against mutants of the oracle that rtol = atol = 1e-4 lets through (they must be rejected at the margin M the GPU tests use) and one it must accept;
+the half budget of the fp16 kernels (ulp16, budget_half) against honest fp32 evaluations rounded to half and against the wrong kernels that
+rtol = atol = 4e-3 lets through."""
 import copy
 import functools
 import os
@@ -396,3 +398,186 @@ def test_the_oracle_does_not_scale_in_the_pairwise_unit(shape):
     print("%s K=%d: the fp32 C oracle at %.1f x E32p max, %.1f x E32p mean, %.1f x per channel" % (shape, shape[3] * shape[5] ** 2, rmax, rmean, rchan))
     if shape == DEEP:
         assert rmax > 4
+
+
+# ---- the half budget (the fp16 convolution kernels: tests/test_conv_f16_budget_gpu.py) ----
+
+TOLH = dict(rtol=4e-3, atol=4e-3)  # the bound of every older test of the f16 kernels, against the quantised oracle
+
+
+def _h32(a):
+    """Round to half (nearest even) and back to float32: what a half tensor stores."""
+    return np.asarray(a, np.float32).astype(np.float16).astype(np.float32)
+
+
+def test_ulp16_is_the_spacing_of_binary16():
+    r = np.random.default_rng(16)
+    v = np.concatenate([
+        r.standard_normal(60000) * np.exp2(r.integers(-12, 14, 60000)),          # the normal range, both signs
+        r.uniform(-2.0 ** -14, 2.0 ** -14, 20000),                               # subnormals
+        np.exp2(r.integers(-16, 15, 20000)) * (1.0 + r.uniform(-2e-4, 2e-4, 20000)) * r.choice([-1.0, 1.0], 20000),  # either side of powers of two
+        np.exp2(np.arange(-26, 16.0)), -np.exp2(np.arange(-26, 16.0)), np.nextafter(np.exp2(np.arange(-26, 16.0)), 0), [0.0, 65504.0, -65504.0]])
+    assert v.dtype == np.float64 and v.size >= 100000
+    u = ref64.ulp16(v)
+    assert (np.abs(ref64.half(v) - v) <= 0.5 * u).all()
+    assert u[np.abs(v) < 2.0 ** -14].tolist() == [2.0 ** -24] * int((np.abs(v) < 2.0 ** -14).sum())
+    assert ref64.ulp16(1.0) == 2.0 ** -10 and ref64.ulp16(np.nextafter(1.0, 0)) == 2.0 ** -11 and ref64.ulp16(-0.75) == 2.0 ** -11
+    h = np.arange(0, 0x7BFF, dtype=np.uint16).view(np.float16)  # every non-negative half below the largest (whose np.spacing overflows)
+    np.testing.assert_array_equal(ref64.ulp16(h.astype(np.float64)), np.spacing(h).astype(np.float64))
+    np.testing.assert_array_equal(ref64.ulp16(-h.astype(np.float64)), np.spacing(h).astype(np.float64))  # (np.spacing of a negative power of two steps toward zero)
+    assert ref64.ulp16(65504.0) == 32.0
+
+
+# N, H, W, IC, OC, k, activation: two images of more than one 8 x 32 tile, ragged against it.  K = 576, 1152, 2304, 243
+HALF_LAYERS = [(2, 9, 33, 64, 64, 3, ""), (2, 9, 33, 128, 128, 3, "relu"), (2, 9, 33, 256, 64, 3, "tanh"), (2, 9, 33, 3, 32, 9, "")]
+HALF_IDS = ["64-64", "128-128_relu", "256-64_tanh", "3-32_9x9"]
+HALF_TILE = (8, 32)
+
+
+@functools.lru_cache(maxsize=None)
+def _half_case(layer):
+    """(x, w) rounded to half, the fp32 bias, the float64 reference, the pairwise fp32 evaluation and the quantised C oracle of one layer: read-only."""
+    n, h, w, ic, oc, k, act = layer
+    x, wt, b = _h32(_rand((n, h, w, ic), 31)), _h32(_rand((oc, ic, k, k), 32, 1.0 / np.sqrt(k * k * ic))), _rand((oc,), 33, 0.1)
+    pads, out_hw = _geometry(h, w, k, 1, "same")
+    out = (x, wt, b, ref64.conv_layer_general(x, wt, b, 1, pads, "constant", out_hw, None, act), ref64.conv_layer_pairwise32(x, wt, b, 1, pads, "constant", out_hw, None, act),
+           O.conv2d(x, wt, b, 1, pads, "constant", act, threads=8))
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _truncated_half(y):
+    """fp32 -> half toward zero: the store of a kernel that cuts the mantissa instead of rounding it."""
+    y = np.asarray(y, np.float32)
+    h = y.astype(np.float16)
+    away = np.abs(h.astype(np.float32)) > np.abs(y)
+    return np.where(away, np.nextafter(h, np.float16(0)), h).astype(np.float32)
+
+
+def _tap_parts(x, wt):
+    """The k*k tap contributions of a "same" stride-1 layer, each an fp32 matmul over the input channels: [k*k][N,H,W,OC]."""
+    n, h, w, ic = x.shape
+    oc, _, k, _ = wt.shape
+    p = k // 2
+    xp = np.zeros((n, h + 2 * p, w + 2 * p, ic), np.float32)
+    xp[:, p:p + h, p:p + w] = x
+    return [xp[:, dy:dy + h, dx:dx + w] @ np.ascontiguousarray(wt[:, :, dy, dx].T) for dy in range(k) for dx in range(k)]
+
+
+HALF_MUTANTS = ["trunc", "splitk16", "acc16", "bias16", "preact16", "hole", "swap"]
+
+
+def _half_mutant(layer, kind):
+    """What a wrong f16 kernel would store, as float32 holding halves; None where the mutant does not apply to the layer."""
+    n, h, w, ic, oc, k, act = layer
+    x, wt, b, want64, pair32, oracle = _half_case(layer)
+    pads, out_hw = _geometry(h, w, k, 1, "same")
+    if kind == "trunc":
+        return _truncated_half(pair32)
+    if kind == "splitk16":  # K in two halves (kernel rows 0 .. k/2 and the rest), each partial sum rounded to half before they are added
+        parts = _tap_parts(x, wt)
+        cut = (k // 2 + 1) * k
+        v = _h32(np.sum(parts[:cut], axis=0, dtype=np.float32)) + _h32(np.sum(parts[cut:], axis=0, dtype=np.float32)) + b
+        return _h32(ref64.activation32(act, v))
+    if kind == "acc16":  # the accumulator kept in half from tap to tap
+        acc = np.zeros((n,) + out_hw + (oc,), np.float32)
+        for part in _tap_parts(x, wt):
+            acc = _h32(acc + part)
+        return _h32(ref64.activation32(act, acc + b))
+    if kind == "bias16":
+        return _h32(ref64.conv_layer_pairwise32(x, wt, _h32(b), 1, pads, "constant", out_hw, None, act))
+    if kind == "preact16":  # the pre-activation rounded to half before a transcendental activation
+        if act not in ("tanh", "sigmoid"):
+            return None
+        return _h32(ref64.activation32(act, _h32(ref64.conv2d_pairwise32(x, wt, b, 1, pads, "constant", out_hw))))
+    y = _h32(pair32)
+    if kind == "hole":  # one tile never written
+        y[1, :HALF_TILE[0], :HALF_TILE[1]] = np.nan
+        return y
+    if kind == "swap":  # one tile taken from the neighbouring image
+        y[1, :HALF_TILE[0], :HALF_TILE[1]] = y[0, :HALF_TILE[0], :HALF_TILE[1]]
+        return y
+    raise ValueError(kind)
+
+
+def _torch32(layer):
+    import torch
+    import torch.nn.functional as F
+
+    n, h, w, ic, oc, k, act = layer
+    x, wt, b, want64, pair32, oracle = _half_case(layer)
+    v = F.conv2d(torch.from_numpy(x).permute(0, 3, 1, 2), torch.from_numpy(wt), torch.from_numpy(b), padding=k // 2).permute(0, 2, 3, 1).numpy()
+    return ref64.activation32(act, np.ascontiguousarray(v))
+
+
+@pytest.mark.parametrize("how", ["pairwise", "oracle", "torch"])
+@pytest.mark.parametrize("layer", HALF_LAYERS, ids=HALF_IDS)
+def test_budget_half_accepts_honest_evaluations(layer, how):
+    """Three fp32 evaluations of different summation order, each rounded to half once: all inside M_F16, the pairwise one below 1 by construction."""
+    x, wt, b, want64, pair32, oracle = _half_case(layer)
+    y32 = {"pairwise": lambda: pair32, "oracle": lambda: oracle, "torch": lambda: _torch32(layer)}[how]()
+    assert y32.dtype == np.float32
+    ratio, mismatch, chan = ref64.budget_half(_h32(y32), want64, pair32, ref64.M_F16, what=how, tile=HALF_TILE)
+    print("HALF honest %s %s: %.2f x E32p max, %.3f %% mismatch, %.4f ulp per channel" % (how, layer, ratio, 100 * mismatch, chan))
+    if how == "pairwise":
+        assert ratio <= 1.0
+
+
+@pytest.mark.parametrize("kind", HALF_MUTANTS)
+@pytest.mark.parametrize("layer", HALF_LAYERS, ids=HALF_IDS)
+def test_budget_half_rejects_the_mutants(layer, kind):
+    x, wt, b, want64, pair32, oracle = _half_case(layer)
+    y = _half_mutant(layer, kind)
+    if y is None:
+        assert kind == "preact16" and layer[6] not in ("tanh", "sigmoid")
+        return
+    with pytest.raises(AssertionError) as e:
+        ref64.budget_half(y, want64, pair32, ref64.M_F16, what=kind, tile=HALF_TILE)
+    msg = str(e.value)
+    print("HALF mutant %s %s: %s" % (kind, layer, msg[:330]))
+    if kind == "hole":
+        assert "%d of %d values are not finite" % (8 * 32 * layer[4], y.size) in msg and "(n, y, x, channel) = (1, 0, 0, 0)" in msg, msg
+    else:
+        assert "out of the half budget" in msg, msg
+    if kind == "swap":
+        assert re.search(r"worst \(n, y, x, channel\) = \(1, [0-7], ([0-9]|[12][0-9]|3[01]), \d+\); tile 8x32 \(TH x TW\): tile \(ty, tx\) = \(0, 0\)", msg), msg
+
+
+# Whether the mutant passes allclose(..., rtol 4e-3, atol 4e-3) against the quantised oracle, per layer in the order of HALF_LAYERS: measured, and asserted
+# so that a change is noticed.  Every arithmetic mutant passes on every layer it applies to: the truncating store, the half split-K partials, the half
+# accumulator, the half bias and the half pre-activation.
+PASSES_TOLH = {"trunc": (True, True, True, True), "splitk16": (True, True, True, True), "acc16": (True, True, True, True),
+               "bias16": (True, True, True, True), "preact16": (None, None, True, None), "hole": (False,) * 4, "swap": (False,) * 4}
+
+
+def test_what_the_older_bound_lets_through():
+    """The gap this budget closes: TOLH against the quantised oracle accepts a store that truncates, split-K partials kept in half, an accumulator kept in
+    half from tap to tap, a half bias and a half pre-activation on every layer they apply to, while budget_half rejects each of them (116 x E32p max at the
+    least, the half bias; 800 x and more for the others).  Only a missing or misplaced tile fails both."""
+    for kind in HALF_MUTANTS:
+        for layer, expected in zip(HALF_LAYERS, PASSES_TOLH[kind]):
+            y = _half_mutant(layer, kind)
+            if y is None:
+                assert expected is None
+                continue
+            x, wt, b, want64, pair32, oracle = _half_case(layer)
+            want = _h32(oracle)
+            passes = bool(np.isfinite(y).all() and np.allclose(y, want, **TOLH))
+            over = np.maximum(np.abs(np.nan_to_num(y).astype(np.float64) - want64) - 0.5 * ref64.ulp16(want64), 0).max() / np.abs(pair32.astype(np.float64) - want64).max()
+            print("HALF gap %-9s %-13s passes TOLH: %-5s  budget_half statistic %.0f" % (kind, "x".join(map(str, layer[3:6])), passes, over))
+            assert passes == expected, (kind, layer)
+            with pytest.raises(AssertionError):
+                ref64.budget_half(y, want64, pair32, ref64.M_F16, what=kind)
+
+
+def test_the_half_margin_is_a_power_of_two_below_every_mutant():
+    """The cap of M_F16: the largest power of two at which every mutant above is still rejected (the half bias, 116 x at its smallest: 64)."""
+    assert ref64.M_F16 & (ref64.M_F16 - 1) == 0 and ref64.M_F16 <= 64
+    for layer in HALF_LAYERS:
+        x, wt, b, want64, pair32, oracle = _half_case(layer)
+        for kind in HALF_MUTANTS:
+            y = _half_mutant(layer, kind)
+            if y is not None:
+                with pytest.raises(AssertionError):
+                    ref64.budget_half(y, want64, pair32, 64, what=kind)
