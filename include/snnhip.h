@@ -598,6 +598,15 @@ int snnhip_chain_plan_create(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, 
  *       out[(s*64 + lane)*8 + j] = W[row lane%16][ic = 8*(g%2) + j][tap = 2*s + g/2],  s = 0..3, g = lane/16, j = 0..7
  *       out[2048 + lane*4 + j]   = W[row lane%16][ic = 4*g + j][tap = 8],               j = 0..3 */
 int snnhip_espcn_f16_pack_weights(const float* w_oihw, int ic, int k, int r, unsigned short* out, int capacity, int* count);
+/* The same for the rules at the published ESPCN widths, 1 -> 64 -> 32 -> r*r (espcn_f16_wide.hip): every K-step of a 3x3
+ * image is one tap and 32 input channels of v_mfma_f32_16x16x32_f16, MFMA rows in blocks of 16.  Host side only; any other shape returns
+ * SNNHIP_E_INVALID.
+ *   oc = 64, ic = 1, k = 3 or 5, r = 0:   [64][1][k][k] -> 2048 halfs,   out[(mb*64 + lane)*8 + j] = W[oc = 16*mb + lane%16][tap = 8*(lane/16) + j],
+ *                                                                         zero from tap k*k on
+ *   oc = 32, ic = 64, k = 3, r = 0:       [32][64][3][3] -> 18432 halfs, MFMA row = output channel, MB = 2 row blocks, KC = 2 K-steps per tap
+ *   oc = r*r, ic = 32, k = 3, r = 2,3,4:  [r*r][32][3][3] -> 4608 halfs, MFMA row 4*dy + dx = channel r*dy + dx (other rows zero), MB = 1, KC = 1
+ *       out[((ks*MB + mb)*64 + lane)*8 + j] = W[row 16*mb + lane%16][ic = 32*(ks % KC) + 8*(lane/16) + j][tap = ks / KC],  ks = 0 .. 9*KC - 1, j = 0..7 */
+int snnhip_espcn_f16_wide_pack_weights(const float* w_oihw, int oc, int ic, int k, int r, unsigned short* out, int capacity, int* count);
 
 /* Graph-level fusion: the ONE place where an operator DAG is searched for fusable groups (the host mirror's
  * HipBackend::finalizeStages and the Python GraphRunner both call it; the rules themselves are snnhip_chain_plan_create's).

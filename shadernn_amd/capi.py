@@ -214,6 +214,7 @@ SIGNATURES = {
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
+    "snnhip_espcn_f16_wide_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_graph_fuse": (C.c_int, [_P, C.POINTER(GraphNode), C.c_int, C.POINTER(FusedNode)]),
     "snnhip_plan_run": (C.c_int, [_P, _P, _P]),
     "snnhip_plan_run_n": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P]),
@@ -907,6 +908,16 @@ def espcn_f16_pack_weights(w_oihw, r=0):
     out = np.zeros(2304, np.uint16)
     n = C.c_int(0)
     check(lib().snnhip_espcn_f16_pack_weights(w.ctypes.data_as(_P), w.shape[1], w.shape[2], r, out.ctypes.data_as(_P), out.size, C.byref(n)))
+    return out[: n.value].view(np.float16).copy()
+
+
+def espcn_f16_wide_pack_weights(w_oihw, r=0):
+    """snnhip_espcn_f16_wide_pack_weights (host side only, no GPU): the lane-ordered fp16 images of the fp16 ESPCN kernels at the published widths, as
+    float16.  w_oihw [64][1][k][k] (k = 3, 5), [32][64][3][3] with r = 0 (MFMA row = channel) or [r*r][32][3][3] with r = 2, 3, 4 (row 4*dy + dx)."""
+    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
+    out = np.zeros(18432, np.uint16)
+    n = C.c_int(0)
+    check(lib().snnhip_espcn_f16_wide_pack_weights(w.ctypes.data_as(_P), w.shape[0], w.shape[1], w.shape[2], r, out.ctypes.data_as(_P), out.size, C.byref(n)))
     return out[: n.value].view(np.float16).copy()
 
 

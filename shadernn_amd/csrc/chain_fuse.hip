@@ -1,12 +1,13 @@
 // chain_fuse.hip -- the chain planner (make_chain_plan): a linear run of plans is rewritten into fewer launches.  No kernel lives here: every rule
 // either builds a plan through a factory of the unit that owns the kernel, or a fused ESPCN launch through that unit's header (espcn_fused.h,
-// espcn_d2s_mfma.h, espcn_f16.h, espcn_stream.hip's entry points in snnhip_internal.h).
+// espcn_d2s_mfma.h, espcn_f16.h, espcn_f16_wide.h, espcn_stream.hip's entry points in snnhip_internal.h).
 //
 // The reference runs one compute dispatch + one full barrier per layer (core/src/ic2/vulkanRenderpass.cpp:257-259) and round-trips every
 // intermediate through a texture.  Rules, tried at every position in this order (the order is behaviour):
 //   E    Conv2D (MFMA kernel) + Add                                   -> one two-input convolution plan, returned as is (never a chain)
 //   C    the whole ESPCN x2 pattern, SNNHIP_ESPCN_FUSION=stream       -> one row-streaming launch (espcn_stream.hip)
 //   A16 / B16   rules A / B on fp16 tensors, SNNHIP_ESPCN_F16=1       -> espcn_f16.hip
+//   A16 / B16 wide   the same at the published widths 1 -> 64 -> 32 -> r*r, fp16 only, same switch   -> espcn_f16_wide.hip
 //   A    conv KxK (1 -> 16) + act -> conv 3x3 (16 -> 16) + act        -> kernel A (espcn_fused.hip)
 //   B    conv 3x3 (16 -> r*r) + act -> depth-to-space(r) + tanh       -> kernel B (r = 2: espcn_fused.hip; r = 3, 4: espcn_d2s_mfma.hip)
 //   J, G D                                                            -> plans of conv2d_stem_f32.hip, irb_fused.hip / dwpw_march.hip, conv2d_mfma.hip
@@ -17,6 +18,7 @@
 
 #include "espcn_d2s_mfma.h"
 #include "espcn_f16.h"
+#include "espcn_f16_wide.h"
 #include "espcn_fused.h"
 #include "snnhip_internal.h"
 
@@ -55,15 +57,30 @@ bool is_same_conv(const ConvGeom& g, int k, int ic, int oc, int dtype = SNNHIP_F
     return g.dtype == dtype && g.preMode == 0 && g.kh == k && g.kw == k && g.IC == ic && g.OC == oc && g.sh == 1 && g.sw == 1 && g.padx == k / 2 && g.pady == k / 2 &&
            (g.padMode == SNNHIP_PAD_CONSTANT || g.padMode == SNNHIP_PAD_NONE) && g.OH == g.H && g.OW == g.W && plain_act(g.act);
 }
-// the head of the ESPCN pattern (rules A, A16, C): conv 5x5 or 3x3 (1 -> 16) -> conv 3x3 (16 -> 16)
-bool is_conv_pair(const ConvPlanBase* c0, const ConvPlanBase* c1, int dtype) {
-    return c0 && c1 && !c0->depthwise && !c1->depthwise && (is_same_conv(c0->g, 5, 1, 16, dtype) || is_same_conv(c0->g, 3, 1, 16, dtype)) &&
-           is_same_conv(c1->g, 3, 16, 16, dtype);
+// The widths of the ESPCN pattern: C1 behind the first convolution, C2 behind the second (= what the tail reads).  The rules compare them with the
+// widths their kernels are built for: (16, 16) the reference demo's reduced net, (64, 32) the published one (fp16 only, espcn_f16_wide.hip).
+struct EspcnWidths {
+    int c1 = 0, c2 = 0;
+    bool operator==(const EspcnWidths& o) const { return c1 == o.c1 && c2 == o.c2; }
+};
+constexpr EspcnWidths kNarrow{16, 16}, kWide{kEspcnF16WideC1, kEspcnF16WideC2};
+// the head of the ESPCN pattern (rules A, A16, A16 wide, C): conv 5x5 or 3x3 (1 -> C1) -> conv 3x3 (C1 -> C2); returns (C1, C2), or (0, 0)
+EspcnWidths conv_pair_widths(const ConvPlanBase* c0, const ConvPlanBase* c1, int dtype) {
+    if (!c0 || !c1 || c0->depthwise || c1->depthwise) return {};
+    const EspcnWidths w{c0->g.OC, c1->g.OC};
+    return ((is_same_conv(c0->g, 5, 1, w.c1, dtype) || is_same_conv(c0->g, 3, 1, w.c1, dtype)) && is_same_conv(c1->g, 3, w.c1, w.c2, dtype)) ? w : EspcnWidths{};
 }
-// its tail (rules B, B16): conv 3x3 (16 -> r*r) -> depth-to-space(r), r = 2, 3, 4; returns r, or 0
-int d2s_tail_factor(const ConvPlanBase* c0, const SubpixelPlanBase* sp1, int dtype) {
+bool is_conv_pair(const ConvPlanBase* c0, const ConvPlanBase* c1, int dtype, const EspcnWidths& want = kNarrow) { return conv_pair_widths(c0, c1, dtype) == want; }
+// its tail (rules B, B16, B16 wide): conv 3x3 (C2 -> r*r) -> depth-to-space(r), r = 2, 3, 4; returns r where C2 is the width asked for, or 0
+int d2s_tail_factor(const ConvPlanBase* c0, const SubpixelPlanBase* sp1, int dtype, int c2 = kNarrow.c2) {
     const int r = (c0 && sp1) ? sp1->d.factor : 0;
-    return (r >= 2 && r <= 4 && !c0->depthwise && is_same_conv(c0->g, 3, 16, r * r, dtype) && sp1->d.mode == SNNHIP_SUBPIXEL_D2S && sp1->d.C == r * r) ? r : 0;
+    return (r >= 2 && r <= 4 && !c0->depthwise && is_same_conv(c0->g, 3, c2, r * r, dtype) && sp1->d.mode == SNNHIP_SUBPIXEL_D2S && sp1->d.C == r * r) ? r : 0;
+}
+// The fp16 tails (B16, B16 wide) behind an ESPCN head of other widths than their kernel family's -- (64, 16), (32, 32), ... -- decline: such a net
+// stays per layer as a whole.  A tail with no such head in front of it (a chain that starts at the tail) is taken as before.
+bool behind_other_head(const ConvPlanBase* h0, const ConvPlanBase* h1, const EspcnWidths& want) {
+    const EspcnWidths head = conv_pair_widths(h0, h1, SNNHIP_F16);
+    return head.c1 != 0 && !(head == want);
 }
 void rename_kernel(std::string& desc, const char* from, const char* to) {
     const size_t at = desc.find(from);
@@ -229,6 +246,59 @@ struct FusedB16 : FusedLaunch { // rule B16 and its 8-bit form, upscale 2, 3 or 
         u16out = true;
         qout16 = U16OutCfg{uo.scale[0], uo.offset[0], static_cast<float>(uo.maxval), uo.shift};
         rename_kernel(desc, "kernel=espcn_f16_d2s_kernel", "kernel=espcn_f16_d2s_u16_kernel");
+        return true;
+    }
+};
+
+struct FusedA16Wide : FusedLaunch { // rule A16 wide and its frame forms (espcn_f16_wide.hip): w1, w2 hold halfs (espcn_f16_wide_pack_w1 / _w3)
+    EspcnF16AParams p{};
+    int k1 = 5, frameBits = 0;
+    U16InCfg qin16{0.0f, 0.0f, 0};
+    float *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr;
+    int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
+        return espcn_f16_wide_a_launch(ctx->stream, k1, p, frameBits, qin16, x, reinterpret_cast<const _Float16*>(w1), reinterpret_cast<const _Float16*>(w2), e1, e2,
+                                       reinterpret_cast<_Float16*>(y), evStart, evStop);
+    }
+    bool foldU8In(const snnhip_u8_in_desc& ui, std::string& desc) override {
+        if (ui.dtype != SNNHIP_F16 || frameBits) return false;
+        frameBits = 8;
+        p.mean = ui.means[0];
+        p.norm = ui.norms[0];
+        rename_kernel(desc, "kernel=espcn_f16_wide_conv_pair_kernel", "kernel=espcn_f16_wide_conv_pair_kernel<u8>");
+        return true;
+    }
+    bool foldU16In(const snnhip_u16_in_desc& ui, std::string& desc) override {
+        if (ui.dtype != SNNHIP_F16 || frameBits) return false;
+        frameBits = 16;
+        qin16 = U16InCfg{ui.means[0], ui.norms[0], ui.shift};
+        rename_kernel(desc, "kernel=espcn_f16_wide_conv_pair_kernel", "kernel=espcn_f16_wide_conv_pair_u16_kernel");
+        return true;
+    }
+};
+
+struct FusedB16Wide : FusedLaunch { // rule B16 wide and its frame forms, upscale 2, 3 or 4 (espcn_f16_wide.hip): w holds halfs
+    EspcnF16BParams p{};
+    int r = 2, frameBits = 0;
+    U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
+    float *w = nullptr, *e = nullptr;
+    int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
+        return espcn_f16_wide_b_launch(ctx->stream, r, p, frameBits, qout16, reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(w), e, y, evStart,
+                                       evStop);
+    }
+    bool foldU8Out(const snnhip_u8_out_desc& uo, std::string& desc) override {
+        if (uo.dtype != SNNHIP_F16 || frameBits) return false;
+        frameBits = 8;
+        p.qscale = uo.scale[0];
+        p.qoffset = uo.offset[0];
+        const size_t at = desc.find(">", desc.find("kernel=espcn_f16_wide_d2s_kernel<"));
+        if (at != std::string::npos) desc.insert(at, ",u8");
+        return true;
+    }
+    bool foldU16Out(const snnhip_u16_out_desc& uo, std::string& desc) override {
+        if (uo.dtype != SNNHIP_F16 || frameBits) return false;
+        frameBits = 16;
+        qout16 = U16OutCfg{uo.scale[0], uo.offset[0], static_cast<float>(uo.maxval), uo.shift};
+        rename_kernel(desc, "kernel=espcn_f16_wide_d2s_kernel", "kernel=espcn_f16_wide_d2s_u16_kernel");
         return true;
     }
 };
@@ -399,7 +469,7 @@ int rule_b16(Planner& pl, int i, Step& st) {
     auto* c0 = pl.as<ConvPlanBase>(i);
     auto* sp1 = pl.as<SubpixelPlanBase>(i + 1);
     const int r16 = pl.sw.f16 ? d2s_tail_factor(c0, sp1, SNNHIP_F16) : 0;
-    if (!r16) return 0;
+    if (!r16 || (i >= 2 && behind_other_head(pl.as<ConvPlanBase>(i - 2), pl.as<ConvPlanBase>(i - 1), kNarrow))) return 0;
     const ConvGeom& g0 = c0->g;
     auto f = std::make_unique<FusedB16>();
     f->r = r16;
@@ -414,6 +484,57 @@ int rule_b16(Planner& pl, int i, Step& st) {
              r16 * r16, r16, kEspcnF16TW_B, kEspcnF16TH_B, r16, tilesB * (kEspcnF16TW_B * kEspcnF16TH_B / 16) * (4 * 16384.0 + 8192.0));
     const double bytes = 2.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (16 + r16 * r16) + static_cast<double>(r16 * r16) * 16 * 9);
     return fill_step(st, std::move(f), sp1->outDims, buf, c0->flops, bytes, 2);
+}
+
+// ---- rule A16 wide: the same pattern at the published widths (1 -> 64 -> 32) on fp16 tensors -> kernel A16 wide of espcn_f16_wide.hip
+int rule_a16_wide(Planner& pl, int i, Step& st) {
+    auto *c0 = pl.as<ConvPlanBase>(i), *c1 = pl.as<ConvPlanBase>(i + 1);
+    if (!pl.sw.f16 || !is_conv_pair(c0, c1, SNNHIP_F16, kWide)) return 0;
+    const ConvGeom& g0 = c0->g;
+    constexpr int C1 = kWide.c1, C2 = kWide.c2, TW = kEspcnF16WideTW_A, TH = kEspcnF16WideTH_A;
+    const int K1 = g0.kh, taps1 = K1 * K1;
+    auto f = std::make_unique<FusedA16Wide>();
+    f->k1 = K1;
+    f->p = EspcnF16AParams{g0.N, g0.H, g0.W, up_div(g0.W, TW), up_div(g0.H, TH), make_act_cfg(g0.act, g0.leaky), make_act_cfg(c1->g.act, c1->g.leaky), 0.0f, 1.0f};
+    std::vector<_Float16> w1h(kEspcnF16WideW1Halfs), w2h(kEspcnF16WideW2Halfs);
+    espcn_f16_wide_pack_w1(c0->w_oihw.data(), C1, K1, w1h.data());
+    espcn_f16_wide_pack_w3(c1->w_oihw.data(), C1, C2, 0, w2h.data());
+    pl.upload_halfs(w1h, &f->w1);
+    pl.upload_halfs(w2h, &f->w2);
+    pl.upload(fold_epilogue(c0->epi4, C1, g0.useBN), &f->e1);
+    pl.upload(fold_epilogue(c1->epi4, C2, c1->g.useBN), &f->e2);
+    // MFMA flops issued per tile (16384 per 16x16x32): conv1 C1/16 per 16 pixels of the halo region (the waves take two groups a turn), conv2
+    // 9 * C1/32 K-steps x C2/16 row blocks per 16 pixels
+    const double tilesA = static_cast<double>(f->p.tilesX) * f->p.tilesY * g0.N;
+    const int groups1 = round_up(up_div((TW + 2) * (TH + 2), 16), 2);
+    char buf[320];
+    snprintf(buf, sizeof(buf), "fused[conv%dx%d(1->%d)+conv3x3(%d->%d)] mfma_f32_16x16x32_f16 tile=%dx%d kernel=espcn_f16_wide_conv_pair_kernel mfma_flops=%.6g", K1, K1,
+             C1, C1, C2, TW, TH, tilesA * 16384.0 * (groups1 * (C1 / 16) + (TW * TH / 16) * (9 * C1 / 32) * (C2 / 16)));
+    const double bytes = 2.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (1 + C2) + static_cast<double>(C1) * taps1 + static_cast<double>(C1) * C2 * 9);
+    return fill_step(st, std::move(f), c1->outDims, buf, c0->flops + c1->flops, bytes, 2);
+}
+
+// ---- rule B16 wide: the tail behind it (32 -> r*r, upscale 2, 3, 4) on fp16 tensors -> kernel B16 wide<r> of espcn_f16_wide.hip
+int rule_b16_wide(Planner& pl, int i, Step& st) {
+    auto* c0 = pl.as<ConvPlanBase>(i);
+    auto* sp1 = pl.as<SubpixelPlanBase>(i + 1);
+    const int r = pl.sw.f16 ? d2s_tail_factor(c0, sp1, SNNHIP_F16, kWide.c2) : 0;
+    if (!r || (i >= 2 && behind_other_head(pl.as<ConvPlanBase>(i - 2), pl.as<ConvPlanBase>(i - 1), kWide))) return 0;
+    const ConvGeom& g0 = c0->g;
+    constexpr int C2 = kWide.c2, TW = kEspcnF16WideTW_B, TH = kEspcnF16WideTH_B;
+    auto f = std::make_unique<FusedB16Wide>();
+    f->r = r;
+    f->p = EspcnF16BParams{g0.N, g0.H, g0.W, up_div(g0.W, TW), up_div(g0.H, TH), make_act_cfg(g0.act, g0.leaky), 1.0f, 0.0f};
+    std::vector<_Float16> wh(kEspcnF16WideW3Halfs);
+    espcn_f16_wide_pack_w3(c0->w_oihw.data(), C2, 16, r, wh.data());
+    pl.upload_halfs(wh, &f->w);
+    pl.upload(fold_epilogue(c0->epi4, r * r, g0.useBN, r), &f->e);
+    const double tilesB = static_cast<double>(f->p.tilesX) * f->p.tilesY * g0.N;
+    char buf[256];
+    snprintf(buf, sizeof(buf), "fused[conv3x3(%d->%d)+depth_to_space(%d)+tanh] mfma_f32_16x16x32_f16 tile=%dx%d kernel=espcn_f16_wide_d2s_kernel<%d> mfma_flops=%.6g", C2,
+             r * r, r, TW, TH, r, tilesB * (TW * TH / 16) * (9 * C2 / 32) * 16384.0);
+    const double bytes = 2.0 * (static_cast<double>(g0.N) * g0.H * g0.W * (C2 + r * r) + static_cast<double>(r * r) * C2 * 9);
+    return fill_step(st, std::move(f), sp1->outDims, buf, c0->flops + sp1->flops, bytes, 2);
 }
 
 // ---- rule A: kernel A of espcn_fused.hip, conv2 as Winograd F(2x2,3x3) (default) or direct (SNNHIP_ESPCN_A=direct)
@@ -574,7 +695,7 @@ int rule_pad_conv(Planner& pl, int i, Step& st) {
     return wrap_plan(pl, fused, true, 2, st);
 }
 
-int (*const kRules[])(Planner& pl, int i, Step& st) = {rule_stream, rule_a16, rule_b16, rule_a, rule_b, rule_b_mfma, rule_stem_pool, rule_stem_irb, rule_irb, rule_dwpw,
+int (*const kRules[])(Planner& pl, int i, Step& st) = {rule_stream, rule_a16, rule_b16, rule_a16_wide, rule_b16_wide, rule_a, rule_b, rule_b_mfma, rule_stem_pool, rule_stem_irb, rule_irb, rule_dwpw,
                            rule_upsample_pad_conv, rule_pad_conv};
 
 // ---- rule I: an InstanceNorm step followed by a convolution step (as given, or built by rule D above) whose kernel can normalise in its

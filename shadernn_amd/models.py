@@ -37,9 +37,13 @@ def _dense(rng, name, inu, outu, act):
             "ic": inu, "oc": outu}
 
 
-def espcn_weights(seed=1, scale=2):
-    """ESPCN at upscale factor r = scale: conv5x5 1->16 relu, conv3x3 16->16 relu, conv3x3 16->r*r linear, depth-to-space(r)+tanh.
-    scale=2 is the net (names, weights, RNG order) this function has always returned; other factors carry "upscale" on the Subpixel layer."""
+def espcn_weights(seed=1, scale=2, widths=(16, 16)):
+    """ESPCN at upscale factor r = scale: conv5x5 1->C1 relu, conv3x3 C1->C2 relu, conv3x3 C2->r*r linear, depth-to-space(r)+tanh, (C1, C2) = widths.
+    scale=2 is the net (names, weights, RNG order) this function has always returned; other factors carry "upscale" on the Subpixel layer.
+    widths=(16, 16) is the reference demo's reduced net (the default: unchanged), (64, 32) the net as published."""
+    c1, c2 = (int(c) for c in widths)
+    if c1 < 1 or c2 < 1:
+        raise ValueError("espcn_weights: widths must be positive, got %r" % (widths,))
     r = int(scale)
     if r < 1:
         raise ValueError("espcn_weights: scale must be >= 1, got %r" % (scale,))
@@ -48,7 +52,7 @@ def espcn_weights(seed=1, scale=2):
     if r != 2:
         sub["upscale"] = r
     return {"name": "ESPCN_%dX" % r, "input_channels": 1,
-            "layers": [_conv(rng, "conv2d", 1, 16, 5, "relu"), _conv(rng, "conv2d_1", 16, 16, 3, "relu"), _conv(rng, "conv2d_2", 16, r * r, 3, "linear"),
+            "layers": [_conv(rng, "conv2d", 1, c1, 5, "relu"), _conv(rng, "conv2d_1", c1, c2, 3, "relu"), _conv(rng, "conv2d_2", c2, r * r, 3, "linear"),
                        sub]}
 
 

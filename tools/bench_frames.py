@@ -23,6 +23,13 @@ step per form with the spread over the rounds, the kernels of the launch trace, 
 
     python tools/bench_frames.py --half --scale 2
 
+--half --widths 64,32 (with any --scale): the net at the published widths 1 -> 64 -> 32 -> r*r.  No fused fp32 form exists
+for it, so the forms are f16_layers, f16 (the two launches of espcn_f16_wide.hip) and f16_u8; each fused form also reports its issued MFMA flops and
+its two floors (its own bytes at --hbm-tbs, those flops at --f16-mfma-tflops).  --out FILE merges the record into a JSON file under the key
+half_64_32_scale<r>: profiles/espcn_wide_frames.json holds the runs at 1080p x2, 720p x3 and 540p x4.
+
+    python tools/bench_frames.py --half --widths 64,32 --scale 3 --out profiles/espcn_wide_frames.json
+
 --bits 10 | 12 | 16 (with any --scale): two more forms in the same alternation and the same
 end-to-end rounds, u16 (16-bit frames, the conversions folded into the fp32 kernels: two launches) and u16_sep (u16_in, the fp32 chain, u16_out:
 four launches), on low-aligned frames of that bit depth normalised symmetrically ((2^bits - 1) / 2).  The f32 and u8 forms of the same run are the
@@ -116,7 +123,9 @@ def main_half(a):
     snn.load_library()
     ctx = capi.Context(0)
     R = a.scale
-    net = models.espcn_weights(seed=1, scale=R)
+    widths = tuple(int(c) for c in a.widths.split(","))
+    wide = widths != (16, 16)  # no fused fp32 form at other widths: the f32 arm is left out
+    net = models.espcn_weights(seed=1, scale=R, widths=widths)
     H, W = a.h or 2160 // R, a.w or 3840 // R
     u8 = np.random.default_rng(1).integers(0, 256, size=(1, H, W, 1), dtype=np.uint8)
     f32 = ((u8.astype(np.float32) - 127.5) * np.float32(1 / 127.5))
@@ -171,12 +180,12 @@ def main_half(a):
         finally:
             capi.set_option("SNNHIP_ESPCN_F16", None)
         assert c16u16.num_steps() == 2, c16u16.describe()
-    forms = {
-        "f32": dict(plan=capi.chain_plan(ctx, l32), x=capi.Tensor(ctx, 1, H, W, 1), y=capi.Tensor(ctx, *shape)),
+    forms = {} if wide else {"f32": dict(plan=capi.chain_plan(ctx, l32), x=capi.Tensor(ctx, 1, H, W, 1), y=capi.Tensor(ctx, *shape))}
+    forms.update({
         "f16_layers": dict(plan=Seq(l16, capi.F16), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.F16), y=capi.Tensor(ctx, *shape, dtype=capi.F16)),
         "f16": dict(plan=c16, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.F16), y=capi.Tensor(ctx, *shape, dtype=capi.F16)),
         "f16_u8": dict(plan=c16u8, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U8), y=capi.Tensor(ctx, *shape, dtype=capi.U8)),
-    }
+    })
     if a.bits:
         forms["f16_u16"] = dict(plan=c16u16, x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U16), y=capi.Tensor(ctx, *shape, dtype=capi.U16))
         forms["f16_u16_sep"] = dict(plan=Seq([win, c16, wout], capi.F16), x=capi.Tensor(ctx, 1, H, W, 1, dtype=capi.U16), y=capi.Tensor(ctx, *shape, dtype=capi.U16))
@@ -202,9 +211,11 @@ def main_half(a):
                 f["plan"].run(f["x"], f["y"])
             timer.stop()
             dev[k].append(timer.elapsed_ms() / a.iters)
-    y16, y32 = forms["f16"]["y"].numpy(), forms["f32"]["y"].numpy()
-    out = {"frame": "%dx%d -> %dx%d" % (H, W, R * H, R * W), "scale": R, "rounds": a.rounds, "iters": a.iters,
-           "max_abs_f16_minus_f32": float(np.abs(y16 - y32).max()), "max_abs_f16_minus_f16_layers": float(np.abs(y16 - forms["f16_layers"]["y"].numpy()).max())}
+    y16 = forms["f16"]["y"].numpy()
+    out = {"frame": "%dx%d -> %dx%d" % (H, W, R * H, R * W), "scale": R, "widths": list(widths), "rounds": a.rounds, "iters": a.iters,
+           "max_abs_f16_minus_f16_layers": float(np.abs(y16 - forms["f16_layers"]["y"].numpy()).max())}
+    if not wide:
+        out["max_abs_f16_minus_f32"] = float(np.abs(y16 - forms["f32"]["y"].numpy()).max())
     for k, f in forms.items():
         plan, d = f["plan"], statistics.median(dev[k])
         capi.trace_begin()
@@ -220,7 +231,16 @@ def main_half(a):
                   "steps": [plan.step_describe(i) for i in range(plan.num_steps())],
                   "kernels": [{"function": it.get("function"), "launches": it.get("launches", 0),
                                "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]}
-    out["device_f16_over_f32"] = round(out["f16"]["device_ms_median"] / out["f32"]["device_ms_median"], 4)
+        # the fused forms against their two floors: the steps' own bytes at the HBM rate, the MFMA flops they issue at the f16 matrix peak
+        issued = [float(s.split("mfma_flops=")[1].split()[0]) for s in out[k]["steps"] if "mfma_flops=" in s]
+        if k != "f16_layers" and len(issued) == plan.num_steps():
+            out[k]["mfma_flops_issued"] = sum(issued)
+            out[k]["floor_ms_hbm"] = round(nbytes / (a.hbm_tbs * 1e12) * 1e3, 4)
+            out[k]["floor_ms_mfma_f16"] = round(sum(issued) / (a.f16_mfma_tflops * 1e12) * 1e3, 4)
+            out[k]["hbm_floor_over_median"] = round(out[k]["floor_ms_hbm"] / d, 4)
+            out[k]["mfma_floor_over_median"] = round(out[k]["floor_ms_mfma_f16"] / d, 4)
+    if not wide:
+        out["device_f16_over_f32"] = round(out["f16"]["device_ms_median"] / out["f32"]["device_ms_median"], 4)
     out["device_f16_over_f16_layers"] = round(out["f16"]["device_ms_median"] / out["f16_layers"]["device_ms_median"], 4)
     out["device_f16_u8_over_f16"] = round(out["f16_u8"]["device_ms_median"] / out["f16"]["device_ms_median"], 4)
     if a.bits:
@@ -230,6 +250,12 @@ def main_half(a):
         out["device_f16_u16_over_f16_u16_sep"] = round(out["f16_u16"]["device_ms_median"] / out["f16_u16_sep"]["device_ms_median"], 4)
     out["spread_max"] = max(out[k]["spread"] for k in forms)
     print(json.dumps(out, indent=1))
+    if a.out:  # merge the record into a JSON file under half[_<c1>_<c2>]_scale<r>
+        rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        rec["half_%sscale%d" % ("%d_%d_" % widths if wide else "", R)] = out
+        with open(a.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
     ctx.close()
 
 
@@ -1099,6 +1125,8 @@ def main_planar(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
+    ap.add_argument("--widths", default="16,16", metavar="C1,C2", help="with --half: the ESPCN's channel widths; 64,32 is the net as published (per-layer fp16, fused fp16, fused fp16 with 8-bit ends)")
+    ap.add_argument("--f16-mfma-tflops", type=float, default=2500.0, help="with --half: the f16 matrix peak the fused steps' issued MFMA flops are held against, TFLOP/s")
     ap.add_argument("--scale", type=int, default=2, choices=[2, 3, 4], help="upscale factor; the input size follows it (output 3840 x 2160) unless --h / --w are given")
     ap.add_argument("--bits", type=int, default=0, choices=[0, 10, 12, 16], help="also time 16-bit frames of this bit depth, folded and as separate launches")
     ap.add_argument("--colour", choices=["RGB8", "RGBA8"], default=None, help="colour frames around the luma chain: r8, colour, the merge launch alone and a device copy of its bytes")
