@@ -214,6 +214,27 @@ int snn_model_create12(const char* json_path, int device, int in_w, int in_h, in
  * pitch below the row's bytes, or an RGB end.  snn_model_upload_frame_nv12 / _download_frame_nv12 keep their behaviour and return -1 on planar ends. */
 int snn_model_upload_frame_planes(snn_model* m, const void* const* planes, const int* pitch_bytes, int n_planes);
 int snn_model_download_frame_planes(snn_model* m, void* const* planes, const int* pitch_bytes, int n_planes);
+/* Frame quality on the device: PSNR and SSIM of the model's output frame against a ground-truth frame, without downloading the output
+ * (include/snnhip.h, snnhip_frame_metrics_plan_create, states the definition).  They sit on an existing model: no entry point of its own.
+ * snn_model_reference_frame takes the ground-truth frame in exactly the dense layout this model's download function takes
+ * (snn_model_download_frame_u8 / _u16 / _nv12); snn_model_reference_frame_planes has the arguments and the acceptance rules of
+ * snn_model_download_frame_planes.  The first call to either allocates device-resident reference tensors and one metrics plan per output plane
+ * tensor: a packed R8 / RGB8 / RGBA8 or 16-bit frame one plan with C = 1, 3 or 4; NV12 / P010 a luma plan (C = 1) and a CbCr plan (C = 2); I420 /
+ * I010 a luma plan and one C = 1 plan over the 2 * batch chroma planes; a fitted out_size the fitted planes.  A later call replaces the reference.
+ * Both return -1, with a logged message, on a model whose output is a float tensor (and for a null argument).
+ * snn_model_frame_metrics runs the plans on the output of the last run against the reference, on the model's stream behind that run and outside the
+ * recorded graph (a replayed graph is not changed: snn_model_run launches what it launched before), waits, and writes one row per (image, plane,
+ * channel), image-major: the frame's channels (plane 0), then on a video output the chroma plane's -- plane 1 with channels 0 (Cb) and 1 (Cr) for
+ * NV12 / P010, planes 1 (Cb) and 2 (Cr) with channel 0 for I420 / I010.  psnr_db is +inf for equal planes; ssim is 1.0 exactly for them.  Returns
+ * the row count, or -1 with a logged message when no reference was set, for a null argument and for max_rows below the count. */
+typedef struct snn_frame_metrics {
+    int image, plane, channel;
+    unsigned long long sse, pixels;
+    double psnr_db, ssim;
+} snn_frame_metrics;
+int snn_model_reference_frame(snn_model* m, const void* frame);
+int snn_model_reference_frame_planes(snn_model* m, const void* const* planes, const int* pitch_bytes, int n_planes);
+int snn_model_frame_metrics(snn_model* m, snn_frame_metrics* rows, int max_rows);
 int snn_model_batch(snn_model* m);
 /* the C-ABI handles behind a model: its context (device + stream) and the device tensor of its last stage's output (borrowed) */
 struct snnhip_ctx* snn_model_hip_ctx(snn_model* m);

@@ -580,6 +580,40 @@ int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* d
  * one with SNNHIP_SITING_CENTRE) and keeps them in device memory.  SNNHIP_E_INVALID with a message for a ratio outside [1/2, 4], a null pointer,
  * too little room and an unknown siting. */
 int snnhip_fit_taps(int in, int out, int siting, float* weights, int* base, int capacity);
+
+/* Frame quality on the device: PSNR and SSIM between a test frame and a reference frame, so that what an arithmetic choice (fused fp32, the fp16
+ * opt-in, 8 / 10 / 12-bit frame ends) or a trained model costs in picture quality can be stated in dB without downloading every output frame.
+ * DESIGN.md section 4.22.  The reference ships a host-side comparison script only (tools/misc/imageComparison.py).  The definition, stated once
+ * (tests/metrics_ref.py restates it in NumPy):
+ *   Shapes: inputs[0] = the test frame a, inputs[1] = the reference frame b, both [N][H][W][C] of the desc's dtype, SNNHIP_U8 or SNNHIP_U16, C = 1..4
+ *     interleaved; run with snnhip_plan_run_n, 2 inputs.  The sample value is v = u >> shift (shift = 0 for SNNHIP_U8): the bits below `shift` are
+ *     ignored, exactly as u16_in ignores them.  Results are per image n and channel c; images and channels never mix.
+ *   SSE and PSNR: sse = sum (a - b)^2 over all H * W pixels, an exact unsigned 64-bit integer; pixels = H * W;
+ *     psnr_db = 10 log10(maxval^2 pixels / sse) in double, +inf for sse == 0.
+ *   SSIM: the integer-moment form on 8x8 windows with a 4-pixel step, modelled on what x264 and ffmpeg's ssim filter compute.  bh = H >> 2,
+ *     bw = W >> 2; rows and columns past 4 bh, 4 bw take no part in SSIM (they do in SSE).  Every 4x4 block has the exact integers s1 = sum a,
+ *     s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b.  A window is the sum of a 2x2 group of neighbouring blocks: (bh - 1)(bw - 1) windows.  Per
+ *     window, from the integer moments converted to double (all below 2^53 up to 16 bits):
+ *         c1 = 0.01^2 maxval^2 64,  c2 = 0.03^2 maxval^2 64 63,  vars = 64 ss - s1^2 - s2^2,  covar = 64 s12 - s1 s2,
+ *         t = (2 s1 s2 + c1)(2 covar + c2) / ((s1^2 + s2^2 + c1)(vars + c2))
+ *     ssim = sum t / windows, in double.  Equal frames give t = 1 exactly in every window, hence ssim = 1.0 exactly.
+ *   Output: SNNHIP_F32 [N][1][C][2] = {psnr_db, ssim}, the doubles rounded to float (psnr_db may be +inf).  The exact results stay in the plan:
+ *     snnhip_frame_metrics_read waits for the context's stream, copies the N * C rows (n-major) {sse, pixels, windows, ssim_sum} to the host and
+ *     returns their count (a negative SNNHIP_E_* code on failure; max_rows below N * C is SNNHIP_E_INVALID).  snnhip_frame_metrics_psnr is the dB
+ *     formula on the host, device-free, for callers that add sse over frames.
+ *   Two launches, no atomics, no memset: a tile kernel that leaves one partial per (block, channel) in a scratch buffer of the plan and a fold kernel
+ *     that adds them in index order.  A result is bit-identical from run to run and the plan can be recorded in an snnhip_graph.
+ * Plan creation returns SNNHIP_E_INVALID with a message starting "frame_metrics" for C outside 1..4, a dtype that is neither SNNHIP_U8 nor SNNHIP_U16,
+ * H or W below 8 (no window would exist) and a maxval / shift that does not fit the container (shift 0 for 8-bit frames, 0..15 for 16-bit ones,
+ * 1 <= maxval, maxval << shift within the container: chroma_up's rules, but up to maxval 65535 with shift 0, integers have no rounding contract to
+ * keep); snnhip_plan_run_n for a tensor of another dtype or shape at either input and an output that is not SNNHIP_F32 [N][1][C][2].
+ * snnhip_plan_describe: "frame_metrics_u8 c=1 tile=32x128 ... kernel=frame_metrics_tile_kernel+frame_metrics_fold_kernel".  snnhip_plan_cost counts
+ * both frames once plus the partials, written and read. */
+typedef struct { int N, H, W, C; int dtype; int maxval, shift; } snnhip_frame_metrics_desc;
+int snnhip_frame_metrics_plan_create(snnhip_ctx* ctx, const snnhip_frame_metrics_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_n, 2 inputs */
+typedef struct { unsigned long long sse, pixels, windows; double ssim_sum; } snnhip_frame_metrics_row;
+int snnhip_frame_metrics_read(snnhip_plan* plan, snnhip_frame_metrics_row* rows, int max_rows);
+double snnhip_frame_metrics_psnr(unsigned long long sse, unsigned long long pixels, int maxval);
 /* index of the largest element of image n of t (first one on ties, like std::max_element in MixedInferenceCore::run, core.cpp:228-234,
  * which reports index + 1 as classifierOutput); stream sync + a 4-byte D2H */
 int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);

@@ -122,6 +122,14 @@ class PlaneFitDesc(C.Structure):
                 ("siting", C.c_int)]
 
 
+class FrameMetricsDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int)]
+
+
+class FrameMetricsRow(C.Structure):
+    _fields_ = [("sse", C.c_ulonglong), ("pixels", C.c_ulonglong), ("windows", C.c_ulonglong), ("ssim_sum", C.c_double)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("compute_units", C.c_int), ("lds_bytes_per_cu", C.c_int), ("hbm_bytes", C.c_size_t), ("device", C.c_int)]
 
@@ -211,6 +219,9 @@ SIGNATURES = {
     "snnhip_rgb_cbcr_planar_plan_create": (C.c_int, [_P, C.POINTER(RgbCbcrDesc), C.POINTER(_P)]),
     "snnhip_plane_fit_plan_create": (C.c_int, [_P, C.POINTER(PlaneFitDesc), C.POINTER(_P)]),
     "snnhip_fit_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
+    "snnhip_frame_metrics_plan_create": (C.c_int, [_P, C.POINTER(FrameMetricsDesc), C.POINTER(_P)]),
+    "snnhip_frame_metrics_read": (C.c_int, [_P, C.POINTER(FrameMetricsRow), C.c_int]),
+    "snnhip_frame_metrics_psnr": (C.c_double, [C.c_ulonglong, C.c_ulonglong, C.c_int]),
     "snnhip_tensor_argmax": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -885,6 +896,35 @@ def fit_taps(n_in, n_out, siting="centre", capacity=None):
     base = (C.c_int * max(n, 1))()
     check(lib().snnhip_fit_taps(n_in, n_out, SITING.get(siting, siting), _fptr(w), base, w.size if capacity is None else capacity))
     return w, np.array(base[:n], np.int32)
+
+
+FRAME_METRICS_TILE = (32, 128)  # (rows, columns) of pixels one block of frame_metrics_tile_kernel owns (csrc/frame_metrics.h); the plan's description carries it
+
+
+def frame_metrics_plan(ctx, N, H, W, Cc, dtype=U8, maxval=None, shift=0):
+    """snnhip_frame_metrics_plan_create: PSNR and SSIM of a test frame against a reference frame, per image and channel.  Run it with
+    plan([test, reference], out), out an F32 tensor [N][1][C][2] = {psnr_db, ssim}; frame_metrics_read(plan) gives the exact rows."""
+    d = FrameMetricsDesc()
+    d.N, d.H, d.W, d.C, d.dtype, d.shift = N, H, W, Cc, dtype, shift
+    d.maxval = (255 if dtype == U8 else 65535) if maxval is None else maxval
+    h = _P()
+    check(lib().snnhip_frame_metrics_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def frame_metrics_read(plan, max_rows=None):
+    """snnhip_frame_metrics_read: waits for the context's stream; one dict {sse, pixels, windows, ssim_sum, ssim} per (image, channel), image-major."""
+    n, _, c, _ = plan.out_shape()
+    rows = (FrameMetricsRow * (n * c if max_rows is None else max(max_rows, 1)))()
+    got = lib().snnhip_frame_metrics_read(plan.h, rows, n * c if max_rows is None else max_rows)
+    if got < 0:
+        check(got)
+    return [{"sse": r.sse, "pixels": r.pixels, "windows": r.windows, "ssim_sum": r.ssim_sum, "ssim": r.ssim_sum / r.windows} for r in rows[:got]]
+
+
+def frame_metrics_psnr(sse, pixels, maxval):
+    """snnhip_frame_metrics_psnr: 10 log10(maxval^2 pixels / sse) in double, inf for sse == 0 (host side, no device)."""
+    return lib().snnhip_frame_metrics_psnr(int(sse), int(pixels), int(maxval))
 
 
 def deconv2d_plan(ctx, N, H, W, w_oihw, bias=None, stride=2, same=True, act="", leaky=0.0, bn=None):

@@ -33,6 +33,9 @@ SIGNATURES = {
     "snn_model_download_frame_u16": (C.c_int, [_P, _P]),
     "snn_model_upload_frame_u8": (C.c_int, [_P, _P]),
     "snn_model_download_frame_u8": (C.c_int, [_P, _P]),
+    "snn_model_reference_frame": (C.c_int, [_P, _P]),
+    "snn_model_reference_frame_planes": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
+    "snn_model_frame_metrics": (C.c_int, [_P, _P, C.c_int]),
     "snn_model_batch": (C.c_int, [_P]),
     "snn_model_hip_ctx": (_P, [_P]),
     "snn_model_output_tensor": (_P, [_P]),
@@ -75,6 +78,11 @@ SIGNATURES = {
     "snn_frames_resolve": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "snn_dump_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int * 4), _FP, C.c_long]),
 }
+
+
+class FrameMetrics(C.Structure):  # snn_frame_metrics
+    _fields_ = [("image", C.c_int), ("plane", C.c_int), ("channel", C.c_int), ("sse", C.c_ulonglong), ("pixels", C.c_ulonglong), ("psnr_db", C.c_double),
+                ("ssim", C.c_double)]
 
 
 def lib():
@@ -392,6 +400,50 @@ class Model:
         y, cb, cr = np.empty((n, oh, ow), dt), np.empty((n, oh // 2, ow // 2), dt), np.empty((n, oh // 2, ow // 2), dt)
         self.download_planes([a[i] for i in range(n) for a in (y, cb, cr)])
         return (y[0], cb[0], cr[0]) if n == 1 else (y, cb, cr)
+
+    def _output_extent(self):
+        d = (C.c_int * 3)()
+        lib().snn_model_output_dims(self.h, C.byref(d))
+        return (self.out_size[1], self.out_size[0]) if self.out_size is not None else (d[0], d[1]), d[2]
+
+    def set_reference(self, ref):
+        """The ground-truth frame metrics() compares the output against, at the OUTPUT's extent, mirroring upload_frame / upload_planes: one array
+        [batch x] H x W x C for a packed output frame (snn_model_reference_frame); the pair (y, cbcr) for an NV12 / P010 output, the triple (y, cb,
+        cr) for a planar one; or batch * n_planes 2-D arrays with any row pitch, frame by frame, as upload_planes takes them
+        (snn_model_reference_frame_planes).  Kept on the device; a later call replaces it."""
+        dt, n = self.frame_dtypes[1], self.batch
+        (oh, ow), oc = self._output_extent()
+        if self.out_end != "yuv":
+            assert isinstance(ref, np.ndarray), "a packed output frame takes one array [batch x] H x W x C"
+            ref = np.ascontiguousarray(ref, dtype=dt)
+            assert ref.size == n * oh * ow * (self.out_channels or oc), "the reference has the output frame's extent: %d x %d x %d" % (oh, ow, self.out_channels or oc)
+            assert lib().snn_model_reference_frame(self.h, ref.ctypes.data_as(_P)) == 0, "snn_model_reference_frame refused (see the log)"
+            return
+        parts = list(ref)
+        k = 3 if self.planar else 2
+        if len(parts) == n * k and all(isinstance(a, np.ndarray) and a.ndim == 2 for a in parts):  # plane arrays, any pitch
+            ptrs, pitches, k, keep = self._plane_args(parts, dt)
+            assert lib().snn_model_reference_frame_planes(self.h, ptrs, pitches, k) == 0, "snn_model_reference_frame_planes refused (see the log)"
+            del keep
+            return
+        assert len(parts) == k, "an %s output takes %s" % ("I420 / I010" if self.planar else "NV12 / P010", "(y, cb, cr)" if self.planar else "(y, cbcr)")
+        if self.planar:
+            y, cb, cr = (np.ascontiguousarray(a, dtype=dt).reshape(n, hh, ww) for a, (hh, ww) in zip(parts, ((oh, ow), (oh // 2, ow // 2), (oh // 2, ow // 2))))
+            return self.set_reference([a[i] for i in range(n) for a in (y, cb, cr)])
+        y = np.ascontiguousarray(parts[0], dtype=dt).reshape(n, oh * ow)
+        cbcr = np.ascontiguousarray(parts[1], dtype=dt).reshape(n, (oh // 2) * ow)
+        frames = np.ascontiguousarray(np.concatenate([y, cbcr], axis=1))
+        assert lib().snn_model_reference_frame(self.h, frames.ctypes.data_as(_P)) == 0, "snn_model_reference_frame refused (see the log)"
+
+    def metrics(self):
+        """snn_model_frame_metrics: PSNR and SSIM of the last run's output frame against the reference, computed on the device.  One dict {image,
+        plane, channel, sse, pixels, psnr_db, ssim} per (image, plane, channel), image-major; plane 0 is the frame (or its luma plane), a video
+        output's chroma follows as plane 1 with channels 0 / 1 (NV12 / P010) or planes 1 / 2 (I420 / I010)."""
+        cap = self.batch * 8
+        rows = (FrameMetrics * cap)()
+        n = lib().snn_model_frame_metrics(self.h, rows, cap)
+        assert n >= 0, "snn_model_frame_metrics refused: no reference set, or the output is a float tensor (see the log)"
+        return [{f: getattr(r, f) for f, _ in FrameMetrics._fields_} for r in rows[:n]]
 
     def upload(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.in_shape)

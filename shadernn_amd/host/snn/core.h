@@ -90,6 +90,7 @@ public:
     snnhip_tensor* chromaOutput() const;
     bool planarVideo() const;  // the chroma tensors are planar [2 * batch][h][w][1] (snn_model_create12)
     bool encodeOutput() const; // the output is the NV12 frame of snn_model_create10: frameOutput() its luma plane, chromaOutput() its CbCr plane
+    const FrameSpec& frames() const { return cp.frames; } // the resolved description the model was built from (snn_model_reference_frame reads the output's depth)
 
 private:
     GpuContext* context;

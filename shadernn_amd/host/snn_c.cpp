@@ -24,6 +24,15 @@ struct snn_model {
     bool half = false;
     SNNModelOutput modelOutput;
     std::vector<char> staging; // host buffer of snn_model_upload_frame_planes / _download_frame_planes for planes that are not tight and adjacent
+    // frame quality against a ground-truth frame (snn_model_reference_frame / _frame_metrics): one per output plane tensor, made by the first reference
+    struct MetricsEnd {
+        snnhip_tensor* ref = nullptr;    // the reference plane(s), the output tensor's extent and dtype
+        snnhip_tensor* result = nullptr; // F32 [n][1][c][2], the plan's own output
+        snnhip_plan* plan = nullptr;
+        int maxval = 255;
+    };
+    MetricsEnd metricsFrame, metricsChroma; // the output frame (or its luma plane), the chroma plane(s) of a video output
+    bool referenceSet = false;
 };
 
 static dp::ShaderGenOptions makeOptions(int w, int h, int c, bool fuse, bool half = false, int batch = 1) {
@@ -218,10 +227,8 @@ static int movePieces(snn_model* m, snnhip_tensor* t, const std::vector<char*>& 
     return upload ? (snnhip_tensor_upload_raw(t, s, total) == SNNHIP_OK ? 0 : -1) : 0;
 }
 
-static int moveFramePlanes(snn_model* m, void* const* planes, const int* pitch, int n_planes, bool upload) {
-    if (!m || !planes || !pitch || !m->core) return -1;
-    snnhip_tensor* y = upload ? m->core->frameInput() : m->core->frameOutput();
-    snnhip_tensor* c = upload ? m->core->chromaInput() : m->core->chromaOutput();
+// ... between the caller's planes and the luma tensor y and chroma tensor c of one end of the model (or the reference tensors of that extent)
+static int movePlanesOf(snn_model* m, snnhip_tensor* y, snnhip_tensor* c, void* const* planes, const int* pitch, int n_planes, bool upload) {
     if (!y || !c) return -1; // an RGB end, or no video frames at all
     const bool planar = m->core->planarVideo();
     if (n_planes != (planar ? 3 : 2)) return -1;
@@ -252,6 +259,11 @@ static int moveFramePlanes(snn_model* m, void* const* planes, const int* pitch, 
     }
 }
 
+static int moveFramePlanes(snn_model* m, void* const* planes, const int* pitch, int n_planes, bool upload) {
+    if (!m || !planes || !pitch || !m->core) return -1;
+    return movePlanesOf(m, upload ? m->core->frameInput() : m->core->frameOutput(), upload ? m->core->chromaInput() : m->core->chromaOutput(), planes, pitch, n_planes, upload);
+}
+
 int snn_model_upload_frame_planes(snn_model* m, const void* const* planes, const int* pitch_bytes, int n_planes) {
     return moveFramePlanes(m, const_cast<void* const*>(planes), pitch_bytes, n_planes, true);
 }
@@ -260,8 +272,17 @@ int snn_model_download_frame_planes(snn_model* m, void* const* planes, const int
     return moveFramePlanes(m, planes, pitch_bytes, n_planes, false);
 }
 
+static void freeMetrics(snn_model::MetricsEnd& e) {
+    if (e.plan) snnhip_plan_destroy(e.plan);
+    if (e.ref) snnhip_tensor_free(e.ref);
+    if (e.result) snnhip_tensor_free(e.result);
+    e = snn_model::MetricsEnd();
+}
+
 int snn_model_destroy(snn_model* m) {
     if (!m) return 0;
+    freeMetrics(m->metricsFrame); // (before the context goes: they live on its device)
+    freeMetrics(m->metricsChroma);
     m->core.reset();
     m->inputs = ImageTextureArray(nullptr);
     m->outputs = ImageTextureArray(nullptr);
@@ -293,6 +314,143 @@ int snn_model_download_frame_u16(snn_model* m, unsigned short* nhwc) {
     snnhip_tensor* t = m && nhwc ? m->core->frameOutput() : nullptr;
     if (!t || snnhip_tensor_dtype(t) != SNNHIP_U16) return -1;
     return snnhip_tensor_download_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
+}
+
+// the reference tensor, the metrics plan and its result tensor for one output plane tensor `out`
+static int makeMetricsEnd(snnhip_ctx* ctx, snnhip_tensor* out, int maxval, int shift, snn_model::MetricsEnd* e) {
+    int d[4];
+    if (snnhip_tensor_dims(out, d) != SNNHIP_OK) return -1;
+    const int dtype = snnhip_tensor_dtype(out);
+    snnhip_frame_metrics_desc desc{d[0], d[1], d[2], d[3], dtype, dtype == SNNHIP_U8 ? 255 : maxval, dtype == SNNHIP_U8 ? 0 : shift};
+    if (snnhip_frame_metrics_plan_create(ctx, &desc, &e->plan) != SNNHIP_OK || snnhip_tensor_alloc(ctx, d[0], d[1], d[2], d[3], dtype, &e->ref) != SNNHIP_OK ||
+        snnhip_tensor_alloc(ctx, d[0], 1, d[3], 2, SNNHIP_F32, &e->result) != SNNHIP_OK) {
+        SNN_LOGE("snn_model_reference_frame: %s", snnhip_last_error());
+        freeMetrics(*e);
+        return -1;
+    }
+    e->maxval = desc.maxval;
+    return 0;
+}
+
+// the first reference of a model allocates what its metrics need; false (logged) on a model whose output is a float tensor
+static bool ensureMetrics(snn_model* m, const char* who) {
+    snnhip_tensor* y = m->core->frameOutput();
+    if (!y) {
+        SNN_LOGE("%s: the model's output is a float tensor: frame metrics compare 8- / 16-bit output frames (create the model with an output frame format)", who);
+        return false;
+    }
+    if (m->metricsFrame.plan) return true;
+    snnhip_ctx* ctx = snn_model_hip_ctx(m);
+    if (!ctx) return false;
+    const FrameSpec& f = m->core->frames();
+    // the depth of the output frame: the video end's for an RGB frame made from it, otherwise the model's own output map (the luma plane's on a video end)
+    const bool fromVideo = f.sink == FrameSpec::Sink::RGB_FROM_YUV;
+    if (makeMetricsEnd(ctx, y, fromVideo ? f.maxval : f.model.out_maxval, fromVideo ? f.shift : f.model.out_shift, &m->metricsFrame) != 0) return false;
+    snnhip_tensor* c = m->core->chromaOutput();
+    if (c && makeMetricsEnd(ctx, c, f.maxval, f.shift, &m->metricsChroma) != 0) {
+        freeMetrics(m->metricsFrame);
+        return false;
+    }
+    return true;
+}
+
+int snn_model_reference_frame(snn_model* m, const void* frame) {
+    if (!m || !frame || !m->core) {
+        SNN_LOGE("snn_model_reference_frame: null argument");
+        return -1;
+    }
+    try {
+        if (!ensureMetrics(m, "snn_model_reference_frame")) return -1;
+        snnhip_tensor* y = m->metricsFrame.ref;
+        snnhip_tensor* c = m->metricsChroma.ref;
+        if (!c) return snnhip_tensor_upload_raw(y, frame, snnhip_tensor_bytes(y)) == SNNHIP_OK ? (m->referenceSet = true, 0) : -1;
+        if (m->core->planarVideo()) {
+            SNN_LOGE("snn_model_reference_frame: a planar output takes its reference through snn_model_reference_frame_planes, as it is downloaded");
+            return -1;
+        }
+        // the layout of snn_model_download_frame_nv12: `batch` frames, each the luma plane followed by the interleaved chroma plane
+        const size_t yb = snnhip_tensor_bytes(y) / static_cast<size_t>(m->batch), cb = snnhip_tensor_bytes(c) / static_cast<size_t>(m->batch);
+        char* p = static_cast<char*>(const_cast<void*>(frame));
+        if (movePlane(y, m->batch, p, yb + cb, 0, true) != 0 || movePlane(c, m->batch, p, yb + cb, yb, true) != 0) return -1;
+        m->referenceSet = true;
+        return 0;
+    } catch (...) { // (std::bad_alloc of a staging buffer)
+        return -2;
+    }
+}
+
+int snn_model_reference_frame_planes(snn_model* m, const void* const* planes, const int* pitch_bytes, int n_planes) {
+    if (!m || !planes || !pitch_bytes || !m->core) {
+        SNN_LOGE("snn_model_reference_frame_planes: null argument");
+        return -1;
+    }
+    try {
+        if (!ensureMetrics(m, "snn_model_reference_frame_planes")) return -1;
+        const int rc = movePlanesOf(m, m->metricsFrame.ref, m->metricsChroma.ref, const_cast<void* const*>(planes), pitch_bytes, n_planes, true);
+        if (rc == 0) m->referenceSet = true;
+        return rc;
+    } catch (...) {
+        return -2;
+    }
+}
+
+int snn_model_frame_metrics(snn_model* m, snn_frame_metrics* rows, int max_rows) {
+    if (!m || !rows || !m->core) {
+        SNN_LOGE("snn_model_frame_metrics: null argument");
+        return -1;
+    }
+    if (!m->referenceSet) {
+        SNN_LOGE("snn_model_frame_metrics: no reference frame was set (snn_model_reference_frame / _frame_planes)");
+        return -1;
+    }
+    try {
+        const snn_model::MetricsEnd* ends[2] = {&m->metricsFrame, &m->metricsChroma};
+        snnhip_tensor* outs[2] = {m->core->frameOutput(), m->core->chromaOutput()};
+        std::vector<snnhip_frame_metrics_row> got[2];
+        int dims[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        // both plans go onto the model's stream behind its last run, outside the recorded graph; the reads wait for them
+        for (int e = 0; e < 2; ++e) {
+            if (!ends[e]->plan) continue;
+            const snnhip_tensor* in[2] = {outs[e], ends[e]->ref};
+            if (!outs[e] || snnhip_plan_run_n(ends[e]->plan, in, 2, ends[e]->result) != SNNHIP_OK) {
+                SNN_LOGE("snn_model_frame_metrics: %s", snnhip_last_error());
+                return -1;
+            }
+        }
+        for (int e = 0; e < 2; ++e) {
+            if (!ends[e]->plan) continue;
+            snnhip_tensor_dims(ends[e]->ref, dims[e]);
+            got[e].resize(static_cast<size_t>(dims[e][0]) * dims[e][3]);
+            if (snnhip_frame_metrics_read(ends[e]->plan, got[e].data(), static_cast<int>(got[e].size())) != static_cast<int>(got[e].size())) {
+                SNN_LOGE("snn_model_frame_metrics: %s", snnhip_last_error());
+                return -1;
+            }
+        }
+        // image-major: the frame's (or luma plane's) channels, then the chroma plane's channels (interleaved: one plane, two channels; planar: plane
+        // 2n is Cb and 2n + 1 Cr of image n, one channel each)
+        const bool planar = m->core->planarVideo();
+        int n = 0;
+        auto put = [&](int image, int plane, int channel, const snnhip_frame_metrics_row& r, int maxval) {
+            if (n < max_rows) rows[n] = snn_frame_metrics{image, plane, channel, r.sse, r.pixels, snnhip_frame_metrics_psnr(r.sse, r.pixels, maxval),
+                                                          r.ssim_sum / static_cast<double>(r.windows)};
+            ++n;
+        };
+        for (int image = 0; image < m->batch; ++image) {
+            for (int c = 0; c < dims[0][3]; ++c) put(image, 0, c, got[0][static_cast<size_t>(image) * dims[0][3] + c], ends[0]->maxval);
+            if (!ends[1]->plan) continue;
+            if (planar)
+                for (int p = 0; p < 2; ++p) put(image, 1 + p, 0, got[1][static_cast<size_t>(2 * image + p)], ends[1]->maxval);
+            else
+                for (int c = 0; c < dims[1][3]; ++c) put(image, 1, c, got[1][static_cast<size_t>(image) * dims[1][3] + c], ends[1]->maxval);
+        }
+        if (n > max_rows) {
+            SNN_LOGE("snn_model_frame_metrics: room for %d rows, the model's output has %d", max_rows, n);
+            return -1;
+        }
+        return n;
+    } catch (...) {
+        return -2;
+    }
 }
 
 int snn_model_upload_input(snn_model* m, const float* nhwc) {

@@ -100,6 +100,15 @@ file under the key <format>[_<out>]_<in>_x<r>[_<fit>]: profiles/espcn_planar_fra
 1080p.
 
     python tools/bench_frames.py --video I420 --video-out RGB8 --scale 2 --out profiles/espcn_planar_frames.json
+
+--metrics [--half]: frame metrics on the device.  For the 4K U8 luma plane (x2 from 1080p), an NV12 frame and an RGB8
+frame of that size, in one process and mirrored: metrics (the frame_metrics launches alone, device events), copy (one hipMemcpyDtoDAsync of the
+frame's bytes: it moves through HBM what the launches read), d2h (the download of the frame, what a user without the plan has to do; host clock)
+and metrics_read (launches plus the read of the rows; host clock).  The condition recorded with them: the metrics launches take less time than the
+download measured in the same run.  With --half also PSNR and SSIM of the fused fp16 chain's 8-bit output against the fused fp32 chain's on the
+seeded input.  --out FILE merges the record under the key metrics_<H>x<W>[_half]: profiles/espcn_metrics_frames.json.
+
+    python tools/bench_frames.py --metrics --half --out profiles/espcn_metrics_frames.json
 """
 import argparse
 import json
@@ -1122,9 +1131,166 @@ def main_planar(a):
     ctx.close()
 
 
+def main_metrics(a):
+    """--metrics: frame metrics (PSNR / SSIM on the device) against what a user without them has to do, a download of the frame.  For the 4K U8 luma
+    plane, an NV12 frame and an RGB8 frame: the metrics launches alone, a device copy of the same bytes and the device-to-host copy of the frame, in
+    one process, mirrored; with --half also the quality of the fused fp16 chain's 8-bit output against the fused fp32 chain's."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R = a.scale
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    OH, OW = R * H, R * W
+    assert OH % 2 == 0 and OW % 2 == 0, "4:2:0 frames have even extents"
+    rng = np.random.default_rng(1)
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+
+    def noisy(shape):  # a frame and a copy a few grey levels away: what is measured does not depend on the values
+        ref = rng.integers(0, 256, size=shape, dtype=np.uint8)
+        return np.clip(ref.astype(np.int16) + rng.integers(-3, 4, size=shape), 0, 255).astype(np.uint8), ref
+
+    planes = {"luma": [(1, OH, OW, 1)], "nv12": [(1, OH, OW, 1), (1, OH // 2, OW // 2, 2)], "rgb8": [(1, OH, OW, 3)]}
+    forms, recs, d2h = {}, {}, {}
+    for fmt, shapes in planes.items():
+        parts = []
+        for shp in shapes:
+            t, r = noisy(shp)
+            parts.append(dict(plan=capi.frame_metrics_plan(ctx, *shp), a=capi.Tensor.from_numpy(ctx, t, dtype=capi.U8), b=capi.Tensor.from_numpy(ctx, r, dtype=capi.U8),
+                              out=capi.Tensor(ctx, shp[0], 1, shp[3], 2), host=np.empty(shp, np.uint8), bytes=int(np.prod(shp))))
+        frame_bytes = sum(p["bytes"] for p in parts)
+        src, dst = capi.Tensor(ctx, 1, 1, frame_bytes, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, frame_bytes, 1, dtype=capi.U8)
+        src.upload_u8(rng.integers(0, 256, size=frame_bytes, dtype=np.uint8))
+
+        def run_metrics(parts=parts):
+            for p in parts:
+                p["plan"].run([p["a"], p["b"]], p["out"])
+
+        def run_copy(src=src, dst=dst, n=frame_bytes):  # reads n bytes and writes n: the 2 n bytes the metrics launches read
+            rc = hip.hipMemcpyDtoDAsync(dst.data_ptr(), src.data_ptr(), n, stream)
+            assert rc == 0, rc
+
+        def run_d2h(parts=parts):  # what a user without the plan does: the output frame over the host link
+            for p in parts:
+                capi.check(capi.lib().snnhip_tensor_download_raw(p["a"].h, p["host"].ctypes.data_as(capi._P), p["host"].nbytes))
+
+        def run_read(parts=parts):  # the metrics launches and the read of their rows (a sync and N * C * 32 bytes)
+            for p in parts:
+                p["plan"].run([p["a"], p["b"]], p["out"])
+            return [capi.frame_metrics_read(p["plan"]) for p in parts]
+
+        forms[fmt + ":metrics"], forms[fmt + ":copy"] = run_metrics, run_copy
+        d2h[fmt + ":d2h"], d2h[fmt + ":metrics_read"] = run_d2h, run_read
+        recs[fmt] = dict(parts=parts, frame_bytes=frame_bytes, read=run_read)
+    for f in list(forms.values()) + list(d2h.values()):
+        for _ in range(a.warmup):
+            f()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {k: [] for k in forms}
+    host = {k: [] for k in d2h}
+    for _ in range(a.rounds):
+        for k in list(forms) + list(forms)[::-1]:  # mirrored, device events around `iters` enqueued runs
+            timer.start()
+            for _ in range(a.iters):
+                forms[k]()
+            timer.stop()
+            dev[k].append(timer.elapsed_ms() / a.iters)
+        for k in list(d2h) + list(d2h)[::-1]:  # host clock around work that ends in a synchronise (both forms wait for the device every frame)
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                d2h[k]()
+            host[k].append((time.perf_counter() - t0) * 1e3 / a.iters)
+
+    def stat(v):
+        m = statistics.median(v)
+        return {"ms_median": round(m, 5), "ms_min": round(min(v), 5), "ms_max": round(max(v), 5), "spread": round((max(v) - min(v)) / m, 4)}
+
+    out = {"frame": "%dx%d" % (OH, OW), "rounds": a.rounds, "iters": a.iters, "timing": "metrics / copy: device events around iters enqueued runs; d2h / metrics_read: host clock, every frame ends in a synchronise"}
+    for fmt, rec in recs.items():
+        o = {"frame_bytes": rec["frame_bytes"], "metrics": stat(dev[fmt + ":metrics"]), "copy": stat(dev[fmt + ":copy"]), "d2h": stat(host[fmt + ":d2h"]),
+             "metrics_read": stat(host[fmt + ":metrics_read"]), "steps": [p["plan"].describe() for p in rec["parts"]]}
+        m, c, d = o["metrics"]["ms_median"], o["copy"]["ms_median"], o["d2h"]["ms_median"]
+        o["metrics_hbm_bytes"] = int(sum(p["plan"].cost()[1] for p in rec["parts"]))
+        o["metrics_tbs"] = round(o["metrics_hbm_bytes"] / (m * 1e-3) / 1e12, 3)
+        o["copy_hbm_bytes"] = 2 * rec["frame_bytes"]
+        o["copy_tbs"] = round(o["copy_hbm_bytes"] / (c * 1e-3) / 1e12, 3)
+        o["d2h_gbs"] = round(rec["frame_bytes"] / (d * 1e-3) / 1e9, 2)
+        o["metrics_over_copy"] = round(m / c, 3)         # a finding, not a gate
+        o["metrics_over_d2h"] = round(m / d, 4)          # the condition: below 1
+        o["metrics_read_over_d2h"] = round(o["metrics_read"]["ms_median"] / d, 4)
+        o["condition_metrics_faster_than_d2h"] = bool(m < d and o["metrics"]["ms_max"] < o["d2h"]["ms_min"])
+        capi.trace_begin()
+        for _ in range(a.iters):
+            forms[fmt + ":metrics"]()
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        o["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                         "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+        rows = rec["read"]()
+        o["rows"] = [{"psnr_db": round(capi.frame_metrics_psnr(r["sse"], r["pixels"], 255), 4), "ssim": round(r["ssim"], 6)} for part in rows for r in part]
+        out[fmt] = o
+    out["spread_max"] = max(out[f][k]["spread"] for f in recs for k in ("metrics", "copy", "d2h", "metrics_read"))
+    out["condition_met"] = all(out[f]["condition_metrics_faster_than_d2h"] for f in recs)
+
+    if a.half:  # what the fp16 opt-in costs in picture quality: its 8-bit output against the fused fp32 chain's, same weights, same seeded input
+        net = models.espcn_weights(seed=1, scale=R)
+        u8 = np.random.default_rng(1).integers(0, 256, size=(1, H, W, 1), dtype=np.uint8)
+
+        def chain(dtype):
+            layers, shape = [], (1, H, W, 1)
+            for layer in net["layers"]:
+                p = _layer_plan(ctx, layer, shape, dtype)
+                layers.append(p)
+                shape = p.out_shape()
+            ends = [capi.u8_in_plan(ctx, 1, H, W, 1, (127.5, 0, 0, 0), (1 / 127.5, 1, 1, 1), dtype=dtype)] + layers + [capi.u8_out_plan(ctx, *shape, (127.5, 0, 0, 0), (127.5, 0, 0, 0), dtype=dtype)]
+            c = capi.chain_plan(ctx, ends)
+            assert c.num_steps() == 2, c.describe()
+            return c, shape
+
+        c32, shape = chain(capi.F32)
+        capi.set_option("SNNHIP_ESPCN_F16", "1")
+        try:
+            c16, _ = chain(capi.F16)
+        finally:
+            capi.set_option("SNNHIP_ESPCN_F16", None)
+        x = capi.Tensor.from_numpy(ctx, u8, dtype=capi.U8)
+        y32, y16 = capi.Tensor(ctx, *shape, dtype=capi.U8), capi.Tensor(ctx, *shape, dtype=capi.U8)
+        c32.run(x, y32)
+        c16.run(x, y16)
+        plan = capi.frame_metrics_plan(ctx, *shape)
+        res = capi.Tensor(ctx, shape[0], 1, shape[3], 2)
+        plan.run([y16, y32], res)  # test: fp16, reference: fp32
+        row = capi.frame_metrics_read(plan)[0]
+        h16, h32 = y16.numpy_u8().astype(np.int16), y32.numpy_u8().astype(np.int16)
+        diff = np.abs(h16 - h32)
+        out["f16_vs_f32"] = {"input": "seeded uniform noise, %dx%d, U8" % (H, W), "test": c16.describe(), "reference": c32.describe(), "sse": row["sse"], "pixels": row["pixels"],
+                             "psnr_db": capi.frame_metrics_psnr(row["sse"], row["pixels"], 255), "ssim": row["ssim"],
+                             "host_check_sse": int((diff.astype(np.int64) ** 2).sum()), "bytes_that_differ": int((diff > 0).sum()), "max_abs_difference": int(diff.max())}
+        assert out["f16_vs_f32"]["host_check_sse"] == row["sse"]
+    print(json.dumps(out, indent=1))
+    if a.out:
+        rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        rec["metrics_%dx%d%s" % (OH, OW, "_half" if a.half else "")] = out
+        with open(a.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
+    ap.add_argument("--metrics", action="store_true", help="frame metrics on the device against a device copy and a download of the same frame (4K luma, NV12, RGB8); with --half also PSNR / SSIM of the fused fp16 chain's 8-bit output against the fused fp32 chain's")
     ap.add_argument("--widths", default="16,16", metavar="C1,C2", help="with --half: the ESPCN's channel widths; 64,32 is the net as published (per-layer fp16, fused fp16, fused fp16 with 8-bit ends)")
     ap.add_argument("--f16-mfma-tflops", type=float, default=2500.0, help="with --half: the f16 matrix peak the fused steps' issued MFMA flops are held against, TFLOP/s")
     ap.add_argument("--scale", type=int, default=2, choices=[2, 3, 4], help="upscale factor; the input size follows it (output 3840 x 2160) unless --h / --w are given")
@@ -1146,6 +1312,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
+    if a.metrics:
+        return main_metrics(a)
     if a.video in ("I420", "I010") or a.video_out == "I420":
         assert (a.video_out == "I420") == bool(a.colour) and not (a.colour and a.video), "--video I420 | I010 [--video-out RGB8 | RGBA8] [--fit WxH], or --colour ... --video-out I420"
         assert not (a.fit and a.video_out), "--fit goes with --video alone"

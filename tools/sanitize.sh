@@ -1,6 +1,7 @@
 #!/bin/bash
 # Host-side checker target (SURVEY section 5 "Race detection / sanitizers": the reference has none, core/CMakeLists.txt:235).
 #   tools/sanitize.sh            builds lib/libsnn_core_asan.so (-fsanitize=address,undefined) and runs the CPU suite's host tests against it
+#   tools/sanitize.sh checks     builds the same library and runs every tools/*_host_check.cpp against it as a stand-alone ASan + UBSan program
 #   tools/sanitize.sh gpu        on a GPU box: the smoke test + the host-mirror GPU tests under the same library, plus the kernels under
 #                                AMD_LOG_LEVEL=1 HSA_ENABLE_DEBUG=1 (out-of-bounds accesses of a kernel show up as a memory-access fault that aborts the run)
 #   tools/sanitize.sh guard      on a GPU box: the device-side guard mode (SNNHIP_GUARD=1, include/snnhip.h: red zones of 0xFF around every device allocation,
@@ -17,6 +18,18 @@ if [ "${1:-cpu}" = "guard" ]; then
   exit 0
 fi
 python -c "import __graft_entry__ as g; g.build_hip(); g.build_host(); print(g.build_host(sanitize='address,undefined'))"
+if [ "${1:-cpu}" = "checks" ]; then
+  # the stand-alone host-check programs (tools/*_host_check.cpp: device-free paths of the frame features, each with its own main), built with the
+  # sanitizers and linked against lib/libsnn_core_asan.so; nothing is preloaded, nothing runs inside python
+  mkdir -p build
+  for src in tools/*_host_check.cpp; do
+    name=$(basename "$src" .cpp)
+    g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -Iinclude -Ishadernn_amd/host "$src" -o "build/$name" \
+        -Lshadernn_amd/lib -lsnn_core_asan -lsnnhip -Wl,-rpath,"$PWD/shadernn_amd/lib" -Wl,-rpath,/opt/rocm/lib
+    ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 "build/$name"
+  done
+  exit 0
+fi
 ASAN=$(gcc -print-file-name=libasan.so); UBSAN=$(gcc -print-file-name=libubsan.so)
 export LD_PRELOAD="$ASAN:$UBSAN" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:protect_shadow_gap=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
 export SNN_CORE_LIB_PATH="$PWD/shadernn_amd/lib/libsnn_core_asan.so"
