@@ -82,9 +82,9 @@ bool behind_other_head(const ConvPlanBase* h0, const ConvPlanBase* h1, const Esp
     const EspcnWidths head = conv_pair_widths(h0, h1, SNNHIP_F16);
     return head.c1 != 0 && !(head == want);
 }
-void rename_kernel(std::string& desc, const char* from, const char* to) {
+void rename_kernel(std::string& desc, const std::string& from, const std::string& to) {
     const size_t at = desc.find(from);
-    if (at != std::string::npos) desc.replace(at, strlen(from), to);
+    if (at != std::string::npos) desc.replace(at, from.size(), to);
 }
 
 // Chain rule F: Conv2D -> InstanceNorm.  The convolution (conv2d_mfma, fp16 LDS epilogue) leaves (mean, M2) of every output tile and channel
@@ -120,186 +120,95 @@ struct FusedLaunch {
     virtual int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const = 0;
     // true: the launch takes a dispatch-stamped event pair (snnhip_plan::profAcquire); false: the chain brackets it (profBegin / profEnd)
     virtual bool stampsItsEvents() const { return true; }
-    // An 8-bit frame conversion next to this launch moves into it: the family takes the conversion's parameters and rewrites its own
-    // description.  false = this family (or the form selected) keeps the separate launch.
-    virtual bool foldU8In(const snnhip_u8_in_desc&, std::string&) { return false; }
-    virtual bool foldU8Out(const snnhip_u8_out_desc&, std::string&) { return false; }
-    // the same for the 16-bit frame conversions
-    virtual bool foldU16In(const snnhip_u16_in_desc&, std::string&) { return false; }
-    virtual bool foldU16Out(const snnhip_u16_out_desc&, std::string&) { return false; }
+    // A frame conversion (8- or 16-bit, to / from tensors of `dtype`) next to this launch moves into it: the family keeps the frame end and renames
+    // its kernel in its description.  false = this family (or the form selected) keeps the separate launch.
+    virtual bool foldIn(const FrameIn&, int /*dtype*/, std::string& /*desc*/) { return false; }
+    virtual bool foldOut(const FrameOut&, int /*dtype*/, std::string& /*desc*/) { return false; }
 };
 
-struct FusedA : FusedLaunch { // rules A / A8
+// A family's kernel under its three frame ends, as its description spells it (tests and launch traces know these names): the launch's own tensor
+// type, an 8-bit frame, a 16-bit frame.  DESIGN.md section 4.23 has the table.
+struct FrameKernels {
+    std::string plain, u8, u16;
+};
+// What every fold checks and does: the conversion is of the launch's tensor type, the end is not folded yet, and the family's form takes frames
+// (the predicate next to its launch function).
+template <class Frame>
+bool fold_frame(Frame& end, const Frame& f, bool sameType, bool takesFrame, const FrameKernels& k, std::string& desc) {
+    if (!sameType || end.bits || !takesFrame) return false;
+    end = f;
+    rename_kernel(desc, "kernel=" + k.plain, "kernel=" + (f.bits == 16 ? k.u16 : k.u8));
+    return true;
+}
+
+struct FusedA : FusedLaunch { // rule A and its frame forms A8 / A16-bit (SNNHIP_ESPCN_A=direct keeps the conversion's own launch)
     FusedAParams p{};
     int k1 = 5;
-    bool wino = true, u8in = false, u16in = false;
-    U8InCfg qin{0.0f, 0.0f};
-    U16InCfg qin16{0.0f, 0.0f, 0};
+    bool wino = true;
+    FrameIn frame;
     float *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
-        if (u16in)
-            return espcn_fused_a_u16_launch(ctx->stream, p, k1, qin16, ctx->props.multiProcessorCount, reinterpret_cast<const unsigned short*>(x), w1, w2, e1, e2, y,
-                                            evStart, evStop);
-        return espcn_fused_a_launch(ctx->stream, p, k1, wino, u8in, qin, ctx->props.multiProcessorCount, x, w1, w2, e1, e2, y, evStart, evStop);
+        return espcn_fused_a_launch(ctx->stream, p, k1, wino, frame, ctx->props.multiProcessorCount, x, w1, w2, e1, e2, y, evStart, evStop);
     }
-    bool foldU8In(const snnhip_u8_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F32 || !wino || u8in || u16in) return false; // (SNNHIP_ESPCN_A=direct keeps the separate launch)
-        u8in = true;
-        qin = U8InCfg{ui.means[0], ui.norms[0]};
-        rename_kernel(desc, "kernel=conv_kxk_c1o16_wino3x3_c16o16_kernel", "kernel=conv_kxk_c1o16_wino3x3_c16o16_u8_kernel");
-        return true;
-    }
-    bool foldU16In(const snnhip_u16_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F32 || !wino || u8in || u16in) return false;
-        u16in = true;
-        qin16 = U16InCfg{ui.means[0], ui.norms[0], ui.shift};
-        rename_kernel(desc, "kernel=conv_kxk_c1o16_wino3x3_c16o16_kernel", "kernel=conv_kxk_c1o16_wino3x3_c16o16_u16_kernel");
-        return true;
+    bool foldIn(const FrameIn& f, int dtype, std::string& desc) override {
+        return fold_frame(frame, f, dtype == SNNHIP_F32, espcn_fused_a_takes_frame(wino),
+                          {"conv_kxk_c1o16_wino3x3_c16o16_kernel", "conv_kxk_c1o16_wino3x3_c16o16_u8_kernel", "conv_kxk_c1o16_wino3x3_c16o16_u16_kernel"}, desc);
     }
 };
 
-struct FusedB : FusedLaunch { // rules B / B8: upscale 2 on espcn_fused.hip's kernel B, 3 / 4 on the matrix-core kernel of espcn_d2s_mfma.hip
+struct FusedB : FusedLaunch { // rule B and its frame forms: upscale 2 on espcn_fused.hip's kernel B (SNNHIP_ESPCN_B=wino keeps the conversion's own
+                              // launch), 3 / 4 on the matrix-core kernel of espcn_d2s_mfma.hip
     FusedBParams p{};
     int r = 2;
-    bool wino = false, u8out = false, u16out = false;
-    U8OutCfg qout{0.0f, 0.0f};
-    U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
+    bool wino = false;
+    FrameOut frame;
     float *w = nullptr, *e = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
-        if (u16out && r == 2) return espcn_fused_b_u16_launch(ctx->stream, p, qout16, x, w, e, reinterpret_cast<unsigned short*>(y), evStart, evStop);
-        if (u16out) return espcn_d2s_mfma_u16_launch(ctx->stream, r, p, qout16, x, w, e, reinterpret_cast<unsigned short*>(y), evStart, evStop);
-        if (r == 2) return espcn_fused_b_launch(ctx->stream, p, wino, u8out, qout, x, w, e, y, evStart, evStop);
-        return espcn_d2s_mfma_launch(ctx->stream, r, p, u8out, qout.scale, qout.offset, x, w, e, y, evStart, evStop);
+        if (r == 2) return espcn_fused_b_launch(ctx->stream, p, wino, frame, x, w, e, y, evStart, evStop);
+        return espcn_d2s_mfma_launch(ctx->stream, r, p, frame, x, w, e, y, evStart, evStop);
     }
-    bool foldU8Out(const snnhip_u8_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F32 || wino || u8out || u16out) return false; // (SNNHIP_ESPCN_B=wino keeps the separate launch)
-        u8out = true;
-        qout = U8OutCfg{uo.scale[0], uo.offset[0]};
-        if (r == 2) rename_kernel(desc, "kernel=conv3x3_c16o4_d2s_tanh_kernel", "kernel=conv3x3_c16o4_d2s_tanh_u8_kernel");
-        else rename_kernel(desc, "kernel=conv3x3_c16oR_d2s_tanh_kernel", "kernel=conv3x3_c16oR_d2s_tanh_u8_kernel");
-        return true;
-    }
-    bool foldU16Out(const snnhip_u16_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F32 || wino || u8out || u16out) return false;
-        u16out = true;
-        qout16 = U16OutCfg{uo.scale[0], uo.offset[0], static_cast<float>(uo.maxval), uo.shift};
-        if (r == 2) rename_kernel(desc, "kernel=conv3x3_c16o4_d2s_tanh_kernel", "kernel=conv3x3_c16o4_d2s_tanh_u16_kernel");
-        else rename_kernel(desc, "kernel=conv3x3_c16oR_d2s_tanh_kernel", "kernel=conv3x3_c16oR_d2s_tanh_u16_kernel");
-        return true;
+    bool foldOut(const FrameOut& f, int dtype, std::string& desc) override {
+        if (r == 2)
+            return fold_frame(frame, f, dtype == SNNHIP_F32, espcn_fused_b_takes_frame(wino),
+                              {"conv3x3_c16o4_d2s_tanh_kernel", "conv3x3_c16o4_d2s_tanh_u8_kernel", "conv3x3_c16o4_d2s_tanh_u16_kernel"}, desc);
+        return fold_frame(frame, f, dtype == SNNHIP_F32, espcn_d2s_mfma_takes_frame(),
+                          {"conv3x3_c16oR_d2s_tanh_kernel", "conv3x3_c16oR_d2s_tanh_u8_kernel", "conv3x3_c16oR_d2s_tanh_u16_kernel"}, desc);
     }
 };
 
-struct FusedA16 : FusedLaunch { // rule A16 and its 8-bit form (espcn_f16.hip): w1, w2 hold halfs (espcn_f16_pack_w1 / _w3)
+// Rules A16 / B16 and their frame forms, narrow (espcn_f16.hip) or -- wide -- at the published widths (espcn_f16_wide.hip): the two units' launch
+// functions have one signature and their kernel names differ by the "wide_"; the weight buffers hold halfs (espcn_f16[_wide]_pack_w1 / _w3).
+struct FusedA16 : FusedLaunch {
     EspcnF16AParams p{};
     int k1 = 5;
-    bool u8in = false, u16in = false;
-    U16InCfg qin16{0.0f, 0.0f, 0};
+    bool wide = false;
+    FrameIn frame;
     float *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
-        if (u16in)
-            return espcn_f16_a_u16_launch(ctx->stream, k1, p, qin16, reinterpret_cast<const unsigned short*>(x), reinterpret_cast<const _Float16*>(w1),
-                                          reinterpret_cast<const _Float16*>(w2), e1, e2, reinterpret_cast<_Float16*>(y), evStart, evStop);
-        return espcn_f16_a_launch(ctx->stream, k1, p, u8in, x, reinterpret_cast<const _Float16*>(w1), reinterpret_cast<const _Float16*>(w2), e1, e2,
-                                  reinterpret_cast<_Float16*>(y), evStart, evStop);
+        return (wide ? espcn_f16_wide_a_launch : espcn_f16_a_launch)(ctx->stream, k1, p, frame, x, reinterpret_cast<const _Float16*>(w1),
+                                                                      reinterpret_cast<const _Float16*>(w2), e1, e2, reinterpret_cast<_Float16*>(y), evStart, evStop);
     }
-    bool foldU8In(const snnhip_u8_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F16 || u8in || u16in) return false;
-        u8in = true;
-        p.mean = ui.means[0];
-        p.norm = ui.norms[0];
-        rename_kernel(desc, "kernel=espcn_f16_conv_pair_kernel", "kernel=espcn_f16_conv_pair_kernel<u8>");
-        return true;
-    }
-    bool foldU16In(const snnhip_u16_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F16 || u8in || u16in) return false;
-        u16in = true;
-        qin16 = U16InCfg{ui.means[0], ui.norms[0], ui.shift};
-        rename_kernel(desc, "kernel=espcn_f16_conv_pair_kernel", "kernel=espcn_f16_conv_pair_u16_kernel");
-        return true;
+    bool foldIn(const FrameIn& f, int dtype, std::string& desc) override {
+        const std::string k = wide ? "espcn_f16_wide_conv_pair" : "espcn_f16_conv_pair";
+        return fold_frame(frame, f, dtype == SNNHIP_F16, wide ? espcn_f16_wide_takes_frame() : espcn_f16_takes_frame(),
+                          {k + "_kernel", k + "_kernel<u8>", k + "_u16_kernel"}, desc);
     }
 };
 
-struct FusedB16 : FusedLaunch { // rule B16 and its 8-bit form, upscale 2, 3 or 4 (espcn_f16.hip): w holds halfs
+struct FusedB16 : FusedLaunch { // upscale 2, 3 or 4
     EspcnF16BParams p{};
     int r = 2;
-    bool u8out = false, u16out = false;
-    U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
+    bool wide = false;
+    FrameOut frame;
     float *w = nullptr, *e = nullptr;
     int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
-        if (u16out)
-            return espcn_f16_b_u16_launch(ctx->stream, r, p, qout16, reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(w), e,
-                                          reinterpret_cast<unsigned short*>(y), evStart, evStop);
-        return espcn_f16_b_launch(ctx->stream, r, p, u8out, reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(w), e, y, evStart,
-                                  evStop);
+        return (wide ? espcn_f16_wide_b_launch : espcn_f16_b_launch)(ctx->stream, r, p, frame, reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(w), e,
+                                                                      y, evStart, evStop);
     }
-    bool foldU8Out(const snnhip_u8_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F16 || u8out || u16out) return false;
-        u8out = true;
-        p.qscale = uo.scale[0];
-        p.qoffset = uo.offset[0];
-        const size_t at = desc.find(">", desc.find("kernel=espcn_f16_d2s_kernel<"));
-        if (at != std::string::npos) desc.insert(at, ",u8");
-        return true;
-    }
-    bool foldU16Out(const snnhip_u16_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F16 || u8out || u16out) return false;
-        u16out = true;
-        qout16 = U16OutCfg{uo.scale[0], uo.offset[0], static_cast<float>(uo.maxval), uo.shift};
-        rename_kernel(desc, "kernel=espcn_f16_d2s_kernel", "kernel=espcn_f16_d2s_u16_kernel");
-        return true;
-    }
-};
-
-struct FusedA16Wide : FusedLaunch { // rule A16 wide and its frame forms (espcn_f16_wide.hip): w1, w2 hold halfs (espcn_f16_wide_pack_w1 / _w3)
-    EspcnF16AParams p{};
-    int k1 = 5, frameBits = 0;
-    U16InCfg qin16{0.0f, 0.0f, 0};
-    float *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr;
-    int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
-        return espcn_f16_wide_a_launch(ctx->stream, k1, p, frameBits, qin16, x, reinterpret_cast<const _Float16*>(w1), reinterpret_cast<const _Float16*>(w2), e1, e2,
-                                       reinterpret_cast<_Float16*>(y), evStart, evStop);
-    }
-    bool foldU8In(const snnhip_u8_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F16 || frameBits) return false;
-        frameBits = 8;
-        p.mean = ui.means[0];
-        p.norm = ui.norms[0];
-        rename_kernel(desc, "kernel=espcn_f16_wide_conv_pair_kernel", "kernel=espcn_f16_wide_conv_pair_kernel<u8>");
-        return true;
-    }
-    bool foldU16In(const snnhip_u16_in_desc& ui, std::string& desc) override {
-        if (ui.dtype != SNNHIP_F16 || frameBits) return false;
-        frameBits = 16;
-        qin16 = U16InCfg{ui.means[0], ui.norms[0], ui.shift};
-        rename_kernel(desc, "kernel=espcn_f16_wide_conv_pair_kernel", "kernel=espcn_f16_wide_conv_pair_u16_kernel");
-        return true;
-    }
-};
-
-struct FusedB16Wide : FusedLaunch { // rule B16 wide and its frame forms, upscale 2, 3 or 4 (espcn_f16_wide.hip): w holds halfs
-    EspcnF16BParams p{};
-    int r = 2, frameBits = 0;
-    U16OutCfg qout16{0.0f, 0.0f, 0.0f, 0};
-    float *w = nullptr, *e = nullptr;
-    int launch(snnhip_ctx* ctx, const float* x, float* y, hipEvent_t evStart, hipEvent_t evStop) const override {
-        return espcn_f16_wide_b_launch(ctx->stream, r, p, frameBits, qout16, reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(w), e, y, evStart,
-                                       evStop);
-    }
-    bool foldU8Out(const snnhip_u8_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F16 || frameBits) return false;
-        frameBits = 8;
-        p.qscale = uo.scale[0];
-        p.qoffset = uo.offset[0];
-        const size_t at = desc.find(">", desc.find("kernel=espcn_f16_wide_d2s_kernel<"));
-        if (at != std::string::npos) desc.insert(at, ",u8");
-        return true;
-    }
-    bool foldU16Out(const snnhip_u16_out_desc& uo, std::string& desc) override {
-        if (uo.dtype != SNNHIP_F16 || frameBits) return false;
-        frameBits = 16;
-        qout16 = U16OutCfg{uo.scale[0], uo.offset[0], static_cast<float>(uo.maxval), uo.shift};
-        rename_kernel(desc, "kernel=espcn_f16_wide_d2s_kernel", "kernel=espcn_f16_wide_d2s_u16_kernel");
-        return true;
+    bool foldOut(const FrameOut& f, int dtype, std::string& desc) override {
+        const std::string k = wide ? "espcn_f16_wide_d2s" : "espcn_f16_d2s", R = std::to_string(r);
+        return fold_frame(frame, f, dtype == SNNHIP_F16, wide ? espcn_f16_wide_takes_frame() : espcn_f16_takes_frame(),
+                          {k + "_kernel<" + R + ">", k + "_kernel<" + R + ",u8>", k + "_u16_kernel<" + R + ">"}, desc);
     }
 };
 
@@ -493,7 +402,8 @@ int rule_a16_wide(Planner& pl, int i, Step& st) {
     const ConvGeom& g0 = c0->g;
     constexpr int C1 = kWide.c1, C2 = kWide.c2, TW = kEspcnF16WideTW_A, TH = kEspcnF16WideTH_A;
     const int K1 = g0.kh, taps1 = K1 * K1;
-    auto f = std::make_unique<FusedA16Wide>();
+    auto f = std::make_unique<FusedA16>();
+    f->wide = true;
     f->k1 = K1;
     f->p = EspcnF16AParams{g0.N, g0.H, g0.W, up_div(g0.W, TW), up_div(g0.H, TH), make_act_cfg(g0.act, g0.leaky), make_act_cfg(c1->g.act, c1->g.leaky), 0.0f, 1.0f};
     std::vector<_Float16> w1h(kEspcnF16WideW1Halfs), w2h(kEspcnF16WideW2Halfs);
@@ -522,7 +432,8 @@ int rule_b16_wide(Planner& pl, int i, Step& st) {
     if (!r || (i >= 2 && behind_other_head(pl.as<ConvPlanBase>(i - 2), pl.as<ConvPlanBase>(i - 1), kWide))) return 0;
     const ConvGeom& g0 = c0->g;
     constexpr int C2 = kWide.c2, TW = kEspcnF16WideTW_B, TH = kEspcnF16WideTH_B;
-    auto f = std::make_unique<FusedB16Wide>();
+    auto f = std::make_unique<FusedB16>();
+    f->wide = true;
     f->r = r;
     f->p = EspcnF16BParams{g0.N, g0.H, g0.W, up_div(g0.W, TW), up_div(g0.H, TH), make_act_cfg(g0.act, g0.leaky), 1.0f, 0.0f};
     std::vector<_Float16> wh(kEspcnF16WideW3Halfs);
@@ -854,48 +765,66 @@ void pass_conv_stats_into_norm(Planner& pl) {
     }
 }
 
-// ---- rules A8 / B8 and their fp16 forms: an 8-bit frame conversion (1 channel, of the fused launch's tensor type) next to a fused ESPCN launch
-// moves into it.  u8_in directly in front: the kernel stages bytes and normalises them; u8_out directly behind: its epilogue quantises and stores
-// bytes.  Which launches take the fold is theirs to say (FusedLaunch::foldU8In / foldU8Out).  Both compute the stand-alone plans' expressions, so
-// the fused chain's bytes are the unfused chain's.  Only at the chain's ends: an 8-bit tensor is never one of its intermediates.
+// ---- the frame ends (rules A8 / B8, their 16-bit and fp16 forms): a frame conversion (1 channel, of the fused launch's tensor type) next to a fused
+// ESPCN launch moves into it.  u8_in / u16_in directly in front: the kernel stages the frame and normalises it; u8_out / u16_out directly behind: its
+// epilogue quantises and stores the frame.  Which launches take the fold is theirs to say (FusedLaunch::foldIn / foldOut).  Both compute the
+// stand-alone plans' expressions, so the fused chain's bytes are the unfused chain's.  Only at the chain's ends: a frame is never an intermediate.
+struct FrameTensor { // the float side of a conversion plan
+    int dtype = SNNHIP_F32;
+    double pixels = 0;
+    // what folding saves per pixel: the tensor element (4 or 2 bytes) becomes a frame element
+    double bytes_saved(int bits) const { return ((dtype == SNNHIP_F16 ? 2 : 4) - bits / 8) * pixels; }
+};
+// a one-channel u16_in / u8_in plan as a FrameIn, a u16_out / u8_out plan as a FrameOut
+bool frame_in_of(const snnhip_plan* plan, FrameIn* f, FrameTensor* t) {
+    snnhip_u16_in_desc w;
+    snnhip_u8_in_desc u;
+    if (u16_in_plan_desc(plan, &w) && w.C == 1) {
+        *f = FrameIn{16, w.means[0], w.norms[0], w.shift};
+        *t = FrameTensor{w.dtype, static_cast<double>(w.N) * w.H * w.W};
+        return true;
+    }
+    if (u8_in_plan_desc(plan, &u) && u.C == 1) {
+        *f = FrameIn{8, u.means[0], u.norms[0], 0};
+        *t = FrameTensor{u.dtype, static_cast<double>(u.N) * u.H * u.W};
+        return true;
+    }
+    return false;
+}
+bool frame_out_of(const snnhip_plan* plan, FrameOut* f, FrameTensor* t) {
+    snnhip_u16_out_desc w;
+    snnhip_u8_out_desc u;
+    if (u16_out_plan_desc(plan, &w) && w.C == 1) {
+        *f = FrameOut{16, w.scale[0], w.offset[0], static_cast<float>(w.maxval), w.shift};
+        *t = FrameTensor{w.dtype, static_cast<double>(w.N) * w.H * w.W};
+        return true;
+    }
+    if (u8_out_plan_desc(plan, &u) && u.C == 1) {
+        *f = FrameOut{8, u.scale[0], u.offset[0], 255.0f, 0};
+        *t = FrameTensor{u.dtype, static_cast<double>(u.N) * u.H * u.W};
+        return true;
+    }
+    return false;
+}
+
 void pass_u8_ends(Planner& pl) {
     std::vector<Step>& steps = pl.chain->steps;
     for (size_t k = 0; k + 1 < steps.size(); ++k) {
         Step &a = steps[k], &b = steps[k + 1];
-        snnhip_u8_in_desc ui;
-        snnhip_u8_out_desc uo;
-        snnhip_u16_in_desc wi;
-        snnhip_u16_out_desc wo;
-        // the 16-bit conversions, same places: 2 bytes per frame pixel instead of the fp32 tensor's 4 (the fp16 kernels move 2 either way)
-        if (k == 0 && a.plain && b.fused && u16_in_plan_desc(a.plain, &wi) && wi.C == 1 && b.fused->foldU16In(wi, b.desc)) {
-            b.desc = "u16_in(1ch) + " + b.desc;
+        FrameIn fi;
+        FrameOut fo;
+        FrameTensor t;
+        if (k == 0 && a.plain && b.fused && frame_in_of(a.plain, &fi, &t) && b.fused->foldIn(fi, t.dtype, b.desc)) {
+            b.desc = "u" + std::to_string(fi.bits) + "_in(1ch) + " + b.desc;
             b.flops += a.flops;
-            b.bytes -= (wi.dtype == SNNHIP_F16 ? 0.0 : 2.0) * wi.N * wi.H * wi.W;
+            b.bytes -= t.bytes_saved(fi.bits);
             steps.erase(steps.begin() + static_cast<long>(k));
             ++pl.fusedCount;
             --k;
-            continue;
-        }
-        if (k + 2 == steps.size() && a.fused && b.plain && u16_out_plan_desc(b.plain, &wo) && wo.C == 1 && a.fused->foldU16Out(wo, a.desc)) {
-            a.desc += " + u16_out(1ch)";
+        } else if (k + 2 == steps.size() && a.fused && b.plain && frame_out_of(b.plain, &fo, &t) && a.fused->foldOut(fo, t.dtype, a.desc)) {
+            a.desc += " + u" + std::to_string(fo.bits) + "_out(1ch)";
             a.flops += b.flops;
-            a.bytes -= (wo.dtype == SNNHIP_F16 ? 0.0 : 2.0) * wo.N * wo.H * wo.W;
-            memcpy(a.outDims, b.outDims, sizeof(a.outDims));
-            steps.erase(steps.begin() + static_cast<long>(k) + 1);
-            ++pl.fusedCount;
-            continue;
-        }
-        if (k == 0 && a.plain && b.fused && u8_in_plan_desc(a.plain, &ui) && ui.C == 1 && b.fused->foldU8In(ui, b.desc)) {
-            b.desc = "u8_in(1ch) + " + b.desc;
-            b.flops += a.flops;
-            b.bytes -= (ui.dtype == SNNHIP_F16 ? 1.0 : 3.0) * ui.N * ui.H * ui.W; // 1 byte per input pixel instead of 2 / 4
-            steps.erase(steps.begin() + static_cast<long>(k));
-            ++pl.fusedCount;
-            --k;
-        } else if (k + 2 == steps.size() && a.fused && b.plain && u8_out_plan_desc(b.plain, &uo) && uo.C == 1 && a.fused->foldU8Out(uo, a.desc)) {
-            a.desc += " + u8_out(1ch)";
-            a.flops += b.flops;
-            a.bytes -= (uo.dtype == SNNHIP_F16 ? 1.0 : 3.0) * uo.N * uo.H * uo.W; // 1 byte per output pixel instead of 2 / 4
+            a.bytes -= t.bytes_saved(fo.bits);
             memcpy(a.outDims, b.outDims, sizeof(a.outDims));
             steps.erase(steps.begin() + static_cast<long>(k) + 1);
             ++pl.fusedCount;

@@ -1,4 +1,5 @@
-// espcn_common.h -- what the three ESPCN kernel units (espcn_fused.hip, espcn_d2s_mfma.hip, espcn_f16.hip) share.
+// espcn_common.h -- what the ESPCN kernel units (espcn_fused.hip, espcn_d2s_mfma.hip, espcn_f16.hip, espcn_f16_wide.hip) and the chain planner share:
+// the tile order, the kernels' frame-end parameter blocks and the host-side description of a frame end (FrameIn / FrameOut).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,6 +45,21 @@ struct FrameBits<unsigned char> {
 template <>
 struct FrameBits<unsigned short> {
     static constexpr int value = 16;
+};
+
+// ---- host side: the one description of a frame end that the planner hands to a launch function.  bits as FrameBits: 0 = the launch reads / writes its
+// own tensor type, 8 / 16 = a frame (the maps of snnhip_u8_in / u16_in and snnhip_u8_out / u16_out; shift and maxval are the 16-bit forms').  Never a
+// kernel argument: each launch function builds its kernel's own block from it (U8InCfg{f.mean, f.norm}, ...), and which block a kernel keeps its 8-bit
+// map in is its unit's matter.
+struct FrameIn {
+    int bits = 0;
+    float mean = 0.0f, norm = 1.0f;
+    int shift = 0;
+};
+struct FrameOut {
+    int bits = 0;
+    float scale = 1.0f, offset = 0.0f, maxval = 0.0f;
+    int shift = 0;
 };
 
 // MFMA row of a depth-to-space tail (kernel B for r = 3 / 4, kernel B16): row 4*dy + dx holds channel r*dy + dx (r = 2, 3, 4); -1 = the row stays zero

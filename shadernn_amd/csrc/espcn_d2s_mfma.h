@@ -12,12 +12,10 @@ constexpr int kD2sMfmaTW = 32, kD2sMfmaTH = 8; // low-resolution pixels per bloc
 using EspcnD2sParams = FusedBParams; // input [N, H, W, 16]; tiles of kD2sMfmaTW x kD2sMfmaTH; same fields, same tile decode as kernel B for upscale 2
 
 // Conv2D 3x3 (16 -> r*r) + act -> depth-to-space(r) + tanh in one launch, r = 3 or 4.  w: the lane-ordered A-operand image (36 x 64 floats, MFMA
-// row 4*dy + dx = channel r*dy + dx), ep: 16 x {scale, shift} in MFMA row order.  u8out: y is an 8-bit frame, q = quantize_u8(o, qscale, qoffset).
-// evStart / evStop: a plan-profile event pair or null.
-int espcn_d2s_mfma_launch(hipStream_t stream, int r, const EspcnD2sParams& p, bool u8out, float qscale, float qoffset, const float* x, const float* w,
-                          const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop);
-// The same with a 16-bit output frame: q = quantize_u16(o, scale, offset, maxval) << shift.
-int espcn_d2s_mfma_u16_launch(hipStream_t stream, int r, const EspcnD2sParams& p, const U16OutCfg& q, const float* x, const float* w, const float* ep,
-                              unsigned short* y, hipEvent_t evStart, hipEvent_t evStop);
+// row 4*dy + dx = channel r*dy + dx), ep: 16 x {scale, shift} in MFMA row order.  f: what y takes -- floats, an 8-bit frame, q = quantize_u8(o,
+// scale, offset), or a 16-bit one, q = quantize_u16(o, scale, offset, maxval) << shift.  evStart / evStop: a plan-profile event pair or null.
+inline bool espcn_d2s_mfma_takes_frame() { return true; } // its one form writes frames
+int espcn_d2s_mfma_launch(hipStream_t stream, int r, const EspcnD2sParams& p, const FrameOut& f, const float* x, const float* w, const float* ep, void* y,
+                          hipEvent_t evStart, hipEvent_t evStop);
 
 } // namespace snnhip

@@ -40,44 +40,31 @@ __global__ __launch_bounds__(256, 4) void conv3x3_c16oR_d2s_tanh_u16_kernel(Espc
 #include "espcn_d2s_mfma_body.h"
 }
 
-} // namespace
-
-int espcn_d2s_mfma_launch(hipStream_t stream, int r, const EspcnD2sParams& p, bool u8out, float qscale, float qoffset, const float* x, const float* w,
-                          const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop) {
-    SNNHIP_REQUIRE(r == 3 || r == 4, "espcn_d2s_mfma: upscale factor %d (3 or 4)", r);
-    const dim3 grid(p.tilesX * p.tilesY * p.N);
-    const U8OutCfg q{qscale, qoffset};
-    const bool simple = act_is_simple(p.act.act);
-#define SNNHIP_LAUNCH_BR(R, S)                                                                                                                   \
-    if (u8out)                                                                                                                                   \
-        SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_u8_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w, ep,                  \
-                         static_cast<unsigned char*>(y));                                                                                        \
-    else                                                                                                                                         \
-        SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<float*>(y))
-    if (r == 3) {
-        if (simple) SNNHIP_LAUNCH_BR(3, true); else SNNHIP_LAUNCH_BR(3, false);
-    } else {
-        if (simple) SNNHIP_LAUNCH_BR(4, true); else SNNHIP_LAUNCH_BR(4, false);
-    }
-#undef SNNHIP_LAUNCH_BR
+template <int R, bool S>
+int launch_br(hipStream_t stream, dim3 grid, const EspcnD2sParams& p, const FrameOut& f, const float* x, const float* w, const float* ep, void* y,
+               hipEvent_t evStart, hipEvent_t evStop) {
+    if (f.bits == 16)
+        SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_u16_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, U16OutCfg{f.scale, f.offset, f.maxval, f.shift},
+                         x, w, ep, static_cast<unsigned short*>(y));
+    else if (f.bits == 8)
+        SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_u8_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, U8OutCfg{f.scale, f.offset}, x, w, ep,
+                         static_cast<unsigned char*>(y));
+    else
+        SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<float*>(y));
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
 }
 
-int espcn_d2s_mfma_u16_launch(hipStream_t stream, int r, const EspcnD2sParams& p, const U16OutCfg& q, const float* x, const float* w, const float* ep,
-                              unsigned short* y, hipEvent_t evStart, hipEvent_t evStop) {
+} // namespace
+
+int espcn_d2s_mfma_launch(hipStream_t stream, int r, const EspcnD2sParams& p, const FrameOut& f, const float* x, const float* w, const float* ep, void* y,
+                          hipEvent_t evStart, hipEvent_t evStop) {
     SNNHIP_REQUIRE(r == 3 || r == 4, "espcn_d2s_mfma: upscale factor %d (3 or 4)", r);
     const dim3 grid(p.tilesX * p.tilesY * p.N);
     const bool simple = act_is_simple(p.act.act);
-#define SNNHIP_LAUNCH_BR16(R, S) SNNHIP_LAUNCH_EV((conv3x3_c16oR_d2s_tanh_u16_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w, ep, y)
-    if (r == 3) {
-        if (simple) SNNHIP_LAUNCH_BR16(3, true); else SNNHIP_LAUNCH_BR16(3, false);
-    } else {
-        if (simple) SNNHIP_LAUNCH_BR16(4, true); else SNNHIP_LAUNCH_BR16(4, false);
-    }
-#undef SNNHIP_LAUNCH_BR16
-    SNNHIP_CHECK_HIP(hipGetLastError());
-    return SNNHIP_OK;
+    if (r == 3)
+        return simple ? launch_br<3, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_br<3, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
+    return simple ? launch_br<4, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_br<4, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
 }
 
 } // namespace snnhip

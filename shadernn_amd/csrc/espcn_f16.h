@@ -37,19 +37,16 @@ struct EspcnF16BParams {
     float qscale, qoffset; // u8out: q = quantize_u8(float(half(tanh)), qscale, qoffset)
 };
 
-// Kernel A16: Conv2D k1 x k1 (1 -> 16) + act -> Conv2D 3x3 (16 -> 16) + act on fp16 tensors (x: halfs, or bytes with u8in), k1 = 3 or 5.
-// w1 / w2: the images above; ep1 / ep2: 16 x {scale, shift} fp32.  evStart / evStop: a plan-profile event pair or null.
-int espcn_f16_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, bool u8in, const void* x, const _Float16* w1, const _Float16* w2,
+// Kernel A16: Conv2D k1 x k1 (1 -> 16) + act -> Conv2D 3x3 (16 -> 16) + act on fp16 tensors, k1 = 3 or 5.  f: what x holds -- halfs, an 8-bit
+// frame, half((float(u) - mean) * norm) (the launch writes the map into its copy of p), or a 16-bit one, half((float(u >> shift) - mean) * norm)
+// (a U16InCfg block of its own).  w1 / w2: the images above; ep1 / ep2: 16 x {scale, shift} fp32.  evStart / evStop: a plan-profile event pair or null.
+inline bool espcn_f16_takes_frame() { return true; } // kernels A16 and B16 read / write frames in their one form
+int espcn_f16_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const FrameIn& f, const void* x, const _Float16* w1, const _Float16* w2,
                        const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop);
-// Kernel B16<r>: Conv2D 3x3 (16 -> r*r) + act -> depth-to-space(r) + tanh, r = 2, 3, 4 (y: halfs, or bytes with u8out).  ep: 16 x {scale, shift}
-// in MFMA row order.
-int espcn_f16_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, bool u8out, const _Float16* x, const _Float16* w, const float* ep, void* y,
+// Kernel B16<r>: Conv2D 3x3 (16 -> r*r) + act -> depth-to-space(r) + tanh, r = 2, 3, 4.  f: what y takes -- halfs, an 8-bit frame (the map goes
+// into the launch's copy of p), or a 16-bit one, quantize_u16(float(half(tanh)), scale, offset, maxval) << shift (a U16OutCfg block).  ep: 16 x
+// {scale, shift} in MFMA row order.
+int espcn_f16_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const FrameOut& f, const _Float16* x, const _Float16* w, const float* ep, void* y,
                        hipEvent_t evStart, hipEvent_t evStop);
-// The 16-bit frame forms of the two: x a 16-bit frame, half((float(u >> shift) - mean) * norm); y a 16-bit frame,
-// quantize_u16(float(half(tanh)), scale, offset, maxval) << shift.  Their parameter blocks are their own (espcn_common.h).
-int espcn_f16_a_u16_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const U16InCfg& q, const unsigned short* x, const _Float16* w1, const _Float16* w2,
-                           const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop);
-int espcn_f16_b_u16_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const U16OutCfg& q, const _Float16* x, const _Float16* w, const float* ep,
-                           unsigned short* y, hipEvent_t evStart, hipEvent_t evStop);
 
 } // namespace snnhip

@@ -113,6 +113,43 @@ __global__ __launch_bounds__(256) void espcn_f16_d2s_u16_kernel(EspcnF16BParams 
 #include "espcn_f16_b_body.h"
 }
 
+// ---- the launch sites, as in espcn_f16_wide.hip.  The 8-bit forms keep their map in the kernel's parameter block: a stack copy of p takes it.
+template <int K1, bool S>
+int launch_a(hipStream_t stream, dim3 grid, EspcnF16AParams p, const FrameIn& f, const void* x, const _Float16* w1, const _Float16* w2, const float* ep1,
+              const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
+    if (f.bits == 16) {
+        SNNHIP_LAUNCH_EV((espcn_f16_conv_pair_u16_kernel<K1, S>), grid, dim3(256), 0, stream, evStart, evStop, p, U16InCfg{f.mean, f.norm, f.shift},
+                         static_cast<const unsigned short*>(x), w1, w2, ep1, ep2, y);
+    } else if (f.bits == 8) {
+        p.mean = f.mean;
+        p.norm = f.norm;
+        SNNHIP_LAUNCH_EV((espcn_f16_conv_pair_kernel<K1, unsigned char, S>), grid, dim3(256), 0, stream, evStart, evStop, p, static_cast<const unsigned char*>(x), w1,
+                         w2, ep1, ep2, y);
+    } else {
+        SNNHIP_LAUNCH_EV((espcn_f16_conv_pair_kernel<K1, _Float16, S>), grid, dim3(256), 0, stream, evStart, evStop, p, static_cast<const _Float16*>(x), w1, w2, ep1,
+                         ep2, y);
+    }
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
+template <int R, bool S>
+int launch_b(hipStream_t stream, dim3 grid, EspcnF16BParams p, const FrameOut& f, const _Float16* x, const _Float16* w, const float* ep, void* y,
+              hipEvent_t evStart, hipEvent_t evStop) {
+    if (f.bits == 16) {
+        SNNHIP_LAUNCH_EV((espcn_f16_d2s_u16_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, U16OutCfg{f.scale, f.offset, f.maxval, f.shift}, x, w, ep,
+                         static_cast<unsigned short*>(y));
+    } else if (f.bits == 8) {
+        p.qscale = f.scale;
+        p.qoffset = f.offset;
+        SNNHIP_LAUNCH_EV((espcn_f16_d2s_kernel<R, unsigned char, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<unsigned char*>(y));
+    } else {
+        SNNHIP_LAUNCH_EV((espcn_f16_d2s_kernel<R, _Float16, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<_Float16*>(y));
+    }
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
+
 } // namespace
 
 void espcn_f16_pack_w3(const float* w_oihw, int r, _Float16* out) {
@@ -136,83 +173,28 @@ void espcn_f16_pack_w1(const float* w_oihw, int k, _Float16* out) {
         }
 }
 
-int espcn_f16_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, bool u8in, const void* x, const _Float16* w1, const _Float16* w2,
+int espcn_f16_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const FrameIn& f, const void* x, const _Float16* w1, const _Float16* w2,
                        const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
     SNNHIP_REQUIRE(k1 == 3 || k1 == 5, "espcn_f16: first convolution %dx%d (3x3 or 5x5)", k1, k1);
     const dim3 grid(p.tilesX * p.tilesY * p.N);
     const bool simple = act_is_simple(p.act1.act) && act_is_simple(p.act2.act);
-#define SNNHIP_LAUNCH_A16(K, S)                                                                                                                  \
-    if (u8in)                                                                                                                                    \
-        SNNHIP_LAUNCH_EV((espcn_f16_conv_pair_kernel<K, unsigned char, S>), grid, dim3(256), 0, stream, evStart, evStop, p,                      \
-                         static_cast<const unsigned char*>(x), w1, w2, ep1, ep2, y);                                                             \
-    else                                                                                                                                         \
-        SNNHIP_LAUNCH_EV((espcn_f16_conv_pair_kernel<K, _Float16, S>), grid, dim3(256), 0, stream, evStart, evStop, p,                           \
-                         static_cast<const _Float16*>(x), w1, w2, ep1, ep2, y)
-    if (k1 == 5) {
-        if (simple) SNNHIP_LAUNCH_A16(5, true); else SNNHIP_LAUNCH_A16(5, false);
-    } else {
-        if (simple) SNNHIP_LAUNCH_A16(3, true); else SNNHIP_LAUNCH_A16(3, false);
-    }
-#undef SNNHIP_LAUNCH_A16
-    SNNHIP_CHECK_HIP(hipGetLastError());
-    return SNNHIP_OK;
+    if (k1 == 5)
+        return simple ? launch_a<5, true>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop)
+                      : launch_a<5, false>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
+    return simple ? launch_a<3, true>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop)
+                  : launch_a<3, false>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
 }
 
-int espcn_f16_a_u16_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const U16InCfg& q, const unsigned short* x, const _Float16* w1, const _Float16* w2,
-                           const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
-    SNNHIP_REQUIRE(k1 == 3 || k1 == 5, "espcn_f16: first convolution %dx%d (3x3 or 5x5)", k1, k1);
-    const dim3 grid(p.tilesX * p.tilesY * p.N);
-    const bool simple = act_is_simple(p.act1.act) && act_is_simple(p.act2.act);
-#define SNNHIP_LAUNCH_A16W(K, S) SNNHIP_LAUNCH_EV((espcn_f16_conv_pair_u16_kernel<K, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w1, w2, ep1, ep2, y)
-    if (k1 == 5) {
-        if (simple) SNNHIP_LAUNCH_A16W(5, true); else SNNHIP_LAUNCH_A16W(5, false);
-    } else {
-        if (simple) SNNHIP_LAUNCH_A16W(3, true); else SNNHIP_LAUNCH_A16W(3, false);
-    }
-#undef SNNHIP_LAUNCH_A16W
-    SNNHIP_CHECK_HIP(hipGetLastError());
-    return SNNHIP_OK;
-}
-
-int espcn_f16_b_u16_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const U16OutCfg& q, const _Float16* x, const _Float16* w, const float* ep,
-                           unsigned short* y, hipEvent_t evStart, hipEvent_t evStop) {
-    SNNHIP_REQUIRE(r >= 2 && r <= 4, "espcn_f16: upscale factor %d (2, 3 or 4)", r);
-    const dim3 grid(p.tilesX * p.tilesY * p.N);
-    const bool simple = act_is_simple(p.act.act);
-#define SNNHIP_LAUNCH_B16W(R, S) SNNHIP_LAUNCH_EV((espcn_f16_d2s_u16_kernel<R, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w, ep, y)
-    if (r == 2) {
-        if (simple) SNNHIP_LAUNCH_B16W(2, true); else SNNHIP_LAUNCH_B16W(2, false);
-    } else if (r == 3) {
-        if (simple) SNNHIP_LAUNCH_B16W(3, true); else SNNHIP_LAUNCH_B16W(3, false);
-    } else {
-        if (simple) SNNHIP_LAUNCH_B16W(4, true); else SNNHIP_LAUNCH_B16W(4, false);
-    }
-#undef SNNHIP_LAUNCH_B16W
-    SNNHIP_CHECK_HIP(hipGetLastError());
-    return SNNHIP_OK;
-}
-
-int espcn_f16_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, bool u8out, const _Float16* x, const _Float16* w, const float* ep, void* y,
+int espcn_f16_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const FrameOut& f, const _Float16* x, const _Float16* w, const float* ep, void* y,
                        hipEvent_t evStart, hipEvent_t evStop) {
     SNNHIP_REQUIRE(r >= 2 && r <= 4, "espcn_f16: upscale factor %d (2, 3 or 4)", r);
     const dim3 grid(p.tilesX * p.tilesY * p.N);
     const bool simple = act_is_simple(p.act.act);
-#define SNNHIP_LAUNCH_B16(R, S)                                                                                                                  \
-    if (u8out)                                                                                                                                   \
-        SNNHIP_LAUNCH_EV((espcn_f16_d2s_kernel<R, unsigned char, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep,                  \
-                         static_cast<unsigned char*>(y));                                                                                        \
-    else                                                                                                                                         \
-        SNNHIP_LAUNCH_EV((espcn_f16_d2s_kernel<R, _Float16, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<_Float16*>(y))
-    if (r == 2) {
-        if (simple) SNNHIP_LAUNCH_B16(2, true); else SNNHIP_LAUNCH_B16(2, false);
-    } else if (r == 3) {
-        if (simple) SNNHIP_LAUNCH_B16(3, true); else SNNHIP_LAUNCH_B16(3, false);
-    } else {
-        if (simple) SNNHIP_LAUNCH_B16(4, true); else SNNHIP_LAUNCH_B16(4, false);
-    }
-#undef SNNHIP_LAUNCH_B16
-    SNNHIP_CHECK_HIP(hipGetLastError());
-    return SNNHIP_OK;
+    if (r == 2)
+        return simple ? launch_b<2, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_b<2, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
+    if (r == 3)
+        return simple ? launch_b<3, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_b<3, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
+    return simple ? launch_b<4, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_b<4, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
 }
 
 } // namespace snnhip

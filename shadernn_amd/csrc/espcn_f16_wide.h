@@ -33,13 +33,14 @@ void espcn_f16_wide_pack_w3(const float* w_oihw, int ic, int rows, int r, _Float
 void espcn_f16_wide_pack_w1(const float* w_oihw, int c1, int k, _Float16* out);
 
 // Kernel A16 wide: Conv2D k1 x k1 (1 -> 64) + act -> Conv2D 3x3 (64 -> 32) + act on fp16 tensors, k1 = 3 or 5.  The parameter blocks are the narrow
-// kernels' (tiles of kEspcnF16WideTW_A x kEspcnF16WideTH_A).  frameBits: 0 = x holds halfs, 8 = an 8-bit frame (p.mean / p.norm), 16 = a 16-bit frame (q).
-// w1 / w2: the images above; ep1 / ep2: 64 / 32 x {scale, shift} fp32.
-int espcn_f16_wide_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, int frameBits, const U16InCfg& q, const void* x, const _Float16* w1,
-                            const _Float16* w2, const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop);
-// Kernel B16 wide<r>: Conv2D 3x3 (32 -> r*r) + act -> depth-to-space(r) + tanh, r = 2, 3, 4.  frameBits: 0 = y takes halfs, 8 = an 8-bit frame
-// (p.qscale / p.qoffset), 16 = a 16-bit frame (q).  ep: 16 x {scale, shift} in MFMA row order.
-int espcn_f16_wide_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, int frameBits, const U16OutCfg& q, const _Float16* x, const _Float16* w,
-                            const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop);
+// kernels' (tiles of kEspcnF16WideTW_A x kEspcnF16WideTH_A).  f: what x holds -- halfs, an 8-bit frame (its map goes into the launch's copy of p) or a
+// 16-bit one (a U16InCfg block), as kernel A16.  w1 / w2: the images above; ep1 / ep2: 64 / 32 x {scale, shift} fp32.
+inline bool espcn_f16_wide_takes_frame() { return true; } // both kernels read / write frames in their one form
+int espcn_f16_wide_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const FrameIn& f, const void* x, const _Float16* w1, const _Float16* w2,
+                            const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop);
+// Kernel B16 wide<r>: Conv2D 3x3 (32 -> r*r) + act -> depth-to-space(r) + tanh, r = 2, 3, 4.  f: what y takes, as kernel B16.  ep: 16 x {scale,
+// shift} in MFMA row order.
+int espcn_f16_wide_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const FrameOut& f, const _Float16* x, const _Float16* w, const float* ep, void* y,
+                            hipEvent_t evStart, hipEvent_t evStop);
 
 } // namespace snnhip

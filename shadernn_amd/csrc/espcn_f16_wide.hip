@@ -100,35 +100,42 @@ __global__ __launch_bounds__(256) void espcn_f16_wide_d2s_u16_kernel(EspcnF16BPa
 #include "espcn_f16_wide_b_body.h"
 }
 
+// ---- the launch sites.  The 8-bit forms keep their map in the kernel's parameter block: a stack copy of p takes it.
 template <int K1, bool S>
-int launch_a(hipStream_t stream, const dim3 grid, const EspcnF16AParams& p, int frameBits, const U16InCfg& q, const void* x, const _Float16* w1,
-             const _Float16* w2, const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
+int launch_a(hipStream_t stream, const dim3 grid, EspcnF16AParams p, const FrameIn& f, const void* x, const _Float16* w1, const _Float16* w2, const float* ep1,
+             const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
     constexpr int C1 = kEspcnF16WideC1, C2 = kEspcnF16WideC2;
-    if (frameBits == 16)
-        SNNHIP_LAUNCH_EV((espcn_f16_wide_conv_pair_u16_kernel<K1, C1, C2, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q,
+    if (f.bits == 16) {
+        SNNHIP_LAUNCH_EV((espcn_f16_wide_conv_pair_u16_kernel<K1, C1, C2, S>), grid, dim3(256), 0, stream, evStart, evStop, p, U16InCfg{f.mean, f.norm, f.shift},
                          static_cast<const unsigned short*>(x), w1, w2, ep1, ep2, y);
-    else if (frameBits == 8)
+    } else if (f.bits == 8) {
+        p.mean = f.mean;
+        p.norm = f.norm;
         SNNHIP_LAUNCH_EV((espcn_f16_wide_conv_pair_kernel<K1, C1, C2, unsigned char, S>), grid, dim3(256), 0, stream, evStart, evStop, p,
                          static_cast<const unsigned char*>(x), w1, w2, ep1, ep2, y);
-    else
+    } else {
         SNNHIP_LAUNCH_EV((espcn_f16_wide_conv_pair_kernel<K1, C1, C2, _Float16, S>), grid, dim3(256), 0, stream, evStart, evStop, p,
                          static_cast<const _Float16*>(x), w1, w2, ep1, ep2, y);
+    }
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
 }
 
 template <int R, bool S>
-int launch_b(hipStream_t stream, const dim3 grid, const EspcnF16BParams& p, int frameBits, const U16OutCfg& q, const _Float16* x, const _Float16* w,
-             const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop) {
+int launch_b(hipStream_t stream, const dim3 grid, EspcnF16BParams p, const FrameOut& f, const _Float16* x, const _Float16* w, const float* ep, void* y,
+             hipEvent_t evStart, hipEvent_t evStop) {
     constexpr int C2 = kEspcnF16WideC2;
-    if (frameBits == 16)
-        SNNHIP_LAUNCH_EV((espcn_f16_wide_d2s_u16_kernel<R, C2, S>), grid, dim3(256), 0, stream, evStart, evStop, p, q, x, w, ep,
-                         static_cast<unsigned short*>(y));
-    else if (frameBits == 8)
+    if (f.bits == 16) {
+        SNNHIP_LAUNCH_EV((espcn_f16_wide_d2s_u16_kernel<R, C2, S>), grid, dim3(256), 0, stream, evStart, evStop, p, U16OutCfg{f.scale, f.offset, f.maxval, f.shift},
+                         x, w, ep, static_cast<unsigned short*>(y));
+    } else if (f.bits == 8) {
+        p.qscale = f.scale;
+        p.qoffset = f.offset;
         SNNHIP_LAUNCH_EV((espcn_f16_wide_d2s_kernel<R, C2, unsigned char, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep,
                          static_cast<unsigned char*>(y));
-    else
+    } else {
         SNNHIP_LAUNCH_EV((espcn_f16_wide_d2s_kernel<R, C2, _Float16, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<_Float16*>(y));
+    }
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
 }
@@ -158,31 +165,28 @@ void espcn_f16_wide_pack_w1(const float* w_oihw, int c1, int k, _Float16* out) {
             }
 }
 
-int espcn_f16_wide_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, int frameBits, const U16InCfg& q, const void* x, const _Float16* w1,
-                            const _Float16* w2, const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
+int espcn_f16_wide_a_launch(hipStream_t stream, int k1, const EspcnF16AParams& p, const FrameIn& f, const void* x, const _Float16* w1, const _Float16* w2,
+                            const float* ep1, const float* ep2, _Float16* y, hipEvent_t evStart, hipEvent_t evStop) {
     SNNHIP_REQUIRE(k1 == 3 || k1 == 5, "espcn_f16_wide: first convolution %dx%d (3x3 or 5x5)", k1, k1);
     const dim3 grid(p.tilesX * p.tilesY * p.N);
     const bool simple = act_is_simple(p.act1.act) && act_is_simple(p.act2.act);
     if (k1 == 5)
-        return simple ? launch_a<5, true>(stream, grid, p, frameBits, q, x, w1, w2, ep1, ep2, y, evStart, evStop)
-                      : launch_a<5, false>(stream, grid, p, frameBits, q, x, w1, w2, ep1, ep2, y, evStart, evStop);
-    return simple ? launch_a<3, true>(stream, grid, p, frameBits, q, x, w1, w2, ep1, ep2, y, evStart, evStop)
-                  : launch_a<3, false>(stream, grid, p, frameBits, q, x, w1, w2, ep1, ep2, y, evStart, evStop);
+        return simple ? launch_a<5, true>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop)
+                      : launch_a<5, false>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
+    return simple ? launch_a<3, true>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop)
+                  : launch_a<3, false>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
 }
 
-int espcn_f16_wide_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, int frameBits, const U16OutCfg& q, const _Float16* x, const _Float16* w,
-                            const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop) {
+int espcn_f16_wide_b_launch(hipStream_t stream, int r, const EspcnF16BParams& p, const FrameOut& f, const _Float16* x, const _Float16* w, const float* ep, void* y,
+                            hipEvent_t evStart, hipEvent_t evStop) {
     SNNHIP_REQUIRE(r >= 2 && r <= 4, "espcn_f16_wide: upscale factor %d (2, 3 or 4)", r);
     const dim3 grid(p.tilesX * p.tilesY * p.N);
     const bool simple = act_is_simple(p.act.act);
     if (r == 2)
-        return simple ? launch_b<2, true>(stream, grid, p, frameBits, q, x, w, ep, y, evStart, evStop)
-                      : launch_b<2, false>(stream, grid, p, frameBits, q, x, w, ep, y, evStart, evStop);
+        return simple ? launch_b<2, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_b<2, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
     if (r == 3)
-        return simple ? launch_b<3, true>(stream, grid, p, frameBits, q, x, w, ep, y, evStart, evStop)
-                      : launch_b<3, false>(stream, grid, p, frameBits, q, x, w, ep, y, evStart, evStop);
-    return simple ? launch_b<4, true>(stream, grid, p, frameBits, q, x, w, ep, y, evStart, evStop)
-                  : launch_b<4, false>(stream, grid, p, frameBits, q, x, w, ep, y, evStart, evStop);
+        return simple ? launch_b<3, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_b<3, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
+    return simple ? launch_b<4, true>(stream, grid, p, f, x, w, ep, y, evStart, evStop) : launch_b<4, false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
 }
 
 } // namespace snnhip

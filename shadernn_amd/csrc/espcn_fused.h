@@ -46,20 +46,17 @@ inline int wino_conv1_tap(int K1, int s, int g) {
 constexpr int wino_conv1_ksteps(int K1) { return K1 + (K1 > 4 ? 2 : 0); }
 
 // Kernel A: Conv2D k1 x k1 (1 -> 16) + act -> Conv2D 3x3 (16 -> 16) + act, k1 = 3 or 5.  wino: conv2 as Winograd F(2x2,3x3) on persistent blocks
-// (W_WPS per compute unit; tiles of W_TW x W_TH), else direct (one block per A_TW x A_TH tile).  u8in (Winograd form only): x is an 8-bit
-// frame.  w1 / w2: espcn_pack_conv1 + espcn_pack_wino (wino) or espcn_pack_conv3x3_lanes(., 0); ep1 / ep2: fold_epilogue.  evStart / evStop: a
+// (W_WPS per compute unit; tiles of W_TW x W_TH), else direct (one block per A_TW x A_TH tile).  f: what x holds (floats, or an 8- / 16-bit
+// frame).  w1 / w2: espcn_pack_conv1 + espcn_pack_wino (wino) or espcn_pack_conv3x3_lanes(., 0); ep1 / ep2: fold_epilogue.  evStart / evStop: a
 // plan-profile event pair or null.
-int espcn_fused_a_launch(hipStream_t stream, const FusedAParams& p, int k1, bool wino, bool u8in, const U8InCfg& qin, int computeUnits, const void* x,
-                         const float* w1, const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop);
+inline bool espcn_fused_a_takes_frame(bool wino) { return wino; } // only the Winograd form reads frames; the launch refuses any other
+int espcn_fused_a_launch(hipStream_t stream, const FusedAParams& p, int k1, bool wino, const FrameIn& f, int computeUnits, const void* x, const float* w1,
+                         const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop);
 // Kernel B: Conv2D 3x3 (16 -> 4) + act -> depth-to-space(2) + tanh, one block per tile.  wino: the 4x4x1-MFMA Winograd form (BW_TW x BW_TH,
-// w = espcn_pack_wino), else the VALU form (B_TW x B_TH, w = espcn_pack_b_direct).  u8out (VALU form only): y is an 8-bit frame.
-int espcn_fused_b_launch(hipStream_t stream, const FusedBParams& p, bool wino, bool u8out, const U8OutCfg& qout, const float* x, const float* w,
-                         const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop);
-// The 16-bit frame forms of the two (Winograd kernel A reading a 16-bit frame; VALU kernel B writing one): snnhip_u16_in / u16_out folded in.
-int espcn_fused_a_u16_launch(hipStream_t stream, const FusedAParams& p, int k1, const U16InCfg& qin, int computeUnits, const unsigned short* x, const float* w1,
-                             const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop);
-int espcn_fused_b_u16_launch(hipStream_t stream, const FusedBParams& p, const U16OutCfg& qout, const float* x, const float* w, const float* ep, unsigned short* y,
-                             hipEvent_t evStart, hipEvent_t evStop);
+// w = espcn_pack_wino), else the VALU form (B_TW x B_TH, w = espcn_pack_b_direct).  f: what y takes (floats, or an 8- / 16-bit frame).
+inline bool espcn_fused_b_takes_frame(bool wino) { return !wino; } // only the VALU form writes frames
+int espcn_fused_b_launch(hipStream_t stream, const FusedBParams& p, bool wino, const FrameOut& f, const float* x, const float* w, const float* ep, void* y,
+                         hipEvent_t evStart, hipEvent_t evStop);
 
 // ---- host-side weight images; w_oihw = the convolution's [OC][IC][k][k] fp32 weights
 // lane-ordered conv1 (1 -> 16, k1 x k1) A operand: image[s*64 + l] = W[oc = l & 15][tap], tap = 4s + l/16 (zero from k1*k1 on), or -- winoOrder --

@@ -526,88 +526,89 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16o4_wino_d2s_tanh_kernel(Fus
     SNNHIP_STAMP(6);
 }
 
+// ---- the launch sites: one function template per kernel over its compile-time parameters; the frame end (FrameIn / FrameOut, espcn_common.h) picks
+// the kernel and becomes that kernel's own parameter block here
+template <int K1, int AM>
+void launch_a_wino(hipStream_t stream, dim3 grid, const FusedAParams& p, const FrameIn& f, const void* x, const float* w1, const float* w2, const float* ep1,
+                   const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop) {
+    if (f.bits == 16)
+        SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_u16_kernel<K1, W_TH, AM, W_WPS>), grid, dim3(256), 0, stream, evStart, evStop, p,
+                         U16InCfg{f.mean, f.norm, f.shift}, static_cast<const unsigned short*>(x), w1, w2, ep1, ep2, y);
+    else if (f.bits == 8)
+        SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_u8_kernel<K1, W_TH, AM, W_WPS>), grid, dim3(256), 0, stream, evStart, evStop, p,
+                         U8InCfg{f.mean, f.norm}, static_cast<const unsigned char*>(x), w1, w2, ep1, ep2, y);
+    else
+        SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_kernel<K1, W_TH, AM, W_WPS>), grid, dim3(256), 0, stream, evStart, evStop, p,
+                         static_cast<const float*>(x), w1, w2, ep1, ep2, y);
+}
+
+template <int K1, bool S>
+void launch_a_direct(hipStream_t stream, dim3 grid, const FusedAParams& p, const float* x, const float* w1, const float* w2, const float* ep1, const float* ep2,
+                     float* y, hipEvent_t evStart, hipEvent_t evStop) {
+    SNNHIP_LAUNCH_EV((conv_kxk_c1o16_conv3x3_c16o16_kernel<K1, A_TW, A_TH, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w1, w2, ep1, ep2, y);
+}
+
+template <bool S>
+void launch_b_valu(hipStream_t stream, dim3 grid, const FusedBParams& p, const FrameOut& f, const float* x, const float* w, const float* ep, void* y,
+                   hipEvent_t evStart, hipEvent_t evStop) {
+    if (f.bits == 16)
+        SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u16_kernel<B_TW, B_TH, S>), grid, dim3(256), 0, stream, evStart, evStop, p,
+                         U16OutCfg{f.scale, f.offset, f.maxval, f.shift}, x, w, ep, static_cast<unsigned short*>(y));
+    else if (f.bits == 8)
+        SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u8_kernel<B_TW, B_TH, S>), grid, dim3(256), 0, stream, evStart, evStop, p, U8OutCfg{f.scale, f.offset}, x, w, ep,
+                         static_cast<unsigned char*>(y));
+    else
+        SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_kernel<B_TW, B_TH, S>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, static_cast<float*>(y));
+}
+
 } // namespace
 
-int espcn_fused_a_launch(hipStream_t stream, const FusedAParams& p, int k1, bool wino, bool u8in, const U8InCfg& qin, int computeUnits, const void* x,
-                         const float* w1, const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop) {
+int espcn_fused_a_launch(hipStream_t stream, const FusedAParams& p, int k1, bool wino, const FrameIn& f, int computeUnits, const void* x, const float* w1,
+                         const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop) {
+    SNNHIP_REQUIRE(f.bits == 0 || espcn_fused_a_takes_frame(wino), "espcn_fused_a: the direct form takes no %d-bit frame", f.bits);
     const int ntiles = p.tilesX * p.tilesY * p.N;
     const bool simple = act_is_simple(p.act1.act) && act_is_simple(p.act2.act);
     if (wino) {
         const int slots = W_WPS * (computeUnits > 0 ? computeUnits : 256);
-        dim3 grid(ntiles < slots ? ntiles : slots); // persistent: W_WPS blocks per CU walk the tile list
-#define SNNHIP_LAUNCH_W(K, AM)                                                                                                                       \
-    if (u8in)                                                                                                                                         \
-        SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_u8_kernel<K, W_TH, AM, W_WPS>), grid, dim3(256), 0, stream, evStart, evStop, p, qin,          \
-                         static_cast<const unsigned char*>(x), w1, w2, ep1, ep2, y);                                                                  \
-    else                                                                                                                                              \
-        SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_kernel<K, W_TH, AM, W_WPS>), grid, dim3(256), 0, stream, evStart, evStop, p,                  \
-                         static_cast<const float*>(x), w1, w2, ep1, ep2, y)
+        const dim3 grid(ntiles < slots ? ntiles : slots); // persistent: W_WPS blocks per CU walk the tile list
         const int am = (p.act1.act == SNNHIP_ACT_RELU && p.act2.act == SNNHIP_ACT_RELU) ? 2 : (simple ? 1 : 0);
         if (k1 == 5) {
-            if (am == 2) SNNHIP_LAUNCH_W(5, 2); else if (am == 1) SNNHIP_LAUNCH_W(5, 1); else SNNHIP_LAUNCH_W(5, 0);
+            if (am == 2) launch_a_wino<5, 2>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
+            else if (am == 1) launch_a_wino<5, 1>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
+            else launch_a_wino<5, 0>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
         } else {
-            if (am == 2) SNNHIP_LAUNCH_W(3, 2); else if (am == 1) SNNHIP_LAUNCH_W(3, 1); else SNNHIP_LAUNCH_W(3, 0);
+            if (am == 2) launch_a_wino<3, 2>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
+            else if (am == 1) launch_a_wino<3, 1>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
+            else launch_a_wino<3, 0>(stream, grid, p, f, x, w1, w2, ep1, ep2, y, evStart, evStop);
         }
-#undef SNNHIP_LAUNCH_W
     } else {
-        dim3 grid(ntiles);
-#define SNNHIP_LAUNCH_A(K, S)                                                                                                                        \
-    SNNHIP_LAUNCH_EV((conv_kxk_c1o16_conv3x3_c16o16_kernel<K, A_TW, A_TH, S>), grid, dim3(256), 0, stream, evStart, evStop, p,                       \
-                     static_cast<const float*>(x), w1, w2, ep1, ep2, y)
+        const dim3 grid(ntiles);
+        const float* x32 = static_cast<const float*>(x);
         if (k1 == 5) {
-            if (simple) SNNHIP_LAUNCH_A(5, true); else SNNHIP_LAUNCH_A(5, false);
+            if (simple) launch_a_direct<5, true>(stream, grid, p, x32, w1, w2, ep1, ep2, y, evStart, evStop);
+            else launch_a_direct<5, false>(stream, grid, p, x32, w1, w2, ep1, ep2, y, evStart, evStop);
         } else {
-            if (simple) SNNHIP_LAUNCH_A(3, true); else SNNHIP_LAUNCH_A(3, false);
+            if (simple) launch_a_direct<3, true>(stream, grid, p, x32, w1, w2, ep1, ep2, y, evStart, evStop);
+            else launch_a_direct<3, false>(stream, grid, p, x32, w1, w2, ep1, ep2, y, evStart, evStop);
         }
-#undef SNNHIP_LAUNCH_A
     }
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
 }
 
-int espcn_fused_a_u16_launch(hipStream_t stream, const FusedAParams& p, int k1, const U16InCfg& qin, int computeUnits, const unsigned short* x, const float* w1,
-                             const float* w2, const float* ep1, const float* ep2, float* y, hipEvent_t evStart, hipEvent_t evStop) {
-    const int ntiles = p.tilesX * p.tilesY * p.N;
-    const bool simple = act_is_simple(p.act1.act) && act_is_simple(p.act2.act);
-    const int slots = W_WPS * (computeUnits > 0 ? computeUnits : 256);
-    dim3 grid(ntiles < slots ? ntiles : slots); // persistent, as espcn_fused_a_launch
-#define SNNHIP_LAUNCH_W16(K, AM) \
-    SNNHIP_LAUNCH_EV((conv_kxk_c1o16_wino3x3_c16o16_u16_kernel<K, W_TH, AM, W_WPS>), grid, dim3(256), 0, stream, evStart, evStop, p, qin, x, w1, w2, ep1, ep2, y)
-    const int am = (p.act1.act == SNNHIP_ACT_RELU && p.act2.act == SNNHIP_ACT_RELU) ? 2 : (simple ? 1 : 0);
-    if (k1 == 5) {
-        if (am == 2) SNNHIP_LAUNCH_W16(5, 2); else if (am == 1) SNNHIP_LAUNCH_W16(5, 1); else SNNHIP_LAUNCH_W16(5, 0);
-    } else {
-        if (am == 2) SNNHIP_LAUNCH_W16(3, 2); else if (am == 1) SNNHIP_LAUNCH_W16(3, 1); else SNNHIP_LAUNCH_W16(3, 0);
-    }
-#undef SNNHIP_LAUNCH_W16
-    SNNHIP_CHECK_HIP(hipGetLastError());
-    return SNNHIP_OK;
-}
-
-int espcn_fused_b_u16_launch(hipStream_t stream, const FusedBParams& p, const U16OutCfg& qout, const float* x, const float* w, const float* ep, unsigned short* y,
-                             hipEvent_t evStart, hipEvent_t evStop) {
-    dim3 grid(p.tilesX * p.tilesY * p.N); // one block per tile
-    if (act_is_simple(p.act.act)) SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u16_kernel<B_TW, B_TH, true>), grid, dim3(256), 0, stream, evStart, evStop, p, qout, x, w, ep, y);
-    else SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u16_kernel<B_TW, B_TH, false>), grid, dim3(256), 0, stream, evStart, evStop, p, qout, x, w, ep, y);
-    SNNHIP_CHECK_HIP(hipGetLastError());
-    return SNNHIP_OK;
-}
-
-int espcn_fused_b_launch(hipStream_t stream, const FusedBParams& p, bool wino, bool u8out, const U8OutCfg& qout, const float* x, const float* w,
-                         const float* ep, void* y, hipEvent_t evStart, hipEvent_t evStop) {
-    dim3 grid(p.tilesX * p.tilesY * p.N); // one block per tile
+int espcn_fused_b_launch(hipStream_t stream, const FusedBParams& p, bool wino, const FrameOut& f, const float* x, const float* w, const float* ep, void* y,
+                         hipEvent_t evStart, hipEvent_t evStop) {
+    SNNHIP_REQUIRE(f.bits == 0 || espcn_fused_b_takes_frame(wino), "espcn_fused_b: the Winograd form writes no %d-bit frame", f.bits);
+    const dim3 grid(p.tilesX * p.tilesY * p.N); // one block per tile
     const bool simple = act_is_simple(p.act.act);
-    float* y32 = static_cast<float*>(y);
-    unsigned char* y8 = static_cast<unsigned char*>(y);
     if (wino) {
+        float* y32 = static_cast<float*>(y);
         if (simple) SNNHIP_LAUNCH_EV((conv3x3_c16o4_wino_d2s_tanh_kernel<true>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, y32);
         else SNNHIP_LAUNCH_EV((conv3x3_c16o4_wino_d2s_tanh_kernel<false>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, y32);
-    } else if (u8out) {
-        if (simple) SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u8_kernel<B_TW, B_TH, true>), grid, dim3(256), 0, stream, evStart, evStop, p, qout, x, w, ep, y8);
-        else SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_u8_kernel<B_TW, B_TH, false>), grid, dim3(256), 0, stream, evStart, evStop, p, qout, x, w, ep, y8);
+    } else if (simple) {
+        launch_b_valu<true>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
     } else {
-        if (simple) SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_kernel<B_TW, B_TH, true>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, y32);
-        else SNNHIP_LAUNCH_EV((conv3x3_c16o4_d2s_tanh_kernel<B_TW, B_TH, false>), grid, dim3(256), 0, stream, evStart, evStop, p, x, w, ep, y32);
+        launch_b_valu<false>(stream, grid, p, f, x, w, ep, y, evStart, evStop);
     }
     SNNHIP_CHECK_HIP(hipGetLastError());
     return SNNHIP_OK;
