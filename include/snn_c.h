@@ -170,8 +170,8 @@ int snn_model_create10(const char* json_path, int device, int in_w, int in_h, in
  * snn_model_describe lists both launches.  Returns -1, before anything is built on the device, for a null struct, for what snn_model_create8
  * refuses, for an out_w or out_h that is odd or below 2 and for out_w / in_w or out_h / in_h outside [1/2, 4]; and, once the model file gives r,
  * for an output larger than r * in or smaller than r * in / 2 on either axis (the logged message names r and says which r would fit).
- * Not offered: RGB output at a fitted size, fitted RGB8 colour frames, grey frames (the plan itself takes them: snnhip_plane_fit_plan_create),
- * ratios below 1/2.  The reference has nothing for this: its vendored libyuv scales planes on the CPU with box / bilinear filters. */
+ * RGB output at a fitted size and fitted RGB8 colour frames are snn_model_create13 below.  Not offered: grey frames (the plan itself takes them:
+ * snnhip_plane_fit_plan_create), ratios below 1/2.  The reference has nothing for this: its vendored libyuv scales planes on the CPU with box / bilinear filters. */
 typedef struct snn_fit_io {
     snn_video_io video;
     int out_w, out_h;
@@ -193,8 +193,9 @@ int snn_model_create11(const char* json_path, int device, int in_w, int in_h, in
  * as above, a fitted size together with an RGB end, and everything the NV12 counterpart of the path refuses: a model that is not one channel in and
  * out, odd extents, maxval other than 255 (8-bit) or outside 255 .. 4095 (16-bit) or with maxval + 1 not a multiple of 256, a shift that does not fit, an unknown
  * siting or range, a matrix outside 0 < kr, 0 < kb, kr + kb < 1, batch < 1; the fitted size's rules (even, ratio in [1/2, 4]); and, once the model file
- * gives r, r = 1 with RGB in and a fitted size outside [r * in / 2, r * in].  Not offered: 4:2:2 / 4:4:4 and packed layouts, BGR order, RGB output at a
- * fitted size, 16-bit RGB -> I010, pitched DEVICE surfaces (the device tensors stay dense). */
+ * gives r, r = 1 with RGB in and a fitted size outside [r * in / 2, r * in].  RGB output at a fitted size comes through snn_model_create13 below,
+ * not through this struct.  Not offered: 4:2:2 / 4:4:4 and packed layouts, BGR order, 16-bit RGB -> I010, pitched DEVICE surfaces (the device tensors
+ * stay dense). */
 enum { SNN_IO_I420 = 0x401, SNN_IO_I420_16 = 0x501 }; /* (low byte = the model's channel count) */
 typedef struct snn_planar_io {
     int in_format;  /* SNN_IO_I420, SNN_IO_I420_16, or SNN_IO_RGB8 / SNN_IO_RGBA8 (capture in) */
@@ -205,6 +206,37 @@ typedef struct snn_planar_io {
 } snn_planar_io;      /* 10 * 4 bytes */
 int snn_model_create12(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_planar_io* io, snn_model** out);
+/* RGB frames at ANY output size behind a luma-only model: what a display path asks for (720p to 1080p through the x2 or the x3 model, 1080p to
+ * 1440p).  Through a struct and an entry point of their own: every earlier struct and entry point keeps its layout, behaviour and refusals
+ * (snn_model_create12 still refuses a fitted size together with an RGB end).  Two paths, every launch on one stream and inside the recorded graph
+ * with capture_graph:
+ *     NV12 / P010 / I420 / I010 -> RGB(A) at out_w x out_h    4 launches   the model built exactly as snn_model_create9 builds it (planar planes:
+ *                                                                          snn_model_create12's RGB path), then [luma fit] and [rgb fit]
+ *     RGB8 / RGBA8 -> the same format at out_w x out_h        5 launches   the model built exactly as snn_model_create7 builds it with the luma maps
+ *                                                                          in_mean 0, in_norm 1 / 255, out_scale 255, out_offset 0: snnhip_rgb_luma in
+ *                                                                          front, then [luma fit] and [rgb fit]
+ * [luma fit] is snnhip_plane_fit_plan_create with C = 1 (centre) from the model's r-fold luma frame to out_h x out_w, exactly as in
+ * snn_model_create11's path; [rgb fit] is snnhip_rgb_fit_plan_create from that plane and the ORIGINAL chroma planes (or the colour frame that went
+ * in) to the RGB frame (include/snnhip.h states the arithmetic).  No r-fold chroma plane and no r-fold RGB frame exists anywhere; ESPCN stays its
+ * two fused kernels with folded ends (the fp16 opt-in works too).  snn_model_upload_frame_nv12 / _planes / _u8 take the frames as on the paths
+ * above; snn_model_download_frame_u8 / _u16 return [batch][out_h][out_w][C] (A = maxval << shift from video, the alpha of the source pixel
+ * underneath from RGBA8); snn_model_describe lists both launches; snn_model_reference_frame / snn_model_frame_metrics work on the fitted frame (one
+ * packed plan).  out_w and out_h need not be even.  Returns -1, before anything is built on the device, for a null struct, for what
+ * snn_model_create9 / snn_model_create12 (video in) or snn_model_create7 (RGB in) refuses, for formats that do not pair up (video in: RGB8 / RGBA8
+ * for 8-bit, RGB16 / RGBA16 for 16-bit; RGB in: the same format out), for out_w or out_h below 1 and for out / in outside [1/2, 4] (video in) or
+ * [1, 4] (RGB in) on either axis; and, once the model file gives r, for an output outside [r * in / 2, r * in] on either axis or, with RGB in, below
+ * the input's extent -- the colour frame is never shrunk, so r = 1 then permits out = in alone (the logged message names r and says which r would
+ * fit).  Not offered: grey frames at a fitted size (the plan itself takes them: snnhip_plane_fit_plan_create), ratios below 1/2, RGB16 sources, BGR
+ * order, 4:2:2 / 4:4:4, a fused luma-fit + RGB launch. */
+typedef struct snn_rgb_fit_io {
+    int in_format;  /* SNN_IO_NV12, SNN_IO_NV12_16, SNN_IO_I420, SNN_IO_I420_16, or SNN_IO_RGB8 / SNN_IO_RGBA8 */
+    int out_format; /* video in: RGB8 / RGBA8 (8-bit), RGB16 / RGBA16 (16-bit); RGB in: the same format */
+    int maxval, shift, siting, range; /* video in: as snn_video_rgb_io; RGB in: not looked at */
+    float kr, kb;
+    int out_w, out_h; /* the size of the RGB frame that comes back; need not be even */
+} snn_rgb_fit_io;     /* 10 * 4 bytes */
+int snn_model_create13(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_rgb_fit_io* io, snn_model** out);
 /* Frames as plane pointers with row pitches (ffmpeg's data[] / linesize[]).  `planes` holds batch * n_planes pointers, frame by frame, in the order
  * Y, Cb, Cr (a YV12 caller swaps the last two) for a planar end, n_planes = 3; Y, CbCr for the NV12 / P010 ends of models made by snn_model_create8
  * / 9 / 10 / 11, n_planes = 2 (pitched NV12 surfaces).  pitch_bytes[n_planes] is the row pitch of each plane, the same for every frame.  Planes that

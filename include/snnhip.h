@@ -570,8 +570,9 @@ int snnhip_rgb_cbcr_planar_plan_create(snnhip_ctx* ctx, const snnhip_rgb_cbcr_de
  * message names the axis and both extents), bad dims, and dtype, maxval, shift and siting as chroma_up does; snnhip_plan_run for a tensor of another
  * dtype or shape at either end.  snnhip_plan_describe: "plane_fit_u8 c=2 1440x2560->1080x1920 siting=left tile=22x128 taps=8 ... kernel=
  * plane_fit_kernel" (the tile in output pixels).  snnhip_plan_cost counts the input once and the output once.
- * Not built: RGB output at a fitted size, fitted RGB8 colour frames, ratios below 1/2 (they need more than eight taps); the host mirror
- * (include/snn_c.h, snn_model_create11) puts this plan behind NV12 / P010 models only, grey frames go through the plan itself.  The reference has
+ * RGB output at a fitted size and fitted RGB8 colour frames are snnhip_rgb_fit_plan_create below, behind this plan with C = 1 on the luma frame.
+ * Not built: ratios below 1/2 (they need more than eight taps); the host mirror (include/snn_c.h, snn_model_create11) puts this plan behind
+ * NV12 / P010 models only, grey frames go through the plan itself.  The reference has
  * nothing for this: the libyuv it vendors scales planes on the CPU with box / bilinear filters. */
 typedef struct { int N, H, W, C; int OH, OW; int dtype; int maxval, shift; int siting; } snnhip_plane_fit_desc;
 int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run */
@@ -580,6 +581,53 @@ int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* d
  * one with SNNHIP_SITING_CENTRE) and keeps them in device memory.  SNNHIP_E_INVALID with a message for a ratio outside [1/2, 4], a null pointer,
  * too little room and an unknown siting. */
 int snnhip_fit_taps(int in, int out, int siting, float* weights, int* base, int capacity);
+
+/* Packed RGB at any output size behind a luma-only model: the luma frame ALREADY at the output size (the model's r-fold frame through
+ * snnhip_plane_fit_plan_create with C = 1, centre) and the ORIGINAL low-resolution chroma source in, RGB or RGBA at the output size out, in one
+ * launch -- 720p to 1080p through the x2 or the x3 model, 1080p to 1440p.  No r-fold chroma plane and no r-fold RGB frame exists anywhere.  The two
+ * fixed-phase RGB sinks above (yuv_rgb, ycc_merge) keep r or 2r phases in registers and cannot take a table per coordinate; this plan has
+ * plane_fit's shape.  DESIGN.md section 4.24.  The contract, stated once:
+ *   Shapes: inputs[0] = Yfit [N][OH][OW][1]; inputs[1] = the chroma source, by `source`; output [N][OH][OW][C], C = 3 (R, G, B) or 4 (+ A); run
+ *     with snnhip_plan_run_n, 2 inputs.  H, W of the desc are the chroma source's extent: the chroma plane's for the two video sources, the
+ *     low-resolution frame's for SNNHIP_RGB_FIT_RGB.  The source is only ever enlarged: a 4:2:0 chroma plane 2r/2 .. 2r-fold, an RGB frame 1 .. r-fold.
+ *   Phase: separable, each axis with its own ratio, 1 <= O / I <= 8.  Output X reads source position s = (X + 1/2) I / O - off: the output is a luma
+ *     grid.  off = 1/2 on the vertical axis, on a horizontal axis with SNNHIP_SITING_CENTRE and always for SNNHIP_RGB_FIT_RGB; off = 1/4 on the
+ *     horizontal axis of a left-sited 4:2:0 plane (chroma sample i sits at luma column 2i): yuv_rgb's phase to the luma grid, NOT plane_fit's to a
+ *     chroma grid.  In integers: a = 4 off (2 or 1), Nn = (4X + 2) I - a O, D = 4 O, base = floor(Nn / D), t = (Nn - base D) / D.
+ *   Weights: plane_fit's rule with f = 1: the eight Keys values (a = -0.5) at |k - 3 - t| summed in ascending order in double, each divided by the
+ *     sum and rounded to float.  The outer four are exactly 0; the table keeps the inner four, taps at base - 1 .. base + 2, indices clamped to the
+ *     source (replicate edge).  Vertical, then horizontal, fp32 accumulation.
+ *   Video sources (SNNHIP_RGB_FIT_CBCR, SNNHIP_RGB_FIT_PLANAR): everything is yuv_rgb's.  Values are float(u >> shift); what is filtered is the
+ *     sample minus Coff; the five coefficients are snnhip_yuv_rgb_coefficients'; per output pixel yl = cy (Yfit - Yoff), R = yl + crv Cr~,
+ *     B = yl + cbu Cb~, G = yl - (cgv Cr~ + cgu Cb~), full-range RGB, q = unsigned(clamp(rint(.), 0, maxval)) << shift, A = maxval << shift.  Yfit
+ *     and the output have the chroma tensor's dtype (SNNHIP_U8 or SNNHIP_U16, maxval <= 4095, maxval + 1 a multiple of 256).
+ *   RGB source (SNNHIP_RGB_FIT_RGB, SNNHIP_U8 only; maxval, shift, siting and range of the desc are not read): everything is ycc_merge's.  Per
+ *     low-resolution pixel the unquantised ylo (the one device function of rgb_luma and ycc_merge), dR = R - ylo, dB = B - ylo, resampled;
+ *     R' = Yfit + dR~, B' = Yfit + dB~, G' = Yfit - (kr dR~ + kb dB~) / kg, q = clamp(rint(.), 0, 255); for C = 4 the alpha byte of source pixel
+ *     ((2Y + 1) H / (2 OH), (2X + 1) W / (2 OW)) by integer division (at OH = rH that is ycc_merge's Y / r).
+ *   Consequences: for O = 2r I the table is snnhip_bicubic_taps_420's row X mod 2r and for O = r I (centre) snnhip_bicubic_taps' row X mod r, with
+ *     the same bases and the weights to one float ulp (the division by a sum that is 1 to 1e-15).  O == I with off = 1/2 gives base = X and weights
+ *     (0, 1, 0, 0).  Neutral chroma, or a grey source frame, gives R = G = B = the quantised luma term, byte for byte; constant chroma planes give
+ *     constant chroma terms.  In fp32 the value in front of the rounding stays within 2.7e-5 / 1.2e-4 / 4.6e-4 (video, 8 / 10 / 12 bits) and 6.3e-5
+ *     (RGB source, whole-range bytes) of a float64 evaluation (measured: tests/rgb_fit_ref.py).
+ * Plan creation returns SNNHIP_E_INVALID with a message starting "rgb_fit desc" for bad dims, C outside {3, 4}, an unknown source, a ratio outside
+ * [1, 8] on either axis (the message names the axis and both extents), the RGB source with a dtype other than SNNHIP_U8, and for the video sources
+ * everything yuv_rgb refuses about dtype, maxval, shift, siting and range; kr, kb outside 0 < kr, 0 < kb, kr + kb < 1 for every source.  It also
+ * checks what the kernel relies on -- bases never step back, no tile's source span exceeds its LDS rows -- and refuses otherwise.
+ * snnhip_plan_run_n refuses a tensor of another dtype or shape at any position.  snnhip_plan_describe: "rgb_fit_u8 src=cbcr c=3 360x640->1080x1920
+ * siting=left range=limited tile=22x256 taps=4 lds=49152 ... kernel=rgb_fit_kernel" (the tile in output pixels).  snnhip_plan_cost counts both
+ * inputs once and the output once.  Not built: a fused luma fit (three float planes through LDS), RGB16 sources, BGR order, 4:2:2 / 4:4:4.  The
+ * reference has nothing for this: the libyuv it vendors scales and converts on the CPU. */
+#define SNNHIP_RGB_FIT_CBCR 0   /* inputs[1] = [N][H][W][2] interleaved CbCr (NV12 / P010) */
+#define SNNHIP_RGB_FIT_PLANAR 1 /* inputs[1] = [2N][H][W][1], plane 2n = Cb, 2n + 1 = Cr (I420 / I010) */
+#define SNNHIP_RGB_FIT_RGB 2    /* inputs[1] = U8 [N][H][W][C], the original colour frame */
+typedef struct { int N, H, W; int OH, OW; int C; int source; int dtype; int maxval, shift; int siting, range; float kr, kb; } snnhip_rgb_fit_desc;
+int snnhip_rgb_fit_plan_create(snnhip_ctx* ctx, const snnhip_rgb_fit_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_n, 2 inputs */
+/* host only, no context: the table of one axis with `in` source samples and `out` outputs: weights [out][4] (capacity >= 4 * out floats) and base
+ * [out] ints; output X reads in[clamp(base[X] - 1 + k)] with weights[X][k], k = 0..3.  SNNHIP_SITING_LEFT is the horizontal axis of a left-sited
+ * 4:2:0 plane, SNNHIP_SITING_CENTRE everything else.  The plan builds its two tables with this function and keeps them in device memory.
+ * SNNHIP_E_INVALID with a message for a ratio outside [1, 8], a null pointer, too little room and an unknown siting. */
+int snnhip_rgb_fit_taps(int in, int out, int siting, float* weights, int* base, int capacity);
 
 /* Frame quality on the device: PSNR and SSIM between a test frame and a reference frame, so that what an arithmetic choice (fused fp32, the fp16
  * opt-in, 8 / 10 / 12-bit frame ends) or a trained model costs in picture quality can be stated in dB without downloading every output frame.

@@ -122,6 +122,11 @@ class PlaneFitDesc(C.Structure):
                 ("siting", C.c_int)]
 
 
+class RgbFitDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("OH", C.c_int), ("OW", C.c_int), ("C", C.c_int), ("source", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int),
+                ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
+
+
 class FrameMetricsDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int)]
 
@@ -219,6 +224,8 @@ SIGNATURES = {
     "snnhip_rgb_cbcr_planar_plan_create": (C.c_int, [_P, C.POINTER(RgbCbcrDesc), C.POINTER(_P)]),
     "snnhip_plane_fit_plan_create": (C.c_int, [_P, C.POINTER(PlaneFitDesc), C.POINTER(_P)]),
     "snnhip_fit_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
+    "snnhip_rgb_fit_plan_create": (C.c_int, [_P, C.POINTER(RgbFitDesc), C.POINTER(_P)]),
+    "snnhip_rgb_fit_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_frame_metrics_plan_create": (C.c_int, [_P, C.POINTER(FrameMetricsDesc), C.POINTER(_P)]),
     "snnhip_frame_metrics_read": (C.c_int, [_P, C.POINTER(FrameMetricsRow), C.c_int]),
     "snnhip_frame_metrics_psnr": (C.c_double, [C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -895,6 +902,32 @@ def fit_taps(n_in, n_out, siting="centre", capacity=None):
     w = np.zeros((n, 8), np.float32)
     base = (C.c_int * max(n, 1))()
     check(lib().snnhip_fit_taps(n_in, n_out, SITING.get(siting, siting), _fptr(w), base, w.size if capacity is None else capacity))
+    return w, np.array(base[:n], np.int32)
+
+
+RGB_FIT_SOURCE = {"cbcr": 0, "planar": 1, "rgb": 2}  # SNNHIP_RGB_FIT_*
+
+
+def rgb_fit_plan(ctx, N, H, W, OH, OW, Cc, source="cbcr", dtype=U8, maxval=None, shift=0, siting="left", range="limited", kr=BT601[0], kb=BT601[1]):
+    """plan.run([Yfit [N][OH][OW][1], the chroma source], out [N][OH][OW][Cc]): packed RGB (Cc = 3) or RGBA (Cc = 4) at any output size from the luma
+    frame already at that size and the ORIGINAL chroma source, enlarged 1- to 8-fold, in one launch (include/snnhip.h states the arithmetic).
+    source "cbcr": CbCr [N][H][W][2]; "planar": [2N][H][W][1], plane 2n = Cb, 2n + 1 = Cr; "rgb": the U8 colour frame [N][H][W][Cc].  H, W are the
+    source's extent; maxval defaults to 255 (a 16-bit frame must say)."""
+    if maxval is None:
+        maxval = 255
+    d = RgbFitDesc(N, H, W, OH, OW, Cc, RGB_FIT_SOURCE.get(source, source), dtype, maxval, shift, SITING.get(siting, siting), RANGE.get(range, range), kr, kb)
+    h = _P()
+    check(lib().snnhip_rgb_fit_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def rgb_fit_taps(n_in, n_out, siting="centre", capacity=None):
+    """snnhip_rgb_fit_taps (host side only, no GPU): (weights float32 [n_out][4], base int32 [n_out]) of one enlarging axis to the luma grid; output
+    X reads in[clamp(base[X] - 1 + k)] with weights[X][k]; siting "left" is the horizontal axis of a left-sited 4:2:0 plane."""
+    n = max(int(n_out), 0)
+    w = np.zeros((n, 4), np.float32)
+    base = (C.c_int * max(n, 1))()
+    check(lib().snnhip_rgb_fit_taps(n_in, n_out, SITING.get(siting, siting), _fptr(w), base, w.size if capacity is None else capacity))
     return w, np.array(base[:n], np.int32)
 
 

@@ -25,6 +25,7 @@ SIGNATURES = {
     "snn_model_create10": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create11": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create12": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create13": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_upload_frame_planes": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     "snn_model_download_frame_planes": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     "snn_model_upload_frame_nv12": (C.c_int, [_P, _P]),
@@ -199,6 +200,12 @@ class PlanarIO(C.Structure):
                 ("kr", C.c_float), ("kb", C.c_float), ("out_w", C.c_int), ("out_h", C.c_int)]
 
 
+class RgbFitIO(C.Structure):
+    """snn_rgb_fit_io (include/snn_c.h): video or colour frames in, an RGB / RGBA frame at out_w x out_h out around a luma-only model."""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("maxval", C.c_int), ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int),
+                ("kr", C.c_float), ("kb", C.c_float), ("out_w", C.c_int), ("out_h", C.c_int)]
+
+
 # name: (SNN_IO_NV12 / SNN_IO_NV12_16 / SNN_IO_I420 / SNN_IO_I420_16, maxval, shift); I010 is ffmpeg's yuv420p10le: 10 bits in the low end of 2 bytes
 VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6), "I420": (0x401, 255, 0), "I010": (0x501, 1023, 0)}
 PLANAR_FORMATS = ("I420", "I010")
@@ -214,7 +221,7 @@ class Model:
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
                  out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114, video=None,
-                 siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited", out_size=None):
+                 siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited", out_size=None, rgb_size=None):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
         output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
@@ -242,7 +249,11 @@ class Model:
         video "I420" / "I010" (snn_model_create12): planar 4:2:0 frames, what software decoders and encoders use -- everything above for "NV12" /
         "P010" with the triple (y, cb, cr) in place of the pair: alone (the same planar format comes back), with out_size, with video_out "RGB8" /
         "RGBA8" ("I420") or "RGB16" / "RGBA16" ("I010"); and colour "RGB8" / "RGBA8" with video_out "I420".  video_range sets the luma plane's maps on
-        every one of them (in_means / in_norms / out_scale / out_offset are not used).  upload_planes / download_planes take arrays with a row pitch."""
+        every one of them (in_means / in_norms / out_scale / out_offset are not used).  upload_planes / download_planes take arrays with a row pitch.
+        rgb_size (w, h) beside video and video_out "RGB8" / ... , or beside colour "RGB8" / "RGBA8" alone (snn_model_create13): the RGB frame comes
+        back at that size (it need not be even), between half and all of r times the input on each axis and, with colour, no smaller than the
+        input -- the model's luma frame resampled to the size, then RGB from it and the ORIGINAL chroma planes (or the colour frame that went in)
+        in one more launch; no r-fold chroma or RGB frame is formed.  With colour the luma maps are 0, 1 / 255, 255, 0 (in_means / ... are not used)."""
         self.h = _P()
         self.batch = batch
         self.video = video  # the upload end: None = one array (the model's frame or a colour frame), else planes of this format
@@ -251,7 +262,29 @@ class Model:
         self.out_size = None
         in_channels, u8 = c, (np.uint8, np.uint8)
         assert out_size is None or (video is not None and video_out is None and colour is None), "out_size fits an NV12 / P010 frame: it goes with video= alone"
-        if colour is not None and video_out is not None:
+        if rgb_size is not None:
+            assert out_size is None and input_format is None and output_format is None, "rgb_size is the size of an RGB frame: not beside out_size / input_format / output_format"
+            assert (video is not None and video_out in VIDEO_OUT_FORMATS and colour is None) or (colour in ("RGB8", "RGBA8") and video is None and video_out is None), \
+                "rgb_size goes with video= and video_out=\"RGB8\" / \"RGBA8\" / \"RGB16\" / \"RGBA16\", or with colour=\"RGB8\" / \"RGBA8\" alone"
+            assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
+            size = self.out_size = (int(rgb_size[0]), int(rgb_size[1]))
+            if colour is not None:
+                in_channels = self.out_channels = {"RGB8": 3, "RGBA8": 4}[colour]
+                self.frame_dtypes = u8
+                io = RgbFitIO(FRAME_FORMATS[colour], FRAME_FORMATS[colour], 255, 0, SITINGS["centre"], VIDEO_RANGES["full"], kr, kb, *size)
+            else:
+                assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
+                assert siting in SITINGS, "siting is \"left\" or \"centre\""
+                fmt, maxval, shift = VIDEO_FORMATS[video]
+                pair, self.out_channels = VIDEO_OUT_FORMATS[video_out]
+                wide = fmt in (0x301, 0x501)
+                assert pair == (0x301 if wide else 0x201), "%s frames come back as %s" % (video, "RGB16 / RGBA16" if wide else "RGB8 / RGBA8")
+                maxval = maxval if video_maxval is None else video_maxval
+                shift = shift if video_shift is None else video_shift
+                in_channels, self.frame_dtypes = 1, ((np.uint16, np.uint16) if wide else u8)
+                io = RgbFitIO(fmt, FRAME_FORMATS[video_out], maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, *size)
+            entry = 13
+        elif colour is not None and video_out is not None:
             assert video is None, "colour frames go in: video= names NV12 / P010 frames at the input"
             assert colour in ("RGB8", "RGBA8"), "colour is \"RGB8\" or \"RGBA8\""
             assert video_out in ("NV12", "I420"), "a colour frame leaves as video_out=\"NV12\" or \"I420\""
@@ -309,7 +342,7 @@ class Model:
                 entry, io = 6, FrameIO2(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps, frame_in_shift, frame_out_maxval, frame_out_shift)
             else:
                 entry, io = 5, FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps)
-        self.planar = entry == 12
+        self.planar = entry == 12 or (entry == 13 and video in PLANAR_FORMATS)
         self.in_shape = (h, w, in_channels) if batch == 1 else (batch, h, w, in_channels)
         create = getattr(lib(), "snn_model_create%d" % entry)
         assert create(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph), int(batch),
@@ -332,6 +365,8 @@ class Model:
         if self.out_end == "yuv":
             oh, ow = (self.out_size[1], self.out_size[0]) if self.out_size is not None else (d[0], d[1])
             return self._download_planar(oh, ow) if self.planar else self._download_video(oh, ow)
+        if self.out_size is not None:  # rgb_size: the RGB frame at that size
+            d = (self.out_size[1], self.out_size[0], d[2])
         if self.out_channels:
             d = (d[0], d[1], self.out_channels)
         out = np.empty(tuple(d) if self.batch == 1 else (self.batch,) + tuple(d), dtype=self.frame_dtypes[1])

@@ -202,6 +202,37 @@ bool resolveFrames(const snn_planar_io* io, int in_w, int in_h, int in_c, int ba
     return ok;
 }
 
+// ---- snn_model_create13: RGB at out_w x out_h.  A video source resolves through snn_model_create9's struct (snn_model_create12's for planar planes),
+// a colour source through snn_model_create7's with the full-range luma maps; only the sink and the size are added.  The ratio rules that need no r:
+// the r-fold frame (r = 1..4) is brought down by at most a half, so out / in lies in [1/2, 4]; a colour frame is never shrunk, [1, 4]
+bool resolveFrames(const snn_rgb_fit_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* s) {
+    if (!io || io->out_w < 1 || io->out_h < 1 || in_w < 1 || in_h < 1) return false;
+    if (io->out_w > 4ll * in_w || io->out_h > 4ll * in_h) return false;
+    if (isRgb8(io->in_format)) {
+        if (io->out_format != io->in_format || io->out_w < in_w || io->out_h < in_h) return false;
+        const snn_colour_io c{io->in_format, io->kr, io->kb, 0.0f, 1.0f / 255.0f, 255.0f, 0.0f};
+        if (!resolveFrames(&c, in_w, in_h, in_c, batch, s)) return false;
+        s->sink = Sink::RGB_MERGED_FITTED;
+    } else {
+        if (2ll * io->out_w < in_w || 2ll * io->out_h < in_h) return false;
+        const bool planar = io->in_format == SNN_IO_I420 || io->in_format == SNN_IO_I420_16;
+        if (!isRgb8(io->out_format) && io->out_format != SNN_IO_RGB16 && io->out_format != SNN_IO_RGBA16) return false; // (the resolvers below pair it with the input)
+        if (planar) {
+            const snn_planar_io p{io->in_format, io->out_format, io->maxval, io->shift, io->siting, io->range, io->kr, io->kb, 0, 0};
+            if (!resolveFrames(&p, in_w, in_h, in_c, batch, s)) return false;
+        } else {
+            const snn_video_rgb_io v{io->in_format, io->out_format, io->maxval, io->shift, io->siting, io->range, io->kr, io->kb};
+            if (!resolveFrames(&v, in_w, in_h, in_c, batch, s)) return false;
+        }
+        if (s->sink != Sink::RGB_FROM_YUV) return false;
+        s->sink = Sink::RGB_FROM_YUV_FITTED;
+    }
+    s->fitW = io->out_w;
+    s->fitH = io->out_h;
+    s->entry = "snn_model_create13";
+    return true;
+}
+
 bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int batch, FrameSpec* s) {
     if (!s || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return false;
     *s = FrameSpec();
@@ -214,6 +245,7 @@ bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int 
     case 10: return resolveFrames(static_cast<const snn_encode_io*>(io), in_w, in_h, in_c, batch, s);
     case 11: return resolveFrames(static_cast<const snn_fit_io*>(io), in_w, in_h, in_c, batch, s);
     case 12: return resolveFrames(static_cast<const snn_planar_io*>(io), in_w, in_h, in_c, batch, s);
+    case 13: return resolveFrames(static_cast<const snn_rgb_fit_io*>(io), in_w, in_h, in_c, batch, s);
     default: return false;
     }
 }
@@ -225,24 +257,31 @@ bool framesFitModel(const FrameSpec& spec, int in_w, int in_h, const InferenceGr
     if (out.channels != 1 || r < 1 || r > 4 || out.width != r * w || out.height != r * h) return false;
     // a 4:2:0 frame made from RGB: r = 2..4 (r = 1 would decimate the chroma grid) and an even extent
     if (spec.sink == Sink::YUV420_FROM_RGB && (r < 2 || (r * w) % 2 || (r * h) % 2)) return false;
-    if (spec.sink != Sink::FITTED) return true;
-    // the r-fold frame is resampled DOWN to the target: r * in / 2 <= out <= r * in on both axes
+    if (spec.sink != Sink::FITTED && spec.sink != Sink::RGB_FROM_YUV_FITTED && spec.sink != Sink::RGB_MERGED_FITTED) return true;
+    // the r-fold frame is resampled DOWN to the target: r * in / 2 <= out <= r * in on both axes; and a colour frame that went in is never shrunk
+    // (its chroma differences are only enlarged), so r = 1 then permits out = in alone
+    const bool colourIn = spec.sink == Sink::RGB_MERGED_FITTED;
     const long long rw = static_cast<long long>(r) * in_w, rh = static_cast<long long>(r) * in_h;
-    if (spec.fitW <= rw && spec.fitH <= rh && 2ll * spec.fitW >= rw && 2ll * spec.fitH >= rh) return true;
+    auto fitsAt = [&](long long q) {
+        return spec.fitW <= q * in_w && spec.fitH <= q * in_h && 2ll * spec.fitW >= q * in_w && 2ll * spec.fitH >= q * in_h && (!colourIn || (spec.fitW >= in_w && spec.fitH >= in_h));
+    };
+    if (fitsAt(r)) return true;
     std::string fits;
     for (int q = 1; q <= 4; ++q)
-        if (spec.fitW <= 1ll * q * in_w && spec.fitH <= 1ll * q * in_h && 2ll * spec.fitW >= 1ll * q * in_w && 2ll * spec.fitH >= 1ll * q * in_h)
-            fits += (fits.empty() ? "" : ", ") + std::to_string(q);
-    SNN_LOGE("%s: the model is r = %u: %dx%d -> %lldx%lld, and %dx%d is %s; %s%s", spec.entry, r, in_w, in_h, rw, rh, spec.fitW, spec.fitH,
-             (spec.fitW > rw || spec.fitH > rh) ? "larger than that" : "less than half of that", fits.empty() ? "no r = 1..4 fits both axes" : "a model of r = ", fits.c_str());
+        if (fitsAt(q)) fits += (fits.empty() ? "" : ", ") + std::to_string(q);
+    const char* why = (spec.fitW > rw || spec.fitH > rh)             ? "larger than that"
+                      : (2ll * spec.fitW < rw || 2ll * spec.fitH < rh) ? "less than half of that"
+                                                                       : "smaller than the colour frame that goes in, which is never shrunk";
+    SNN_LOGE("%s: the model is r = %u: %dx%d -> %lldx%lld, and %dx%d is %s; %s%s", spec.entry, r, in_w, in_h, rw, rh, spec.fitW, spec.fitH, why,
+             fits.empty() ? "no r = 1..4 fits both axes" : "a model of r = ", fits.c_str());
     return false;
 }
 
 std::string formatFrameSpec(const FrameSpec& s) {
     static const char* const sources[] = {"model", "rgb", "yuv420"};
-    static const char* const sinks[] = {"model", "rgb_merged", "chroma_up", "fitted", "rgb_from_yuv", "yuv420_from_rgb"};
+    static const char* const sinks[] = {"model", "rgb_merged", "chroma_up", "fitted", "rgb_from_yuv", "yuv420_from_rgb", "rgb_from_yuv_fitted", "rgb_merged_fitted"};
     static_assert(sizeof(sources) / sizeof(*sources) == static_cast<size_t>(Source::YUV420) + 1, "one name for every FrameSpec::Source");
-    static_assert(sizeof(sinks) / sizeof(*sinks) == static_cast<size_t>(Sink::YUV420_FROM_RGB) + 1, "one name for every FrameSpec::Sink");
+    static_assert(sizeof(sinks) / sizeof(*sinks) == static_cast<size_t>(Sink::RGB_MERGED_FITTED) + 1, "one name for every FrameSpec::Sink");
     const snn_frame_io2& m = s.model;
     auto four = [](const float* v) { return formatString("%.9g,%.9g,%.9g,%.9g", v[0], v[1], v[2], v[3]); };
     return formatString("in=0x%x out=0x%x means=%s norms=%s scale=%s offset=%s in_shift=%d out_maxval=%d out_shift=%d", m.in_format, m.out_format, four(m.in_means).c_str(),

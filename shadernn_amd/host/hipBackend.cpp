@@ -157,6 +157,20 @@ void HipBackend::initFrames(const FrameSpec& f, int n, int inH, int inW, int inC
         stepsOut.push_back({p, frameOutT, chromaInT, downloadT, "[rgb out]", "snnhip_plan_run_n (luma + chroma plane -> RGB frame)"});
         break;
     }
+    case Sink::RGB_FROM_YUV_FITTED:
+    case Sink::RGB_MERGED_FITTED: { // the model's output luma frame resampled to the target, then RGB from it and the ORIGINAL chroma source (no r-fold chroma or RGB frame)
+        const bool video = f.sink == Sink::RGB_FROM_YUV_FITTED;
+        snnhip_plane_fit_desc ld{out[0], out[1], out[2], 1, f.fitH, f.fitW, vd, video ? f.maxval : 255, video ? f.shift : 0, SNNHIP_SITING_CENTRE}; // as Sink::FITTED
+        hipChk(snnhip_plane_fit_plan_create(ctx, &ld, &p), "snnhip_plane_fit_plan_create (luma)");
+        snnhip_tensor* lumaFitT = ownTensor(out[0], f.fitH, f.fitW, 1, vd, "snnhip_tensor_alloc (fitted luma plane)");
+        stepsOut.push_back({p, frameOutT, nullptr, lumaFitT, "[luma fit]", "snnhip_plan_run (luma frame -> fitted luma plane)"});
+        const int source = !video ? SNNHIP_RGB_FIT_RGB : f.planar ? SNNHIP_RGB_FIT_PLANAR : SNNHIP_RGB_FIT_CBCR;
+        snnhip_rgb_fit_desc d{in[0], video ? in[1] / 2 : in[1], video ? in[2] / 2 : in[2], f.fitH, f.fitW, f.channels, source, vd, f.maxval, f.shift, f.siting, f.range, f.kr, f.kb};
+        hipChk(snnhip_rgb_fit_plan_create(ctx, &d, &p), "snnhip_rgb_fit_plan_create");
+        downloadT = ownTensor(out[0], f.fitH, f.fitW, f.channels, vd, "snnhip_tensor_alloc (fitted RGB output frame)");
+        stepsOut.push_back({p, lumaFitT, video ? chromaInT : uploadT, downloadT, "[rgb fit]", "snnhip_plan_run_n (fitted luma plane + chroma source -> RGB frame)"});
+        break;
+    }
     case Sink::YUV420_FROM_RGB: { // the model's output frame IS the luma plane; the chroma planes from the colour input frame
         if (r < 2 || out[1] % 2 || out[2] % 2) SNN_RIP("an NV12 output frame needs r = 2..4 and an even extent: %dx%d -> %dx%d", in[1], in[2], out[1], out[2]);
         snnhip_rgb_cbcr_desc d{in[0], in[1], in[2], f.channels, r, f.siting, f.range, f.kr, f.kb};

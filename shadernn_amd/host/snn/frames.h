@@ -1,5 +1,5 @@
 // snn/frames.h -- the resolved description of a model's frame ends (HIP extension; device-free: nothing here touches the GPU).  Every
-// snn_model_create5..12 struct of include/snn_c.h resolves to ONE FrameSpec, and everything below the entry points -- createModel,
+// snn_model_create5..13 struct of include/snn_c.h resolves to ONE FrameSpec, and everything below the entry points -- createModel,
 // MixedInferenceCore::CreationParameters, HipBackend::initFrames -- takes that one description.
 #pragma once
 #include <string>
@@ -13,14 +13,15 @@ struct FrameSpec {
     // the model's own end formats and maps: SNN_IO_FLOAT, or the 8- / 16-bit frame whose conversion joins the fusion graph (ESPCN folds it into its kernels)
     snn_frame_io2 model{SNN_IO_FLOAT, SNN_IO_FLOAT, {0, 0, 0, 0}, {1, 1, 1, 1}, {1, 1, 1, 1}, {0, 0, 0, 0}, 0, 65535, 0};
     enum class Source { MODEL, RGB, YUV420 } source = Source::MODEL; // what the caller uploads: the model's frame, an RGB frame, luma + 4:2:0 chroma
-    // what comes back: the model's frame, the merged RGB frame, luma + r-fold chroma, luma + chroma fitted to fitW x fitH, RGB from luma + chroma, luma + chroma from RGB
-    enum class Sink { MODEL, RGB_MERGED, CHROMA_UP, FITTED, RGB_FROM_YUV, YUV420_FROM_RGB } sink = Sink::MODEL;
+    // what comes back: the model's frame, the merged RGB frame, luma + r-fold chroma, luma + chroma fitted to fitW x fitH, RGB from luma + chroma, luma + chroma from RGB,
+    // and the two RGB frames at fitW x fitH: from luma + chroma, merged with the colour frame that went in
+    enum class Sink { MODEL, RGB_MERGED, CHROMA_UP, FITTED, RGB_FROM_YUV, YUV420_FROM_RGB, RGB_FROM_YUV_FITTED, RGB_MERGED_FITTED } sink = Sink::MODEL;
     int channels = 0;                                  // of the RGB end(s): 3 or 4
     bool wide = false;                                 // the video end's samples sit in 2-byte containers
     int maxval = 255, shift = 0;                       // ... with this depth and alignment (the chroma planes'; the luma plane's are model's)
     int siting = SNN_SITING_LEFT, range = SNN_RANGE_LIMITED;
     float kr = 0.299f, kb = 0.114f;                    // the matrix of the RGB end
-    int fitW = 0, fitH = 0;                            // Sink::FITTED
+    int fitW = 0, fitH = 0;                            // Sink::FITTED, Sink::RGB_FROM_YUV_FITTED, Sink::RGB_MERGED_FITTED
     bool planar = false;                               // the chroma planes are separate Cb and Cr planes (I420 / I010), not one interleaved CbCr plane
     const char* entry = "snn_model_create5";           // the entry point the request came through (log lines name it)
 };
@@ -34,11 +35,13 @@ bool resolveFrames(const snn_video_rgb_io* io, int in_w, int in_h, int in_c, int
 bool resolveFrames(const snn_encode_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 bool resolveFrames(const snn_fit_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 bool resolveFrames(const snn_planar_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
-// ... by the number of the entry point, 5..12 (`io` is that entry point's struct)
+bool resolveFrames(const snn_rgb_fit_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
+// ... by the number of the entry point, 5..13 (`io` is that entry point's struct)
 bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 
 // The rules that need the model's factor r, from the output desc of its last layer: a frame path around the model needs one channel out at r = 1..4
-// times the input on both axes; luma + chroma from RGB r >= 2 and an even r * extent; a fitted size lies within [r * in / 2, r * in] (logged).
+// times the input on both axes; luma + chroma from RGB r >= 2 and an even r * extent; a fitted size lies within [r * in / 2, r * in], and is
+// no smaller than the colour frame that went in (logged).
 bool framesFitModel(const FrameSpec& spec, int in_w, int in_h, const InferenceGraph::IODesc& out);
 
 ColorFormat frameColorFormat(int snnIoFormat); // SNN_IO_R8 .. SNN_IO_RGBA16 -> ColorFormat (NONE for SNN_IO_FLOAT and anything else)

@@ -183,6 +183,11 @@ int snn_model_create12(const char* json_path, int device, int in_w, int in_h, in
     return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 12, io);
 }
 
+int snn_model_create13(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_rgb_fit_io* io, snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 13, io);
+}
+
 // one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame
 static int movePlane(snnhip_tensor* t, int batch, char* frames, size_t stride, size_t offset, bool upload) {
     const size_t total = snnhip_tensor_bytes(t), plane = total / static_cast<size_t>(batch);
@@ -344,7 +349,7 @@ static bool ensureMetrics(snn_model* m, const char* who) {
     if (!ctx) return false;
     const FrameSpec& f = m->core->frames();
     // the depth of the output frame: the video end's for an RGB frame made from it, otherwise the model's own output map (the luma plane's on a video end)
-    const bool fromVideo = f.sink == FrameSpec::Sink::RGB_FROM_YUV;
+    const bool fromVideo = f.sink == FrameSpec::Sink::RGB_FROM_YUV || f.sink == FrameSpec::Sink::RGB_FROM_YUV_FITTED;
     if (makeMetricsEnd(ctx, y, fromVideo ? f.maxval : f.model.out_maxval, fromVideo ? f.shift : f.model.out_shift, &m->metricsFrame) != 0) return false;
     snnhip_tensor* c = m->core->chromaOutput();
     if (c && makeMetricsEnd(ctx, c, f.maxval, f.shift, &m->metricsChroma) != 0) {

@@ -674,6 +674,190 @@ def main_fit(a):
     ctx.close()
 
 
+def main_rgb_fit(a):
+    """--video NV12 | P010 | I420 --video-out RGB8 | RGBA8 --rgb-fit WxH, or --colour RGB8 | RGBA8 --rgb-fit WxH: the RGB frame at that size (the chain,
+    the luma fit, rgb_fit; rgb_luma in front for a colour frame) beside the r-fold RGB step of the same r (yuv_rgb / ycc_merge), the fitted NV12
+    step (video, even sizes), the plane_fit + rgb_fit launches alone, a device copy of their bytes, rgb_fit and the fixed-phase RGB launch alone
+    from the trace, and end to end with one frame's H2D + D2H.  Alternated in one process in mirrored order."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi, models
+    from shadernn_amd.runner import _layer_plan
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    R = a.scale
+    OW, OH = (int(v) for v in a.rgb_fit.lower().split("x"))
+    colour = a.colour is not None
+    Cc = {"RGB8": 3, "RGBA8": 4}[a.colour if colour else a.video_out]
+    wide, planar = a.video == "P010", a.video == "I420"
+    maxval, shift, dt, npdt = (1023, 6, capi.U16, np.uint16) if wide else (255, 0, capi.U8, np.uint8)
+    k = (maxval + 1) / 256.0
+    yoff, yspan = (0.0, 255.0) if colour else (16.0 * k, 219.0 * k) if a.range == "limited" else (0.0, float(maxval))  # the luma maps snn_model_create13 derives
+    net = models.espcn_weights(seed=1, scale=R)
+    H, W = a.h or 2160 // R, a.w or 3840 // R
+    assert colour or (H % 2 == 0 and W % 2 == 0), "4:2:0 frames have even extents"
+    assert R * H >= OH >= R * H / 2 and R * W >= OW >= R * W / 2, "the target lies between half and all of the x%d frame %dx%d" % (R, R * W, R * H)
+    rng = np.random.default_rng(1)
+    layers, shape = [], (1, H, W, 1)
+    for layer in net["layers"]:
+        p = _layer_plan(ctx, layer, shape)
+        layers.append(p)
+        shape = p.out_shape()
+    if wide:
+        ends = (capi.u16_in_plan(ctx, 1, H, W, 1, (yoff, 0, 0, 0), (1 / yspan, 1, 1, 1), shift), capi.u16_out_plan(ctx, *shape, (yspan, 0, 0, 0), (yoff, 0, 0, 0), maxval, shift))
+    else:
+        ends = (capi.u8_in_plan(ctx, 1, H, W, 1, (yoff, 0, 0, 0), (1 / yspan, 1, 1, 1)), capi.u8_out_plan(ctx, *shape, (yspan, 0, 0, 0), (yoff, 0, 0, 0)))
+    grey = capi.chain_plan(ctx, [ends[0]] + layers + [ends[1]])
+    assert grey.num_steps() == 2, grey.describe()
+    fit_y = capi.plane_fit_plan(ctx, 1, R * H, R * W, 1, OH, OW, dt, maxval, shift, "centre")
+    oshape, rshape = (1, OH, OW, Cc), (1, R * H, R * W, Cc)
+    t_y = capi.Tensor(ctx, 1, H, W, 1, dtype=dt)
+    t_yhi, t_fy = capi.Tensor(ctx, *shape, dtype=dt), capi.Tensor(ctx, 1, OH, OW, 1, dtype=dt)
+    t_out, t_rout = capi.Tensor(ctx, *oshape, dtype=dt), capi.Tensor(ctx, *rshape, dtype=dt)
+    front = None
+    if colour:
+        src_h = rng.integers(0, 256, size=(1, H, W, Cc), dtype=np.uint8)
+        t_src_frame = capi.Tensor.from_numpy(ctx, src_h, dtype=capi.U8)
+        front = capi.rgb_luma_plan(ctx, 1, H, W, Cc)
+        rgb_fit = capi.rgb_fit_plan(ctx, 1, H, W, OH, OW, Cc, "rgb")
+        fixed = capi.ycc_merge_plan(ctx, 1, H, W, Cc, R)
+        ups = [(t_src_frame, src_h)]
+    else:
+        y_h = (rng.integers(int(16 * k), int(236 * k), size=(1, H, W, 1)) << shift).astype(npdt)
+        c_h = (rng.integers(int(16 * k), int(241 * k), size=(2 if planar else 1, H // 2, W // 2, 1 if planar else 2)) << shift).astype(npdt)
+        t_y.upload_u16(y_h) if wide else t_y.upload_u8(y_h)
+        t_src_frame = capi.Tensor.from_numpy(ctx, c_h, dtype=dt)
+        rgb_fit = capi.rgb_fit_plan(ctx, 1, H // 2, W // 2, OH, OW, Cc, "planar" if planar else "cbcr", dt, maxval, shift, a.siting, a.range)
+        mk = capi.yuv_rgb_planar_plan if planar else capi.yuv_rgb_plan
+        fixed = mk(ctx, 1, H // 2, W // 2, Cc, R, dt, maxval, shift, a.siting, a.range)
+        ups = [(t_y, y_h), (t_src_frame, c_h)]
+    nv12_fit = None
+    if not colour and OH % 2 == 0 and OW % 2 == 0:  # the fitted NV12 / I420 step of the same target
+        nv12_fit = capi.plane_fit_plan(ctx, 2 if planar else 1, H // 2, W // 2, 1 if planar else 2, OH // 2, OW // 2, dt, maxval, shift, a.siting)
+        t_fc = capi.Tensor(ctx, 2 if planar else 1, OH // 2, OW // 2, 1 if planar else 2, dtype=dt)
+    pair_bytes = int(fit_y.cost()[1] + rgb_fit.cost()[1])
+    half = pair_bytes // 2
+    t_csrc, t_cdst = capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half, 1, dtype=capi.U8)
+    t_csrc.upload_u8(np.random.default_rng(3).integers(0, 256, size=half, dtype=np.uint8))
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+
+    def run_model():
+        if front is not None:
+            front.run(t_src_frame, t_y)
+        grey.run(t_y, t_yhi)
+
+    def run_pair():
+        fit_y.run(t_yhi, t_fy)
+        rgb_fit.run([t_fy, t_src_frame], t_out)
+
+    def run_rgb_fitted():
+        run_model()
+        run_pair()
+
+    def run_rgb_rfold():
+        run_model()
+        fixed.run([t_yhi, t_src_frame], t_rout)
+
+    def run_nv12_fitted():
+        grey.run(t_y, t_yhi)
+        fit_y.run(t_yhi, t_fy)
+        nv12_fit.run(t_src_frame, t_fc)
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(t_cdst.data_ptr(), t_csrc.data_ptr(), half, stream)
+        assert rc == 0, rc
+
+    forms = {"rgb_fitted": run_rgb_fitted, "rgb_rfold": run_rgb_rfold, "fit_pair": run_pair, "copy": run_copy}
+    if nv12_fit is not None:
+        forms["nv12_fitted"] = run_nv12_fitted
+    out_h, rout_h = np.empty(oshape, npdt), np.empty(rshape, npdt)
+    io = {"rgb_fitted": (ups, [(t_out, out_h)]), "rgb_rfold": (ups, [(t_rout, rout_h)])}
+    for f in forms.values():
+        for _ in range(a.warmup):
+            f()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {n: [] for n in forms}
+    e2e = {n: [] for n in io}
+    order = list(forms) + list(forms)[::-1]  # mirrored: A B C D D C B A
+    for _ in range(a.rounds):
+        for n in order:
+            timer.start()
+            for _ in range(a.iters):
+                forms[n]()
+            timer.stop()
+            dev[n].append(timer.elapsed_ms() / a.iters)
+    for _ in range(a.rounds):
+        for n in list(io) + list(io)[::-1]:
+            up, downs = io[n]
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                for t, h in up:
+                    capi.check(capi.lib().snnhip_tensor_upload_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+                forms[n]()
+                for t, h in downs:
+                    capi.check(capi.lib().snnhip_tensor_download_raw(t.h, h.ctypes.data_as(capi._P), h.nbytes))
+            e2e[n].append((time.perf_counter() - t0) * 1e3 / a.iters)
+    source = a.colour if colour else a.video
+    out = {"frame": "%dx%d -> x%d %dx%d -> %dx%d" % (H, W, R, R * H, R * W, OH, OW), "scale": R, "source": source, "channels": Cc, "siting": a.siting, "range": a.range,
+           "ratio": round(OH / (R * H), 4), "rounds": a.rounds, "iters": a.iters}
+    for n in forms:
+        d = statistics.median(dev[n])
+        out[n] = {"device_ms_median": round(d, 4), "device_ms_min": round(min(dev[n]), 4), "device_ms_max": round(max(dev[n]), 4),
+                  "device_spread": round((max(dev[n]) - min(dev[n])) / d, 4)}
+        if n in io:
+            e = statistics.median(e2e[n])
+            out[n].update({"e2e_ms_median": round(e, 4), "e2e_ms_min": round(min(e2e[n]), 4), "e2e_ms_max": round(max(e2e[n]), 4), "e2e_frames_per_s": round(1e3 / e, 1),
+                           "io_bytes_per_frame": int(sum(h.nbytes for _, h in io[n][0]) + sum(h.nbytes for _, h in io[n][1]))})
+    out["rgb_fitted"]["steps"] = ([front.describe()] if front is not None else []) + [grey.step_describe(i) for i in range(2)] + [fit_y.describe(), rgb_fit.describe()]
+    out["rgb_rfold"]["steps"] = ([front.describe()] if front is not None else []) + [grey.step_describe(i) for i in range(2)] + [fixed.describe()]
+
+    def traced(run, needle):
+        """us per launch of the kernel whose function name holds `needle`, from the launch trace of `run` alone"""
+        capi.trace_begin()
+        for _ in range(a.iters):
+            run()
+        ctx.sync()
+        rep = capi.trace_end()
+        kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+        hit = [it for it in kernels if it.get("function") and needle in it["function"]]
+        return round(1e3 * hit[0].get("total_ms", hit[0].get("ms", 0.0)) / max(hit[0].get("launches", 0), 1), 2) if hit else None
+
+    alone = {"luma_fit": (lambda: fit_y.run(t_yhi, t_fy), "plane_fit", fit_y), "rgb_fit": (lambda: rgb_fit.run([t_fy, t_src_frame], t_out), "rgb_fit_kernel", rgb_fit),
+             "fixed_phase": (lambda: fixed.run([t_yhi, t_src_frame], t_rout), "ycc_merge" if colour else "yuv_rgb", fixed)}
+    out["launches"] = {}
+    for n, (run, needle, plan) in alone.items():
+        us = traced(run, needle)
+        rec = {"plan": plan.describe(), "hbm_bytes": int(plan.cost()[1]), "us_per_launch_traced": us}
+        if us:
+            rec["tbs_traced"] = round(rec["hbm_bytes"] / (us * 1e-6) / 1e12, 3)
+        out["launches"][n] = rec
+    copy_us = 1e3 * out["copy"]["device_ms_median"]
+    out["device_fitted_over_rfold"] = round(out["rgb_fitted"]["device_ms_median"] / out["rgb_rfold"]["device_ms_median"], 4)
+    out["e2e_fps_fitted_over_rfold"] = round(out["rgb_fitted"]["e2e_frames_per_s"] / out["rgb_rfold"]["e2e_frames_per_s"], 4)
+    out["pair_vs_copy"] = {"pair_hbm_bytes": pair_bytes, "pair_us_event_timed_loop": round(1e3 * out["fit_pair"]["device_ms_median"], 2),
+                           "pair_tbs_event_timed_loop": round(pair_bytes / (out["fit_pair"]["device_ms_median"] * 1e-3) / 1e12, 3), "copy_bytes_each_way": half,
+                           "copy_hbm_bytes": 2 * half, "copy_us": round(copy_us, 2), "copy_tbs": round(2 * half / (copy_us * 1e-6) / 1e12, 3)}
+    out["pair_vs_copy"]["pair_over_copy_rate"] = round(out["pair_vs_copy"]["pair_tbs_event_timed_loop"] / out["pair_vs_copy"]["copy_tbs"], 4)
+    print(json.dumps(out, indent=1))
+    if a.out:
+        record = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                record = json.load(f)
+        record["%s_%s_%dx%d_x%d_to_%dx%d" % (source, "RGB8" if Cc == 3 else "RGBA8", W, H, R, OW, OH)] = out
+        with open(a.out, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
+    ctx.close()
+
+
 def main_video_rgb(a):
     """--video ... --video-out ...: nv12 / nv12_rgb / yuv_rgb / copy / rgb8."""
     import ctypes
@@ -1301,6 +1485,8 @@ def main():
     ap.add_argument("--video-out", choices=["RGB8", "RGBA8", "NV12", "I420"], default=None,
                     help="with --video: packed RGB / RGBA out of the yuv_rgb launch (16-bit containers for P010) beside the NV12 step; NV12 with --colour: an NV12 frame out of the rgb_cbcr launch")
     ap.add_argument("--fit", default=None, metavar="WxH", help="with --video: the NV12 / P010 frame at this output size (the chain, then two plane_fit launches) beside the plain step of the same r")
+    ap.add_argument("--rgb-fit", default=None, metavar="WxH", help="with --video NV12 | P010 | I420 --video-out RGB8 | RGBA8, or with --colour alone: the RGB frame at this output size "
+                    "(the chain, the luma fit, rgb_fit) beside the r-fold RGB step of the same r; --out merges the record into a JSON file")
     ap.add_argument("--range", choices=["limited", "full"], default="limited", help="the stream's range with --video-out")
     ap.add_argument("--siting", choices=["left", "centre"], default="left", help="horizontal chroma siting of --video")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
@@ -1314,6 +1500,10 @@ def main():
     a = ap.parse_args()
     if a.metrics:
         return main_metrics(a)
+    if a.rgb_fit:
+        assert not a.fit and ((a.video in ("NV12", "P010", "I420") and a.video_out in ("RGB8", "RGBA8") and not a.colour) or (a.colour and not a.video and not a.video_out)), \
+            "--rgb-fit goes with --video NV12 | P010 | I420 --video-out RGB8 | RGBA8, or with --colour RGB8 | RGBA8 alone"
+        return main_rgb_fit(a)
     if a.video in ("I420", "I010") or a.video_out == "I420":
         assert (a.video_out == "I420") == bool(a.colour) and not (a.colour and a.video), "--video I420 | I010 [--video-out RGB8 | RGBA8] [--fit WxH], or --colour ... --video-out I420"
         assert not (a.fit and a.video_out), "--fit goes with --video alone"
