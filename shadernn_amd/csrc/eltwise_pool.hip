@@ -235,13 +235,44 @@ __global__ __launch_bounds__(256) void upsample_kernel(snnhip_upsample_desc d, i
 }
 
 // ------------------------------------------------------------------------------------------------ instance norm
-// Statistics per (image, channel) over H*W.  The shader makes two passes (mean, then sum (x-mean)^2); here ONE statistics sweep
-// accumulates S1 = sum (x - p) and S2 = sum (x - p)^2 around a per-channel pivot p = x[n, 0, 0, c] (so that S2/HW - (S1/HW)^2 does not
-// cancel: the pivot is within a few standard deviations of the mean), then one sweep normalises: 2 reads + 1 write of the tensor
-// instead of 3 + 1.  Work split: block = (image n, row slab s); its 256 threads are CL channel lanes x 256/CL pixel lanes with
+// Statistics per (image, channel) over H*W.  The shader makes two passes (mean, then sum (x-mean)^2); here ONE statistics sweep reduces every
+// slab to a (count, mean, M2) record per channel, then one sweep normalises: 2 reads + 1 write of the tensor instead of 3 + 1.  No pivot
+// per plane: on half tensors the four pixels a thread has in flight are in registers, so their own mean and M2 = sum (x - mean)^2 are taken in two passes over
+// those registers, and the thread's running record takes them in with the parallel-variance update -- every term added to an M2 is a square,
+// nothing is subtracted from a sum of squares, so no plane can make it cancel (one pivot per plane, x[n, 0, 0, c], the earlier form
+// S2/HW - (S1/HW)^2, lost the variance to a single outlying first sample).  fp32 tensors keep double records instead (NormStat, below): sums around each
+// thread's own first pixel, exact to far below an fp32 ulp.  Thread records, slab records and the fold merge the same way
+// (stat_merge) as trees of a fixed shape: deterministic.
+// Work split: block = (image n, row slab s); its 256 threads are CL channel lanes x 256/CL pixel lanes with
 // CL*CV >= min(C, 128) so that one wave instruction reads whole pixels (contiguous C*4 bytes) instead of half-lines.
-// Partials go to part[n][s][2][C]; a tiny fold kernel turns them into mean[n][C] and mul[n][C] in a fixed order (deterministic).
-// STAGE 0: partial S1, S2      STAGE 2: y = act((x - mean) * mul + beta)
+// Records go to part[n][s][{mean, M2}][C] (the count follows from the slab's extent); a tiny fold kernel turns them into shift[n][C] and mul[n][C].
+// STAGE 0: slab records      STAGE 2: y = act(x * mul + shift)
+// fp32 tensors keep their records in double (NormStat<float>::type): an fp32 result has no headroom -- a variance one fp32 ulp off moves the largest
+// output of a plane by an ulp, which is the whole error of a straightforward fp32 evaluation there -- so their multiplier and shift are formed from
+// float64 statistics and rounded once.  Half tensors round the result to 11 bits: fp32 records, two channels per instruction.
+template <typename F>
+struct RunStatT {
+    F n, m, q;
+};
+typedef RunStatT<float> RunStat;
+template <typename T>
+struct NormStat {
+    typedef float type;
+};
+template <>
+struct NormStat<float> {
+    typedef double type;
+};
+// parallel-variance update: n = na + nb,  d = mb - ma,  m = ma + d nb/n,  M2 = M2a + M2b + d^2 na nb/n; nb = 0 changes nothing
+template <typename F>
+__device__ __forceinline__ void stat_merge(RunStatT<F>& a, F nb, F mb, F qb) {
+    if (nb <= F(0)) return;
+    const F n = a.n + nb, dm = mb - a.m, f = nb / n;
+    a.m += dm * f;
+    a.q += qb + dm * dm * a.n * f;
+    a.n = n;
+}
+
 struct InResidual { // graph rule H: the Add behind an InstanceNorm, applied in the norm's normalise sweep
     const void* p = nullptr;
     int H = 0, W = 0;
@@ -260,7 +291,10 @@ __global__ __launch_bounds__(256) void instancenorm_kernel(snnhip_instancenorm_d
     // the norm (top-left aligned, add_ragged_kernel's rule): outside it the sum is the norm alone, or 0 when the residual is the Add's FIRST input.
     const T* __restrict__ res = static_cast<const T*>(ra.p);
     const bool ragged = ra.p && (ra.H != d.H || ra.W != d.W);
-    __shared__ float red[2 * 256 * CV];
+    typedef typename NormStat<T>::type F; // the type of the statistics records
+    constexpr bool WIDE = sizeof(F) == 8;
+    __shared__ F red[STAGE == 0 ? 2 * 256 * CV : 1];
+    __shared__ F redN[STAGE == 0 ? 256 : 1]; // stage 0: pixels behind each thread's record
     const int n = blockIdx.x / S, s = blockIdx.x % S;
     const int tid = threadIdx.x;
     const int CL = 1 << CLs, PL = 256 >> CLs;       // channel lanes, pixel lanes
@@ -278,13 +312,68 @@ __global__ __launch_bounds__(256) void instancenorm_kernel(snnhip_instancenorm_d
         float piv[CV], mul[CV], bt[CV];
 #pragma unroll
         for (int k = 0; k < CV; ++k) {
-            piv[k] = cok ? (STAGE == 0 ? static_cast<float>(xn[c + k]) : statMean[static_cast<size_t>(n) * d.C + c + k]) : 0.0f; // stage 0: pivot, stage 2: shift
+            piv[k] = (STAGE == 2 && cok) ? statMean[static_cast<size_t>(n) * d.C + c + k] : 0.0f; // stage 2: shift
             mul[k] = (STAGE == 2 && cok) ? statMul[static_cast<size_t>(n) * d.C + c + k] : 0.0f;
             bt[k] = (STAGE == 2 && cok) ? beta[c + k] : 0.0f;
         }
-        float s1[CV], s2[CV];
+        // stage 0: the thread's running record (cnt pixels, mean, M2 per channel)
+        float cnt = 0.0f, rm[CV], rq[CV];
 #pragma unroll
-        for (int k = 0; k < CV; ++k) s1[k] = s2[k] = 0.0f;
+        for (int k = 0; k < CV; ++k) rm[k] = rq[k] = 0.0f;
+        auto take4 = [&](const float (&v)[U][CV]) { // the U = 4 pixels in flight: their own mean and M2 in two passes over the registers, then one update
+            const float nn = cnt + 4.0f, f = 4.0f * __builtin_amdgcn_rcpf(nn), w = cnt * f;
+            if constexpr (CV % 2 == 0) { // two channels per instruction (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32): the sweep is issue-bound on half tensors
+                typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+                for (int k = 0; k < CV; k += 2) {
+                    const f2 a0 = {v[0][k], v[0][k + 1]}, a1 = {v[1][k], v[1][k + 1]}, a2 = {v[2][k], v[2][k + 1]}, a3 = {v[3][k], v[3][k + 1]};
+                    const f2 m = ((a0 + a1) + (a2 + a3)) * 0.25f;
+                    const f2 d0 = a0 - m, d1 = a1 - m, d2 = a2 - m, d3 = a3 - m;
+                    const f2 q = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3), r = {rm[k], rm[k + 1]}, dm = m - r;
+                    const f2 r2 = dm * f + r, q2 = q + dm * dm * w;
+                    rm[k] = r2.x;
+                    rm[k + 1] = r2.y;
+                    rq[k] += q2.x;
+                    rq[k + 1] += q2.y;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < CV; ++k) {
+                    const float m = ((v[0][k] + v[1][k]) + (v[2][k] + v[3][k])) * 0.25f;
+                    const float d0 = v[0][k] - m, d1 = v[1][k] - m, d2 = v[2][k] - m, d3 = v[3][k] - m;
+                    const float q = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3), dm = m - rm[k];
+                    rm[k] = fmaf(dm, f, rm[k]);
+                    rq[k] += q + dm * dm * w;
+                }
+            }
+            cnt = nn;
+        };
+        // ... and in double (fp32 tensors): sums of x - p and (x - p)^2 around the thread's first pixel p; p is one of the thread's n samples, so the sum of
+        // squares is at most (n + 2) M2 and the subtraction below costs a few of the 53 bits
+        double pv[CV], w1[CV], w2[CV];
+#pragma unroll
+        for (int k = 0; k < CV; ++k) pv[k] = w1[k] = w2[k] = 0.0;
+        auto take1 = [&](const float (&v)[CV]) {
+            if constexpr (WIDE) {
+#pragma unroll
+                for (int k = 0; k < CV; ++k) {
+                    if (cnt == 0.0f) pv[k] = static_cast<double>(v[k]);
+                    const double dv = static_cast<double>(v[k]) - pv[k];
+                    w1[k] += dv;
+                    w2[k] = fma(dv, dv, w2[k]);
+                }
+                cnt += 1.0f;
+                return;
+            }
+            const float nn = cnt + 1.0f, f = __builtin_amdgcn_rcpf(nn), w = cnt * f;
+#pragma unroll
+            for (int k = 0; k < CV; ++k) {
+                const float dm = v[k] - rm[k];
+                rm[k] = fmaf(dm, f, rm[k]);
+                rq[k] += dm * dm * w;
+            }
+            cnt = nn;
+        };
         // residual of pixel p (rule H): where it sits in the (possibly smaller) residual tensor, or -1 outside it.  32-bit arithmetic: H * W < 2^31.
         auto res_pixel = [&](size_t p) -> long {
             if (!ragged) return static_cast<long>(p);
@@ -293,12 +382,7 @@ __global__ __launch_bounds__(256) void instancenorm_kernel(snnhip_instancenorm_d
         };
         auto consume = [&](const float (&v)[CV], size_t p, const float (&rv)[CV], long rp) {
             if (STAGE == 0) {
-#pragma unroll
-                for (int k = 0; k < CV; ++k) {
-                    const float dv = v[k] - piv[k];
-                    s1[k] += dv;
-                    s2[k] += dv * dv;
-                }
+                take1(v);
             } else {
                 float o[CV];
                 if (FAST) { // (epi_act's switch per value -- 16 values in flight per thread, each behind its own branches -- is what the generic form below costs)
@@ -352,6 +436,15 @@ __global__ __launch_bounds__(256) void instancenorm_kernel(snnhip_instancenorm_d
 #pragma unroll
                     for (int u = 0; u < U; ++u) rp[u] = -1;
                 }
+                if (STAGE == 0) {
+                    if constexpr (WIDE) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) take1(v[u]);
+                    } else {
+                        take4(v);
+                    }
+                    continue;
+                }
 #pragma unroll
                 for (int u = 0; u < U; ++u) consume(v[u], p + static_cast<size_t>(u) * PL, rv[u], rp[u]); // same pixel order as the plain loop
             }
@@ -369,89 +462,97 @@ __global__ __launch_bounds__(256) void instancenorm_kernel(snnhip_instancenorm_d
             }
         }
         if (STAGE == 0) {
-            __syncthreads();
+            // thread record -> LDS, then a tree over the pixel lanes: lane pl takes in lane pl + w, w = PL/2 .. 1 (a fixed shape, whatever the data)
+            RunStatT<F> a[CV]; // (cnt = 0: a lane without pixels, or beyond the channels)
 #pragma unroll
             for (int k = 0; k < CV; ++k) {
-                red[tid * CV + k] = s1[k];
-                red[256 * CV + tid * CV + k] = s2[k];
-            }
-            __syncthreads();
-            if (tid < CL * CV) { // thread -> (channel lane tid / CV, component tid % CV): fold the pixel lanes in a fixed order
-                const int lane = tid / CV, k = tid % CV;
-                float a1 = 0.0f, a2 = 0.0f;
-                for (int j = 0; j < PL; ++j) {
-                    a1 += red[(j * CL + lane) * CV + k];
-                    a2 += red[256 * CV + (j * CL + lane) * CV + k];
+                if constexpr (WIDE) {
+                    const double m1 = cnt > 0.0f ? w1[k] / static_cast<double>(cnt) : 0.0;
+                    a[k] = RunStatT<F>{static_cast<F>(cnt), static_cast<F>(pv[k] + m1), static_cast<F>(fmax(w2[k] - w1[k] * m1, 0.0))};
+                } else {
+                    a[k] = RunStatT<F>{static_cast<F>(cnt), static_cast<F>(rm[k]), static_cast<F>(rq[k])};
                 }
-                const int cc = c0 + lane * CV + k;
-                if (cc < d.C) {
-                    float* po = partOut + (static_cast<size_t>(n) * S + s) * 2 * d.C;
-                    po[cc] = a1;
-                    po[d.C + cc] = a2;
+            }
+            for (int w = PL >> 1; w > 0; w >>= 1) {
+                __syncthreads();
+                if (pl >= w && pl < 2 * w) {
+                    redN[tid] = a[0].n;
+#pragma unroll
+                    for (int k = 0; k < CV; ++k) {
+                        red[tid * CV + k] = a[k].m;
+                        red[256 * CV + tid * CV + k] = a[k].q;
+                    }
+                }
+                __syncthreads();
+                if (pl < w) {
+                    const int o = tid + w * CL;
+                    const F nb = redN[o];
+#pragma unroll
+                    for (int k = 0; k < CV; ++k) stat_merge(a[k], nb, red[o * CV + k], red[256 * CV + o * CV + k]);
+                }
+            }
+            if (pl == 0 && cok) {
+                F* po = reinterpret_cast<F*>(partOut) + (static_cast<size_t>(n) * S + s) * 2 * d.C;
+#pragma unroll
+                for (int k = 0; k < CV; ++k) {
+                    po[c + k] = a[k].m;
+                    po[d.C + c + k] = a[k].q;
                 }
             }
         }
     }
 }
 
-// mean[n][c] = p + S1/HW,  mul[n][c] = gamma[c] / sqrt(S2/HW - (S1/HW)^2 + eps)   with S1, S2 summed over the slabs in a fixed order:
-// one block per (image, channel), thread t adds slabs t, t+256, ..., then a shared-memory tree (deterministic; a single thread walking
-// ~1000 slab partials with dependent L2 loads took longer than both sweeps together)
+// shift[n][c] = beta - mean * mul,  mul[n][c] = gamma[c] / sqrt(M2/HW + eps)   with the slab records merged in a fixed order: one block per
+// (image, channel), thread t merges slabs t, t+256, ..., then a shared-memory tree (deterministic; a single thread walking ~1000 slab
+// records with dependent L2 loads took longer than both sweeps together)
 template <typename T>
-__global__ __launch_bounds__(256) void instancenorm_fold_kernel(int NC, int C, int S, int HW, float invHW, float eps, const T* __restrict__ x,
-                                                               const float* __restrict__ part, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                               float* __restrict__ shift, float* __restrict__ mul) {
-    __shared__ float r1[256], r2[256];
-    const int i = blockIdx.x;
+__global__ __launch_bounds__(256) void instancenorm_fold_kernel(int C, int S, int HW, int pixelsPerSlab, float eps, const float* __restrict__ partIn,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ shift,
+                                                               float* __restrict__ mul) {
+    typedef typename NormStat<T>::type F;
+    __shared__ F rn[256], rm[256], rq[256];
+    const F* part = reinterpret_cast<const F*>(partIn);
+    const int i = blockIdx.x, t = threadIdx.x;
     const int n = i / C, c = i % C;
-    float a1 = 0.0f, a2 = 0.0f;
-    for (int j = threadIdx.x; j < S; j += 256) {
-        const float* po = part + (static_cast<size_t>(n) * S + j) * 2 * C;
-        a1 += po[c];
-        a2 += po[C + c];
+    RunStatT<F> a{F(0), F(0), F(0)};
+    for (int j = t; j < S; j += 256) {
+        const F* po = part + (static_cast<size_t>(n) * S + j) * 2 * C;
+        stat_merge<F>(a, static_cast<F>(min(pixelsPerSlab, HW - j * pixelsPerSlab)), po[c], po[C + c]);
     }
-    r1[threadIdx.x] = a1;
-    r2[threadIdx.x] = a2;
-    __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
-        if (static_cast<int>(threadIdx.x) < w) {
-            r1[threadIdx.x] += r1[threadIdx.x + w];
-            r2[threadIdx.x] += r2[threadIdx.x + w];
+        __syncthreads();
+        if (t >= w && t < 2 * w) {
+            rn[t] = a.n;
+            rm[t] = a.m;
+            rq[t] = a.q;
         }
         __syncthreads();
+        if (t < w) stat_merge<F>(a, rn[t + w], rm[t + w], rq[t + w]);
     }
-    if (threadIdx.x != 0) return;
-    a1 = r1[0];
-    a2 = r2[0];
-    const float piv = static_cast<float>(x[static_cast<size_t>(n) * HW * C + c]);
-    const float m1 = a1 * invHW;
-    float var = a2 * invHW - m1 * m1;
-    var = var > 0.0f ? var : 0.0f;
-    // the normalisation as ONE multiply-add per value, y = x * mul + shift (every consumer -- the normalise sweep below and the convolutions that
+    if (t != 0) return;
+    F var = a.q / a.n;
+    var = var > F(0) ? var : F(0);
+    // the normalisation as ONE multiply-add per value, y = x * mul + shift (every consumer -- the normalise sweep above and the convolutions that
     // normalise while they stage, graph rule I -- evaluates exactly this fma, so they stay bit-identical to one another)
-    const float mu = gamma[c] / sqrtf(var + eps);
-    mul[i] = mu;
-    shift[i] = beta[c] - (piv + m1) * mu;
+    if constexpr (sizeof(F) == 8) { // float64 statistics: the multiplier and, with that multiplier, the shift rounded to fp32 once each
+        const float mu = static_cast<float>(static_cast<double>(gamma[c]) / sqrt(var + static_cast<double>(eps)));
+        mul[i] = mu;
+        shift[i] = static_cast<float>(static_cast<double>(beta[c]) - a.m * static_cast<double>(mu));
+    } else {
+        const float mu = gamma[c] / sqrtf(var + eps);
+        mul[i] = mu;
+        shift[i] = beta[c] - a.m * mu;
+    }
 }
 
 // Chain rule F: the producing convolution already reduced every output tile to (mean_t, M2_t) per channel (conv2d_mfma_kernel's LDS
 // epilogue), so the statistics sweep over the tensor is not needed.  The tile records are combined with the parallel-variance update
 //     n = na + nb,  d = mb - ma,  m = ma + d nb/n,  M2 = M2a + M2b + d^2 na nb/n
-// in a fixed order, in two levels so that the reads stay channel-contiguous and enough blocks are in flight (a 1378x818 image is ~9000
+// (stat_merge, above) in a fixed order, in two levels so that the reads stay channel-contiguous and enough blocks are in flight (a 1378x818 image is ~9000
 // tiles; one block per (image, channel) walking them with a 2*C-float stride took longer than the sweep it replaced):
 //   level 1: block = (64-tile chunk, image); thread = (channel lane, 1 of 4 tile lanes) folds 16 tiles, the 4 lanes are folded through LDS
 //   level 2: block = image, thread = (channel lane, 1 of 4 chunk lanes): folds the chunk records, writes mean and gamma / sqrt(var + eps)
-struct RunStat {
-    float n, m, q;
-};
-__device__ __forceinline__ void stat_merge(RunStat& a, float nb, float mb, float qb) {
-    if (nb <= 0.0f) return;
-    const float n = a.n + nb, dm = mb - a.m, f = nb / n;
-    a.m += dm * f;
-    a.q += qb + dm * dm * a.n * f;
-    a.n = n;
-}
-
 constexpr int kFoldChunk = 64; // tiles per level-1 block
 
 __global__ __launch_bounds__(256) void instancenorm_fold_tiles1_kernel(int C, int H, int W, int tilesX, int tilesY, int TH, int TW, const float* __restrict__ part,
@@ -702,7 +803,6 @@ struct InstanceNormPlan : snnhip_plan {
         const dim3 g(static_cast<unsigned>(d.N * S));
         const int NC = d.N * d.C, HW = d.H * d.W;
         const dim3 gf(static_cast<unsigned>(NC)); // one block per (image, channel)
-        const float invHW = 1.0f / (static_cast<float>(d.H) * static_cast<float>(d.W));
         const bool fastNorm = (d.act == SNNHIP_ACT_NONE || d.act == SNNHIP_ACT_RELU) && (!res || addAct == SNNHIP_ACT_NONE) && !snnhip::option("SNNHIP_NORM_GENERIC_ACT");
 #define SNNHIP_IN(ST, CVV)                                                                                                                                     \
     do {                                                                                                                                                       \
@@ -717,7 +817,7 @@ struct InstanceNormPlan : snnhip_plan {
                           d_beta, d_part, mptr<T>(out), ST == 2 ? ra : InResidual());                                                                          \
     } while (0)
 #define SNNHIP_FOLD() \
-    SNNHIP_LAUNCH(instancenorm_fold_kernel<T>, gf, dim3(256), 0, ctx->stream, NC, d.C, S, HW, invHW, d.eps, cptr<T>(in[0]), d_part, d_gamma, d_beta, d_mean, d_mul)
+    SNNHIP_LAUNCH(instancenorm_fold_kernel<T>, gf, dim3(256), 0, ctx->stream, d.C, S, HW, pixelsPerSlab, d.eps, d_part, d_gamma, d_beta, d_mean, d_mul)
         const bool sweep = !(tiles && tiles->part);
         // launch trace: each pass under its own scope with the bytes that pass has to move (the statistics sweep reads the tensor once, the
         // normalise sweep reads it [and the residual] once and writes it once; the folds move a few KB)
@@ -1052,7 +1152,7 @@ int snnhip_instancenorm_plan_create(snnhip_ctx* ctx, const snnhip_instancenorm_d
         while ((1 << cls) * cv < desc->C && cls < (cv == 4 ? 5 : 6)) ++cls;
         plan->CLs = cls;
     }
-    std::vector<float> zeros(static_cast<size_t>(desc->N) * plan->S * desc->C * 2, 0.0f);
+    std::vector<float> zeros(static_cast<size_t>(desc->N) * plan->S * desc->C * 2 * 2, 0.0f); // slab records {mean, M2}: float for half tensors, double for fp32
     if (rc == SNNHIP_OK) rc = plan->upload(zeros.data(), zeros.size(), &plan->d_part);
     if (rc == SNNHIP_OK) rc = plan->upload(zeros.data(), static_cast<size_t>(desc->N) * desc->C, &plan->d_mean);
     if (rc == SNNHIP_OK) rc = plan->upload(zeros.data(), static_cast<size_t>(desc->N) * desc->C, &plan->d_mul);

@@ -14,7 +14,11 @@ with a third bound on the mean signed error per output channel (a bias off by 2e
 
 The fp16 convolution kernels (half storage, products of half operands accumulated in fp32, an fp32 epilogue, one round-to-nearest-even store) are held to
 the correctly rounded half of the exact result: budget_half allows M_F16 times E32p max beyond half a binary16 ulp (ulp16), where a tolerance of a few
-half ulps lets a truncating store or partial sums kept in half through."""
+half ulps lets a truncating store or partial sums kept in half through.
+
+InstanceNorm (the stand-alone plan, the convolution's tile statistics, the norm + Add pair) is held plane by plane: instancenorm is the float64 reference,
+instancenorm32 a straightforward two-pass fp32 model of the contract whose distance from it is the unit, floored at the rounding of the shift of the one-FMA form
+(norm_floor); budget_norm holds a result to M_NORM times that, half tensors through budget_half."""
 import numpy as np
 
 # The margin of every budget test: twice the largest ratio any fp32 kernel family showed against float64 on an MI355X (2.02, DESIGN.md section 3
@@ -369,7 +373,7 @@ def ulp16(v):
     return np.ldexp(1.0, np.maximum(e, -14) - 10)
 
 
-def budget_half(got, ref64, pair32, M, what="", tile=None):
+def budget_half(got, ref64, pair32, M, what="", tile=None, floor=0.0):
     """Holds `got` [N,H,W,C], read back from a half tensor, to the correctly rounded half of the exact result.  ref64 is the float64 layer on the
     half-rounded inputs and weights (bias and BN parameters fp32), pair32 the pairwise fp32 evaluation of the same values, not rounded to half.
         max over elements of max(|got - ref64| - 0.5 ulp16(ref64), 0) <= M * E32p_max,     E32p_max = max |pair32 - ref64|.
@@ -380,7 +384,7 @@ def budget_half(got, ref64, pair32, M, what="", tile=None):
     ref64 = _f64(ref64)
     got = np.asarray(got)
     assert got.ndim == 4 and got.shape == ref64.shape == np.asarray(pair32).shape, (got.shape, ref64.shape, np.asarray(pair32).shape)
-    e32max = float(np.abs(_f64(pair32) - ref64).max())
+    e32max = max(float(np.abs(_f64(pair32) - ref64).max()), float(floor))  # (floor: a unit the caller derives where pair32 can be exact, budget_norm)
     bad = ~np.isfinite(got)
     if bad.any():
         raise AssertionError("%s%d of %d values are not finite (never written, or NaN / Inf computed): first at %s"
@@ -401,3 +405,121 @@ def budget_half(got, ref64, pair32, M, what="", tile=None):
                              % (what and what + ": ", omax, ratio, e32max, M, got.flat[i], ref64.flat[i], ulp.flat[i], diff.flat[i] / ulp.flat[i], 100 * mismatch,
                                 float(chan.max()), int(np.argmax(chan)), _where_conv(i, got.shape, tile)))
     return ratio, mismatch, float(chan.max())
+
+
+# ---------------------------------------------------------------------------------------------------------------- instance norm
+# The margin of the InstanceNorm budget tests (budget_norm): the project's own margin for the ESPCN kernels (M) and the fp16 convolutions (M_F16).
+M_NORM = 8
+
+
+def _plane_stats64(x):
+    """(mean, population variance) per (image, channel) of x [N,H,W,C] in float64, each [N,1,1,C]."""
+    x = _f64(x)
+    mean = x.mean(axis=(1, 2), keepdims=True)
+    return mean, ((x - mean) ** 2).mean(axis=(1, 2), keepdims=True)
+
+
+def instancenorm(x, beta, gamma, eps=1e-5, act="", alpha=0.0, mean_shift=0.0, var_scale=1.0):
+    """InstanceNorm in float64: per (n, c) the mean and the population variance over H*W, y = act((x - mean) gamma / sqrt(var + eps) + beta); eps and
+    alpha are the plan's fp32 constants.  mean_shift (in units of sqrt(var + eps)) and var_scale (on var + eps) build the mutants of tests/test_ref64.py."""
+    x = _f64(x)
+    mean, var = _plane_stats64(x)
+    ve = (var + float(np.float32(eps))) * var_scale
+    y = (x - (mean + mean_shift * np.sqrt(ve))) * (_f64(gamma) / np.sqrt(ve)) + _f64(beta)
+    return activation(act, y, alpha)
+
+
+def _pairwise_sum32(a):
+    """fp32 sum over axis 0 by a tree of fp32 additions (neighbours added level by level, an odd one out carried up unchanged)."""
+    p = np.asarray(a, np.float32)
+    while p.shape[0] > 1:
+        q = p[0:p.shape[0] - 1:2] + p[1::2]
+        p = np.concatenate([q, p[-1:]]) if p.shape[0] & 1 else q
+    assert p.dtype == np.float32
+    return p[0]
+
+
+def instancenorm32(x, beta, gamma, eps=1e-5, act="", alpha=0.0):
+    """A float32 NumPy model of the contract, evaluated the straightforward way (no pivot, two passes): the mean a pairwise fp32 sum, the variance a
+    pairwise fp32 sum of (x - mean)^2, mul = gamma / sqrtf(var + eps), shift = beta - mean * mul, y = fma(x, mul, shift) (formed in float64 and
+    rounded once).  A model of a correct fp32 implementation, not of the kernel: its distance from instancenorm() is the unit E of budget_norm."""
+    f = np.float32
+    x = np.asarray(x, f)
+    n, h, w, c = x.shape
+    xs = np.ascontiguousarray(x.reshape(n, h * w, c).transpose(1, 0, 2))  # [HW, N, C]
+    hw = f(h * w)
+    mean = _pairwise_sum32(xs) / hw
+    dv = xs - mean
+    var = _pairwise_sum32(dv * dv) / hw
+    mul = np.asarray(gamma, f) / np.sqrt(var + f(eps))
+    shift = np.asarray(beta, f) - mean * mul
+    assert mean.dtype == var.dtype == mul.dtype == shift.dtype == f
+    y = (xs.astype(np.float64) * mul.astype(np.float64) + shift.astype(np.float64)).astype(f)
+    y = activation32(act, y, alpha)
+    assert y.dtype == f
+    return np.ascontiguousarray(y.transpose(1, 0, 2)).reshape(n, h, w, c)
+
+
+def norm_floor(x, beta, gamma, eps=1e-5):
+    """[N, C]: one fp32 ulp of |mean * mul| + |beta|, the rounding of shift = beta - mean * mul that the one-FMA form cannot avoid (and what keeps a
+    constant plane, on which the model's own error is 0, from a budget of zero)."""
+    mean, var = _plane_stats64(x)
+    mul = _f64(gamma) / np.sqrt(var + float(np.float32(eps)))
+    return np.spacing((np.abs(mean * mul) + np.abs(_f64(beta))).astype(np.float32)).astype(np.float64)[:, 0, 0, :]
+
+
+def _plane_words(x, n, c, idx, w):
+    """What a failure says of the plane: where the worst pixel is, |mean| / std, and how far x[n, 0, 0, c] is from the mean in standard deviations."""
+    txt = "plane (n, c) = (%d, %d), worst pixel (y, x) = (%d, %d)" % (n, c, idx // w, idx % w)
+    if x is not None:
+        p = _f64(x)[n, :, :, c]
+        m, s = float(p.mean()), float(p.std())
+        txt += ", |mean|/std = %s, x[n,0,0,c] is %s std from the mean" % (("%.3g" % (abs(m) / s)) if s > 0 else "inf (std = 0)",
+                                                                       ("%.3g" % (abs(p[0, 0] - m) / s)) if s > 0 else "0 (std = 0)")
+    return txt
+
+
+def budget_norm(got, ref64, model32, M, floor, what="", x=None, half_out=False):
+    """Holds an InstanceNorm result `got` [N,H,W,C] to the float64 reference plane by plane.  Per (image, channel) plane
+        E = max(max over the plane |model32 - ref64|, floor[n, c]),     floor = norm_floor(...),
+    and both the max and the mean of |got - ref64| over the plane must be <= M * E.  half_out: `got` was read back from a half tensor and ref64 is the
+    float64 result on the half-rounded input; the allowance is half a binary16 ulp of the exact value plus M * E (budget_half, per plane).
+    x (the norm's input) only serves the failure message.  Returns the largest ratio reached over the planes (error, or in half the excess over half
+    an ulp, in units of E)."""
+    ref64 = _f64(ref64)
+    got = np.asarray(got)
+    model32 = np.asarray(model32)
+    assert got.ndim == 4 and got.shape == ref64.shape == model32.shape, (got.shape, ref64.shape, model32.shape)
+    n_, h, w, c_ = got.shape
+    floor = _f64(floor)
+    assert floor.shape == (n_, c_), (floor.shape, got.shape)
+    pre = what and what + ": "
+    bad = ~np.isfinite(got)
+    if bad.any():
+        n, y, xx, c = (int(v) for v in np.unravel_index(int(np.argmax(bad)), got.shape))
+        raise AssertionError("%s%d of %d values are not finite (never written, or NaN / Inf computed): first at (n, y, x, c) = (%d, %d, %d, %d)"
+                             % (pre, int(bad.sum()), bad.size, n, y, xx, c))
+    err = np.abs(_f64(got) - ref64)
+    e = np.maximum(np.abs(_f64(model32) - ref64).max(axis=(1, 2)), floor)  # [N, C]
+    worst, failed = 0.0, []  # every plane is measured; a failure reports the plane with the largest ratio and how many planes are out
+    for n in range(n_):
+        for c in range(c_):
+            pe = err[n, :, :, c]
+            if half_out:
+                sl = (slice(n, n + 1), slice(None), slice(None), slice(c, c + 1))
+                try:
+                    ratio = budget_half(got[sl], ref64[sl], model32[sl], M, floor=float(floor[n, c]))[0]
+                except AssertionError as exc:
+                    over = np.maximum(pe - 0.5 * ulp16(ref64[n, :, :, c]), 0.0)
+                    ratio = float(over.max()) / e[n, c]
+                    failed.append((ratio, "%s; %s" % (exc, _plane_words(x, n, c, int(np.argmax(over)), w))))
+            else:
+                emax, emean = float(pe.max()), float(pe.mean())
+                ratio = emax / e[n, c]
+                if not (emax <= M * e[n, c] and emean <= M * e[n, c]):
+                    failed.append((ratio, "out of the float64 budget: max error %.3e = %.2f x E (%.3e), mean error %.3e = %.2f x E, allowed %g x; %s"
+                                   % (emax, ratio, e[n, c], emean, emean / e[n, c], M, _plane_words(x, n, c, int(np.argmax(pe)), w))))
+            worst = max(worst, ratio)
+    if failed:
+        raise AssertionError("%s%d of %d planes out of the budget, the worst: %s" % (pre, len(failed), n_ * c_, max(failed, key=lambda t: t[0])[1]))
+    return worst

@@ -347,13 +347,18 @@ def test_instancenorm_add_graph_fusion(ctx, monkeypatch, n, h, w, c, act, add_ac
     assert all(p is not None for p, _ in snn.graph_fuse(ctx, nodes))
 
 
+_RULE_I = [(1, 40, 56, 32, 64, 3, 2, "relu"), (2, 37, 45, 64, 128, 3, 2, "relu"), (1, 33, 70, 16, 32, 3, 1, ""), (2, 19, 23, 64, 64, 3, 1, "leakyRelu"),
+           (1, 30, 30, 8, 16, 5, 1, "relu"), (2, 21, 70, 32, 3, 9, 1, "relu"), (1, 17, 40, 16, 3, 7, 1, "")]
+
+
 @pytest.mark.parametrize("with_pad,with_up", [(False, False), (True, False), (True, True)])
-@pytest.mark.parametrize("n,h,w,ic,oc,k,s,act", [(1, 40, 56, 32, 64, 3, 2, "relu"), (2, 37, 45, 64, 128, 3, 2, "relu"), (1, 33, 70, 16, 32, 3, 1, ""), (2, 19, 23, 64, 64, 3, 1, "leakyRelu"),
-                                                (1, 30, 30, 8, 16, 5, 1, "relu"), (2, 21, 70, 32, 3, 9, 1, "relu"), (1, 17, 40, 16, 3, 7, 1, "")])
-def test_instancenorm_conv_chain_fusion(ctx, monkeypatch, n, h, w, ic, oc, k, s, act, with_pad, with_up):
+@pytest.mark.parametrize("n,h,w,ic,oc,k,s,act,pivot", [pytest.param(*c, None, id="-".join(map(str, c))) for c in _RULE_I] +  # (the ids these cases always had)
+                         [pytest.param(1, 33, 70, 16, 32, 3, 1, "", 10.0, id="1-33-70-16-32-3-1--pivot10")])
+def test_instancenorm_conv_chain_fusion(ctx, monkeypatch, n, h, w, ic, oc, k, s, act, pivot, with_pad, with_up):
     """Graph rule I (fp16): InstanceNorm -> [UpSampling] -> [Pad] -> Conv2D as the norm's statistics sweep + fold and ONE convolution launch that
     normalises while it stages its input.  Same arithmetic and rounding points as the separate launches: bit-identical to them (and within
-    tolerance of the oracle); zero padding of a 'same' convolution stays zero."""
+    tolerance of the oracle); zero padding of a 'same' convolution stays zero.  pivot: a quiet plane, N(0, 0.05), whose first sample x[n, 0, 0, c]
+    is that value -- statistics that differ between a right and a wrong fold (tests/test_instancenorm_budget_gpu.py holds them to float64)."""
     import shadernn_amd as snn
 
     if with_up and (s != 1 or oc == 3):
@@ -361,6 +366,9 @@ def test_instancenorm_conv_chain_fusion(ctx, monkeypatch, n, h, w, ic, oc, k, s,
     monkeypatch.setenv("SNNHIP_CONV_WIDE", "0")  # (the wide kernel gets its own cases in test_conv_wide_gpu.py)
     dt = snn.F16
     x = 1.5 * _rand((n, h, w, ic), 1) + 0.2
+    if pivot is not None:
+        x = 0.05 * _rand((n, h, w, ic), 1)
+        x[:, 0, 0, :] = pivot
     wt, b = _rand((oc, ic, k, k), 2, 1.0 / np.sqrt(ic * k * k)), _rand((oc,), 3, 0.5)
     beta, gamma = _rand((ic,), 4, 0.3), 1.0 + _rand((ic,), 5, 0.2)
     norm = snn.instancenorm_plan(ctx, n, h, w, ic, beta, gamma, act=act, leaky=0.1)

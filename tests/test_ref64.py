@@ -581,3 +581,80 @@ def test_the_half_margin_is_a_power_of_two_below_every_mutant():
             if y is not None:
                 with pytest.raises(AssertionError):
                     ref64.budget_half(y, want64, pair32, 64, what=kind)
+
+
+# ---------------------------------------------------------------------------------------------------------------- instance norm
+import norm_cases  # noqa: E402
+
+NORM_SHAPES = [(1, 40, 60, 4), (3, 17, 23, 5)]
+NORM_CASES = [(s, d, f) for s in NORM_SHAPES for d in ("f32", "f16") for f in norm_cases.families(d)]
+NORM_IDS = ["%s-%s-%s" % ("x".join(map(str, s)), d, f) for s, d, f in NORM_CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def _norm_case(shape, dtype, family, act="leakyRelu"):
+    x = norm_cases.plane(family, shape, dtype, seed=3)
+    beta, gamma = norm_cases.params(shape[3], seed=3)
+    want64 = ref64.instancenorm(x, beta, gamma, 1e-5, act, 0.1)
+    model32 = ref64.instancenorm32(x, beta, gamma, 1e-5, act, 0.1)
+    floor = ref64.norm_floor(x, beta, gamma, 1e-5)
+    for a in (want64, model32, floor):
+        a.setflags(write=False)
+    return x, beta, gamma, want64, model32, floor
+
+
+def _norm_got(model32, dtype):
+    """What a tensor of that type hands back of an fp32 evaluation."""
+    return ref64.half(model32) if dtype == "f16" else model32
+
+
+def test_instancenorm_agrees_with_the_c_oracle():
+    """ref64.instancenorm against the fp32 C oracle (two passes over the plane, one term after the other) on a benign plane, to the oracle's precision:
+    its outputs are of magnitude 4 and its sums of 2400 terms lose a few ulps, 1e-5 leaves a factor of ten."""
+    shape = (2, 40, 60, 5)
+    x = norm_cases.plane("benign", shape)
+    beta, gamma = norm_cases.params(shape[3])
+    for act in ("", "relu", "leakyRelu"):
+        want = ref64.instancenorm(x, beta, gamma, 1e-5, act, 0.1)
+        assert want.dtype == np.float64
+        np.testing.assert_allclose(O.instancenorm(x, beta, gamma, act, 0.1), want, rtol=0, atol=1e-5)
+    np.testing.assert_allclose(O.instancenorm(x, beta, gamma, "", 0.0, eps=1e-3), ref64.instancenorm(x, beta, gamma, 1e-3), rtol=0, atol=1e-5)
+
+
+@pytest.mark.parametrize("shape,dtype,family", NORM_CASES, ids=NORM_IDS)
+def test_the_norm_stick_is_sound_on_every_family(shape, dtype, family):
+    """instancenorm32 on the adverse planes.  It is inside budget_norm at M = 1 by construction (it is the unit), rounded to half where the tensor is half.
+    That the unit itself is fp32-sized is the second assertion: per plane, E stays below half of M_NORM fp32 ulps of the largest output plus the shift
+    term |mean * mul| + |beta| -- an fp32 evaluation rounds the mean, the multiplier, the shift and the result once each, and a pairwise sum adds little
+    to that -- so M_NORM x E never grows into a tolerance that a lost digit passes."""
+    x, beta, gamma, want64, model32, floor = _norm_case(shape, dtype, family)
+    assert model32.dtype == np.float32 and want64.dtype == np.float64
+    ratio = ref64.budget_norm(_norm_got(model32, dtype), want64, model32, 1, floor, what=family, x=x, half_out=dtype == "f16")
+    assert ratio <= 1.0
+    e = np.abs(model32.astype(np.float64) - want64).max(axis=(1, 2))
+    unit = np.spacing(np.abs(want64).max(axis=(1, 2)).astype(np.float32)).astype(np.float64) + floor
+    worst = float((e / unit).max())
+    print("NORMSTICK %s %s %s: E = %.2f fp32 ulps of (largest output, shift term)" % ("x".join(map(str, shape)), dtype, family, worst))
+    assert worst <= ref64.M_NORM / 2, worst
+
+
+NORM_MUTANTS = {"variance": dict(var_scale=1.0 + 1e-3), "mean": dict(mean_shift=1e-3)}
+
+
+@pytest.mark.parametrize("kind", sorted(NORM_MUTANTS))
+@pytest.mark.parametrize("shape,dtype,family", NORM_CASES, ids=NORM_IDS)
+def test_budget_norm_rejects_the_mutants(shape, dtype, family, kind):
+    """The budget can fail: statistics off by 1e-3 -- var + eps scaled by 1 + 1e-3, or the mean moved by 1e-3 sqrt(var + eps) -- are rejected on every
+    family at M_NORM.  (Relative to var + eps, not to var: on a constant plane, and where the variance is far below eps, the result does not depend on
+    the variance at all and a mutant of it alone is no mutant.)  The variance mutant scales (x - mean) mul by 5e-4: on a constant plane that product
+    is zero and the exact result is unchanged, which is the one combination that must pass instead."""
+    x, beta, gamma, want64, model32, floor = _norm_case(shape, dtype, family)
+    y = ref64.instancenorm(x, beta, gamma, 1e-5, "leakyRelu", 0.1, **NORM_MUTANTS[kind])
+    y = ref64.half(y) if dtype == "f16" else y.astype(np.float32)
+    check = lambda: ref64.budget_norm(y, want64, model32, ref64.M_NORM, floor, what=kind, x=x, half_out=dtype == "f16")
+    if kind == "variance" and family == "constant":
+        check()
+        return
+    with pytest.raises(AssertionError) as info:
+        check()
+    assert "plane (n, c) = (" in str(info.value) and "std from the mean" in str(info.value), str(info.value)
