@@ -8,6 +8,7 @@
 //
 // Unlike the fixed-phase kernels next to it (frame_resample.h: r outputs per input, four taps from registers) every output coordinate has its own
 // weights and a shrinking axis reaches eight taps, so the two passes meet in LDS.  A block of 256 threads owns an output tile of TH x TW pixels.
+// The walk of pass 1 and the lane set-up of pass 2 are frame_fit_core.h's, shared with rgb_fit; this file has the strips and the epilogue.
 //   Pass 1, vertical: the tile's input column span is cut into dword-wide strips.  A lane walks its strip down the input rows with a window of the
 //     raw dwords of the last eight (four) rows, a few loads ahead of their use, and writes one filtered float row into LDS per output row; the rows'
 //     bases and weights are the same for the whole block (scalar loads).  When the span has fewer strips than the block has lanes (enlarging: 45 of 256
@@ -25,41 +26,34 @@
 namespace snnhip {
 namespace {
 
-struct FitParams {
-    int N, H, W, OH, OW;
-    int tilesX, tilesY;
-    int shift;
-    float maxval;
-    const float* wy; // [OH][8]
-    const int* by;   // [OH]
-    const float* wx; // [OW][8]
-    const int* bx;   // [OW]
-};
+using FitParams = FitHead; // plane_fit adds nothing to the shared head
 
-constexpr int kFitAhead = 4; // rows a strip's loads run ahead of their use
-
-// the dword of elements e .. e + NE - 1 of a row of W pixels; `fast`: the row is dword-aligned and the strip lies inside it
-template <typename E, int C>
-__device__ __forceinline__ unsigned fit_load_strip(const E* __restrict__ row, int e, int W, bool fast) {
-    constexpr int NE = 4 / static_cast<int>(sizeof(E)), BITS = 8 * static_cast<int>(sizeof(E));
-    unsigned w = 0u;
-    if (fast) {
-        load_words<1>(row + e, &w);
-    } else {
-#pragma unroll
-        for (int j = 0; j < NE; ++j) {
-            const int ee = e + j;
-            const int px = min(max(ee >> (C - 1), 0), W - 1); // arithmetic shift: floor for the columns left of the plane
-            w |= static_cast<unsigned>(row[static_cast<size_t>(px) * C + (ee & (C - 1))]) << (BITS * j);
-        }
+// the strips of pass 1 (frame_fit_core.h): a strip is the dword of elements pos .. pos + NE - 1 of a row; the window keeps the raw dwords and
+// converts when it filters (floats would take NE times the registers)
+template <typename E, int C, bool WIDE>
+struct PlaneFitStrips {
+    static constexpr FitRule R = kPlaneFitRule;
+    static constexpr FitGeom G{static_cast<int>(sizeof(E)), C, WIDE ? 1 : 0};
+    static constexpr int ES = static_cast<int>(sizeof(E)), NE = G.ne(), K0 = G.k0(), NT = G.taps(), NR = 1, NF = NE, NW = 1;
+    using Win = unsigned;
+    const E* plane;
+    int W, e0, shift;
+    __device__ __forceinline__ int pos(int s) const { return e0 + s * NE; }
+    __device__ __forceinline__ bool fast(int e) const { // the row is dword-aligned and the strip lies inside it
+        return (reinterpret_cast<size_t>(plane) & 3) == 0 && (static_cast<size_t>(W) * C * ES) % 4 == 0 && e >= 0 && e + NE <= W * C;
     }
-    return w;
-}
+    __device__ __forceinline__ void load(int cy, int e, bool fast, unsigned* raw) const { raw[0] = fit_load_strip<E, C>(plane + static_cast<size_t>(cy) * W * C, e, W, fast); }
+    __device__ __forceinline__ void enter(const unsigned* raw, unsigned* row) const { row[0] = raw[0]; }
+    __device__ __forceinline__ float at(const unsigned* row, int j) const { return static_cast<float>(frame_elem<E>(row, j) >> shift); }
+    __device__ __forceinline__ int off(int b) const { return (b - 3 + K0) * C - e0; }
+};
 
 template <typename E, int C, bool WIDE>
 __global__ __launch_bounds__(kFitThreads) void plane_fit_kernel(FitParams P, const E* __restrict__ in, E* __restrict__ out) {
-    constexpr FitGeom G{static_cast<int>(sizeof(E)), C, WIDE ? 1 : 0};
-    constexpr int ES = static_cast<int>(sizeof(E)), NE = G.ne(), TW = G.tw(), TH = G.th(), K0 = G.k0(), NT = G.taps(), RS = G.rowStride(), MAXS = G.maxStrips();
+    using V = PlaneFitStrips<E, C, WIDE>;
+    constexpr FitGeom G = V::G;
+    constexpr FitTile T = G.tile();
+    constexpr int ES = V::ES, NE = V::NE, TW = T.tw, TH = T.th(), NT = V::NT, RS = T.rowStride(), MAXS = T.maxStrips;
     constexpr int NPX = NE / C > 0 ? NE / C : 1; // pixels of an output dword (a 16-bit CbCr pixel is the whole dword)
     static_assert(TH * RS <= kFitLdsFloats && TH >= 1, "the tile's filtered rows fit the LDS");
     static_assert(C == 1 || C == 2, "one plane or interleaved CbCr");
@@ -73,99 +67,42 @@ __global__ __launch_bounds__(kFitThreads) void plane_fit_kernel(FitParams P, con
     const int tcols = min(TW, OW - ox0), trows = min(TH, OH - oy0);
     const E* plane = in + n * H * W * C;
 
-    // the tile's input column span as dword strips: elements e0 .. e0 + S * NE - 1 of a row, e0 a multiple of NE at or below its first element
-    const int e0 = ((P.bx[ox0] - 3 + K0) * C) & ~(NE - 1);
-    const int eLast = (P.bx[ox0 + tcols - 1] - 3 + K0 + NT - 1) * C + C - 1;
-    const int S = min((eLast - e0) / NE + 1, MAXS); // (the plan checked every tile against MAXS)
+    // the tile's input column span as dword strips: elements e0 .. e0 + S * NE - 1 of a row
+    const int e0 = G.first(P.bx[ox0]);
+    const int S = min(G.strips(e0, P.bx[ox0 + tcols - 1]), MAXS); // (the plan checked every tile against MAXS)
 
-    // ---- pass 1
-    {
-        const bool rowsAligned = (reinterpret_cast<size_t>(plane) & 3) == 0 && (static_cast<size_t>(W) * C * ES) % 4 == 0;
-        const int sets = S >= kFitThreads ? 1 : kFitThreads / S;
-        const int chunk = (trows + sets - 1) / sets;
-        for (int u = tid; u < S * sets; u += kFitThreads) {
-            const int s = u % S, q = u / S;
-            const int t0 = q * chunk, t1 = min(t0 + chunk, trows);
-            if (t0 >= t1) continue;
-            const int e = e0 + s * NE;
-            const bool fast = rowsAligned && e >= 0 && e + NE <= W * C;
-            int next = P.by[oy0 + t0] - 3 + K0;                    // the next input row to enter the window
-            const int last = P.by[oy0 + t1 - 1] - 3 + K0 + NT - 1; // the last one this chunk reads
-            unsigned win[NT], pre[kFitAhead];
-#pragma unroll
-            for (int k = 0; k < NT; ++k) win[k] = 0u;
-#pragma unroll
-            for (int k = 0; k < kFitAhead; ++k) {
-                const int cy = min(max(min(next + k, last), 0), H - 1);
-                pre[k] = fit_load_strip<E, C>(plane + static_cast<size_t>(cy) * W * C, e, W, fast);
-            }
-            for (int t = t0; t < t1; ++t) {
-                const int top = P.by[oy0 + t] - 3 + K0 + NT; // one past the window's last row
-                const float* wrow = P.wy + static_cast<size_t>(oy0 + t) * kFitTaps + K0;
-                while (next < top) {
-#pragma unroll
-                    for (int k = 0; k + 1 < NT; ++k) win[k] = win[k + 1];
-                    win[NT - 1] = pre[0];
-#pragma unroll
-                    for (int k = 0; k + 1 < kFitAhead; ++k) pre[k] = pre[k + 1];
-                    const int cy = min(max(min(next + kFitAhead, last), 0), H - 1);
-                    pre[kFitAhead - 1] = fit_load_strip<E, C>(plane + static_cast<size_t>(cy) * W * C, e, W, fast);
-                    ++next;
-                }
-                float wk[NT];
-#pragma unroll
-                for (int k = 0; k < NT; ++k) wk[k] = wrow[k];
-                float* dst = lds + t * RS;
-#pragma unroll
-                for (int j = 0; j < NE; ++j) {
-                    float acc = wk[0] * static_cast<float>(frame_elem<E>(&win[0], j) >> P.shift);
-#pragma unroll
-                    for (int k = 1; k < NT; ++k) acc += wk[k] * static_cast<float>(frame_elem<E>(&win[k], j) >> P.shift);
-                    dst[fit_skew(s * NE + j)] = acc;
-                }
-            }
-        }
-    }
+    const V v{plane, W, e0, P.shift};
+    fit_vertical_pass(v, P, lds, RS, S, oy0, trows, tid);
     __syncthreads();
 
-    // ---- pass 2
-    {
-        const int g = tid & 63; // the lane's dword of an output row of the tile
-        if (g * NPX >= tcols) return;
-        float w[NPX][NT];
-        int off[NPX];
+    // ---- pass 2: quantise and pack.  Whole dwords out; elements where the row is not dword-aligned or the dword crosses the edge.
+    const int g = tid & 63; // the lane's dword of an output row of the tile
+    if (g * NPX >= tcols) return;
+    const FitLane<NPX, NT> L = fit_lane<NPX>(v, P, g, ox0, tcols);
+    const int valid = L.valid * C; // elements of the lane's dword inside the plane
+    E* oplane = out + n * OH * OW * C;
+    const bool whole = valid == NE && (reinterpret_cast<size_t>(oplane) & 3) == 0 && (static_cast<size_t>(OW) * C * ES) % 4 == 0;
+    for (int t = tid >> 6; t < trows; t += kFitWaves) {
+        const float* src = lds + t * RS;
+        unsigned q[NE];
 #pragma unroll
-        for (int p = 0; p < NPX; ++p) {
-            const int X = min(ox0 + g * NPX + p, OW - 1);
-            off[p] = (P.bx[X] - 3 + K0) * C - e0;
+        for (int j = 0; j < NE; ++j) {
+            const int p = j / C, c = j % C;
+            float acc = L.w[p][0] * src[fit_skew(L.off[p] + c)];
 #pragma unroll
-            for (int k = 0; k < NT; ++k) w[p][k] = P.wx[static_cast<size_t>(X) * kFitTaps + K0 + k];
+            for (int k = 1; k < NT; ++k) acc += L.w[p][k] * src[fit_skew(L.off[p] + k * C + c)];
+            q[j] = quantize_frame(acc, P.maxval) << P.shift;
         }
-        const int valid = min(NPX, tcols - g * NPX) * C; // elements of the lane's dword inside the plane
-        E* oplane = out + n * OH * OW * C;
-        const bool whole = valid == NE && (reinterpret_cast<size_t>(oplane) & 3) == 0 && (static_cast<size_t>(OW) * C * ES) % 4 == 0;
-        for (int t = tid >> 6; t < trows; t += kFitThreads / 64) {
-            const float* src = lds + t * RS;
-            unsigned q[NE];
+        E* dst = oplane + (static_cast<size_t>(oy0 + t) * OW + ox0) * C + static_cast<size_t>(g) * NE;
+        if (whole) {
+            unsigned word = 0u;
 #pragma unroll
-            for (int j = 0; j < NE; ++j) {
-                const int p = j / C, c = j % C;
-                float acc = w[p][0] * src[fit_skew(off[p] + c)];
+            for (int j = 0; j < NE; ++j) word |= q[j] << (8 * ES * j);
+            store_words<1>(dst, &word);
+        } else {
 #pragma unroll
-                for (int k = 1; k < NT; ++k) acc += w[p][k] * src[fit_skew(off[p] + k * C + c)];
-                q[j] = quantize_frame(acc, P.maxval) << P.shift;
-            }
-            E* dst = oplane + (static_cast<size_t>(oy0 + t) * OW + ox0) * C + static_cast<size_t>(g) * NE;
-            if (whole) {
-                unsigned word = 0u;
-#pragma unroll
-                for (int j = 0; j < NE; ++j) word |= q[j] << (8 * ES * j);
-                store_words<1>(dst, &word);
-            } else {
-#pragma unroll
-                for (int j = 0; j < NE; ++j)
-                    if (j < valid) dst[j] = static_cast<E>(q[j]);
-            }
+            for (int j = 0; j < NE; ++j)
+                if (j < valid) dst[j] = static_cast<E>(q[j]);
         }
     }
 }
@@ -214,7 +151,7 @@ using namespace snnhip;
 extern "C" {
 
 int snnhip_fit_taps(int in, int out, int siting, float* weights, int* base, int capacity) {
-    return fill_fit_taps("fit_taps", in, out, siting, weights, base, capacity);
+    return fill_fit_taps(kPlaneFitRule, "fit_taps", in, out, siting, weights, base, capacity);
 }
 
 int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* desc, snnhip_plan** out) {
@@ -231,28 +168,14 @@ int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* d
     if (fmt != SNNHIP_OK) return fmt;
     const bool wide = desc->OH < desc->H || desc->OW < desc->W;
     const FitGeom g{bits / 8, desc->C, wide ? 1 : 0};
-    const int th = g.th(), tw = g.tw();
-    const int tilesX = up_div(desc->OW, tw), tilesY = up_div(desc->OH, th);
-    const double blocks = static_cast<double>(desc->N) * tilesX * tilesY;
+    const FitTile tile = g.tile();
     const double inElems = static_cast<double>(desc->N) * desc->H * desc->W * desc->C;
     const double outElems = static_cast<double>(desc->N) * desc->OH * desc->OW * desc->C;
-    SNNHIP_REQUIRE(blocks < 2147483648.0 && inElems < 9.0e15 && outElems < 9.0e15 && static_cast<double>(desc->W) * desc->C < 1.0e9 &&
-                       static_cast<double>(desc->OW) * kFitTaps < 2.0e9 && static_cast<double>(desc->OH) * kFitTaps < 2.0e9,
-                   "plane_fit desc: %dx%dx%d -> %dx%d is too large", desc->N, desc->H, desc->W, desc->OH, desc->OW);
-    std::vector<float> wy(static_cast<size_t>(desc->OH) * kFitTaps), wx(static_cast<size_t>(desc->OW) * kFitTaps);
-    std::vector<int> by(desc->OH), bx(desc->OW);
-    int rc = snnhip_fit_taps(desc->H, desc->OH, SNNHIP_SITING_CENTRE, wy.data(), by.data(), static_cast<int>(wy.size()));
-    if (rc == SNNHIP_OK) rc = snnhip_fit_taps(desc->W, desc->OW, desc->siting, wx.data(), bx.data(), static_cast<int>(wx.size()));
+    SNNHIP_REQUIRE(inElems < 9.0e15 && outElems < 9.0e15 && static_cast<double>(desc->W) * desc->C < 1.0e9, "plane_fit desc: %dx%dx%d -> %dx%d is too large", desc->N, desc->H,
+                   desc->W, desc->OH, desc->OW);
+    FitAxes axes;
+    int rc = axes.build("plane_fit", snnhip_fit_taps, kFitTaps, g, desc->N, desc->H, desc->W, desc->OH, desc->OW, desc->siting);
     if (rc != SNNHIP_OK) return rc;
-    // what the kernel relies on: bases never step back, and no tile's column span has more strips than its LDS rows hold
-    for (int x = 1; x < desc->OW; ++x) SNNHIP_REQUIRE(bx[x] >= bx[x - 1], "plane_fit: column bases step back at %d", x);
-    for (int y = 1; y < desc->OH; ++y) SNNHIP_REQUIRE(by[y] >= by[y - 1], "plane_fit: row bases step back at %d", y);
-    for (int tx = 0; tx < tilesX; ++tx) {
-        const int x0 = tx * tw, x1 = std::min(x0 + tw, desc->OW) - 1;
-        const int e0 = ((bx[x0] - g.lo()) * desc->C) & ~(g.ne() - 1);
-        const int eLast = (bx[x1] + g.hi()) * desc->C + desc->C - 1;
-        SNNHIP_REQUIRE((eLast - e0) / g.ne() + 1 <= g.maxStrips(), "plane_fit: tile column %d spans %d strips, %d fit", tx, (eLast - e0) / g.ne() + 1, g.maxStrips());
-    }
     auto* plan = new PlaneFitPlan();
     plan->ctx = ctx;
     plan->dtype = desc->dtype;
@@ -260,30 +183,11 @@ int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* d
     plan->rawOutput = desc->dtype;
     plan->d = *desc;
     plan->wide = wide;
-    plan->P = FitParams{};
-    plan->P.N = desc->N;
-    plan->P.H = desc->H;
-    plan->P.W = desc->W;
-    plan->P.OH = desc->OH;
-    plan->P.OW = desc->OW;
-    plan->P.tilesX = tilesX;
-    plan->P.tilesY = tilesY;
-    plan->P.shift = desc->shift;
-    plan->P.maxval = static_cast<float>(desc->maxval);
-    float *dwy = nullptr, *dwx = nullptr, *dby = nullptr, *dbx = nullptr;
-    rc = plan->upload(wy.data(), wy.size(), &dwy);
-    if (rc == SNNHIP_OK) rc = plan->upload(wx.data(), wx.size(), &dwx);
-    if (rc == SNNHIP_OK) rc = plan->upload(reinterpret_cast<const float*>(by.data()), by.size(), &dby); // (a copy of bytes: ints are as wide as floats)
-    if (rc == SNNHIP_OK) rc = plan->upload(reinterpret_cast<const float*>(bx.data()), bx.size(), &dbx);
+    rc = axes.upload(plan, &plan->P, desc->shift, desc->maxval);
     if (rc != SNNHIP_OK) {
         delete plan;
         return rc;
     }
-    static_assert(sizeof(int) == sizeof(float), "the base tables travel through upload()");
-    plan->P.wy = dwy;
-    plan->P.wx = dwx;
-    plan->P.by = reinterpret_cast<const int*>(dby);
-    plan->P.bx = reinterpret_cast<const int*>(dbx);
     plan->inDims[0] = plan->outDims[0] = desc->N;
     plan->inDims[1] = desc->H;
     plan->inDims[2] = desc->W;
@@ -295,8 +199,8 @@ int snnhip_plane_fit_plan_create(snnhip_ctx* ctx, const snnhip_plane_fit_desc* d
     plan->flops = 2.0 * nt * (outElems + static_cast<double>(desc->N) * desc->OH * desc->W * desc->C); // both passes
     char buf[280];
     snprintf(buf, sizeof(buf), "plane_fit_u%d c=%d %dx%d->%dx%d siting=%s tile=%dx%d taps=%d lds=%d maxval=%d shift=%d kernel=plane_fit_kernel", bits, desc->C, desc->H,
-             desc->W, desc->OH, desc->OW, desc->siting == SNNHIP_SITING_LEFT ? "left" : "centre", th, tw, nt, static_cast<int>(kFitLdsFloats * sizeof(float)), desc->maxval,
-             desc->shift);
+             desc->W, desc->OH, desc->OW, desc->siting == SNNHIP_SITING_LEFT ? "left" : "centre", tile.th(), tile.tw, nt, static_cast<int>(kFitLdsFloats * sizeof(float)),
+             desc->maxval, desc->shift);
     plan->desc = buf;
     *out = plan;
     return SNNHIP_OK;

@@ -8,8 +8,8 @@
 //             the quantiser are yuv_rgb's for the video sources and ycc_merge's for the colour frame.
 //
 // The fixed-phase RGB kernels (frame_yuv_rgb.hip, frame_colour.hip) keep r or 2r phases in registers; a base per output coordinate would turn their
-// register windows into dynamically indexed arrays, that is, scratch.  So this kernel has plane_fit's shape (frame_fit.hip): the two passes meet in
-// LDS, and a block of 256 threads owns an output tile of TH x TW pixels.
+// register windows into dynamically indexed arrays, that is, scratch.  So this kernel has plane_fit's shape (frame_fit.hip) and shares its walk
+// (frame_fit_core.h: pass 1, the lane set-up of pass 2): the two passes meet in LDS, and a block of 256 threads owns an output tile of TH x TW pixels.
 //   Pass 1, vertical: the tile's source column span is cut into strips of SP pixels -- a dword of CbCr, a dword of each plane, four RGB(A) pixels --
 //     one lane per strip.  A lane walks its strip down the source rows with a window of the last four rows as float pairs, (Cb - Coff, Cr - Coff) or
 //     (dB, dR), converted once when a row enters (an enlarged source row serves several output rows); raw loads run a few rows ahead of their use.
@@ -29,121 +29,96 @@
 namespace snnhip {
 namespace {
 
-struct RgbFitParams {
-    int N, H, W, OH, OW; // H, W: the chroma source
-    int tilesX, tilesY;
-    int shift;
-    float maxval;
+struct RgbFitParams : FitHead { // H, W: the chroma source
     unsigned alpha;   // maxval << shift (video sources)
     YuvRgbCoeffs m;   // video sources
     float kr, kg, kb; // the RGB source
-    const float* wy;  // [OH][4]
-    const int* by;    // [OH]
-    const float* wx;  // [OW][4]
-    const int* bx;    // [OW]
 };
 
-constexpr int kRgbFitAhead = 4; // rows a strip's loads run ahead of their use
-
+// the strips of pass 1 (frame_fit_core.h): a strip is SP source pixels from pixel pos on -- a dword of CbCr, a dword of each plane, four RGB(A)
+// pixels; the window keeps float pairs, converted once when a row enters (an enlarged source row serves several output rows)
 template <typename E, int SRC, int CO>
-struct RgbFitLane {
+struct RgbFitStrips {
+    static constexpr FitRule R = kRgbFitRule;
     static constexpr int ES = static_cast<int>(sizeof(E)), NE = 4 / ES, BITS = 8 * ES;
     static constexpr RgbFitGeom G{ES, SRC};
+    static constexpr int K0 = R.k0, NT = R.nk;
     static constexpr int SP = G.sp();                                                                   // source pixels of a strip
-    static constexpr int NF = 2 * SP;                                                                   // floats of a strip in a filtered row
+    static constexpr int NF = 2 * SP, NW = NF;                                                          // floats of a strip in a filtered row
     static constexpr int NR = SRC == SNNHIP_RGB_FIT_CBCR ? 1 : SRC == SNNHIP_RGB_FIT_PLANAR ? 2 : CO; // raw dwords of a strip in a source row
     static_assert(SRC != SNNHIP_RGB_FIT_RGB || ES == 1, "colour frames are 8-bit");
     static_assert(SRC != SNNHIP_RGB_FIT_CBCR || NF == NE, "a CbCr strip is one dword");
-};
+    using Win = float;
+    const RgbFitParams& P;
+    const E* img; // image n of the source: its CbCr plane, its Cb plane (Cr follows planeElems behind it) or its colour frame
+    size_t planeElems;
+    int W, px0;
+    bool rowsAligned; // every row of the image starts on a dword (one decision for the block)
 
-// whether every row of image `img` of the source starts on a dword (one decision for the block)
-template <typename E, int SRC, int CO>
-__device__ __forceinline__ bool rgb_fit_rows_aligned(const E* img, size_t planeElems, int W) {
-    constexpr int ES = static_cast<int>(sizeof(E));
-    if constexpr (SRC == SNNHIP_RGB_FIT_CBCR) return (reinterpret_cast<size_t>(img) & 3) == 0 && (static_cast<size_t>(W) * 2 * ES) % 4 == 0;
-    else if constexpr (SRC == SNNHIP_RGB_FIT_PLANAR)
-        return ((reinterpret_cast<size_t>(img) | reinterpret_cast<size_t>(img + planeElems)) & 3) == 0 && (static_cast<size_t>(W) * ES) % 4 == 0;
-    else return (reinterpret_cast<size_t>(img) & 3) == 0 && (static_cast<size_t>(W) * CO) % 4 == 0;
-}
-
-// the raw dwords of source pixels px .. px + SP - 1 of row cy (0 <= cy < H); `fast`: rows are dword-aligned and the strip lies inside the row
-// (px is a multiple of SP, so the strip starts on a dword); otherwise elements, the pixel index clamped to [0, W - 1]
-template <typename E, int SRC, int CO>
-__device__ __forceinline__ void rgb_fit_load(const E* __restrict__ img, size_t planeElems, int cy, int px, int W, bool fast, unsigned* raw) {
-    using L = RgbFitLane<E, SRC, CO>;
-    if constexpr (SRC == SNNHIP_RGB_FIT_CBCR) {
-        const E* row = img + static_cast<size_t>(cy) * W * 2;
-        if (fast) {
-            load_words<1>(row + static_cast<size_t>(px) * 2, raw);
+    __device__ __forceinline__ RgbFitStrips(const RgbFitParams& P_, const E* img_, size_t planeElems_, int px0_) : P(P_), img(img_), planeElems(planeElems_), W(P_.W), px0(px0_) {
+        if constexpr (SRC == SNNHIP_RGB_FIT_CBCR) rowsAligned = (reinterpret_cast<size_t>(img) & 3) == 0 && (static_cast<size_t>(W) * 2 * ES) % 4 == 0;
+        else if constexpr (SRC == SNNHIP_RGB_FIT_PLANAR)
+            rowsAligned = ((reinterpret_cast<size_t>(img) | reinterpret_cast<size_t>(img + planeElems)) & 3) == 0 && (static_cast<size_t>(W) * ES) % 4 == 0;
+        else rowsAligned = (reinterpret_cast<size_t>(img) & 3) == 0 && (static_cast<size_t>(W) * CO) % 4 == 0;
+    }
+    __device__ __forceinline__ int pos(int s) const { return px0 + s * SP; }
+    // (px is a multiple of SP, so a strip inside the row starts on a dword)
+    __device__ __forceinline__ bool fast(int px) const { return rowsAligned && px >= 0 && px + SP <= W; }
+    // the raw dwords of source pixels px .. px + SP - 1 of row cy; unless `fast`, by elements, the pixel index clamped to [0, W - 1]
+    __device__ __forceinline__ void load(int cy, int px, bool fast, unsigned* raw) const {
+        if constexpr (SRC == SNNHIP_RGB_FIT_CBCR) {
+            raw[0] = fit_load_strip<E, 2>(img + static_cast<size_t>(cy) * W * 2, px * 2, W, fast);
+        } else if constexpr (SRC == SNNHIP_RGB_FIT_PLANAR) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) raw[c] = fit_load_strip<E, 1>(img + c * planeElems + static_cast<size_t>(cy) * W, px, W, fast);
         } else {
-            unsigned w = 0u;
-#pragma unroll
-            for (int j = 0; j < L::NE; ++j) {
-                const int p = min(max(px + (j >> 1), 0), W - 1);
-                w |= static_cast<unsigned>(row[static_cast<size_t>(p) * 2 + (j & 1)]) << (L::BITS * j);
-            }
-            raw[0] = w;
-        }
-    } else if constexpr (SRC == SNNHIP_RGB_FIT_PLANAR) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const E* row = img + c * planeElems + static_cast<size_t>(cy) * W;
+            const E* row = img + static_cast<size_t>(cy) * W * CO;
             if (fast) {
-                load_words<1>(row + px, raw + c);
+                load_words<CO>(row + static_cast<size_t>(px) * CO, raw);
             } else {
-                unsigned w = 0u;
 #pragma unroll
-                for (int j = 0; j < L::NE; ++j) w |= static_cast<unsigned>(row[min(max(px + j, 0), W - 1)]) << (L::BITS * j);
-                raw[c] = w;
+                for (int k = 0; k < CO; ++k) raw[k] = 0u;
+#pragma unroll
+                for (int i = 0; i < 4 * CO; ++i) {
+                    const int p = min(max(px + i / CO, 0), W - 1);
+                    raw[i >> 2] |= static_cast<unsigned>(row[static_cast<size_t>(p) * CO + i % CO]) << (8 * (i & 3));
+                }
             }
         }
-    } else {
-        const E* row = img + static_cast<size_t>(cy) * W * CO;
-        if (fast) {
-            load_words<CO>(row + static_cast<size_t>(px) * CO, raw);
+    }
+    // a strip's raw dwords as the float pairs that are filtered: (Cb - Coff, Cr - Coff), exact in fp32, or (dB, dR) around the unquantised luma
+    __device__ __forceinline__ void enter(const unsigned* raw, float* f) const {
+        if constexpr (SRC == SNNHIP_RGB_FIT_CBCR) {
+#pragma unroll
+            for (int j = 0; j < NF; ++j) f[j] = static_cast<float>(frame_elem<E>(raw, j) >> P.shift) - P.m.coff;
+        } else if constexpr (SRC == SNNHIP_RGB_FIT_PLANAR) {
+#pragma unroll
+            for (int p = 0; p < SP; ++p) {
+                f[2 * p] = static_cast<float>(frame_elem<E>(raw, p) >> P.shift) - P.m.coff;
+                f[2 * p + 1] = static_cast<float>(frame_elem<E>(raw + 1, p) >> P.shift) - P.m.coff;
+            }
         } else {
 #pragma unroll
-            for (int k = 0; k < CO; ++k) raw[k] = 0u;
-#pragma unroll
-            for (int i = 0; i < 4 * CO; ++i) {
-                const int p = min(max(px + i / CO, 0), W - 1);
-                raw[i >> 2] |= static_cast<unsigned>(row[static_cast<size_t>(p) * CO + i % CO]) << (8 * (i & 3));
+            for (int p = 0; p < SP; ++p) {
+                const float r = static_cast<float>(frame_elem<E>(raw, p * CO)), g = static_cast<float>(frame_elem<E>(raw, p * CO + 1)),
+                            b = static_cast<float>(frame_elem<E>(raw, p * CO + 2));
+                const float yl = luma_f32(r, g, b, P.kr, P.kg, P.kb);
+                f[2 * p] = b - yl;
+                f[2 * p + 1] = r - yl;
             }
         }
     }
-}
-
-// a strip's raw dwords as the float pairs that are filtered: (Cb - Coff, Cr - Coff), exact in fp32, or (dB, dR) around the unquantised luma
-template <typename E, int SRC, int CO>
-__device__ __forceinline__ void rgb_fit_convert(const RgbFitParams& P, const unsigned* raw, float* f) {
-    using L = RgbFitLane<E, SRC, CO>;
-    if constexpr (SRC == SNNHIP_RGB_FIT_CBCR) {
-#pragma unroll
-        for (int j = 0; j < L::NF; ++j) f[j] = static_cast<float>(frame_elem<E>(raw, j) >> P.shift) - P.m.coff;
-    } else if constexpr (SRC == SNNHIP_RGB_FIT_PLANAR) {
-#pragma unroll
-        for (int p = 0; p < L::SP; ++p) {
-            f[2 * p] = static_cast<float>(frame_elem<E>(raw, p) >> P.shift) - P.m.coff;
-            f[2 * p + 1] = static_cast<float>(frame_elem<E>(raw + 1, p) >> P.shift) - P.m.coff;
-        }
-    } else {
-#pragma unroll
-        for (int p = 0; p < L::SP; ++p) {
-            const float r = static_cast<float>(frame_elem<E>(raw, p * CO)), g = static_cast<float>(frame_elem<E>(raw, p * CO + 1)),
-                        b = static_cast<float>(frame_elem<E>(raw, p * CO + 2));
-            const float yl = luma_f32(r, g, b, P.kr, P.kg, P.kb);
-            f[2 * p] = b - yl;
-            f[2 * p + 1] = r - yl;
-        }
-    }
-}
+    __device__ __forceinline__ float at(const float* row, int j) const { return row[j]; }
+    __device__ __forceinline__ int off(int b) const { return (b - 1 - px0) * 2; }
+};
 
 template <typename E, int SRC, int CO>
 __global__ __launch_bounds__(kFitThreads) void rgb_fit_kernel(RgbFitParams P, const E* __restrict__ yfit, const E* __restrict__ src, E* __restrict__ out) {
-    using L = RgbFitLane<E, SRC, CO>;
-    constexpr RgbFitGeom G = L::G;
-    constexpr int ES = L::ES, NE = L::NE, BITS = L::BITS, SP = L::SP, NF = L::NF, NR = L::NR, NT = kRgbFitTaps;
-    constexpr int NPX = G.npx(), TW = G.tw(), TH = G.th(), RS = G.rowStride(), MAXS = G.maxStrips();
+    using V = RgbFitStrips<E, SRC, CO>;
+    constexpr RgbFitGeom G = V::G;
+    constexpr FitTile T = G.tile();
+    constexpr int ES = V::ES, NE = V::NE, BITS = V::BITS, NT = V::NT;
+    constexpr int NPX = G.npx(), TW = T.tw, TH = T.th(), RS = T.rowStride(), MAXS = T.maxStrips;
     static_assert(TH * RS <= kFitLdsFloats && TH >= 1, "the tile's filtered rows fit the LDS");
     static_assert(NPX == NE, "a lane owns one dword of Yfit");
     __shared__ float lds[kFitLdsFloats];
@@ -155,139 +130,79 @@ __global__ __launch_bounds__(kFitThreads) void rgb_fit_kernel(RgbFitParams P, co
     const int ox0 = tile.tx * TW, oy0 = tile.ty * TH;
     const int tcols = min(TW, OW - ox0), trows = min(TH, OH - oy0);
     const size_t planeElems = static_cast<size_t>(H) * W;
-    // image n of the source: its CbCr plane, its Cb plane (Cr follows planeElems behind it) or its colour frame
     const E* img = src + n * planeElems * (SRC == SNNHIP_RGB_FIT_RGB ? CO : 2);
 
-    // the tile's source column span as strips: pixels px0 .. px0 + S * SP - 1, px0 a multiple of SP at or below its first pixel
-    const int px0 = (P.bx[ox0] - 1) & ~(SP - 1); // (two's complement: the floor for the columns left of the source)
-    const int pxLast = P.bx[ox0 + tcols - 1] + 2;
-    const int S = min((pxLast - px0) / SP + 1, MAXS); // (the plan checked every tile against MAXS)
+    // the tile's source column span as strips: pixels px0 .. px0 + S * SP - 1
+    const int px0 = G.first(P.bx[ox0]);
+    const int S = min(G.strips(px0, P.bx[ox0 + tcols - 1]), MAXS); // (the plan checked every tile against MAXS)
 
-    // ---- pass 1
-    {
-        const bool rowsAligned = rgb_fit_rows_aligned<E, SRC, CO>(img, planeElems, W);
-        const int sets = S >= kFitThreads ? 1 : kFitThreads / S;
-        const int chunk = (trows + sets - 1) / sets;
-        for (int u = tid; u < S * sets; u += kFitThreads) {
-            const int s = u % S, q = u / S;
-            const int t0 = q * chunk, t1 = min(t0 + chunk, trows);
-            if (t0 >= t1) continue;
-            const int px = px0 + s * SP;
-            const bool fast = rowsAligned && px >= 0 && px + SP <= W;
-            int next = P.by[oy0 + t0] - 1;            // the next source row to enter the window
-            const int last = P.by[oy0 + t1 - 1] + 2;  // the last one this chunk reads
-            float win[NT][NF];
-            unsigned pre[kRgbFitAhead][NR];
-#pragma unroll
-            for (int k = 0; k < NT; ++k)
-#pragma unroll
-                for (int j = 0; j < NF; ++j) win[k][j] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < kRgbFitAhead; ++k) rgb_fit_load<E, SRC, CO>(img, planeElems, min(max(min(next + k, last), 0), H - 1), px, W, fast, pre[k]);
-            for (int t = t0; t < t1; ++t) {
-                const int top = P.by[oy0 + t] - 1 + NT; // one past the window's last row
-                const float* wrow = P.wy + static_cast<size_t>(oy0 + t) * NT;
-                while (next < top) {
-#pragma unroll
-                    for (int k = 0; k + 1 < NT; ++k)
-#pragma unroll
-                        for (int j = 0; j < NF; ++j) win[k][j] = win[k + 1][j];
-                    rgb_fit_convert<E, SRC, CO>(P, pre[0], win[NT - 1]);
-#pragma unroll
-                    for (int k = 0; k + 1 < kRgbFitAhead; ++k)
-#pragma unroll
-                        for (int j = 0; j < NR; ++j) pre[k][j] = pre[k + 1][j];
-                    rgb_fit_load<E, SRC, CO>(img, planeElems, min(max(min(next + kRgbFitAhead, last), 0), H - 1), px, W, fast, pre[kRgbFitAhead - 1]);
-                    ++next;
-                }
-                float wk[NT];
-#pragma unroll
-                for (int k = 0; k < NT; ++k) wk[k] = wrow[k];
-                float* dst = lds + t * RS;
-#pragma unroll
-                for (int j = 0; j < NF; ++j) {
-                    float acc = wk[0] * win[0][j];
-#pragma unroll
-                    for (int k = 1; k < NT; ++k) acc += wk[k] * win[k][j];
-                    dst[fit_skew(s * NF + j)] = acc;
-                }
-            }
-        }
-    }
+    const V v(P, img, planeElems, px0);
+    fit_vertical_pass(v, P, lds, RS, S, oy0, trows, tid);
     __syncthreads();
 
-    // ---- pass 2
-    {
-        const int g = tid & 63; // the lane's dword of a row of Yfit
-        if (g * NPX >= tcols) return;
-        float w[NPX][NT];
-        int off[NPX];
-        int ax[NPX]; // the source column whose alpha an output column copies (colour frames with C = 4)
+    // ---- pass 2.  Per row: the taps from LDS, the Yfit dword from memory, the matrix, the quantiser, C dwords out
+    const int g = tid & 63; // the lane's dword of a row of Yfit
+    if (g * NPX >= tcols) return;
+    const FitLane<NPX, NT> F = fit_lane<NPX>(v, P, g, ox0, tcols);
+    int ax[NPX]; // the source column whose alpha an output column copies (colour frames with C = 4)
+#pragma unroll
+    for (int p = 0; p < NPX; ++p) ax[p] = static_cast<int>((2ll * F.X[p] + 1) * W / (2ll * OW));
+    const int valid = F.valid; // pixels of the lane's dword inside the frame
+    const E* yimg = yfit + n * OH * OW;
+    E* oimg = out + n * OH * OW * CO;
+    const bool whole = valid == NPX && ((reinterpret_cast<size_t>(yimg) | reinterpret_cast<size_t>(oimg)) & 3) == 0 && (static_cast<size_t>(OW) * ES) % 4 == 0 &&
+                       (static_cast<size_t>(OW) * CO * ES) % 4 == 0;
+    for (int t = tid >> 6; t < trows; t += kFitWaves) {
+        const float* row = lds + t * RS;
+        const size_t pix = static_cast<size_t>(oy0 + t) * OW + ox0 + static_cast<size_t>(g) * NPX;
+        unsigned u = 0u;
+        if (whole) {
+            load_words<1>(yimg + pix, &u);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NPX; ++j)
+                if (j < valid) u |= static_cast<unsigned>(yimg[pix + j]) << (BITS * j);
+        }
+        const E* arow = img; // (read for colour frames with C = 4 only)
+        if constexpr (SRC == SNNHIP_RGB_FIT_RGB && CO == 4) arow = img + static_cast<size_t>((2ll * (oy0 + t) + 1) * H / (2ll * OH)) * W * CO;
+        unsigned word[CO];
+#pragma unroll
+        for (int k = 0; k < CO; ++k) word[k] = 0u;
 #pragma unroll
         for (int p = 0; p < NPX; ++p) {
-            const int X = min(ox0 + g * NPX + p, OW - 1);
-            off[p] = (P.bx[X] - 1 - px0) * 2;
-            ax[p] = static_cast<int>((2ll * X + 1) * W / (2ll * OW));
+            float c0 = F.w[p][0] * row[fit_skew(F.off[p])], c1 = F.w[p][0] * row[fit_skew(F.off[p] + 1)];
 #pragma unroll
-            for (int k = 0; k < NT; ++k) w[p][k] = P.wx[static_cast<size_t>(X) * NT + k];
+            for (int k = 1; k < NT; ++k) {
+                c0 += F.w[p][k] * row[fit_skew(F.off[p] + 2 * k)];
+                c1 += F.w[p][k] * row[fit_skew(F.off[p] + 2 * k + 1)];
+            }
+            const float yv = static_cast<float>(frame_elem<E>(&u, p) >> P.shift);
+            unsigned e[4];
+            if constexpr (SRC == SNNHIP_RGB_FIT_RGB) { // c0 = dB~, c1 = dR~
+                e[0] = quantize_frame(yv + c1, P.maxval);
+                e[1] = quantize_frame(yv - (P.kr * c1 + P.kb * c0) / P.kg, P.maxval);
+                e[2] = quantize_frame(yv + c0, P.maxval);
+                e[3] = CO == 4 ? static_cast<unsigned>(arow[static_cast<size_t>(ax[p]) * CO + 3]) : 0u;
+            } else { // c0 = Cb~ - Coff, c1 = Cr~ - Coff
+                const float yl = P.m.cy * (yv - P.m.yoff);
+                e[0] = quantize_frame(yl + P.m.crv * c1, P.maxval) << P.shift;
+                e[1] = quantize_frame(yl - (P.m.cgv * c1 + P.m.cgu * c0), P.maxval) << P.shift;
+                e[2] = quantize_frame(yl + P.m.cbu * c0, P.maxval) << P.shift;
+                e[3] = P.alpha;
+            }
+#pragma unroll
+            for (int c = 0; c < CO; ++c) {
+                const int i = p * CO + c;
+                word[i / NE] |= e[c] << (BITS * (i % NE));
+            }
         }
-        const int valid = min(NPX, tcols - g * NPX); // pixels of the lane's dword inside the frame
-        const E* yimg = yfit + n * OH * OW;
-        E* oimg = out + n * OH * OW * CO;
-        const bool whole = valid == NPX && ((reinterpret_cast<size_t>(yimg) | reinterpret_cast<size_t>(oimg)) & 3) == 0 && (static_cast<size_t>(OW) * ES) % 4 == 0 &&
-                           (static_cast<size_t>(OW) * CO * ES) % 4 == 0;
-        for (int t = tid >> 6; t < trows; t += kFitThreads / 64) {
-            const float* row = lds + t * RS;
-            const size_t pix = static_cast<size_t>(oy0 + t) * OW + ox0 + static_cast<size_t>(g) * NPX;
-            unsigned u = 0u;
-            if (whole) {
-                load_words<1>(yimg + pix, &u);
-            } else {
+        E* dst = oimg + pix * CO;
+        if (whole) {
+            store_words<CO>(dst, word);
+        } else {
 #pragma unroll
-                for (int j = 0; j < NPX; ++j)
-                    if (j < valid) u |= static_cast<unsigned>(yimg[pix + j]) << (BITS * j);
-            }
-            const E* arow = img; // (read for colour frames with C = 4 only)
-            if constexpr (SRC == SNNHIP_RGB_FIT_RGB && CO == 4) arow = img + static_cast<size_t>((2ll * (oy0 + t) + 1) * H / (2ll * OH)) * W * CO;
-            unsigned word[CO];
-#pragma unroll
-            for (int k = 0; k < CO; ++k) word[k] = 0u;
-#pragma unroll
-            for (int p = 0; p < NPX; ++p) {
-                float c0 = w[p][0] * row[fit_skew(off[p])], c1 = w[p][0] * row[fit_skew(off[p] + 1)];
-#pragma unroll
-                for (int k = 1; k < NT; ++k) {
-                    c0 += w[p][k] * row[fit_skew(off[p] + 2 * k)];
-                    c1 += w[p][k] * row[fit_skew(off[p] + 2 * k + 1)];
-                }
-                const float yv = static_cast<float>(frame_elem<E>(&u, p) >> P.shift);
-                unsigned e[4];
-                if constexpr (SRC == SNNHIP_RGB_FIT_RGB) { // c0 = dB~, c1 = dR~
-                    e[0] = quantize_frame(yv + c1, P.maxval);
-                    e[1] = quantize_frame(yv - (P.kr * c1 + P.kb * c0) / P.kg, P.maxval);
-                    e[2] = quantize_frame(yv + c0, P.maxval);
-                    e[3] = CO == 4 ? static_cast<unsigned>(arow[static_cast<size_t>(ax[p]) * CO + 3]) : 0u;
-                } else { // c0 = Cb~ - Coff, c1 = Cr~ - Coff
-                    const float yl = P.m.cy * (yv - P.m.yoff);
-                    e[0] = quantize_frame(yl + P.m.crv * c1, P.maxval) << P.shift;
-                    e[1] = quantize_frame(yl - (P.m.cgv * c1 + P.m.cgu * c0), P.maxval) << P.shift;
-                    e[2] = quantize_frame(yl + P.m.cbu * c0, P.maxval) << P.shift;
-                    e[3] = P.alpha;
-                }
-#pragma unroll
-                for (int c = 0; c < CO; ++c) {
-                    const int i = p * CO + c;
-                    word[i / NE] |= e[c] << (BITS * (i % NE));
-                }
-            }
-            E* dst = oimg + pix * CO;
-            if (whole) {
-                store_words<CO>(dst, word);
-            } else {
-#pragma unroll
-                for (int i = 0; i < NPX * CO; ++i)
-                    if (i < valid * CO) dst[i] = static_cast<E>(frame_elem<E>(word, i));
-            }
+            for (int i = 0; i < NPX * CO; ++i)
+                if (i < valid * CO) dst[i] = static_cast<E>(frame_elem<E>(word, i));
         }
     }
 }
@@ -341,7 +256,7 @@ using namespace snnhip;
 extern "C" {
 
 int snnhip_rgb_fit_taps(int in, int out, int siting, float* weights, int* base, int capacity) {
-    return fill_rgb_fit_taps("rgb_fit_taps", in, out, siting, weights, base, capacity);
+    return fill_fit_taps(kRgbFitRule, "rgb_fit_taps", in, out, siting, weights, base, capacity);
 }
 
 int snnhip_rgb_fit_plan_create(snnhip_ctx* ctx, const snnhip_rgb_fit_desc* desc, snnhip_plan** out) {
@@ -369,32 +284,19 @@ int snnhip_rgb_fit_plan_create(snnhip_ctx* ctx, const snnhip_rgb_fit_desc* desc,
     }
     SNNHIP_REQUIRE(matrix_ok(desc->kr, desc->kb), "rgb_fit desc: kr = %g, kb = %g (0 < kr, 0 < kb, kr + kb < 1)", desc->kr, desc->kb);
     const RgbFitGeom g{bits / 8, d.source};
-    const int th = g.th(), tw = g.tw();
-    const int tilesX = up_div(d.OW, tw), tilesY = up_div(d.OH, th);
-    const double blocks = static_cast<double>(d.N) * tilesX * tilesY;
+    const FitTile tile = g.tile();
     const int sc = d.source == SNNHIP_RGB_FIT_RGB ? d.C : 2;
     const double srcElems = static_cast<double>(d.N) * d.H * d.W * sc;
     const double outPixels = static_cast<double>(d.N) * d.OH * d.OW;
-    SNNHIP_REQUIRE(blocks < 2147483648.0 && srcElems < 9.0e15 && outPixels * d.C < 9.0e15 && static_cast<double>(d.W) * sc < 1.0e9 &&
-                       static_cast<double>(d.OW) * kRgbFitTaps < 2.0e9 && static_cast<double>(d.OH) * kRgbFitTaps < 2.0e9 && 2.0 * d.N < 2147483648.0,
+    SNNHIP_REQUIRE(srcElems < 9.0e15 && outPixels * d.C < 9.0e15 && static_cast<double>(d.W) * sc < 1.0e9 && 2.0 * d.N < 2147483648.0,
                    "rgb_fit desc: %dx%dx%d -> %dx%d is too large", d.N, d.H, d.W, d.OH, d.OW);
-    std::vector<float> wy(static_cast<size_t>(d.OH) * kRgbFitTaps), wx(static_cast<size_t>(d.OW) * kRgbFitTaps);
-    std::vector<int> by(d.OH), bx(d.OW);
-    int rc = snnhip_rgb_fit_taps(d.H, d.OH, SNNHIP_SITING_CENTRE, wy.data(), by.data(), static_cast<int>(wy.size()));
-    if (rc == SNNHIP_OK) rc = snnhip_rgb_fit_taps(d.W, d.OW, d.siting, wx.data(), bx.data(), static_cast<int>(wx.size()));
+    FitAxes axes;
+    int rc = axes.build("rgb_fit", snnhip_rgb_fit_taps, kRgbFitTaps, g, d.N, d.H, d.W, d.OH, d.OW, d.siting);
     if (rc != SNNHIP_OK) return rc;
-    // what the kernel relies on: bases never step back and stay within one pixel of the source, and no tile's column span has more strips than its
-    // LDS rows hold
-    for (int x = 1; x < d.OW; ++x) SNNHIP_REQUIRE(bx[x] >= bx[x - 1], "rgb_fit: column bases step back at %d", x);
-    for (int y = 1; y < d.OH; ++y) SNNHIP_REQUIRE(by[y] >= by[y - 1], "rgb_fit: row bases step back at %d", y);
+    // what the kernel relies on beyond the core's checks: bases stay within one pixel of the source
+    const std::vector<int>&by = axes.by, &bx = axes.bx;
     SNNHIP_REQUIRE(bx[0] >= -1 && bx[d.OW - 1] < d.W && by[0] >= -1 && by[d.OH - 1] < d.H, "rgb_fit: bases %d..%d / %d..%d leave the %dx%d source", by[0], by[d.OH - 1], bx[0],
                    bx[d.OW - 1], d.H, d.W);
-    for (int tx = 0; tx < tilesX; ++tx) {
-        const int x0 = tx * tw, x1 = std::min(x0 + tw, d.OW) - 1;
-        const int px0 = (bx[x0] - 1) & ~(g.sp() - 1);
-        const int strips = (bx[x1] + 2 - px0) / g.sp() + 1;
-        SNNHIP_REQUIRE(strips <= g.maxStrips(), "rgb_fit: tile column %d spans %d strips, %d fit", tx, strips, g.maxStrips());
-    }
     auto* plan = new RgbFitPlan();
     plan->ctx = ctx;
     plan->numInputs = 2;
@@ -403,34 +305,16 @@ int snnhip_rgb_fit_plan_create(snnhip_ctx* ctx, const snnhip_rgb_fit_desc* desc,
     plan->rawOutput = d.dtype;
     plan->d = d;
     plan->P = RgbFitParams{};
-    plan->P.N = d.N;
-    plan->P.H = d.H;
-    plan->P.W = d.W;
-    plan->P.OH = d.OH;
-    plan->P.OW = d.OW;
-    plan->P.tilesX = tilesX;
-    plan->P.tilesY = tilesY;
-    plan->P.shift = d.shift;
-    plan->P.maxval = static_cast<float>(d.maxval);
+    rc = axes.upload(plan, &plan->P, d.shift, d.maxval);
+    if (rc != SNNHIP_OK) {
+        delete plan;
+        return rc;
+    }
     plan->P.alpha = static_cast<unsigned>(d.maxval) << d.shift;
     if (video) plan->P.m = yuv_rgb_coeffs(d.maxval, d.range, d.kr, d.kb);
     plan->P.kr = d.kr;
     plan->P.kg = static_cast<float>(1.0 - static_cast<double>(d.kr) - static_cast<double>(d.kb)); // as rgb_luma and ycc_merge form it
     plan->P.kb = d.kb;
-    float *dwy = nullptr, *dwx = nullptr, *dby = nullptr, *dbx = nullptr;
-    rc = plan->upload(wy.data(), wy.size(), &dwy);
-    if (rc == SNNHIP_OK) rc = plan->upload(wx.data(), wx.size(), &dwx);
-    if (rc == SNNHIP_OK) rc = plan->upload(reinterpret_cast<const float*>(by.data()), by.size(), &dby); // (a copy of bytes: ints are as wide as floats)
-    if (rc == SNNHIP_OK) rc = plan->upload(reinterpret_cast<const float*>(bx.data()), bx.size(), &dbx);
-    if (rc != SNNHIP_OK) {
-        delete plan;
-        return rc;
-    }
-    static_assert(sizeof(int) == sizeof(float), "the base tables travel through upload()");
-    plan->P.wy = dwy;
-    plan->P.wx = dwx;
-    plan->P.by = reinterpret_cast<const int*>(dby);
-    plan->P.bx = reinterpret_cast<const int*>(dbx);
     plan->inDims[0] = plan->outDims[0] = d.N;
     plan->inDims[1] = plan->outDims[1] = d.OH;
     plan->inDims[2] = plan->outDims[2] = d.OW;
@@ -441,8 +325,8 @@ int snnhip_rgb_fit_plan_create(snnhip_ctx* ctx, const snnhip_rgb_fit_desc* desc,
     plan->flops = 2.0 * 2.0 * kRgbFitTaps * (outPixels + static_cast<double>(d.N) * d.OH * d.W) + 12.0 * outPixels;
     char buf[320];
     snprintf(buf, sizeof(buf), "rgb_fit_u%d src=%s c=%d %dx%d->%dx%d siting=%s range=%s tile=%dx%d taps=%d lds=%d maxval=%d shift=%d kr=%g kb=%g kernel=rgb_fit_kernel", bits,
-             source_name(d.source), d.C, d.H, d.W, d.OH, d.OW, d.siting == SNNHIP_SITING_LEFT ? "left" : "centre", d.range == SNNHIP_RANGE_LIMITED ? "limited" : "full", th, tw,
-             kRgbFitTaps, static_cast<int>(kFitLdsFloats * sizeof(float)), d.maxval, d.shift, d.kr, d.kb);
+             source_name(d.source), d.C, d.H, d.W, d.OH, d.OW, d.siting == SNNHIP_SITING_LEFT ? "left" : "centre", d.range == SNNHIP_RANGE_LIMITED ? "limited" : "full", tile.th(),
+             tile.tw, kRgbFitTaps, static_cast<int>(kFitLdsFloats * sizeof(float)), d.maxval, d.shift, d.kr, d.kb);
     plan->desc = buf;
     *out = plan;
     return SNNHIP_OK;

@@ -180,3 +180,26 @@ def test_reference_in_float32_stays_within_a_sixth_of_eps(depth):
             worst = max(worst, float(d.max()))
     print("fit reference, maxval %d: float32 to float64 distance %.2e, eps %.0e" % (maxval, worst, R.EPS[maxval]))
     assert worst <= R.EPS[maxval] / 6
+
+
+def lane_set_frames(th):
+    """The frames of tests/test_frame_fit_gpu.py::test_rows_dealt_to_lane_sets_meet_at_the_chunk_boundaries as (u, OH, OW), for a tile of `th` rows:
+    U8, C = 1, 11 rows enlarged to th - 1 and th + 1 (a tile one row short; a full tile and a tile of one row), 20 -> 30 and 200 -> 300 columns.  An
+    enlarged tile's column span has fewer than 128 dword strips, so pass 1 deals the tile's rows to two or more lane sets: 30 columns take 7 strips
+    and 36 sets, more sets than rows, chunks of one row; the 256 columns of a full tile at 3/2 take 44 strips and 5 sets, the last chunk short."""
+    assert 11 <= th - 1 and th + 1 <= 4 * 11, th
+    frames = []
+    for k, (w, ow) in enumerate([(20, 30), (200, 300)]):
+        for j, oh in enumerate((th - 1, th + 1)):
+            u = np.random.default_rng(900 + 2 * k + j).integers(0, 256, size=(1, 11, w, 1)).astype(np.uint8)
+            frames.append((u, oh, ow))
+    return frames
+
+
+@pytest.mark.parametrize("th", range(12, 33))
+def test_near_ties_of_the_lane_set_frames_stay_under_the_cap(th):
+    """The GPU test reads the tile height from the plan; the kernel's tiles have at most 32 rows and these frames need at least 12.  On the reference
+    alone, for every height the frames can take."""
+    values = [R.fit_values(u, oh, ow, "left") for u, oh, ow in lane_set_frames(th)]
+    ties = sum(int(R.near_tie(v, R.EPS[255]).sum()) for v in values)
+    assert ties <= R.MAX_TIE_FRACTION * sum(v.size for v in values)

@@ -190,3 +190,18 @@ def test_the_plan_is_clean_under_the_guard(ctx):
     env = dict(os.environ, SNNHIP_GUARD="1", PYTHONPATH=ROOT + os.pathsep + os.path.join(ROOT, "tests"))
     r = subprocess.run([sys.executable, "-c", textwrap.dedent(code)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0 and "GUARD-OK" in r.stdout, r.stdout[-3000:]
+
+
+def test_rows_dealt_to_lane_sets_meet_at_the_chunk_boundaries(ctx):
+    """Pass 1 deals a tile's rows to lane sets when the tile's column span has fewer strips than the block has lanes: sets >= 2, chunks of
+    ceil(rows / sets).  One row less and one row more than a tile of an enlarging plan (tests/test_frame_fit.py::lane_set_frames, whose near ties are
+    counted there): chunks of one row with sets to spare, a short last chunk, a second tile of a single row."""
+    from shadernn_amd import capi
+    from test_frame_fit import lane_set_frames
+
+    probe = capi.plane_fit_plan(ctx, 1, 11, 20, 1, 12, 30, capi.U8, 255, 0, "left")  # enlarging: the four-tap instance
+    th, _ = tile_of(probe)
+    probe.destroy()
+    items = [(run_plan(ctx, u, oh, ow, "u8", 255, 0, "left"), R.fit_values(u, oh, ow, "left"), 255, 0) for u, oh, ow in lane_set_frames(th)]
+    frac, ndiff = R.compare_all(items)
+    print("plane_fit lane sets, tile of %d rows, %d runs: near ties %.3f %%, %d values differ" % (th, len(items), 100 * frac, ndiff))

@@ -213,6 +213,25 @@ def test_reference_in_float32_stays_within_a_quarter_of_eps(case):
         assert clamps <= R.MAX_CLAMP_FRACTION
 
 
+def lane_set_frames(th):
+    """The frames of tests/test_frame_rgb_fit_gpu.py::test_rows_dealt_to_lane_sets_meet_at_the_chunk_boundaries as (yfit, cbcr), for a tile of `th`
+    rows: the CbCr source, U8, 11 rows enlarged to th - 1 and th + 1 (a tile one row short; a full tile and a tile of one row), 20 -> 30 and
+    200 -> 300 columns.  An enlarged tile's column span has fewer than 128 strips, so pass 1 deals the tile's rows to two or more lane sets: 30
+    columns take 12 strips and 21 sets, chunks of one or two rows; the 256 columns of a full tile at 3/2 take 88 strips and 2 sets."""
+    assert 11 <= th - 1 and th + 1 <= 8 * 11, th
+    return [R.video_frame(1, 11, w, oh, ow, 255, 0, np.uint8, seed=900 + 2 * k + j) for k, (w, ow) in enumerate([(20, 30), (200, 300)])
+            for j, oh in enumerate((th - 1, th + 1))]
+
+
+@pytest.mark.parametrize("th", range(12, 33))
+def test_near_ties_of_the_lane_set_frames_stay_under_the_cap(th):
+    """The GPU test reads the tile height from the plan; the kernel's tiles have at most 32 rows and these frames need at least 12.  On the reference
+    alone, for every height the frames can take."""
+    values = [R.video_values(yfit, cbcr) for yfit, cbcr in lane_set_frames(th)]
+    ties = sum(int(R.near_tie(v, R.EPS[255]).sum()) for v in values)
+    assert ties <= R.MAX_TIE_FRACTION["video"] * sum(v.size for v in values)
+
+
 # ---- the host mirror: snn_model_create13 and its resolver, device-free
 
 W, H = 32, 24

@@ -100,6 +100,21 @@ def test_rgb_plan_matches_the_reference(ctx, c):
     print(rgb_sweep(ctx, c, shapes_for(ctx, "rgb", c, "u8", 255, 0)))
 
 
+def test_rows_dealt_to_lane_sets_meet_at_the_chunk_boundaries(ctx):
+    """Pass 1 deals a tile's rows to lane sets when the tile's column span has fewer strips than the block has lanes: sets >= 2, chunks of
+    ceil(rows / sets).  One row less and one row more than a tile (tests/test_frame_rgb_fit.py::lane_set_frames, whose near ties are counted
+    there): chunks of one and two rows, two sets with a short second chunk, a second tile of a single row."""
+    from shadernn_amd import capi
+    from test_frame_rgb_fit import lane_set_frames
+
+    probe = capi.rgb_fit_plan(ctx, 1, 11, 20, 12, 30, 3, "cbcr", capi.U8, 255, 0)
+    th, _ = tile_of(probe)
+    probe.destroy()
+    items = [(run_plan(ctx, yfit, cbcr, "cbcr", 3), R.video_values(yfit, cbcr), 255, 0) for yfit, cbcr in lane_set_frames(th)]
+    frac, ndiff = R.compare_all(items, "video")
+    print("rgb_fit lane sets, tile of %d rows, %d runs: near ties %.3f %%, %d values differ" % (th, len(items), 100 * frac, ndiff))
+
+
 def test_odd_widths_unaligned_rows_and_ratio_eight(ctx):
     """Odd OW: the RGB8 pitch 3 OW and the 8-bit Yfit pitch are no multiples of 4, so rows start off a dword; an odd source width does the same to the
     source rows of every layout.  Ratio 8 on both axes is the far end of the range."""
