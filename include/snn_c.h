@@ -237,6 +237,38 @@ typedef struct snn_rgb_fit_io {
 } snn_rgb_fit_io;     /* 10 * 4 bytes */
 int snn_model_create13(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_rgb_fit_io* io, snn_model** out);
+/* Video frames in front of an RGB(A) model: a decoder's NV12 / P010 / I420 / I010 frame of ANY even size goes straight to the model's normalised input
+ * tensor -- ResNet-18, MobileNetV2, YOLOv3-tiny, Candy -- in ONE launch in front of the model's own (include/snnhip.h, snnhip_yuv_tensor_plan_create,
+ * states the arithmetic: yuv_rgb's unrounded RGB value per source pixel, resize's sampling rule, (sample - mean) * norm).  Through a struct and an
+ * entry point of their own: every earlier struct and entry point keeps its layout, behaviour and refusals.  Here in_w, in_h and in_c are the MODEL's
+ * input extent and channels, in_c = 3 (R, G, B) or 4 (+ alpha); src_w x src_h is the frame's.  The model is built exactly as snn_model_create4 builds
+ * it, or, with an 8-bit out_format, as snn_model_create5 builds it with in_format = SNN_IO_FLOAT and that out_format, out_scale and out_offset (Candy:
+ * video in, RGB8 out).  The launch, "[yuv tensor]" in snn_model_describe, runs on the model's stream from the frame's device planes into the model's
+ * own input tensor, sits inside the recorded graph with capture_graph and counts towards SNN_GRAPH_MIN_LAUNCHES; prefer_half models get its fp16
+ * instance.  The plane tensors and the input tensor are allocated once: a recorded graph replays across uploads.  snn_model_upload_frame_nv12 takes
+ * dense frames (src_h * src_w luma elements, then (src_h / 2) * src_w interleaved chroma elements), snn_model_upload_frame_planes pitched planes
+ * (n_planes = 2, or 3 for the planar formats); snn_model_upload_input and snn_model_upload_input_u8 return -1 on such a model;
+ * snn_model_download_input returns the tensor the launch wrote; the downloads are the model's usual ones.  Returns -1, before anything is built on
+ * the device, for a null struct, an in_format that is none of the four, an out_format that is neither SNN_IO_FLOAT nor an 8-bit format, in_c outside
+ * {3, 4}, an odd or non-positive src_w / src_h, in_w or in_h below 1, batch below 1, an unknown filter, siting or range, kr / kb outside 0 < kr,
+ * 0 < kb, kr + kb < 1, maxval + 1 not a multiple of 256, maxval above 255 (8-bit) / 4095 (16-bit) and a maxval << shift that does not fit the
+ * container.  Not offered: anti-aliased shrinking (the sampler is the reference's plain bilinear resize), letterboxing and crop rectangles,
+ * 4:2:2 / 4:4:4, BGR order, and video in front of the luma-only model paths, which have their own entry points above. */
+enum { SNN_FILTER_NEAREST = 0, SNN_FILTER_LINEAR = 1 };
+typedef struct snn_video_tensor_io {
+    int in_format;    /* SNN_IO_NV12, SNN_IO_NV12_16, SNN_IO_I420 or SNN_IO_I420_16 */
+    int out_format;   /* SNN_IO_FLOAT, or an 8-bit format of the model output's own channel count */
+    int src_w, src_h; /* the frame's luma extent, both even */
+    int maxval, shift, siting, range; /* as snn_video_rgb_io */
+    float kr, kb;
+    int filter;       /* SNN_FILTER_NEAREST or SNN_FILTER_LINEAR */
+    float means[4], norms[4]; /* t = (sample - means[c]) * norms[c]; three are used */
+    float alpha;      /* channel 3 of a 4-channel input */
+    float out_scale[4], out_offset[4]; /* an 8-bit out_format: as snn_frame_io */
+} snn_video_tensor_io; /* 28 * 4 bytes */
+int snn_model_create14(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_video_tensor_io* io, snn_model** out);
+int snn_model_download_input(snn_model* m, float* nhwc); /* the model's input tensor, [batch x] H x W x C floats (what [yuv tensor] wrote, or the last upload) */
 /* Frames as plane pointers with row pitches (ffmpeg's data[] / linesize[]).  `planes` holds batch * n_planes pointers, frame by frame, in the order
  * Y, Cb, Cr (a YV12 caller swaps the last two) for a planar end, n_planes = 3; Y, CbCr for the NV12 / P010 ends of models made by snn_model_create8
  * / 9 / 10 / 11, n_planes = 2 (pitched NV12 surfaces).  pitch_bytes[n_planes] is the row pitch of each plane, the same for every frame.  Planes that
@@ -347,7 +379,7 @@ int snn_yolo_decode(const float* head_coarse, const float* head_fine, int net_si
  * Test hook for the loader's number grammar (overflow saturates to +-HUGE_VAL, underflow gives +-0 / a denormal, like the reference's strtod). */
 int snn_json_number(const char* text, double* out);
 
-/* Host-only: what snn_model_create<entry> (entry = 5..12, `io` that entry point's struct or NULL) resolves its struct to for an in_w x in_h x in_c
+/* Host-only: what snn_model_create<entry> (entry = 5..14, `io` that entry point's struct or NULL) resolves its struct to for an in_w x in_h x in_c
  * input and `batch` images, before any model file is opened: -1 where the entry point refuses the request, otherwise 0 and one canonical text line in
  * buf, "<the model's own end formats and maps> | <the frames the caller uploads and gets back, and their parameters> | entry=<name>".  Test hook for
  * the "built exactly as" statements above: two requests that name the same model resolve to the same first part (shadernn_amd/host/snn/frames.h). */

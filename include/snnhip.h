@@ -629,6 +629,50 @@ int snnhip_rgb_fit_plan_create(snnhip_ctx* ctx, const snnhip_rgb_fit_desc* desc,
  * SNNHIP_E_INVALID with a message for a ratio outside [1, 8], a null pointer, too little room and an unknown siting. */
 int snnhip_rgb_fit_taps(int in, int out, int siting, float* weights, int* base, int capacity);
 
+/* A 4:2:0 video frame in front of an RGB(A) model: the decoder's planes in, the model's NORMALISED INPUT TENSOR at the model's input size out, in one
+ * launch -- what lets a classifier, a detector or a style network take NV12 / P010 / I420 / I010 without a CPU conversion.  No RGB frame and no
+ * full-resolution float frame exists anywhere (the composition it replaces is yuv_rgb at r = 1, image_u8, resize: three launches, an 8-bit rounding
+ * in the middle, 8-bit video only).  DESIGN.md section 4.26.  The contract, stated once:
+ *   Shapes: inputs[0] = the luma plane [N][H][W][1]; inputs[1] = the chroma, interleaved CbCr [N][H/2][W/2][2] (snnhip_yuv_tensor_plan_create) or
+ *     planar [2N][H/2][W/2][1], plane 2n = Cb and 2n + 1 = Cr of image n (snnhip_yuv_tensor_planar_plan_create, the same desc); both of `src_dtype`,
+ *     SNNHIP_U8 or SNNHIP_U16; H and W even.  Output [N][OH][OW][C] of `out_dtype`, SNNHIP_F32 or SNNHIP_F16, C = 3 (R, G, B) or 4 (R, G, B, alpha).
+ *     Run with snnhip_plan_run_n, 2 inputs.  Values are float(u >> shift); maxval, shift, siting, range, kr, kb mean what they mean for yuv_rgb.
+ *   Source pixel: at luma pixel (Y, X), v_c(Y, X) is yuv_rgb's expression at r = 1 for channel c -- snnhip_bicubic_taps_420(1, siting) along a row,
+ *     (1, centre) along a column, what is filtered is the sample minus Coff, horizontal then vertical, the five coefficients of
+ *     snnhip_yuv_rgb_coefficients, yl = cy (Y - Yoff), R = yl + crv Cr~, G = yl - (cgv Cr~ + cgu Cb~), B = yl + cbu Cb~, fp32 throughout -- NOT
+ *     rounded, and clamped to [0, maxval] as a float.
+ *   Sampling: output coordinate o of an axis with `in` source and `out` output samples sits at source position u = (o + 1/2) in / out - 1/2 (resize's
+ *     rule; in integers u = ((2o + 1) in - out) / (2 out)).  The positions come from snnhip_yuv_tensor_taps, computed on the host; the kernel does no
+ *     position arithmetic.  SNNHIP_YUV_TENSOR_LINEAR: i0 = floor(u), a = the exact fraction u - i0 rounded to double and then to float, source indices
+ *     i0 and i0 + 1 clamped to [0, in - 1]; sample_c = top (1 - ay) + bot ay with top = v_c(y0, x0) (1 - ax) + v_c(y0, x1) ax and bot likewise on
+ *     row y1, in fp32 (horizontal first, resize's form); two indices that clamp to the same source pixel read the same value.
+ *     SNNHIP_YUV_TENSOR_NEAREST: the source pixel floor(((2o + 1) in) / (2 out)) on each axis.  Nothing is low-passed: shrinking aliases as the
+ *     reference's bilinear resize does.
+ *   Output: t[n][oy][ox][c] = (sample_c - means[c]) * norms[c] for c < 3, t[..][3] = alpha for C = 4; stored as fp32, or rounded to nearest even
+ *     as fp16.
+ *   Consequences: at OH = H, OW = W every a is 0 and t is the source pixel itself; with means 0 and norms 1, rint(t) is yuv_rgb's value at r = 1
+ *     wherever the value is not within yuv_rgb's near-tie eps of a rounding tie.  Neutral chroma gives R = G = B exactly.  In fp32 a value stays within
+ *     3.9e-5 / 1.8e-4 / 5.9e-4 (8 / 10 / 12 bits, per unit of |norm|; measured, tests/yuv_tensor_ref.py) of a float64 evaluation; the tests hold
+ *     every output element to |norms[c]| E, E = four times that: 1.56e-4 / 7.2e-4 / 2.36e-3, plus half an fp16 ulp for fp16 output.
+ * Plan creation returns SNNHIP_E_INVALID with a message starting "yuv_tensor desc" for everything yuv_rgb refuses (dtype, maxval, shift, maxval + 1
+ * not a multiple of 256, siting, range, kr / kb), bad dims, an odd H or W, OH or OW below 1, C outside {3, 4}, an unknown filter and an out_dtype that
+ * is neither SNNHIP_F32 nor SNNHIP_F16.  snnhip_plan_run_n refuses, with a message starting "yuv_tensor" / "yuv_tensor_planar", a tensor of another
+ * dtype or shape at any position.  snnhip_plan_describe: "yuv_tensor_u8 c=4 f32 linear siting=left range=limited 1080x1920->224x224 tile=256
+ * taps=bilinear ... kernel=yuv_tensor_kernel" (the tile in flat output pixels per block; taps=single when one source pixel serves an output pixel:
+ * nearest, or linear tables whose weights are all 0, ratio 1 among them).  snnhip_plan_cost counts both inputs once and the output once.
+ * Not offered: anti-aliased shrinking (the reference's resize is a plain bilinear sampler, and plane_fit's stretched cubic stops at 1/2);
+ * letterboxing and crop rectangles; 4:2:2 / 4:4:4; BGR order; video in front of the luma-only model paths, which have their own plans above. */
+#define SNNHIP_YUV_TENSOR_NEAREST 0
+#define SNNHIP_YUV_TENSOR_LINEAR 1
+typedef struct { int N, H, W; int OH, OW, C; int src_dtype, out_dtype; int maxval, shift; int siting, range; float kr, kb; int filter; float means[3], norms[3]; float alpha; } snnhip_yuv_tensor_desc; /* H, W: the LUMA plane */
+int snnhip_yuv_tensor_plan_create(snnhip_ctx* ctx, const snnhip_yuv_tensor_desc* desc, snnhip_plan** out);        /* run with snnhip_plan_run_n, 2 inputs */
+int snnhip_yuv_tensor_planar_plan_create(snnhip_ctx* ctx, const snnhip_yuv_tensor_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_n, 2 inputs */
+/* host only, no context: the table of one axis with `in` source samples and `out` outputs: weight [out] floats (a; 0 for nearest) and index [out][2]
+ * ints (i0 and i0 + 1 clamped to the axis; nearest: the source index twice); `capacity` is the room in coordinates (weight holds that many floats,
+ * index twice as many ints).  The plan builds its two tables with this function and keeps them in device memory.  SNNHIP_E_INVALID with a message
+ * for a null pointer, in or out outside 1 .. 2^30, an unknown filter and too little room. */
+int snnhip_yuv_tensor_taps(int in, int out, int filter, float* weight, int* index, int capacity);
+
 /* Frame quality on the device: PSNR and SSIM between a test frame and a reference frame, so that what an arithmetic choice (fused fp32, the fp16
  * opt-in, 8 / 10 / 12-bit frame ends) or a trained model costs in picture quality can be stated in dB without downloading every output frame.
  * DESIGN.md section 4.22.  The reference ships a host-side comparison script only (tools/misc/imageComparison.py).  The definition, stated once

@@ -122,6 +122,12 @@ class PlaneFitDesc(C.Structure):
                 ("siting", C.c_int)]
 
 
+class YuvTensorDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("OH", C.c_int), ("OW", C.c_int), ("C", C.c_int), ("src_dtype", C.c_int), ("out_dtype", C.c_int), ("maxval", C.c_int),
+                ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float), ("filter", C.c_int), ("means", C.c_float * 3),
+                ("norms", C.c_float * 3), ("alpha", C.c_float)]
+
+
 class RgbFitDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("OH", C.c_int), ("OW", C.c_int), ("C", C.c_int), ("source", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int),
                 ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
@@ -226,6 +232,9 @@ SIGNATURES = {
     "snnhip_fit_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_rgb_fit_plan_create": (C.c_int, [_P, C.POINTER(RgbFitDesc), C.POINTER(_P)]),
     "snnhip_rgb_fit_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
+    "snnhip_yuv_tensor_plan_create": (C.c_int, [_P, C.POINTER(YuvTensorDesc), C.POINTER(_P)]),
+    "snnhip_yuv_tensor_planar_plan_create": (C.c_int, [_P, C.POINTER(YuvTensorDesc), C.POINTER(_P)]),
+    "snnhip_yuv_tensor_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
     "snnhip_frame_metrics_plan_create": (C.c_int, [_P, C.POINTER(FrameMetricsDesc), C.POINTER(_P)]),
     "snnhip_frame_metrics_read": (C.c_int, [_P, C.POINTER(FrameMetricsRow), C.c_int]),
     "snnhip_frame_metrics_psnr": (C.c_double, [C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -903,6 +912,34 @@ def fit_taps(n_in, n_out, siting="centre", capacity=None):
     base = (C.c_int * max(n, 1))()
     check(lib().snnhip_fit_taps(n_in, n_out, SITING.get(siting, siting), _fptr(w), base, w.size if capacity is None else capacity))
     return w, np.array(base[:n], np.int32)
+
+
+YUV_TENSOR_FILTER = {"nearest": 0, "linear": 1}  # SNNHIP_YUV_TENSOR_*
+
+
+def yuv_tensor_plan(ctx, N, H, W, OH, OW, Cc, src_dtype=U8, out_dtype=F32, maxval=None, shift=0, siting="left", range="limited", kr=BT601[0], kb=BT601[1], filter="linear",
+                    means=(0, 0, 0), norms=(1, 1, 1), alpha=1.0, planar=False):
+    """plan.run([Y [N][H][W][1], chroma], out [N][OH][OW][Cc]): a 4:2:0 video frame (U8 / U16 planes, H and W even) straight to the normalised fp32 /
+    fp16 input tensor of an RGB (Cc = 3) or RGBA (Cc = 4) model at the model's input size, in one launch (include/snnhip.h states the arithmetic).
+    The chroma is interleaved CbCr [N][H/2][W/2][2], or with planar=True [2N][H/2][W/2][1] (plane 2n = Cb, 2n + 1 = Cr).  H, W are the LUMA
+    plane's; maxval defaults to 255 (a 16-bit frame must say)."""
+    if maxval is None:
+        maxval = 255
+    d = YuvTensorDesc(N, H, W, OH, OW, Cc, src_dtype, out_dtype, maxval, shift, SITING.get(siting, siting), RANGE.get(range, range), kr, kb, YUV_TENSOR_FILTER.get(filter, filter),
+                      (C.c_float * 3)(*means[:3]), (C.c_float * 3)(*norms[:3]), alpha)
+    h = _P()
+    check((lib().snnhip_yuv_tensor_planar_plan_create if planar else lib().snnhip_yuv_tensor_plan_create)(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def yuv_tensor_taps(n_in, n_out, filter="linear", capacity=None):
+    """snnhip_yuv_tensor_taps (host side only, no GPU): (a float32 [n_out], index int32 [n_out][2]) of one axis: output o blends source samples
+    index[o][0] and index[o][1] (already clamped) with weights 1 - a[o] and a[o]; nearest: the source index twice and a = 0."""
+    n = max(int(n_out), 0)
+    a = np.zeros(max(n, 1), np.float32)
+    idx = (C.c_int * (2 * max(n, 1)))()
+    check(lib().snnhip_yuv_tensor_taps(n_in, n_out, YUV_TENSOR_FILTER.get(filter, filter), _fptr(a), idx, n if capacity is None else capacity))
+    return a[:n], np.array(idx[:2 * n], np.int32).reshape(n, 2)
 
 
 RGB_FIT_SOURCE = {"cbcr": 0, "planar": 1, "rgb": 2}  # SNNHIP_RGB_FIT_*

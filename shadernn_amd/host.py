@@ -26,6 +26,8 @@ SIGNATURES = {
     "snn_model_create11": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create12": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_model_create13": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_create14": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "snn_model_download_input": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "snn_model_upload_frame_planes": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     "snn_model_download_frame_planes": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     "snn_model_upload_frame_nv12": (C.c_int, [_P, _P]),
@@ -206,6 +208,14 @@ class RgbFitIO(C.Structure):
                 ("kr", C.c_float), ("kb", C.c_float), ("out_w", C.c_int), ("out_h", C.c_int)]
 
 
+class VideoTensorIO(C.Structure):
+    """snn_video_tensor_io (include/snn_c.h): a 4:2:0 video frame of src_w x src_h in front of an RGB(A) model, straight to its normalised input tensor."""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("src_w", C.c_int), ("src_h", C.c_int), ("maxval", C.c_int), ("shift", C.c_int), ("siting", C.c_int),
+                ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float), ("filter", C.c_int), ("means", C.c_float * 4), ("norms", C.c_float * 4), ("alpha", C.c_float),
+                ("out_scale", C.c_float * 4), ("out_offset", C.c_float * 4)]
+
+
+VIDEO_FILTERS = {"nearest": 0, "linear": 1}  # SNN_FILTER_*
 # name: (SNN_IO_NV12 / SNN_IO_NV12_16 / SNN_IO_I420 / SNN_IO_I420_16, maxval, shift); I010 is ffmpeg's yuv420p10le: 10 bits in the low end of 2 bytes
 VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6), "I420": (0x401, 255, 0), "I010": (0x501, 1023, 0)}
 PLANAR_FORMATS = ("I420", "I010")
@@ -221,7 +231,8 @@ class Model:
     def __init__(self, json_path, w, h, c, device=0, dump_outputs=False, fuse_chains=True, profiling=False, prefer_half=False, capture_graph=False,
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
                  out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114, video=None,
-                 siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited", out_size=None, rgb_size=None):
+                 siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited", out_size=None, rgb_size=None, frame_size=None,
+                 video_filter="linear", alpha=1.0):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
         output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
@@ -253,16 +264,46 @@ class Model:
         rgb_size (w, h) beside video and video_out "RGB8" / ... , or beside colour "RGB8" / "RGBA8" alone (snn_model_create13): the RGB frame comes
         back at that size (it need not be even), between half and all of r times the input on each axis and, with colour, no smaller than the
         input -- the model's luma frame resampled to the size, then RGB from it and the ORIGINAL chroma planes (or the colour frame that went in)
-        in one more launch; no r-fold chroma or RGB frame is formed.  With colour the luma maps are 0, 1 / 255, 255, 0 (in_means / ... are not used)."""
+        in one more launch; no r-fold chroma or RGB frame is formed.  With colour the luma maps are 0, 1 / 255, 255, 0 (in_means / ... are not used).
+        frame_size (src_w, src_h) beside video "NV12" / "P010" / "I420" / "I010" (snn_model_create14): video in front of an RGB(A) model -- w, h, c are
+        the MODEL's input, c = 3 or 4, and a frame of that (even) size goes straight to the model's normalised input tensor in one launch:
+        t = (sample - in_means[c]) * in_norms[c] with the sample in 0 .. maxval, channel 3 = alpha, video_filter "linear" / "nearest", siting,
+        video_range, kr, kb the stream's.  upload_frame / upload_planes take the planes at frame_size; upload() and upload_u8() are refused;
+        input_tensor() returns what the launch wrote.  output_format "RGB8" / ... (with out_scale / out_offset) makes the model's output an 8-bit
+        frame as snn_model_create5 does; otherwise output() returns floats."""
         self.h = _P()
         self.batch = batch
         self.video = video  # the upload end: None = one array (the model's frame or a colour frame), else planes of this format
         self.out_end = "frame"  # what comes back: "frame" = one array of out_channels (0: the model's own), "yuv" = luma + chroma planes
         self.out_channels = 0
         self.out_size = None
+        self.frame_hw = None  # the extent of the planes that go in, where it is not the model input's (frame_size)
         in_channels, u8 = c, (np.uint8, np.uint8)
+        if frame_size is not None:
+            assert video in VIDEO_FORMATS, "frame_size is the size of a video frame: it goes with video=\"NV12\" / \"P010\" / \"I420\" / \"I010\""
+            assert video_out is None and colour is None and out_size is None and rgb_size is None and input_format is None, \
+                "frame_size puts video in front of an RGB model: not beside video_out / colour / out_size / rgb_size / input_format"
+            assert output_format in (None, "float", "R8", "RGB8", "RGBA8"), "the model's output is float or an 8-bit frame"
+            assert c in (3, 4), "the model takes 3 (RGB) or 4 (RGB + alpha) input channels"
+            assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
+            assert siting in SITINGS, "siting is \"left\" or \"centre\""
+            assert video_filter in VIDEO_FILTERS, "video_filter is \"linear\" or \"nearest\""
+            assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
+            sw, sh = int(frame_size[0]), int(frame_size[1])
+            assert sw >= 2 and sh >= 2 and sw % 2 == 0 and sh % 2 == 0, "a 4:2:0 frame has an even extent"
+            fmt, maxval, shift = VIDEO_FORMATS[video]
+            maxval = maxval if video_maxval is None else video_maxval
+            shift = shift if video_shift is None else video_shift
+            self.frame_hw = (sh, sw)
+            self.frame_dtypes = (np.uint16 if fmt in (0x301, 0x501) else np.uint8, np.uint8)
+            maps = [(C.c_float * 4)(*(tuple(m) + (0,) * 4)[:4]) for m in (in_means, in_norms, out_scale, out_offset)]
+            tensor_io = VideoTensorIO(fmt, FRAME_FORMATS[output_format], sw, sh, maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, VIDEO_FILTERS[video_filter],
+                                      maps[0], maps[1], alpha, maps[2], maps[3])
+            video_out = colour = None
         assert out_size is None or (video is not None and video_out is None and colour is None), "out_size fits an NV12 / P010 frame: it goes with video= alone"
-        if rgb_size is not None:
+        if frame_size is not None:
+            entry, io = 14, tensor_io
+        elif rgb_size is not None:
             assert out_size is None and input_format is None and output_format is None, "rgb_size is the size of an RGB frame: not beside out_size / input_format / output_format"
             assert (video is not None and video_out in VIDEO_OUT_FORMATS and colour is None) or (colour in ("RGB8", "RGBA8") and video is None and video_out is None), \
                 "rgb_size goes with video= and video_out=\"RGB8\" / \"RGBA8\" / \"RGB16\" / \"RGBA16\", or with colour=\"RGB8\" / \"RGBA8\" alone"
@@ -342,7 +383,7 @@ class Model:
                 entry, io = 6, FrameIO2(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps, frame_in_shift, frame_out_maxval, frame_out_shift)
             else:
                 entry, io = 5, FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps)
-        self.planar = entry == 12 or (entry == 13 and video in PLANAR_FORMATS)
+        self.planar = entry == 12 or (entry in (13, 14) and video in PLANAR_FORMATS)
         self.in_shape = (h, w, in_channels) if batch == 1 else (batch, h, w, in_channels)
         create = getattr(lib(), "snn_model_create%d" % entry)
         assert create(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph), int(batch),
@@ -379,7 +420,7 @@ class Model:
     def _upload_video(self, y, cbcr):
         """(y, cbcr) -> `batch` frames, each the luma plane followed by the interleaved chroma plane, the layout snn_model_upload_frame_nv12 takes"""
         dt, n = self.frame_dtypes[0], self.batch
-        h, w = self.in_shape[-3], self.in_shape[-2]
+        h, w = self.frame_hw or (self.in_shape[-3], self.in_shape[-2])
         y = np.ascontiguousarray(y, dtype=dt).reshape(n, h * w)
         cbcr = np.ascontiguousarray(cbcr, dtype=dt).reshape(n, (h // 2) * w)
         frames = np.ascontiguousarray(np.concatenate([y, cbcr], axis=1))
@@ -424,7 +465,7 @@ class Model:
     def _upload_planar(self, y, cb, cr):
         """(y, cb, cr), [batch x] H x W and twice [batch x] H/2 x W/2 -> snn_model_upload_frame_planes with tight pitches"""
         dt, n = self.frame_dtypes[0], self.batch
-        h, w = self.in_shape[-3], self.in_shape[-2]
+        h, w = self.frame_hw or (self.in_shape[-3], self.in_shape[-2])
         y = np.ascontiguousarray(y, dtype=dt).reshape(n, h, w)
         cb = np.ascontiguousarray(cb, dtype=dt).reshape(n, h // 2, w // 2)
         cr = np.ascontiguousarray(cr, dtype=dt).reshape(n, h // 2, w // 2)
@@ -479,6 +520,13 @@ class Model:
         n = lib().snn_model_frame_metrics(self.h, rows, cap)
         assert n >= 0, "snn_model_frame_metrics refused: no reference set, or the output is a float tensor (see the log)"
         return [{f: getattr(r, f) for f, _ in FrameMetrics._fields_} for r in rows[:n]]
+
+    def input_tensor(self):
+        """snn_model_download_input: the model's input tensor as float32 [batch x] H x W x C -- what the [yuv tensor] launch of a frame_size model wrote
+        in the last run, or the last upload()."""
+        out = np.empty(self.in_shape, np.float32)
+        assert lib().snn_model_download_input(self.h, _fp(out)) == 0
+        return out
 
     def upload(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.in_shape)

@@ -96,7 +96,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         if (cp.profiling) stage.timer.reset(backend->createDeviceTimer(layer.name));
     }
     const int frameIn = cp.frames.model.in_format, frameOut = cp.frames.model.out_format; // SNN_IO_*: the low byte is the channel count
-    if (frameIn != SNN_IO_FLOAT || frameOut != SNN_IO_FLOAT) {
+    if (frameIn != SNN_IO_FLOAT || frameOut != SNN_IO_FLOAT || cp.frames.source == FrameSpec::Source::YUV420_TENSOR) {
         auto* hb = dynamic_cast<dp::HipBackend*>(backend);
         SNN_CHK(hb && stages.back().stageOutputs.size() > 0);
         const ImageTexture& o = stages.back().stageOutputs[0];

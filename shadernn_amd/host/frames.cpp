@@ -233,6 +233,42 @@ bool resolveFrames(const snn_rgb_fit_io* io, int in_w, int in_h, int in_c, int b
     return true;
 }
 
+// ---- snn_model_create14: a 4:2:0 frame of src_w x src_h in front of an RGB(A) model.  The model resolves as snn_model_create4's (float at both
+// ends), or through snn_model_create5's struct with a float input and the 8-bit out_format
+bool resolveFrames(const snn_video_tensor_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* s) {
+    if (!io || (in_c != 3 && in_c != 4)) return false;
+    const bool planar = io->in_format == SNN_IO_I420 || io->in_format == SNN_IO_I420_16, wide = io->in_format == SNN_IO_NV12_16 || io->in_format == SNN_IO_I420_16;
+    if (!planar && io->in_format != SNN_IO_NV12 && io->in_format != SNN_IO_NV12_16) return false;
+    if (!evenExtent(io->src_w, io->src_h) || (io->filter != SNN_FILTER_NEAREST && io->filter != SNN_FILTER_LINEAR)) return false;
+    if (!knownSiting(io->siting) || !knownRange(io->range) || !rangedDepth(io->maxval) || !knownMatrix(io->kr, io->kb)) return false;
+    if (io->maxval > 4095 || !fitsContainer(io->maxval, io->shift, wide)) return false; // (as snn_model_create8)
+    if (io->out_format == SNN_IO_FLOAT) {
+        if (!resolveFrames(static_cast<const snn_frame_io*>(nullptr), in_w, in_h, in_c, batch, s)) return false;
+    } else {
+        snn_frame_io f{SNN_IO_FLOAT, io->out_format, {0, 0, 0, 0}, {1, 1, 1, 1}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+        memcpy(f.out_scale, io->out_scale, sizeof(f.out_scale));
+        memcpy(f.out_offset, io->out_offset, sizeof(f.out_offset));
+        if (!resolveFrames(&f, in_w, in_h, in_c, batch, s)) return false;
+    }
+    s->source = Source::YUV420_TENSOR;
+    s->channels = in_c;
+    s->wide = wide;
+    s->maxval = io->maxval;
+    s->shift = io->shift;
+    s->siting = io->siting;
+    s->range = io->range;
+    s->kr = io->kr;
+    s->kb = io->kb;
+    s->planar = planar;
+    s->srcW = io->src_w;
+    s->srcH = io->src_h;
+    s->filter = io->filter;
+    for (int c = 0; c < 3; ++c) s->tensorMeans[c] = io->means[c], s->tensorNorms[c] = io->norms[c];
+    s->alpha = io->alpha;
+    s->entry = "snn_model_create14";
+    return true;
+}
+
 bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int batch, FrameSpec* s) {
     if (!s || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return false;
     *s = FrameSpec();
@@ -246,12 +282,14 @@ bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int 
     case 11: return resolveFrames(static_cast<const snn_fit_io*>(io), in_w, in_h, in_c, batch, s);
     case 12: return resolveFrames(static_cast<const snn_planar_io*>(io), in_w, in_h, in_c, batch, s);
     case 13: return resolveFrames(static_cast<const snn_rgb_fit_io*>(io), in_w, in_h, in_c, batch, s);
+    case 14: return resolveFrames(static_cast<const snn_video_tensor_io*>(io), in_w, in_h, in_c, batch, s);
     default: return false;
     }
 }
 
 bool framesFitModel(const FrameSpec& spec, int in_w, int in_h, const InferenceGraph::IODesc& out) {
     if (spec.source == Source::MODEL && spec.sink == Sink::MODEL) return true;
+    if (spec.source == Source::YUV420_TENSOR) return true; // any model of 3 or 4 input channels: the frame ends in its input tensor
     // the model must be luma-only: one channel out, at 1..4 times the input's extent
     const uint32_t w = static_cast<uint32_t>(in_w), h = static_cast<uint32_t>(in_h), r = out.width / w;
     if (out.channels != 1 || r < 1 || r > 4 || out.width != r * w || out.height != r * h) return false;
@@ -278,17 +316,23 @@ bool framesFitModel(const FrameSpec& spec, int in_w, int in_h, const InferenceGr
 }
 
 std::string formatFrameSpec(const FrameSpec& s) {
-    static const char* const sources[] = {"model", "rgb", "yuv420"};
+    static const char* const sources[] = {"model", "rgb", "yuv420", "yuv420_tensor"};
     static const char* const sinks[] = {"model", "rgb_merged", "chroma_up", "fitted", "rgb_from_yuv", "yuv420_from_rgb", "rgb_from_yuv_fitted", "rgb_merged_fitted"};
-    static_assert(sizeof(sources) / sizeof(*sources) == static_cast<size_t>(Source::YUV420) + 1, "one name for every FrameSpec::Source");
+    static_assert(sizeof(sources) / sizeof(*sources) == static_cast<size_t>(Source::YUV420_TENSOR) + 1, "one name for every FrameSpec::Source");
     static_assert(sizeof(sinks) / sizeof(*sinks) == static_cast<size_t>(Sink::RGB_MERGED_FITTED) + 1, "one name for every FrameSpec::Sink");
     const snn_frame_io2& m = s.model;
     auto four = [](const float* v) { return formatString("%.9g,%.9g,%.9g,%.9g", v[0], v[1], v[2], v[3]); };
+    // (the lines of snn_model_create5..13 stay as they were: what only snn_model_create14 sets is appended to its own line alone)
+    const std::string tensor = s.source != Source::YUV420_TENSOR
+                                   ? std::string()
+                                   : formatString(" | src=%dx%d filter=%d tensor_means=%.9g,%.9g,%.9g tensor_norms=%.9g,%.9g,%.9g alpha=%.9g", s.srcW, s.srcH, s.filter, s.tensorMeans[0],
+                                                  s.tensorMeans[1], s.tensorMeans[2], s.tensorNorms[0], s.tensorNorms[1], s.tensorNorms[2], s.alpha);
     return formatString("in=0x%x out=0x%x means=%s norms=%s scale=%s offset=%s in_shift=%d out_maxval=%d out_shift=%d", m.in_format, m.out_format, four(m.in_means).c_str(),
                         four(m.in_norms).c_str(), four(m.out_scale).c_str(), four(m.out_offset).c_str(), m.in_shift, m.out_maxval, m.out_shift) +
            formatString(" | source=%s sink=%s channels=%d wide=%d maxval=%d shift=%d siting=%d range=%d kr=%.9g kb=%.9g fit=%dx%d planar=%d | entry=%s",
                         sources[static_cast<int>(s.source)], sinks[static_cast<int>(s.sink)], s.channels, s.wide ? 1 : 0, s.maxval, s.shift, s.siting, s.range, s.kr, s.kb,
-                        s.fitW, s.fitH, s.planar ? 1 : 0, s.entry);
+                        s.fitW, s.fitH, s.planar ? 1 : 0, s.entry) +
+           tensor;
 }
 
 } // namespace snn

@@ -105,6 +105,19 @@ void HipBackend::initFrames(const FrameSpec& f, int n, int inH, int inW, int inC
     uploadT = frameInT;
     downloadT = frameOutT;
     if (f.source == Source::MODEL && f.sink == Sink::MODEL) return;
+    if (f.source == Source::YUV420_TENSOR) { // a 4:2:0 frame of any even size straight into the model's own (float) input tensor: one launch in front
+        const int sd = f.wide ? SNNHIP_U16 : SNNHIP_U8;
+        planarChroma = f.planar;
+        uploadT = ownTensor(n, f.srcH, f.srcW, 1, sd, "snnhip_tensor_alloc (luma input plane)");
+        chromaInT = ownTensor(f.planar ? 2 * n : n, f.srcH / 2, f.srcW / 2, f.planar ? 1 : 2, sd, "snnhip_tensor_alloc (chroma input plane)");
+        snnhip_yuv_tensor_desc d{n, f.srcH, f.srcW, inH, inW, inC, sd, dtype, f.maxval, f.shift, f.siting, f.range, f.kr, f.kb, f.filter,
+                                 {f.tensorMeans[0], f.tensorMeans[1], f.tensorMeans[2]}, {f.tensorNorms[0], f.tensorNorms[1], f.tensorNorms[2]}, f.alpha};
+        snnhip_plan* p = nullptr;
+        if (f.planar) hipChk(snnhip_yuv_tensor_planar_plan_create(ctx, &d, &p), "snnhip_yuv_tensor_planar_plan_create");
+        else hipChk(snnhip_yuv_tensor_plan_create(ctx, &d, &p), "snnhip_yuv_tensor_plan_create");
+        stepsIn.push_back({p, uploadT, chromaInT, nullptr, "[yuv tensor]", "snnhip_plan_run_n (video frame -> input tensor)"}); // out: the model's input tensor, bound at run
+        return;
+    }
 
     // colour or video frames around a luma-only model: the luma plane IS the model's frame at a video end
     const int vd = f.wide ? SNNHIP_U16 : SNNHIP_U8;
@@ -193,15 +206,16 @@ std::string HipBackend::describeFrames() const {
     return s;
 }
 
-void HipBackend::runSteps(const std::vector<FrameStep>& steps) {
+void HipBackend::runSteps(const std::vector<FrameStep>& steps, snnhip_tensor* modelInput) {
     for (auto& s : steps) {
         const snnhip_tensor* ins[2] = {s.in0, s.in1};
-        hipChk(s.in1 ? snnhip_plan_run_n(s.plan, ins, 2, s.out) : snnhip_plan_run(s.plan, s.in0, s.out), s.what);
+        snnhip_tensor* out = s.out ? s.out : modelInput; // (a step without a tensor of its own writes the model's input tensor)
+        hipChk(s.in1 ? snnhip_plan_run_n(s.plan, ins, 2, out) : snnhip_plan_run(s.plan, s.in0, out), s.what);
     }
 }
 
 void HipBackend::runFrameIn(const ImageTexture& modelInput) {
-    runSteps(stepsIn);
+    runSteps(stepsIn, modelInput.tensor());
     if (frameInPlan && !frameInFused) hipChk(snnhip_plan_run(frameInPlan, frameInT, modelInput.tensor()), "snnhip_plan_run (frame in)");
 }
 

@@ -134,11 +134,11 @@ private:
     struct FrameStep {
         snnhip_plan* plan;
         const snnhip_tensor *in0, *in1;
-        snnhip_tensor* out;
+        snnhip_tensor* out; // (null: the model's own input tensor, known when the inference runs)
         const char *label, *what; // the bracketed name of describe(); what a failed launch is reported as
     };
     snnhip_tensor* ownTensor(int n, int h, int w, int c, int dtype, const char* what);
-    static void runSteps(const std::vector<FrameStep>& steps);
+    static void runSteps(const std::vector<FrameStep>& steps, snnhip_tensor* modelInput = nullptr);
     snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned: the model's own conversions, nodes of the fusion graph (finalizeStages)
     snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // the model's own frames, SNNHIP_U8 or SNNHIP_U16
     bool frameInFused = false, frameOutFused = false;

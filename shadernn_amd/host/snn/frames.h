@@ -1,5 +1,5 @@
 // snn/frames.h -- the resolved description of a model's frame ends (HIP extension; device-free: nothing here touches the GPU).  Every
-// snn_model_create5..13 struct of include/snn_c.h resolves to ONE FrameSpec, and everything below the entry points -- createModel,
+// snn_model_create5..14 struct of include/snn_c.h resolves to ONE FrameSpec, and everything below the entry points -- createModel,
 // MixedInferenceCore::CreationParameters, HipBackend::initFrames -- takes that one description.
 #pragma once
 #include <string>
@@ -12,7 +12,9 @@ namespace snn {
 struct FrameSpec {
     // the model's own end formats and maps: SNN_IO_FLOAT, or the 8- / 16-bit frame whose conversion joins the fusion graph (ESPCN folds it into its kernels)
     snn_frame_io2 model{SNN_IO_FLOAT, SNN_IO_FLOAT, {0, 0, 0, 0}, {1, 1, 1, 1}, {1, 1, 1, 1}, {0, 0, 0, 0}, 0, 65535, 0};
-    enum class Source { MODEL, RGB, YUV420 } source = Source::MODEL; // what the caller uploads: the model's frame, an RGB frame, luma + 4:2:0 chroma
+    // what the caller uploads: the model's frame, an RGB frame, luma + 4:2:0 chroma around a luma model, luma + 4:2:0 chroma of srcW x srcH in front of
+    // an RGB(A) model (one launch into the model's float input tensor: snn_model_create14)
+    enum class Source { MODEL, RGB, YUV420, YUV420_TENSOR } source = Source::MODEL;
     // what comes back: the model's frame, the merged RGB frame, luma + r-fold chroma, luma + chroma fitted to fitW x fitH, RGB from luma + chroma, luma + chroma from RGB,
     // and the two RGB frames at fitW x fitH: from luma + chroma, merged with the colour frame that went in
     enum class Sink { MODEL, RGB_MERGED, CHROMA_UP, FITTED, RGB_FROM_YUV, YUV420_FROM_RGB, RGB_FROM_YUV_FITTED, RGB_MERGED_FITTED } sink = Sink::MODEL;
@@ -23,6 +25,8 @@ struct FrameSpec {
     float kr = 0.299f, kb = 0.114f;                    // the matrix of the RGB end
     int fitW = 0, fitH = 0;                            // Sink::FITTED, Sink::RGB_FROM_YUV_FITTED, Sink::RGB_MERGED_FITTED
     bool planar = false;                               // the chroma planes are separate Cb and Cr planes (I420 / I010), not one interleaved CbCr plane
+    int srcW = 0, srcH = 0, filter = SNN_FILTER_LINEAR; // Source::YUV420_TENSOR: the frame's extent, the sampler,
+    float tensorMeans[3] = {0, 0, 0}, tensorNorms[3] = {1, 1, 1}, alpha = 1.0f; // ... and the normalisation of the input tensor
     const char* entry = "snn_model_create5";           // the entry point the request came through (log lines name it)
 };
 
@@ -36,7 +40,8 @@ bool resolveFrames(const snn_encode_io* io, int in_w, int in_h, int in_c, int ba
 bool resolveFrames(const snn_fit_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 bool resolveFrames(const snn_planar_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 bool resolveFrames(const snn_rgb_fit_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
-// ... by the number of the entry point, 5..13 (`io` is that entry point's struct)
+bool resolveFrames(const snn_video_tensor_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
+// ... by the number of the entry point, 5..14 (`io` is that entry point's struct)
 bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 
 // The rules that need the model's factor r, from the output desc of its last layer: a frame path around the model needs one channel out at r = 1..4

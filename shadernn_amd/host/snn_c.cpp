@@ -22,6 +22,7 @@ struct snn_model {
     ImageTextureArray outputs{nullptr};
     int inW = 0, inH = 0, inC = 0, batch = 1;
     bool half = false;
+    bool videoTensor = false; // snn_model_create14: the input tensor is written by the [yuv tensor] launch, never by an upload of floats or bytes
     SNNModelOutput modelOutput;
     std::vector<char> staging; // host buffer of snn_model_upload_frame_planes / _download_frame_planes for planes that are not tight and adjacent
     // frame quality against a ground-truth frame (snn_model_reference_frame / _frame_metrics): one per output plane tensor, made by the first reference
@@ -97,6 +98,7 @@ static int createModel(const ModelArgs& a, const FrameSpec& spec) {
         m->core = MixedInferenceCore::create(m->context, cp);
         makeIO(m, half);
         m->half = half;
+        m->videoTensor = spec.source == FrameSpec::Source::YUV420_TENSOR;
     } catch (const std::exception& e) {
         SNN_LOGE("snn_model_create: %s", e.what());
         snn_model_destroy(m);
@@ -186,6 +188,11 @@ int snn_model_create12(const char* json_path, int device, int in_w, int in_h, in
 int snn_model_create13(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_rgb_fit_io* io, snn_model** out) {
     return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 13, io);
+}
+
+int snn_model_create14(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_video_tensor_io* io, snn_model** out) {
+    return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 14, io);
 }
 
 // one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame
@@ -297,7 +304,7 @@ int snn_model_destroy(snn_model* m) {
 }
 
 int snn_model_upload_frame_u8(snn_model* m, const unsigned char* nhwc) {
-    snnhip_tensor* t = m && nhwc ? m->core->frameInput() : nullptr;
+    snnhip_tensor* t = m && nhwc && !m->videoTensor ? m->core->frameInput() : nullptr; // (a video frame in front of an RGB model: _upload_frame_nv12 / _planes)
     if (t && snnhip_tensor_dtype(t) != SNNHIP_U8) return -1; // (a 16-bit end: snn_model_upload_frame_u16)
     return t && snnhip_tensor_upload_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
 }
@@ -310,7 +317,7 @@ int snn_model_download_frame_u8(snn_model* m, unsigned char* nhwc) {
 }
 
 int snn_model_upload_frame_u16(snn_model* m, const unsigned short* nhwc) {
-    snnhip_tensor* t = m && nhwc ? m->core->frameInput() : nullptr;
+    snnhip_tensor* t = m && nhwc && !m->videoTensor ? m->core->frameInput() : nullptr;
     if (!t || snnhip_tensor_dtype(t) != SNNHIP_U16) return -1;
     return snnhip_tensor_upload_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
 }
@@ -459,7 +466,14 @@ int snn_model_frame_metrics(snn_model* m, snn_frame_metrics* rows, int max_rows)
 }
 
 int snn_model_upload_input(snn_model* m, const float* nhwc) {
+    if (m->videoTensor) return -1; // (frames go in: snn_model_upload_frame_nv12 / _planes)
     m->inputs[0].uploadNHWC(nhwc);
+    return 0;
+}
+
+int snn_model_download_input(snn_model* m, float* nhwc) {
+    if (!m || !nhwc) return -1;
+    m->inputs[0].downloadNHWC(nhwc);
     return 0;
 }
 
@@ -521,7 +535,7 @@ int snn_yolo_decode(const float* head_coarse, const float* head_fine, int net_si
 
 int snn_model_upload_input_u8(snn_model* m, const unsigned char* pixels, int w, int h, int channels, const float means[4], const float norms[4],
                               const float resize_means[4], const float resize_norms[4]) {
-    if (m->inC != 4) return -1;
+    if (m->inC != 4 || m->videoTensor) return -1;
     auto arr = [](const float* p, float dflt) { return std::array<float, 4>{{p ? p[0] : dflt, p ? p[1] : dflt, p ? p[2] : dflt, p ? p[3] : dflt}}; };
     ImageTexture& t = m->inputs[0];
     t.loadU8AndNormalize(pixels, static_cast<uint32_t>(w), static_cast<uint32_t>(h), static_cast<uint32_t>(channels), arr(means, 0.0f), arr(norms, 1.0f));

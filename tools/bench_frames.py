@@ -1471,6 +1471,112 @@ def main_metrics(a):
     ctx.close()
 
 
+def main_yuv_tensor(a):
+    """--video NV12 | P010 | I420 --tensor WxH [--half] [--batch N]: video frames in front of an RGB(A) model.  The yuv_tensor launch alone (frame of
+    --h x --w, 1080p by default, to the WxH x 4 input tensor), the three launches it replaces (yuv_rgb at r = 1, image_u8, resize: 8-bit frames only)
+    and a device copy of the launch's own bytes, in one process, alternated in mirrored order: medians with spreads."""
+    import ctypes
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    OW, OH = (int(v) for v in a.tensor.lower().split("x"))
+    H, W, N, Cc = a.h or 1080, a.w or 1920, a.batch, 4
+    assert H % 2 == 0 and W % 2 == 0, "4:2:0 frames have even extents"
+    planar, wide = a.video == "I420", a.video == "P010"
+    dt, npdt, maxval, shift = (capi.U16, np.uint16, 1023, 6) if wide else (capi.U8, np.uint8, 255, 0)
+    odt = capi.F16 if a.half else capi.F32
+    rng = np.random.default_rng(1)
+    k = (maxval + 1) // 256
+    means, norms = (123.675 * k, 116.28 * k, 103.53 * k), (1 / (58.395 * k), 1 / (57.12 * k), 1 / (57.375 * k))
+    y = capi.Tensor.from_numpy(ctx, (rng.integers(16 * k, 236 * k, size=(N, H, W, 1)) << shift).astype(npdt), dtype=dt)
+    cshape = (2 * N, H // 2, W // 2, 1) if planar else (N, H // 2, W // 2, 2)
+    c = capi.Tensor.from_numpy(ctx, (rng.integers(16 * k, 241 * k, size=cshape) << shift).astype(npdt), dtype=dt)
+    t_new = capi.Tensor(ctx, N, OH, OW, Cc, dtype=odt)
+    plan = capi.yuv_tensor_plan(ctx, N, H, W, OH, OW, Cc, dt, odt, maxval, shift, a.siting, a.range, filter="linear", means=means, norms=norms, alpha=1.0, planar=planar)
+    forms = {"yuv_tensor": lambda: plan.run([y, c], t_new)}
+    steps = {"yuv_tensor": [plan.describe()]}
+    new_bytes = int(plan.cost()[1])
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+    half_bytes = new_bytes // 2  # a copy of n bytes reads n and writes n: the launch's bytes, read + written, are 2 n
+    src, dst = capi.Tensor(ctx, 1, 1, half_bytes, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half_bytes, 1, dtype=capi.U8)
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(dst.data_ptr(), src.data_ptr(), half_bytes, stream)
+        assert rc == 0, rc
+
+    forms["copy"] = run_copy
+    three_bytes = None
+    if not wide:  # the composition of existing plans: an RGBA8 frame and a 4-channel float frame at the source size in between
+        p1 = (capi.yuv_rgb_planar_plan if planar else capi.yuv_rgb_plan)(ctx, N, H // 2, W // 2, 4, 1, capi.U8, 255, 0, a.siting, a.range)
+        p2 = capi.image_u8_plan(ctx, N, H, W, 4)
+        p3 = capi.resize_plan(ctx, N, H, W, 4, OH, OW, means + (0.0,), norms + (1.0,), linear=True)
+        rgba, f, t_old = capi.Tensor(ctx, N, H, W, 4, dtype=capi.U8), capi.Tensor(ctx, N, H, W, 4, dtype=odt), capi.Tensor(ctx, N, OH, OW, 4, dtype=odt)
+
+        def run_three():
+            p1.run([y, c], rgba)
+            p2.run(rgba, f)
+            p3.run(f, t_old)
+
+        forms["three_launches"] = run_three
+        steps["three_launches"] = [p.describe() for p in (p1, p2, p3)]
+        three_bytes = int(sum(p.cost()[1] for p in (p1, p2, p3)))
+    for fn in forms.values():
+        for _ in range(a.warmup):
+            fn()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {name: [] for name in forms}
+    for _ in range(a.rounds):
+        for name in list(forms) + list(forms)[::-1]:  # mirrored, device events around `iters` enqueued runs
+            timer.start()
+            for _ in range(a.iters):
+                forms[name]()
+            timer.stop()
+            dev[name].append(timer.elapsed_ms() / a.iters)
+
+    def stat(v):
+        m = statistics.median(v)
+        return {"ms_median": round(m, 5), "ms_min": round(min(v), 5), "ms_max": round(max(v), 5), "spread": round((max(v) - min(v)) / m, 4)}
+
+    out = {"video": a.video, "frame": "%dx%d" % (H, W), "tensor": "%dx%dx%d %s" % (OH, OW, Cc, "f16" if a.half else "f32"), "batch": N, "rounds": a.rounds, "iters": a.iters,
+           "timing": "device events around iters enqueued runs, the forms alternated in mirrored order", "steps": steps}
+    for name in forms:
+        out[name] = stat(dev[name])
+    out["yuv_tensor"]["hbm_bytes"] = new_bytes
+    out["yuv_tensor"]["tbs"] = round(new_bytes / (out["yuv_tensor"]["ms_median"] * 1e-3) / 1e12, 3)
+    out["copy"]["hbm_bytes"] = 2 * half_bytes
+    out["copy"]["tbs"] = round(2 * half_bytes / (out["copy"]["ms_median"] * 1e-3) / 1e12, 3)
+    out["yuv_tensor_over_copy"] = round(out["yuv_tensor"]["ms_median"] / out["copy"]["ms_median"], 3)  # a finding, not a gate
+    if three_bytes is not None:
+        out["three_launches"]["hbm_bytes"] = three_bytes
+        out["yuv_tensor_over_three_launches"] = round(out["yuv_tensor"]["ms_median"] / out["three_launches"]["ms_median"], 4)
+        # the condition: the one launch takes no longer than the three, beyond the run's own spread
+        out["condition_no_slower_than_three_launches"] = bool(out["yuv_tensor"]["ms_median"] <= out["three_launches"]["ms_median"] or
+                                                              out["yuv_tensor"]["ms_min"] <= out["three_launches"]["ms_max"])
+    capi.trace_begin()
+    for _ in range(a.iters):
+        forms["yuv_tensor"]()
+    ctx.sync()
+    rep = capi.trace_end()
+    kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+    out["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                       "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+    print(json.dumps(out, indent=1))
+    if a.out:
+        rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        rec["%s_%dx%d_to_%dx%dx%d_%s_b%d" % (a.video.lower(), W, H, OW, OH, Cc, "f16" if a.half else "f32", N)] = out
+        with open(a.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
@@ -1487,6 +1593,9 @@ def main():
     ap.add_argument("--fit", default=None, metavar="WxH", help="with --video: the NV12 / P010 frame at this output size (the chain, then two plane_fit launches) beside the plain step of the same r")
     ap.add_argument("--rgb-fit", default=None, metavar="WxH", help="with --video NV12 | P010 | I420 --video-out RGB8 | RGBA8, or with --colour alone: the RGB frame at this output size "
                     "(the chain, the luma fit, rgb_fit) beside the r-fold RGB step of the same r; --out merges the record into a JSON file")
+    ap.add_argument("--tensor", default=None, metavar="WxH", help="with --video NV12 | P010 | I420 alone: video in front of an RGB(A) model -- the yuv_tensor launch from a frame of "
+                    "--h x --w (1080p by default) to the WxH x 4 input tensor (fp16 with --half), the three launches it replaces and a device copy of its bytes")
+    ap.add_argument("--batch", type=int, default=1, help="with --tensor: frames per launch")
     ap.add_argument("--range", choices=["limited", "full"], default="limited", help="the stream's range with --video-out")
     ap.add_argument("--siting", choices=["left", "centre"], default="left", help="horizontal chroma siting of --video")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
@@ -1500,6 +1609,9 @@ def main():
     a = ap.parse_args()
     if a.metrics:
         return main_metrics(a)
+    if a.tensor:
+        assert a.video in ("NV12", "P010", "I420") and not a.video_out and not a.colour and not a.fit and not a.rgb_fit, "--tensor goes with --video NV12 | P010 | I420 alone"
+        return main_yuv_tensor(a)
     if a.rgb_fit:
         assert not a.fit and ((a.video in ("NV12", "P010", "I420") and a.video_out in ("RGB8", "RGBA8") and not a.colour) or (a.colour and not a.video and not a.video_out)), \
             "--rgb-fit goes with --video NV12 | P010 | I420 --video-out RGB8 | RGBA8, or with --colour RGB8 | RGBA8 alone"
