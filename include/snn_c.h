@@ -268,6 +268,37 @@ typedef struct snn_video_tensor_io {
 } snn_video_tensor_io; /* 28 * 4 bytes */
 int snn_model_create14(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
                        int prefer_half, int capture_graph, int batch, const snn_video_tensor_io* io, snn_model** out);
+/* Encoder frames behind an RGB(A) model: the model's output tensor leaves as the planes of a 4:2:0 frame of the same extent -- NV12 / P010 / I420 /
+ * I010, what a hardware or software encoder takes -- in ONE launch behind the model's last stage (include/snnhip.h, snnhip_tensor_yuv_plan_create,
+ * states the arithmetic: p = clamp(x * out_scale + out_offset, 0, maxval), the luma code, the chroma differences decimated 2 x 2, the chroma codes).
+ * With snn_model_create14's frame in front, "decoder -> RGB model -> encoder" runs with no float frame and no RGB frame crossing the host link.
+ * Through a struct and an entry point of their own: every earlier struct and entry point keeps its layout, behaviour and refusals.  The model is
+ * built exactly as snn_model_create4 builds it; with an 8-bit in_format exactly as snn_model_create5 builds it with that in_format, in_means, in_norms
+ * and a float output; with a video in_format exactly as snn_model_create14 builds it from video_in with a float output.  The launch, "[tensor yuv]"
+ * in snn_model_describe, runs on the model's stream from the model's own output tensor (the fp16 tensor of a prefer_half model) into plane tensors
+ * that are allocated once, sits inside the recorded graph with capture_graph and counts towards SNN_GRAPH_MIN_LAUNCHES.  snn_model_download_frame_nv12
+ * returns dense frames (H * W luma elements, then (H / 2) * W interleaved chroma elements; SNN_IO_NV12 / _NV12_16), snn_model_download_frame_planes
+ * pitched planes (n_planes = 2, or 3 for the planar formats); snn_model_reference_frame* and snn_model_frame_metrics work on them as for the other
+ * video ends (one luma row and two chroma rows per image); snn_model_download_output, snn_model_download_frame_u8 and _u16 return -1 on such a
+ * model.  Returns -1, before anything is built on the device, for a null struct, an out_format that is none of the four, an in_format that is
+ * neither SNN_IO_FLOAT, an 8-bit format of in_c channels nor one of the four video formats, a video in_format that video_in.in_format does not
+ * repeat or whose video_in.out_format is not SNN_IO_FLOAT, everything snn_model_create14 refuses about video_in, batch below 1, an unknown siting or
+ * range, kr / kb outside 0 < kr, 0 < kb, kr + kb < 1, maxval + 1 not a multiple of 256, maxval above 255 (8-bit) / 4095 (16-bit) and a
+ * maxval << shift that does not fit the container; and, once the model file gives the output, for a model whose output has not 3 or 4 channels or an
+ * odd extent.  Not offered: resizing at this end (a fitted encoder size would be plane_fit behind it), 4:2:2 / 4:4:4, BGR order, a cubic or longer
+ * decimation filter, and folding the conversion into the model's last convolution. */
+typedef struct snn_tensor_video_io {
+    int in_format;   /* SNN_IO_FLOAT; an 8-bit frame format of the model input's channel count (in_means / in_norms as snn_frame_io);
+                        or SNN_IO_NV12 / _NV12_16 / _I420 / _I420_16: then video_in describes the frame in front, exactly as snn_model_create14 takes it */
+    int out_format;  /* SNN_IO_NV12, SNN_IO_NV12_16, SNN_IO_I420 or SNN_IO_I420_16 */
+    int maxval, shift, siting, range; /* the OUTPUT stream's, as snn_video_rgb_io */
+    float kr, kb;
+    float out_scale[4], out_offset[4]; /* three are used: p = clamp(x * out_scale[c] + out_offset[c], 0, maxval), full-range RGB at the output depth */
+    float in_means[4], in_norms[4];    /* an 8-bit in_format: as snn_frame_io */
+    snn_video_tensor_io video_in;      /* looked at only with a video in_format; its out_format must be SNN_IO_FLOAT */
+} snn_tensor_video_io; /* 52 * 4 bytes */
+int snn_model_create15(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_tensor_video_io* io, snn_model** out);
 int snn_model_download_input(snn_model* m, float* nhwc); /* the model's input tensor, [batch x] H x W x C floats (what [yuv tensor] wrote, or the last upload) */
 /* Frames as plane pointers with row pitches (ffmpeg's data[] / linesize[]).  `planes` holds batch * n_planes pointers, frame by frame, in the order
  * Y, Cb, Cr (a YV12 caller swaps the last two) for a planar end, n_planes = 3; Y, CbCr for the NV12 / P010 ends of models made by snn_model_create8
@@ -379,7 +410,7 @@ int snn_yolo_decode(const float* head_coarse, const float* head_fine, int net_si
  * Test hook for the loader's number grammar (overflow saturates to +-HUGE_VAL, underflow gives +-0 / a denormal, like the reference's strtod). */
 int snn_json_number(const char* text, double* out);
 
-/* Host-only: what snn_model_create<entry> (entry = 5..14, `io` that entry point's struct or NULL) resolves its struct to for an in_w x in_h x in_c
+/* Host-only: what snn_model_create<entry> (entry = 5..15, `io` that entry point's struct or NULL) resolves its struct to for an in_w x in_h x in_c
  * input and `batch` images, before any model file is opened: -1 where the entry point refuses the request, otherwise 0 and one canonical text line in
  * buf, "<the model's own end formats and maps> | <the frames the caller uploads and gets back, and their parameters> | entry=<name>".  Test hook for
  * the "built exactly as" statements above: two requests that name the same model resolve to the same first part (shadernn_amd/host/snn/frames.h). */

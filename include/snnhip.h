@@ -673,6 +673,44 @@ int snnhip_yuv_tensor_planar_plan_create(snnhip_ctx* ctx, const snnhip_yuv_tenso
  * for a null pointer, in or out outside 1 .. 2^30, an unknown filter and too little room. */
 int snnhip_yuv_tensor_taps(int in, int out, int filter, float* weight, int* index, int capacity);
 
+/* The output tensor of an RGB(A) model to the planes of a 4:2:0 video frame of the same extent, in one launch: what a hardware or software encoder
+ * takes (NV12 / P010 / I420 / I010) behind a style or enhancement network, 1.5 bytes per pixel (3 for 10-bit) instead of a float tensor or a packed
+ * RGB8 frame crossing the host link.  It is the other end of yuv_tensor, and the decimation filter that rgb_cbcr's r = 1 lacks.  DESIGN.md section
+ * 4.27.  The contract, stated once:
+ *   Shapes: inputs[0] = the tensor [N][H][W][C] of `in_dtype`, SNNHIP_F32 or SNNHIP_F16, C = 3 (R, G, B) or 4 (channel 3 is ignored, whatever it holds);
+ *     H and W even, at least 2.  outputs[0] = the luma plane [N][H][W][1]; outputs[1] = the chroma, interleaved CbCr [N][H/2][W/2][2]
+ *     (snnhip_tensor_yuv_plan_create) or planar [2N][H/2][W/2][1], plane 2n = Cb and 2n + 1 = Cr of image n (snnhip_tensor_yuv_planar_plan_create, the
+ *     same desc); both of `out_dtype`, SNNHIP_U8 or SNNHIP_U16.  maxval, shift, siting, range, kr, kb mean what they mean for yuv_rgb.  The plan has
+ *     two outputs: run it with snnhip_plan_run_io, 1 input, 2 outputs.
+ *   Pixel: p_c = clamp(fmaf(x_c, scale[c], offset[c]), 0, maxval) in fp32 (an fp16 tensor's values widened): full-range RGB in units of the output
+ *     depth.  A model that emits 0..255 uses scale 1 for 8-bit and 1023 / 255 for 10-bit; a tanh model maxval / 2 for both scale and offset.
+ *   Luma: ylo = kr R + kg G + kb B in fp32, unquantised (the one device function of rgb_luma, ycc_merge and rgb_cbcr, kg = 1 - kr - kb as there);
+ *     with k = (maxval + 1) / 256 and Yoff, Yrange, Coff, Crange of yuv_rgb's matrix for the range, ys = Yrange / maxval, Y = Yoff + ys ylo,
+ *     q = unsigned(clamp(rint(Y), 0, maxval)) << shift, ties to even.
+ *   Chroma differences, per luma pixel: dB = B - ylo, dR = R - ylo, unquantised.
+ *   Decimation: chroma sample (J, I) reads luma rows 2J and 2J + 1 with weights 1/2, 1/2 (the vertical axis is always centred, as everywhere in this
+ *     family).  Along a row SNNHIP_SITING_CENTRE reads columns 2I and 2I + 1 with weights 1/2, 1/2; SNNHIP_SITING_LEFT reads columns 2I - 1, 2I, 2I + 1
+ *     with weights 1/4, 1/2, 1/4, the index clamped to [0, W - 1] (only column -1 can clamp: W is even).  Horizontal first, then vertical, in fp32, in
+ *     the order (w0 d0 + w1 d1) + w2 d2.  The weights are exact in binary: there is no table.
+ *   Chroma matrix: cbs = Crange / (2 (1 - kb) maxval), crs = Crange / (2 (1 - kr) maxval), computed in double and rounded to float: the reciprocals of
+ *     yuv_rgb's cbu and crv.  Cb = Coff + cbs dB~, Cr = Coff + crs dR~, through the same quantiser.
+ *   Consequences: a grey tensor (R = G = B after the map) gives Cb = Cr = Coff in every sample; a constant tensor gives constant planes; on a 2 x 2-
+ *     replicated tensor both sitings agree except in column 0.  In fp32 the value in front of the rounding stays within 3.1e-5 / 1.25e-4 / 4.8e-4
+ *     (8 / 10 / 12 bits; measured, tests/tensor_yuv_ref.py) of a float64 evaluation.
+ * Plan creation returns SNNHIP_E_INVALID with a message starting "tensor_yuv desc" for everything yuv_rgb refuses (dtype of the planes, maxval, shift,
+ * maxval + 1 not a multiple of 256, siting, range, kr / kb), C outside {3, 4}, an odd or non-positive H or W, N < 1 and an in_dtype that is neither
+ * SNNHIP_F32 nor SNNHIP_F16.  snnhip_plan_run and snnhip_plan_run_n refuse this plan with a message starting "tensor_yuv"; snnhip_plan_run_io refuses,
+ * with a message, a wrong n_in or n_out and a tensor of another dtype or shape at any position.  snnhip_plan_describe: "tensor_yuv_u8 c=3 f16
+ * siting=left range=limited 720x1280 tile=2048 ... kernel=tensor_yuv_kernel" (tensor_yuv_planar_... / tensor_yuv_planar_kernel for planar chroma; the
+ * tile in luma pixels per block).  snnhip_plan_cost counts the input once and both outputs once.
+ * Not offered: resizing at this end (a fitted encoder size is plane_fit behind it); 4:2:2 / 4:4:4; BGR order; a cubic or longer decimation filter;
+ * folding the conversion into a model's last convolution. */
+typedef struct { int N, H, W, C; int in_dtype, out_dtype; int maxval, shift; int siting, range; float kr, kb; float scale[3], offset[3]; } snnhip_tensor_yuv_desc;
+int snnhip_tensor_yuv_plan_create(snnhip_ctx* ctx, const snnhip_tensor_yuv_desc* desc, snnhip_plan** out);        /* chroma out: [N][H/2][W/2][2], interleaved CbCr (NV12 / P010) */
+int snnhip_tensor_yuv_planar_plan_create(snnhip_ctx* ctx, const snnhip_tensor_yuv_desc* desc, snnhip_plan** out); /* chroma out: [2N][H/2][W/2][1], plane 2n = Cb, 2n + 1 = Cr (I420 / I010) */
+/* host only, no context: out[0..4] = Yoff, ys, Coff, cbs, crs of the map above (capacity >= 5 floats) */
+int snnhip_tensor_yuv_coefficients(int maxval, int range, float kr, float kb, float* out, int capacity);
+
 /* Frame quality on the device: PSNR and SSIM between a test frame and a reference frame, so that what an arithmetic choice (fused fp32, the fp16
  * opt-in, 8 / 10 / 12-bit frame ends) or a trained model costs in picture quality can be stated in dB without downloading every output frame.
  * DESIGN.md section 4.22.  The reference ships a host-side comparison script only (tools/misc/imageComparison.py).  The definition, stated once
@@ -762,6 +800,9 @@ int snnhip_graph_fuse(snnhip_ctx* ctx, const snnhip_graph_node* nodes, int n, sn
 int snnhip_plan_run(snnhip_plan* plan, const snnhip_tensor* in, snnhip_tensor* out);
 /* multi-input ops (add, concat): inputs[n_in] */
 int snnhip_plan_run_n(snnhip_plan* plan, const snnhip_tensor* const* inputs, int n_in, snnhip_tensor* out);
+/* a plan with more than one output: the tensor_yuv plans (1 input; outputs[0] = the luma plane, outputs[1] = the chroma).  Every other plan is
+ * refused with a message; the two functions above refuse a tensor_yuv plan.  The same launch trace, guard mode and graph capture as those two. */
+int snnhip_plan_run_io(snnhip_plan* plan, const snnhip_tensor* const* inputs, int n_in, snnhip_tensor* const* outputs, int n_out);
 int snnhip_plan_output_dims(const snnhip_plan* plan, int dims_nhwc[4]);
 /* Human-readable kernel-variant description ("conv2d_mfma_f32 tile=...") for logs and tests. */
 int snnhip_plan_describe(const snnhip_plan* plan, char* buf, size_t buflen);

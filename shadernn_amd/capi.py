@@ -133,6 +133,11 @@ class RgbFitDesc(C.Structure):
                 ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float)]
 
 
+class TensorYuvDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("in_dtype", C.c_int), ("out_dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int),
+                ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float), ("scale", C.c_float * 3), ("offset", C.c_float * 3)]
+
+
 class FrameMetricsDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int)]
 
@@ -235,6 +240,9 @@ SIGNATURES = {
     "snnhip_yuv_tensor_plan_create": (C.c_int, [_P, C.POINTER(YuvTensorDesc), C.POINTER(_P)]),
     "snnhip_yuv_tensor_planar_plan_create": (C.c_int, [_P, C.POINTER(YuvTensorDesc), C.POINTER(_P)]),
     "snnhip_yuv_tensor_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.POINTER(C.c_int), C.c_int]),
+    "snnhip_tensor_yuv_plan_create": (C.c_int, [_P, C.POINTER(TensorYuvDesc), C.POINTER(_P)]),
+    "snnhip_tensor_yuv_planar_plan_create": (C.c_int, [_P, C.POINTER(TensorYuvDesc), C.POINTER(_P)]),
+    "snnhip_tensor_yuv_coefficients": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, _FP, C.c_int]),
     "snnhip_frame_metrics_plan_create": (C.c_int, [_P, C.POINTER(FrameMetricsDesc), C.POINTER(_P)]),
     "snnhip_frame_metrics_read": (C.c_int, [_P, C.POINTER(FrameMetricsRow), C.c_int]),
     "snnhip_frame_metrics_psnr": (C.c_double, [C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -245,6 +253,7 @@ SIGNATURES = {
     "snnhip_graph_fuse": (C.c_int, [_P, C.POINTER(GraphNode), C.c_int, C.POINTER(FusedNode)]),
     "snnhip_plan_run": (C.c_int, [_P, _P, _P]),
     "snnhip_plan_run_n": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P]),
+    "snnhip_plan_run_io": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P), C.c_int]),
     "snnhip_plan_output_dims": (C.c_int, [_P, C.POINTER(C.c_int * 4)]),
     "snnhip_plan_describe": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
     "snnhip_plan_cost": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -521,6 +530,12 @@ class Plan:
             check(lib().snnhip_plan_run_n(self.h, arr, len(x), y.h))
         else:
             check(lib().snnhip_plan_run(self.h, x.h, y.h))
+
+    def run_io(self, xs, ys):
+        """snnhip_plan_run_io: a plan with more than one output (tensor_yuv_plan); xs and ys are lists of tensors"""
+        a = (_P * max(len(xs), 1))(*[t.h for t in xs])
+        b = (_P * max(len(ys), 1))(*[t.h for t in ys])
+        check(lib().snnhip_plan_run_io(self.h, a, len(xs), b, len(ys)))
 
     def __call__(self, x, y=None):
         if y is None:
@@ -940,6 +955,28 @@ def yuv_tensor_taps(n_in, n_out, filter="linear", capacity=None):
     idx = (C.c_int * (2 * max(n, 1)))()
     check(lib().snnhip_yuv_tensor_taps(n_in, n_out, YUV_TENSOR_FILTER.get(filter, filter), _fptr(a), idx, n if capacity is None else capacity))
     return a[:n], np.array(idx[:2 * n], np.int32).reshape(n, 2)
+
+
+def tensor_yuv_plan(ctx, N, H, W, Cc, in_dtype=F32, out_dtype=U8, maxval=None, shift=0, siting="left", range="limited", kr=BT601[0], kb=BT601[1], scale=(1, 1, 1),
+                    offset=(0, 0, 0), planar=False):
+    """plan.run_io([T [N][H][W][Cc]], [Y [N][H][W][1], chroma]): the fp32 / fp16 output tensor of an RGB (Cc = 3) or RGBA (Cc = 4, channel 3 ignored) model
+    straight to the planes of a 4:2:0 video frame of the same extent (U8 / U16, H and W even), in one launch (include/snnhip.h states the arithmetic).
+    The chroma is interleaved CbCr [N][H/2][W/2][2], or with planar=True [2N][H/2][W/2][1] (plane 2n = Cb, 2n + 1 = Cr); p = clamp(x * scale + offset,
+    0, maxval) is full-range RGB at the output depth.  maxval defaults to 255 (a 16-bit frame must say)."""
+    if maxval is None:
+        maxval = 255
+    d = TensorYuvDesc(N, H, W, Cc, in_dtype, out_dtype, maxval, shift, SITING.get(siting, siting), RANGE.get(range, range), kr, kb, (C.c_float * 3)(*scale[:3]),
+                      (C.c_float * 3)(*offset[:3]))
+    h = _P()
+    check((lib().snnhip_tensor_yuv_planar_plan_create if planar else lib().snnhip_tensor_yuv_plan_create)(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
+
+
+def tensor_yuv_coefficients(maxval=255, range="limited", kr=BT601[0], kb=BT601[1], capacity=None):
+    """snnhip_tensor_yuv_coefficients (host side only, no GPU): float32 (Yoff, ys, Coff, cbs, crs) of the full-range RGB -> Y'CbCr codes map."""
+    out = np.zeros(5, np.float32)
+    check(lib().snnhip_tensor_yuv_coefficients(maxval, RANGE.get(range, range), kr, kb, _fptr(out), out.size if capacity is None else capacity))
+    return out
 
 
 RGB_FIT_SOURCE = {"cbcr": 0, "planar": 1, "rgb": 2}  # SNNHIP_RGB_FIT_*

@@ -226,6 +226,16 @@ int snnhip_plan::invoke(const snnhip_tensor* const* in, int nIn, snnhip_tensor* 
     return run(in, nIn, out);
 }
 
+int snnhip_plan::runIO(const snnhip_tensor* const*, int, snnhip_tensor* const*, int) {
+    snnhip::set_error("plan_run_io: only a tensor_yuv plan has more than one output; this one runs through snnhip_plan_run / snnhip_plan_run_n (%s)", desc.c_str());
+    return SNNHIP_E_INVALID;
+}
+
+int snnhip_plan::invokeIO(const snnhip_tensor* const* in, int nIn, snnhip_tensor* const* out, int nOut) {
+    snnhip::TraceScope scope(this);
+    return runIO(in, nIn, out, nOut);
+}
+
 int snnhip_plan::upload(const float* host, size_t count, float** dev) {
     void* p = nullptr;
     SNNHIP_CHECK_HIP(snnhip::dev_malloc(&p, count ? count * sizeof(float) : 4, "packed weights / table of a plan"));
@@ -909,6 +919,7 @@ int snnhip_plan_run_n(snnhip_plan* plan, const snnhip_tensor* const* inputs, int
     SNNHIP_REQUIRE(plan && inputs && out && n_in > 0, "plan_run: null argument");
     for (int i = 0; i < n_in; ++i) SNNHIP_REQUIRE(inputs[i] && inputs[i]->data, "plan_run: input %d is null", i);
     SNNHIP_REQUIRE(out->data, "plan_run: output has no storage");
+    if (plan->numOutputs != 1) return plan->run(inputs, n_in, out); // a tensor_yuv plan: its run() refuses and names snnhip_plan_run_io
     // a raw frame tensor (SNNHIP_U8 / SNNHIP_U16) is accepted exactly where the plan declares one
     for (int i = 0; i < n_in; ++i) {
         SNNHIP_REQUIRE(inputs[i]->dtype != SNNHIP_U8 || plan->rawInput == SNNHIP_U8, "plan_run: input %d is an 8-bit image tensor (%s)", i, plan->desc.c_str());
@@ -934,6 +945,22 @@ int snnhip_plan_run_n(snnhip_plan* plan, const snnhip_tensor* const* inputs, int
         return plan->profEnd(0);
     }
     return plan->invoke(inputs, n_in, out);
+}
+
+int snnhip_plan_run_io(snnhip_plan* plan, const snnhip_tensor* const* inputs, int n_in, snnhip_tensor* const* outputs, int n_out) {
+    SNNHIP_REQUIRE(plan && inputs && outputs && n_in > 0 && n_out > 0, "plan_run_io: null argument");
+    SNNHIP_REQUIRE(plan->numOutputs > 1, "plan_run_io: only a tensor_yuv plan has more than one output; this one runs through snnhip_plan_run / snnhip_plan_run_n (%s)",
+                   plan->desc.c_str());
+    for (int i = 0; i < n_in; ++i) SNNHIP_REQUIRE(inputs[i] && inputs[i]->data, "plan_run_io: input %d is null", i);
+    for (int i = 0; i < n_out; ++i) SNNHIP_REQUIRE(outputs[i] && outputs[i]->data, "plan_run_io: output %d is null or has no storage", i);
+    if (plan->profiling && !plan->profilesItself()) {
+        int rc = plan->profBegin(0);
+        if (rc != SNNHIP_OK) return rc;
+        rc = plan->invokeIO(inputs, n_in, outputs, n_out);
+        if (rc != SNNHIP_OK) return rc;
+        return plan->profEnd(0);
+    }
+    return plan->invokeIO(inputs, n_in, outputs, n_out);
 }
 
 int snnhip_plan_num_steps(const snnhip_plan* plan) { return plan ? plan->numSteps() : 0; }

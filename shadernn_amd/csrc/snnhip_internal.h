@@ -137,6 +137,7 @@ struct snnhip_plan {
     int inDims[4] = {0, 0, 0, 0};   // N,H,W,C of input 0
     int outDims[4] = {0, 0, 0, 0};
     int numInputs = 1;
+    int numOutputs = 1;       // 2: a tensor_yuv plan (frame_tensor_yuv.hip), which runs through runIO() / snnhip_plan_run_io and whose run() refuses
     int dtype = SNNHIP_F32;   // element type of the tensors this plan runs on ...
     bool anyDtype = false;    // ... unless it adapts to the tensors of each call (element-wise / pooling / shape operators)
     // raw frame dtype of this plan's input 0 / output (SNNHIP_U8 or SNNHIP_U16), -1 = none: snnhip_image_u8_plan_create and the u8_in / u16_in plans read
@@ -170,6 +171,9 @@ struct snnhip_plan {
     virtual int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) = 0;
     // run() under a launch-trace scope of this plan (snnhip_trace_begin): what the C-ABI and every composite plan call
     int invoke(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out);
+    // the same for a plan with more than one output (numOutputs > 1); every other plan refuses
+    virtual int runIO(const snnhip_tensor* const* in, int nIn, snnhip_tensor* const* out, int nOut);
+    int invokeIO(const snnhip_tensor* const* in, int nIn, snnhip_tensor* const* out, int nOut);
     virtual int numSteps() const { return 1; }
     virtual std::string stepDesc(int) const { return desc; }
     virtual void stepCost(int, double* f, double* b) const {

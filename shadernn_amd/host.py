@@ -78,6 +78,7 @@ SIGNATURES = {
                                            C.c_char_p, C.c_int]),
     "snn_graph_summary": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "snn_json_number": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]),
+    "snn_model_create15": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "snn_frames_resolve": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "snn_dump_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int * 4), _FP, C.c_long]),
 }
@@ -129,7 +130,7 @@ def json_number(text):
 def frames_resolve(entry, io, w, h, c, batch=1):
     """The frame description snn_model_create<entry> resolves its struct `io` (None: a null struct) to, as one canonical line "<the model part> |
     <the frame ends> | entry=<name>"; None if the entry point refuses the request before it opens the model file.  Host-only."""
-    buf = C.create_string_buffer(1024)
+    buf = C.create_string_buffer(2048)
     rc = lib().snn_frames_resolve(entry, None if io is None else C.byref(io), w, h, c, batch, buf, len(buf))
     return buf.value.decode() if rc == 0 else None
 
@@ -215,6 +216,14 @@ class VideoTensorIO(C.Structure):
                 ("out_scale", C.c_float * 4), ("out_offset", C.c_float * 4)]
 
 
+class TensorVideoIO(C.Structure):
+    """snn_tensor_video_io (include/snn_c.h): the output tensor of an RGB(A) model to the planes of a 4:2:0 frame of the same extent; video_in as
+    snn_model_create14 takes it when a video frame goes in."""
+    _fields_ = [("in_format", C.c_int), ("out_format", C.c_int), ("maxval", C.c_int), ("shift", C.c_int), ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float),
+                ("kb", C.c_float), ("out_scale", C.c_float * 4), ("out_offset", C.c_float * 4), ("in_means", C.c_float * 4), ("in_norms", C.c_float * 4),
+                ("video_in", VideoTensorIO)]
+
+
 VIDEO_FILTERS = {"nearest": 0, "linear": 1}  # SNN_FILTER_*
 # name: (SNN_IO_NV12 / SNN_IO_NV12_16 / SNN_IO_I420 / SNN_IO_I420_16, maxval, shift); I010 is ffmpeg's yuv420p10le: 10 bits in the low end of 2 bytes
 VIDEO_FORMATS = {"NV12": (0x201, 255, 0), "P010": (0x301, 1023, 6), "I420": (0x401, 255, 0), "I010": (0x501, 1023, 0)}
@@ -232,7 +241,7 @@ class Model:
                  batch=1, input_format=None, output_format=None, in_means=(0, 0, 0, 0), in_norms=(1, 1, 1, 1), out_scale=(1, 1, 1, 1),
                  out_offset=(0, 0, 0, 0), frame_in_shift=0, frame_out_maxval=65535, frame_out_shift=0, colour=None, kr=0.299, kb=0.114, video=None,
                  siting="left", video_maxval=None, video_shift=None, video_out=None, video_range="limited", out_size=None, rgb_size=None, frame_size=None,
-                 video_filter="linear", alpha=1.0):
+                 video_filter="linear", alpha=1.0, encode=None, encode_maxval=None, encode_shift=None):
         """batch > 1: every stage tensor carries `batch` images (snn_model_create4); upload() takes and output() returns a leading batch axis.
         input_format / output_format "R8" / "RGB8" / "RGBA8": 8-bit frames at that end (snn_model_create5): upload_frame(uint8) feeds the input,
         output_frame() returns the uint8 output; y = (u - in_means[c]) * in_norms[c] in, clamp(rint(x * out_scale[c] + out_offset[c]), 0, 255) out.
@@ -270,7 +279,14 @@ class Model:
         t = (sample - in_means[c]) * in_norms[c] with the sample in 0 .. maxval, channel 3 = alpha, video_filter "linear" / "nearest", siting,
         video_range, kr, kb the stream's.  upload_frame / upload_planes take the planes at frame_size; upload() and upload_u8() are refused;
         input_tensor() returns what the launch wrote.  output_format "RGB8" / ... (with out_scale / out_offset) makes the model's output an 8-bit
-        frame as snn_model_create5 does; otherwise output() returns floats."""
+        frame as snn_model_create5 does; otherwise output() returns floats.
+        encode "NV12" / "P010" / "I420" / "I010" (snn_model_create15): an encoder's frame behind an RGB(A) model -- the model's output tensor (3 or 4
+        channels, an even extent) leaves as the planes of a 4:2:0 frame of its own extent in one launch behind the model:
+        p = clamp(x * out_scale[c] + out_offset[c], 0, maxval) is full-range RGB at the output depth (encode_maxval / encode_shift override the
+        format's: P010 1023, 6), siting, video_range, kr, kb the OUTPUT stream's.  It goes beside nothing (upload() takes floats), beside
+        input_format "RGB8" / "RGBA8" (upload_frame takes uint8, in_means / in_norms), or beside video=..., frame_size=... (video in as above AND out:
+        the stream's parameters serve both ends).  output_frame / download_frame return the pair (y, cbcr) or the triple (y, cb, cr),
+        download_planes fills pitched planes; output() and the 8-bit downloads are refused."""
         self.h = _P()
         self.batch = batch
         self.video = video  # the upload end: None = one array (the model's frame or a colour frame), else planes of this format
@@ -300,8 +316,28 @@ class Model:
             tensor_io = VideoTensorIO(fmt, FRAME_FORMATS[output_format], sw, sh, maxval, shift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, VIDEO_FILTERS[video_filter],
                                       maps[0], maps[1], alpha, maps[2], maps[3])
             video_out = colour = None
+        if encode is not None:
+            assert encode in VIDEO_FORMATS, "encode is \"NV12\", \"P010\", \"I420\" or \"I010\""
+            assert video_out is None and colour is None and out_size is None and rgb_size is None and output_format is None, \
+                "encode makes the output a 4:2:0 frame: not beside video_out / colour / out_size / rgb_size / output_format"
+            assert (video is None) == (frame_size is None), "video frames in front of encode= need video= and frame_size= together"
+            assert input_format in (None, "float", "RGB8", "RGBA8") and (input_format in (None, "float") or video is None), \
+                "encode goes beside nothing, beside input_format=\"RGB8\" / \"RGBA8\", or beside video= and frame_size="
+            assert video_range in VIDEO_RANGES, "video_range is \"limited\" or \"full\""
+            assert siting in SITINGS, "siting is \"left\" or \"centre\""
+            assert kr > 0 and kb > 0 and kr + kb < 1, "0 < kr, 0 < kb, kr + kb < 1"
+            efmt, emaxval, eshift = VIDEO_FORMATS[encode]
+            emaxval = emaxval if encode_maxval is None else encode_maxval
+            eshift = eshift if encode_shift is None else encode_shift
+            maps = [(C.c_float * 4)(*(tuple(m) + (0,) * 4)[:4]) for m in (out_scale, out_offset, in_means, in_norms)]
+            encode_io = TensorVideoIO(fmt if video is not None else FRAME_FORMATS[input_format], efmt, emaxval, eshift, SITINGS[siting], VIDEO_RANGES[video_range], kr, kb, *maps,
+                                      tensor_io if video is not None else VideoTensorIO())
+            self.frame_dtypes = (self.frame_dtypes[0] if video is not None else np.uint8, np.uint16 if efmt in (0x301, 0x501) else np.uint8)
+            self.out_end = "yuv"
         assert out_size is None or (video is not None and video_out is None and colour is None), "out_size fits an NV12 / P010 frame: it goes with video= alone"
-        if frame_size is not None:
+        if encode is not None:
+            entry, io = 15, encode_io
+        elif frame_size is not None:
             entry, io = 14, tensor_io
         elif rgb_size is not None:
             assert out_size is None and input_format is None and output_format is None, "rgb_size is the size of an RGB frame: not beside out_size / input_format / output_format"
@@ -383,7 +419,8 @@ class Model:
                 entry, io = 6, FrameIO2(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps, frame_in_shift, frame_out_maxval, frame_out_shift)
             else:
                 entry, io = 5, FrameIO(FRAME_FORMATS[input_format], FRAME_FORMATS[output_format], *maps)
-        self.planar = entry == 12 or (entry in (13, 14) and video in PLANAR_FORMATS)
+        self.planar = entry == 12 or (entry in (13, 14, 15) and video in PLANAR_FORMATS)
+        self.out_planar = encode in PLANAR_FORMATS if entry == 15 else self.planar  # the download end's layout: its own behind encode=
         self.in_shape = (h, w, in_channels) if batch == 1 else (batch, h, w, in_channels)
         create = getattr(lib(), "snn_model_create%d" % entry)
         assert create(json_path.encode(), device, w, h, c, int(dump_outputs), int(fuse_chains), int(profiling), int(prefer_half), int(capture_graph), int(batch),
@@ -405,7 +442,7 @@ class Model:
         lib().snn_model_output_dims(self.h, C.byref(d))
         if self.out_end == "yuv":
             oh, ow = (self.out_size[1], self.out_size[0]) if self.out_size is not None else (d[0], d[1])
-            return self._download_planar(oh, ow) if self.planar else self._download_video(oh, ow)
+            return self._download_planar(oh, ow) if self.out_planar else self._download_video(oh, ow)
         if self.out_size is not None:  # rgb_size: the RGB frame at that size
             d = (self.out_size[1], self.out_size[0], d[2])
         if self.out_channels:
@@ -496,14 +533,14 @@ class Model:
             assert lib().snn_model_reference_frame(self.h, ref.ctypes.data_as(_P)) == 0, "snn_model_reference_frame refused (see the log)"
             return
         parts = list(ref)
-        k = 3 if self.planar else 2
+        k = 3 if self.out_planar else 2
         if len(parts) == n * k and all(isinstance(a, np.ndarray) and a.ndim == 2 for a in parts):  # plane arrays, any pitch
             ptrs, pitches, k, keep = self._plane_args(parts, dt)
             assert lib().snn_model_reference_frame_planes(self.h, ptrs, pitches, k) == 0, "snn_model_reference_frame_planes refused (see the log)"
             del keep
             return
-        assert len(parts) == k, "an %s output takes %s" % ("I420 / I010" if self.planar else "NV12 / P010", "(y, cb, cr)" if self.planar else "(y, cbcr)")
-        if self.planar:
+        assert len(parts) == k, "an %s output takes %s" % ("I420 / I010" if self.out_planar else "NV12 / P010", "(y, cb, cr)" if self.out_planar else "(y, cbcr)")
+        if self.out_planar:
             y, cb, cr = (np.ascontiguousarray(a, dtype=dt).reshape(n, hh, ww) for a, (hh, ww) in zip(parts, ((oh, ow), (oh // 2, ow // 2), (oh // 2, ow // 2))))
             return self.set_reference([a[i] for i in range(n) for a in (y, cb, cr)])
         y = np.ascontiguousarray(parts[0], dtype=dt).reshape(n, oh * ow)

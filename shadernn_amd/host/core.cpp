@@ -96,7 +96,7 @@ bool MixedInferenceCore::init(const CreationParameters& cp_) {
         if (cp.profiling) stage.timer.reset(backend->createDeviceTimer(layer.name));
     }
     const int frameIn = cp.frames.model.in_format, frameOut = cp.frames.model.out_format; // SNN_IO_*: the low byte is the channel count
-    if (frameIn != SNN_IO_FLOAT || frameOut != SNN_IO_FLOAT || cp.frames.source == FrameSpec::Source::YUV420_TENSOR) {
+    if (frameIn != SNN_IO_FLOAT || frameOut != SNN_IO_FLOAT || cp.frames.source == FrameSpec::Source::YUV420_TENSOR || cp.frames.sink == FrameSpec::Sink::YUV420_FROM_TENSOR) {
         auto* hb = dynamic_cast<dp::HipBackend*>(backend);
         SNN_CHK(hb && stages.back().stageOutputs.size() > 0);
         const ImageTexture& o = stages.back().stageOutputs[0];
@@ -136,6 +136,7 @@ snnhip_tensor* MixedInferenceCore::frameOutput() const { return frameBackend ? f
 snnhip_tensor* MixedInferenceCore::chromaInput() const { return frameBackend ? frameBackend->chromaInput() : nullptr; }
 snnhip_tensor* MixedInferenceCore::chromaOutput() const { return frameBackend ? frameBackend->chromaOutput() : nullptr; }
 bool MixedInferenceCore::planarVideo() const { return frameBackend && frameBackend->planarVideo(); }
+bool MixedInferenceCore::planarOutput() const { return frameBackend && frameBackend->planarOutput(); }
 bool MixedInferenceCore::encodeOutput() const { return frameBackend && frameBackend->encodeOutput(); }
 
 void MixedInferenceCore::run(RunParameters& rp) { // core.cpp:97-245

@@ -269,6 +269,41 @@ bool resolveFrames(const snn_video_tensor_io* io, int in_w, int in_h, int in_c, 
     return true;
 }
 
+// ---- snn_model_create15: the output tensor of an RGB(A) model to a 4:2:0 frame.  The model resolves as snn_model_create4's, through
+// snn_model_create5's struct with the 8-bit in_format and a float output, or through snn_model_create14's struct with a float output; only the sink
+// and the output stream are added
+bool resolveFrames(const snn_tensor_video_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* s) {
+    if (!io) return false;
+    auto video = [](int f) { return f == SNN_IO_NV12 || f == SNN_IO_NV12_16 || f == SNN_IO_I420 || f == SNN_IO_I420_16; };
+    if (!video(io->out_format)) return false;
+    const bool planar = io->out_format == SNN_IO_I420 || io->out_format == SNN_IO_I420_16, wide = io->out_format == SNN_IO_NV12_16 || io->out_format == SNN_IO_I420_16;
+    if (!knownSiting(io->siting) || !knownRange(io->range) || !rangedDepth(io->maxval) || !knownMatrix(io->kr, io->kb)) return false;
+    if (io->maxval > 4095 || !fitsContainer(io->maxval, io->shift, wide)) return false; // (as snn_model_create8)
+    if (io->in_format == SNN_IO_FLOAT) {
+        if (!resolveFrames(static_cast<const snn_frame_io*>(nullptr), in_w, in_h, in_c, batch, s)) return false;
+    } else if (video(io->in_format)) {
+        if (io->video_in.in_format != io->in_format || io->video_in.out_format != SNN_IO_FLOAT || !resolveFrames(&io->video_in, in_w, in_h, in_c, batch, s)) return false;
+    } else {
+        if (!frameOrFloat(io->in_format, false)) return false; // (the 8-bit formats only)
+        snn_frame_io f{io->in_format, SNN_IO_FLOAT, {0, 0, 0, 0}, {1, 1, 1, 1}, {1, 1, 1, 1}, {0, 0, 0, 0}};
+        memcpy(f.in_means, io->in_means, sizeof(f.in_means));
+        memcpy(f.in_norms, io->in_norms, sizeof(f.in_norms));
+        if (!resolveFrames(&f, in_w, in_h, in_c, batch, s)) return false;
+    }
+    s->sink = Sink::YUV420_FROM_TENSOR;
+    s->encWide = wide;
+    s->encPlanar = planar;
+    s->encMaxval = io->maxval;
+    s->encShift = io->shift;
+    s->encSiting = io->siting;
+    s->encRange = io->range;
+    s->encKr = io->kr;
+    s->encKb = io->kb;
+    for (int c = 0; c < 3; ++c) s->encScale[c] = io->out_scale[c], s->encOffset[c] = io->out_offset[c];
+    s->entry = "snn_model_create15";
+    return true;
+}
+
 bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int batch, FrameSpec* s) {
     if (!s || batch < 1 || in_w < 1 || in_h < 1 || in_c < 1) return false;
     *s = FrameSpec();
@@ -283,12 +318,19 @@ bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int 
     case 12: return resolveFrames(static_cast<const snn_planar_io*>(io), in_w, in_h, in_c, batch, s);
     case 13: return resolveFrames(static_cast<const snn_rgb_fit_io*>(io), in_w, in_h, in_c, batch, s);
     case 14: return resolveFrames(static_cast<const snn_video_tensor_io*>(io), in_w, in_h, in_c, batch, s);
+    case 15: return resolveFrames(static_cast<const snn_tensor_video_io*>(io), in_w, in_h, in_c, batch, s);
     default: return false;
     }
 }
 
 bool framesFitModel(const FrameSpec& spec, int in_w, int in_h, const InferenceGraph::IODesc& out) {
     if (spec.source == Source::MODEL && spec.sink == Sink::MODEL) return true;
+    if (spec.sink == Sink::YUV420_FROM_TENSOR) { // any model of 3 or 4 output channels and an even output extent: the frame starts in its output tensor
+        if ((out.channels == 3 || out.channels == 4) && evenExtent(static_cast<int>(out.width), static_cast<int>(out.height))) return true;
+        SNN_LOGE("%s: a 4:2:0 output frame needs a model of 3 or 4 output channels and an even output extent; this one gives %ux%ux%u", spec.entry, out.height, out.width,
+                 out.channels);
+        return false;
+    }
     if (spec.source == Source::YUV420_TENSOR) return true; // any model of 3 or 4 input channels: the frame ends in its input tensor
     // the model must be luma-only: one channel out, at 1..4 times the input's extent
     const uint32_t w = static_cast<uint32_t>(in_w), h = static_cast<uint32_t>(in_h), r = out.width / w;
@@ -317,9 +359,10 @@ bool framesFitModel(const FrameSpec& spec, int in_w, int in_h, const InferenceGr
 
 std::string formatFrameSpec(const FrameSpec& s) {
     static const char* const sources[] = {"model", "rgb", "yuv420", "yuv420_tensor"};
-    static const char* const sinks[] = {"model", "rgb_merged", "chroma_up", "fitted", "rgb_from_yuv", "yuv420_from_rgb", "rgb_from_yuv_fitted", "rgb_merged_fitted"};
+    static const char* const sinks[] = {"model", "rgb_merged", "chroma_up", "fitted", "rgb_from_yuv", "yuv420_from_rgb", "rgb_from_yuv_fitted", "rgb_merged_fitted",
+                                        "yuv420_from_tensor"};
     static_assert(sizeof(sources) / sizeof(*sources) == static_cast<size_t>(Source::YUV420_TENSOR) + 1, "one name for every FrameSpec::Source");
-    static_assert(sizeof(sinks) / sizeof(*sinks) == static_cast<size_t>(Sink::RGB_MERGED_FITTED) + 1, "one name for every FrameSpec::Sink");
+    static_assert(sizeof(sinks) / sizeof(*sinks) == static_cast<size_t>(Sink::YUV420_FROM_TENSOR) + 1, "one name for every FrameSpec::Sink");
     const snn_frame_io2& m = s.model;
     auto four = [](const float* v) { return formatString("%.9g,%.9g,%.9g,%.9g", v[0], v[1], v[2], v[3]); };
     // (the lines of snn_model_create5..13 stay as they were: what only snn_model_create14 sets is appended to its own line alone)
@@ -327,12 +370,18 @@ std::string formatFrameSpec(const FrameSpec& s) {
                                    ? std::string()
                                    : formatString(" | src=%dx%d filter=%d tensor_means=%.9g,%.9g,%.9g tensor_norms=%.9g,%.9g,%.9g alpha=%.9g", s.srcW, s.srcH, s.filter, s.tensorMeans[0],
                                                   s.tensorMeans[1], s.tensorMeans[2], s.tensorNorms[0], s.tensorNorms[1], s.tensorNorms[2], s.alpha);
+    // ... and what only snn_model_create15 sets to its own line alone
+    const std::string encode = s.sink != Sink::YUV420_FROM_TENSOR
+                                   ? std::string()
+                                   : formatString(" | encode wide=%d planar=%d maxval=%d shift=%d siting=%d range=%d kr=%.9g kb=%.9g enc_scale=%.9g,%.9g,%.9g enc_offset=%.9g,%.9g,%.9g",
+                                                  s.encWide ? 1 : 0, s.encPlanar ? 1 : 0, s.encMaxval, s.encShift, s.encSiting, s.encRange, s.encKr, s.encKb, s.encScale[0], s.encScale[1],
+                                                  s.encScale[2], s.encOffset[0], s.encOffset[1], s.encOffset[2]);
     return formatString("in=0x%x out=0x%x means=%s norms=%s scale=%s offset=%s in_shift=%d out_maxval=%d out_shift=%d", m.in_format, m.out_format, four(m.in_means).c_str(),
                         four(m.in_norms).c_str(), four(m.out_scale).c_str(), four(m.out_offset).c_str(), m.in_shift, m.out_maxval, m.out_shift) +
            formatString(" | source=%s sink=%s channels=%d wide=%d maxval=%d shift=%d siting=%d range=%d kr=%.9g kb=%.9g fit=%dx%d planar=%d | entry=%s",
                         sources[static_cast<int>(s.source)], sinks[static_cast<int>(s.sink)], s.channels, s.wide ? 1 : 0, s.maxval, s.shift, s.siting, s.range, s.kr, s.kb,
                         s.fitW, s.fitH, s.planar ? 1 : 0, s.entry) +
-           tensor;
+           tensor + encode;
 }
 
 } // namespace snn

@@ -107,7 +107,7 @@ void HipBackend::initFrames(const FrameSpec& f, int n, int inH, int inW, int inC
     if (f.source == Source::MODEL && f.sink == Sink::MODEL) return;
     if (f.source == Source::YUV420_TENSOR) { // a 4:2:0 frame of any even size straight into the model's own (float) input tensor: one launch in front
         const int sd = f.wide ? SNNHIP_U16 : SNNHIP_U8;
-        planarChroma = f.planar;
+        planarChroma = planarChromaOut = f.planar;
         uploadT = ownTensor(n, f.srcH, f.srcW, 1, sd, "snnhip_tensor_alloc (luma input plane)");
         chromaInT = ownTensor(f.planar ? 2 * n : n, f.srcH / 2, f.srcW / 2, f.planar ? 1 : 2, sd, "snnhip_tensor_alloc (chroma input plane)");
         snnhip_yuv_tensor_desc d{n, f.srcH, f.srcW, inH, inW, inC, sd, dtype, f.maxval, f.shift, f.siting, f.range, f.kr, f.kb, f.filter,
@@ -116,8 +116,21 @@ void HipBackend::initFrames(const FrameSpec& f, int n, int inH, int inW, int inC
         if (f.planar) hipChk(snnhip_yuv_tensor_planar_plan_create(ctx, &d, &p), "snnhip_yuv_tensor_planar_plan_create");
         else hipChk(snnhip_yuv_tensor_plan_create(ctx, &d, &p), "snnhip_yuv_tensor_plan_create");
         stepsIn.push_back({p, uploadT, chromaInT, nullptr, "[yuv tensor]", "snnhip_plan_run_n (video frame -> input tensor)"}); // out: the model's input tensor, bound at run
-        return;
     }
+    if (f.sink == Sink::YUV420_FROM_TENSOR) { // the model's own (float) output tensor straight to the planes of a 4:2:0 frame of its extent: one launch behind
+        const int ed = f.encWide ? SNNHIP_U16 : SNNHIP_U8;
+        planarChromaOut = f.encPlanar;
+        lumaChromaFromTensor = true;
+        downloadT = ownTensor(n, outH, outW, 1, ed, "snnhip_tensor_alloc (luma output plane)");
+        chromaOutT = ownTensor(f.encPlanar ? 2 * n : n, outH / 2, outW / 2, f.encPlanar ? 1 : 2, ed, "snnhip_tensor_alloc (chroma output plane)");
+        snnhip_tensor_yuv_desc d{n, outH, outW, outC, dtype, ed, f.encMaxval, f.encShift, f.encSiting, f.encRange, f.encKr, f.encKb,
+                                 {f.encScale[0], f.encScale[1], f.encScale[2]}, {f.encOffset[0], f.encOffset[1], f.encOffset[2]}};
+        snnhip_plan* p = nullptr;
+        if (f.encPlanar) hipChk(snnhip_tensor_yuv_planar_plan_create(ctx, &d, &p), "snnhip_tensor_yuv_planar_plan_create");
+        else hipChk(snnhip_tensor_yuv_plan_create(ctx, &d, &p), "snnhip_tensor_yuv_plan_create");
+        stepsOut.push_back({p, nullptr, nullptr, downloadT, "[tensor yuv]", "snnhip_plan_run_io (output tensor -> video frame)", chromaOutT}); // in: the model's output tensor, bound at run
+    }
+    if (f.source == Source::YUV420_TENSOR || f.sink == Sink::YUV420_FROM_TENSOR) return;
 
     // colour or video frames around a luma-only model: the luma plane IS the model's frame at a video end
     const int vd = f.wide ? SNNHIP_U16 : SNNHIP_U8;
@@ -125,7 +138,7 @@ void HipBackend::initFrames(const FrameSpec& f, int n, int inH, int inW, int inC
     int in[4], out[4];
     const int r = frameScale(frameInT, frameOutT, f.source == Source::YUV420, in, out);
     const int cc = f.planar ? 1 : 2, cn = f.planar ? 2 * in[0] : in[0]; // planar: every Cb and Cr plane is an image of one channel
-    planarChroma = f.planar;
+    planarChroma = planarChromaOut = f.planar;
     snnhip_plan* p = nullptr;
     if (f.source == Source::RGB) { // the colour frame's luma plane into the model's input frame
         snnhip_rgb_luma_desc d{in[0], in[1], in[2], f.channels, f.kr, f.kb};
@@ -206,11 +219,16 @@ std::string HipBackend::describeFrames() const {
     return s;
 }
 
-void HipBackend::runSteps(const std::vector<FrameStep>& steps, snnhip_tensor* modelInput) {
+void HipBackend::runSteps(const std::vector<FrameStep>& steps, snnhip_tensor* modelInput, const snnhip_tensor* modelOutput) {
     for (auto& s : steps) {
-        const snnhip_tensor* ins[2] = {s.in0, s.in1};
+        const snnhip_tensor* ins[2] = {s.in0 ? s.in0 : modelOutput, s.in1}; // (a step without an input of its own reads the model's output tensor)
         snnhip_tensor* out = s.out ? s.out : modelInput; // (a step without a tensor of its own writes the model's input tensor)
-        hipChk(s.in1 ? snnhip_plan_run_n(s.plan, ins, 2, out) : snnhip_plan_run(s.plan, s.in0, out), s.what);
+        if (s.out1) { // two outputs
+            snnhip_tensor* outs[2] = {out, s.out1};
+            hipChk(snnhip_plan_run_io(s.plan, ins, s.in1 ? 2 : 1, outs, 2), s.what);
+        } else {
+            hipChk(s.in1 ? snnhip_plan_run_n(s.plan, ins, 2, out) : snnhip_plan_run(s.plan, ins[0], out), s.what);
+        }
     }
 }
 
@@ -221,7 +239,7 @@ void HipBackend::runFrameIn(const ImageTexture& modelInput) {
 
 void HipBackend::runFrameOut(const ImageTexture& lastOutput) {
     if (frameOutPlan && !frameOutFused) hipChk(snnhip_plan_run(frameOutPlan, lastOutput.tensor(), frameOutT), "snnhip_plan_run (frame out)");
-    runSteps(stepsOut);
+    runSteps(stepsOut, nullptr, lastOutput.tensor());
 }
 
 // counterpart of VulkanBackend::initRenderPasses -> VulkanRenderPass ctor (vulkanBackend.cpp:43-78, vulkanRenderpass.cpp:103-178):

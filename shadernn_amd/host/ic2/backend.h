@@ -122,7 +122,8 @@ public:
     int frameLaunches() const { return static_cast<int>(stepsIn.size() + stepsOut.size()); }
     std::string describeFrames() const; // one line for every step: "<label> <the plan's description>"
     bool planarVideo() const { return planarChroma; }
-    bool encodeOutput() const { return lumaChromaFromRgb; }
+    bool planarOutput() const { return planarChromaOut; }
+    bool encodeOutput() const { return lumaChromaFromRgb || lumaChromaFromTensor; }
     // the tensors the caller moves frames through, by role (null: no such end)
     snnhip_tensor* frameInput() const { return uploadT; }
     snnhip_tensor* frameOutput() const { return downloadT; }
@@ -130,22 +131,25 @@ public:
     snnhip_tensor* chromaOutput() const { return chromaOutT; }
 
 private:
-    // one launch in front of or behind the model: plan (owned) from in0 (and in1) to out, all three among frameTensors
+    // one launch in front of or behind the model: plan (owned) from in0 (and in1) to out (and out1), all among frameTensors
     struct FrameStep {
         snnhip_plan* plan;
-        const snnhip_tensor *in0, *in1;
+        const snnhip_tensor *in0, *in1; // (in0 null: the model's own output tensor, known when the inference runs)
         snnhip_tensor* out; // (null: the model's own input tensor, known when the inference runs)
         const char *label, *what; // the bracketed name of describe(); what a failed launch is reported as
+        snnhip_tensor* out1 = nullptr; // a second output: the step runs through snnhip_plan_run_io (the chroma of [tensor yuv])
     };
     snnhip_tensor* ownTensor(int n, int h, int w, int c, int dtype, const char* what);
-    static void runSteps(const std::vector<FrameStep>& steps, snnhip_tensor* modelInput = nullptr);
+    static void runSteps(const std::vector<FrameStep>& steps, snnhip_tensor* modelInput = nullptr, const snnhip_tensor* modelOutput = nullptr);
     snnhip_plan *frameInPlan = nullptr, *frameOutPlan = nullptr; // owned: the model's own conversions, nodes of the fusion graph (finalizeStages)
     snnhip_tensor *frameInT = nullptr, *frameOutT = nullptr;      // the model's own frames, SNNHIP_U8 or SNNHIP_U16
     bool frameInFused = false, frameOutFused = false;
     std::vector<FrameStep> stepsIn, stepsOut;
     std::vector<snnhip_tensor*> frameTensors; // owned: every frame tensor
     snnhip_tensor *uploadT = nullptr, *downloadT = nullptr, *chromaInT = nullptr, *chromaOutT = nullptr; // by role, among frameTensors
-    bool planarChroma = false;      // chromaInT / chromaOutT are [2n][h][w][1]
+    bool planarChroma = false;      // chromaInT (and, but for [tensor yuv], chromaOutT) are [2n][h][w][1]
+    bool planarChromaOut = false;   // chromaOutT is [2n][h][w][1]: planarChroma's value, or the output stream's own behind [tensor yuv]
+    bool lumaChromaFromTensor = false; // downloadT is the luma plane and chromaOutT the chroma of a 4:2:0 frame made from the model's output tensor
     bool lumaChromaFromRgb = false; // downloadT is the luma plane and chromaOutT the chroma plane of a 4:2:0 frame made from RGB
     snnhip_ctx* ctx;
     std::vector<snnhip_plan*> chainPlans; // owned

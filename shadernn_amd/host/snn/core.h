@@ -89,7 +89,8 @@ public:
     snnhip_tensor* chromaInput() const; // the CbCr planes of a video model (snn_model_create8), null otherwise
     snnhip_tensor* chromaOutput() const;
     bool planarVideo() const;  // the chroma tensors are planar [2 * batch][h][w][1] (snn_model_create12)
-    bool encodeOutput() const; // the output is the NV12 frame of snn_model_create10: frameOutput() its luma plane, chromaOutput() its CbCr plane
+    bool planarOutput() const; // ... the output's: planarVideo(), or the output stream's own layout behind [tensor yuv] (snn_model_create15)
+    bool encodeOutput() const; // the output is the 4:2:0 frame of snn_model_create10 / 15: frameOutput() its luma plane, chromaOutput() its chroma
     const FrameSpec& frames() const { return cp.frames; } // the resolved description the model was built from (snn_model_reference_frame reads the output's depth)
 
 private:

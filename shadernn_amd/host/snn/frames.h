@@ -1,5 +1,5 @@
 // snn/frames.h -- the resolved description of a model's frame ends (HIP extension; device-free: nothing here touches the GPU).  Every
-// snn_model_create5..14 struct of include/snn_c.h resolves to ONE FrameSpec, and everything below the entry points -- createModel,
+// snn_model_create5..15 struct of include/snn_c.h resolves to ONE FrameSpec, and everything below the entry points -- createModel,
 // MixedInferenceCore::CreationParameters, HipBackend::initFrames -- takes that one description.
 #pragma once
 #include <string>
@@ -16,8 +16,9 @@ struct FrameSpec {
     // an RGB(A) model (one launch into the model's float input tensor: snn_model_create14)
     enum class Source { MODEL, RGB, YUV420, YUV420_TENSOR } source = Source::MODEL;
     // what comes back: the model's frame, the merged RGB frame, luma + r-fold chroma, luma + chroma fitted to fitW x fitH, RGB from luma + chroma, luma + chroma from RGB,
-    // and the two RGB frames at fitW x fitH: from luma + chroma, merged with the colour frame that went in
-    enum class Sink { MODEL, RGB_MERGED, CHROMA_UP, FITTED, RGB_FROM_YUV, YUV420_FROM_RGB, RGB_FROM_YUV_FITTED, RGB_MERGED_FITTED } sink = Sink::MODEL;
+    // the two RGB frames at fitW x fitH: from luma + chroma, merged with the colour frame that went in; and luma + 4:2:0 chroma of the model's own
+    // extent from the output tensor of an RGB(A) model (one launch behind the model's last stage: snn_model_create15)
+    enum class Sink { MODEL, RGB_MERGED, CHROMA_UP, FITTED, RGB_FROM_YUV, YUV420_FROM_RGB, RGB_FROM_YUV_FITTED, RGB_MERGED_FITTED, YUV420_FROM_TENSOR } sink = Sink::MODEL;
     int channels = 0;                                  // of the RGB end(s): 3 or 4
     bool wide = false;                                 // the video end's samples sit in 2-byte containers
     int maxval = 255, shift = 0;                       // ... with this depth and alignment (the chroma planes'; the luma plane's are model's)
@@ -27,6 +28,11 @@ struct FrameSpec {
     bool planar = false;                               // the chroma planes are separate Cb and Cr planes (I420 / I010), not one interleaved CbCr plane
     int srcW = 0, srcH = 0, filter = SNN_FILTER_LINEAR; // Source::YUV420_TENSOR: the frame's extent, the sampler,
     float tensorMeans[3] = {0, 0, 0}, tensorNorms[3] = {1, 1, 1}, alpha = 1.0f; // ... and the normalisation of the input tensor
+    // Sink::YUV420_FROM_TENSOR: the OUTPUT stream (the fields above stay the input end's: a video frame in front fills them as snn_model_create14 does)
+    bool encWide = false, encPlanar = false;
+    int encMaxval = 255, encShift = 0, encSiting = SNN_SITING_LEFT, encRange = SNN_RANGE_LIMITED;
+    float encKr = 0.299f, encKb = 0.114f;
+    float encScale[3] = {1, 1, 1}, encOffset[3] = {0, 0, 0}; // the output map: p = clamp(x * scale + offset, 0, encMaxval)
     const char* entry = "snn_model_create5";           // the entry point the request came through (log lines name it)
 };
 
@@ -41,12 +47,13 @@ bool resolveFrames(const snn_fit_io* io, int in_w, int in_h, int in_c, int batch
 bool resolveFrames(const snn_planar_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 bool resolveFrames(const snn_rgb_fit_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 bool resolveFrames(const snn_video_tensor_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
-// ... by the number of the entry point, 5..14 (`io` is that entry point's struct)
+bool resolveFrames(const snn_tensor_video_io* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
+// ... by the number of the entry point, 5..15 (`io` is that entry point's struct)
 bool resolveFrames(int entry, const void* io, int in_w, int in_h, int in_c, int batch, FrameSpec* spec);
 
 // The rules that need the model's factor r, from the output desc of its last layer: a frame path around the model needs one channel out at r = 1..4
 // times the input on both axes; luma + chroma from RGB r >= 2 and an even r * extent; a fitted size lies within [r * in / 2, r * in], and is
-// no smaller than the colour frame that went in (logged).
+// no smaller than the colour frame that went in (logged); luma + chroma from the output tensor needs 3 or 4 channels out and an even extent (logged).
 bool framesFitModel(const FrameSpec& spec, int in_w, int in_h, const InferenceGraph::IODesc& out);
 
 ColorFormat frameColorFormat(int snnIoFormat); // SNN_IO_R8 .. SNN_IO_RGBA16 -> ColorFormat (NONE for SNN_IO_FLOAT and anything else)

@@ -195,6 +195,18 @@ int snn_model_create14(const char* json_path, int device, int in_w, int in_h, in
     return create({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, 14, io);
 }
 
+int snn_model_create15(const char* json_path, int device, int in_w, int in_h, int in_c, int dump_outputs, int fuse_chains, int profiling,
+                       int prefer_half, int capture_graph, int batch, const snn_tensor_video_io* io, snn_model** out) {
+    FrameSpec spec;
+    if (!resolveFrames(15, io, in_w, in_h, in_c, batch, &spec)) { // (what the model file decides is framesFitModel's to refuse and to log)
+        if (!io) SNN_LOGE("snn_model_create15: null struct");
+        else SNN_LOGE("snn_model_create15: the request was refused (formats 0x%x -> 0x%x, maxval %d, shift %d, siting %d, range %d, kr %g, kb %g, input %dx%dx%d, batch %d)",
+                      io->in_format, io->out_format, io->maxval, io->shift, io->siting, io->range, io->kr, io->kb, in_w, in_h, in_c, batch);
+        return -1;
+    }
+    return createModel({json_path, device, in_w, in_h, in_c, dump_outputs, fuse_chains, profiling, prefer_half, capture_graph, batch, out}, spec);
+}
+
 // one plane of every frame between the caller's interleaved frames and a contiguous device tensor; `stride` and `offset` in bytes within a frame
 static int movePlane(snnhip_tensor* t, int batch, char* frames, size_t stride, size_t offset, bool upload) {
     const size_t total = snnhip_tensor_bytes(t), plane = total / static_cast<size_t>(batch);
@@ -213,7 +225,7 @@ static int moveVideoFrames(snn_model* m, void* frames, bool upload) {
     if (!m || !frames || !m->core) return -1;
     snnhip_tensor* y = upload ? m->core->frameInput() : m->core->frameOutput();
     snnhip_tensor* c = upload ? m->core->chromaInput() : m->core->chromaOutput();
-    if (!y || !c || m->core->planarVideo()) return -1; // (planar ends: snn_model_upload_frame_planes / _download_frame_planes)
+    if (!y || !c || (upload ? m->core->planarVideo() : m->core->planarOutput())) return -1; // (planar ends: snn_model_upload_frame_planes / _download_frame_planes)
     const size_t yb = snnhip_tensor_bytes(y) / static_cast<size_t>(m->batch), cb = snnhip_tensor_bytes(c) / static_cast<size_t>(m->batch);
     char* p = static_cast<char*>(frames);
     if (movePlane(y, m->batch, p, yb + cb, 0, upload) != 0) return -1;
@@ -240,9 +252,8 @@ static int movePieces(snn_model* m, snnhip_tensor* t, const std::vector<char*>& 
 }
 
 // ... between the caller's planes and the luma tensor y and chroma tensor c of one end of the model (or the reference tensors of that extent)
-static int movePlanesOf(snn_model* m, snnhip_tensor* y, snnhip_tensor* c, void* const* planes, const int* pitch, int n_planes, bool upload) {
+static int movePlanesOf(snn_model* m, snnhip_tensor* y, snnhip_tensor* c, void* const* planes, const int* pitch, int n_planes, bool upload, bool planar) {
     if (!y || !c) return -1; // an RGB end, or no video frames at all
-    const bool planar = m->core->planarVideo();
     if (n_planes != (planar ? 3 : 2)) return -1;
     int yd[4], cd[4];
     if (snnhip_tensor_dims(y, yd) != SNNHIP_OK || snnhip_tensor_dims(c, cd) != SNNHIP_OK || yd[0] != m->batch || yd[3] != 1) return -1;
@@ -273,7 +284,8 @@ static int movePlanesOf(snn_model* m, snnhip_tensor* y, snnhip_tensor* c, void* 
 
 static int moveFramePlanes(snn_model* m, void* const* planes, const int* pitch, int n_planes, bool upload) {
     if (!m || !planes || !pitch || !m->core) return -1;
-    return movePlanesOf(m, upload ? m->core->frameInput() : m->core->frameOutput(), upload ? m->core->chromaInput() : m->core->chromaOutput(), planes, pitch, n_planes, upload);
+    return movePlanesOf(m, upload ? m->core->frameInput() : m->core->frameOutput(), upload ? m->core->chromaInput() : m->core->chromaOutput(), planes, pitch, n_planes, upload,
+                        upload ? m->core->planarVideo() : m->core->planarOutput());
 }
 
 int snn_model_upload_frame_planes(snn_model* m, const void* const* planes, const int* pitch_bytes, int n_planes) {
@@ -325,6 +337,7 @@ int snn_model_upload_frame_u16(snn_model* m, const unsigned short* nhwc) {
 int snn_model_download_frame_u16(snn_model* m, unsigned short* nhwc) {
     snnhip_tensor* t = m && nhwc ? m->core->frameOutput() : nullptr;
     if (!t || snnhip_tensor_dtype(t) != SNNHIP_U16) return -1;
+    if (m->core->frames().sink == FrameSpec::Sink::YUV420_FROM_TENSOR) return -1; // (a P010 / I010 frame of snn_model_create15: snn_model_download_frame_nv12 / _planes)
     return snnhip_tensor_download_raw(t, nhwc, snnhip_tensor_bytes(t)) == SNNHIP_OK ? 0 : -1;
 }
 
@@ -357,9 +370,11 @@ static bool ensureMetrics(snn_model* m, const char* who) {
     const FrameSpec& f = m->core->frames();
     // the depth of the output frame: the video end's for an RGB frame made from it, otherwise the model's own output map (the luma plane's on a video end)
     const bool fromVideo = f.sink == FrameSpec::Sink::RGB_FROM_YUV || f.sink == FrameSpec::Sink::RGB_FROM_YUV_FITTED;
-    if (makeMetricsEnd(ctx, y, fromVideo ? f.maxval : f.model.out_maxval, fromVideo ? f.shift : f.model.out_shift, &m->metricsFrame) != 0) return false;
+    const bool encoded = f.sink == FrameSpec::Sink::YUV420_FROM_TENSOR; // both planes have the output stream's own depth
+    const int lumaMaxval = encoded ? f.encMaxval : fromVideo ? f.maxval : f.model.out_maxval, lumaShift = encoded ? f.encShift : fromVideo ? f.shift : f.model.out_shift;
+    if (makeMetricsEnd(ctx, y, lumaMaxval, lumaShift, &m->metricsFrame) != 0) return false;
     snnhip_tensor* c = m->core->chromaOutput();
-    if (c && makeMetricsEnd(ctx, c, f.maxval, f.shift, &m->metricsChroma) != 0) {
+    if (c && makeMetricsEnd(ctx, c, encoded ? f.encMaxval : f.maxval, encoded ? f.encShift : f.shift, &m->metricsChroma) != 0) {
         freeMetrics(m->metricsFrame);
         return false;
     }
@@ -376,7 +391,7 @@ int snn_model_reference_frame(snn_model* m, const void* frame) {
         snnhip_tensor* y = m->metricsFrame.ref;
         snnhip_tensor* c = m->metricsChroma.ref;
         if (!c) return snnhip_tensor_upload_raw(y, frame, snnhip_tensor_bytes(y)) == SNNHIP_OK ? (m->referenceSet = true, 0) : -1;
-        if (m->core->planarVideo()) {
+        if (m->core->planarOutput()) {
             SNN_LOGE("snn_model_reference_frame: a planar output takes its reference through snn_model_reference_frame_planes, as it is downloaded");
             return -1;
         }
@@ -398,7 +413,7 @@ int snn_model_reference_frame_planes(snn_model* m, const void* const* planes, co
     }
     try {
         if (!ensureMetrics(m, "snn_model_reference_frame_planes")) return -1;
-        const int rc = movePlanesOf(m, m->metricsFrame.ref, m->metricsChroma.ref, const_cast<void* const*>(planes), pitch_bytes, n_planes, true);
+        const int rc = movePlanesOf(m, m->metricsFrame.ref, m->metricsChroma.ref, const_cast<void* const*>(planes), pitch_bytes, n_planes, true, m->core->planarOutput());
         if (rc == 0) m->referenceSet = true;
         return rc;
     } catch (...) {
@@ -440,7 +455,7 @@ int snn_model_frame_metrics(snn_model* m, snn_frame_metrics* rows, int max_rows)
         }
         // image-major: the frame's (or luma plane's) channels, then the chroma plane's channels (interleaved: one plane, two channels; planar: plane
         // 2n is Cb and 2n + 1 Cr of image n, one channel each)
-        const bool planar = m->core->planarVideo();
+        const bool planar = m->core->planarOutput();
         int n = 0;
         auto put = [&](int image, int plane, int channel, const snnhip_frame_metrics_row& r, int maxval) {
             if (n < max_rows) rows[n] = snn_frame_metrics{image, plane, channel, r.sse, r.pixels, snnhip_frame_metrics_psnr(r.sse, r.pixels, maxval),
@@ -563,6 +578,7 @@ snnhip_ctx* snn_model_hip_ctx(snn_model* m) {
 snnhip_tensor* snn_model_output_tensor(snn_model* m) { return lastOutput(m).tensor(); }
 
 int snn_model_download_output(snn_model* m, float* nhwc) {
+    if (m->core->frames().sink == FrameSpec::Sink::YUV420_FROM_TENSOR) return -1; // (the frame comes back: snn_model_download_frame_nv12 / _planes)
     lastOutput(m).downloadNHWC(nhwc);
     return 0;
 }

@@ -1577,6 +1577,123 @@ def main_yuv_tensor(a):
     ctx.close()
 
 
+def main_tensor_yuv(a):
+    """--encode NV12 | P010 | I420 [--half] [--batch N] [--h --w]: encoder frames behind an RGB model.  The tensor_yuv launch alone (a 0 .. 255 tensor of
+    --h x --w x 3, 720p by default, to the frame's planes), a device copy of the launch's own bytes and the u8_out launch of the same tensor (the only
+    device-side 8-bit end there was), in one process, alternated in mirrored order: device-event medians with spreads.  Then end to end with one
+    frame's download, host clock: the launch + the planes (1.5 bytes per pixel, 3 for P010) against u8_out + the RGB8 frame and against the float
+    tensor alone."""
+    import ctypes
+    import time
+
+    import shadernn_amd as snn
+    from shadernn_amd import capi
+
+    snn.load_library()
+    ctx = capi.Context(0)
+    H, W, N, Cc = a.h or 720, a.w or 1280, a.batch, 3
+    assert H % 2 == 0 and W % 2 == 0, "4:2:0 frames have even extents"
+    planar, wide = a.encode == "I420", a.encode == "P010"
+    dt, maxval, shift = (capi.U16, 1023, 6) if wide else (capi.U8, 255, 0)
+    idt = capi.F16 if a.half else capi.F32
+    rng = np.random.default_rng(1)
+    src = capi.Tensor.from_numpy(ctx, rng.uniform(-10.0, 265.0, size=(N, H, W, Cc)).astype(np.float32), dtype=idt)
+    scale = (maxval / 255.0,) * 3
+    plan = capi.tensor_yuv_plan(ctx, N, H, W, Cc, idt, dt, maxval, shift, a.siting, a.range, scale=scale, planar=planar)
+    luma = capi.Tensor(ctx, N, H, W, 1, dtype=dt)
+    chroma = capi.Tensor(ctx, 2 * N if planar else N, H // 2, W // 2, 1 if planar else 2, dtype=dt)
+    u8 = capi.u8_out_plan(ctx, N, H, W, Cc, dtype=idt)
+    rgb8 = capi.Tensor(ctx, N, H, W, Cc, dtype=capi.U8)
+    forms = {"tensor_yuv": lambda: plan.run_io([src], [luma, chroma]), "u8_out": lambda: u8.run(src, rgb8)}
+    steps = {"tensor_yuv": [plan.describe()], "u8_out": [u8.describe()]}
+    new_bytes = int(plan.cost()[1])
+    hip = _hip_runtime()
+    hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    stream = ctx.stream()
+    half_bytes = new_bytes // 2  # a copy of n bytes reads n and writes n: the launch's bytes, read + written, are 2 n
+    csrc, cdst = capi.Tensor(ctx, 1, 1, half_bytes, 1, dtype=capi.U8), capi.Tensor(ctx, 1, 1, half_bytes, 1, dtype=capi.U8)
+
+    def run_copy():
+        rc = hip.hipMemcpyDtoDAsync(cdst.data_ptr(), csrc.data_ptr(), half_bytes, stream)
+        assert rc == 0, rc
+
+    forms["copy"] = run_copy
+    for fn in forms.values():
+        for _ in range(a.warmup):
+            fn()
+    ctx.sync()
+    timer = capi.Timer(ctx)
+    dev = {name: [] for name in forms}
+    for _ in range(a.rounds):
+        for name in list(forms) + list(forms)[::-1]:  # mirrored, device events around `iters` enqueued runs
+            timer.start()
+            for _ in range(a.iters):
+                forms[name]()
+            timer.stop()
+            dev[name].append(timer.elapsed_ms() / a.iters)
+
+    def stat(v):
+        m = statistics.median(v)
+        return {"ms_median": round(m, 5), "ms_min": round(min(v), 5), "ms_max": round(max(v), 5), "spread": round((max(v) - min(v)) / m, 4)}
+
+    out = {"encode": a.encode, "tensor": "%dx%dx%d %s" % (H, W, Cc, "f16" if a.half else "f32"), "batch": N, "siting": a.siting, "range": a.range, "rounds": a.rounds, "iters": a.iters,
+           "timing": "device events around iters enqueued runs, the forms alternated in mirrored order", "steps": steps}
+    for name in forms:
+        out[name] = stat(dev[name])
+    out["tensor_yuv"]["hbm_bytes"] = new_bytes
+    out["tensor_yuv"]["tbs"] = round(new_bytes / (out["tensor_yuv"]["ms_median"] * 1e-3) / 1e12, 3)
+    out["copy"]["hbm_bytes"] = 2 * half_bytes
+    out["copy"]["tbs"] = round(2 * half_bytes / (out["copy"]["ms_median"] * 1e-3) / 1e12, 3)
+    out["u8_out"]["hbm_bytes"] = int(u8.cost()[1])
+    out["u8_out"]["tbs"] = round(out["u8_out"]["hbm_bytes"] / (out["u8_out"]["ms_median"] * 1e-3) / 1e12, 3)
+    out["tensor_yuv_rate_over_copy_rate"] = round(out["tensor_yuv"]["tbs"] / out["copy"]["tbs"], 3)  # a finding, not a gate: the launch's rate as a share of a device copy's
+    out["tensor_yuv_over_u8_out"] = round(out["tensor_yuv"]["ms_median"] / out["u8_out"]["ms_median"], 3)
+
+    # ---- end to end with one frame's download (pageable host memory, the host clock around launch + download; the download waits for the launch)
+    def frame_yuv():
+        plan.run_io([src], [luma, chroma])
+        return (luma.numpy_u16(), chroma.numpy_u16()) if wide else (luma.numpy_u8(), chroma.numpy_u8())
+
+    def frame_rgb8():
+        u8.run(src, rgb8)
+        return rgb8.numpy_u8()
+
+    ends = {"tensor_yuv_and_planes": frame_yuv, "u8_out_and_rgb8": frame_rgb8, "float_tensor": src.numpy}
+    for fn in ends.values():
+        fn()
+    host = {name: [] for name in ends}
+    for _ in range(a.rounds):
+        for name in list(ends) + list(ends)[::-1]:
+            ctx.sync()
+            t0 = time.perf_counter()
+            ends[name]()
+            host[name].append((time.perf_counter() - t0) * 1e3)
+    es = np.dtype(np.uint16 if wide else np.uint8).itemsize
+    d2h = {"tensor_yuv_and_planes": N * H * W * 3 // 2 * es, "u8_out_and_rgb8": N * H * W * Cc, "float_tensor": N * H * W * Cc * 4}  # (a half tensor downloads as floats)
+    out["end_to_end"] = {"timing": "host clock around the launch and one download into pageable memory, alternated in mirrored order"}
+    for name in ends:
+        out["end_to_end"][name] = dict(stat(host[name]), d2h_bytes=d2h[name])
+    out["end_to_end"]["planes_over_rgb8"] = round(out["end_to_end"]["tensor_yuv_and_planes"]["ms_median"] / out["end_to_end"]["u8_out_and_rgb8"]["ms_median"], 3)
+    out["end_to_end"]["planes_over_float"] = round(out["end_to_end"]["tensor_yuv_and_planes"]["ms_median"] / out["end_to_end"]["float_tensor"]["ms_median"], 3)
+    capi.trace_begin()
+    for _ in range(a.iters):
+        forms["tensor_yuv"]()
+    ctx.sync()
+    rep = capi.trace_end()
+    kernels = rep.get("kernels", rep) if isinstance(rep, dict) else rep
+    out["kernels"] = [{"function": it.get("function"), "launches": it.get("launches", 0),
+                       "us_per_launch": round(1e3 * it.get("total_ms", it.get("ms", 0.0)) / max(it.get("launches", 0), 1), 2)} for it in kernels]
+    print(json.dumps(out, indent=1))
+    if a.out:
+        rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        rec["%s_%dx%dx%d_%s_b%d" % (a.encode.lower(), W, H, Cc, "f16" if a.half else "f32", N)] = out
+        with open(a.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--half", action="store_true", help="the fp16 forms: fused fp32, per-layer fp16, fused fp16 (SNNHIP_ESPCN_F16=1), fused fp16 with 8-bit ends")
@@ -1595,7 +1712,9 @@ def main():
                     "(the chain, the luma fit, rgb_fit) beside the r-fold RGB step of the same r; --out merges the record into a JSON file")
     ap.add_argument("--tensor", default=None, metavar="WxH", help="with --video NV12 | P010 | I420 alone: video in front of an RGB(A) model -- the yuv_tensor launch from a frame of "
                     "--h x --w (1080p by default) to the WxH x 4 input tensor (fp16 with --half), the three launches it replaces and a device copy of its bytes")
-    ap.add_argument("--batch", type=int, default=1, help="with --tensor: frames per launch")
+    ap.add_argument("--encode", choices=["NV12", "P010", "I420"], default=None, help="alone: encoder frames behind an RGB model -- the tensor_yuv launch from a --h x --w x 3 tensor "
+                    "(720p by default, fp16 with --half), a device copy of its bytes, the u8_out launch of the same tensor, and end to end with one frame's download")
+    ap.add_argument("--batch", type=int, default=1, help="with --tensor / --encode: frames per launch")
     ap.add_argument("--range", choices=["limited", "full"], default="limited", help="the stream's range with --video-out")
     ap.add_argument("--siting", choices=["left", "centre"], default="left", help="horizontal chroma siting of --video")
     ap.add_argument("--per-layer", action="store_true", help="also time the per-layer forms (always on for --scale 3 / 4)")
@@ -1609,6 +1728,9 @@ def main():
     a = ap.parse_args()
     if a.metrics:
         return main_metrics(a)
+    if a.encode:
+        assert not a.video and not a.video_out and not a.colour and not a.fit and not a.rgb_fit and not a.tensor, "--encode goes alone (with --half, --batch, --h, --w, --siting, --range)"
+        return main_tensor_yuv(a)
     if a.tensor:
         assert a.video in ("NV12", "P010", "I420") and not a.video_out and not a.colour and not a.fit and not a.rgb_fit, "--tensor goes with --video NV12 | P010 | I420 alone"
         return main_yuv_tensor(a)
