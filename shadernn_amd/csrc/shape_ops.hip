@@ -6,6 +6,7 @@
 // Replaces (reference): shadertemplate_vk_concat.comp:39-52 + concatenationVulkan.cpp:31-88, shadertemplate_vk_unary.comp:40-90 +
 // unaryVulkan.cpp:30-83, shadertemplate_cs_4x_deconv_2s_RGBA.glsl:150-195 + deconv2dGL.cpp:282-355, shadertemplate_fs_calculation.glsl:25-41,
 // shadertemplate_vk_resize.comp:41-62 + imageTextureVulkan.cpp:137-183, image.cpp:712-796 (norm2rgba32f), core.cpp:228-234 (argmax).
+#include "deconv2d_mfma.h"
 #include "epilogue.h"
 #include "plan_util.h"
 #include "snnhip_internal.h"
@@ -448,6 +449,22 @@ int snnhip_deconv2d_plan_create(snnhip_ctx* ctx, const snnhip_conv2d_desc* desc,
                    "deconv2d desc: activation id %d (deconv2dGL.cpp:198-207 knows relu, tanh, sigmoid, leakyRelu)", desc->act);
     if (desc->useBN) SNNHIP_REQUIRE(bn_beta && bn_gamma && bn_mean && bn_var, "deconv2d_plan_create: useBN set but a BN array is null");
     SNNHIP_CHECK_HIP(hipSetDevice(ctx->device));
+    {   // SNNHIP_DECONV=direct|mfma: an eligible shape takes the matrix-core kernel (deconv2d_mfma.hip) unless "direct" pins the kernel below
+        DeconvGeom dg;
+        dg.N = desc->N; dg.H = desc->H; dg.W = desc->W; dg.IC = desc->IC; dg.OC = desc->OC; dg.k = desc->kh; dg.s = desc->sh; dg.p = desc->padT;
+        dg.OH = desc->OH > 0 ? desc->OH : desc->sh * desc->H;
+        dg.OW = desc->OW > 0 ? desc->OW : desc->sw * desc->W;
+        dg.act = desc->act; dg.useBN = desc->useBN ? 1 : 0; dg.leaky = desc->leaky;
+        const char* sw = snnhip::option("SNNHIP_DECONV");
+        SNNHIP_REQUIRE(!sw || !*sw || !strcmp(sw, "direct") || !strcmp(sw, "mfma"), "SNNHIP_DECONV=%s: expected direct or mfma", sw);
+        // the crossover: while the direct kernel's threads (one per pixel x 4 channels) all fit the device at once and each
+        // adds at most 128 terms per channel, it is at its launch floor and 2 - 9 us ahead in fp32; "mfma" overrides
+        const int tapsPerPhase = up_div(dg.k, dg.s) * up_div(dg.k, dg.s);
+        const bool small = tapsPerPhase * dg.IC <= 128 && static_cast<double>(dg.N) * dg.OH * dg.OW * up_div(dg.OC, 4) <= 32768.0;
+        const bool forced = sw && !strcmp(sw, "mfma");
+        if (!(sw && !strcmp(sw, "direct")) && (forced || !small) && deconv2d_mfma_eligible(dg))
+            return make_deconv2d_mfma_plan(ctx, dg, w_oihw, make_epilogue_table(dg.OC, 64, desc->useBias && bias, bias, desc->useBN, bn_beta, bn_gamma, bn_mean, bn_var), out);
+    }
     auto* plan = new DeconvPlan();
     plan->ctx = ctx;
     plan->anyDtype = true;

@@ -4,6 +4,10 @@ MobileNetV2 pointwise/depthwise b32), each with its algorithmic FLOPs / bytes an
 (fp32 MFMA 157.3 TFLOP/s, HBM 8 TB/s).  Timing: `reps` back-to-back launches between two HIP events on the context stream.
 
     python tools/bench_layers.py [--reps 50] [--force mfma|generic] [--json out.json]
+
+--deconv N,H,W,IC,OC,k,stride (repeatable; --only deconv runs just these) times deconv2d_plan ("same" padding) the same way, the matrix-core kernel and
+SNNHIP_DECONV=direct alternated in mirrored order (m d d m ...) in this one process: `regions` timed regions of `reps` launches each, the median per kernel
+and its spread (max - min); floors: 157.3 TFLOP/s fp32 / 2516 TFLOP/s fp16 on the algorithmic FLOPs, 8 TB/s on the plan's bytes.
 """
 import argparse
 import json
@@ -45,6 +49,64 @@ LAYERS = [
 ]
 
 
+def deconv_name(shape, fp16):
+    N, H, W, IC, OC, k, s = shape
+    return "deconv %dx%d s%d %d->%d @%dx%d b%d %s" % (k, k, s, IC, OC, H, W, N, "fp16" if fp16 else "fp32")
+
+
+def bench_deconv(snn, ctx, rng, shape, args):
+    N, H, W, IC, OC, k, s = shape
+    name = deconv_name(shape, args.fp16)
+    dt = snn.F16 if args.fp16 else snn.F32
+    x = rng.random((N, H, W, IC), dtype=np.float32)
+    w = (rng.standard_normal((OC, IC, k, k)) / np.sqrt(k * k * IC / (s * s))).astype(np.float32)
+    b = rng.uniform(-0.1, 0.1, OC).astype(np.float32)
+    xt = snn.Tensor.from_numpy(ctx, x, dtype=dt)
+    plans, exported = {}, os.environ.get("SNNHIP_DECONV")
+    for kind in ("mfma", "direct"):
+        os.environ["SNNHIP_DECONV"] = kind
+        plans[kind] = snn.deconv2d_plan(ctx, N, H, W, w, b, stride=s, same=True, act="relu")
+    if exported is None:
+        del os.environ["SNNHIP_DECONV"]
+    else:
+        os.environ["SNNHIP_DECONV"] = exported
+    yt = snn.Tensor(ctx, *plans["mfma"].out_shape(), dtype=dt)
+    for p in plans.values():
+        for _ in range(5):
+            p.run(xt, yt)
+    ctx.sync()
+    t = snn.Timer(ctx)
+    times = {"mfma": [], "direct": []}
+    for r in range(args.regions):
+        for kind in (("mfma", "direct") if r % 2 == 0 else ("direct", "mfma")):
+            t.start()
+            for _ in range(args.reps):
+                plans[kind].run(xt, yt)
+            t.stop()
+            ctx.sync()
+            times[kind].append(1e3 * t.elapsed_ms() / args.reps)
+    row = {"layer": name}
+    for kind, p in plans.items():
+        us, spread = float(np.median(times[kind])), float(max(times[kind]) - min(times[kind]))
+        fl, by = p.cost()
+        if kind == "direct":  # its plan books 4-byte elements whatever the tensors are: the tensors at their size + its [tap][ic][oc/4] float4 table
+            oh, ow = p.out_shape()[1:3]
+            by = (2.0 if args.fp16 else 4.0) * N * (H * W * IC + oh * ow * OC) + 16.0 * k * k * IC * ((OC + 3) // 4)
+        t_mfma, t_hbm = fl / PEAK_TF / 1e6, by / PEAK_GBS / 1e3
+        row[kind] = {"us": us, "spread_us": spread, "regions": times[kind], "tflops": fl / us / 1e6, "gbps": by / us / 1e3, "bound": "mfma" if t_mfma >= t_hbm else "hbm",
+                     "frac": max(t_mfma, t_hbm) / us, "kernel": p.describe()}
+        print("%-46s %-6s %9.1f us (spread %6.1f) %7.2f TF/s %8.1f GB/s  %4s-bound %5.1f%%  | %s" % (name, kind, us, spread, row[kind]["tflops"], row[kind]["gbps"], row[kind]["bound"],
+                                                                                                  100 * row[kind]["frac"], p.describe()), flush=True)
+    row["speedup"] = row["direct"]["us"] / row["mfma"]["us"]
+    row["faster_beyond_spread"] = row["direct"]["us"] - row["mfma"]["us"] > max(row["mfma"]["spread_us"], row["direct"]["spread_us"])
+    t.destroy()
+    for p in plans.values():
+        p.destroy()
+    xt.free()
+    yt.free()
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
@@ -53,6 +115,8 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--fp16", action="store_true", help="half tensors (fp16 MFMA path; roofline against 2516 TFLOP/s)")
     ap.add_argument("--shape", action="append", default=[], help="extra ad-hoc layer N,H,W,IC,OC,k,stride (repeatable; with --only=adhoc runs just these)")
+    ap.add_argument("--deconv", action="append", default=[], help="Conv2DTranspose layer N,H,W,IC,OC,k,stride (repeatable), mfma and direct alternated")
+    ap.add_argument("--regions", type=int, default=7, help="timed regions per kernel of a --deconv layer")
     args = ap.parse_args()
     global PEAK_TF
     if args.fp16:
@@ -99,6 +163,11 @@ def main():
         plan.destroy()
         xt.free()
         yt.free()
+    for sh in args.deconv:
+        shape = [int(t) for t in sh.split(",")]
+        if args.only and args.only not in deconv_name(shape, args.fp16):
+            continue
+        rows.append(bench_deconv(snn, ctx, rng, shape, args))
     if args.json:
         json.dump(rows, open(args.json, "w"), indent=1)
 
