@@ -347,6 +347,10 @@ int snn_model_download_output(snn_model* m, float* nhwc);
 int snn_model_set_type(snn_model* m, int model_type);
 int snn_model_classifier_output(snn_model* m);                             /* 1-based arg-max of the last stage, 0 = none */
 int snn_model_detections(snn_model* m, float* rows6, int max_rows);         /* YOLO stage output {class, score, x, y, w, h}; returns the row count */
+/* The same for image `image` of the batch.  With the device head (batch > 1, or SNNHIP_YOLO_HEAD=device; include/snnhip.h, snnhip_yolo_head_plan_create)
+ * the stage is one launch inside the inference and run() downloads nothing: this call waits for the stream and reads that image's rows (at most 100)
+ * and count from the device tensors.  With the CPU stage only image 0 exists.  -1 for an image outside the batch. */
+int snn_model_detections_n(snn_model* m, int image, float* rows6, int max_rows);
 /* Input pre-processing on the device, the demo's call sequence (modelInference.cpp:92-97): decoded 8-bit image (1 / 3 / 4 channels) ->
  * convertToRGBA32FAndNormalize(means, norms) -> resize to the model's input size with (resize_means, resize_norms), bilinear.
  * The model must take a 4-channel input (RGBA texture). */

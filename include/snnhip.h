@@ -711,6 +711,41 @@ int snnhip_tensor_yuv_planar_plan_create(snnhip_ctx* ctx, const snnhip_tensor_yu
 /* host only, no context: out[0..4] = Yoff, ys, Coff, cbs, crs of the map above (capacity >= 5 floats) */
 int snnhip_tensor_yuv_coefficients(int maxval, int range, float kr, float kb, float* out, int capacity);
 
+/* The YOLO v3 detection head on the device: decode, stable score sort and greedy NMS of every image of a batch in one launch (one block per image, no
+ * scratch buffer, no global atomic, no memset: bit-identical from run to run, recordable in an snnhip_graph).  The reference runs this on the CPU from
+ * downloaded heads (yololayer.cpp:27-226); the list here is that list.  DESIGN.md section 4.29.  The contract, stated once (tests/yolo_ref.py restates
+ * it in float64 NumPy):
+ *   Shapes: inputs[h], h < n_heads, = head h, [N][g][g][anchors_per_cell * (5 + classes)] with g = net_size / grid_scale[h], dense true channel count,
+ *     SNNHIP_F32 or SNNHIP_F16, all heads of one type (fp16 values are widened; all arithmetic is fp32).  A candidate is (head, gy, gx, anchor), in that
+ *     order; its values are {tx, ty, tw, th, objectness, class logits}.  At most 4096 candidates per image.
+ *   Class and confidence: the class is the first maximum of the class logits (strict >, from -FLT_MAX); prob = 1 / (1 + e^-obj (1 + e^-cls)) -- the
+ *     reference's expression as written (yololayer.cpp:147), not the product of two sigmoids.  A candidate survives when prob > conf_threshold.
+ *   Box: with a = masks[head * anchors_per_cell + anchor], cx = (gx + sigmoid(tx)) / g, cy = (gy + sigmoid(ty)) / g,
+ *     w = e^tw anchors[2a] / float(grid_scale g), h = e^th anchors[2a + 1] / float(grid_scale g), x = cx - w / 2, y = cy - h / 2.
+ *   Order: survivors sorted by descending score, equal scores in candidate order (std::stable_sort).
+ *   NMS: greedy in that order; a kept box suppresses every later box of its class whose yoloIoU with it is > iou_threshold (yololayer.cpp:57-112:
+ *     0 when the boxes do not meet, else inter / (wa ha + wb hb - inter)).  The kept boxes in order are the rows; max_boxes keeps the first max_boxes.
+ *   Outputs: outputs[0] = SNNHIP_F32 [N][max_boxes][1][6], rows {class, score, x, y, w, h}, every row past the count zeros;
+ *     outputs[1] = SNNHIP_F32 [N][1][1][2] = {rows written, boxes that passed the confidence threshold} (integers, exact in a float).
+ *   Arithmetic: no contraction, IEEE division, expf of the device library: a decision differs from the CPU's only where expf's last bits do.
+ * Plan creation returns SNNHIP_E_INVALID with a message starting "yolo_head" for a null argument, N < 1, n_heads outside {1, 2}, a net_size that is
+ * not a multiple of 32 in 32..512 or of every grid_scale, anchors_per_cell outside 1..3, classes outside 1..2^20, more than 4096 candidates per image,
+ * a mask entry outside 0..5, max_boxes outside 1..candidates and a threshold outside (0, 1).  snnhip_plan_run and snnhip_plan_run_n refuse the plan with
+ * a message starting "yolo_head"; snnhip_plan_run_io refuses, with a message, a wrong n_in or n_out and a tensor of another dtype or shape at any
+ * position.  snnhip_plan_describe: "yolo_head net=416 heads=2 candidates=2535 classes=1 max_boxes=100 ... cap=4096 lds=98824 kernel=yolo_head_kernel".
+ * Not offered: more than two heads or 4096 candidates (the full-size YOLOv3's 10647), class-agnostic or soft NMS, boxes in pixels. */
+typedef struct snnhip_yolo_head_desc {
+    int N, net_size;            /* net_size: multiple of 32, 32..512 */
+    int n_heads;                /* 1 or 2; head h has grid net_size / grid_scale[h] */
+    int grid_scale[2];          /* reference: {32, 16} */
+    int anchors_per_cell;       /* reference: 3 */
+    int classes;                /* >= 1; reference: 1.  channels per head = anchors_per_cell * (5 + classes) */
+    float anchors[12]; int masks[6];   /* reference values: yololayer.cpp:36-37 */
+    float conf_threshold, iou_threshold;   /* reference: 0.35, 0.45 */
+    int max_boxes;              /* rows written per image, 1..candidates */
+} snnhip_yolo_head_desc;
+int snnhip_yolo_head_plan_create(snnhip_ctx* ctx, const snnhip_yolo_head_desc* desc, snnhip_plan** out); /* run with snnhip_plan_run_io, n_heads inputs, 2 outputs */
+
 /* Frame quality on the device: PSNR and SSIM between a test frame and a reference frame, so that what an arithmetic choice (fused fp32, the fp16
  * opt-in, 8 / 10 / 12-bit frame ends) or a trained model costs in picture quality can be stated in dB without downloading every output frame.
  * DESIGN.md section 4.22.  The reference ships a host-side comparison script only (tools/misc/imageComparison.py).  The definition, stated once
@@ -800,8 +835,9 @@ int snnhip_graph_fuse(snnhip_ctx* ctx, const snnhip_graph_node* nodes, int n, sn
 int snnhip_plan_run(snnhip_plan* plan, const snnhip_tensor* in, snnhip_tensor* out);
 /* multi-input ops (add, concat): inputs[n_in] */
 int snnhip_plan_run_n(snnhip_plan* plan, const snnhip_tensor* const* inputs, int n_in, snnhip_tensor* out);
-/* a plan with more than one output: the tensor_yuv plans (1 input; outputs[0] = the luma plane, outputs[1] = the chroma).  Every other plan is
- * refused with a message; the two functions above refuse a tensor_yuv plan.  The same launch trace, guard mode and graph capture as those two. */
+/* a plan with more than one output: the tensor_yuv plans (1 input; outputs[0] = the luma plane, outputs[1] = the chroma) and the yolo_head plan
+ * (n_heads inputs; outputs[0] = the rows, outputs[1] = the counts).  Every other plan is refused with a message; the two functions above refuse
+ * these plans.  The same launch trace, guard mode and graph capture as those two. */
 int snnhip_plan_run_io(snnhip_plan* plan, const snnhip_tensor* const* inputs, int n_in, snnhip_tensor* const* outputs, int n_out);
 int snnhip_plan_output_dims(const snnhip_plan* plan, int dims_nhwc[4]);
 /* Human-readable kernel-variant description ("conv2d_mfma_f32 tile=...") for logs and tests. */

@@ -138,6 +138,11 @@ class TensorYuvDesc(C.Structure):
                 ("siting", C.c_int), ("range", C.c_int), ("kr", C.c_float), ("kb", C.c_float), ("scale", C.c_float * 3), ("offset", C.c_float * 3)]
 
 
+class YoloHeadDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("net_size", C.c_int), ("n_heads", C.c_int), ("grid_scale", C.c_int * 2), ("anchors_per_cell", C.c_int), ("classes", C.c_int),
+                ("anchors", C.c_float * 12), ("masks", C.c_int * 6), ("conf_threshold", C.c_float), ("iou_threshold", C.c_float), ("max_boxes", C.c_int)]
+
+
 class FrameMetricsDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("maxval", C.c_int), ("shift", C.c_int)]
 
@@ -243,6 +248,7 @@ SIGNATURES = {
     "snnhip_tensor_yuv_plan_create": (C.c_int, [_P, C.POINTER(TensorYuvDesc), C.POINTER(_P)]),
     "snnhip_tensor_yuv_planar_plan_create": (C.c_int, [_P, C.POINTER(TensorYuvDesc), C.POINTER(_P)]),
     "snnhip_tensor_yuv_coefficients": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, _FP, C.c_int]),
+    "snnhip_yolo_head_plan_create": (C.c_int, [_P, C.POINTER(YoloHeadDesc), C.POINTER(_P)]),
     "snnhip_frame_metrics_plan_create": (C.c_int, [_P, C.POINTER(FrameMetricsDesc), C.POINTER(_P)]),
     "snnhip_frame_metrics_read": (C.c_int, [_P, C.POINTER(FrameMetricsRow), C.c_int]),
     "snnhip_frame_metrics_psnr": (C.c_double, [C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -532,7 +538,7 @@ class Plan:
             check(lib().snnhip_plan_run(self.h, x.h, y.h))
 
     def run_io(self, xs, ys):
-        """snnhip_plan_run_io: a plan with more than one output (tensor_yuv_plan); xs and ys are lists of tensors"""
+        """snnhip_plan_run_io: a plan with more than one output (tensor_yuv_plan, yolo_head_plan); xs and ys are lists of tensors"""
         a = (_P * max(len(xs), 1))(*[t.h for t in xs])
         b = (_P * max(len(ys), 1))(*[t.h for t in ys])
         check(lib().snnhip_plan_run_io(self.h, a, len(xs), b, len(ys)))
@@ -977,6 +983,27 @@ def tensor_yuv_coefficients(maxval=255, range="limited", kr=BT601[0], kb=BT601[1
     out = np.zeros(5, np.float32)
     check(lib().snnhip_tensor_yuv_coefficients(maxval, RANGE.get(range, range), kr, kb, _fptr(out), out.size if capacity is None else capacity))
     return out
+
+
+YOLO_ANCHORS = (10, 14, 23, 27, 37, 58, 81, 82, 135, 169, 344, 319)  # yololayer.cpp:36-37
+YOLO_MASKS = (3, 4, 5, 1, 2, 3)
+
+
+def yolo_head_desc(N, net_size=416, n_heads=2, grid_scale=(32, 16), anchors_per_cell=3, classes=1, anchors=YOLO_ANCHORS, masks=YOLO_MASKS, conf=0.35, iou=0.45,
+                   max_boxes=100):
+    """The snnhip_yolo_head_desc of the arguments; the defaults are the reference's YOLOv3-tiny head (yololayer.cpp:36-37, 182-183)."""
+    scale = (list(grid_scale) + [0, 0])[:2]
+    return YoloHeadDesc(N, net_size, n_heads, (C.c_int * 2)(*scale), anchors_per_cell, classes, (C.c_float * 12)(*(list(anchors) + [0] * 12)[:12]),
+                        (C.c_int * 6)(*(list(masks) + [0] * 6)[:6]), conf, iou, max_boxes)
+
+
+def yolo_head_plan(ctx, N, **kw):
+    """plan.run_io([head [N][g][g][A * (5 + classes)], ...], [rows [N][max_boxes][1][6], counts [N][1][1][2]]): the YOLO v3 head -- decode, stable score
+    sort, greedy NMS -- of every image in one launch; fp32 or fp16 heads, fp32 outputs (include/snnhip.h states the contract).  Keywords: yolo_head_desc's."""
+    d = yolo_head_desc(N, **kw)
+    h = _P()
+    check(lib().snnhip_yolo_head_plan_create(ctx.h, C.byref(d), C.byref(h)))
+    return Plan(ctx, h)
 
 
 RGB_FIT_SOURCE = {"cbcr": 0, "planar": 1, "rgb": 2}  # SNNHIP_RGB_FIT_*

@@ -137,7 +137,7 @@ struct snnhip_plan {
     int inDims[4] = {0, 0, 0, 0};   // N,H,W,C of input 0
     int outDims[4] = {0, 0, 0, 0};
     int numInputs = 1;
-    int numOutputs = 1;       // 2: a tensor_yuv plan (frame_tensor_yuv.hip), which runs through runIO() / snnhip_plan_run_io and whose run() refuses
+    int numOutputs = 1;       // 2: a tensor_yuv plan (frame_tensor_yuv.hip) or the yolo_head plan (yolo_head.hip), which run through runIO() / snnhip_plan_run_io; their run() refuses
     int dtype = SNNHIP_F32;   // element type of the tensors this plan runs on ...
     bool anyDtype = false;    // ... unless it adapts to the tensors of each call (element-wise / pooling / shape operators)
     // raw frame dtype of this plan's input 0 / output (SNNHIP_U8 or SNNHIP_U16), -1 = none: snnhip_image_u8_plan_create and the u8_in / u16_in plans read

@@ -67,6 +67,7 @@ SIGNATURES = {
     "snn_model_set_type": (C.c_int, [_P, C.c_int]),
     "snn_model_classifier_output": (C.c_int, [_P]),
     "snn_model_detections": (C.c_int, [_P, _FP, C.c_int]),
+    "snn_model_detections_n": (C.c_int, [_P, C.c_int, _FP, C.c_int]),
     "snn_model_upload_input_u8": (C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, _FP]),
     "snn_yolo_decode": (C.c_int, [_FP, _FP, C.c_int, _FP, C.c_int]),
     "snn_model_num_stages": (C.c_int, [_P]),
@@ -586,9 +587,11 @@ class Model:
         """1-based class index of the last run (MixedInferenceCore::run, core.cpp:228-234); 0 = none."""
         return lib().snn_model_classifier_output(self.h)
 
-    def detections(self, max_rows=100):
+    def detections(self, max_rows=100, image=0):
+        """rows {class, score, x, y, w, h} of image `image`: the CPU stage's list (image 0 only), or with the device head its first 100 rows"""
         rows = np.zeros((max_rows, 6), np.float32)
-        n = lib().snn_model_detections(self.h, _fp(rows), max_rows)
+        n = lib().snn_model_detections_n(self.h, image, _fp(rows), max_rows)
+        assert n >= 0, n
         return rows[:n].copy()
 
     def run(self):

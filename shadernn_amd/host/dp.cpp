@@ -179,6 +179,8 @@ private:
         }
         layer->getOutputDims(width, height, depth);
 
+        if (auto* yolo = dynamic_cast<YOLOLayer*>(layer.get()))
+            if (yolo->useDevice(options.batch)) stage.layerLoc = yolo->getLayerExecutionType(); // the head as a GPU stage (yolo_head.hip)
         if (stage.layerLoc == InferenceGraph::LayerExecutionType::CPU) {
             if (i == 0) SNN_RIP("CPU layer currently cannot cannot be the 1-st layer in the graph !");
             if (options.batch != 1)

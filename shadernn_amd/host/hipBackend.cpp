@@ -24,7 +24,12 @@ void HipRenderPass::run() {
     if (skip) return;
     const snnhip_tensor* in0 = rawInput ? rawInput : input->tensor();
     snnhip_tensor* out = rawOutput ? rawOutput : output->tensor();
-    if (extraInputs.empty()) {
+    if (out1) {
+        std::vector<const snnhip_tensor*> ins{in0};
+        for (auto* t : extraInputs) ins.push_back(t->tensor());
+        snnhip_tensor* outs[2] = {out, out1};
+        hipChk(snnhip_plan_run_io(plan, ins.data(), static_cast<int>(ins.size()), outs, 2), "snnhip_plan_run_io");
+    } else if (extraInputs.empty()) {
         hipChk(snnhip_plan_run(plan, in0, out), "snnhip_plan_run");
     } else {
         std::vector<const snnhip_tensor*> ins{in0};
@@ -255,6 +260,14 @@ void HipBackend::initRenderPasses(GenericModelLayer* layer, ImageTextureArrayAcc
         hipChk(pass.createPlan(ctx, &plan), pass.source.c_str());
         int od[4];
         hipChk(snnhip_plan_output_dims(plan, od), "snnhip_plan_output_dims");
+        if (auto* yolo = dynamic_cast<YOLOLayer*>(layer)) { // two outputs of the plan's own shape, read by snn_model_detections_n; the stage's texture stays unused
+            auto rp = std::make_shared<HipRenderPass>(plan, &in[0], &out[0], layer->getName(), true);
+            for (size_t k = 1; k < in.size(); ++k) rp->extraInputs.push_back(&in[k]);
+            rp->rawOutput = yolo->deviceRows = ownTensor(od[0], od[1], od[2], od[3], SNNHIP_F32, "snnhip_tensor_alloc (detection rows)");
+            rp->out1 = yolo->deviceCounts = ownTensor(od[0], 1, 1, 2, SNNHIP_F32, "snnhip_tensor_alloc (detection counts)");
+            rps.push_back(rp);
+            continue;
+        }
         ImageTexture& o = out[0];
         // Dense produces [1][1][1][Out] while the reference's texture is Out x 1 x 1: accept both, reject real mismatches
         const size_t want = static_cast<size_t>(od[0]) * od[1] * od[2] * od[3];
@@ -314,7 +327,8 @@ void HipBackend::finalizeStages(RenderStagesArray& stages, bool dumpOutputs, boo
     auto passOf = [&](size_t i) -> HipRenderPass* {
         auto* ml = static_cast<GenericModelLayer*>(stages[i].layer->modelLayer);
         if (!ml || stages[i].layer->isInputLayer || stages[i].backend != Backend::Backend_GPU || ml->getRenderPasses().size() != 1) return nullptr;
-        return dynamic_cast<HipRenderPass*>(ml->getRenderPasses()[0].get());
+        auto* rp = dynamic_cast<HipRenderPass*>(ml->getRenderPasses()[0].get());
+        return rp && rp->out1 ? nullptr : rp; // (a two-output pass is opaque to the fusion pass: its producers stay materialised)
     };
     // node space: [u8_in frame conversion] + one node per stage + [u8_out frame conversion]; the conversions are ordinary plan nodes, so the
     // chain rules see them (rules A8 / B8 fold them into the ESPCN kernels)

@@ -90,6 +90,7 @@ public:
     bool skip = false; // fused into an earlier pass
     const snnhip_tensor* rawInput = nullptr; // HIP extension: the 8-bit input frame a fused plan reads instead of `input` (rule A8)
     snnhip_tensor* rawOutput = nullptr;      // ... and the 8-bit output frame it writes instead of `output` (rule B8)
+    snnhip_tensor* out1 = nullptr; // a second output: the pass runs through snnhip_plan_run_io and never fuses (the YOLO head: rows in rawOutput, counts here)
 };
 
 class HipBackend : public DeviceBackend {

@@ -569,7 +569,13 @@ public:
     void computeImageTexture(ImageTextureArray& inputMat, ImageTextureArray& outputMat) override;
     InferenceGraph::LayerExecutionType getLayerExecutionType() const override { return executeBackend; }
     void setLayerExecutionType(InferenceGraph::LayerExecutionType e) override { executeBackend = e; }
-    void createInferencePasses(const LayerGenOptions&) override {}
+    // HIP flavour: the head as one launch inside the inference (snnhip_yolo_head_plan_create, reference constants, 100 rows).  useDevice decides once,
+    // when the graph is generated: SNNHIP_YOLO_HEAD=device|cpu forces either, otherwise batch 1 keeps the CPU stage and batch > 1 takes the device head.
+    bool useDevice(uint32_t batch);
+    bool onDevice() const { return executeBackend != InferenceGraph::LayerExecutionType::CPU; }
+    void createInferencePasses(const LayerGenOptions&) override; // nothing for the CPU stage
+    // the device head's outputs (owned by the backend): rows [N][100][1][6], counts [N][1][1][2]; null for the CPU stage
+    snnhip_tensor *deviceRows = nullptr, *deviceCounts = nullptr;
     // decode + NMS on host floats, heads in NHWC with the true channel count (3 x 6); returns rows {class, score, x, y, w, h}
     static std::vector<std::vector<float>> decode(const std::vector<const float*>& heads, int netSize = 416);
 

@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <unordered_map>
 
 #include "../../include/snnhip.h"
@@ -720,6 +722,33 @@ std::vector<std::vector<float>> YOLOLayer::decode(const std::vector<const float*
         out.push_back({static_cast<float>(boxes[i].cls), boxes[i].score, boxes[i].x, boxes[i].y, boxes[i].w, boxes[i].h});
     }
     return out;
+}
+
+bool YOLOLayer::useDevice(uint32_t batch) {
+    const char* forced = getenv("SNNHIP_YOLO_HEAD");
+    const bool device = forced && !strcmp(forced, "device") ? true : forced && !strcmp(forced, "cpu") ? false : batch > 1;
+    if (device) executeBackend = InferenceGraph::LayerExecutionType::GPU_HIP;
+    return device;
+}
+
+void YOLOLayer::createInferencePasses(const LayerGenOptions&) {
+    if (!onDevice()) return;
+    if (inputDims.size() != 2) SNN_RIP("YOLO layer %s: the device head takes the coarse and the fine head, got %zu inputs", name.c_str(), inputDims.size());
+    snnhip_yolo_head_desc d = {};
+    d.N = static_cast<int>(inputDims[0].batch);
+    d.net_size = static_cast<int>(inputDims[0].width) * kYoloGridScale[0];
+    d.n_heads = 2;
+    d.grid_scale[0] = kYoloGridScale[0], d.grid_scale[1] = kYoloGridScale[1];
+    d.anchors_per_cell = kYoloGridChannel;
+    d.classes = kYoloClasses;
+    for (int i = 0; i < 12; ++i) d.anchors[i] = kYoloAnchors[i];
+    for (int i = 0; i < 6; ++i) d.masks[i] = kYoloMasks[i];
+    d.conf_threshold = 0.35f, d.iou_threshold = 0.45f; // yololayer.cpp:182-183
+    d.max_boxes = 100;                                   // the layer's declared 600 x 1 output (yololayer.h:44-48)
+    passes = std::make_shared<InferencePasses>();
+    passes->passes.resize(1);
+    passes->passes[0].source = formatString("YOLO head net=%d", d.net_size);
+    passes->passes[0].createPlan = [d](snnhip_ctx* ctx, snnhip_plan** out) { return snnhip_yolo_head_plan_create(ctx, &d, out); };
 }
 
 void YOLOLayer::computeImageTexture(ImageTextureArray& inputTex, ImageTextureArray& outputTex) { // yololayer.cpp:177-226

@@ -1,4 +1,5 @@
 // snn_c.cpp -- C binding of the host mirror for tests / harnesses (see include/snn_c.h).
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -542,7 +543,21 @@ static int copyRows(const std::vector<std::vector<float>>& rows, float* rows6, i
     return n;
 }
 
-int snn_model_detections(snn_model* m, float* rows6, int max_rows) { return copyRows(m->modelOutput.detectionOutput, rows6, max_rows); }
+int snn_model_detections_n(snn_model* m, int image, float* rows6, int max_rows) {
+    if (!m || !rows6 || max_rows < 0 || image < 0 || image >= m->batch) return -1;
+    RenderStage& last = m->core->stage(m->core->numStages() - 1);
+    auto* yolo = dynamic_cast<dp::YOLOLayer*>(static_cast<dp::GenericModelLayer*>(last.layer->modelLayer));
+    if (!yolo || !yolo->deviceRows) return image == 0 ? copyRows(m->modelOutput.detectionOutput, rows6, max_rows) : -1; // the CPU stage: one image
+    int rd[4], cd[4];
+    if (!m->core->sync() || snnhip_tensor_dims(yolo->deviceRows, rd) != SNNHIP_OK || snnhip_tensor_dims(yolo->deviceCounts, cd) != SNNHIP_OK) return -1;
+    std::vector<float> rows(static_cast<size_t>(rd[0]) * rd[1] * 6), counts(static_cast<size_t>(cd[0]) * 2);
+    if (snnhip_tensor_download(yolo->deviceRows, rows.data()) != SNNHIP_OK || snnhip_tensor_download(yolo->deviceCounts, counts.data()) != SNNHIP_OK) return -1;
+    const int n = std::min(static_cast<int>(counts[static_cast<size_t>(image) * 2]), max_rows);
+    std::copy_n(rows.begin() + static_cast<size_t>(image) * rd[1] * 6, static_cast<size_t>(n) * 6, rows6);
+    return n;
+}
+
+int snn_model_detections(snn_model* m, float* rows6, int max_rows) { return snn_model_detections_n(m, 0, rows6, max_rows); }
 
 int snn_yolo_decode(const float* head_coarse, const float* head_fine, int net_size, float* rows6, int max_rows) {
     return copyRows(dp::YOLOLayer::decode({head_coarse, head_fine}, net_size), rows6, max_rows);

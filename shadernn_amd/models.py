@@ -191,6 +191,23 @@ def unet(seed=1, base=64, in_channels=1, depth=4):
     return {"name": "unet", "input_channels": in_channels, "layers": L}
 
 
+def with_yolo_head(net, classes=1, max_boxes=100, conf=0.35, iou=0.45, seed=1):
+    """A two-headed detector (net["outputs"]: YOLOv3-tiny of the zoo) with the reference's "YOLO" layer behind its heads, coarse head first.  A head
+    that does not carry 3 * (5 + classes) channels (the zoo file's 255 = 80 classes) is re-made with that width and fresh weights: the reference's
+    layer, and the host mirror's, decode `classes` = 1 (yololayer.cpp:36-40)."""
+    rng = np.random.default_rng(seed)
+    heads, layers, c = list(net["outputs"]), [], 3 * (5 + classes)
+    for l in net["layers"]:
+        if l["name"] in heads and l["oc"] != c:
+            narrow = _conv(rng, l["name"], l["ic"], c, l["kernel"], "linear")
+            narrow["w"] *= 20.0 / 6.0  # logits wide enough for a few hundred boxes over the threshold
+            narrow["b"] = rng.uniform(-1.0, 1.0, c).astype(np.float32)
+            l = dict(narrow, inputs=l["inputs"]) if "inputs" in l else narrow
+        layers.append(l)
+    layers.append(_op("YOLO", "yolo", c, inputs=heads, classes=classes, max_boxes=max_boxes, conf=conf, iou=iou))
+    return {k: v for k, v in dict(net, layers=layers).items() if k != "outputs"}
+
+
 def output_names(net):
     """The net's result layers: net["outputs"] when it has several heads, else the last layer."""
     return list(net.get("outputs", [net["layers"][-1]["name"]]))

@@ -50,6 +50,14 @@ def _layer_plan(ctx, layer, shape, dtype=capi.F32):
     raise ValueError("unsupported layer type " + t)
 
 
+def _yolo_plan(ctx, layer, head_shapes, net_size):
+    """the "YOLO" op: head h is [N][g][g][3 * (5 + classes)] with g = net_size / grid_scale[h] (rows [N][max_boxes][1][6] and counts [N][1][1][2] out)"""
+    n, classes = head_shapes[0][0], int(layer.get("classes", 1))
+    assert all(s[1] == s[2] and s[3] == 3 * (5 + classes) and net_size % s[1] == 0 for s in head_shapes), (head_shapes, classes)
+    return capi.yolo_head_plan(ctx, n, net_size=net_size, n_heads=len(head_shapes), grid_scale=[net_size // s[1] for s in head_shapes], classes=classes,
+                               conf=layer.get("conf", 0.35), iou=layer.get("iou", 0.45), max_boxes=int(layer.get("max_boxes", 100)))
+
+
 def _plain(act):
     return "" if act in ("linear", "none", None) else act
 
@@ -127,7 +135,16 @@ class GraphRunner:
         index = {"input": -1}
         nodes, self.layer_plans = [], []
         self.output_names = models.output_names(net)  # several for multi-head graphs (YOLOv3-tiny)
+        yolo = {}  # node -> (plan, producer nodes): the two-output head plan stays outside the fusion pass, its heads stay materialised
+        keep = set(self.output_names) | {i for l, ins in prods if l["type"] == "YOLO" for i in ins}
         for k, (layer, ins) in enumerate(prods):
+            if layer["type"] == "YOLO":
+                plan = _yolo_plan(ctx, layer, [shapes[i] for i in ins], h)
+                shapes[layer["name"]], index[layer["name"]] = plan.out_shape(), k
+                self.layer_plans.append(plan)
+                yolo[k] = (plan, [index[i] for i in ins])
+                nodes.append((None, [], True))
+                continue
             shape = shapes[ins[0]]
             if layer["type"] == "Add":  # output extent = max over the inputs (genericlayer.cpp:64-90)
                 shape = (shape[0], max(shapes[i][1] for i in ins), max(shapes[i][2] for i in ins), shape[3])
@@ -140,18 +157,21 @@ class GraphRunner:
             shapes[layer["name"]] = out_shape
             index[layer["name"]] = k
             self.layer_plans.append(plan)
-            nodes.append((plan, [index[i] for i in ins], layer["name"] in self.output_names))
+            nodes.append((plan, [index[i] for i in ins], layer["name"] in keep))
         fused = capi.graph_fuse(ctx, nodes) if fuse else [(p, i) for p, i, _ in nodes]
         names = ["input"] + [l["name"] for l, _ in prods]  # node index + 1
         self.tensors = {"input": self.x}
         self.steps = []  # (plan, [input tensors], output tensor, layer)
         self.fused_layers = []
         for k, ((layer, _), (plan, ins)) in enumerate(zip(prods, fused)):
+            plan, ins = yolo.get(k, (plan, ins))
             if plan is None:
                 self.fused_layers.append(layer["name"])
                 continue
-            t = capi.Tensor(ctx, *shapes[layer["name"]], dtype=dtype)
+            t = capi.Tensor(ctx, *shapes[layer["name"]], dtype=capi.F32 if k in yolo else dtype)
             self.tensors[layer["name"]] = t
+            if k in yolo:
+                self.tensors[layer["name"] + ":counts"] = capi.Tensor(ctx, shapes[layer["name"]][0], 1, 1, 2)
             self.steps.append((plan, [self.tensors[names[i + 1]] for i in ins], t, layer))
         self.fused_norms = [l["name"] for p, _, _, l in self.steps if "instancenorm(fold" in p.describe()]  # chain rule F (opt-in)
         self.y = self.steps[-1][2]
@@ -177,13 +197,22 @@ class GraphRunner:
         return f, b
 
     def run_device(self):
-        for plan, ins, out, _ in self.steps:
-            plan.run(ins if len(ins) > 1 else ins[0], out)
+        for plan, ins, out, layer in self.steps:
+            if layer["type"] == "YOLO":
+                plan.run_io(ins, [out, self.tensors[layer["name"] + ":counts"]])
+            else:
+                plan.run(ins if len(ins) > 1 else ins[0], out)
 
     def __call__(self, x):
         self.x.upload(np.ascontiguousarray(x, dtype=np.float32))
         self.run_device()
         return self.y.numpy()
+
+    def detections(self, image=0):
+        """rows {class, score, x, y, w, h} of image `image` behind a "YOLO" op (the net's last layer)"""
+        name = self.net["layers"][-1]["name"]
+        count = int(self.tensors[name + ":counts"].numpy()[image, 0, 0, 0])
+        return self.tensors[name].numpy()[image, :count, 0]
 
     def outputs(self):
         return [self.tensors[n].numpy() for n in self.output_names]

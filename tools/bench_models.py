@@ -5,6 +5,9 @@ the toy style net at 720p batch 1 (the operator set of config 5, fp32).  Synthet
 Prints images/s, achieved TFLOP/s and GB/s on the algorithmic (per-layer, unfused) accounting, and the slowest layers.
 
     python tools/bench_models.py [--reps 20] [--model resnet18|mobilenetv2|candy|style|unet|yolov3-tiny] [--batch N] [--json out.json]
+    python tools/bench_models.py --model yolov3-tiny --head [--fp16] [--reps 50] [--rounds 7] [--json out.json]
+        the zoo graph WITH its YOLO layer (models.with_yolo_head) through the host mirror: batch 1 on the CPU stage (the only path before the device
+        head), batch 1 on the device head, batch 8 on the device head, alternated in one process
 """
 import argparse
 import json
@@ -18,6 +21,55 @@ sys.path.insert(0, ROOT)
 PEAK_TF, PEAK_GBS = 157.3, 8000.0
 
 
+def bench_head(args):
+    """One inference = run() (ends in the stream wait) + reading every image's detections.  The three models live side by side and take turns, `rounds`
+    times `reps` inferences each on a host clock; median [min, max] over the rounds."""
+    import tempfile
+    import time
+
+    from shadernn_amd import host, models
+
+    net = models.with_yolo_head(models.zoo("yolov3-tiny", (416, 416, 3)))
+    path = models.write_json(net, 416, 416, os.path.join(tempfile.mkdtemp(), "yolov3_tiny_head.json"), bin_weights=True)
+    built = []
+    for name, batch, head in (("batch1_cpu_stage", 1, "cpu"), ("batch1_device_head", 1, "device"), ("batch8_device_head", 8, "device")):
+        os.environ["SNNHIP_YOLO_HEAD"] = head  # read when the graph is generated
+        m = host.Model(path, 416, 416, 3, batch=batch, prefer_half=args.fp16, capture_graph=True)
+        m.set_type("detection")
+        m.upload(np.random.default_rng(1).random((batch, 416, 416, 3), dtype=np.float32))
+        for _ in range(5):
+            m.run()
+        # (rows: the CPU stage keeps its whole list, the device head 100 rows)
+        built.append((name, batch, m, [len(m.detections(max_rows=4096, image=i)) for i in range(batch)], any("yolo_head" in s[2] for s in m.plan_steps())))
+    del os.environ["SNNHIP_YOLO_HEAD"]
+    ms = {name: {"run": [], "run_and_read": []} for name, *_ in built}
+    for _ in range(args.rounds):
+        for name, batch, m, _, _ in built:
+            for what in ("run", "run_and_read"):
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    m.run()
+                    if what == "run_and_read":
+                        for i in range(batch):
+                            m.detections(image=i)
+                ms[name][what].append(1e3 * (time.perf_counter() - t0) / args.reps)
+    out = {"what": "YOLOv3-tiny of the zoo, heads of 3 x 6 channels, with its YOLO layer through host.Model (recorded graph); ms per inference, host clock around run() "
+                   "[+ detections() of every image], median [min, max] over the rounds; baseline = batch1_cpu_stage", "dtype": "f16" if args.fp16 else "f32",
+           "reps": args.reps, "rounds": args.rounds, "configs": {}}
+    for name, batch, m, rows, device in built:
+        c = {"batch": batch, "device_head": device, "rows_per_image": rows, "launches": len(m.plan_steps())}
+        for what, v in ms[name].items():
+            c[what + "_ms"] = {"median": float(np.median(v)), "min": min(v), "max": max(v)}
+        c["images_per_s"] = batch / c["run_and_read_ms"]["median"] * 1e3
+        out["configs"][name] = c
+        print("%-20s run %.3f ms [%.3f, %.3f]  run + read %.3f ms [%.3f, %.3f]  %.0f images/s  rows %s" % (
+            name, c["run_ms"]["median"], c["run_ms"]["min"], c["run_ms"]["max"], c["run_and_read_ms"]["median"], c["run_and_read_ms"]["min"],
+            c["run_and_read_ms"]["max"], c["images_per_s"], rows[:2]), flush=True)
+        m.close()
+    if args.json:
+        json.dump(out, open(args.json, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -26,7 +78,13 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--tune", action="store_true", help="SNNHIP_CONV_TUNE=1: time a few (block width, split-K) candidates per convolution at plan creation")
     ap.add_argument("--fp16", action="store_true", help="half tensors + fp16 MFMA convolutions (graphs without depthwise / dense / pooling layers)")
+    ap.add_argument("--head", action="store_true", help="yolov3-tiny with its YOLO layer through the host mirror: CPU stage b1, device head b1, device head b8")
+    ap.add_argument("--rounds", type=int, default=7, help="--head: rounds the three configurations alternate over")
     args = ap.parse_args()
+    if args.head:
+        if args.model != "yolov3-tiny":
+            ap.error("--head goes with --model yolov3-tiny")
+        return bench_head(args)
     if args.tune:
         os.environ.setdefault("SNNHIP_CONV_TUNE", "1")  # =2 (set by the caller) also logs every candidate, see tools/report_tune.py
     import shadernn_amd as snn
