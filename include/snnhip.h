@@ -806,6 +806,17 @@ int snnhip_espcn_f16_pack_weights(const float* w_oihw, int ic, int k, int r, uns
  *   oc = r*r, ic = 32, k = 3, r = 2,3,4:  [r*r][32][3][3] -> 4608 halfs, MFMA row 4*dy + dx = channel r*dy + dx (other rows zero), MB = 1, KC = 1
  *       out[((ks*MB + mb)*64 + lane)*8 + j] = W[row 16*mb + lane%16][ic = 32*(ks % KC) + 8*(lane/16) + j][tap = ks / KC],  ks = 0 .. 9*KC - 1, j = 0..7 */
 int snnhip_espcn_f16_wide_pack_weights(const float* w_oihw, int oc, int ic, int k, int r, unsigned short* out, int capacity, int* count);
+/* The pre-summation behind the "up-convolution" plans of the U-Net decoder (conv2d_upconv2.hip): nearest x2 UpSampling2D ->
+ * Conv2D 2x2 stride 1 with constant padding and ONE pad row and ONE pad column in total, evaluated on the low-resolution tensor L.  Host side only.
+ * Along an axis with near pad p (rows: padL, columns: padT -- the reference's swap), output coordinate 2 m + phase, tap t reads
+ * L[m + floor((phase - p + t) / 2)] = L[m - p + a], zero outside the image; taps with the same a are added in fp32.  Per axis three (phase, a) pairs carry
+ * taps, numbered e = 0, 1, 2 in ascending (phase, a):
+ *     p = 1:  (0, 0) <- tap 0,   (0, 1) <- tap 1,   (1, 1) <- taps 0 + 1          p = 0:  (0, 0) <- taps 0 + 1,   (1, 0) <- tap 0,   (1, 1) <- tap 1
+ * out[(3 ey + ex)][oc][ic] is the sum over the row taps of ey and the column taps of ex of w_oihw[oc][ic][ty][tx] (nine [OC][IC] matrices), so that
+ *     y[2 m + py][2 q + px][oc] = sum over (ey, ex) with phase (py, px), sum over ic, of out[3 ey + ex][oc][ic] * L[m - padL + a(ey)][q - padT + a(ex)][ic].
+ * Reads N, H, W of desc not at all; SNNHIP_E_INVALID with a message unless kh = kw = 2, sh = sw = 1, padMode = SNNHIP_PAD_CONSTANT,
+ * padT + padB = 1 and padL + padR = 1. */
+int snnhip_upconv2_presum_weights(const snnhip_conv2d_desc* desc, const float* w_oihw, float* out /* [9][OC][IC] */);
 
 /* Graph-level fusion: the ONE place where an operator DAG is searched for fusable groups (the host mirror's
  * HipBackend::finalizeStages and the Python GraphRunner both call it; the rules themselves are snnhip_chain_plan_create's).

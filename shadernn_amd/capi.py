@@ -256,6 +256,7 @@ SIGNATURES = {
     "snnhip_chain_plan_create": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "snnhip_espcn_f16_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "snnhip_espcn_f16_wide_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
+    "snnhip_upconv2_presum_weights": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
     "snnhip_graph_fuse": (C.c_int, [_P, C.POINTER(GraphNode), C.c_int, C.POINTER(FusedNode)]),
     "snnhip_plan_run": (C.c_int, [_P, _P, _P]),
     "snnhip_plan_run_n": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P]),
@@ -1093,6 +1094,16 @@ def espcn_f16_wide_pack_weights(w_oihw, r=0):
     n = C.c_int(0)
     check(lib().snnhip_espcn_f16_wide_pack_weights(w.ctypes.data_as(_P), w.shape[0], w.shape[1], w.shape[2], r, out.ctypes.data_as(_P), out.size, C.byref(n)))
     return out[: n.value].view(np.float16).copy()
+
+
+def upconv2_presum_weights(w_oihw, pads, stride=1, pad_mode="constant"):
+    """snnhip_upconv2_presum_weights (host side only, no GPU): the nine pre-summed [OC][IC] matrices of UpSampling2D x2 -> Conv2D 2x2 "same" on the
+    low-resolution tensor, [9][OC][IC] float32 in the order include/snnhip.h documents.  w_oihw [OC][IC][kh][kw], pads (T, B, L, R)."""
+    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
+    d = _conv_desc(1, 2, 2, w.shape[1], w.shape[0], (w.shape[2], w.shape[3]), stride, pads, pad_mode, "", 0.0, False, False)
+    out = np.zeros((9, w.shape[0], w.shape[1]), np.float32)
+    check(lib().snnhip_upconv2_presum_weights(C.byref(d), w.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+    return out
 
 
 def chain_plan(ctx, plans):

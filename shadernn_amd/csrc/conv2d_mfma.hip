@@ -536,6 +536,18 @@ int make_conv2d_mfma_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
             if (rc != SNNHIP_E_UNSUPPORTED) return rc;
         }
     }
+    // nearest x2 UpSampling -> Conv2D 2x2 "same" (the U-Net decoder, no Pad layer): nine pre-summed (phase, low-resolution pixel) GEMMs on the low-resolution
+    // tensor (conv2d_upconv2.hip; SNNHIP_CONV=upconv2 forces it for every eligible shape, SNNHIP_UPCONV2=0 keeps the direct kernel)
+    if (g.preShift == 1 && g.kh == 2) {
+        const char* force = snnhip::option("SNNHIP_CONV");
+        const char* w = snnhip::option("SNNHIP_UPCONV2");
+        const bool forced = force && strcmp(force, "upconv2") == 0;
+        const bool allowed = !force && !(w && atoi(w) == 0) && !snnhip::option("SNNHIP_CONV_BN") && !snnhip::option("SNNHIP_CONV_SPLITK") && !snnhip::option("SNNHIP_CONV_C8");
+        if (forced || allowed) {
+            const int rc = make_conv2d_upconv2_plan(ctx, g, w_oihw, epi4, out);
+            if (rc != SNNHIP_E_UNSUPPORTED) return rc;
+        }
+    }
     // fp16 3x3 stride-1 layers on large maps: the 4 x 2 register-block kernel of conv2d_wide_f16.hip (SNNHIP_CONV=wide forces it for every
     // eligible shape, SNNHIP_CONV=mfma / SNNHIP_CONV_WIDE=0 keep the 128-pixel kernel)
     {
