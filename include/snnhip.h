@@ -786,7 +786,13 @@ int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);
 /* Try to replace a linear chain of plans (plan[i+1] consumes only plan[i]'s output) by fused kernels.
  * On success *out runs the whole chain in <= n launches; intermediate tensors that become internal are never
  * materialised.  Returns SNNHIP_E_UNSUPPORTED when no fusion rule matches (callers keep the unfused plans).
- * Implemented rule set: see DESIGN.md section 4 (ESPCN: conv5x5(1->16)+conv3x3(16->16), conv3x3(16->4)+subpixel). */
+ * Implemented rule set: see DESIGN.md section 4 (ESPCN: conv5x5(1->16)+conv3x3(16->16), conv3x3(16->4)+subpixel).
+ * Rule K is the one exception to "linear": {Concatenate, Conv2D} or {UpSampling2D x2 nearest, Concatenate, Conv2D}, the
+ * upsampling feeding the concat's input 0, become ONE two-input convolution plan, returned as is: snnhip_plan_run_n(plan, {input 0 [in front of
+ * its upsampling], input 1}, 2, out); its description carries "+concat(C0+C1)" [and "+upsample(x2 on input 0)"], its cost counts both inputs once
+ * and no concatenated tensor.  Opt-in (SNNHIP_CONV=cat) except where it was measured faster; SNNHIP_CAT=0 switches it off.  C0 must be a multiple of the
+ * kernel's channel chunk (16 fp32 / 32 fp16 channels, 8 / 16 where the planner halves it) and of 4, OC == C0 + C1, stride 1, activation none / relu / relu6 / leakyRelu;
+ * anything else returns SNNHIP_E_UNSUPPORTED and the caller keeps its plans. */
 int snnhip_chain_plan_create(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_plan** out);
 /* The fp16 ESPCN rules (SNNHIP_ESPCN_F16=1) keep their weights as lane-ordered fp16 images for the f16 matrix cores.  This
  * is the packing itself, host side only (no context, no device), so that it can be checked without a GPU.  w_oihw is fp32 and is rounded to nearest
@@ -826,8 +832,10 @@ int snnhip_upconv2_presum_weights(const snnhip_conv2d_desc* desc, const float* w
  * owned == 0 -> the node's own plan (run it with out[i].inputs: a folded identity producer, e.g. a Flatten in front of a Dense layer, is
  * skipped by re-wiring); owned == 1 -> a new fused plan the caller destroys with
  * snnhip_plan_destroy, to be run with out[i].inputs (it produces node i's tensor).  The per-layer plans must outlive the fused ones.
- * Groups searched: Conv2D -> Add where the Add is the convolution's only consumer (rule E, two-input fused plan), and maximal
- * linear runs (each operator the sole consumer of the previous one) handed to the chain planner (rules A-D, F). */
+ * Groups searched: Conv2D -> Add where the Add is the convolution's only consumer (rule E, two-input fused plan); a Concatenate whose only
+ * consumer is a convolution and whose tensor is not `keep`, its input 0 optionally through an UpSampling2D that nobody else reads (rule K: the
+ * concat node [and the upsampling node] get plan == NULL, the convolution node the owned two-input plan with the two producers as inputs); and
+ * maximal linear runs (each operator the sole consumer of the previous one) handed to the chain planner (rules A-D, F). */
 #define SNNHIP_GRAPH_MAX_INPUTS 4
 typedef struct snnhip_graph_node {
     snnhip_plan* plan;

@@ -5,6 +5,7 @@
 // The reference runs one compute dispatch + one full barrier per layer (core/src/ic2/vulkanRenderpass.cpp:257-259) and round-trips every
 // intermediate through a texture.  Rules, tried at every position in this order (the order is behaviour):
 //   E    Conv2D (MFMA kernel) + Add                                   -> one two-input convolution plan, returned as is (never a chain)
+//   K    [UpSampling2D x2 nearest on input 0 ->] Concatenate -> Conv2D -> one two-input convolution plan, returned as is (conv2d_mfma's two-source staging)
 //   C    the whole ESPCN x2 pattern, SNNHIP_ESPCN_FUSION=stream       -> one row-streaming launch (espcn_stream.hip)
 //   A16 / B16   rules A / B on fp16 tensors, SNNHIP_ESPCN_F16=1       -> espcn_f16.hip
 //   A16 / B16 wide   the same at the published widths 1 -> 64 -> 32 -> r*r, fp16 only, same switch   -> espcn_f16_wide.hip
@@ -48,6 +49,10 @@ struct Switches {
     const double normFusionMinBytes = (minMbWord ? atof(minMbWord) : 128.0) * 1048576.0;
     const bool stemNoStats = option("SNNHIP_STEM_NO_STATS") != nullptr;
     const bool noKernelFold = option("SNNHIP_NO_KERNEL_FOLD") != nullptr;
+    // rule K: SNNHIP_CAT=0 keeps the Concatenate's own launch, SNNHIP_CONV=cat takes the rule wherever it can run (default: cat_default below)
+    const char* const catWord = option("SNNHIP_CAT");
+    const bool noCat = catWord && atoi(catWord) == 0;
+    const bool catForced = is(option("SNNHIP_CONV"), "cat");
 };
 
 bool plain_act(int act) { return act >= 0 && act <= SNNHIP_ACT_SILU; }
@@ -568,7 +573,7 @@ int rule_upsample_pad_conv(Planner& pl, int i, Step& st) {
     if (!up || up->d.mode != SNNHIP_UPSAMPLE_NEAREST || up->d.scale != 2.0f || up->OH != 2 * up->d.H || up->OW != 2 * up->d.W || pl.sw.noPadFusion) return 0;
     auto* pd2 = pl.as<PadPlanBase>(i + 1);
     auto* cv = pl.as<ConvPlanBase>(i + (pd2 ? 2 : 1));
-    if (!cv || cv->depthwise || cv->g.preMode != 0 || cv->desc.rfind("conv2d_mfma", 0) != 0 || cv->g.N != up->d.N || cv->g.IC != up->d.C ||
+    if (!cv || cv->depthwise || cv->g.preMode != 0 || cv->g.C0 || cv->desc.rfind("conv2d_mfma", 0) != 0 || cv->g.N != up->d.N || cv->g.IC != up->d.C ||
         !(pd2 ? (pd2->d.H == up->OH && pd2->d.W == up->OW && cv->g.H == pd2->OH && cv->g.W == pd2->OW) : (cv->g.H == up->OH && cv->g.W == up->OW)))
         return 0;
     ConvGeom g2 = cv->g;
@@ -589,7 +594,7 @@ int rule_upsample_pad_conv(Planner& pl, int i, Step& st) {
 int rule_pad_conv(Planner& pl, int i, Step& st) {
     auto* pd = pl.as<PadPlanBase>(i);
     auto* c1 = pl.as<ConvPlanBase>(i + 1);
-    if (!pd || !c1 || c1->depthwise || c1->g.preMode != 0 || c1->g.N != pd->d.N || c1->g.H != pd->OH || c1->g.W != pd->OW || c1->g.IC != pd->d.C ||
+    if (!pd || !c1 || c1->depthwise || c1->g.preMode != 0 || c1->g.C0 || c1->g.N != pd->d.N || c1->g.H != pd->OH || c1->g.W != pd->OW || c1->g.IC != pd->d.C ||
         !(c1->desc.rfind("conv2d_mfma", 0) == 0 || c1->desc.rfind("conv2d_rowfold", 0) == 0) || pl.sw.noPadFusion)
         return 0;
     ConvGeom g2 = c1->g;
@@ -604,6 +609,40 @@ int rule_pad_conv(Planner& pl, int i, Step& st) {
     if (frc != SNNHIP_OK) return 0;
     fused->ctx = pl.ctx;
     return wrap_plan(pl, fused, true, 2, st);
+}
+
+// ---- rule K: [Concatenate, Conv2D] or [UpSampling2D x2 nearest, Concatenate, Conv2D] (the upsampling feeds the concat's input 0) -> ONE convolution
+// launch that stages its K chunks from the two tensors in turn (conv2d_mfma_kernel.h, CAT instances); the concatenated tensor never exists.  Like
+// rule E the plan takes two inputs -- snnhip_plan_run_n(plan, {input 0 [in front of its upsampling], input 1}, 2, out) -- and is returned as is.
+//
+// Default routing, measured per precision and layer class by tools/bench_cat.py against the Concatenate launch + the layer's own convolution plan in
+// one process (profiles/cat_layers.json): a class is taken where the fused plan won by more than the run's own spread.  That is fp16 with the
+// upsampling on input 0 (YOLOv3-tiny's second head, where the layer's own plan is this kernel too: 34.9 against 38.5 us, three launches become one).
+// The plain concats of U-Net lose -- fp32 0.55x - 0.69x against Concatenate + conv2d_wino, fp16 0.77x - 0.86x against Concatenate + conv2d_wide_f16 on
+// the three large maps, 1.05x inside the spread on the deepest one -- and stay opt-in (SNNHIP_CONV=cat); so does fp32 with the upsampling (0.61x).
+bool cat_default(const ConvGeom& g, bool up) { return g.dtype == SNNHIP_F16 && up; }
+int rule_cat_conv(snnhip_ctx* ctx, const Switches& sw, snnhip_plan* const* plans, int n, snnhip_plan** out) {
+    auto* up = n == 3 ? dynamic_cast<UpsamplePlanBase*>(plans[0]) : nullptr;
+    auto* cv = dynamic_cast<ConvPlanBase*>(plans[n - 1]);
+    snnhip_concat_desc cd;
+    if (sw.noCat || (n == 3 && !up) || !concat_plan_desc(plans[n - 2], &cd) || !cv || cv->depthwise || cv->g.C0 || cv->g.preMode || cv->g.addAct >= 0 || cv->g.normShift)
+        return SNNHIP_E_UNSUPPORTED;
+    if (cd.OC != cd.C0 + cd.C1 || cv->g.IC != cd.OC || cv->g.N != cd.N || cv->g.H != cd.H || cv->g.W != cd.W) return SNNHIP_E_UNSUPPORTED;
+    if (up && (up->d.mode != SNNHIP_UPSAMPLE_NEAREST || up->d.scale != 2.0f || up->OH != 2 * up->d.H || up->OW != 2 * up->d.W || up->d.N != cd.N || up->OH != cd.H ||
+               up->OW != cd.W || up->d.C != cd.C0))
+        return SNNHIP_E_UNSUPPORTED;
+    if (!sw.catForced && !cat_default(cv->g, up != nullptr)) return SNNHIP_E_UNSUPPORTED;
+    ConvGeom g2 = cv->g;
+    g2.C0 = cd.C0;
+    if (up) { // as rule D's [UpSampling2D, Conv2D]: an identity pad in front of the upsampling -- of input 0 only
+        g2.catUp = 1;
+        g2.preMode = SNNHIP_PAD_CONSTANT;
+        g2.preX = g2.preY = 0;
+        g2.preShift = 1;
+        g2.srcH = up->d.H;
+        g2.srcW = up->d.W;
+    }
+    return make_conv2d_mfma_plan(ctx, g2, cv->w_oihw.data(), cv->epi4, out); // SNNHIP_E_UNSUPPORTED: the separate plans stay
 }
 
 int (*const kRules[])(Planner& pl, int i, Step& st) = {rule_stream, rule_a16, rule_b16, rule_a16_wide, rule_b16_wide, rule_a, rule_b, rule_b_mfma, rule_stem_pool, rule_stem_irb, rule_irb, rule_dwpw,
@@ -841,13 +880,17 @@ int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_pl
     if (n == 2 && !sw.noAddFusion) {
         auto* cv = dynamic_cast<ConvPlanBase*>(plans[0]);
         auto* ad = dynamic_cast<EltwisePlanBase*>(plans[1]);
-        if (cv && ad && ad->mode == 0 && !cv->depthwise && cv->g.addAct < 0 && cv->desc.rfind("conv2d_mfma", 0) == 0 && cv->g.act != SNNHIP_ACT_SILU_QUIRK &&
+        if (cv && ad && ad->mode == 0 && !cv->depthwise && cv->g.addAct < 0 && !cv->g.C0 && cv->desc.rfind("conv2d_mfma", 0) == 0 && cv->g.act != SNNHIP_ACT_SILU_QUIRK &&
             ad->d.N == cv->g.N && ad->d.H == cv->g.OH && ad->d.W == cv->g.OW && ad->d.C == cv->g.OC) {
             ConvGeom g2 = cv->g;
             g2.addAct = ad->d.act;
             g2.addLeaky = ad->d.leaky;
             return make_conv2d_mfma_plan(ctx, g2, cv->w_oihw.data(), cv->epi4, out);
         }
+    }
+    if (n == 2 || n == 3) {
+        const int rc = rule_cat_conv(ctx, sw, plans, n, out);
+        if (rc != SNNHIP_E_UNSUPPORTED) return rc;
     }
     for (int i = 0; i < n; ++i)
         if (plans[i]->numInputs != 1 && !(i == n - 1 && plans[i]->numInputs == 2)) {

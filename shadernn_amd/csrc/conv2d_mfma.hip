@@ -36,6 +36,9 @@ KernelFn pick_conv2d_mfma_bn32_f32(int c8, int r, bool simple, int taps);
 KernelFn pick_conv2d_mfma_bn128_f16(int c8, int r, bool simple, int taps);
 KernelFn pick_conv2d_mfma_bn64_f16(int c8, int r, bool simple, int taps);
 KernelFn pick_conv2d_mfma_bn32_f16(int c8, int r, bool simple, int taps);
+// the two-source instances (chain rule K), one translation unit per precision (conv2d_mfma_cat_f{32,16}.hip)
+CatKernelFn pick_conv2d_mfma_cat_f32(int bn, int c8, int r, int taps);
+CatKernelFn pick_conv2d_mfma_cat_f16(int bn, int c8, int r, int taps);
 
 namespace {
 
@@ -128,13 +131,14 @@ namespace {
 
 struct MfmaConvPlan : ConvPlanBase {
     float* d_ws = nullptr; // split-K workspace
-    MfmaParams p;
+    MfmaCatParams p; // (the single-source kernels take its MfmaParams part)
     ActCfg ac;
     float* d_w = nullptr;
     float* d_epi = nullptr;
     size_t ldsBytes = 0;
     dim3 grid;
     void (*kernel)(MfmaParams, ActCfg, const void*, const void*, const float4*, void*, float*) = nullptr;
+    CatKernelFn catKernel = nullptr; // chain rule K: run(input 0, input 1) -> conv(concat(input 0, input 1)), `kernel` is null then
 
     bool fusedAdd = false; // chain rule E: run(x, residual) -> act2(conv(x) + residual)
     bool enableTileStats() override {
@@ -144,7 +148,8 @@ struct MfmaConvPlan : ConvPlanBase {
         const size_t need = std::max(static_cast<size_t>(128) * (BN + 8) * 2, static_cast<size_t>(2) * 256 * 8 * sizeof(float)); // output tile, then the fold scratch over it
         if (need > ldsBytes) {
             if (need > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(need)) != hipSuccess)
+                hipFuncSetAttribute(catKernel ? reinterpret_cast<const void*>(catKernel) : reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(need)) != hipSuccess)
                 return false;
             ldsBytes = need;
         }
@@ -158,10 +163,19 @@ struct MfmaConvPlan : ConvPlanBase {
         return true;
     }
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
-        SNNHIP_REQUIRE(nIn == (fusedAdd ? 2 : 1), "conv2d: expects %d input(s), got %d", fusedAdd ? 2 : 1, nIn);
+        SNNHIP_REQUIRE(nIn == numInputs, "conv2d: expects %d input(s), got %d", numInputs, nIn);
         const snnhip_tensor* x = in[0];
-        MfmaParams p = this->p; // per-launch copy: the residual pointer travels in the kernel argument block
+        MfmaCatParams p = this->p; // per-launch copy: the residual pointer (and input 1's) travels in the kernel argument block
         p.res = nullptr;
+        const int xC = catKernel ? p.C0 : p.IC;
+        if (catKernel) {
+            const snnhip_tensor* x1 = in[1];
+            SNNHIP_REQUIRE(x1->n == p.N && x1->h == p.srcH1 && x1->w == p.srcW1 && x1->c == p.IC - p.C0, "conv2d+concat: input 1 dims %dx%dx%dx%d != plan %dx%dx%dx%d", x1->n,
+                           x1->h, x1->w, x1->c, p.N, p.srcH1, p.srcW1, p.IC - p.C0);
+            SNNHIP_REQUIRE(x->dtype == dtype && x1->dtype == dtype && out->dtype == dtype, "conv2d+concat: tensor dtypes %d, %d -> %d, the plan's is %d", x->dtype, x1->dtype,
+                           out->dtype, dtype);
+            p.x1 = x1->data;
+        }
         if (fusedAdd) {
             const snnhip_tensor* r = in[1];
             SNNHIP_REQUIRE(r->n == p.N && r->h == p.OH && r->w == p.OW && r->c == p.OC && r->dtype == dtype,
@@ -169,12 +183,16 @@ struct MfmaConvPlan : ConvPlanBase {
                            p.OW, p.OC);
             p.res = p.splitK > 1 ? nullptr : static_cast<const void*>(r->data); // split-K: the reduce pass adds it
         }
-        SNNHIP_REQUIRE(x->n == p.N && x->h == p.srcH && x->w == p.srcW && x->c == p.IC, "conv2d: input dims %dx%dx%dx%d != plan %dx%dx%dx%d",
-                       x->n, x->h, x->w, x->c, p.N, p.srcH, p.srcW, p.IC);
+        SNNHIP_REQUIRE(x->n == p.N && x->h == p.srcH && x->w == p.srcW && x->c == xC, "conv2d: input dims %dx%dx%dx%d != plan %dx%dx%dx%d",
+                       x->n, x->h, x->w, x->c, p.N, p.srcH, p.srcW, xC);
         SNNHIP_REQUIRE(out->n == p.N && out->h == p.OH && out->w == p.OW && out->c == p.OC, "conv2d: output dims %dx%dx%dx%d != plan %dx%dx%dx%d",
                        out->n, out->h, out->w, out->c, p.N, p.OH, p.OW, p.OC);
-        SNNHIP_LAUNCH(kernel, grid, dim3(256), ldsBytes, ctx->stream, p, ac, static_cast<const void*>(x->data), static_cast<const void*>(d_w),
-                           reinterpret_cast<const float4*>(d_epi), static_cast<void*>(out->data), d_ws);
+        if (catKernel)
+            SNNHIP_LAUNCH(catKernel, grid, dim3(256), ldsBytes, ctx->stream, p, ac, static_cast<const void*>(x->data), static_cast<const void*>(d_w),
+                          reinterpret_cast<const float4*>(d_epi), static_cast<void*>(out->data), d_ws);
+        else
+            SNNHIP_LAUNCH(kernel, grid, dim3(256), ldsBytes, ctx->stream, static_cast<const MfmaParams&>(p), ac, static_cast<const void*>(x->data), static_cast<const void*>(d_w),
+                          reinterpret_cast<const float4*>(d_epi), static_cast<void*>(out->data), d_ws);
         if (p.splitK > 1)
             return launch_splitk_reduce(ctx, p.OC, p.splitK, p.useBN, ac, d_ws, reinterpret_cast<const float4*>(d_epi), out, fusedAdd ? in[1] : nullptr, p.ac2);
         SNNHIP_CHECK_HIP(hipGetLastError());
@@ -203,8 +221,14 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     // and the 16-wide thin layers (OC < 32 with IC < 32, e.g. ESPCN's 16->16: half of the narrowest 32-wide block is padding) measured
     // faster there too (241 vs 276 us at 1080p)
     const bool f16 = g.dtype == SNNHIP_F16; // fp16 tensors: this is the only general convolution kernel, it takes every shape
-    if (!forced && !f16 && (g.OC < 16 || (g.OC < 32 && g.IC < 32))) return SNNHIP_E_UNSUPPORTED;
-    const double inCount = static_cast<double>(g.N) * (g.preMode ? g.srcH : g.H) * (g.preMode ? g.srcW : g.W) * g.IC;
+    const bool cat = g.C0 > 0;              // chain rule K: this is the only kernel with the two-source staging
+    if (!forced && !f16 && !cat && (g.OC < 16 || (g.OC < 32 && g.IC < 32))) return SNNHIP_E_UNSUPPORTED;
+    // two sources: stride 1, the simple epilogue, no third input (fused Add), no norm in the staging; input 0's channels are whole texel planes
+    // (the reference concatenates planes: with C0 % 4 != 0 its result has a gap, quirk Q21, and the separate Concatenate keeps it)
+    if (cat && (g.C0 >= g.IC || g.C0 % 4 != 0 || g.sh != 1 || g.sw != 1 || !act_is_simple(g.act) || g.addAct >= 0 || g.normShift || (g.catUp && (g.preShift != 1 || !g.preMode))))
+        return SNNHIP_E_UNSUPPORTED;
+    const bool fullSize = !g.preMode || g.catUp; // (catUp: input 1 is at the convolution's size -- IC channels there bound both inputs)
+    const double inCount = static_cast<double>(g.N) * (fullSize ? g.H : g.srcH) * (fullSize ? g.W : g.srcW) * g.IC;
     const double outCount = static_cast<double>(g.N) * g.OH * g.OW * g.OC;
     if (inCount >= 2147483647.0 || outCount >= 2147483647.0) return SNNHIP_E_UNSUPPORTED; // 32-bit element offsets in the kernel
 
@@ -289,12 +313,18 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         }
     }
     if (best < 0) return SNNHIP_E_UNSUPPORTED;
-    MfmaParams p{};
+    if (cat && (C8 == 0 || C8 > 2 || g.C0 % ICc != 0)) return SNNHIP_E_UNSUPPORTED; // a chunk lies wholly in one source
+    MfmaCatParams p{};
     p.N = g.N; p.H = g.H; p.W = g.W; p.IC = g.IC; p.OC = g.OC; p.kh = g.kh; p.kw = g.kw; p.sh = g.sh; p.sw = g.sw;
     p.padx = g.padx; p.pady = g.pady; p.padMode = g.padMode; p.useBN = g.useBN; p.OH = g.OH; p.OW = g.OW;
     p.preMode = g.preMode; p.preX = g.preX; p.preY = g.preY; p.preShift = g.preMode ? g.preShift : 0;
     p.srcH = g.preMode ? g.srcH : g.H;
     p.srcW = g.preMode ? g.srcW : g.W;
+    p.x1 = nullptr;
+    p.C0 = g.C0;
+    p.srcH1 = g.catUp ? g.H : p.srcH; // catUp: input 1 is at the convolution's own size, under an identity pad
+    p.srcW1 = g.catUp ? g.W : p.srcW;
+    p.preShift1 = g.catUp ? 0 : p.preShift;
     p.res = nullptr;
     p.statPart = nullptr;
     p.ac2 = make_act_cfg(g.addAct >= 0 ? g.addAct : SNNHIP_ACT_NONE, g.addLeaky);
@@ -378,15 +408,17 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     p.normTabOfs = static_cast<int>(ldsNeed / 4);
     if (preNorm) ldsNeed += static_cast<size_t>(2) * g.IC * sizeof(float); // [shift | mul] behind the staging buffers
     p.coordTabOfs = static_cast<int>(ldsNeed / 4);
-    ldsNeed += static_cast<size_t>(p.tileH + p.tileW) * sizeof(int); // the staging's row / column tables
+    ldsNeed += static_cast<size_t>(p.tileH + p.tileW) * sizeof(int) * (cat ? 2 : 1); // the staging's row / column tables (one pair per source)
     if (p.ldsEpi) ldsNeed = std::max(ldsNeed, static_cast<size_t>(128) * (BN + 8) * 2);
     const bool simple = act_is_simple(g.act);
     KernelFn fn = nullptr;
+    CatKernelFn catFn = nullptr;
     const int staticTaps = p.c8Outer ? 0 : taps; // (the half-by-half order lives in the run-time tap loop)
-    if (BN == 128) fn = f16 ? pick_conv2d_mfma_bn128_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn128_f32(C8, R, simple, taps);
+    if (cat) catFn = f16 ? pick_conv2d_mfma_cat_f16(BN, C8, R, staticTaps) : pick_conv2d_mfma_cat_f32(BN, C8, R, taps);
+    else if (BN == 128) fn = f16 ? pick_conv2d_mfma_bn128_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn128_f32(C8, R, simple, taps);
     if (BN == 64) fn = f16 ? pick_conv2d_mfma_bn64_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn64_f32(C8, R, simple, taps);
     if (BN == 32) fn = f16 ? pick_conv2d_mfma_bn32_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn32_f32(C8, R, simple, taps);
-    if (!fn) return SNNHIP_E_UNSUPPORTED;
+    if (!fn && !catFn) return SNNHIP_E_UNSUPPORTED;
 
     auto* plan = new MfmaConvPlan();
     plan->ctx = ctx;
@@ -396,9 +428,10 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     plan->p = p;
     plan->ac = make_act_cfg(g.act, g.leaky);
     plan->kernel = fn;
+    plan->catKernel = catFn;
     plan->ldsBytes = ldsNeed;
     plan->fusedAdd = g.addAct >= 0;
-    if (plan->fusedAdd) plan->numInputs = 2;
+    if (plan->fusedAdd || cat) plan->numInputs = 2;
     plan->grid = dim3(p.tilesX * p.tilesY * up_div(g.N, TB), p.OCp / BN, p.splitK);
     if (p.splitK > 1) {
         void* ws = nullptr;
@@ -412,7 +445,8 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         plan->d_ws = static_cast<float*>(ws);
     }
     if (ldsNeed > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsNeed));
+        hipError_t e = hipFuncSetAttribute(cat ? reinterpret_cast<const void*>(catFn) : reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(ldsNeed));
         if (e != hipSuccess) {
             set_error("hipFuncSetAttribute(%zu) failed: %s", ldsNeed, hipGetErrorString(e));
             delete plan;
@@ -460,7 +494,7 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         delete plan;
         return rc;
     }
-    plan->inDims[0] = g.N; plan->inDims[1] = p.srcH; plan->inDims[2] = p.srcW; plan->inDims[3] = g.IC;
+    plan->inDims[0] = g.N; plan->inDims[1] = p.srcH; plan->inDims[2] = p.srcW; plan->inDims[3] = cat ? g.C0 : g.IC;
     plan->outDims[0] = g.N; plan->outDims[1] = g.OH; plan->outDims[2] = g.OW; plan->outDims[3] = g.OC;
     plan->flops = 2.0 * taps * g.IC * g.OC * static_cast<double>(g.OH) * g.OW * g.N;
     plan->bytes = 4.0 * (static_cast<double>(g.N) * g.H * g.W * g.IC + static_cast<double>(g.N) * g.OH * g.OW * g.OC +
@@ -475,8 +509,14 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     const double esz = f16 ? 2.0 : 4.0;
     plan->bytes = esz * (static_cast<double>(g.N) * p.srcH * p.srcW * g.IC + static_cast<double>(g.N) * g.OH * g.OW * g.OC + static_cast<double>(g.OC) * g.IC * taps);
     plan->desc = buf;
-    if (g.preMode) plan->desc += " +pad(" + std::string(g.preMode == SNNHIP_PAD_REFLECT ? "reflect" : g.preMode == SNNHIP_PAD_REPLICATE ? "replicate" : "constant") + ")";
-    if (g.preMode && g.preShift) plan->desc += " +upsample(x2)";
+    if (cat) { // both inputs once, no concatenated tensor
+        plan->bytes = esz * (static_cast<double>(g.N) * p.srcH * p.srcW * g.C0 + static_cast<double>(g.N) * p.srcH1 * p.srcW1 * (g.IC - g.C0) +
+                             static_cast<double>(g.N) * g.OH * g.OW * g.OC + static_cast<double>(g.OC) * g.IC * taps);
+        plan->desc += " +concat(" + std::to_string(g.C0) + "+" + std::to_string(g.IC - g.C0) + ")";
+        if (g.catUp) plan->desc += " +upsample(x2 on input 0)";
+    }
+    if (g.preMode && !g.catUp) plan->desc += " +pad(" + std::string(g.preMode == SNNHIP_PAD_REFLECT ? "reflect" : g.preMode == SNNHIP_PAD_REPLICATE ? "replicate" : "constant") + ")";
+    if (g.preMode && g.preShift && !g.catUp) plan->desc += " +upsample(x2)";
     if (plan->fusedAdd) {
         plan->desc += " +add";
         plan->bytes += esz * static_cast<double>(g.N) * g.OH * g.OW * g.OC; // the residual is read once
@@ -491,6 +531,8 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
 // heuristics were fitted on a handful of shapes; measured on the ResNet-18 body (fp16, batch 32) the best candidate is 10-25 % faster on
 // the 28x28 / 14x14 / 7x7 stages, where block count, residency and the split-K reduce pass trade against each other.
 int make_conv2d_mfma_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out) {
+    // two sources (chain rule K): the kernel of this file is the only one whose staging takes them
+    if (g.C0 > 0) return make_conv2d_mfma_plan_ex(ctx, g, w_oihw, epi4, MfmaOverride(), out);
     // fp32 3x3 stride-1 layers with GEMM-sized channel counts: Winograd F(2x2,3x3) on the matrix pipe (conv2d_wino.hip), 2.25x fewer MFMA
     // flops than the implicit GEMM below.  SNNHIP_CONV=wino forces it for every eligible shape, SNNHIP_CONV=mfma / SNNHIP_CONV_WINO=0 keep
     // the direct kernel (tests run both on the same inputs).

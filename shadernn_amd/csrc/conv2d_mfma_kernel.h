@@ -54,6 +54,17 @@ struct MfmaParams { // (declared after ActCfg: epilogue.h)
     int coordTabOfs; // float offset in LDS of the staging's row / column tables (tileH + tileW ints)
 };
 
+// Two-source staging (chain rule K, the CAT instances of conv2d_mfma_cat_bn*.hip): the convolution reads Concatenate(input 0, input 1) without the
+// concatenated tensor ever existing.  K walks input 0's C0 channels, then input 1's IC - C0; C0 is a multiple of the channel chunk, so a chunk lies
+// wholly in one source and the block changes source ONCE, between two chunks: base pointer, pixel pitch, channel offset and the elements' global
+// offsets are set there (set_source below), nothing is chosen per element.  The single-source instances compile none of it.  Each source resolves padding and the
+// upsampling shift against its own extent (YOLOv3-tiny: input 0 sits behind a nearest x2 UpSampling2D, input 1 is at the convolution's size).
+struct MfmaCatParams : MfmaParams {
+    const void* x1;               // input 1: [N][srcH1][srcW1][IC - C0] (input 0 is the kernel's x: [N][srcH][srcW][C0])
+    int C0;                       // channels taken from input 0
+    int srcH1, srcW1, preShift1;  // input 1's extent and upsampling shift (input 0: srcH, srcW, preShift)
+};
+
 // LDS layout of the staged activations.  A pixel owns ICc floats = ICc/4 16-byte slots; the slot is XOR-swizzled with
 // bits of the linear pixel index so that the 16-byte bank slot (address/16 mod 16) is a bijection of (pixel mod 16):
 // a ds_read_b128 lane group (16 lanes: {0-3,12-15,20-27} / {4-11,16-19,28-31} of each half-wave, MI355X_MICROARCH.md
@@ -80,8 +91,8 @@ __device__ __forceinline__ int lds_off(int pl, int slot) {
 // is ONE 16-byte slot and the K axis runs over the taps instead of the channels -- the two lane halves of a K step read two DIFFERENT taps
 // (h = 0: tap 2j, h = 1: tap 2j+1) of the same pixel slot layout, so a 7x7x3 stem takes 25 K steps instead of 49 and 3 of every 4 (fp32)
 // operand lanes carry data instead of 3 of 8.  Weights are packed [step][h][oc] to match; an odd tap count pads the last h = 1 half with zeros.
-template <int WM, int WN, int MT, int NT, int C8, int R, bool SIMPLE, bool F16, int TAPS = 0>
-__global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCfg ac, const void* __restrict__ xv, const void* __restrict__ wpv,
+template <int WM, int WN, int MT, int NT, int C8, int R, bool SIMPLE, bool F16, int TAPS = 0, bool CAT = false>
+__global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(typename std::conditional<CAT, MfmaCatParams, MfmaParams>::type p, ActCfg ac, const void* __restrict__ xv, const void* __restrict__ wpv,
                                                           const float4* __restrict__ epi, void* __restrict__ yv, float* __restrict__ ws) {
     static_assert(WM * WN == 4, "4 waves per block");
     static_assert(WM * MT == 4, "128 pixels per block");
@@ -111,6 +122,11 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
     const int ix0 = ox0 * p.sw - p.padx, iy0 = oy0 * p.sh - p.pady;
     const int taps = p.kh * p.kw;
     const bool vec4 = (p.IC % CH) == 0;
+    // CAT: the source of the chunks being staged -- its tensor, its channel count (= pixel pitch), where its channels start on the K axis, whether
+    // its pixels are whole 16-byte slots (set_source below); the single-source instances never touch these
+    const T* xs = x;
+    int srcC = p.IC, srcC0 = 0;
+    bool srcVec4 = vec4;
 
     // ---- the source pixel of a staged pixel is separable (its row depends on the tile row only, its column on the tile column only): padding /
     // fused Pad / fused UpSampling are resolved once per tile row and column into two LDS tables, an element below is two look-ups (resolved per
@@ -125,6 +141,17 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
             s1 = s1 < 0 ? -1 : (pp < 0 ? -1 : pp >> p.preShift); // nearest x2: upsampled pixel (y, x) is source pixel (y / 2, x / 2) (vk_upsampling2d_nearest.comp:50-65)
         }
         syTab[i] = (isRow && s1 >= 0) ? s1 * p.srcW : s1;
+    }
+    if constexpr (CAT) { // the same two tables for input 1, resolved against ITS extent and shift, behind input 0's
+        for (int i = tid; i < p.tileH + p.tileW; i += 256) {
+            const bool isRow = i < p.tileH;
+            int s1 = resolve_nobranch(isRow ? iy0 + i : ix0 + (i - p.tileH), isRow ? p.H : p.W, p.padMode);
+            if (p.preMode) {
+                const int pp = resolve_nobranch(s1 - (isRow ? p.preY : p.preX), (isRow ? p.srcH1 : p.srcW1) << p.preShift1, p.preMode);
+                s1 = s1 < 0 ? -1 : (pp < 0 ? -1 : pp >> p.preShift1);
+            }
+            sxTab[p.tileW + i] = (isRow && s1 >= 0) ? s1 * p.srcW1 : s1;
+        }
     }
     __syncthreads();
 
@@ -150,13 +177,51 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
             if (rowPix >= 0 && sx >= 0 && n < p.N) gofs[r] = (n * p.srcH * p.srcW + rowPix + sx) * p.IC + q * CH;
         }
     }
+    // CAT: input `s` becomes the source of the chunks staged from here on (block-uniform: at the start, and once more where K crosses C0) -- the
+    // elements keep their LDS slots, their global offsets are taken again from that input's tables, extent and pixel pitch
+    auto set_source = [&](int s) {
+        if constexpr (CAT) {
+            xs = s ? static_cast<const T*>(p.x1) : x;
+            srcC = s ? p.IC - p.C0 : p.C0;
+            srcC0 = s ? p.C0 : 0;
+            srcVec4 = (srcC % CH) == 0;
+            const int* const rowTab = s ? sxTab + p.tileW : syTab;
+            const int* const colTab = rowTab + p.tileH;
+            const int sH = s ? p.srcH1 : p.srcH, sW = s ? p.srcW1 : p.srcW;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int e = tid + 256 * r;
+                gofs[r] = -1;
+                if (e < p.total) {
+                    const int pix = e / Q;
+                    const int t2 = p.tileW == 1 ? pix : static_cast<int>(__umulhi(static_cast<unsigned>(pix), p.magicW));
+                    const int b = p.tileH == 1 ? t2 : static_cast<int>(__umulhi(static_cast<unsigned>(t2), p.magicH));
+                    const int rowPix = rowTab[t2 - b * p.tileH], sx = colTab[pix - t2 * p.tileW];
+                    if (rowPix >= 0 && sx >= 0 && b0 + b < p.N) gofs[r] = ((b0 + b) * sH * sW + rowPix + sx) * srcC + q * CH;
+                }
+            }
+        }
+    };
+    if constexpr (CAT) set_source(static_cast<int>(blockIdx.z) * p.chunksPerSplit * (2 * CH * C8) >= p.C0 ? 1 : 0); // (a split of K may start inside input 1)
     float4 stage[R];
     auto stage_load = [&](int ic0) {
         const int icq = ic0 + q * CH;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gofs[r] >= 0 && icq < p.IC && !(SNNHIP_ABL & 4)) { // ablation bit 4: no activation loads
+            if constexpr (CAT) { // the same load with the current source's tensor, channel count and channel origin
+                if (gofs[r] >= 0 && icq - srcC0 < srcC) {
+                    const T* src = xs + gofs[r] + (ic0 - srcC0);
+                    if (srcVec4) {
+                        v = *reinterpret_cast<const float4*>(src);
+                    } else {
+                        T tmp[CH];
+#pragma unroll
+                        for (int j = 0; j < CH; ++j) tmp[j] = icq - srcC0 + j < srcC ? src[j] : static_cast<T>(0.0f);
+                        v = *reinterpret_cast<const float4*>(tmp);
+                    }
+                }
+            } else if (gofs[r] >= 0 && icq < p.IC && !(SNNHIP_ABL & 4)) { // ablation bit 4: no activation loads
                 const T* src = x + gofs[r] + ic0;
                 if (vec4) {
                     v = *reinterpret_cast<const float4*>(src);
@@ -285,6 +350,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
     for (int chunk = chunk0; chunk < chunk1; ++chunk) {
         const float* cur = smem + ((chunk - chunk0) & 1) * p.bufFloats;
         const bool more = chunk + 1 < chunk1;
+        if constexpr (CAT)
+            if (more && srcC0 == 0 && (chunk + 1) * 2 * CH * C8 >= p.C0) set_source(1); // (uniform) the next chunk is input 1's first
         if (more) stage_load((chunk + 1) * 2 * CH * C8);
 
         float4 an[MT];
@@ -598,6 +665,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(MfmaParams p, ActCf
 // split-K second pass: y[m][oc] = act(BN(bias + sum_z ws[z][m][oc])), summed in a fixed order (deterministic)
 typedef void (*KernelFn)(MfmaParams, ActCfg, const void*, const void*, const float4*, void*, float*);
 
+typedef void (*CatKernelFn)(MfmaCatParams, ActCfg, const void*, const void*, const float4*, void*, float*);
+
 // the variant table, one precision per instantiation (F16 is a template parameter so that a translation unit compiles one precision only)
 template <int WM, int WN, int MT, int NT, bool F16>
 KernelFn pick_kernel(int c8, int r, bool simple, int taps) {
@@ -627,6 +696,32 @@ KernelFn pick_kernel(int c8, int r, bool simple, int taps) {
     SNNHIP_PICK(4, 5)
     SNNHIP_PICK(4, 9)
     SNNHIP_PICK(8, 9)
+#undef SNNHIP_PICK
+    return nullptr;
+}
+
+// ... and the two-source instances (conv2d_mfma_cat_bn*.hip): whole channel chunks (no tap pairs), the chunk widths the planner picks for stride-1
+// layers, the activations of the simple epilogue
+template <int WM, int WN, int MT, int NT, bool F16>
+CatKernelFn pick_kernel_cat(int c8, int r, int taps) {
+    if constexpr (F16) {
+#define SNNHIP_PICK_T(C8_, R_, T_) \
+    if (taps == T_ && c8 == C8_ && r == R_) return conv2d_mfma_kernel<WM, WN, MT, NT, C8_, R_, true, true, T_, true>;
+        if (!snnhip::option("SNNHIP_CONV_ROLLED")) {
+            SNNHIP_PICK_T(1, 3, 9)
+            SNNHIP_PICK_T(2, 3, 9)
+            SNNHIP_PICK_T(2, 5, 9)
+        }
+#undef SNNHIP_PICK_T
+    }
+#define SNNHIP_PICK(C8_, R_) \
+    if (c8 == C8_ && r == R_) return conv2d_mfma_kernel<WM, WN, MT, NT, C8_, R_, true, F16, 0, true>;
+    SNNHIP_PICK(1, 3)
+    SNNHIP_PICK(1, 5)
+    SNNHIP_PICK(1, 9)
+    SNNHIP_PICK(2, 3)
+    SNNHIP_PICK(2, 5)
+    SNNHIP_PICK(2, 9)
 #undef SNNHIP_PICK
     return nullptr;
 }

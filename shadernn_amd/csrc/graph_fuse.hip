@@ -4,6 +4,8 @@
 // E Conv2D -> Add, F Conv2D -> InstanceNorm).  This file only decides which groups of a DAG are offered to it:
 //   0. inverted-residual blocks with a skip connection: Add(project(depthwise(expand(X))), X) (MobileNetV2);
 //   1. residual pairs: an Add one of whose inputs is a convolution that nobody else reads (ResNet skip connections);
+//   1c. skip concatenations: a Concatenate that only a convolution reads, input 0 optionally through an UpSampling2D nobody else reads (rule K:
+//      the U-Net decoder, YOLOv3-tiny's second head);
 //   2. maximal linear runs: node t+1 reads only node t, node t is read only by node t+1 (Candy's pad -> conv -> norm strings, ESPCN).
 // Counterpart in the reference: none -- it dispatches one compute shader per layer (vulkanRenderpass.cpp:257-259).
 #include <vector>
@@ -139,6 +141,43 @@ extern "C" int snnhip_graph_fuse(snnhip_ctx* ctx, const snnhip_graph_node* nodes
             out[src].n_inputs = 0;
             taken[static_cast<size_t>(k)] = taken[static_cast<size_t>(src)] = 1;
             break;
+        }
+    }
+
+    // ---- 1c. [UpSampling2D x2 ->] Concatenate -> Conv2D (rule K): a Concatenate that only a convolution reads -> the fused plan sits at the
+    // convolution node and reads the concat's two producers (input 0 through an upsampling that nobody else reads: its producer instead)
+    for (int k = 0; k < n; ++k) {
+        if (!nodes[k].plan || nodes[k].n_inputs != 1 || taken[static_cast<size_t>(k)]) continue;
+        const int cat = nodes[k].inputs[0];
+        auto* cv = dynamic_cast<ConvPlanBase*>(nodes[k].plan);
+        if (!cv || cv->depthwise || !foldable(cat) || nodes[cat].n_inputs != 2 || !concat_plan_desc(nodes[cat].plan, nullptr)) continue;
+        const int up = nodes[cat].inputs[0];
+        const bool viaUp = foldable(up) && nodes[up].n_inputs == 1 && up != nodes[cat].inputs[1] && dynamic_cast<UpsamplePlanBase*>(nodes[up].plan);
+        snnhip_plan* fused = nullptr;
+        int rc = SNNHIP_E_UNSUPPORTED;
+        if (viaUp) {
+            snnhip_plan* three[3] = {nodes[up].plan, nodes[cat].plan, nodes[k].plan};
+            rc = make_chain_plan(ctx, three, 3, &fused);
+        }
+        const bool withUp = rc == SNNHIP_OK;
+        if (rc == SNNHIP_E_UNSUPPORTED) {
+            snnhip_plan* pair[2] = {nodes[cat].plan, nodes[k].plan};
+            rc = make_chain_plan(ctx, pair, 2, &fused);
+        }
+        if (rc == SNNHIP_E_UNSUPPORTED) continue;
+        if (rc != SNNHIP_OK) return fail(rc);
+        out[k].plan = fused;
+        out[k].owned = 1;
+        out[k].n_inputs = 2;
+        out[k].inputs[0] = withUp ? nodes[up].inputs[0] : up;
+        out[k].inputs[1] = nodes[cat].inputs[1];
+        out[cat].plan = nullptr;
+        out[cat].n_inputs = 0;
+        taken[static_cast<size_t>(k)] = taken[static_cast<size_t>(cat)] = 1;
+        if (withUp) {
+            out[up].plan = nullptr;
+            out[up].n_inputs = 0;
+            taken[static_cast<size_t>(up)] = 1;
         }
     }
 

@@ -340,6 +340,13 @@ struct DeconvPlan : snnhip_plan {
 };
 
 } // namespace
+
+bool concat_plan_desc(const snnhip_plan* plan, snnhip_concat_desc* d) {
+    auto* p = dynamic_cast<const ConcatPlan*>(plan);
+    if (p && d) *d = p->d;
+    return p != nullptr;
+}
+
 } // namespace snnhip
 
 using namespace snnhip;

@@ -224,6 +224,11 @@ struct ConvGeom {
     const float* normMul = nullptr;
     int normAct = 0; // none / relu / relu6 / leakyRelu only
     float normLeaky = 0.0f;
+    // Concatenate in front of the convolution (chain rule K): the plan takes TWO inputs, channels [0, C0) of the convolution's input are input 0's,
+    // [C0, IC) are input 1's (a tensor of IC - C0 channels); 0 = none.  catUp: input 0 ALONE sits behind a nearest x2 UpSampling2D -- preMode /
+    // preShift / srcH / srcW describe input 0 (as rule D sets them for [UpSampling2D, Conv2D]), input 1 is at the convolution's own H x W.
+    int C0 = 0;
+    int catUp = 0;
 };
 int resolve_conv_geom(const snnhip_conv2d_desc* d, bool depthwise, ConvGeom* g);
 
@@ -305,6 +310,8 @@ bool u8_out_plan_desc(const snnhip_plan* plan, snnhip_u8_out_desc* d);
 // frame_u16.hip: the same for the 16-bit frame conversions
 bool u16_in_plan_desc(const snnhip_plan* plan, snnhip_u16_in_desc* d);
 bool u16_out_plan_desc(const snnhip_plan* plan, snnhip_u16_out_desc* d);
+// shape_ops.hip: identify a Concatenate plan (chain rule K folds it into the convolution behind it)
+bool concat_plan_desc(const snnhip_plan* plan, snnhip_concat_desc* d);
 // eltwise_pool.hip: identify a Pooling plan (resolved output dims included)
 bool pool2d_plan_desc(const snnhip_plan* plan, snnhip_pool2d_desc* d);
 // conv2d_stem_f32.hip, chain rule J: Conv2D 7x7 stride 2 of an RGB image -> MaxPooling2D 3x3 stride 2 (the head of ResNet-18) as one launch: the pooling
