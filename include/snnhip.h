@@ -792,7 +792,11 @@ int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);
  * its upsampling], input 1}, 2, out); its description carries "+concat(C0+C1)" [and "+upsample(x2 on input 0)"], its cost counts both inputs once
  * and no concatenated tensor.  Opt-in (SNNHIP_CONV=cat) except where it was measured faster; SNNHIP_CAT=0 switches it off.  C0 must be a multiple of the
  * kernel's channel chunk (16 fp32 / 32 fp16 channels, 8 / 16 where the planner halves it) and of 4, OC == C0 + C1, stride 1, activation none / relu / relu6 / leakyRelu;
- * anything else returns SNNHIP_E_UNSUPPORTED and the caller keeps its plans. */
+ * anything else returns SNNHIP_E_UNSUPPORTED and the caller keeps its plans.
+ * Rule L: {Conv2D stride 1, MaxPooling2D 2x2 stride 2 without padding} become ONE convolution launch that writes the pooled
+ * tensor; its description carries "+maxpool(2x2)", its cost counts the input, the weights and the pooled output.  Off unless SNNHIP_POOL_FUSE=1
+ * (environment or snnhip_set_option); SNNHIP_CONV=pool takes it wherever it can run.  Max pooling only, activation none / relu / relu6 / leakyRelu,
+ * IC * kh * kw <= 1152, no fused Pad / Add / norm on the convolution; anything else keeps the separate plans. */
 int snnhip_chain_plan_create(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_plan** out);
 /* The fp16 ESPCN rules (SNNHIP_ESPCN_F16=1) keep their weights as lane-ordered fp16 images for the f16 matrix cores.  This
  * is the packing itself, host side only (no context, no device), so that it can be checked without a GPU.  w_oihw is fp32 and is rounded to nearest

@@ -11,7 +11,7 @@
 //   A16 / B16 wide   the same at the published widths 1 -> 64 -> 32 -> r*r, fp16 only, same switch   -> espcn_f16_wide.hip
 //   A    conv KxK (1 -> 16) + act -> conv 3x3 (16 -> 16) + act        -> kernel A (espcn_fused.hip)
 //   B    conv 3x3 (16 -> r*r) + act -> depth-to-space(r) + tanh       -> kernel B (r = 2: espcn_fused.hip; r = 3, 4: espcn_d2s_mfma.hip)
-//   J, G D                                                            -> plans of conv2d_stem_f32.hip, irb_fused.hip / dwpw_march.hip, conv2d_mfma.hip
+//   J, L, G, D                                                        -> plans of conv2d_stem_f32.hip, conv2d_mfma.hip (L: Conv2D -> MaxPooling2D 2x2, opt-in), irb_fused.hip / dwpw_march.hip, conv2d_mfma.hip
 // and three passes over the steps they built: I (InstanceNorm -> convolution), F (convolution -> InstanceNorm, with H and I behind it) and the
 // 8-bit ends A8 / B8 (and their fp16 forms).
 #include <cstdlib>
@@ -53,6 +53,9 @@ struct Switches {
     const char* const catWord = option("SNNHIP_CAT");
     const bool noCat = catWord && atoi(catWord) == 0;
     const bool catForced = is(option("SNNHIP_CONV"), "cat");
+    // rule L: opt-in -- SNNHIP_POOL_FUSE=1 switches it on, SNNHIP_CONV=pool takes it wherever it can run
+    const char* const poolWord = option("SNNHIP_POOL_FUSE");
+    const bool poolFuse = (poolWord && poolWord[0] && strcmp(poolWord, "0") != 0) || is(option("SNNHIP_CONV"), "pool");
 };
 
 bool plain_act(int act) { return act >= 0 && act <= SNNHIP_ACT_SILU; }
@@ -537,6 +540,27 @@ int rule_stem_pool(Planner& pl, int i, Step& st) {
     return built ? wrap_plan(pl, spool, true, 2, st) : 0;
 }
 
+// ---- rule L: Conv2D stride 1 (+bias, BN, simple activation) -> MaxPooling2D 2x2 stride 2 (YOLOv3-tiny's backbone) -> ONE conv2d_mfma launch whose M axis
+// walks the tile window-major, so that a lane's four accumulator rows are one pooling window (conv2d_mfma_kernel.h, POOL instances); the full-resolution
+// tensor never exists.  Opt-in (SNNHIP_POOL_FUSE=1 / SNNHIP_CONV=pool).  K = IC * kh * kw <= 1152: the longest single chain the error budgets of the fp32
+// / fp16 convolution tests were measured for without a split over K, which the pooling epilogue cannot take.
+int rule_conv_pool(Planner& pl, int i, Step& st) {
+    auto* cv = pl.as<ConvPlanBase>(i);
+    snnhip_pool2d_desc pd;
+    if (!pl.sw.poolFuse || !cv || i + 1 >= pl.n || !pool2d_plan_desc(pl.plans[i + 1], &pd) || cv->depthwise) return 0;
+    const ConvGeom& g = cv->g;
+    if (pd.type != SNNHIP_POOL_MAX || pd.kh != 2 || pd.kw != 2 || pd.sh != 2 || pd.sw != 2 || pd.padT != 0 || pd.padL != 0 || pd.N != g.N || pd.H != g.OH || pd.W != g.OW || pd.C != g.OC)
+        return 0;
+    if (!((pd.OH == g.OH / 2 || pd.OH == (g.OH + 1) / 2) && (pd.OW == g.OW / 2 || pd.OW == (g.OW + 1) / 2))) return 0;
+    if (g.sh != 1 || g.sw != 1 || g.preMode || g.C0 || g.poolOH || g.addAct >= 0 || g.normShift || cv->numInputs != 1 || !act_is_simple(g.act) || g.IC * g.kh * g.kw > 1152) return 0;
+    ConvGeom g2 = g;
+    g2.poolOH = pd.OH;
+    g2.poolOW = pd.OW;
+    snnhip_plan* fused = nullptr;
+    if (make_conv2d_mfma_plan(pl.ctx, g2, cv->w_oihw.data(), cv->epi4, &fused) != SNNHIP_OK) return 0;
+    return wrap_plan(pl, fused, true, 2, st);
+}
+
 // ---- rule G with the network's stem as the 'expand' layer: Conv2D 3x3 (3 -> C channels) -> DepthwiseConv2D 3x3 -> Conv2D 1x1 (the head of
 // MobileNetV2) -> the same kernel, its staging gathers the 27 image values per pixel; the stem's output never reaches memory
 int rule_stem_irb(Planner& pl, int i, Step& st) {
@@ -645,7 +669,7 @@ int rule_cat_conv(snnhip_ctx* ctx, const Switches& sw, snnhip_plan* const* plans
     return make_conv2d_mfma_plan(ctx, g2, cv->w_oihw.data(), cv->epi4, out); // SNNHIP_E_UNSUPPORTED: the separate plans stay
 }
 
-int (*const kRules[])(Planner& pl, int i, Step& st) = {rule_stream, rule_a16, rule_b16, rule_a16_wide, rule_b16_wide, rule_a, rule_b, rule_b_mfma, rule_stem_pool, rule_stem_irb, rule_irb, rule_dwpw,
+int (*const kRules[])(Planner& pl, int i, Step& st) = {rule_stream, rule_a16, rule_b16, rule_a16_wide, rule_b16_wide, rule_a, rule_b, rule_b_mfma, rule_stem_pool, rule_conv_pool, rule_stem_irb, rule_irb, rule_dwpw,
                            rule_upsample_pad_conv, rule_pad_conv};
 
 // ---- rule I: an InstanceNorm step followed by a convolution step (as given, or built by rule D above) whose kernel can normalise in its

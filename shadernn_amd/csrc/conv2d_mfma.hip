@@ -39,6 +39,9 @@ KernelFn pick_conv2d_mfma_bn32_f16(int c8, int r, bool simple, int taps);
 // the two-source instances (chain rule K), one translation unit per precision (conv2d_mfma_cat_f{32,16}.hip)
 CatKernelFn pick_conv2d_mfma_cat_f32(int bn, int c8, int r, int taps);
 CatKernelFn pick_conv2d_mfma_cat_f16(int bn, int c8, int r, int taps);
+// the pooling instances (chain rule L), one translation unit per precision (conv2d_mfma_pool_f{32,16}.hip)
+PoolKernelFn pick_conv2d_mfma_pool_f32(int bn, int c8, int r, int taps);
+PoolKernelFn pick_conv2d_mfma_pool_f16(int bn, int c8, int r, int taps);
 
 namespace {
 
@@ -139,11 +142,13 @@ struct MfmaConvPlan : ConvPlanBase {
     dim3 grid;
     void (*kernel)(MfmaParams, ActCfg, const void*, const void*, const float4*, void*, float*) = nullptr;
     CatKernelFn catKernel = nullptr; // chain rule K: run(input 0, input 1) -> conv(concat(input 0, input 1)), `kernel` is null then
+    PoolKernelFn poolKernel = nullptr; // chain rule L: run(x) -> maxpool2x2(conv(x)) into a tensor of the pooled extent, `kernel` is null then
+    int poolOH = 0, poolOW = 0;
 
     bool fusedAdd = false; // chain rule E: run(x, residual) -> act2(conv(x) + residual)
     bool enableTileStats() override {
         if (statPart) return true;
-        if (dtype != SNNHIP_F16 || !p.ldsEpi || p.splitK != 1 || p.TBs != 0 || fusedAdd) return false;
+        if (dtype != SNNHIP_F16 || !p.ldsEpi || p.splitK != 1 || p.TBs != 0 || fusedAdd || poolKernel) return false;
         const int BN = p.OCp / static_cast<int>(grid.y);
         const size_t need = std::max(static_cast<size_t>(128) * (BN + 8) * 2, static_cast<size_t>(2) * 256 * 8 * sizeof(float)); // output tile, then the fold scratch over it
         if (need > ldsBytes) {
@@ -185,9 +190,18 @@ struct MfmaConvPlan : ConvPlanBase {
         }
         SNNHIP_REQUIRE(x->n == p.N && x->h == p.srcH && x->w == p.srcW && x->c == xC, "conv2d: input dims %dx%dx%dx%d != plan %dx%dx%dx%d",
                        x->n, x->h, x->w, x->c, p.N, p.srcH, p.srcW, xC);
-        SNNHIP_REQUIRE(out->n == p.N && out->h == p.OH && out->w == p.OW && out->c == p.OC, "conv2d: output dims %dx%dx%dx%d != plan %dx%dx%dx%d",
-                       out->n, out->h, out->w, out->c, p.N, p.OH, p.OW, p.OC);
-        if (catKernel)
+        const int outH = poolKernel ? poolOH : p.OH, outW = poolKernel ? poolOW : p.OW;
+        SNNHIP_REQUIRE(out->n == p.N && out->h == outH && out->w == outW && out->c == p.OC, "conv2d: output dims %dx%dx%dx%d != plan %dx%dx%dx%d",
+                       out->n, out->h, out->w, out->c, p.N, outH, outW, p.OC);
+        if (poolKernel) {
+            SNNHIP_REQUIRE(x->dtype == dtype && out->dtype == dtype, "conv2d+maxpool: tensor dtypes %d -> %d, the plan's is %d", x->dtype, out->dtype, dtype);
+            MfmaPoolParams pp{};
+            static_cast<MfmaParams&>(pp) = p;
+            pp.poolOH = poolOH;
+            pp.poolOW = poolOW;
+            SNNHIP_LAUNCH(poolKernel, grid, dim3(256), ldsBytes, ctx->stream, pp, ac, static_cast<const void*>(x->data), static_cast<const void*>(d_w),
+                          reinterpret_cast<const float4*>(d_epi), static_cast<void*>(out->data), d_ws);
+        } else if (catKernel)
             SNNHIP_LAUNCH(catKernel, grid, dim3(256), ldsBytes, ctx->stream, p, ac, static_cast<const void*>(x->data), static_cast<const void*>(d_w),
                           reinterpret_cast<const float4*>(d_epi), static_cast<void*>(out->data), d_ws);
         else
@@ -222,7 +236,11 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     // faster there too (241 vs 276 us at 1080p)
     const bool f16 = g.dtype == SNNHIP_F16; // fp16 tensors: this is the only general convolution kernel, it takes every shape
     const bool cat = g.C0 > 0;              // chain rule K: this is the only kernel with the two-source staging
-    if (!forced && !f16 && !cat && (g.OC < 16 || (g.OC < 32 && g.IC < 32))) return SNNHIP_E_UNSUPPORTED;
+    const bool pool = g.poolOH > 0;         // chain rule L: this is the only kernel with the pooling epilogue
+    if (!forced && !f16 && !cat && !pool && (g.OC < 16 || (g.OC < 32 && g.IC < 32))) return SNNHIP_E_UNSUPPORTED;
+    // pooling epilogue: stride 1 (a lane's four GEMM rows are one 2x2 window of adjacent pixels), the simple epilogue, one plain source
+    if (pool && (g.sh != 1 || g.sw != 1 || !act_is_simple(g.act) || g.addAct >= 0 || g.normShift || g.preMode || cat || g.poolOW <= 0 || 2 * g.poolOH > g.OH + 1 || 2 * g.poolOW > g.OW + 1))
+        return SNNHIP_E_UNSUPPORTED;
     // two sources: stride 1, the simple epilogue, no third input (fused Add), no norm in the staging; input 0's channels are whole texel planes
     // (the reference concatenates planes: with C0 % 4 != 0 its result has a gap, quirk Q21, and the separate Concatenate keeps it)
     if (cat && (g.C0 >= g.IC || g.C0 % 4 != 0 || g.sh != 1 || g.sw != 1 || !act_is_simple(g.act) || g.addAct >= 0 || g.normShift || (g.catUp && (g.preShift != 1 || !g.preMode))))
@@ -264,7 +282,10 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         L.tileW = (TW - 1) * g.sw + g.kw;
         L.evenCols = g.sw == 2 ? (L.tileW + 1) / 2 : 0;
         L.rowPitch = L.tileW;
-        if (TW < 32)  // lanes of one 32-lane half span several tile rows: their row step must be == TW (mod 16)
+        if (pool) // window-major M order: a 16-lane read group covers 2 rows x 8 columns (TW >= 16), 4 x 4 (TW = 8) or 4 x 2 of two images (TW = 4) of the
+                  // staged tile; distinct mod 16 iff the row step is == 8 (== 4 for TW = 4) (mod 16), DESIGN.md section 4.32
+            while (L.rowPitch % 16 != (TW >= 8 ? 8 : 4)) ++L.rowPitch;
+        else if (TW < 32)  // lanes of one 32-lane half span several tile rows: their row step must be == TW (mod 16)
             while ((g.sh * L.rowPitch) % 16 != TW % 16) ++L.rowPitch;
         L.imgPitch = round_up(L.tileH * L.rowPitch, 16);
         L.total = TB * L.tileH * L.tileW * Qs;
@@ -281,6 +302,7 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         for (int s = 0; s < static_cast<int>(sizeof(shapes) / sizeof(shapes[0])); ++s) {
             const int TB = 1 << shapes[s][0], TH = 1 << shapes[s][1], TW = 1 << shapes[s][2];
             if (preNorm && shapes[s][0] != 0) continue; // the statistics table in LDS is one image's
+            if (pool && shapes[s][1] == 0) continue;    // a tile holds whole 2x2 windows
             const TileLayout L = layout(shapes[s][0], shapes[s][1], shapes[s][2]);
             const size_t lds = oneChunk ? L.ldsBytes / 2 : L.ldsBytes;
             if (L.total > (C8 ? 9 : 5) * 256 || lds > 150 * 1024) continue; // staging registers / LDS
@@ -368,7 +390,7 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
                 BN = cands[c];
             }
         }
-        if (!f16 && kdepth >= 1024 && g.OC >= 128 && mtiles * up_div(g.OC, 128) < cus) { // split-K fills the chip instead of narrow blocks
+        if (!f16 && !pool && kdepth >= 1024 && g.OC >= 128 && mtiles * up_div(g.OC, 128) < cus) { // split-K fills the chip instead of narrow blocks
             BN = (round_up(g.OC, 128) - g.OC) * 8 > g.OC ? 64 : 128;                     // ... unless 128 pads the channels by > 12.5 %
             wideSplit = true;
         }
@@ -392,7 +414,7 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         if (wideSplit) while (want & (want - 1)) want &= want - 1; // 3x3 layers: 3- / 5-way splits measured 10-25 % behind 2 / 4
         if (const char* e = snnhip::option("SNNHIP_CONV_SPLITK")) want = atoi(e);
         if (ov.splitK) want = ov.splitK;
-        if (want < 1 || g.act == SNNHIP_ACT_SILU_QUIRK) want = 1; // the quirk couples 4 adjacent pixels in the epilogue
+        if (want < 1 || g.act == SNNHIP_ACT_SILU_QUIRK || pool) want = 1; // the quirk couples 4 adjacent pixels in the epilogue; the pooling runs in the direct epilogue only
         if (want > p.nChunks) want = p.nChunks;
         p.chunksPerSplit = up_div(p.nChunks, want);
         p.splitK = up_div(p.nChunks, p.chunksPerSplit);
@@ -409,16 +431,22 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     if (preNorm) ldsNeed += static_cast<size_t>(2) * g.IC * sizeof(float); // [shift | mul] behind the staging buffers
     p.coordTabOfs = static_cast<int>(ldsNeed / 4);
     ldsNeed += static_cast<size_t>(p.tileH + p.tileW) * sizeof(int) * (cat ? 2 : 1); // the staging's row / column tables (one pair per source)
-    if (p.ldsEpi) ldsNeed = std::max(ldsNeed, static_cast<size_t>(128) * (BN + 8) * 2);
+    if (p.ldsEpi) ldsNeed = std::max(ldsNeed, static_cast<size_t>(pool ? 32 : 128) * (BN + 8) * 2); // (pooled: one row per window)
     const bool simple = act_is_simple(g.act);
     KernelFn fn = nullptr;
     CatKernelFn catFn = nullptr;
     const int staticTaps = p.c8Outer ? 0 : taps; // (the half-by-half order lives in the run-time tap loop)
-    if (cat) catFn = f16 ? pick_conv2d_mfma_cat_f16(BN, C8, R, staticTaps) : pick_conv2d_mfma_cat_f32(BN, C8, R, taps);
-    else if (BN == 128) fn = f16 ? pick_conv2d_mfma_bn128_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn128_f32(C8, R, simple, taps);
-    if (BN == 64) fn = f16 ? pick_conv2d_mfma_bn64_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn64_f32(C8, R, simple, taps);
-    if (BN == 32) fn = f16 ? pick_conv2d_mfma_bn32_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn32_f32(C8, R, simple, taps);
-    if (!fn && !catFn) return SNNHIP_E_UNSUPPORTED;
+    PoolKernelFn poolFn = nullptr;
+    if (pool) {
+        poolFn = f16 ? pick_conv2d_mfma_pool_f16(BN, C8, R, staticTaps) : pick_conv2d_mfma_pool_f32(BN, C8, R, taps);
+        if (!poolFn) return SNNHIP_E_UNSUPPORTED;
+    } else {
+        if (cat) catFn = f16 ? pick_conv2d_mfma_cat_f16(BN, C8, R, staticTaps) : pick_conv2d_mfma_cat_f32(BN, C8, R, taps);
+        else if (BN == 128) fn = f16 ? pick_conv2d_mfma_bn128_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn128_f32(C8, R, simple, taps);
+        if (BN == 64) fn = f16 ? pick_conv2d_mfma_bn64_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn64_f32(C8, R, simple, taps);
+        if (BN == 32) fn = f16 ? pick_conv2d_mfma_bn32_f16(C8, R, simple, staticTaps) : pick_conv2d_mfma_bn32_f32(C8, R, simple, taps);
+        if (!fn && !catFn) return SNNHIP_E_UNSUPPORTED;
+    }
 
     auto* plan = new MfmaConvPlan();
     plan->ctx = ctx;
@@ -429,6 +457,9 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
     plan->ac = make_act_cfg(g.act, g.leaky);
     plan->kernel = fn;
     plan->catKernel = catFn;
+    plan->poolKernel = poolFn;
+    plan->poolOH = g.poolOH;
+    plan->poolOW = g.poolOW;
     plan->ldsBytes = ldsNeed;
     plan->fusedAdd = g.addAct >= 0;
     if (plan->fusedAdd || cat) plan->numInputs = 2;
@@ -445,7 +476,7 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         plan->d_ws = static_cast<float*>(ws);
     }
     if (ldsNeed > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(cat ? reinterpret_cast<const void*>(catFn) : reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute(pool ? reinterpret_cast<const void*>(poolFn) : cat ? reinterpret_cast<const void*>(catFn) : reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            static_cast<int>(ldsNeed));
         if (e != hipSuccess) {
             set_error("hipFuncSetAttribute(%zu) failed: %s", ldsNeed, hipGetErrorString(e));
@@ -515,6 +546,12 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
         plan->desc += " +concat(" + std::to_string(g.C0) + "+" + std::to_string(g.IC - g.C0) + ")";
         if (g.catUp) plan->desc += " +upsample(x2 on input 0)";
     }
+    if (pool) { // the input, the weights and the POOLED output: the full-resolution tensor never exists
+        plan->outDims[1] = g.poolOH;
+        plan->outDims[2] = g.poolOW;
+        plan->bytes = esz * (static_cast<double>(g.N) * p.srcH * p.srcW * g.IC + static_cast<double>(g.N) * g.poolOH * g.poolOW * g.OC + static_cast<double>(g.OC) * g.IC * taps);
+        plan->desc += " +maxpool(2x2)";
+    }
     if (g.preMode && !g.catUp) plan->desc += " +pad(" + std::string(g.preMode == SNNHIP_PAD_REFLECT ? "reflect" : g.preMode == SNNHIP_PAD_REPLICATE ? "replicate" : "constant") + ")";
     if (g.preMode && g.preShift && !g.catUp) plan->desc += " +upsample(x2)";
     if (plan->fusedAdd) {
@@ -532,7 +569,8 @@ static int make_conv2d_mfma_plan_ex(snnhip_ctx* ctx, const ConvGeom& g, const fl
 // the 28x28 / 14x14 / 7x7 stages, where block count, residency and the split-K reduce pass trade against each other.
 int make_conv2d_mfma_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out) {
     // two sources (chain rule K): the kernel of this file is the only one whose staging takes them
-    if (g.C0 > 0) return make_conv2d_mfma_plan_ex(ctx, g, w_oihw, epi4, MfmaOverride(), out);
+    // ... and the only one with the 2x2 max-pooling epilogue (chain rule L)
+    if (g.C0 > 0 || g.poolOH > 0) return make_conv2d_mfma_plan_ex(ctx, g, w_oihw, epi4, MfmaOverride(), out);
     // fp32 3x3 stride-1 layers with GEMM-sized channel counts: Winograd F(2x2,3x3) on the matrix pipe (conv2d_wino.hip), 2.25x fewer MFMA
     // flops than the implicit GEMM below.  SNNHIP_CONV=wino forces it for every eligible shape, SNNHIP_CONV=mfma / SNNHIP_CONV_WINO=0 keep
     // the direct kernel (tests run both on the same inputs).

@@ -65,6 +65,15 @@ struct MfmaCatParams : MfmaParams {
     int srcH1, srcW1, preShift1;  // input 1's extent and upsampling shift (input 0: srcH, srcW, preShift)
 };
 
+// 2x2 stride-2 max-pooling in the epilogue (chain rule L, the POOL instances of conv2d_mfma_pool_f{32,16}.hip): the M axis of a block tile is walked
+// WINDOW-MAJOR -- pixel i of the tile is position k = i & 3 (dx = k & 1, dy = k >> 1) of window w = i >> 2, the windows row-major over TW/2 x TH/2 x TB --
+// so the four GEMM rows r & 3 that one lane holds are the four pixels of one pooling window: the maximum is three v_max on registers the lane has anyway
+// and the store is one value instead of four.  Staging, the weight stream and the K loop are those of the plain kernel; only the three places that
+// decode i change (tile_pixel below).  Stride 1, tile origins and TH, TW even.  The single-source instances compile none of it.
+struct MfmaPoolParams : MfmaParams {
+    int poolOH, poolOW; // the pooled extent: ceil or floor of (OH, OW) / 2, whichever the pooling layer resolved
+};
+
 // LDS layout of the staged activations.  A pixel owns ICc floats = ICc/4 16-byte slots; the slot is XOR-swizzled with
 // bits of the linear pixel index so that the 16-byte bank slot (address/16 mod 16) is a bijection of (pixel mod 16):
 // a ds_read_b128 lane group (16 lanes: {0-3,12-15,20-27} / {4-11,16-19,28-31} of each half-wave, MI355X_MICROARCH.md
@@ -91,8 +100,8 @@ __device__ __forceinline__ int lds_off(int pl, int slot) {
 // is ONE 16-byte slot and the K axis runs over the taps instead of the channels -- the two lane halves of a K step read two DIFFERENT taps
 // (h = 0: tap 2j, h = 1: tap 2j+1) of the same pixel slot layout, so a 7x7x3 stem takes 25 K steps instead of 49 and 3 of every 4 (fp32)
 // operand lanes carry data instead of 3 of 8.  Weights are packed [step][h][oc] to match; an odd tap count pads the last h = 1 half with zeros.
-template <int WM, int WN, int MT, int NT, int C8, int R, bool SIMPLE, bool F16, int TAPS = 0, bool CAT = false>
-__global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(typename std::conditional<CAT, MfmaCatParams, MfmaParams>::type p, ActCfg ac, const void* __restrict__ xv, const void* __restrict__ wpv,
+template <int WM, int WN, int MT, int NT, int C8, int R, bool SIMPLE, bool F16, int TAPS = 0, bool CAT = false, bool POOL = false>
+__global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(typename std::conditional<CAT, MfmaCatParams, typename std::conditional<POOL, MfmaPoolParams, MfmaParams>::type>::type p, ActCfg ac, const void* __restrict__ xv, const void* __restrict__ wpv,
                                                           const float4* __restrict__ epi, void* __restrict__ yv, float* __restrict__ ws) {
     static_assert(WM * WN == 4, "4 waves per block");
     static_assert(WM * MT == 4, "128 pixels per block");
@@ -109,6 +118,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(typename std::condi
     constexpr int DS = S % 6 == 0 ? 6 : (S == 9 ? 9 : (S == 8 ? 8 : (S % 4 == 0 ? 4 : (S % 3 == 0 ? 3 : (S % 2 == 0 ? 2 : 1))))); // divides S
     constexpr int D = TAPS ? DS : ((MT * NT >= 4) ? 2 : (MT * NT == 2 ? 3 : 4)); // weight prefetch distance in K steps
     static_assert(!TAPS || F16, "the unrolled K loop is instantiated for fp16 only");
+    static_assert(!POOL || (SIMPLE && !CAT), "the pooling epilogue is instantiated for the simple activations of one source only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -269,6 +279,12 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(typename std::condi
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
         const int i = (wm * MT + t) * 32 + l32;
+        if constexpr (POOL) { // window-major: a 16-lane read group covers 2 rows x 8 columns (or 4 x 4) of the staged tile, see the plan's rowPitch
+            const int w = i >> 2;
+            const int b = w >> (p.THs + p.TWs - 2), py = (((w >> (p.TWs - 1)) & (THm >> 1)) << 1) + ((i >> 1) & 1), px = ((w & (TWm >> 1)) << 1) + (i & 1);
+            apix[t] = b * p.imgPitch + py * p.rowPitch + px; // (stride 1)
+            continue;
+        }
         const int b = i >> (p.THs + p.TWs), py = (i >> p.TWs) & THm, px = i & TWm;
         apix[t] = b * p.imgPitch + py * p.sh * p.rowPitch + (p.evenCols ? px : px * p.sw); // sw==2: column 2px+fx -> plane (fx&1), index px+(fx>>1)
     }
@@ -517,6 +533,50 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(typename std::condi
     // the output tile, transposed the other way: 16-byte vectors of the residual, a pixel's channels contiguous, land where the result will stand, and
     // every lane replaces the halfs of its own accumulator slots by act2(value + residual).
     constexpr int EPITCH = BN + 8; // halfs per LDS row of the output tile
+    if constexpr (POOL) {
+        // ---- pooling epilogue: bias -> BN -> activation on each of the lane's four window positions (BN's scale may be negative: the maximum cannot move
+        // in front of it), then the pooling plan's own rule (eltwise_pool.hip): m = -100000, m = max(m, v) over the positions inside the CONVOLUTION's
+        // extent (windows clipped at the bottom / right edge).  fp32 and fp16 without whole 8-channel vectors: the lane stores m, 32 consecutive channels
+        // per half-wave.  fp16 (p.ldsEpi): the pooled tile [32 windows][BN halfs] is transposed through LDS and leaves as 16-byte vectors.
+        _Float16* const ptile = reinterpret_cast<_Float16*>(smem); // (the K loop ended on a barrier: the staging buffers under the tile are dead)
+        const int TWh = TWm >> 1, THh = THm >> 1;                  // masks of a tile's window columns / rows
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int w = (wm * MT + t) * 8 + h + 2 * g; // GEMM rows 4w .. 4w+3 are this lane's acc[t][u][4g .. 4g+3]
+                const int n = b0 + (w >> (p.THs + p.TWs - 2)), oy = oy0 + (((w >> (p.TWs - 1)) & THh) << 1), ox = ox0 + ((w & TWh) << 1);
+                const bool in1 = ox + 1 < p.OW, in2 = oy + 1 < p.OH; // (position 0 is inside wherever the window is stored)
+                const int qy = oy >> 1, qx = ox >> 1;
+                const bool wok = n < p.N && qy < p.poolOH && qx < p.poolOW && oy < p.OH && ox < p.OW;
+                const int pofs = ((n * p.poolOH + qy) * p.poolOW + qx) * p.OC;
+#pragma unroll
+                for (int u = 0; u < NT; ++u) {
+                    const int oc = n0 + u * 32 + l32;
+                    const float4 e = epi[oc]; // table padded to OCp
+                    float m = -100000.0f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float v = apply_act<true>(ac, epi_affine(acc[t][u][4 * g + k], e, p.useBN), 0.0f);
+                        if ((k & 1 ? in1 : true) && (k & 2 ? in2 : true)) m = fmaxf(m, v);
+                    }
+                    if (F16 && p.ldsEpi) ptile[w * EPITCH + wn * (NT * 32) + u * 32 + l32] = static_cast<_Float16>(m);
+                    else if (wok && oc < p.OC) y[pofs + oc] = static_cast<T>(m);
+                }
+            }
+        if (F16 && p.ldsEpi) {
+            __syncthreads();
+            constexpr int VPR = BN / 8; // 16-byte vectors per window row of the pooled tile
+            for (int v = tid; v < 32 * VPR; v += 256) {
+                const int w = v / VPR, c8 = v - w * VPR;
+                const int n = b0 + (w >> (p.THs + p.TWs - 2)), oy = oy0 + (((w >> (p.TWs - 1)) & THh) << 1), ox = ox0 + ((w & TWh) << 1);
+                const int qy = oy >> 1, qx = ox >> 1, oc = blockIdx.y * BN + c8 * 8;
+                if (n < p.N && qy < p.poolOH && qx < p.poolOW && oy < p.OH && ox < p.OW && oc < p.OC)
+                    *reinterpret_cast<float4*>(y + static_cast<size_t>((n * p.poolOH + qy) * p.poolOW + qx) * p.OC + oc) = *reinterpret_cast<const float4*>(ptile + w * EPITCH + c8 * 8);
+            }
+        }
+        return;
+    }
     const bool addSimple = act_is_simple_dev(p.ac2.act);
     _Float16* const otile = reinterpret_cast<_Float16*>(smem);
     const bool resTile = F16 && p.ldsEpi && p.res;
@@ -667,6 +727,8 @@ typedef void (*KernelFn)(MfmaParams, ActCfg, const void*, const void*, const flo
 
 typedef void (*CatKernelFn)(MfmaCatParams, ActCfg, const void*, const void*, const float4*, void*, float*);
 
+typedef void (*PoolKernelFn)(MfmaPoolParams, ActCfg, const void*, const void*, const float4*, void*, float*);
+
 // the variant table, one precision per instantiation (F16 is a template parameter so that a translation unit compiles one precision only)
 template <int WM, int WN, int MT, int NT, bool F16>
 KernelFn pick_kernel(int c8, int r, bool simple, int taps) {
@@ -716,6 +778,34 @@ CatKernelFn pick_kernel_cat(int c8, int r, int taps) {
     }
 #define SNNHIP_PICK(C8_, R_) \
     if (c8 == C8_ && r == R_) return conv2d_mfma_kernel<WM, WN, MT, NT, C8_, R_, true, F16, 0, true>;
+    SNNHIP_PICK(1, 3)
+    SNNHIP_PICK(1, 5)
+    SNNHIP_PICK(1, 9)
+    SNNHIP_PICK(2, 3)
+    SNNHIP_PICK(2, 5)
+    SNNHIP_PICK(2, 9)
+#undef SNNHIP_PICK
+    return nullptr;
+}
+
+// ... and the pooling instances (conv2d_mfma_pool_f{32,16}.hip): tap pairs for the RGB stem, the chunk widths the planner picks for stride-1 layers, the
+// activations of the simple epilogue
+template <int WM, int WN, int MT, int NT, bool F16>
+PoolKernelFn pick_kernel_pool(int c8, int r, int taps) {
+    if constexpr (F16) {
+#define SNNHIP_PICK_T(C8_, R_, T_) \
+    if (taps == T_ && c8 == C8_ && r == R_) return conv2d_mfma_kernel<WM, WN, MT, NT, C8_, R_, true, true, T_, false, true>;
+        if (!snnhip::option("SNNHIP_CONV_ROLLED")) {
+            SNNHIP_PICK_T(1, 3, 9)
+            SNNHIP_PICK_T(2, 3, 9)
+            SNNHIP_PICK_T(2, 5, 9)
+        }
+#undef SNNHIP_PICK_T
+    }
+#define SNNHIP_PICK(C8_, R_) \
+    if (c8 == C8_ && r == R_) return conv2d_mfma_kernel<WM, WN, MT, NT, C8_, R_, true, F16, 0, false, true>;
+    SNNHIP_PICK(0, 3)
+    SNNHIP_PICK(0, 5)
     SNNHIP_PICK(1, 3)
     SNNHIP_PICK(1, 5)
     SNNHIP_PICK(1, 9)

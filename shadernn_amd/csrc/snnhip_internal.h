@@ -229,6 +229,9 @@ struct ConvGeom {
     // preShift / srcH / srcW describe input 0 (as rule D sets them for [UpSampling2D, Conv2D]), input 1 is at the convolution's own H x W.
     int C0 = 0;
     int catUp = 0;
+    // MaxPooling2D 2x2 stride 2 behind the convolution (chain rule L): the plan writes the pooled tensor [N][poolOH][poolOW][OC] (the extent the pooling
+    // layer resolved: ceil or floor of OH / 2, OW / 2; windows clipped to OH x OW) and the full-resolution one never exists; 0 = none
+    int poolOH = 0, poolOW = 0;
 };
 int resolve_conv_geom(const snnhip_conv2d_desc* d, bool depthwise, ConvGeom* g);
 
