@@ -793,6 +793,10 @@ int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);
  * and no concatenated tensor.  Opt-in (SNNHIP_CONV=cat) except where it was measured faster; SNNHIP_CAT=0 switches it off.  C0 must be a multiple of the
  * kernel's channel chunk (16 fp32 / 32 fp16 channels, 8 / 16 where the planner halves it) and of 4, OC == C0 + C1, stride 1, activation none / relu / relu6 / leakyRelu;
  * anything else returns SNNHIP_E_UNSUPPORTED and the caller keeps its plans.
+ * SNNHIP_CAT_KERNEL (environment or snnhip_set_option) builds rule K's plan on the layer's own kernel: "wino" = the two-source
+ * instances of the fp32 Winograd kernel wherever it accepts the geometry (3x3, stride 1, zero or no padding, C0 and C1 multiples of 8, OC of 16, any
+ * activation but the SiLU quirk), "wide" = those of the wide fp16 kernel (3x3, stride 1, C0 and C1 multiples of 16, OC of 32, no upsampling on input 0),
+ * "auto" = the same where the layer's own plan is that kernel, the decision above elsewhere.  Unset: as above.
  * Rule L: {Conv2D stride 1, MaxPooling2D 2x2 stride 2 without padding} become ONE convolution launch that writes the pooled
  * tensor; its description carries "+maxpool(2x2)", its cost counts the input, the weights and the pooled output.  Off unless SNNHIP_POOL_FUSE=1
  * (environment or snnhip_set_option); SNNHIP_CONV=pool takes it wherever it can run.  Max pooling only, activation none / relu / relu6 / leakyRelu,

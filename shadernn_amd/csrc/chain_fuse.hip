@@ -53,6 +53,10 @@ struct Switches {
     const char* const catWord = option("SNNHIP_CAT");
     const bool noCat = catWord && atoi(catWord) == 0;
     const bool catForced = is(option("SNNHIP_CONV"), "cat");
+    // ... and SNNHIP_CAT_KERNEL names the kernel whose two-source instances run it: wino (fp32, conv2d_wino.hip) / wide (fp16, conv2d_wide_f16.hip) take the rule
+    // wherever that kernel accepts the geometry, its size gate skipped; auto takes it where the layer's own plan would be that kernel; unset: the conv2d_mfma CAT instances, as ever
+    const char* const catKernelWord = option("SNNHIP_CAT_KERNEL");
+    const bool catWino = is(catKernelWord, "wino"), catWide = is(catKernelWord, "wide"), catAuto = is(catKernelWord, "auto");
     // rule L: opt-in -- SNNHIP_POOL_FUSE=1 switches it on, SNNHIP_CONV=pool takes it wherever it can run
     const char* const poolWord = option("SNNHIP_POOL_FUSE");
     const bool poolFuse = (poolWord && poolWord[0] && strcmp(poolWord, "0") != 0) || is(option("SNNHIP_CONV"), "pool");
@@ -644,6 +648,8 @@ int rule_pad_conv(Planner& pl, int i, Step& st) {
 // upsampling on input 0 (YOLOv3-tiny's second head, where the layer's own plan is this kernel too: 34.9 against 38.5 us, three launches become one).
 // The plain concats of U-Net lose -- fp32 0.55x - 0.69x against Concatenate + conv2d_wino, fp16 0.77x - 0.86x against Concatenate + conv2d_wide_f16 on
 // the three large maps, 1.05x inside the spread on the deepest one -- and stay opt-in (SNNHIP_CONV=cat); so does fp32 with the upsampling (0.61x).
+// SNNHIP_CAT_KERNEL=wino|wide|auto builds the plan on the two-source instances of the layer's own kernel instead -- conv2d_wino_cat_kernel (fp32),
+// conv2d_wide_cat_kernel (fp16, plain concats) --: that kernel minus the copy.
 bool cat_default(const ConvGeom& g, bool up) { return g.dtype == SNNHIP_F16 && up; }
 int rule_cat_conv(snnhip_ctx* ctx, const Switches& sw, snnhip_plan* const* plans, int n, snnhip_plan** out) {
     auto* up = n == 3 ? dynamic_cast<UpsamplePlanBase*>(plans[0]) : nullptr;
@@ -655,7 +661,11 @@ int rule_cat_conv(snnhip_ctx* ctx, const Switches& sw, snnhip_plan* const* plans
     if (up && (up->d.mode != SNNHIP_UPSAMPLE_NEAREST || up->d.scale != 2.0f || up->OH != 2 * up->d.H || up->OW != 2 * up->d.W || up->d.N != cd.N || up->OH != cd.H ||
                up->OW != cd.W || up->d.C != cd.C0))
         return SNNHIP_E_UNSUPPORTED;
-    if (!sw.catForced && !cat_default(cv->g, up != nullptr)) return SNNHIP_E_UNSUPPORTED;
+    // SNNHIP_CAT_KERNEL=auto: where the layer's own plan is that kernel -- the gates under which make_conv2d_mfma_plan tries it with nothing forced (the wide
+    // kernel's blocks-per-CU gate is inside make_conv2d_wide_plan and holds under auto)
+    const bool onWino = sw.catWino || (sw.catAuto && cv->g.dtype == SNNHIP_F32 && conv2d_wino_is_default(cv->g));
+    const bool onWide = sw.catWide || (sw.catAuto && cv->g.dtype == SNNHIP_F16 && conv2d_wide_is_default());
+    if (!onWino && !onWide && !sw.catForced && !cat_default(cv->g, up != nullptr)) return SNNHIP_E_UNSUPPORTED;
     ConvGeom g2 = cv->g;
     g2.C0 = cd.C0;
     if (up) { // as rule D's [UpSampling2D, Conv2D]: an identity pad in front of the upsampling -- of input 0 only
@@ -665,6 +675,11 @@ int rule_cat_conv(snnhip_ctx* ctx, const Switches& sw, snnhip_plan* const* plans
         g2.preShift = 1;
         g2.srcH = up->d.H;
         g2.srcW = up->d.W;
+    }
+    if (onWino || onWide) {
+        const int rc = onWino ? make_conv2d_wino_plan(ctx, g2, cv->w_oihw.data(), cv->epi4, out) : make_conv2d_wide_plan(ctx, g2, cv->w_oihw.data(), cv->epi4, out);
+        if (rc != SNNHIP_E_UNSUPPORTED || sw.catWino || sw.catWide) return rc; // (named: that kernel only -- the caller keeps its plans; auto: today's decision below)
+        if (!sw.catForced && !cat_default(cv->g, up != nullptr)) return SNNHIP_E_UNSUPPORTED;
     }
     return make_conv2d_mfma_plan(ctx, g2, cv->w_oihw.data(), cv->epi4, out); // SNNHIP_E_UNSUPPORTED: the separate plans stay
 }

@@ -576,10 +576,8 @@ int make_conv2d_mfma_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     // the direct kernel (tests run both on the same inputs).
     {
         const char* force = snnhip::option("SNNHIP_CONV");
-        const char* w = snnhip::option("SNNHIP_CONV_WINO");
         const bool forced = force && strcmp(force, "wino") == 0;
-        const bool allowed = !force && !(w && atoi(w) == 0) && !snnhip::option("SNNHIP_CONV_BN") && !snnhip::option("SNNHIP_CONV_C8") && g.IC >= 32 && g.OC >= 32 && !g.normShift;
-        if (forced || allowed) {
+        if (forced || conv2d_wino_is_default(g)) {
             const int rc = make_conv2d_wino_plan(ctx, g, w_oihw, epi4, out);
             if (rc != SNNHIP_E_UNSUPPORTED || forced) return rc;
         }
@@ -632,10 +630,8 @@ int make_conv2d_mfma_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     // eligible shape, SNNHIP_CONV=mfma / SNNHIP_CONV_WIDE=0 keep the 128-pixel kernel)
     {
         const char* force = snnhip::option("SNNHIP_CONV");
-        const char* w = snnhip::option("SNNHIP_CONV_WIDE");
         const bool forced = force && strcmp(force, "wide") == 0;
-        const bool allowed = !force && !(w && atoi(w) == 0) && !snnhip::option("SNNHIP_CONV_BN") && !snnhip::option("SNNHIP_CONV_SPLITK") && !snnhip::option("SNNHIP_CONV_C8");
-        if (forced || allowed) {
+        if (forced || conv2d_wide_is_default()) {
             const int rc = make_conv2d_wide_plan(ctx, g, w_oihw, epi4, out);
             if (rc != SNNHIP_E_UNSUPPORTED || forced) return rc;
         }

@@ -73,415 +73,32 @@ __device__ __forceinline__ unsigned physical_cu_slot() {
 }
 constexpr int kTokSlots = 2048;
 
+// CAT (chain rule K: Concatenate -> Conv2D, conv2d_wide_cat_kernel below): the K chunks come from TWO tensors of the convolution's own extent.  A chunk is
+// 16 C8 channels and C0 a multiple of that, so a chunk lies wholly in one source; the staged pixel (rowPix + sx) is the same in both, only the base pointer,
+// the pixel pitch and the channel origin change -- block-uniform values chosen per chunk in stage_dma, the lane's address one multiply-add on its pixel index.
+// The DMA count per chunk (R per thread) is that of the single-source kernel: the counted vmcnt behind the K steps holds unchanged.
+struct WideCatParams {
+    const _Float16* x1; // input 1: [N][H][W][IC - C0] (input 0 is the kernel's x: [N][H][W][C0])
+    int C0;             // channels taken from input 0 = its pixel pitch
+};
+
 template <int WM, int WN, int NT, int C8, int R, bool SIMPLE, bool RES>
 __global__ __launch_bounds__(256, 2) void conv2d_wide_kernel(WideParams p, ActCfg ac, const _Float16* __restrict__ x, const float4* __restrict__ wp,
                                                           const float4* __restrict__ epi, _Float16* __restrict__ y) {
-    static_assert(WM * WN == 4, "4 waves per block");
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    constexpr int MT = 4;
-    constexpr int PIX = 32 * MT * WM;
-    constexpr int BN = 32 * NT * WN;
-    constexpr int Q = 2 * C8;  // 16-byte slots per staged pixel
-    constexpr int S = 9 * C8;  // K steps (16 channels each) per chunk
-    // weight ring depth in K steps (divides S).  One step is MT * NT MFMAs: 256 cycles with NT = 2 -- three steps of lead cover an L2 round trip --
-    // but only 128 with NT = 1, where a whole chunk's 9 steps are kept in flight (64 -> 32 @816x1376 b16: 1500 -> 1277 us; no change for NT = 2)
-    constexpr int D = NT == 1 ? 9 : 3;
-    constexpr int kTileW = 34; // staged tile width: the 32-pixel tile row + the 3x3 halo
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave % WM, wn = wave / WM;
-    const int l32 = lane & 31, h = lane >> 5;
-
-    const int mt = blockIdx.x;
-#ifdef SNNHIP_WIDE_TRACE
-    const bool wtrace = (blockIdx.x == 777 || blockIdx.x == 5000) && blockIdx.y == 0 && (tid == 0 || tid == 192);
-    unsigned long long wstamp[8] = {};
-#endif
-    WIDE_MARK(0);
-    const int tx = mt % p.tilesX, ty = (mt / p.tilesX) % p.tilesY, n = mt / (p.tilesX * p.tilesY);
-    const int ox0 = tx << 5, oy0 = ty << p.THs;
-    const int ix0 = ox0 - p.padx, iy0 = oy0 - p.pady;
-
-    // ---- staging.  LDS-DMA (lds_dma16): element e = tid + 256 r lands at 16-byte LDS slot e of the buffer (lane-contiguous, the only
-    // placement the instruction offers).  A pixel owns Q + 1 slots: Q of data and one of padding, so that the 32 pixels of an operand row sit
-    // (Q + 1) * 16 bytes apart -- an odd number of 16-byte bank slots, conflict-free for ds_read_b128 without an XOR swizzle, and every tap /
-    // channel-slot displacement is an immediate offset of the ds_read (with the swizzle of lds_off the unrolled loop kept 72 precomputed
-    // addresses in registers and spilled).  Pixels outside the image (zero padding), the padding slots and the slots past the tile read a
-    // block of zeros behind the packed weights.  No staging registers, no ds_write; the copy for chunk c+1 is issued at the top of chunk c
-    // and waited for with a COUNTED vmcnt before the closing barrier (the weight ring's youngest loads stay in flight).
-    // The source pixel of a staged pixel is separable -- its row depends on the tile row only, its column on the tile column only -- so the padding
-    // / fused Pad / fused UpSampling resolution runs ONCE per tile row and column (52 threads, one coordinate each) into two small LDS tables, and
-    // a thread's R elements are two look-ups each (resolved per element it was ~110 VALU instructions x R: as long as a quarter of the wave's MFMAs)
-    constexpr int QP = Q + 1;
-    float* const epiTab = smem + p.epiOfs; // (behind the staging buffers AND the epilogue's output tile) this block's BN rows of the epilogue table {bias, bnScale, bnMean, bnBeta}
-    float* const biasTab = epiTab + 4 * BN; // the biases alone, contiguous: the four of a lane's channel run are one ds_read_b128
-    int* const syTab = reinterpret_cast<int*>(biasTab + BN); // [tileH <= 32] pixel index of the source row's first pixel, -1 = outside (zeros)
-    int* const sxTab = syTab + 32;                          // [kTileW] source column, -1 = outside
-    float* const normTab = reinterpret_cast<float*>(sxTab + 40); // [2][IC] graph rule I: shift, mul of this block's image
-    if (p.normShift)
-        for (int i = tid; i < p.IC; i += 256) {
-            normTab[i] = p.normShift[n * p.IC + i];
-            normTab[p.IC + i] = p.normMul[n * p.IC + i];
-        }
-    if (tid < BN) {
-        const float4 e4 = epi[blockIdx.y * BN + tid];
-        reinterpret_cast<float4*>(epiTab)[tid] = e4;
-        biasTab[tid] = e4.x;
-    }
-    if (tid >= 192 && tid < 192 + kTileW) {
-        const int c = tid - 192;
-        int sx = resolve_nobranch(ix0 + c, p.W, p.padMode);
-        if (p.preMode) { // a pixel of the (virtual) padded image -> the source pixel the Pad layer would have copied (-1 stays -1: size <= 2^30)
-            const int px = resolve_nobranch(sx - p.preX, p.srcW << p.preShift, p.preMode);
-            sx = sx < 0 ? -1 : (px < 0 ? -1 : px >> p.preShift);
-        }
-        sxTab[c] = sx;
-    } else if (tid >= 128 && tid < 128 + p.tileH) {
-        const int rr = tid - 128;
-        int sy = resolve_nobranch(iy0 + rr, p.H, p.padMode);
-        if (p.preMode) {
-            const int py = resolve_nobranch(sy - p.preY, p.srcH << p.preShift, p.preMode);
-            sy = sy < 0 ? -1 : (py < 0 ? -1 : py >> p.preShift);
-        }
-        syTab[rr] = sy < 0 ? -1 : (n * p.srcH + sy) * p.srcW;
-    }
-    __syncthreads();
-    int gofs[R];
-    unsigned qlPack = 0; // channel slot of element r in bits 4r .. 4r+2 (the norm fix-up below)
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = tid + 256 * r;
-        gofs[r] = -1;
-        if (e < p.total) {
-            const int pix = e / QP;
-            const int ql = e - pix * QP;
-            qlPack |= static_cast<unsigned>(ql) << (4 * r);
-            const int rr = static_cast<int>(__umulhi(static_cast<unsigned>(pix), p.magicW));
-            const int c = pix - rr * p.tileW;
-            const int rowPix = syTab[rr], sx = sxTab[c];
-            if (rowPix >= 0 && sx >= 0 && ql < Q) gofs[r] = (rowPix + sx) * p.IC + ql * 8;
-        }
-    }
-    const _Float16* const zeros = reinterpret_cast<const _Float16*>(wp + p.zeroOfs);
-    auto stage_dma = [&](float* buf, int ic0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const _Float16* src = gofs[r] >= 0 ? x + gofs[r] + ic0 : zeros;
-            lds_dma16(src, buf + (wave * 64 + 256 * r) * 4);
-        }
-    };
-
-    // graph rule I: the DMA cannot touch the values it carries, so the InstanceNorm in front of this layer is applied to the chunk IN LDS: every
-    // thread normalises exactly the 16-byte slots ITS lanes of the DMA wrote (no other thread has seen them: the pass sits between the DMA's
-    // vmcnt wait and the barrier that publishes the chunk), x -> half(act(x * mul[c] + shift[c])) in fp32 -- the arithmetic and rounding point of
-    // the norm's own normalise sweep, so the result is bit-identical to the separate launches.  Padding (zeros block) stays zero.  Costs ~180
-    // instructions per thread and chunk next to the chunk's 144 MFMAs (+10 %); the normalise sweep it replaces is a read + write of the tensor.
-    auto norm_fixup = [&](float* buf, int ic0) {
-        typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (gofs[r] < 0) continue;
-            float* slot = buf + (tid + 256 * r) * 4;
-            const float* tb = normTab + ic0 + 8 * static_cast<int>((qlPack >> (4 * r)) & 7u);
-            h8v hv = *reinterpret_cast<const h8v*>(slot);
-#pragma unroll
-            for (int q4 = 0; q4 < 2; ++q4) {
-                const float4 sh = *reinterpret_cast<const float4*>(tb + 4 * q4), mu = *reinterpret_cast<const float4*>(tb + p.IC + 4 * q4);
-                const float shv[4] = {sh.x, sh.y, sh.z, sh.w}, muv[4] = {mu.x, mu.y, mu.z, mu.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float f = fmaf(static_cast<float>(hv[4 * q4 + k]), muv[k], shv[k]);
-                    // (one branch-free form for every simple activation -- ReLU is alpha 1, lo 0 --: a per-value select between this and fmaxf(f, 0) computed both)
-                    hv[4 * q4 + k] = static_cast<_Float16>(__builtin_amdgcn_fmed3f(fmaxf(f, f * p.normAc.alpha), p.normAc.lo, p.normAc.hi));
-                }
-            }
-            *reinterpret_cast<h8v*>(slot) = hv;
-        }
-    };
-
-    // ---- MFMA operand addressing: lane (l32, h) reads pixel (row wm*MT + t of the tile, column l32), slot 2 c8 + h; aoff = float offset
-    int aoff[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) aoff[t] = (((wm * MT + t) * p.tileW + l32) * QP + h) * 4;
-    const int n0 = blockIdx.y * BN + wn * (NT * 32);
-    const size_t bstep = static_cast<size_t>(2) * p.OCp; // float4 units per K step
-    const float4* bptr = wp + (static_cast<size_t>(h) * p.OCp + n0 + l32);
-
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][u][r] = 0.0f;
-
-    float4 bq[D][NT];
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-#pragma unroll
-        for (int u = 0; u < NT; ++u) bq[d][u] = bptr[u * 32];
-        bptr += bstep;
-    }
-
-    WIDE_MARK(1);
-    stage_dma(smem, 0);
-    lds_dma_wait();
-    if (p.normShift) norm_fixup(smem, 0);
-    unsigned* const tok = p.kTok ? p.kTok + physical_cu_slot() : nullptr;
-    if (tok && tid == 0) { // chunk 0 is in LDS: wait for the CU's other block to leave its K loop
-        while (__hip_atomic_exchange(tok, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
-    }
-    __syncthreads();
-    WIDE_MARK(2);
-
-    float4 a[MT];
-    for (int chunk = 0; chunk < p.nChunks; ++chunk) {
-        const float* cur = smem + (chunk & 1) * p.bufFloats;
-        const bool more = chunk + 1 < p.nChunks;
-        if (more && !(SNNHIP_WIDE_ABL & 4)) stage_dma(smem + ((chunk + 1) & 1) * p.bufFloats, (chunk + 1) * 16 * C8);
-#pragma unroll
-        for (int t = 0; t < MT; ++t) a[t] = *reinterpret_cast<const float4*>(cur + aoff[t]);
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            float4 b[NT];
-#pragma unroll
-            for (int u = 0; u < NT; ++u) b[u] = bq[s % D][u];
-            if (!(SNNHIP_WIDE_ABL & 1)) {
-#pragma unroll
-                for (int u = 0; u < NT; ++u) bq[s % D][u] = bptr[u * 32];
-                bptr += bstep;
-            }
-            __builtin_amdgcn_sched_barrier(0); // the refill stays D steps ahead of its use
-            const int tap = (s + 1) / C8;
-            const int dl = (((tap / 3) * kTileW + (tap % 3)) * QP + ((s + 1) % C8) * 2) * 4; // compile-time: an immediate offset of the ds_read
-            // pixel-tile major: a[t] is dead after its NT MFMAs and is refilled for the next step at once -- no second operand set in registers
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-#pragma unroll
-                for (int u = 0; u < NT; ++u)
-                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(&b[u]), *reinterpret_cast<const h8*>(&a[t]), acc[t][u], 0, 0, 0);
-                if (s + 1 < S && !(SNNHIP_WIDE_ABL & 2)) a[t] = *reinterpret_cast<const float4*>(cur + aoff[t] + dl);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // the DMA of this chunk is older than every weight refill of the chunk; the ring keeps D * NT loads in flight
-        if (D * NT == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (D * NT == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        if (p.normShift && more) norm_fixup(smem + ((chunk + 1) & 1) * p.bufFloats, (chunk + 1) * 16 * C8);
-        __syncthreads();
-    }
-
-    if (tok && tid == 0) __hip_atomic_store(tok, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    WIDE_MARK(3);
-    // ---- epilogue.  The MFMAs ran with the WEIGHTS as the A operand (M = output channels) and the pixels as B (N = 32 pixels of a tile row), so
-    // a lane holds, for ITS pixel, runs of four consecutive output channels: acc[t][u][4g + k] = channel n0 + 32u + 8g + 4h + k of pixel
-    // (row wm*MT + t, column l32).  bias -> BN -> activation, each run goes to the LDS tile [pixel][BN halfs] as ONE ds_write_b64 (with the
-    // pixels in the accumulator rows it took 128 ds_write_b16 per wave and the epilogue ran as long as the block's MFMAs); the tile then leaves
-    // as 16-byte vectors, a pixel's BN channels contiguous (whole 128-byte lines -- storing the 8-byte runs directly was measured 10 % slower
-    // than this round trip: 32 partial lines per store instruction).  The fused residual Add (RES) is added to the fp32 values, in front of
-    // the one rounding; its loads are all issued before the first store (gfx9 counts loads and stores in one vmcnt and retires them out of order
-    // with respect to each other: a load behind a store can only be waited for with vmcnt(0), the full write round trip).
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    constexpr int EPITCH = BN + 8; // halfs per pixel row of the LDS tile: 8-byte runs of 16 consecutive pixels land in distinct banks
-    _Float16* const otile = reinterpret_cast<_Float16*>(smem);
-    const float4* const etab = reinterpret_cast<const float4*>(epiTab) + wn * (NT * 32) + 4 * h;
-    // layers without batch norm (all of the style graphs): the lane's 8 NT biases are read BEFORE the first write of the output tile -- the
-    // compiler cannot tell the table from the tile (one LDS array) and serialises a read - wait - write round trip per channel run otherwise
-    float4 bias4[NT][4];
-    if (!p.useBN) {
-        const float4* const btab = reinterpret_cast<const float4*>(biasTab + wn * (NT * 32) + 4 * h);
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) bias4[u][g] = btab[u * 8 + 2 * g];
-    }
-    // layers without batch norm whose activation is none or relu (every 3x3 layer of the style graphs): bias and clamp, two instructions per value --
-    // the general form below (run-time batch-norm select, mul / max / med3 activation) is seven, and with 128 values per lane the epilogue's
-    // VALU work was a third of the wave's MFMA time
-    const bool fastEpi = SIMPLE && !p.useBN && ac.alpha == 1.0f && ac.hi == __builtin_huge_valf();
-    constexpr int VPR = BN / 8;             // 16-byte vectors per pixel of the tile
-    constexpr int NV = PIX * VPR / 256;     // ... per thread
-    int oofs[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int v = tid + 256 * j;
-        const int i = v / VPR, c8 = v - i * VPR;
-        const int oy = oy0 + (i >> 5), ox = ox0 + (i & 31);
-        oofs[j] = (oy < p.OH && ox < p.OW) ? ((n * p.OH + oy) * p.OW + ox) * p.OC + blockIdx.y * BN + c8 * 8 : -1;
-    }
-    if (RES) { // the residual comes in through the tile, transposed the other way: its 16-byte vectors land where the result will stand (the K loop ended
-               // on a barrier: the staging buffers under the tile are dead), and every lane below adds the run it is about to overwrite to its fp32 values
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int v = tid + 256 * j;
-            const int i = v / VPR, c8 = v - i * VPR;
-            *reinterpret_cast<float4*>(otile + i * EPITCH + c8 * 8) =
-                oofs[j] >= 0 ? *reinterpret_cast<const float4*>(static_cast<const _Float16*>(p.res) + oofs[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        __syncthreads();
-    }
-    if (fastEpi) {
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float bk[4] = {bias4[u][g].x, bias4[u][g].y, bias4[u][g].z, bias4[u][g].w};
-#pragma unroll
-                for (int t = 0; t < MT; ++t) {
-                    h4* const slot = reinterpret_cast<h4*>(otile + ((wm * MT + t) * 32 + l32) * EPITCH + wn * (NT * 32) + u * 32 + 8 * g + 4 * h);
-                    h4 o, r;
-                    if (RES) r = *slot;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        float v = fmaxf(acc[t][u][4 * g + k] + bk[k], ac.lo);
-                        if (RES) v = add_act(p.ac2, true, v + static_cast<float>(r[k]));
-                        o[k] = static_cast<_Float16>(v);
-                    }
-                    *slot = o;
-                }
-            }
-    } else
-#pragma unroll
-    for (int u = 0; u < NT; ++u)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 e[4];
-            if (p.useBN) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) e[k] = etab[u * 32 + 8 * g + k];
-            } else {
-                e[0].x = bias4[u][g].x; e[1].x = bias4[u][g].y; e[2].x = bias4[u][g].z; e[3].x = bias4[u][g].w;
-            }
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                h4* const slot = reinterpret_cast<h4*>(otile + ((wm * MT + t) * 32 + l32) * EPITCH + wn * (NT * 32) + u * 32 + 8 * g + 4 * h);
-                h4 o, r;
-                if (RES) r = *slot;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float v = epi_affine(acc[t][u][4 * g + k], e[k], p.useBN);
-                    v = SIMPLE ? apply_act<true>(ac, v, 0.0f) : epi_act(ac.act, ac.leaky, v, 0.0f);
-                    if (RES) v = add_act(p.ac2, true, v + static_cast<float>(r[k])); // on the fp32 value: the store is the one rounding
-                    o[k] = static_cast<_Float16>(v);
-                }
-                *slot = o;
-            }
-        }
-    WIDE_MARK(4);
-    __syncthreads();
-    // chain rule F (p.statPart, uniform): the InstanceNorm behind this layer needs mean and variance per (image, channel).  A thread's NV vectors are
-    // NV pixels of ONE 8-channel column (256 % VPR == 0): sums of (v - pivot) and (v - pivot)^2 of the stored (rounded) values accumulate in
-    // registers while the vectors pass through, pivot = the thread's first pixel (the differences stay small: no cancellation in S2 - S1^2 / n)
-    WIDE_MARK(5);
-    float sPiv[8], sA[8], sB[8];
-    int sCnt = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sPiv[e] = sA[e] = sB[e] = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int v = tid + 256 * j;
-        const int i = v / VPR, c8 = v - i * VPR;
-        float4 pack = *reinterpret_cast<const float4*>(otile + i * EPITCH + c8 * 8);
-        if (!RES && p.statPart && oofs[j] >= 0) {
-            const _Float16* ch = reinterpret_cast<const _Float16*>(&pack);
-            if (sCnt == 0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sPiv[e] = static_cast<float>(ch[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float f = static_cast<float>(ch[e]) - sPiv[e];
-                sA[e] += f;
-                sB[e] = fmaf(f, f, sB[e]);
-            }
-            ++sCnt;
-        }
-        if (oofs[j] >= 0 && !((SNNHIP_WIDE_ABL & 8) && p.OC != 12345)) *reinterpret_cast<float4*>(y + oofs[j]) = pack;
-    }
-    WIDE_MARK(6);
-#ifdef SNNHIP_WIDE_TRACE
-    if (wtrace && !(!RES && p.statPart))
-        printf("widetrace blk %d tid %d: prologue %llu stage0 %llu kloop %llu epi %llu bar %llu stores %llu total %llu\n", blockIdx.x, tid, wstamp[1] - wstamp[0], wstamp[2] - wstamp[1],
-               wstamp[3] - wstamp[2], wstamp[4] - wstamp[3], wstamp[5] - wstamp[4], wstamp[6] - wstamp[5], wstamp[6] - wstamp[0]);
-#endif
-    if (!RES && p.statPart) {
-        // thread record (count, mean, M2) per channel -> LDS (the output tile is dead); thread c < BN then merges the PG pixel groups of its channel in a
-        // fixed order with the parallel-variance update (n = na + nb, d = mb - ma, m = ma + d nb / n, M2 = M2a + M2b + d^2 na nb / n): deterministic,
-        // and as accurate as the two-pass form whatever the mean / deviation ratio of the layer
-        constexpr int PG = 256 / VPR;
-        float* const sred = smem; // [3][PG][BN]
-        __syncthreads();
-        {
-            const int c8 = tid % VPR, pg = tid / VPR;
-            const float cn = static_cast<float>(sCnt), inv = sCnt > 0 ? 1.0f / cn : 0.0f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float m1 = sA[e] * inv;
-                sred[pg * BN + c8 * 8 + e] = sPiv[e] + m1;
-                sred[(PG + pg) * BN + c8 * 8 + e] = fmaxf(sB[e] - sA[e] * m1, 0.0f);
-            }
-            if (c8 == 0) sred[2 * PG * BN + pg] = cn;
-        }
-        __syncthreads();
-        // two levels, all loads ahead of the dependent arithmetic: thread (channel c, part q) merges 8 pixel groups, thread c < BN the 256 / BN parts
-        // (one thread per channel walking all PG = 16..64 groups was a 64-step chain of LDS round trips and divisions: +60 % on the 32-channel blocks)
-        constexpr int PARTS = 256 / BN, GP = PG / PARTS;
-        float* const sred2 = sred + 2 * PG * BN + PG; // [3][PARTS][BN]
-        {
-            const int c = tid % BN, q = tid / BN;
-            float nb[GP], mb[GP], qb[GP];
-#pragma unroll
-            for (int j = 0; j < GP; ++j) {
-                nb[j] = sred[2 * PG * BN + q * GP + j];
-                mb[j] = sred[(q * GP + j) * BN + c];
-                qb[j] = sred[(PG + q * GP + j) * BN + c];
-            }
-            float na = 0.0f, ma = 0.0f, M2 = 0.0f;
-#pragma unroll
-            for (int j = 0; j < GP; ++j) {
-                const float n2 = na + nb[j], d = mb[j] - ma, r = nb[j] * __builtin_amdgcn_rcpf(fmaxf(n2, 1.0f)); // nb = 0 (a group outside the image): no change
-                ma = fmaf(d, r, ma);
-                M2 += qb[j] + d * d * na * r;
-                na = n2;
-            }
-            sred2[q * BN + c] = na;
-            sred2[(PARTS + q) * BN + c] = ma;
-            sred2[(2 * PARTS + q) * BN + c] = M2;
-        }
-        __syncthreads();
-        if (tid < BN) {
-            float nb[PARTS], mb[PARTS], qb[PARTS];
-#pragma unroll
-            for (int j = 0; j < PARTS; ++j) {
-                nb[j] = sred2[j * BN + tid];
-                mb[j] = sred2[(PARTS + j) * BN + tid];
-                qb[j] = sred2[(2 * PARTS + j) * BN + tid];
-            }
-            float na = 0.0f, ma = 0.0f, M2 = 0.0f;
-#pragma unroll
-            for (int j = 0; j < PARTS; ++j) {
-                const float n2 = na + nb[j], d = mb[j] - ma, r = nb[j] * __builtin_amdgcn_rcpf(fmaxf(n2, 1.0f));
-                ma = fmaf(d, r, ma);
-                M2 += qb[j] + d * d * na * r;
-                na = n2;
-            }
-            float* po = p.statPart + (static_cast<size_t>(n * p.tilesY + ty) * p.tilesX + tx) * 2 * p.OC + blockIdx.y * BN;
-            st_agent(po + tid, ma); // (read by another block of this launch when the kernel folds: norm_fold.h)
-            st_agent(po + p.OC + tid, M2);
-        }
-        WIDE_MARK(7);
-#ifdef SNNHIP_WIDE_TRACE
-        if (wtrace)
-            printf("widetrace blk %d tid %d: prologue %llu stage0 %llu kloop %llu epi %llu bar %llu stores %llu stats %llu total %llu\n", blockIdx.x, tid, wstamp[1] - wstamp[0],
-                   wstamp[2] - wstamp[1], wstamp[3] - wstamp[2], wstamp[4] - wstamp[3], wstamp[5] - wstamp[4], wstamp[6] - wstamp[5], wstamp[7] - wstamp[6], wstamp[7] - wstamp[0]);
-#endif
-        if (p.fold.counter) tile_stats_finish<BN>(p.fold, p.statPart, sred2 + 3 * 256, n, p.tilesX, p.tilesY, 1 << p.THs, 32, p.OH, p.OW, p.OC, blockIdx.y * BN);
-    }
+    constexpr bool CAT = false;
+    const WideCatParams cp = {}; // (unused: every use sits behind CAT)
+#include "conv2d_wide_body.h"
+}
+// the two-source instances (chain rule K); x = input 0, cp.x1 = input 1
+template <int WM, int WN, int NT, int C8, int R, bool SIMPLE>
+__global__ __launch_bounds__(256, 2) void conv2d_wide_cat_kernel(WideParams p, WideCatParams cp, ActCfg ac, const _Float16* __restrict__ x, const float4* __restrict__ wp,
+                                                              const float4* __restrict__ epi, _Float16* __restrict__ y) {
+    constexpr bool RES = false, CAT = true;
+#include "conv2d_wide_body.h"
 }
 
 typedef void (*WideFn)(WideParams, ActCfg, const _Float16*, const float4*, const float4*, _Float16*);
+typedef void (*WideCatFn)(WideParams, WideCatParams, ActCfg, const _Float16*, const float4*, const float4*, _Float16*);
 
 struct WideConvPlan : ConvPlanBase {
     WideParams p;
@@ -491,6 +108,8 @@ struct WideConvPlan : ConvPlanBase {
     size_t ldsBytes = 0;
     dim3 grid;
     WideFn kernel = nullptr;
+    WideCatFn catKernel = nullptr; // chain rule K (g.C0 > 0): the two-source instance, cp its parameter block
+    WideCatParams cp = {};
     bool fusedAdd = false;
 
     // chain rule F: {mean, M2} of every output tile and channel next to the output (the epilogue's LDS round trip carries them: conv2d_wide_kernel)
@@ -519,6 +138,22 @@ struct WideConvPlan : ConvPlanBase {
         return true;
     }
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
+        if (catKernel) { // chain rule K: two inputs in the concat's order, both at the convolution's extent
+            SNNHIP_REQUIRE(nIn == 2, "conv2d+concat: expects 2 inputs, got %d", nIn);
+            for (int s = 0; s < 2; ++s) {
+                const int c = s ? p.IC - cp.C0 : cp.C0;
+                SNNHIP_REQUIRE(in[s]->n == p.N && in[s]->h == p.H && in[s]->w == p.W && in[s]->c == c && in[s]->dtype == SNNHIP_F16,
+                               "conv2d+concat: input %d dims %dx%dx%dx%d (dtype %d) != plan %dx%dx%dx%d fp16", s, in[s]->n, in[s]->h, in[s]->w, in[s]->c, in[s]->dtype, p.N, p.H, p.W, c);
+            }
+            SNNHIP_REQUIRE(out->n == p.N && out->h == p.OH && out->w == p.OW && out->c == p.OC && out->dtype == SNNHIP_F16,
+                           "conv2d: output dims %dx%dx%dx%d != plan %dx%dx%dx%d", out->n, out->h, out->w, out->c, p.N, p.OH, p.OW, p.OC);
+            WideCatParams c2 = cp;
+            c2.x1 = reinterpret_cast<const _Float16*>(in[1]->data);
+            SNNHIP_LAUNCH(catKernel, grid, dim3(256), ldsBytes, ctx->stream, p, c2, ac, reinterpret_cast<const _Float16*>(in[0]->data), reinterpret_cast<const float4*>(d_w),
+                               reinterpret_cast<const float4*>(d_epi), reinterpret_cast<_Float16*>(out->data));
+            SNNHIP_CHECK_HIP(hipGetLastError());
+            return SNNHIP_OK;
+        }
         SNNHIP_REQUIRE(nIn == (fusedAdd ? 2 : 1), "conv2d: expects %d input(s), got %d", fusedAdd ? 2 : 1, nIn);
         const snnhip_tensor* x = in[0];
         WideParams q = p;
@@ -546,8 +181,18 @@ WideFn pick_wide(bool simple, bool res) {
     if (res) return simple ? conv2d_wide_kernel<WM, WN, NT, C8, R, true, true> : conv2d_wide_kernel<WM, WN, NT, C8, R, false, true>;
     return simple ? conv2d_wide_kernel<WM, WN, NT, C8, R, true, false> : conv2d_wide_kernel<WM, WN, NT, C8, R, false, false>;
 }
+template <int WM, int WN, int NT, int C8, int R>
+WideCatFn pick_wide_cat(bool simple) {
+    return simple ? conv2d_wide_cat_kernel<WM, WN, NT, C8, R, true> : conv2d_wide_cat_kernel<WM, WN, NT, C8, R, false>;
+}
 
 } // namespace
+
+// where this kernel is tried for a layer with nothing forced (make_conv2d_mfma_plan, and chain rule K under SNNHIP_CAT_KERNEL=auto)
+bool conv2d_wide_is_default() {
+    const char* w = snnhip::option("SNNHIP_CONV_WIDE");
+    return !snnhip::option("SNNHIP_CONV") && !(w && atoi(w) == 0) && !snnhip::option("SNNHIP_CONV_BN") && !snnhip::option("SNNHIP_CONV_SPLITK") && !snnhip::option("SNNHIP_CONV_C8");
+}
 
 // fp16 3x3 stride-1 layers with IC % 16 == 0, OC % 32 == 0 and at least 0.75 blocks of 256 / 512 pixels per CU; SNNHIP_CONV=wide forces it for
 // every eligible shape, SNNHIP_CONV_WIDE=0 keeps the 128-pixel kernel
@@ -555,11 +200,16 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     if (g.dtype != SNNHIP_F16 || g.kh != 3 || g.kw != 3 || g.sh != 1 || g.sw != 1) return SNNHIP_E_UNSUPPORTED;
     if (g.IC % 16 != 0 || g.OC % 32 != 0 || g.act == SNNHIP_ACT_SILU_QUIRK) return SNNHIP_E_UNSUPPORTED;
     if (g.normShift && !act_is_simple(g.normAct)) return SNNHIP_E_UNSUPPORTED; // graph rule I: the branch-free activations only
-    const double inCount = static_cast<double>(g.N) * (g.preMode ? g.srcH : g.H) * (g.preMode ? g.srcW : g.W) * g.IC;
+    // chain rule K (g.C0 > 0): a plain concat of two tensors at the convolution's extent, whole 16-channel chunks in each; no upsampling on input 0, no fused
+    // Pad, no norm in the staging, no residual (a third input)
+    const bool cat = g.C0 > 0;
+    if (cat && (g.C0 >= g.IC || g.C0 % 16 != 0 || g.catUp || g.preMode || g.normShift || g.addAct >= 0)) return SNNHIP_E_UNSUPPORTED;
+    const double inCount = static_cast<double>(g.N) * (g.preMode ? g.srcH : g.H) * (g.preMode ? g.srcW : g.W) * g.IC; // (CAT: bounds each source's own offsets too)
     const double outCount = static_cast<double>(g.N) * g.OH * g.OW * g.OC;
     if (inCount >= 2147483647.0 || outCount >= 2147483647.0) return SNNHIP_E_UNSUPPORTED;
     const char* force = snnhip::option("SNNHIP_CONV");
-    const bool forced = force && strcmp(force, "wide") == 0;
+    const char* catWord = snnhip::option("SNNHIP_CAT_KERNEL");
+    const bool forced = (force && strcmp(force, "wide") == 0) || (cat && catWord && strcmp(catWord, "wide") == 0); // (the rule's named kernel: the size gate is skipped)
     // the 128 -> 128 body layers of the style graphs: the persistent form (conv2d_widep_f16.hip), unless it declines or SNNHIP_WIDE_PERSIST=0
     if (make_conv2d_widep_plan(ctx, g, w_oihw, epi4, out) == SNNHIP_OK) return SNNHIP_OK;
 
@@ -574,7 +224,7 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
         if (v == 32) { WM = 4; NT = 1; BN = 32; }
     }
     const int THs = WM == 2 ? 3 : 4, TH = 1 << THs, TW = 32;
-    const int C8 = (WM == 2 && g.IC % 32 == 0) ? 2 : 1;
+    const int C8 = (WM == 2 && g.IC % 32 == 0 && g.C0 % 32 == 0) ? 2 : 1; // (CAT: a 32-channel chunk must not straddle the two sources -- the 16-channel chunk then)
     const int cus = ctx->props.multiProcessorCount > 0 ? ctx->props.multiProcessorCount : 256;
     const long tiles = static_cast<long>(g.N) * up_div(g.OH, TH) * up_div(g.OW, TW);
     // measured down to one 183x323 image (230 blocks of 256 pixels on 256 CUs): 24 us here, 35 us with the 128-pixel blocks; below that the
@@ -607,6 +257,14 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     if (WM == 2 && C8 == 1 && R <= 4) fn = pick_wide<2, 2, 2, 1, 4>(simple, withRes);
     if (WM == 4 && NT == 2 && R <= 8) fn = pick_wide<4, 1, 2, 1, 8>(simple, withRes);
     if (WM == 4 && NT == 1 && R <= 8) fn = pick_wide<4, 1, 1, 1, 8>(simple, withRes);
+    WideCatFn catFn = nullptr;
+    if (cat) {
+        if (WM == 2 && C8 == 2 && R <= 7) catFn = pick_wide_cat<2, 2, 2, 2, 7>(simple);
+        if (WM == 2 && C8 == 1 && R <= 4) catFn = pick_wide_cat<2, 2, 2, 1, 4>(simple);
+        if (WM == 4 && NT == 2 && R <= 8) catFn = pick_wide_cat<4, 1, 2, 1, 8>(simple);
+        if (WM == 4 && NT == 1 && R <= 8) catFn = pick_wide_cat<4, 1, 1, 1, 8>(simple);
+        if (!catFn) return SNNHIP_E_UNSUPPORTED;
+    }
     if (!fn) return SNNHIP_E_UNSUPPORTED;
     const int PIX = 128 * WM;
     p.epiOfs = static_cast<int>(std::max(static_cast<size_t>(2) * p.bufFloats * 4, static_cast<size_t>(PIX) * (BN + 8) * 2) / 4);
@@ -625,6 +283,8 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     plan->p = p;
     plan->ac = make_act_cfg(g.act, g.leaky);
     plan->kernel = fn;
+    plan->catKernel = catFn;
+    plan->cp.C0 = g.C0;
 #ifdef SNNHIP_WIDE_LDS_PAD_KB // experiment builds (tools/exp_one.sh): extra LDS per block = fewer blocks per CU (what does a block do when it has the CU to itself?)
     plan->ldsBytes = lds + static_cast<size_t>(SNNHIP_WIDE_LDS_PAD_KB) * 1024;
     hipFuncSetAttribute(reinterpret_cast<const void*>(plan->kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(plan->ldsBytes));
@@ -634,7 +294,7 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     plan->fusedAdd = g.addAct >= 0;
     if (plan->fusedAdd) plan->numInputs = 2;
     plan->grid = dim3(static_cast<unsigned>(tiles), g.OC / BN, 1);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute(cat ? reinterpret_cast<const void*>(catFn) : reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
         set_error("conv2d_wide: hipFuncSetAttribute(%zu) failed", lds);
         delete plan;
         return SNNHIP_E_HIP;
@@ -683,6 +343,11 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     snprintf(buf, sizeof(buf), "conv2d_mfma_wide_f16_32x32x16 k=3x3 s=1 ic=%d oc=%d tile=%dx32px x %doc (4x%d MFMA tiles per wave) chunk=%d lds=%zuB", g.IC, g.OC, TH, BN, NT,
              16 * C8, lds);
     plan->desc = buf;
+    if (cat) { // two inputs; inDims describes input 0, the bytes count both once (their sum is the term above)
+        plan->numInputs = 2;
+        plan->inDims[3] = g.C0;
+        plan->desc += " +concat(" + std::to_string(g.C0) + "+" + std::to_string(g.IC - g.C0) + ")";
+    }
     if (g.preMode) plan->desc += " +pad(" + std::string(g.preMode == SNNHIP_PAD_REFLECT ? "reflect" : g.preMode == SNNHIP_PAD_REPLICATE ? "replicate" : "constant") + ")";
     if (g.preMode && g.preShift) plan->desc += " +upsample(x2)";
     if (g.normShift) plan->desc = "instancenorm(act=" + std::to_string(g.normAct) + ", in LDS behind the DMA) -> " + plan->desc;

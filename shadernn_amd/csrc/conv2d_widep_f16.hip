@@ -820,6 +820,7 @@ struct WidePConvPlan : ConvPlanBase {
 int make_conv2d_widep_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out) {
     if (g.dtype != SNNHIP_F16 || g.kh != 3 || g.kw != 3 || g.sh != 1 || g.sw != 1) return SNNHIP_E_UNSUPPORTED;
     if (g.IC != 128 || g.OC != 128 || !act_is_simple(g.act) || g.addAct >= 0) return SNNHIP_E_UNSUPPORTED; // (other activations / a fused residual: conv2d_wide_kernel)
+    if (g.C0 > 0) return SNNHIP_E_UNSUPPORTED; // (chain rule K: the persistent form stages from one tensor -- the two-source instances of conv2d_wide_f16.hip)
     if (g.normShift && g.normAct != SNNHIP_ACT_RELU && g.normAct != SNNHIP_ACT_NONE) return SNNHIP_E_UNSUPPORTED; // (other norm activations: conv2d_wide_kernel; the med3 form does not fit 256 registers here)
     if (const char* e = snnhip::option("SNNHIP_WIDE_PERSIST"))
         if (atoi(e) == 0) return SNNHIP_E_UNSUPPORTED;

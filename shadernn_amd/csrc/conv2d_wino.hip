@@ -67,280 +67,39 @@ struct WinoParams {
 // output-channel block g: it hands the partner the other block's sixteen positions and adds the partner's to its own -- p0 + p1 in both groups, the order
 // of the reduce pass), and every wave runs the epilogue of ONE channel block.  What a 14x14 stage needed split-K over blockIdx.z + a reduce launch for
 // (partial sums through HBM, 6 us per launch) stays inside the block.
+// CAT (chain rule K: Concatenate -> Conv2D, conv2d_wino_cat_kernel below): the K chunks come from TWO tensors.  A chunk is 8 channels and C0 a multiple of 8,
+// so a chunk lies wholly in one source and a K range (a block's, a blockIdx.z slice's, a K group's) changes source at most once: the source is
+// block-uniform state -- base pointer and channel origin in scalar registers, the threads' global offsets taken again from that source's own pitch and
+// extent at the one chunk where it changes (set in the prologue from the range's first chunk).  One offset set is live, as in the single-source form.
+struct WinoCatParams {
+    const float* x1;   // input 1: N x H x W x pitch1
+    int c0Chunks;      // chunks [0, c0Chunks) are input 0's
+    int pitch0, pitch1; // channels (= pixel pitch) of the two inputs
+    int srcH, srcW;    // input 0's own extent: H x W, or the low-resolution one behind the nearest x2 upsampling ...
+    int shift0;        // ... whose pixel of (sy, sx) is (sy >> shift0, sx >> shift0); input 1 is always at H x W
+};
+
 template <bool SIMPLE, int OPB, int KS = 1>
 __global__ __launch_bounds__(256 * OPB * KS, KS > 1 ? 1 : 3 - OPB) void conv2d_wino_kernel(WinoParams p, ActCfg ac, const float* __restrict__ x, const float4* __restrict__ ug,
                                                                         const float4* __restrict__ epi, float* __restrict__ y, float* __restrict__ ws) {
-    static_assert(KS == 1 || (KS == 2 && OPB == 1), "in-block K split: two groups of four waves");
-    constexpr int NT = 256 * OPB;            // threads of a group
-    constexpr int kUFloats = 4096 * OPB;     // U slab of one chunk: 16 positions x OPB pairs x 64 lanes x float4 (16 / 32 KB)
-    constexpr int UQ = 1024 * OPB;           // ... in float4
-    constexpr int R = 4 / OPB;               // staged activation quads per thread (halo tile of up to 1024 quads)
-    extern __shared__ __attribute__((aligned(16))) float smemAll[];
-    const int lane = threadIdx.x & 63;
-    const int ks = KS > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) : 0; // K group of this wave
-    const int tid = KS > 1 ? (threadIdx.x & 255) : threadIdx.x, wave = tid >> 6;     // thread / wave within the group
-    float* const smem = smemAll + ks * 2 * p.bufFloats;                              // the group's two buffers
-    const int tg = wave & 3, op = wave >> 2;
-    const int n16 = lane & 15, k = lane >> 4;
+    constexpr bool CAT = false;
+    const WinoCatParams cp = {};
+#include "conv2d_wino_body.h"
+}
 
-    const int mt = blockIdx.x;
-    const int tx = mt % p.tilesX, ty = (mt / p.tilesX) % p.tilesY, tb = mt / (p.tilesX * p.tilesY);
-    const int TTW = 1 << p.TTWs, TTH = 1 << p.TTHs;
-    const int ox0 = tx * 2 * TTW, oy0 = ty * 2 * TTH, b0 = tb << p.TBs;
-    const int ix0 = ox0 - p.padx, iy0 = oy0 - p.pady;
+// chain rule K: x = input 0 (cp.pitch0 channels, cp.srcH x cp.srcW), cp.x1 = input 1; the weight image is the layer's own, K in concatenated channel order
+template <bool SIMPLE, int OPB, int KS = 1>
+__global__ __launch_bounds__(256 * OPB * KS, KS > 1 ? 1 : 3 - OPB) void conv2d_wino_cat_kernel(WinoParams p, WinoCatParams cp, ActCfg ac, const float* __restrict__ x,
+                                                                            const float4* __restrict__ ug, const float4* __restrict__ epi, float* __restrict__ y,
+                                                                            float* __restrict__ ws) {
+    constexpr bool CAT = true;
+#include "conv2d_wino_body.h"
+}
 
-    // ---- staging descriptors: element e = tid + NT r -> (pixel of the halo tile, channel quad q = e & 1)
-    const int q = tid & 1;
-    int gofs[4], lofs[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        gofs[r] = lofs[r] = -1;
-        if (r >= R) continue;
-        const int e = tid + NT * r;
-        gofs[r] = -1;
-        lofs[r] = -1;
-        if (e < p.total) {
-            const int pix = e >> 1;
-            const int c = pix % p.inW, t2 = pix / p.inW;
-            const int rr = t2 % p.inH, b = t2 / p.inH;
-            const int sy = iy0 + rr, sx = ix0 + c, n = b0 + b;
-            lofs[r] = kUFloats + 2 * q * p.planeStride + ((b * p.inH + rr) * p.rowPitch + c) * 2;
-            if (sy >= 0 && sy < p.H && sx >= 0 && sx < p.W && n < p.N) gofs[r] = ((n * p.H + sy) * p.W + sx) * p.IC + q * 4;
-        }
-    }
-    int chunk0 = blockIdx.z * p.chunksPerSplit, chunk1 = min(p.nChunks, chunk0 + p.chunksPerSplit);
-    if (KS > 1) { // (the planner only splits even chunk counts: both groups run the same number of iterations, their barriers pair up)
-        const int half = (chunk1 - chunk0) >> 1;
-        chunk0 += ks * half;
-        chunk1 = chunk0 + half;
-    }
-    // U slab of (oc block, chunk): UQ float4, thread t copies float4 t + NT j, j < 4
-    const float4* uptr = ug + (static_cast<size_t>(blockIdx.y) * p.nChunks + chunk0) * UQ + tid;
-
-    // Staging.  U slab: LDS-DMA (global_load_lds_dwordx4: a wave copies 64 consecutive float4 = 1 KiB per instruction straight into the slab,
-    // no staging registers and -- what the ablation builds showed to matter -- no VGPR -> LDS store traffic: the four ds_write_b128 per thread
-    // and chunk it replaces cost the kernel 20 %).  Activations: R quads per thread through registers (zero fill outside the image, split into
-    // the channel-pair planes); plain scalars: arrays captured by reference went to scratch.
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 sxa = zero4, sxb = zero4, sxc = zero4, sxd = zero4;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-#define WINO_STAGE_LOAD(chunk_, buf_)                                                                                             \
-    do {                                                                                                                          \
-        const float4* u_ = uptr + static_cast<size_t>((chunk_) - chunk0) * UQ;                                                    \
-        float* ub_ = (buf_) + 4 * (wave * 64);                                                                                    \
-        if (!(SNNHIP_WINO_ABL & 64)) {                                                                                            \
-            lds_dma16(u_, ub_);                                                                                                   \
-            lds_dma16(u_ + NT, ub_ + 4 * NT);                                                                                     \
-            lds_dma16(u_ + 2 * NT, ub_ + 8 * NT);                                                                                 \
-            lds_dma16(u_ + 3 * NT, ub_ + 12 * NT);                                                                                \
-        }                                                                                                                         \
-        sxa = sxb = sxc = sxd = zero4;                                                                                            \
-        if (SNNHIP_WINO_ABL & 128) break;                                                                                         \
-        if (gofs[0] >= 0) sxa = *reinterpret_cast<const float4*>(x + gofs[0] + (chunk_) * 8);                                     \
-        if (gofs[1] >= 0) sxb = *reinterpret_cast<const float4*>(x + gofs[1] + (chunk_) * 8);                                     \
-        if (R > 2 && gofs[2] >= 0) sxc = *reinterpret_cast<const float4*>(x + gofs[2] + (chunk_) * 8);                            \
-        if (R > 2 && gofs[3] >= 0) sxd = *reinterpret_cast<const float4*>(x + gofs[3] + (chunk_) * 8);                            \
-    } while (0)
-#define WINO_STORE_X(r_, v_)                                                                                     \
-    if (lofs[r_] >= 0) {                                                                                         \
-        *reinterpret_cast<float2*>(b_ + lofs[r_]) = make_float2(v_.x, v_.y);                                     \
-        *reinterpret_cast<float2*>(b_ + lofs[r_] + p.planeStride) = make_float2(v_.z, v_.w);                     \
-    }
-#define WINO_STAGE_STORE(buf_)                                                                                   \
-    do {                                                                                                         \
-        float* b_ = (buf_);                                                                                      \
-        WINO_STORE_X(0, sxa)                                                                                     \
-        WINO_STORE_X(1, sxb)                                                                                     \
-        if (R > 2) {                                                                                             \
-            WINO_STORE_X(2, sxc)                                                                                 \
-            WINO_STORE_X(3, sxd)                                                                                 \
-        }                                                                                                        \
-    } while (0)
-
-    // ---- this lane's tile: t = 16 tg + n16 -> (image b, tile row, tile column) of the block tile
-    const int t = 16 * tg + n16;
-    const int ttx = t & (TTW - 1), tty = (t >> p.TTWs) & (TTH - 1), tbi = t >> (p.TTWs + p.TTHs);
-    const int patch = kUFloats + k * p.planeStride + ((tbi * p.inH + 2 * tty) * p.rowPitch + 2 * ttx) * 2; // + (dy*rowPitch + dx)*2
-    const int uoff = op * 256 + lane * 4;                                                                  // + pos * 256 * OPB: float4 {U[2op].s0, .s1, U[2op+1].s0, .s1}
-
-    f32x4 acc[16][2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-#pragma unroll
-        for (int o = 0; o < 2; ++o) acc[i][o] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    WINO_STAGE_LOAD(chunk0, smem);
-    WINO_STAGE_STORE(smem);
-    lds_dma_wait();
-    __syncthreads();
-
-    for (int chunk = chunk0; chunk < chunk1; ++chunk) {
-        const float* buf = smem + ((chunk - chunk0) & 1) * p.bufFloats;
-        const bool more = chunk + 1 < chunk1;
-        float* nbuf = smem + ((chunk + 1 - chunk0) & 1) * p.bufFloats; // the buffer nobody reads during this chunk
-        if (more && !(SNNHIP_WINO_ABL & 4)) WINO_STAGE_LOAD(chunk + 1, nbuf);
-
-        // Issue order is pinned with sched_barrier: the patch and the first eight U operands are requested up front, the rest while the
-        // first MFMAs run, and the next chunk goes to the OTHER LDS buffer in the middle of the MFMA stream (its global loads were issued a
-        // thousand cycles earlier), so that the end of the chunk is only the barrier.  Left to itself the scheduler sinks every ds_read next
-        // to its use (fewest registers) and the wave eats one LDS latency per position: 31 % matrix-pipe utilisation (PMC), 48 % after.
-        float4 t4[4][2], u[16];
-#define WINO_LDU(i) u[i] = (SNNHIP_WINO_ABL & 16) ? make_float4(1.f, 2.f, 3.f, 4.f) : *reinterpret_cast<const float4*>(buf + uoff + (i) * (256 * OPB))
-#pragma unroll
-        for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) // one ds_read_b128 = two adjacent pixels of the pair plane
-                t4[dy][h2] = (SNNHIP_WINO_ABL & 32) ? make_float4(1.f + dy, 2.f, 3.f + h2, 4.f) : *reinterpret_cast<const float4*>(buf + patch + (dy * p.rowPitch + 2 * h2) * 2);
-        WINO_LDU(0); WINO_LDU(1); WINO_LDU(2); WINO_LDU(3); WINO_LDU(4); WINO_LDU(5); WINO_LDU(6); WINO_LDU(7);
-        __builtin_amdgcn_sched_barrier(0);
-        // the 4x4 patch of (tile, channel pair), both channels of the pair
-        float2 d[4][4];
-#pragma unroll
-        for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                d[dy][2 * h2] = make_float2(t4[dy][h2].x, t4[dy][h2].y);
-                d[dy][2 * h2 + 1] = make_float2(t4[dy][h2].z, t4[dy][h2].w);
-            }
-        // V = Bt d B, Bt = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
-        float2 v[4][4];
-#pragma unroll
-        for (int j = 0; j < 4 && !(SNNHIP_WINO_ABL & 8); ++j) {
-            const float2 a0 = d[0][j], a1 = d[1][j], a2 = d[2][j], a3 = d[3][j];
-            d[0][j] = make_float2(a0.x - a2.x, a0.y - a2.y);
-            d[1][j] = make_float2(a1.x + a2.x, a1.y + a2.y);
-            d[2][j] = make_float2(a2.x - a1.x, a2.y - a1.y);
-            d[3][j] = make_float2(a1.x - a3.x, a1.y - a3.y);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float2 a0 = d[i][0], a1 = d[i][1], a2 = d[i][2], a3 = d[i][3];
-            if (SNNHIP_WINO_ABL & 8) {
-                v[i][0] = a0; v[i][1] = a1; v[i][2] = a2; v[i][3] = a3;
-                continue;
-            }
-            v[i][0] = make_float2(a0.x - a2.x, a0.y - a2.y);
-            v[i][1] = make_float2(a1.x + a2.x, a1.y + a2.y);
-            v[i][2] = make_float2(a2.x - a1.x, a2.y - a1.y);
-            v[i][3] = make_float2(a1.x - a3.x, a1.y - a3.y);
-        }
-        // 16 positions x 2 channel blocks x 2 K steps: M[pos][oc][tile] += U[pos][oc][ic] V[pos][ic][tile]
-#define WINO_STEP(pos)                                                                                       \
-    do {                                                                                                     \
-        const float2 vv_ = v[(pos) >> 2][(pos) & 3];                                                         \
-        acc[pos][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[pos].x, vv_.x, acc[pos][0], 0, 0, 0);           \
-        acc[pos][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[pos].z, vv_.x, acc[pos][1], 0, 0, 0);           \
-        acc[pos][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[pos].y, vv_.y, acc[pos][0], 0, 0, 0);           \
-        acc[pos][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[pos].w, vv_.y, acc[pos][1], 0, 0, 0);           \
-    } while (0)
-        WINO_STEP(0); WINO_STEP(1); WINO_STEP(2); WINO_STEP(3);
-        __builtin_amdgcn_sched_barrier(0);
-        WINO_LDU(8); WINO_LDU(9); WINO_LDU(10); WINO_LDU(11);
-        __builtin_amdgcn_sched_barrier(0);
-        WINO_STEP(4); WINO_STEP(5); WINO_STEP(6); WINO_STEP(7);
-        __builtin_amdgcn_sched_barrier(0);
-        WINO_LDU(12); WINO_LDU(13); WINO_LDU(14); WINO_LDU(15);
-        if (more && !(SNNHIP_WINO_ABL & 2)) WINO_STAGE_STORE(nbuf);
-        __builtin_amdgcn_sched_barrier(0);
-        WINO_STEP(8); WINO_STEP(9); WINO_STEP(10); WINO_STEP(11); WINO_STEP(12); WINO_STEP(13); WINO_STEP(14); WINO_STEP(15);
-#undef WINO_STEP
-#undef WINO_LDU
-        lds_dma_wait(); // (free here: the activation loads issued after the DMA were waited for by the stage store above)
-        if (!(SNNHIP_WINO_ABL & 1)) __syncthreads();
-    }
-
-    // ---- KS = 2: the two K groups exchange one channel block's sums (region of wave w: [pos][lane] float4 = 16 KB, 128 KB in all; the staging buffers are
-    // free: every wave is past the loop's last barrier)
-    if (KS > 1) {
-        f32x4* const xb = reinterpret_cast<f32x4*>(smemAll);
-        f32x4* const mine = xb + ((ks * 4 + wave) * 16) * 64 + lane;
-        const f32x4* const theirs = xb + (((1 - ks) * 4 + wave) * 16) * 64 + lane;
-        if (ks == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mine[i * 64] = acc[i][1];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mine[i * 64] = acc[i][0];
-        }
-        __syncthreads();
-        if (ks == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i][0] += theirs[i * 64]; // p0 + p1
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i][1] = theirs[i * 64] + acc[i][1]; // p0 + p1 as well
-        }
-    }
-
-    // ---- Y = At M A, At = [1 1 1 0; 0 1 -1 -1]; lane holds output channels 4k..4k+3 of each 16-channel block for its tile
-    const int oy = oy0 + 2 * tty, ox = ox0 + 2 * ttx, n = b0 + tbi;
-    const bool addSimple = act_is_simple_dev(p.ac2.act);
-#pragma unroll
-    for (int o = 0; o < 2; ++o) {
-        if (KS > 1 && o != ks) continue; // (wave-uniform: group g finishes channel block g)
-        const int oc = blockIdx.y * (32 * OPB) + (2 * op + o) * 16 + 4 * k;
-        if (oc >= p.OC) continue;
-        // the epilogue rows of the lane's four channels and the residual of its 2 x 2 output pixels are requested FIRST, the inverse transform runs in
-        // the shadow of those loads (requested where they are used -- a table load, then per pixel a residual load, each waited out -- they were eight
-        // exposed L2 round trips per wave: conv1x1_stream's phase trace, DESIGN.md 5.1-8, found the same pattern)
-        float4 e4[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) e4[c] = epi[oc + c];
-        size_t idx4[2][2];
-        bool ok4[2][2];
-        float4 rv4[2][2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int cx = 0; cx < 2; ++cx) {
-                ok4[r][cx] = !(n >= p.N || oy + r >= p.OH || ox + cx >= p.OW);
-                idx4[r][cx] = ((static_cast<size_t>(n) * p.OH + oy + r) * p.OW + ox + cx) * p.OC + oc;
-                rv4[r][cx] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (p.res && p.splitK == 1 && ok4[r][cx]) rv4[r][cx] = *reinterpret_cast<const float4*>(p.res + idx4[r][cx]);
-            }
-        f32x4 yv[2][2];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float t0[4], t1[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                t0[j] = acc[0 * 4 + j][o][c] + acc[1 * 4 + j][o][c] + acc[2 * 4 + j][o][c];
-                t1[j] = acc[1 * 4 + j][o][c] - acc[2 * 4 + j][o][c] - acc[3 * 4 + j][o][c];
-            }
-            yv[0][0][c] = t0[0] + t0[1] + t0[2];
-            yv[0][1][c] = t0[1] - t0[2] - t0[3];
-            yv[1][0][c] = t1[0] + t1[1] + t1[2];
-            yv[1][1][c] = t1[1] - t1[2] - t1[3];
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int cx = 0; cx < 2; ++cx) {
-                if (!ok4[r][cx]) continue;
-                const size_t idx = idx4[r][cx];
-                float o4[4];
-                if (p.splitK > 1) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) o4[c] = yv[r][cx][c];
-                    *reinterpret_cast<float4*>(ws + static_cast<size_t>(blockIdx.z) * (static_cast<size_t>(p.N) * p.OH * p.OW * p.OC) + idx) =
-                        make_float4(o4[0], o4[1], o4[2], o4[3]);
-                    continue;
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float vv = epi_affine(yv[r][cx][c], e4[c], p.useBN);
-                    o4[c] = apply_act<SIMPLE>(ac, vv, 0.0f);
-                }
-                if (p.res) {
-                    const float4 rv = rv4[r][cx];
-                    o4[0] = add_act(p.ac2, addSimple, o4[0] + rv.x);
-                    o4[1] = add_act(p.ac2, addSimple, o4[1] + rv.y);
-                    o4[2] = add_act(p.ac2, addSimple, o4[2] + rv.z);
-                    o4[3] = add_act(p.ac2, addSimple, o4[3] + rv.w);
-                }
-                *reinterpret_cast<float4*>(y + idx) = make_float4(o4[0], o4[1], o4[2], o4[3]);
-            }
-    }
+typedef void (*WinoCatFn)(WinoParams, WinoCatParams, ActCfg, const float*, const float4*, const float4*, float*, float*);
+template <bool SIMPLE>
+WinoCatFn pick_wino_cat(int opb, int ks) {
+    return ks == 2 ? conv2d_wino_cat_kernel<SIMPLE, 1, 2> : opb == 2 ? conv2d_wino_cat_kernel<SIMPLE, 2> : conv2d_wino_cat_kernel<SIMPLE, 1>;
 }
 
 struct WinoConvPlan : ConvPlanBase {
@@ -355,8 +114,29 @@ struct WinoConvPlan : ConvPlanBase {
     bool simple = true;
     int opb = 1;
     int ks = 1; // K groups per block (2: eight waves, the channel chunks split inside the block)
+    WinoCatParams cp = {}; // chain rule K (g.C0 > 0): two inputs in the concat's order
+    WinoCatFn catKernel = nullptr;
+
+    int run_cat(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) {
+        SNNHIP_REQUIRE(nIn == 2, "conv2d+concat: expects 2 inputs, got %d", nIn);
+        const snnhip_tensor *x0 = in[0], *x1 = in[1];
+        SNNHIP_REQUIRE(x0->n == p.N && x0->h == cp.srcH && x0->w == cp.srcW && x0->c == cp.pitch0 && x0->dtype == SNNHIP_F32,
+                       "conv2d+concat: input 0 dims %dx%dx%dx%d (dtype %d) != plan %dx%dx%dx%d fp32", x0->n, x0->h, x0->w, x0->c, x0->dtype, p.N, cp.srcH, cp.srcW, cp.pitch0);
+        SNNHIP_REQUIRE(x1->n == p.N && x1->h == p.H && x1->w == p.W && x1->c == cp.pitch1 && x1->dtype == SNNHIP_F32,
+                       "conv2d+concat: input 1 dims %dx%dx%dx%d (dtype %d) != plan %dx%dx%dx%d fp32", x1->n, x1->h, x1->w, x1->c, x1->dtype, p.N, p.H, p.W, cp.pitch1);
+        SNNHIP_REQUIRE(out->n == p.N && out->h == p.OH && out->w == p.OW && out->c == p.OC && out->dtype == SNNHIP_F32, "conv2d: output dims %dx%dx%dx%d != plan %dx%dx%dx%d",
+                       out->n, out->h, out->w, out->c, p.N, p.OH, p.OW, p.OC);
+        WinoCatParams c = cp; // per-launch copy: input 1's pointer travels in the kernel argument block
+        c.x1 = x1->data;
+        const float4* e4 = reinterpret_cast<const float4*>(d_epi);
+        SNNHIP_LAUNCH(catKernel, grid, dim3(256 * opb * ks), ldsBytes, ctx->stream, p, c, ac, x0->data, reinterpret_cast<const float4*>(d_u), e4, out->data, d_ws);
+        SNNHIP_CHECK_HIP(hipGetLastError());
+        if (p.splitK > 1) return launch_splitk_reduce(ctx, p.OC, p.splitK, p.useBN, ac, d_ws, e4, out, nullptr, p.ac2);
+        return SNNHIP_OK;
+    }
 
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
+        if (catKernel) return run_cat(in, nIn, out);
         SNNHIP_REQUIRE(nIn == (fusedAdd ? 2 : 1), "conv2d: expects %d input(s), got %d", fusedAdd ? 2 : 1, nIn);
         const snnhip_tensor* x = in[0];
         WinoParams q = p; // per-launch copy: the residual pointer travels in the kernel argument block
@@ -392,13 +172,28 @@ struct WinoConvPlan : ConvPlanBase {
 
 } // namespace
 
+// where this kernel is a layer's own plan with nothing forced (make_conv2d_mfma_plan, and chain rule K under SNNHIP_CAT_KERNEL=auto): GEMM-sized channel
+// counts, no norm in the staging, no switch that pins another kernel or a block shape
+bool conv2d_wino_is_default(const ConvGeom& g) {
+    const char* w = snnhip::option("SNNHIP_CONV_WINO");
+    return !snnhip::option("SNNHIP_CONV") && !(w && atoi(w) == 0) && !snnhip::option("SNNHIP_CONV_BN") && !snnhip::option("SNNHIP_CONV_C8") && g.IC >= 32 && g.OC >= 32 && !g.normShift;
+}
+
 int make_conv2d_wino_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out) {
     // eligibility: fp32, 3x3, stride 1, zero padding (or none), no fused Pad in front, whole 8-channel chunks and 16-channel output blocks
-    if (g.dtype != SNNHIP_F32 || g.kh != 3 || g.kw != 3 || g.sh != 1 || g.sw != 1 || g.preMode != 0) return SNNHIP_E_UNSUPPORTED;
+    // chain rule K (g.C0 > 0): two sources, whole chunks in each, no third input (fused Add), no norm in the staging; input 0 alone may sit behind a
+    // nearest x2 upsampling (catUp: the identity pad + shift of rule D, srcH x srcW its low-resolution extent) -- every other fused Pad stays refused
+    const bool cat = g.C0 > 0;
+    const bool catUp = cat && g.catUp && g.preMode == SNNHIP_PAD_CONSTANT && g.preX == 0 && g.preY == 0 && g.preShift == 1 && g.H == 2 * g.srcH && g.W == 2 * g.srcW;
+    if (g.dtype != SNNHIP_F32 || g.kh != 3 || g.kw != 3 || g.sh != 1 || g.sw != 1 || (g.preMode != 0 && !catUp) || (g.catUp && !catUp)) return SNNHIP_E_UNSUPPORTED;
     if (g.padMode != SNNHIP_PAD_CONSTANT && g.padMode != SNNHIP_PAD_NONE) return SNNHIP_E_UNSUPPORTED;
     if (g.IC % 8 != 0 || g.OC % 16 != 0 || g.act == SNNHIP_ACT_SILU_QUIRK) return SNNHIP_E_UNSUPPORTED;
-    const double inCount = static_cast<double>(g.N) * g.H * g.W * g.IC, outCount = static_cast<double>(g.N) * g.OH * g.OW * g.OC;
-    if (inCount >= 2147483647.0 || outCount >= 2147483647.0) return SNNHIP_E_UNSUPPORTED; // 32-bit element offsets in the staging path
+    if (cat && (g.C0 >= g.IC || g.C0 % 8 != 0 || g.addAct >= 0 || g.normShift)) return SNNHIP_E_UNSUPPORTED;
+    const int srcH0 = catUp ? g.srcH : g.H, srcW0 = catUp ? g.srcW : g.W;
+    // 32-bit element offsets in the staging path: each source on its own
+    const double inCount = cat ? std::max(static_cast<double>(g.N) * srcH0 * srcW0 * g.C0, static_cast<double>(g.N) * g.H * g.W * (g.IC - g.C0)) : static_cast<double>(g.N) * g.H * g.W * g.IC;
+    const double outCount = static_cast<double>(g.N) * g.OH * g.OW * g.OC;
+    if (inCount >= 2147483647.0 || outCount >= 2147483647.0) return SNNHIP_E_UNSUPPORTED;
 
     // block tile: TB x TTH x TTW = 64 Winograd tiles, minimising padded tiles; a wave's 16 consecutive tiles must not straddle images
     // (TTH * TTW >= 16 and TTH >= 16 / TTW when TTW < 16: the bank analysis of the patch reads assumes whole tile rows of one image)
@@ -490,7 +285,22 @@ int make_conv2d_wino_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     plan->opb = opb;
     plan->grid = dim3(p.tilesX * p.tilesY * up_div(g.N, TB), p.OCblocks, p.splitK);
     plan->dtype = SNNHIP_F32;
-    for (int s = 0; s < 2; ++s) {
+    if (cat) {
+        plan->numInputs = 2;
+        plan->cp.c0Chunks = g.C0 / 8;
+        plan->cp.pitch0 = g.C0;
+        plan->cp.pitch1 = g.IC - g.C0;
+        plan->cp.srcH = srcH0;
+        plan->cp.srcW = srcW0;
+        plan->cp.shift0 = catUp ? 1 : 0;
+        plan->catKernel = plan->simple ? pick_wino_cat<true>(opb, ks) : pick_wino_cat<false>(opb, ks);
+        if (ldsAll > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(plan->catKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsAll)) != hipSuccess) {
+            set_error("conv2d_wino: hipFuncSetAttribute(%zu) failed", ldsAll);
+            delete plan;
+            return SNNHIP_E_HIP;
+        }
+    }
+    for (int s = 0; s < 2 && !cat; ++s) {
         const void* fn = ks == 2 ? (s ? reinterpret_cast<const void*>(conv2d_wino_kernel<true, 1, 2>) : reinterpret_cast<const void*>(conv2d_wino_kernel<false, 1, 2>))
                          : opb == 2 ? (s ? reinterpret_cast<const void*>(conv2d_wino_kernel<true, 2>) : reinterpret_cast<const void*>(conv2d_wino_kernel<false, 2>))
                                   : (s ? reinterpret_cast<const void*>(conv2d_wino_kernel<true, 1>) : reinterpret_cast<const void*>(conv2d_wino_kernel<false, 1>));
@@ -547,6 +357,13 @@ int make_conv2d_wino_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     snprintf(buf, sizeof(buf), "conv2d_mfma_wino_f32_16x16x4 F(2x2,3x3) k=3x3 s=1 ic=%d oc=%d tile=%dx%dx%dpx x %doc chunk=8 lds=%zuB kgroups=%d splitK=%d mfma_flops=%.6g",
              g.IC, g.OC, TB, 2 * TTH, 2 * TTW, ocPerBlock, ldsAll, ks, p.splitK, mfmaFlops);
     plan->desc = buf;
+    if (cat) { // inDims describes input 0, as the conv2d_mfma cat plan does; both inputs are read once
+        plan->inDims[1] = srcH0; plan->inDims[2] = srcW0; plan->inDims[3] = g.C0;
+        plan->bytes = 4.0 * (static_cast<double>(g.N) * srcH0 * srcW0 * g.C0 + static_cast<double>(g.N) * g.H * g.W * (g.IC - g.C0) + static_cast<double>(g.N) * g.OH * g.OW * g.OC +
+                             static_cast<double>(g.OC) * g.IC * 9);
+        plan->desc += " +concat(" + std::to_string(g.C0) + "+" + std::to_string(g.IC - g.C0) + ")";
+        if (catUp) plan->desc += " +upsample(x2 on input 0)";
+    }
     if (plan->fusedAdd) {
         plan->desc += " +add";
         plan->bytes += 4.0 * static_cast<double>(g.N) * g.OH * g.OW * g.OC;

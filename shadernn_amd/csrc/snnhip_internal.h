@@ -248,6 +248,8 @@ int ksplit_group_end(snnhip_ctx* ctx);
 int make_conv2d_stem_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out); // fp16 9x9 s1, IC <= 4; tried first by make_conv2d_mfma_plan
 int make_conv2d_stem32_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out); // fp32 stems (IC <= 4), tried first by make_conv2d_mfma_plan
 int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out); // fp16 3x3 s1, large maps; tried first by make_conv2d_mfma_plan
+bool conv2d_wino_is_default(const ConvGeom& g); // the gates under which make_conv2d_mfma_plan tries conv2d_wino / conv2d_wide_f16 with nothing forced
+bool conv2d_wide_is_default();
 int make_conv2d_widep_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out); // ... IC = OC = 128: persistent blocks; tried first by make_conv2d_wide_plan
 int make_conv2d_upconv_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out); // fp16 upsample x2 -> reflect pad 1 -> 3x3 on the low-resolution tensor; tried by make_conv2d_mfma_plan
 int make_conv2d_upconv2_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oihw, const std::vector<float>& epi4, snnhip_plan** out); // fp32 / fp16 upsample x2 -> 2x2 "same" as nine pre-summed GEMMs on the low-resolution tensor; tried by make_conv2d_mfma_plan

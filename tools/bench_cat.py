@@ -4,9 +4,11 @@ input 0; batch 8, fp32 and fp16): chain rule K's one two-source convolution laun
 launch,] the Concatenate launch and the layer's own convolution plan as the default routing builds it (conv2d_wino in fp32, conv2d_wide_f16 / conv2d_mfma
 in fp16) -- in one process.  Device times are event pairs around `reps` back-to-back runs; per round the two forms run in mirrored order (new, old, old,
 new), the figure is the median over the rounds with [min, max].  A (precision, layer class) is routed to the rule by default only where it won by more
-than the run's own spread: new max < old min.  --models adds the tools/bench_models.py lines of the two graphs with and without SNNHIP_CAT=0.
+than the run's own spread: new max < old min.  A third form runs in the same rounds where it exists: the rule on the layer's own kernel
+(SNNHIP_CAT_KERNEL=auto: conv2d_wino's two-source instances in fp32, conv2d_wide_f16's in fp16; profiles/cat_kernel_layers.json).  --models adds the tools/bench_models.py lines of
+the two graphs with and without SNNHIP_CAT=0 and under SNNHIP_CAT_KERNEL=auto.
 
-    python tools/bench_cat.py [--reps 50] [--rounds 7] [--batch 8] [--models] [--json profiles/cat_layers.json]
+    python tools/bench_cat.py [--reps 50] [--rounds 7] [--batch 8] [--models] [--json profiles/cat_kernel_layers.json]
 """
 import argparse
 import json
@@ -54,10 +56,20 @@ def main():
             fused = capi.chain_plan(ctx, per_layer)
             capi.set_option("SNNHIP_CONV", None)
             assert "+concat" in fused.describe(), fused.describe()
+            # third form: the rule on the layer's own kernel (SNNHIP_CAT_KERNEL=auto: conv2d_wino's two-source instances in fp32, conv2d_wide_f16's in fp16); None where auto keeps today's decision
+            capi.set_option("SNNHIP_CAT_KERNEL", "auto")
+            try:
+                own = capi.chain_plan(ctx, per_layer)
+            except capi.SnnHipError:
+                own = None
+            capi.set_option("SNNHIP_CAT_KERNEL", None)
+            if own is not None and ("+concat" not in own.describe() or own.describe() == fused.describe()):
+                own.destroy()
+                own = None
             ta, tb = capi.Tensor.from_numpy(ctx, xa, dtype=dt), capi.Tensor.from_numpy(ctx, xb, dtype=dt)
             tu = capi.Tensor(ctx, a.batch, s, s, c0, dtype=dt) if up else ta
             tc = capi.Tensor(ctx, a.batch, s, s, c0 + c1, dtype=dt)
-            ys = {k: capi.Tensor(ctx, a.batch, s, s, oc, dtype=dt) for k in ("cat", "separate")}
+            ys = {k: capi.Tensor(ctx, a.batch, s, s, oc, dtype=dt) for k in ("cat", "separate") + (("own",) if own else ())}
 
             def separate():
                 if up:
@@ -66,6 +78,8 @@ def main():
                 per_layer[-1].run(tc, ys["separate"])
 
             run = {"cat": lambda: fused.run([ta, tb], ys["cat"]), "separate": separate}
+            if own:
+                run["own"] = lambda: own.run([ta, tb], ys["own"])
             for k in run:  # warm-up
                 for _ in range(5):
                     run[k]()
@@ -74,7 +88,7 @@ def main():
             us = {k: [] for k in run}
             for _ in range(a.rounds):
                 pair = {k: [] for k in run}
-                for k in ("cat", "separate", "separate", "cat"):
+                for k in ("cat", "own", "separate", "separate", "own", "cat") if own else ("cat", "separate", "separate", "cat"):
                     timer.start()
                     for _ in range(a.reps):
                         run[k]()
@@ -89,9 +103,14 @@ def main():
                          "wins_beyond_spread": st["cat"]["max"] < st["separate"]["min"], "max_abs_difference": diff,
                          "nominal_tflops_cat": fused.cost()[0] / st["cat"]["median"] * 1e-6,
                          "plans": {"cat": fused.describe(), "separate": [p.describe() for p in per_layer]}})
+            if own:
+                rows[-1].update({"own_kernel_us": st["own"], "own_kernel_speedup_median": st["separate"]["median"] / st["own"]["median"],
+                                 "own_kernel_wins_beyond_spread": st["own"]["max"] < st["separate"]["min"],
+                                 "own_kernel_max_abs_difference": float(np.abs(ys["own"].numpy().astype(np.float64) - ys["separate"].numpy()).max())})
+                rows[-1]["plans"]["own_kernel"] = own.describe()
             for t in {ta, tb, tu, tc} | set(ys.values()):
                 t.free()
-            for p in [fused] + per_layer:
+            for p in [fused] + ([own] if own else []) + per_layer:
                 p.destroy()
     routing = {}
     for r in rows:
@@ -102,7 +121,7 @@ def main():
         out["models"] = {}
         for model in ("unet", "yolov3-tiny"):
             for fp16 in (False, True):
-                for label, env in (("default", {}), ("SNNHIP_CAT=0", {"SNNHIP_CAT": "0"}), ("SNNHIP_CONV=cat", {"SNNHIP_CONV": "cat"})):
+                for label, env in (("default", {}), ("SNNHIP_CAT=0", {"SNNHIP_CAT": "0"}), ("SNNHIP_CONV=cat", {"SNNHIP_CONV": "cat"}), ("SNNHIP_CAT_KERNEL=auto", {"SNNHIP_CAT_KERNEL": "auto"})):
                     cmd = [sys.executable, os.path.join(ROOT, "tools", "bench_models.py"), "--model", model, "--batch", str(a.batch)] + (["--fp16"] if fp16 else [])
                     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, **env), timeout=600)
                     line = [ln for ln in r.stdout.splitlines() if "ms/batch" in ln]
