@@ -800,7 +800,11 @@ int snnhip_tensor_argmax(const snnhip_tensor* t, int n, int* out_index);
  * Rule L: {Conv2D stride 1, MaxPooling2D 2x2 stride 2 without padding} become ONE convolution launch that writes the pooled
  * tensor; its description carries "+maxpool(2x2)", its cost counts the input, the weights and the pooled output.  Off unless SNNHIP_POOL_FUSE=1
  * (environment or snnhip_set_option); SNNHIP_CONV=pool takes it wherever it can run.  Max pooling only, activation none / relu / relu6 / leakyRelu,
- * IC * kh * kw <= 1152, no fused Pad / Add / norm on the convolution; anything else keeps the separate plans. */
+ * IC * kh * kw <= 1152, no fused Pad / Add / norm on the convolution; anything else keeps the separate plans.
+ * SNNHIP_POOL_KERNEL, with rule L on, builds its plan on the layer's own kernel: "wino" = the pooling instances of the fp32
+ * Winograd kernel wherever it accepts the geometry (3x3, zero or no padding, IC a multiple of 8, OC of 16), "auto" = the same where the layer's own plan is
+ * that kernel, "wide" = those of the wide fp16 kernel (3x3, IC a multiple of 16, OC of 32); where the named kernel declines, the plan above; any other word returns
+ * SNNHIP_E_INVALID from every chain plan creation.  Unset: as above. */
 int snnhip_chain_plan_create(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_plan** out);
 /* The fp16 ESPCN rules (SNNHIP_ESPCN_F16=1) keep their weights as lane-ordered fp16 images for the f16 matrix cores.  This
  * is the packing itself, host side only (no context, no device), so that it can be checked without a GPU.  w_oihw is fp32 and is rounded to nearest

@@ -60,6 +60,11 @@ struct Switches {
     // rule L: opt-in -- SNNHIP_POOL_FUSE=1 switches it on, SNNHIP_CONV=pool takes it wherever it can run
     const char* const poolWord = option("SNNHIP_POOL_FUSE");
     const bool poolFuse = (poolWord && poolWord[0] && strcmp(poolWord, "0") != 0) || is(option("SNNHIP_CONV"), "pool");
+    // ... and SNNHIP_POOL_KERNEL names the kernel whose pooling instances run it, with SNNHIP_CAT_KERNEL's semantics: wino (fp32, conv2d_wino_pool_kernel) takes the
+    // rule wherever that kernel accepts the geometry, its IC, OC >= 32 gate skipped; auto takes it where the layer's own plan would be that kernel (SNNHIP_CONV=pool
+    // pins the conv2d_mfma form, as every SNNHIP_CONV= word pins a family); unset: the conv2d_mfma POOL instances, as ever; any other word is an error
+    const char* const poolKernelWord = option("SNNHIP_POOL_KERNEL");
+    const bool poolWino = is(poolKernelWord, "wino"), poolWide = is(poolKernelWord, "wide"), poolAuto = is(poolKernelWord, "auto");
 };
 
 bool plain_act(int act) { return act >= 0 && act <= SNNHIP_ACT_SILU; }
@@ -561,6 +566,21 @@ int rule_conv_pool(Planner& pl, int i, Step& st) {
     g2.poolOH = pd.OH;
     g2.poolOW = pd.OW;
     snnhip_plan* fused = nullptr;
+    // SNNHIP_POOL_KERNEL: the pooling instances of the layer's own kernel -- conv2d_wino_pool_kernel (fp32): a lane's F(2x2,3x3) output tile is one window, and
+    // its split over blockIdx.z ends in splitk_reduce_pool_kernel.  wino: wherever that kernel accepts the geometry; auto: where the layer's own plan is that
+    // kernel (conv2d_wino_is_default: false under any SNNHIP_CONV= word, SNNHIP_CONV=pool included).  Where it declines, the conv2d_mfma form below.
+    // conv2d_wide_pool_kernel (fp16): the vertical maximum in registers, the horizontal one at the read-out of the output tile.  wide: its blocks-per-CU gate
+    // skipped (make_conv2d_wide_plan reads the word); auto: conv2d_wide_is_default(), the size gate inside the plan function holds.
+    const bool onWino = g.dtype == SNNHIP_F32 && (pl.sw.poolWino || (pl.sw.poolAuto && conv2d_wino_is_default(g)));
+    const bool onWide = g.dtype == SNNHIP_F16 && (pl.sw.poolWide || (pl.sw.poolAuto && conv2d_wide_is_default()));
+    if (onWino || onWide) {
+        const int rc = onWino ? make_conv2d_wino_plan(pl.ctx, g2, cv->w_oihw.data(), cv->epi4, &fused) : make_conv2d_wide_plan(pl.ctx, g2, cv->w_oihw.data(), cv->epi4, &fused);
+        if (rc == SNNHIP_OK) return wrap_plan(pl, fused, true, 2, st);
+        if (rc != SNNHIP_E_UNSUPPORTED) {
+            pl.rc = rc;
+            return 0;
+        }
+    }
     if (make_conv2d_mfma_plan(pl.ctx, g2, cv->w_oihw.data(), cv->epi4, &fused) != SNNHIP_OK) return 0;
     return wrap_plan(pl, fused, true, 2, st);
 }
@@ -914,6 +934,10 @@ void pass_u8_ends(Planner& pl) {
 
 int make_chain_plan(snnhip_ctx* ctx, snnhip_plan* const* plans, int n, snnhip_plan** out) {
     const Switches sw;
+    if (sw.poolKernelWord && !sw.poolWino && !sw.poolWide && !sw.poolAuto) { // (whatever the chain holds, whether rule L is on or not)
+        set_error("SNNHIP_POOL_KERNEL=%s: expected wino, wide or auto", sw.poolKernelWord);
+        return SNNHIP_E_INVALID;
+    }
     // ---- rule E: Conv2D (MFMA kernel) + Add -> one launch, the residual is added in the convolution's epilogue.  The fused plan takes TWO
     // inputs, snnhip_plan_run_n(plan, {conv input, residual}, 2, out), so it is returned as is instead of being wrapped into a ChainPlan.
     if (n == 2 && !sw.noAddFusion) {

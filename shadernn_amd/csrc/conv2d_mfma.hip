@@ -97,7 +97,57 @@ __global__ __launch_bounds__(256) void splitk_reduce4_kernel(unsigned MN4, unsig
     }
 }
 
+// The pass behind a split-K convolution whose plan ends in MaxPooling2D 2x2 stride 2 (chain rule L on conv2d_wino_pool_kernel: fp32, the simple epilogue): a thread
+// owns four consecutive channels of one POOLED pixel.  Each of the window's up to four positions is summed over the splitK slices in slice order (z = 0 first: the
+// value the pass above gives that position, bit for bit), finished (bias -> BN -> activation) and taken into the pooling plan's maximum (m = -100000, positions
+// inside OH x OW only).  All of a position's partial sums are requested before the first addition, as above; ws is read once, the full-resolution tensor never written.
+__global__ __launch_bounds__(256) void splitk_reduce_pool_kernel(unsigned total4, unsigned OC4, int OH, int OW, int poolOH, int poolOW, int splitK, size_t MN4, int useBN, ActCfg ac,
+                                                                const float4* __restrict__ ws, const float4* __restrict__ epi, float4* __restrict__ y) {
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total4; i += gridDim.x * 256u) {
+        const unsigned c4 = i % OC4, px = i / OC4;
+        const int qx = static_cast<int>(px % poolOW), qy = static_cast<int>((px / poolOW) % poolOH), n = static_cast<int>(px / (static_cast<unsigned>(poolOW) * poolOH));
+        const float4 ee[4] = {epi[4 * c4], epi[4 * c4 + 1], epi[4 * c4 + 2], epi[4 * c4 + 3]};
+        float m[4] = {-100000.0f, -100000.0f, -100000.0f, -100000.0f};
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int cx = 0; cx < 2; ++cx) {
+                const int oy = 2 * qy + r, ox = 2 * qx + cx;
+                if (oy >= OH || ox >= OW) continue;
+                const size_t at = ((static_cast<size_t>(n) * OH + oy) * OW + ox) * OC4 + c4;
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                for (int z0 = 0; z0 < splitK; z0 += 4) { // four slices in flight
+                    float4 part[4];
+#pragma unroll
+                    for (int z = 0; z < 4; ++z) part[z] = ws[static_cast<size_t>(min(z0 + z, splitK - 1)) * MN4 + at];
+#pragma unroll
+                    for (int z = 0; z < 4; ++z)
+                        if (z0 + z < splitK) {
+                            v[0] += part[z].x;
+                            v[1] += part[z].y;
+                            v[2] += part[z].z;
+                            v[3] += part[z].w;
+                        }
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) m[k] = fmaxf(m[k], apply_act<true>(ac, epi_affine(v[k], ee[k], useBN), 0.0f));
+            }
+        y[i] = make_float4(m[0], m[1], m[2], m[3]);
+    }
+}
+
 } // namespace
+
+int launch_splitk_reduce_pool(snnhip_ctx* ctx, int OH, int OW, int splitK, int useBN, const ActCfg& ac, const float* ws, const float4* e4, snnhip_tensor* out) {
+    const size_t total4 = out->count() / 4, MN4 = static_cast<size_t>(out->n) * OH * OW * (out->c / 4);
+    SNNHIP_REQUIRE(out->dtype == SNNHIP_F32 && out->c % 4 == 0 && act_is_simple(ac.act) && total4 < 0xffffffffull, "split-K pooling reduce: fp32, OC %% 4 == 0, a simple activation (OC = %d)", out->c);
+    const size_t cap = static_cast<size_t>(ctx->props.multiProcessorCount > 0 ? ctx->props.multiProcessorCount : 256) * 8;
+    const dim3 gr(static_cast<unsigned>(std::min<size_t>((total4 + 255) / 256, cap)));
+    SNNHIP_LAUNCH(splitk_reduce_pool_kernel, gr, dim3(256), 0, ctx->stream, static_cast<unsigned>(total4), static_cast<unsigned>(out->c / 4), OH, OW, out->h, out->w, splitK, MN4, useBN, ac,
+                  reinterpret_cast<const float4*>(ws), e4, reinterpret_cast<float4*>(out->data));
+    SNNHIP_CHECK_HIP(hipGetLastError());
+    return SNNHIP_OK;
+}
 
 // Launches the split-K reduce / epilogue pass: out = [act2(] act(BN(bias + sum_z ws[z])) [+ res)], shared with conv2d_wino.hip.
 int launch_splitk_reduce(snnhip_ctx* ctx, int OC, int splitK, int useBN, const ActCfg& ac, const float* ws, const float4* e4, snnhip_tensor* out,

@@ -1,6 +1,6 @@
 // conv2d_wide_body.h -- the body of conv2d_wide_kernel and conv2d_wide_cat_kernel (conv2d_wide_f16.hip), included INSIDE both __global__ definitions: as a shared
 // __device__ function the single-source instances came out with another schedule.  In scope at the include: the template parameters WM, WN, NT, C8, R, SIMPLE,
-// the constants RES and CAT, and p, cp, ac, x, wp, epi, y.
+// the constants RES, CAT and POOL, and p, cp, pq (WidePoolParams: chain rule L, conv2d_wide_pool_kernel), ac, x, wp, epi, y.
     static_assert(WM * WN == 4, "4 waves per block");
     static_assert(!(CAT && RES), "the two-source form has no residual input");
     typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -233,6 +233,62 @@
     // the general form below (run-time batch-norm select, mul / max / med3 activation) is seven, and with 128 values per lane the epilogue's
     // VALU work was a third of the wave's MFMA time
     const bool fastEpi = SIMPLE && !p.useBN && ac.alpha == 1.0f && ac.hi == __builtin_huge_valf();
+    if (POOL) {
+        // ---- chain rule L: MaxPooling2D 2x2 stride 2 behind the epilogue, a two-stage maximum.  The tile's rows start even (oy0 = ty << THs) and MT = 4 is
+        // even, so a window's two ROWS are the lane's accumulators t = 2 tp, 2 tp + 1; its two COLUMNS are in neighbouring lanes.
+        // Stage 1, registers: bias -> BN -> activation in fp32 on both rows (BN's scale may be negative: the maximum stays behind it), the pooling plan's own
+        // rule m = -100000, m = max(m, v) over the rows inside OH, ONE rounding to half, one ds_write_b64 per channel run and row PAIR into the pooled-row tile
+        // [PIX / 64 rows][32 columns][BN halfs]: half the plain epilogue's LDS writes.  Stage 2, read-out: the tile leaves as 16-byte vectors, each the packed
+        // half maximum (v_pk_max_f16) of two adjacent pixels' vectors, the odd column only where it is inside OW.  Rounding to half is monotone, so
+        // max(half(a), half(b)) = half(max(a, b)): the result is the separate launches', bit for bit.
+        static_assert(!POOL || (MT % 2 == 0 && !RES && !CAT), "the pooling epilogue: whole row pairs per lane, one source, no residual");
+        _Float16* const ptile = otile;
+#pragma unroll
+        for (int u = 0; u < NT; ++u)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float4 e[4];
+                if (p.useBN) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = etab[u * 32 + 8 * g + k];
+                } else {
+                    e[0].x = bias4[u][g].x; e[1].x = bias4[u][g].y; e[2].x = bias4[u][g].z; e[3].x = bias4[u][g].w;
+                }
+#pragma unroll
+                for (int tp = 0; tp < MT / 2; ++tp) {
+                    const bool in2 = oy0 + wm * MT + 2 * tp + 1 < p.OH; // (the first row is inside wherever the window is stored)
+                    h4 o;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float m = -100000.0f;
+#pragma unroll
+                        for (int r = 0; r < 2; ++r) {
+                            const float a = acc[2 * tp + r][u][4 * g + k];
+                            const float v = fastEpi ? fmaxf(a + e[k].x, ac.lo) : apply_act<true>(ac, epi_affine(a, e[k], p.useBN), 0.0f); // (the plain epilogue's two forms)
+                            if (r == 0 || in2) m = fmaxf(m, v);
+                        }
+                        o[k] = static_cast<_Float16>(m);
+                    }
+                    *reinterpret_cast<h4*>(ptile + ((wm * (MT / 2) + tp) * 32 + l32) * EPITCH + wn * (NT * 32) + u * 32 + 8 * g + 4 * h) = o;
+                }
+            }
+        __syncthreads();
+        constexpr int PVPR = BN / 8;                    // 16-byte vectors per pooled pixel
+        constexpr int PNV = (PIX / 4) * PVPR / 256;     // ... per thread: PIX / 4 windows per tile
+#pragma unroll
+        for (int j = 0; j < PNV; ++j) {
+            const int v = tid + 256 * j;
+            const int i = v / PVPR, c8 = v - i * PVPR; // window i = (pooled row i >> 4, pooled column i & 15) of the tile
+            const int pr = i >> 4, pc = i & 15;
+            const int oy = oy0 + 2 * pr, ox = ox0 + 2 * pc, qy = oy >> 1, qx = ox >> 1;
+            const h8 a = *reinterpret_cast<const h8*>(ptile + (pr * 32 + 2 * pc) * EPITCH + c8 * 8);
+            const h8 b = *reinterpret_cast<const h8*>(ptile + (pr * 32 + 2 * pc + 1) * EPITCH + c8 * 8);
+            const h8 m = ox + 1 < p.OW ? __builtin_elementwise_max(a, b) : a;
+            if (oy < p.OH && ox < p.OW && qy < pq.poolOH && qx < pq.poolOW)
+                *reinterpret_cast<h8*>(y + static_cast<size_t>((n * pq.poolOH + qy) * pq.poolOW + qx) * p.OC + blockIdx.y * BN + c8 * 8) = m;
+        }
+        return;
+    }
     constexpr int VPR = BN / 8;             // 16-byte vectors per pixel of the tile
     constexpr int NV = PIX * VPR / 256;     // ... per thread
     int oofs[NV];

@@ -82,23 +82,40 @@ struct WideCatParams {
     int C0;             // channels taken from input 0 = its pixel pitch
 };
 
+// POOL (chain rule L: Conv2D -> MaxPooling2D 2x2 stride 2, conv2d_wide_pool_kernel below): the K loop, the LDS-DMA staging and the counted vmcnt are the plain
+// kernel's; only the epilogue behind the loop's last barrier differs (conv2d_wide_body.h: the vertical maximum in registers, the horizontal one at the read-out).
+struct WidePoolParams {
+    int poolOH, poolOW; // the pooling plan's own output extent: ceil or floor of OH / 2, OW / 2
+};
+
 template <int WM, int WN, int NT, int C8, int R, bool SIMPLE, bool RES>
 __global__ __launch_bounds__(256, 2) void conv2d_wide_kernel(WideParams p, ActCfg ac, const _Float16* __restrict__ x, const float4* __restrict__ wp,
                                                           const float4* __restrict__ epi, _Float16* __restrict__ y) {
-    constexpr bool CAT = false;
+    constexpr bool CAT = false, POOL = false;
     const WideCatParams cp = {}; // (unused: every use sits behind CAT)
+    const WidePoolParams pq = {}; // (... behind POOL)
 #include "conv2d_wide_body.h"
 }
 // the two-source instances (chain rule K); x = input 0, cp.x1 = input 1
 template <int WM, int WN, int NT, int C8, int R, bool SIMPLE>
 __global__ __launch_bounds__(256, 2) void conv2d_wide_cat_kernel(WideParams p, WideCatParams cp, ActCfg ac, const _Float16* __restrict__ x, const float4* __restrict__ wp,
                                                               const float4* __restrict__ epi, _Float16* __restrict__ y) {
-    constexpr bool RES = false, CAT = true;
+    constexpr bool RES = false, CAT = true, POOL = false;
+    const WidePoolParams pq = {};
+#include "conv2d_wide_body.h"
+}
+// the pooling instances (chain rule L: the simple activations only); y = [N][pq.poolOH][pq.poolOW][OC]
+template <int WM, int WN, int NT, int C8, int R>
+__global__ __launch_bounds__(256, 2) void conv2d_wide_pool_kernel(WideParams p, WidePoolParams pq, ActCfg ac, const _Float16* __restrict__ x, const float4* __restrict__ wp,
+                                                               const float4* __restrict__ epi, _Float16* __restrict__ y) {
+    constexpr bool SIMPLE = true, RES = false, CAT = false, POOL = true;
+    const WideCatParams cp = {};
 #include "conv2d_wide_body.h"
 }
 
 typedef void (*WideFn)(WideParams, ActCfg, const _Float16*, const float4*, const float4*, _Float16*);
 typedef void (*WideCatFn)(WideParams, WideCatParams, ActCfg, const _Float16*, const float4*, const float4*, _Float16*);
+typedef void (*WidePoolFn)(WideParams, WidePoolParams, ActCfg, const _Float16*, const float4*, const float4*, _Float16*);
 
 struct WideConvPlan : ConvPlanBase {
     WideParams p;
@@ -111,10 +128,13 @@ struct WideConvPlan : ConvPlanBase {
     WideCatFn catKernel = nullptr; // chain rule K (g.C0 > 0): the two-source instance, cp its parameter block
     WideCatParams cp = {};
     bool fusedAdd = false;
+    WidePoolFn poolKernel = nullptr; // chain rule L (g.poolOH > 0): the output is the pooled tensor
+    WidePoolParams pq = {};
 
     // chain rule F: {mean, M2} of every output tile and channel next to the output (the epilogue's LDS round trip carries them: conv2d_wide_kernel)
     bool enableTileStats() override {
         if (statPart) return true;
+        if (poolKernel) return false; // (rule L: the pooling epilogue leaves before the statistics)
         if (fusedAdd) return false; // (rule E: the kernel instantiation with the residual carries no statistics code)
         void* buf = nullptr;
         const size_t bytes = static_cast<size_t>(p.N) * p.tilesY * p.tilesX * 2 * p.OC * sizeof(float);
@@ -150,6 +170,17 @@ struct WideConvPlan : ConvPlanBase {
             WideCatParams c2 = cp;
             c2.x1 = reinterpret_cast<const _Float16*>(in[1]->data);
             SNNHIP_LAUNCH(catKernel, grid, dim3(256), ldsBytes, ctx->stream, p, c2, ac, reinterpret_cast<const _Float16*>(in[0]->data), reinterpret_cast<const float4*>(d_w),
+                               reinterpret_cast<const float4*>(d_epi), reinterpret_cast<_Float16*>(out->data));
+            SNNHIP_CHECK_HIP(hipGetLastError());
+            return SNNHIP_OK;
+        }
+        if (poolKernel) { // chain rule L: one input, the pooled output
+            SNNHIP_REQUIRE(nIn == 1, "conv2d+maxpool: expects 1 input, got %d", nIn);
+            SNNHIP_REQUIRE(in[0]->n == p.N && in[0]->h == p.H && in[0]->w == p.W && in[0]->c == p.IC && in[0]->dtype == SNNHIP_F16,
+                           "conv2d+maxpool: input dims %dx%dx%dx%d (dtype %d) != plan %dx%dx%dx%d fp16", in[0]->n, in[0]->h, in[0]->w, in[0]->c, in[0]->dtype, p.N, p.H, p.W, p.IC);
+            SNNHIP_REQUIRE(out->n == p.N && out->h == pq.poolOH && out->w == pq.poolOW && out->c == p.OC && out->dtype == SNNHIP_F16,
+                           "conv2d+maxpool: output dims %dx%dx%dx%d (dtype %d) != plan %dx%dx%dx%d fp16", out->n, out->h, out->w, out->c, out->dtype, p.N, pq.poolOH, pq.poolOW, p.OC);
+            SNNHIP_LAUNCH(poolKernel, grid, dim3(256), ldsBytes, ctx->stream, p, pq, ac, reinterpret_cast<const _Float16*>(in[0]->data), reinterpret_cast<const float4*>(d_w),
                                reinterpret_cast<const float4*>(d_epi), reinterpret_cast<_Float16*>(out->data));
             SNNHIP_CHECK_HIP(hipGetLastError());
             return SNNHIP_OK;
@@ -209,9 +240,15 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     if (inCount >= 2147483647.0 || outCount >= 2147483647.0) return SNNHIP_E_UNSUPPORTED;
     const char* force = snnhip::option("SNNHIP_CONV");
     const char* catWord = snnhip::option("SNNHIP_CAT_KERNEL");
-    const bool forced = (force && strcmp(force, "wide") == 0) || (cat && catWord && strcmp(catWord, "wide") == 0); // (the rule's named kernel: the size gate is skipped)
+    // chain rule L (g.poolOH > 0), under the gates of conv2d_mfma's pooling form: the simple epilogue, one plain source, no residual, norm, fused Pad or
+    // upsampling, and a pooled extent whose every window has its first position inside the output; the persistent form below has no pooling epilogue
+    const bool pool = g.poolOH > 0;
+    if (pool && (!act_is_simple(g.act) || g.addAct >= 0 || g.normShift || g.preMode || cat || g.poolOW <= 0 || 2 * g.poolOH > g.OH + 1 || 2 * g.poolOW > g.OW + 1)) return SNNHIP_E_UNSUPPORTED;
+    const char* poolWord = snnhip::option("SNNHIP_POOL_KERNEL");
+    const bool forced = (force && strcmp(force, "wide") == 0) || (cat && catWord && strcmp(catWord, "wide") == 0) ||
+                        (pool && poolWord && strcmp(poolWord, "wide") == 0); // (the rule's named kernel: the size gate is skipped)
     // the 128 -> 128 body layers of the style graphs: the persistent form (conv2d_widep_f16.hip), unless it declines or SNNHIP_WIDE_PERSIST=0
-    if (make_conv2d_widep_plan(ctx, g, w_oihw, epi4, out) == SNNHIP_OK) return SNNHIP_OK;
+    if (!pool && make_conv2d_widep_plan(ctx, g, w_oihw, epi4, out) == SNNHIP_OK) return SNNHIP_OK;
 
     // block shape: 256 px x 128 oc when the channels fill it, else 512 px x 64 / 32 oc
     int WM = 4, NT = 2, BN = 64;
@@ -265,6 +302,14 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
         if (WM == 4 && NT == 1 && R <= 8) catFn = pick_wide_cat<4, 1, 1, 1, 8>(simple);
         if (!catFn) return SNNHIP_E_UNSUPPORTED;
     }
+    WidePoolFn poolFn = nullptr;
+    if (pool) {
+        if (WM == 2 && C8 == 2 && R <= 7) poolFn = conv2d_wide_pool_kernel<2, 2, 2, 2, 7>;
+        if (WM == 2 && C8 == 1 && R <= 4) poolFn = conv2d_wide_pool_kernel<2, 2, 2, 1, 4>;
+        if (WM == 4 && NT == 2 && R <= 8) poolFn = conv2d_wide_pool_kernel<4, 1, 2, 1, 8>;
+        if (WM == 4 && NT == 1 && R <= 8) poolFn = conv2d_wide_pool_kernel<4, 1, 1, 1, 8>;
+        if (!poolFn) return SNNHIP_E_UNSUPPORTED;
+    }
     if (!fn) return SNNHIP_E_UNSUPPORTED;
     const int PIX = 128 * WM;
     p.epiOfs = static_cast<int>(std::max(static_cast<size_t>(2) * p.bufFloats * 4, static_cast<size_t>(PIX) * (BN + 8) * 2) / 4);
@@ -285,6 +330,9 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     plan->kernel = fn;
     plan->catKernel = catFn;
     plan->cp.C0 = g.C0;
+    plan->poolKernel = poolFn;
+    plan->pq.poolOH = g.poolOH;
+    plan->pq.poolOW = g.poolOW;
 #ifdef SNNHIP_WIDE_LDS_PAD_KB // experiment builds (tools/exp_one.sh): extra LDS per block = fewer blocks per CU (what does a block do when it has the CU to itself?)
     plan->ldsBytes = lds + static_cast<size_t>(SNNHIP_WIDE_LDS_PAD_KB) * 1024;
     hipFuncSetAttribute(reinterpret_cast<const void*>(plan->kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(plan->ldsBytes));
@@ -294,7 +342,7 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     plan->fusedAdd = g.addAct >= 0;
     if (plan->fusedAdd) plan->numInputs = 2;
     plan->grid = dim3(static_cast<unsigned>(tiles), g.OC / BN, 1);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(cat ? reinterpret_cast<const void*>(catFn) : reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute(pool ? reinterpret_cast<const void*>(poolFn) : cat ? reinterpret_cast<const void*>(catFn) : reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
         set_error("conv2d_wide: hipFuncSetAttribute(%zu) failed", lds);
         delete plan;
         return SNNHIP_E_HIP;
@@ -347,6 +395,12 @@ int make_conv2d_wide_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
         plan->numInputs = 2;
         plan->inDims[3] = g.C0;
         plan->desc += " +concat(" + std::to_string(g.C0) + "+" + std::to_string(g.IC - g.C0) + ")";
+    }
+    if (pool) { // the input, the weights and the POOLED output: the full-resolution tensor never exists
+        plan->outDims[1] = g.poolOH;
+        plan->outDims[2] = g.poolOW;
+        plan->bytes = 2.0 * (static_cast<double>(g.N) * g.H * g.W * g.IC + static_cast<double>(g.N) * g.poolOH * g.poolOW * g.OC + static_cast<double>(g.OC) * g.IC * 9);
+        plan->desc += " +maxpool(2x2)";
     }
     if (g.preMode) plan->desc += " +pad(" + std::string(g.preMode == SNNHIP_PAD_REFLECT ? "reflect" : g.preMode == SNNHIP_PAD_REPLICATE ? "replicate" : "constant") + ")";
     if (g.preMode && g.preShift) plan->desc += " +upsample(x2)";

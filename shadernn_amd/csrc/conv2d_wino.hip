@@ -39,6 +39,8 @@ namespace snnhip {
 // conv2d_mfma.hip: the split-K reduce / epilogue pass
 int launch_splitk_reduce(snnhip_ctx* ctx, int OC, int splitK, int useBN, const ActCfg& ac, const float* ws, const float4* e4, snnhip_tensor* out,
                          const snnhip_tensor* res, const ActCfg& ac2);
+// ... and its pooling form (chain rule L): ws = [splitK][N][OH][OW][OC] raw sums -> out = maxpool2x2(act(BN(bias + sum_z ws[z]))), [N][out->h][out->w][OC]
+int launch_splitk_reduce_pool(snnhip_ctx* ctx, int OH, int OW, int splitK, int useBN, const ActCfg& ac, const float* ws, const float4* e4, snnhip_tensor* out);
 
 namespace {
 
@@ -79,11 +81,18 @@ struct WinoCatParams {
     int shift0;        // ... whose pixel of (sy, sx) is (sy >> shift0, sx >> shift0); input 1 is always at H x W
 };
 
+// POOL (chain rule L: Conv2D -> MaxPooling2D 2x2 stride 2, conv2d_wino_pool_kernel below): a lane's F(2x2,3x3) output tile starts at an even row and column, so it
+// IS one pooling window -- the epilogue takes the maximum of the lane's four finished values and stores one pixel of [N][poolOH][poolOW][OC] (conv2d_wino_body.h).
+struct WinoPoolParams {
+    int poolOH, poolOW; // the pooling plan's own output extent: ceil or floor of OH / 2, OW / 2
+};
+
 template <bool SIMPLE, int OPB, int KS = 1>
 __global__ __launch_bounds__(256 * OPB * KS, KS > 1 ? 1 : 3 - OPB) void conv2d_wino_kernel(WinoParams p, ActCfg ac, const float* __restrict__ x, const float4* __restrict__ ug,
                                                                         const float4* __restrict__ epi, float* __restrict__ y, float* __restrict__ ws) {
-    constexpr bool CAT = false;
+    constexpr bool CAT = false, POOL = false;
     const WinoCatParams cp = {};
+    const WinoPoolParams pq = {};
 #include "conv2d_wino_body.h"
 }
 
@@ -92,7 +101,18 @@ template <bool SIMPLE, int OPB, int KS = 1>
 __global__ __launch_bounds__(256 * OPB * KS, KS > 1 ? 1 : 3 - OPB) void conv2d_wino_cat_kernel(WinoParams p, WinoCatParams cp, ActCfg ac, const float* __restrict__ x,
                                                                             const float4* __restrict__ ug, const float4* __restrict__ epi, float* __restrict__ y,
                                                                             float* __restrict__ ws) {
-    constexpr bool CAT = true;
+    constexpr bool CAT = true, POOL = false;
+    const WinoPoolParams pq = {};
+#include "conv2d_wino_body.h"
+}
+
+// chain rule L: y is the POOLED tensor [N][pq.poolOH][pq.poolOW][OC] (splitK == 1) -- or nobody's: the raw partial tiles go to ws at full resolution
+template <bool SIMPLE, int OPB, int KS = 1>
+__global__ __launch_bounds__(256 * OPB * KS, KS > 1 ? 1 : 3 - OPB) void conv2d_wino_pool_kernel(WinoParams p, WinoPoolParams pq, ActCfg ac, const float* __restrict__ x,
+                                                                             const float4* __restrict__ ug, const float4* __restrict__ epi, float* __restrict__ y,
+                                                                             float* __restrict__ ws) {
+    constexpr bool CAT = false, POOL = true;
+    const WinoCatParams cp = {};
 #include "conv2d_wino_body.h"
 }
 
@@ -100,6 +120,11 @@ typedef void (*WinoCatFn)(WinoParams, WinoCatParams, ActCfg, const float*, const
 template <bool SIMPLE>
 WinoCatFn pick_wino_cat(int opb, int ks) {
     return ks == 2 ? conv2d_wino_cat_kernel<SIMPLE, 1, 2> : opb == 2 ? conv2d_wino_cat_kernel<SIMPLE, 2> : conv2d_wino_cat_kernel<SIMPLE, 1>;
+}
+
+typedef void (*WinoPoolFn)(WinoParams, WinoPoolParams, ActCfg, const float*, const float4*, const float4*, float*, float*);
+WinoPoolFn pick_wino_pool(int opb, int ks) { // (the rule takes the simple activations only)
+    return ks == 2 ? conv2d_wino_pool_kernel<true, 1, 2> : opb == 2 ? conv2d_wino_pool_kernel<true, 2> : conv2d_wino_pool_kernel<true, 1>;
 }
 
 struct WinoConvPlan : ConvPlanBase {
@@ -116,6 +141,22 @@ struct WinoConvPlan : ConvPlanBase {
     int ks = 1; // K groups per block (2: eight waves, the channel chunks split inside the block)
     WinoCatParams cp = {}; // chain rule K (g.C0 > 0): two inputs in the concat's order
     WinoCatFn catKernel = nullptr;
+    WinoPoolParams pq = {}; // chain rule L (g.poolOH > 0): the output is the pooled tensor
+    WinoPoolFn poolKernel = nullptr;
+
+    int run_pool(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) {
+        SNNHIP_REQUIRE(nIn == 1, "conv2d+maxpool: expects 1 input, got %d", nIn);
+        const snnhip_tensor* x = in[0];
+        SNNHIP_REQUIRE(x->n == p.N && x->h == p.H && x->w == p.W && x->c == p.IC && x->dtype == SNNHIP_F32, "conv2d+maxpool: input dims %dx%dx%dx%d (dtype %d) != plan %dx%dx%dx%d fp32",
+                       x->n, x->h, x->w, x->c, x->dtype, p.N, p.H, p.W, p.IC);
+        SNNHIP_REQUIRE(out->n == p.N && out->h == pq.poolOH && out->w == pq.poolOW && out->c == p.OC && out->dtype == SNNHIP_F32,
+                       "conv2d+maxpool: output dims %dx%dx%dx%d (dtype %d) != plan %dx%dx%dx%d fp32", out->n, out->h, out->w, out->c, out->dtype, p.N, pq.poolOH, pq.poolOW, p.OC);
+        const float4* e4 = reinterpret_cast<const float4*>(d_epi);
+        SNNHIP_LAUNCH(poolKernel, grid, dim3(256 * opb * ks), ldsBytes, ctx->stream, p, pq, ac, x->data, reinterpret_cast<const float4*>(d_u), e4, out->data, d_ws);
+        SNNHIP_CHECK_HIP(hipGetLastError());
+        if (p.splitK > 1) return launch_splitk_reduce_pool(ctx, p.OH, p.OW, p.splitK, p.useBN, ac, d_ws, e4, out);
+        return SNNHIP_OK;
+    }
 
     int run_cat(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) {
         SNNHIP_REQUIRE(nIn == 2, "conv2d+concat: expects 2 inputs, got %d", nIn);
@@ -137,6 +178,7 @@ struct WinoConvPlan : ConvPlanBase {
 
     int run(const snnhip_tensor* const* in, int nIn, snnhip_tensor* out) override {
         if (catKernel) return run_cat(in, nIn, out);
+        if (poolKernel) return run_pool(in, nIn, out);
         SNNHIP_REQUIRE(nIn == (fusedAdd ? 2 : 1), "conv2d: expects %d input(s), got %d", fusedAdd ? 2 : 1, nIn);
         const snnhip_tensor* x = in[0];
         WinoParams q = p; // per-launch copy: the residual pointer travels in the kernel argument block
@@ -189,6 +231,10 @@ int make_conv2d_wino_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
     if (g.padMode != SNNHIP_PAD_CONSTANT && g.padMode != SNNHIP_PAD_NONE) return SNNHIP_E_UNSUPPORTED;
     if (g.IC % 8 != 0 || g.OC % 16 != 0 || g.act == SNNHIP_ACT_SILU_QUIRK) return SNNHIP_E_UNSUPPORTED;
     if (cat && (g.C0 >= g.IC || g.C0 % 8 != 0 || g.addAct >= 0 || g.normShift)) return SNNHIP_E_UNSUPPORTED;
+    // chain rule L (g.poolOH > 0), under the gates of conv2d_mfma's pooling form: the simple epilogue, one plain source, no third input, and a pooled extent whose
+    // every window has its first position inside the convolution's output (the ceil or the floor of half of it)
+    const bool pool = g.poolOH > 0;
+    if (pool && (!act_is_simple(g.act) || g.addAct >= 0 || g.normShift || g.preMode || cat || g.poolOW <= 0 || 2 * g.poolOH > g.OH + 1 || 2 * g.poolOW > g.OW + 1)) return SNNHIP_E_UNSUPPORTED;
     const int srcH0 = catUp ? g.srcH : g.H, srcW0 = catUp ? g.srcW : g.W;
     // 32-bit element offsets in the staging path: each source on its own
     const double inCount = cat ? std::max(static_cast<double>(g.N) * srcH0 * srcW0 * g.C0, static_cast<double>(g.N) * g.H * g.W * (g.IC - g.C0)) : static_cast<double>(g.N) * g.H * g.W * g.IC;
@@ -300,7 +346,17 @@ int make_conv2d_wino_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
             return SNNHIP_E_HIP;
         }
     }
-    for (int s = 0; s < 2 && !cat; ++s) {
+    if (pool) {
+        plan->pq.poolOH = g.poolOH;
+        plan->pq.poolOW = g.poolOW;
+        plan->poolKernel = pick_wino_pool(opb, ks);
+        if (ldsAll > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(plan->poolKernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsAll)) != hipSuccess) {
+            set_error("conv2d_wino: hipFuncSetAttribute(%zu) failed", ldsAll);
+            delete plan;
+            return SNNHIP_E_HIP;
+        }
+    }
+    for (int s = 0; s < 2 && !cat && !pool; ++s) {
         const void* fn = ks == 2 ? (s ? reinterpret_cast<const void*>(conv2d_wino_kernel<true, 1, 2>) : reinterpret_cast<const void*>(conv2d_wino_kernel<false, 1, 2>))
                          : opb == 2 ? (s ? reinterpret_cast<const void*>(conv2d_wino_kernel<true, 2>) : reinterpret_cast<const void*>(conv2d_wino_kernel<false, 2>))
                                   : (s ? reinterpret_cast<const void*>(conv2d_wino_kernel<true, 1>) : reinterpret_cast<const void*>(conv2d_wino_kernel<false, 1>));
@@ -363,6 +419,12 @@ int make_conv2d_wino_plan(snnhip_ctx* ctx, const ConvGeom& g, const float* w_oih
                              static_cast<double>(g.OC) * g.IC * 9);
         plan->desc += " +concat(" + std::to_string(g.C0) + "+" + std::to_string(g.IC - g.C0) + ")";
         if (catUp) plan->desc += " +upsample(x2 on input 0)";
+    }
+    if (pool) { // the input, the weights and the POOLED output: the full-resolution tensor never exists (split over blockIdx.z: only as partial sums in the workspace)
+        plan->outDims[1] = g.poolOH;
+        plan->outDims[2] = g.poolOW;
+        plan->bytes = 4.0 * (static_cast<double>(g.N) * g.H * g.W * g.IC + static_cast<double>(g.N) * g.poolOH * g.poolOW * g.OC + static_cast<double>(g.OC) * g.IC * 9);
+        plan->desc += " +maxpool(2x2)";
     }
     if (plan->fusedAdd) {
         plan->desc += " +add";

@@ -1,6 +1,6 @@
-// conv2d_wino_body.h -- the body of conv2d_wino_kernel / conv2d_wino_cat_kernel (conv2d_wino.hip), included INSIDE each of the two kernel definitions.
-// The includer provides: the template parameters SIMPLE, OPB, KS; constexpr bool CAT; the kernel arguments p, ac, x, ug, epi, y, ws; and cp (WinoCatParams:
-// the kernel argument of the CAT form, an empty block nobody reads in the single-source form).  Text, not a function: the single-source kernels keep the
+// conv2d_wino_body.h -- the body of conv2d_wino_kernel / conv2d_wino_cat_kernel / conv2d_wino_pool_kernel (conv2d_wino.hip), included INSIDE each of the three
+// kernel definitions.  The includer provides: the template parameters SIMPLE, OPB, KS; constexpr bool CAT, POOL; the kernel arguments p, ac, x, ug, epi, y, ws; cp
+// (WinoCatParams: the kernel argument of the CAT form, an empty block nobody reads otherwise) and pq (WinoPoolParams, likewise for POOL).  Text, not a function: the single-source kernels keep the
 // instruction streams they had before the two-source form existed (an inlined __device__ body changed their schedule).
     static_assert(KS == 1 || (KS == 2 && OPB == 1), "in-block K split: two groups of four waves");
     constexpr int NT = 256 * OPB;            // threads of a group
@@ -246,7 +246,7 @@
                 ok4[r][cx] = !(n >= p.N || oy + r >= p.OH || ox + cx >= p.OW);
                 idx4[r][cx] = ((static_cast<size_t>(n) * p.OH + oy + r) * p.OW + ox + cx) * p.OC + oc;
                 rv4[r][cx] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (p.res && p.splitK == 1 && ok4[r][cx]) rv4[r][cx] = *reinterpret_cast<const float4*>(p.res + idx4[r][cx]);
+                if (!POOL && p.res && p.splitK == 1 && ok4[r][cx]) rv4[r][cx] = *reinterpret_cast<const float4*>(p.res + idx4[r][cx]);
             }
         f32x4 yv[2][2];
 #pragma unroll
@@ -261,6 +261,26 @@
             yv[0][1][c] = t0[1] - t0[2] - t0[3];
             yv[1][0][c] = t1[0] + t1[1] + t1[2];
             yv[1][1][c] = t1[1] - t1[2] - t1[3];
+        }
+        // POOL (chain rule L): the tile origin is even in both directions, so yv[2][2] is exactly one 2x2 stride-2 pooling window.  bias -> BN -> activation on
+        // each of its four values (BN's scale may be negative: the maximum stays behind it), then the pooling plan's own rule (eltwise_pool.hip): m = -100000,
+        // m = max(m, v) over the positions inside the convolution's OH x OW (a window on the bottom / right edge is clipped; with the floor extent it is not
+        // stored at all) -- ONE float4 per lane and channel block, no exchange, no LDS.  Split over blockIdx.z: raw partial tiles at full resolution below, as
+        // ever; splitk_reduce_pool_kernel (conv2d_mfma.hip) sums, finishes and pools them.
+        if (POOL && p.splitK == 1) {
+            const int qy = oy >> 1, qx = ox >> 1;
+            if (!ok4[0][0] || qy >= pq.poolOH || qx >= pq.poolOW) continue;
+            float m4[4] = {-100000.0f, -100000.0f, -100000.0f, -100000.0f};
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int cx = 0; cx < 2; ++cx) {
+                    if (!ok4[r][cx]) continue;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) m4[c] = fmaxf(m4[c], apply_act<SIMPLE>(ac, epi_affine(yv[r][cx][c], e4[c], p.useBN), 0.0f));
+                }
+            *reinterpret_cast<float4*>(y + ((static_cast<size_t>(n) * pq.poolOH + qy) * pq.poolOW + qx) * p.OC + oc) = make_float4(m4[0], m4[1], m4[2], m4[3]);
+            continue;
         }
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -281,7 +301,7 @@
                     float vv = epi_affine(yv[r][cx][c], e4[c], p.useBN);
                     o4[c] = apply_act<SIMPLE>(ac, vv, 0.0f);
                 }
-                if (p.res) {
+                if (!POOL && p.res) {
                     const float4 rv = rv4[r][cx];
                     o4[0] = add_act(p.ac2, addSimple, o4[0] + rv.x);
                     o4[1] = add_act(p.ac2, addSimple, o4[1] + rv.y);
