@@ -1365,6 +1365,12 @@ IrbFn pick_irb_wave(int ncb, int cj) {
 int make_irb_plan(snnhip_ctx* ctx, snnhip_plan* expandPlan, snnhip_plan* dwPlan, snnhip_plan* projectPlan, snnhip_plan* addPlan, snnhip_plan** out,
                   snnhip_plan* stemPlan) {
     if (snnhip::option("SNNHIP_NO_IRB_FUSION")) return SNNHIP_E_UNSUPPORTED;
+    // half tensors: irb_f16.hip's kernel, opt-in (SNNHIP_IRB_F16=1) until its per-block table says where it wins; the full block only (expand, depthwise, project)
+    if (auto* cdh = dynamic_cast<ConvPlanBase*>(dwPlan); cdh && cdh->g.dtype == SNNHIP_F16) {
+        const char* on = snnhip::option("SNNHIP_IRB_F16");
+        if (!on || atoi(on) == 0 || !expandPlan || stemPlan) return SNNHIP_E_UNSUPPORTED;
+        return make_irb_f16_plan(ctx, expandPlan, dwPlan, projectPlan, addPlan, out);
+    }
     auto* cs = stemPlan ? dynamic_cast<ConvPlanBase*>(stemPlan) : nullptr;
     if (stemPlan) {
         // Opt-in (SNNHIP_STEM_IRB_FUSION=1): MobileNetV2's head at batch 256 takes 403 us fused, 157 + 237 us as stem + two-layer kernel -- the 0.82 GB

@@ -265,6 +265,8 @@ bool chain_adopt_plan(snnhip_plan* chain, snnhip_plan* p); // the chain deletes 
 // irb_fused.hip (chain rule G): Conv2D 1x1 -> DepthwiseConv2D 3x3 -> Conv2D 1x1 [-> Add with the block input] as one kernel; the plans are only read
 int make_irb_plan(snnhip_ctx* ctx, snnhip_plan* expandPlan, snnhip_plan* dwPlan, snnhip_plan* projectPlan, snnhip_plan* addPlan, snnhip_plan** out,
                   snnhip_plan* stemPlan = nullptr);
+// irb_f16.hip (chain rule G on half tensors, behind make_irb_plan and SNNHIP_IRB_F16=1): the same block as one f16-MFMA launch; the plans are only read
+int make_irb_f16_plan(snnhip_ctx* ctx, snnhip_plan* expandPlan, snnhip_plan* dwPlan, snnhip_plan* projectPlan, snnhip_plan* addPlan, snnhip_plan** out);
 // dwpw_march.hip (chain rule G without an expand layer, large maps): DepthwiseConv2D 3x3 stride 1 -> Conv2D 1x1 as one row-marching streaming kernel; the plans are only read
 int make_dwpw_march_plan(snnhip_ctx* ctx, snnhip_plan* dwPlan, snnhip_plan* pwPlan, snnhip_plan** out);
 // ... with the network's stem in front: Conv2D 3x3 stride 2 (3 -> 32 channels) -> DepthwiseConv2D 3x3 -> Conv2D 1x1 as one launch, the stem's output only ever in LDS
